@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - db-structure scorings/sec of the SA tableau search on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json configs[3] / north_star target shape): one 32-SSE synthetic query against a
@@ -21,6 +21,11 @@ bench.py ...` as a child, relays its stdout (the one JSON line) and exits with i
 torch.distributed.run (WORLD_SIZE set) it is one of the ranks.  `--single-process` instead times the
 product's own multi-GPU entry points (sat_multi_*: one host thread, one context per GPU, ncclCommInitAll +
 ncclGather into device 0) in this process.
+
+`--dump-outputs DIR` (rank 0) writes what the timed path returned in its last step, so that two builds can be
+compared output for output on the same seeded inputs: DIR/scores.npy (float64, the int32 score of each dumped
+entry) and DIR/entries.npy (float64, their database ordinals) - every entry, or a fixed seeded sample when
+the whole database would exceed 64 MB.
 
 Prints ONE JSON line (rank 0).  `value` = (entries of the whole database x K) / max-over-ranks time.
 Extra objects: `roofline` (HBM-nominal, see DESIGN.md section 4: the path is VALU/LDS bound, the HBM
@@ -46,6 +51,7 @@ ORDER = 32
 MAXSTART = 128
 MAXITER = 100
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: 8 TB/s spec
+DUMP_MAX_BYTES = 64 << 20
 
 
 def algorithmic_bytes_per_scoring(n2):
@@ -150,6 +156,24 @@ def oracle_sample_ok(scores, total, q, k=16):
     return True, [int(i) for i in idx]
 
 
+def dump_outputs(dirname, scores):
+    """--dump-outputs: the whole database's scores of the last timed step (int32, exact in float64) with the
+    ordinal of each entry; above DUMP_MAX_BYTES a sorted sample drawn with a fixed seed, the same for every build."""
+    import numpy as np
+    scores = np.asarray(scores).reshape(-1)
+    n = scores.shape[0]
+    per_entry = 2 * 8                                      # scores.npy + entries.npy, float64 each
+    keep = (DUMP_MAX_BYTES - 4096) // per_entry            # 4 KB left for the two .npy headers
+    if n > keep:
+        idx = np.sort(np.random.default_rng(20251015).choice(n, size=keep, replace=False))
+    else:
+        idx = np.arange(n)
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "scores.npy"), scores[idx].astype(np.float64))
+    np.save(os.path.join(dirname, "entries.npy"), idx.astype(np.float64))
+    return {"dir": dirname, "files": ["scores.npy", "entries.npy"], "entries": int(idx.shape[0]), "sampled": bool(keep < n)}
+
+
 # ------------------------------------------------------------------------------------------------
 def committed_counters(n_local, kernel_info):
     """HBM traffic and VALU instructions per launch from the rocprofv3 PMC passes of this same command
@@ -229,7 +253,11 @@ def parse_args(argv):
     ap.add_argument("--all-ranks-on-device0", action="store_true", help="rehearsal only: every rank uses GPU 0")
     ap.add_argument("--single-process", action="store_true", help="time the product's sat_multi_* entry points (one host "
                     "thread, ncclCommInitAll + ncclGather) instead of one process per GPU")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the scores of the last timed step as DIR/*.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------
@@ -291,6 +319,8 @@ def run_single_process(args):
         out["oracle_sample_ok"] = bool(ok)
         out["oracle_sample"] = sample
         out["note"] = "value includes the device-0 -> host copy of the rows and their re-ordering (sat_multi_search returns host rows)"
+        if args.dump_outputs:
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, scores[0])
     print(json.dumps(out), flush=True)
     if not ok:
         raise SystemExit("timed search differs from the oracle on the sampled entries")
@@ -506,6 +536,8 @@ def main():
             if ref:
                 out["cpu_baseline_reference"] = ref
             out["cpu_baseline_all_cores"] = cpu_baseline_all_cores(db, q)
+        if args.dump_outputs:
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, whole)
         print(json.dumps(out), flush=True)
         if not ok:
             print("bench.py: the timed search differs from the oracle on the sampled entries", file=sys.stderr)

@@ -1,10 +1,10 @@
 """End-to-end wall time of the command line on the paper's workload shape: 200 SIDs (-q) against a 15 000-entry
 database (python scripts/cli_query_list_e2e.py; optionally a second binary name to compare with)."""
 import os, sys, time, subprocess, tempfile, hashlib
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import cuda_satabsearch_amd as sat
-root = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 d = tempfile.mkdtemp()
 db = sat.synth.make_db(15000, 4, 40, sort=True, name_format="s%06d")
 db.write_ascii(d + "/db.ascii")

@@ -3,7 +3,7 @@
 # (default: the in-tree one).  Output: gpurun_out/ab_TAG/
 set -uo pipefail
 tag=${1:-x}
-repo=${GRAFT_REPO_ROOT:-/root/repo}
+repo=$(cd "$(dirname "$0")/.." && pwd)
 [ -n "${2:-}" ] && export SAT_DEVICE_LIB=$repo/$2
 out=$repo/gpurun_out/ab_$tag
 mkdir -p "$out"

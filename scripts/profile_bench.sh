@@ -4,7 +4,7 @@
 # --pmc combined with the trace domains).  Output: gpurun_out/prof_TAG/
 set -uo pipefail
 tag=${1:-r1}
-repo=${GRAFT_REPO_ROOT:-/root/repo}
+repo=$(cd "$(dirname "$0")/.." && pwd)
 out=$repo/gpurun_out/prof_$tag
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp

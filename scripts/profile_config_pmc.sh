@@ -3,7 +3,7 @@
 # domains) of one workload of scripts/run_config.py.  Output: gpurun_out/pmc_TAG_WORKLOAD/summary.txt
 set -uo pipefail
 tag=${1:-r02}; w=${2:-c4}
-repo=${GRAFT_REPO_ROOT:-/root/repo}
+repo=$(cd "$(dirname "$0")/.." && pwd)
 out=$repo/gpurun_out/pmc_${tag}_$w
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp

@@ -5,7 +5,7 @@
 set -uo pipefail
 tag=${1:-r02}; shift || true
 wl=${@:-c2 c4 c3_1m mixed lorderf n96}
-repo=${GRAFT_REPO_ROOT:-/root/repo}
+repo=$(cd "$(dirname "$0")/.." && pwd)
 out=$repo/gpurun_out/prof_$tag
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp

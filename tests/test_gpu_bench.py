@@ -46,6 +46,30 @@ def test_two_ranks_started_by_bench_itself(scaling):
     assert abs(r["value"] - total * 5 / (r["ms_per_step"] * 5e-3)) < 1e-6 * r["value"]
 
 
+def test_dump_outputs_are_the_timed_scores(tmp_path):
+    """--dump-outputs: the per-process path and the sat_multi_* path, at other step counts, dump the same scores
+    of the same 20 000-entry database, and sampled entries equal the oracle on the kernel's Philox streams."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import cuda_satabsearch_amd as sat
+    import oracle_lib
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    r = _bench("--steps", "3", "--warmup", "1", "--entries", "20000", "--no-cpu-baseline", "--no-regimes",
+               "--no-upload-probe", "--dump-outputs", a)
+    assert r["steps"] == 3 and r["dump_outputs"]["entries"] == 20000 and r["oracle_sample_ok"] is True
+    _bench("--single-process", "--gpus", "2", "--all-ranks-on-device0", "--steps", "1", "--warmup", "0",
+           "--entries", "10000", "--dump-outputs", b)
+    scores, entries = np.load(os.path.join(a, "scores.npy")), np.load(os.path.join(a, "entries.npy"))
+    assert scores.dtype == np.float64 and np.array_equal(entries, np.arange(20000))
+    assert np.array_equal(scores, np.load(os.path.join(b, "scores.npy")))
+    assert np.array_equal(entries, np.load(os.path.join(b, "entries.npy")))
+    q = sat.synth.make_query(32)
+    for g in (0, 7777, 19999):
+        one = sat.synth.make_db(1, 32, 32, first_index=g, total=20000)
+        want, _, _ = oracle_lib.search(one, *q, True, False, 128, db_ordinal=np.array([g]))
+        assert scores[g] == want[0]
+
+
 def test_single_process_multi_gpu_entry_points():
     """--single-process: the product's sat_multi_* calls (two contexts on GPU 0 here: the peer-copy gather)."""
     r = _bench("--single-process", "--gpus", "2", "--all-ranks-on-device0", "--steps", "3", "--warmup", "1",
