@@ -24,6 +24,7 @@ ABI_SYMBOLS = (
     "sat_topk_hits", "sat_stat_d2h_bytes", "sat_debug_lds_layout", "sat_last_launch_info",
     "sat_multi_create", "sat_multi_destroy", "sat_multi_device_count", "sat_multi_gather_kind", "sat_multi_db_upload_packed",
     "sat_multi_shards", "sat_multi_queries_set", "sat_multi_search", "sat_multi_search_topk", "sat_multi_stat_d2h_bytes",
+    "sat_search_matches", "sat_multi_search_matches",
 )
 
 
@@ -106,6 +107,10 @@ def device_lib():
         lib.sat_multi_search.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
         lib.sat_multi_search_topk.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                               C.POINTER(C.c_double)]
+        lib.sat_search_matches.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.POINTER(C.c_double)]
+        lib.sat_multi_search_matches.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
         lib.sat_multi_stat_d2h_bytes.argtypes = [C.c_void_p]
         lib.sat_multi_stat_d2h_bytes.restype = C.c_uint64
         lib.sat_device_scores.argtypes = [C.c_void_p]

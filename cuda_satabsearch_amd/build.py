@@ -42,7 +42,7 @@ def kernel_source_hash():
     bench.py only reports committed counter figures that were measured on the kernel it is running."""
     import hashlib
     h = hashlib.sha256()
-    for f in ("sat_sa_kernel.hpp", "sat_capi.hip", "sat_ctx.hpp"):
+    for f in ("sat_sa_kernel.hpp", "sat_sa_body.inc", "sat_capi.hip", "sat_ctx.hpp"):
         with open(os.path.join(CSRC, f), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()
@@ -72,7 +72,8 @@ def build_device(force=False):
     out = os.path.join(PKG, "libsatabsearch.so")
     srcs = [os.path.join(CSRC, "sat_capi.hip"), os.path.join(CSRC, "sat_topk.hip"), os.path.join(CSRC, "sat_multi.hip")]
     host_o = _host_objects(force)
-    deps = srcs + host_o + [os.path.join(CSRC, "sat_sa_kernel.hpp"), os.path.join(CSRC, "sat_ctx.hpp"),
+    deps = srcs + host_o + [os.path.join(CSRC, "sat_sa_kernel.hpp"), os.path.join(CSRC, "sat_sa_body.inc"),
+                            os.path.join(CSRC, "sat_ctx.hpp"),
                             os.path.join(INC, "satabsearch.h")]
     if force or _stale(out, deps):
         # -Wl,: hipcc would compile a bare .o as HIP source.  librccl is NOT linked: sat_multi.hip loads it on demand
@@ -106,14 +107,14 @@ def build_test_native(force=False):
     if not os.path.exists(src):
         return None
     out = os.path.join(tdir, "librocrand_check.so")
-    if force or _stale(out, [src, os.path.join(CSRC, "sat_sa_kernel.hpp")]):
+    if force or _stale(out, [src, os.path.join(CSRC, "sat_sa_kernel.hpp"), os.path.join(CSRC, "sat_sa_body.inc")]):
         _run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-I", INC, "-I", CSRC, "-o", out, src])
     # the device library once more with the reference's TESTING assertion compiled in (diag/sat_diag.hpp,
     # -DSAT_DIAG_SELFCHECK: every proposed move's score against a full recomputation) - loaded only by
     # tests/test_gpu_parity.py::test_every_move_passes_the_references_self_check, through SAT_DEVICE_LIB
     out3 = os.path.join(tdir, "libsat_selfcheck.so")
     dsrcs = [os.path.join(CSRC, f) for f in ("sat_capi.hip", "sat_topk.hip", "sat_multi.hip")]
-    ddeps = dsrcs + [os.path.join(CSRC, "sat_sa_kernel.hpp"), os.path.join(CSRC, "sat_ctx.hpp"),
+    ddeps = dsrcs + [os.path.join(CSRC, "sat_sa_kernel.hpp"), os.path.join(CSRC, "sat_sa_body.inc"), os.path.join(CSRC, "sat_ctx.hpp"),
                      os.path.join(CSRC, "diag", "sat_diag.hpp"), os.path.join(INC, "satabsearch.h")]
     if force or _stale(out3, ddeps):
         _run([HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared", "-DSAT_DIAG",

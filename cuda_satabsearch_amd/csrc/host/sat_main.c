@@ -48,9 +48,14 @@ static double now_ms(void)
     return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
 }
 
+/* The sanitizer build of the host code links this file against stubs of the device library
+ * (tests/native/gpu_stubs.c) that have no several-matches entry point: a weak reference keeps that link
+ * working, and -m reports the missing entry point instead of calling it. */
+#pragma weak sat_multi_search_matches
+
 static void usage(const char *prog)
 {
-    fprintf(stderr, "Usage: %s [-c] [-q dbfile] [-r restarts] [-g gpus] [-G gpu,gpu,...] [-s seed] [-k K] [-b]\n", prog);
+    fprintf(stderr, "Usage: %s [-c] [-q dbfile] [-r restarts] [-g gpus] [-G gpu,gpu,...] [-s seed] [-k K] [-m M] [-b]\n", prog);
     fprintf(stderr, "  -c : run on host CPU not GPU card\n");
     fprintf(stderr, "  -q dbfile : database is read from dbfile, list of query\n"
                     "              ids is read from stdin\n");
@@ -59,6 +64,8 @@ static void usage(const char *prog)
     fprintf(stderr, "  -G list : the GPUs to use, e.g. 0,2,3 (a GPU named twice holds two shards)\n");
     fprintf(stderr, "  -s seed : seed of the GPU random streams. Default %d\n", SAT_DEFAULT_SEED);
     fprintf(stderr, "  -k K : print only the K best rows per query (GPU mode)\n");
+    fprintf(stderr, "  -m M : up to M (1..%d) non-overlapping matches per structure: after an entry's row,\n"
+                    "         matches 2..M as rows named name:k (GPU mode)\n", SAT_MAX_MATCHES);
     fprintf(stderr, "  -b : cache the parsed database as dbfile.satbin\n");
     exit(1);
 }
@@ -183,6 +190,21 @@ static inline void out_map_line(int a, int b)
 }
 
 static void print_row(const char *name, int score, int n1, int n2, const int32_t *map, int lsoln,
+                      int wide_gap);
+
+/* -m: matches 2 .. count of one entry (scores / maps of its M slots) as rows "name:k", each followed by its map
+ * lines with LSOLN */
+static void print_more_matches(const char *name, int n1, int n2, int count, const int32_t *mscores,
+                               const int32_t *mmaps, int lsoln, int wide_gap)
+{
+    char mname[SAT_MAX_LINE_LEN + 16];
+    for (int m = 1; m < count; m++) {
+        snprintf(mname, sizeof mname, "%s:%d", name, m + 1);
+        print_row(mname, mscores[m], n1, n2, lsoln ? mmaps + (size_t)m * SAT_MAXDIM : NULL, lsoln, wide_gap);
+    }
+}
+
+static void print_row(const char *name, int score, int n1, int n2, const int32_t *map, int lsoln,
                       int wide_gap)
 {
     double norm2score = sat_norm2(score, n1, n2);
@@ -204,14 +226,14 @@ int main(int argc, char *argv[])
 {
     char dbfile[SAT_MAX_LINE_LEN] = "";
     char buf[SAT_MAX_LINE_LEN];
-    int use_gpu = 1, querydbmode = 0, maxstart = 128, want_gpus = 1, bincache = 0, topk = 0;
+    int use_gpu = 1, querydbmode = 0, maxstart = 128, want_gpus = 1, bincache = 0, topk = 0, nmatch = 0;
     unsigned long long seed = SAT_DEFAULT_SEED;
     int ltype = 0, lorder = 0, lsoln = 0;
     char cltype = 'F', clorder = 'F', clsoln = 'F';
     int c;
 
     int dev_list[64], ndev_list = 0;
-    while ((c = getopt(argc, argv, "cq:r:g:G:s:bk:")) != -1) {
+    while ((c = getopt(argc, argv, "cq:r:g:G:s:bk:m:")) != -1) {
         switch (c) {
         case 'c': use_gpu = 0; break;
         case 'q': querydbmode = 1; strncpy(dbfile, optarg, sizeof(dbfile) - 1); break;
@@ -224,8 +246,24 @@ int main(int argc, char *argv[])
         case 's': seed = strtoull(optarg, NULL, 0); break;
         case 'b': bincache = 1; break;
         case 'k': topk = atoi(optarg); break;
+        case 'm': {
+            /* 1 .. SAT_MAX_MATCHES, digits only: anything else (0, a sign, text) is a usage error */
+            char *end = NULL;
+            const long v = strtol(optarg, &end, 10);
+            if (end == optarg || *end != '\0' || v < 1 || v > SAT_MAX_MATCHES) usage(argv[0]);
+            nmatch = (int)v;
+            break;
+        }
         default: usage(argv[0]);
         }
+    }
+    if (nmatch && !use_gpu) {
+        fprintf(stderr, "ERROR: -m needs the GPU path\n");
+        exit(1);
+    }
+    if (nmatch && !sat_multi_search_matches) {
+        fprintf(stderr, "ERROR: this library has no sat_multi_search_matches\n");
+        exit(1);
     }
     fprintf(stderr, "MAXDIM = %d\n", SAT_MAXDIM);
     atexit(out_flush);                                   /* every exit path, exit(1) included */
@@ -429,18 +467,25 @@ int main(int argc, char *argv[])
 
     /* rows of the large class are printed after every query's small-class block */
     int32_t *large_scores = NULL, *large_maps = NULL;
+    /* -m: M slots per row (nm = 1 without -m); the large class keeps every slot for its late rows */
+    const int nm = nmatch > 0 ? nmatch : 1;
+    int32_t *large_counts = NULL;
     if (cls_count[1] > 0 && topk <= 0) {
-        large_scores = (int32_t *)malloc(sizeof(int32_t) * (size_t)cls_count[1] * num_queries);
-        if (lsoln) large_maps = (int32_t *)malloc(sizeof(int32_t) * SAT_MAXDIM * (size_t)cls_count[1] * num_queries);
-        if (!large_scores || (lsoln && !large_maps)) { fprintf(stderr, "malloc failed\n"); exit(1); }
+        large_scores = (int32_t *)malloc(sizeof(int32_t) * (size_t)cls_count[1] * num_queries * nm);
+        if (lsoln) large_maps = (int32_t *)malloc(sizeof(int32_t) * SAT_MAXDIM * (size_t)cls_count[1] * num_queries * nm);
+        if (nmatch) large_counts = (int32_t *)malloc(sizeof(int32_t) * (size_t)cls_count[1] * num_queries);
+        if (!large_scores || (lsoln && !large_maps) || (nmatch && !large_counts)) { fprintf(stderr, "malloc failed\n"); exit(1); }
     }
 
     /* Queries go to the GPUs in batches: one set of launches scores a whole batch (grid =
      * entries x queries), which is what fills the machine when the database is small and the
-     * query list long (-q).  The batch size is bounded by the host result buffers. */
+     * query list long (-q).  The batch size is bounded by the host result buffers: every entry's row (and map)
+     * without -k, and with -m every entry's M slots also under -k (the device holds the same slots, maps as bytes). */
     int batch = 256;
-    if (topk <= 0) {
-        const size_t per_query = (size_t)total * (lsoln ? (SAT_MAXDIM + 1) : 1) * sizeof(int32_t);
+    if (topk <= 0 || nmatch) {
+        size_t per_query = 0;
+        if (!nmatch) per_query = (size_t)total * (lsoln ? (SAT_MAXDIM + 1) : 1) * sizeof(int32_t);
+        else per_query = (size_t)total * (1 + 2 * (size_t)nm + (lsoln ? (size_t)nm * SAT_MAXDIM : 0)) * sizeof(int32_t);
         const size_t budget = (size_t)1 << 30;
         if ((size_t)batch * per_query > budget) batch = (int)(budget / per_query);
     }
@@ -458,10 +503,19 @@ int main(int argc, char *argv[])
         hits = (sat_hit *)malloc(sizeof(sat_hit) * (size_t)kk * batch);
         hit_maps = lsoln ? (int32_t *)malloc(sizeof(int32_t) * SAT_MAXDIM * (size_t)kk * batch) : NULL;
         if (!hits || (lsoln && !hit_maps)) { fprintf(stderr, "malloc failed\n"); exit(1); }
-    } else {
+    } else if (!nmatch) {                              /* (-m: the rows come from the match slots) */
         scores = (int32_t *)malloc(sizeof(int32_t) * (size_t)total * batch);
         ssemaps = lsoln ? (int32_t *)malloc(sizeof(int32_t) * SAT_MAXDIM * (size_t)total * batch) : NULL;
         if (!scores || (lsoln && !ssemaps)) { fprintf(stderr, "malloc failed\n"); exit(1); }
+    }
+    /* -m: every entry's M slots (counts, scores, restarts, maps) of the batch */
+    int32_t *mcounts = NULL, *mscores = NULL, *mrestarts = NULL, *mmaps = NULL;
+    if (nmatch) {
+        mcounts = (int32_t *)malloc(sizeof(int32_t) * (size_t)total * batch);
+        mscores = (int32_t *)malloc(sizeof(int32_t) * (size_t)total * batch * nm);
+        mrestarts = (int32_t *)malloc(sizeof(int32_t) * (size_t)total * batch * nm);
+        mmaps = lsoln ? (int32_t *)malloc(sizeof(int32_t) * SAT_MAXDIM * (size_t)total * batch * nm) : NULL;
+        if (!mcounts || !mscores || !mrestarts || (lsoln && !mmaps)) { fprintf(stderr, "malloc failed\n"); exit(1); }
     }
     uint8_t *qtabs = (uint8_t *)calloc((size_t)batch * SAT_MAXDIM * SAT_MAXDIM, 1);
     float *qdmats = (float *)calloc((size_t)batch * SAT_MAXDIM * SAT_MAXDIM, sizeof(float));
@@ -487,9 +541,19 @@ int main(int argc, char *argv[])
                 nqb, nqb == 1 ? "y" : "ies", sat_set_name(qsrc, qindex[q0]));
         double ms = 0.0;
         int rc = sat_multi_queries_set(multi, nqb, n1s, qtabs, qdmats, SAT_MAXDIM, qtypes, (uint32_t)q0);
-        if (rc == SAT_OK)
+        if (rc == SAT_OK && !nmatch)
             rc = topk > 0 ? sat_multi_search_topk(multi, lorder, lsoln, maxstart, kk, hits, hit_maps, &ms)
                           : sat_multi_search(multi, lorder, lsoln, maxstart, scores, ssemaps, &ms);
+        if (rc == SAT_OK && nmatch) {
+            /* match 0 of every entry is the plain search's score and map: the entry rows come from the match
+             * slots; -k ranks the entries as without -m (its own search), the extra rows from the slots */
+            double ms2 = 0.0;
+            rc = sat_multi_search_matches(multi, lorder, maxstart, nm, mcounts, mscores, mrestarts, mmaps, &ms);
+            if (rc == SAT_OK && topk > 0) {
+                rc = sat_multi_search_topk(multi, lorder, lsoln, maxstart, kk, hits, hit_maps, &ms2);
+                ms += ms2;
+            }
+        }
         if (rc < 0) {
             fprintf(stderr, "kernel launch failed: %s\n", sat_last_error());
             exit_status = 1;
@@ -511,26 +575,39 @@ int main(int argc, char *argv[])
                             if (map[k2] >= 0)
                                 out_map_line(k2 + 1, map[k2] + 1);
                     }
+                    if (nmatch) {
+                        const size_t row = (size_t)b * total + (size_t)h->entry;
+                        print_more_matches(sat_set_name(&db, h->entry), n1, db.order[h->entry], mcounts[row],
+                                           mscores + row * nm, mmaps ? mmaps + row * nm * SAT_MAXDIM : NULL, lsoln, 0);
+                    }
                 }
             }
             continue;
         }
         for (int b = 0; b < nqb; b++) {
             const int qi = q0 + b, qs = qindex[qi], n1 = n1s[b];
-            const int32_t *qscores = scores + (size_t)b * total;
-            const int32_t *qmaps = ssemaps ? ssemaps + (size_t)b * total * SAT_MAXDIM : NULL;
+            /* -m: entry s's slot m at (b * total + s) * nm + m; slot 0 is the plain row */
+            const size_t stride = (size_t)nm;
+            const int32_t *qscores = nmatch ? mscores + (size_t)b * total * nm : scores + (size_t)b * total;
+            const int32_t *qmaps = nmatch ? (mmaps ? mmaps + (size_t)b * total * nm * SAT_MAXDIM : NULL)
+                                          : (ssemaps ? ssemaps + (size_t)b * total * SAT_MAXDIM : NULL);
             print_header(ltype, lorder, lsoln, sat_set_name(qsrc, qs), dbfile);
             for (int d = 0; d < cls_count[0]; d++) {
                 int s = cls_index[0][d];
-                print_row(sat_set_name(&db, s), qscores[s], n1, db.order[s],
-                          qmaps ? qmaps + (size_t)s * SAT_MAXDIM : NULL, lsoln, 0);
+                print_row(sat_set_name(&db, s), qscores[s * stride], n1, db.order[s],
+                          qmaps ? qmaps + (size_t)s * stride * SAT_MAXDIM : NULL, lsoln, 0);
+                if (nmatch)
+                    print_more_matches(sat_set_name(&db, s), n1, db.order[s], mcounts[(size_t)b * total + s],
+                                       qscores + s * stride, qmaps ? qmaps + (size_t)s * stride * SAT_MAXDIM : NULL, lsoln, 0);
             }
             for (int d = 0; d < cls_count[1]; d++) {
                 int s = cls_index[1][d];
-                large_scores[(size_t)qi * cls_count[1] + d] = qscores[s];
+                const size_t row = (size_t)qi * cls_count[1] + d;
+                memcpy(large_scores + row * stride, qscores + s * stride, sizeof(int32_t) * stride);
+                if (nmatch) large_counts[row] = mcounts[(size_t)b * total + s];
                 if (lsoln)
-                    memcpy(large_maps + ((size_t)qi * cls_count[1] + d) * SAT_MAXDIM,
-                           qmaps + (size_t)s * SAT_MAXDIM, sizeof(int32_t) * SAT_MAXDIM);
+                    memcpy(large_maps + row * stride * SAT_MAXDIM,
+                           qmaps + (size_t)s * stride * SAT_MAXDIM, sizeof(int32_t) * SAT_MAXDIM * stride);
             }
         }
     }
@@ -540,8 +617,12 @@ int main(int argc, char *argv[])
             print_header(ltype, lorder, lsoln, sat_set_name(qsrc, qs), dbfile);
             for (int d = 0; d < cls_count[1]; d++) {
                 int s = cls_index[1][d];
-                print_row(sat_set_name(&db, s), large_scores[(size_t)qi * cls_count[1] + d], n1, db.order[s],
-                          lsoln ? large_maps + ((size_t)qi * cls_count[1] + d) * SAT_MAXDIM : NULL, lsoln, 1);
+                const size_t row = (size_t)qi * cls_count[1] + d;
+                print_row(sat_set_name(&db, s), large_scores[row * nm], n1, db.order[s],
+                          lsoln ? large_maps + row * nm * SAT_MAXDIM : NULL, lsoln, 1);
+                if (nmatch)
+                    print_more_matches(sat_set_name(&db, s), n1, db.order[s], large_counts[row], large_scores + row * nm,
+                                       lsoln ? large_maps + row * nm * SAT_MAXDIM : NULL, lsoln, 1);
             }
         }
 bye:
@@ -554,6 +635,11 @@ bye:
     free(hit_maps);
     free(large_scores);
     free(large_maps);
+    free(large_counts);
+    free(mcounts);
+    free(mscores);
+    free(mrestarts);
+    free(mmaps);
     free(qtabs);
     free(qdmats);
     free(qtypes);

@@ -216,6 +216,29 @@ template <int N1P> kernel_fn pick_n1p(int m2w, int cells, bool qlds, int opt, in
     return qlds ? pick_m2w<N1P, true, -1, 0>(m2w, cells) : pick_m2w<N1P, false, -1, 0>(m2w, cells);
 }
 
+// the match mode's kernel (sat_sa_match_kernel: options from the arguments) for a launch's size class and layout
+typedef void (*match_kernel_fn)(const SatKernelArgs, const SatMatchArgs);
+template <int N1P, bool QLDS> match_kernel_fn pick_match_m2w(int m2w, int cells)
+{
+    if (m2w == 1) return sat_sa_match_kernel<N1P, 1, QLDS, SAT_CELLS_FULL8>;
+    if (m2w == 2) return cells == SAT_CELLS_FULL5 ? sat_sa_match_kernel<N1P, 2, QLDS, SAT_CELLS_FULL5>
+                                                   : sat_sa_match_kernel<N1P, 2, QLDS, SAT_CELLS_TRI5>;
+    return sat_sa_match_kernel<N1P, 4, QLDS, SAT_CELLS_TRI5>;
+}
+template <int N1P> match_kernel_fn pick_match_n1p(int m2w, int cells, bool qlds)
+{
+    return qlds ? pick_match_m2w<N1P, true>(m2w, cells) : pick_match_m2w<N1P, false>(m2w, cells);
+}
+match_kernel_fn pick_match_kernel(int n1p, int m2w, int cells, bool qlds)
+{
+    switch (n1p) {
+    case 16: return pick_match_n1p<16>(m2w, cells, qlds);
+    case 32: return pick_match_n1p<32>(m2w, cells, qlds);
+    case 64: return pick_match_n1p<64>(m2w, cells, qlds);
+    default: return pick_match_n1p<112>(m2w, cells, qlds);
+    }
+}
+
 kernel_fn pick_kernel(int n1p, int m2w, int cells, bool qlds, int opt, int wpl)
 {
     switch (n1p) {
@@ -307,13 +330,13 @@ int refresh_descriptors(sat_ctx *ctx, bool lsoln, hipStream_t stream)
 // ones lose to their own start-up and drain phases what the extra residency gains (10.4 M).
 int resident_by_lds(size_t bytes) { return (int)(128 / ((bytes + 1279) / 1280)); }
 
-int pick_epw(kernel_fn fn, int threads, size_t lds_stride)
+int pick_epw(const void *fn, int threads, size_t lds_stride)
 {
     int best = 1, best_entries = 0;
     for (int k = 1; k * threads <= 512 && (size_t)k * lds_stride <= kLdsLimit; k++) {
         if (k > 1 && (k * threads / 64) % 4 != 0) continue;
         int by_regs = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&by_regs, reinterpret_cast<const void *>(fn), k * threads, 0) != hipSuccess) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&by_regs, fn, k * threads, 0) != hipSuccess) {
             (void)hipGetLastError();
             return 1;
         }
@@ -334,7 +357,11 @@ struct ListView {
     int n;                       // entries covered = begin[kNumBuckets] - begin[0]
 };
 
-int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t stream, const ListView *piece = nullptr)
+// mx: one pass of the match mode (sat_search_matches) instead of a plain search; lsoln is 0 then.  Its record pass
+// keeps one record slab per entry slot (scores and db sets of every restart) in the best-map scratch, its replay
+// pass a best-map slab per slot there and runs max_matches restarts per entry (workgroups sized for that).
+int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t stream, const ListView *piece = nullptr,
+                  const SatMatchArgs *mx = nullptr)
 {
     if (!ctx) return fail(SAT_EINVAL, "null context");
     if (ctx->n_entries <= 0) return fail(SAT_ESTATE, "no database uploaded");
@@ -364,7 +391,7 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
 #endif
 
     struct Planned {
-        kernel_fn fn; SatKernelArgs args; int count, nqc, threads, n2max, max_entries, epw; size_t lds, slab_words;
+        kernel_fn fn; match_kernel_fn mfn; SatKernelArgs args; int count, nqc, threads, n2max, max_entries, epw; size_t lds, slab_words;
         int n1p, m2w, qlds, opt, wpl, cells;     // the instantiation's template arguments (sat_last_launch_info)
     };
     std::vector<Planned> plan;
@@ -395,7 +422,8 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
             // chains: one per restart up to 256; shrink until the workgroup fits the LDS.
             // query cells: through L1/L2 for 32-SSE-class queries and up (frees 8+ KB of LDS per
             // workgroup: more resident waves), in LDS for the small class
-            int chains = (maxstart + 63) / 64 * 64;
+            const int plan_starts = (mx && mx->replay) ? mx->max_matches : maxstart;
+            int chains = (plan_starts + 63) / 64 * 64;
             if (chains > 256) chains = 256;
             if (ctx->tune.chains >= 64 && ctx->tune.chains < chains) chains = ctx->tune.chains / 64 * 64;
             // work compaction needs sparse maps: with LORDER = F almost every step proposes a real
@@ -411,7 +439,7 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
                 if (chains > 64) { chains -= 64; continue; }
                 if (qlds) {                                    // query cells stay in L1/L2 instead
                     qlds = false;
-                    chains = (maxstart + 63) / 64 * 64;
+                    chains = (plan_starts + 63) / 64 * 64;
                     if (chains > 256) chains = 256;
                     continue;
                 }
@@ -445,21 +473,22 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
             a.lpc_shift = lpc_shift;
             a.compact = compact ? 1 : 0;
             // option-specialised instantiation when the layout is the default one for these options
-            const bool special = (lpc_shift == 0 || m2w == 4) && compact == (lorder != 0) && !ctx->tune.general;
+            const bool special = (lpc_shift == 0 || m2w == 4) && compact == (lorder != 0) && !ctx->tune.general && !mx;
             const int opt = special ? (lorder ? 1 : 0) | (lsoln ? 2 : 0) | (lpc_shift << 2) : -1;
-            kernel_fn fn = pick_kernel(n1p, m2w, cells, qlds, opt, ctx->class_wpl[c]);
-            if (!fn) return fail(SAT_EDEVICE, "no kernel variant for n1p=%d m2w=%d", n1p, m2w);
-            if (ctx->lds_attr_done.insert(reinterpret_cast<const void *>(fn)).second)
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));
+            kernel_fn fn = mx ? nullptr : pick_kernel(n1p, m2w, cells, qlds, opt, ctx->class_wpl[c]);
+            match_kernel_fn mfn = mx ? pick_match_kernel(n1p, m2w, cells, qlds) : nullptr;
+            const void *fn_ptr = mx ? reinterpret_cast<const void *>(mfn) : reinterpret_cast<const void *>(fn);
+            if (!fn_ptr) return fail(SAT_EDEVICE, "no kernel variant for n1p=%d m2w=%d", n1p, m2w);
+            if (ctx->lds_attr_done.insert(fn_ptr).second)
+                HIP_TRY(hipFuncSetAttribute(fn_ptr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));
             a.entry_list = view.d_list + (one_launch ? view.begin[0] : view.begin[b]);
             // entries per workgroup (see pick_epw); small launches keep one, for the most workgroups
             const size_t lds_stride = (lds + 15) & ~(size_t)15;
             int epw = 1;
             if ((long long)count * nqc >= 8192) {
-                const auto key = std::make_tuple(reinterpret_cast<const void *>(fn), threads, lds_stride);
+                const auto key = std::make_tuple(fn_ptr, threads, lds_stride);
                 auto it = ctx->epw_choice.find(key);
-                if (it == ctx->epw_choice.end()) it = ctx->epw_choice.emplace(key, pick_epw(fn, threads, lds_stride)).first;
+                if (it == ctx->epw_choice.end()) it = ctx->epw_choice.emplace(key, pick_epw(fn_ptr, threads, lds_stride)).first;
                 epw = it->second;
             }
             if (ctx->tune.epw >= 1 && (size_t)ctx->tune.epw * lds_stride <= kLdsLimit && ctx->tune.epw * threads <= 1024)
@@ -470,13 +499,15 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
             Planned pl;
             pl.epw = epw;
             pl.fn = fn;
+            pl.mfn = mfn;
             pl.args = a;
             pl.count = count;
             pl.nqc = nqc;
             pl.threads = threads;
             pl.lds = lds;
             pl.n2max = n2max;
-            pl.slab_words = lsoln ? (size_t)((n1max + 3) / 4) * chains : 0;
+            pl.slab_words = (lsoln || (mx && mx->replay)) ? (size_t)((n1max + 3) / 4) * chains
+                          : (mx ? (size_t)(1 + m2w) * (size_t)maxstart : 0);
             pl.n1p = n1p;
             pl.m2w = m2w;
             pl.cells = cells;
@@ -502,7 +533,8 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
     // that the slabs of all concurrent launches stay under 1 GiB together (a lane of launches reuses
     // its region launch after launch).  grid.y is limited to 65535: very long query lists are split too.
     const size_t lane_budget_words = ((size_t)1 << 30) / 4 / (size_t)nlanes;
-    if (lsoln) {
+    const bool slabs = lsoln || mx;
+    if (slabs) {
         size_t need_total = 0;
         for (size_t i = 0; i < plan.size(); i++) {
             Planned &pl = plan[i];
@@ -524,13 +556,13 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
             ctx->bmap_slabs_cap = need_total;
         }
     }
-    const size_t lane_region_words = lsoln ? ctx->bmap_slabs_cap / (size_t)nlanes : 0;
+    const size_t lane_region_words = slabs ? ctx->bmap_slabs_cap / (size_t)nlanes : 0;
     for (size_t i = 0; i < plan.size(); i++) {
         const Planned &pl = plan[i];
         const int lane = fork ? (int)(i % (size_t)nlanes) : 0;
         hipStream_t s = fork ? ctx->side_stream[lane] : stream;
         if (fork && i < (size_t)nlanes) HIP_TRY(hipStreamWaitEvent(s, ctx->ev_fork, 0));
-        const int max_entries = lsoln ? pl.max_entries : pl.count;
+        const int max_entries = slabs ? pl.max_entries : pl.count;
         for (int q0 = 0; q0 < pl.nqc; q0 += 65535) {
             const int qn = pl.nqc - q0 < 65535 ? pl.nqc - q0 : 65535;
             for (int e0 = 0; e0 < pl.count; e0 += max_entries) {
@@ -538,13 +570,20 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
                 SatKernelArgs part = pl.args;
                 part.queries = pl.args.queries + q0;
                 part.entry_list = pl.args.entry_list + e0;
-                if (lsoln) {
+                SatMatchArgs mpart = mx ? *mx : SatMatchArgs{};
+                if (lsoln || (mx && mx->replay)) {
                     part.bmap_slabs = ctx->d_bmap_slabs + (size_t)lane * lane_region_words;
                     part.bmap_slab_words = (uint32_t)pl.slab_words;
+                } else if (mx) {
+                    mpart.rec_slabs = ctx->d_bmap_slabs + (size_t)lane * lane_region_words;
+                    mpart.rec_slab_words = (uint32_t)pl.slab_words;
                 }
                 part.n_list = en;
                 const size_t lds_launch = pl.epw > 1 ? (size_t)pl.epw * pl.args.lds_stride : pl.lds;
-                hipLaunchKernelGGL(pl.fn, dim3((en + pl.epw - 1) / pl.epw, qn), dim3(pl.threads * pl.epw), lds_launch, s, part);
+                if (mx)
+                    hipLaunchKernelGGL(pl.mfn, dim3((en + pl.epw - 1) / pl.epw, qn), dim3(pl.threads * pl.epw), lds_launch, s, part, mpart);
+                else
+                    hipLaunchKernelGGL(pl.fn, dim3((en + pl.epw - 1) / pl.epw, qn), dim3(pl.threads * pl.epw), lds_launch, s, part);
                 HIP_TRY(hipGetLastError());
             }
         }
@@ -559,6 +598,11 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
     ctx->last_launch_info.clear();
     for (size_t i = 0; i < plan.size(); i++) {
         char buf[160];
+        if (mx)
+            snprintf(buf, sizeof buf, "%ssat_sa_match_kernel<%d, %d, %s, %d> grid %d x %d block %d x %d lds %zu", i ? "; " : "", plan[i].n1p,
+                     plan[i].m2w, plan[i].qlds ? "true" : "false", plan[i].cells,
+                     (plan[i].count + plan[i].epw - 1) / plan[i].epw, plan[i].nqc, plan[i].epw, plan[i].threads, plan[i].lds);
+        else
         snprintf(buf, sizeof buf, "%ssat_sa_kernel<%d, %d, %s, %d, %d, %d> grid %d x %d block %d x %d lds %zu", i ? "; " : "", plan[i].n1p,
                  plan[i].m2w, plan[i].qlds ? "true" : "false", plan[i].opt, plan[i].wpl, plan[i].cells,
                  (plan[i].count + plan[i].epw - 1) / plan[i].epw, plan[i].nqc, plan[i].epw, plan[i].threads, plan[i].lds);
@@ -685,6 +729,10 @@ void sat_ctx_destroy(sat_ctx *ctx)
     dev_free(ctx->d_qblob);
     dev_free(ctx->d_qdesc);
     dev_free(ctx->d_bmap_slabs);
+    dev_free(ctx->d_mcounts);
+    dev_free(ctx->d_mscores);
+    dev_free(ctx->d_mrestarts);
+    dev_free(ctx->d_mmaps);
     dev_free(ctx->d_ptab);
     dev_free(ctx->d_prow);
     dev_free(ctx->d_keys);
@@ -1194,6 +1242,129 @@ int sat_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart,
         *kernel_ms = ms;
     }
     return sat_results(ctx, lsoln, scores, ssemaps);
+}
+
+}  // extern "C"
+
+int sat_matches_launch(sat_ctx *ctx, int lorder, int maxstart, int max_matches, bool maps)
+{
+    if (!ctx) return fail(SAT_EINVAL, "null context");
+    if (max_matches < 1 || max_matches > SAT_MAX_MATCHES)
+        return fail(SAT_EINVAL, "max_matches must be 1..%d (got %d)", SAT_MAX_MATCHES, max_matches);
+    if (ctx->n_entries <= 0) return fail(SAT_ESTATE, "no database uploaded");
+    if (ctx->queries.empty()) return fail(SAT_ESTATE, "no query set");
+    if (maxstart < 1) return fail(SAT_EINVAL, "maxstart must be >= 1 (got %d)", maxstart);
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t rows = ctx->queries.size() * (size_t)ctx->n_entries;
+    // each buffer against its own capacity in elements (counts: one per row, scores / restarts: M per row, maps:
+    // M x SAT_MAXDIM bytes per row); a capacity is reset before its buffer is replaced, so a failed allocation
+    // leaves none that claims more than it holds
+    const size_t slots = rows * (size_t)max_matches;
+    if (rows > ctx->mcounts_cap) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        dev_free(ctx->d_mcounts);
+        ctx->mcounts_cap = 0;
+        HIP_TRY(hipMalloc(&ctx->d_mcounts, rows * sizeof(int32_t)));
+        ctx->mcounts_cap = rows;
+    }
+    if (slots > ctx->mslots_cap) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        dev_free(ctx->d_mscores);
+        dev_free(ctx->d_mrestarts);
+        ctx->mslots_cap = 0;
+        HIP_TRY(hipMalloc(&ctx->d_mscores, slots * sizeof(int32_t)));
+        HIP_TRY(hipMalloc(&ctx->d_mrestarts, slots * sizeof(int32_t)));
+        ctx->mslots_cap = slots;
+    }
+    const size_t map_bytes = maps ? slots * SAT_MAXDIM : 0;
+    if (map_bytes > ctx->mmaps_cap) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        dev_free(ctx->d_mmaps);
+        ctx->mmaps_cap = 0;
+        HIP_TRY(hipMalloc(&ctx->d_mmaps, map_bytes));
+        ctx->mmaps_cap = map_bytes;
+    }
+    SatMatchArgs mx{};
+    mx.desc_base = ctx->d_qdesc;
+    mx.n_entries = ctx->n_entries;
+    mx.max_matches = max_matches;
+    mx.replay = 0;
+    mx.map_pitch = SAT_MAXDIM;
+    mx.counts = ctx->d_mcounts;
+    mx.scores = ctx->d_mscores;
+    mx.restarts = ctx->d_mrestarts;
+    mx.maps = ctx->d_mmaps;
+    int rc = launch_search(ctx, lorder, 0, maxstart, ctx->stream, nullptr, &mx);
+    if (rc != SAT_OK) return rc;
+    // sat_last_launch_info names both passes
+    const std::string record_info = ctx->last_launch_info;
+    ctx->last_launch_info = "record pass: " + record_info;
+    if (!maps) return SAT_OK;
+    // the replay pass reads the record pass's counts and restarts: same stream, and the order buckets of one pass
+    // are joined back onto it before the next pass forks
+    mx.replay = 1;
+    rc = launch_search(ctx, lorder, 0, maxstart, ctx->stream, nullptr, &mx);
+    if (rc == SAT_OK) ctx->last_launch_info = "record pass: " + record_info + " | replay pass: " + ctx->last_launch_info;
+    return rc;
+}
+
+int sat_matches_collect(sat_ctx *ctx, int max_matches, int32_t *counts, int32_t *scores, int32_t *restarts,
+                        int32_t *ssemaps, size_t total, size_t offset)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const size_t nq = ctx->queries.size(), N = (size_t)ctx->n_entries, M = (size_t)max_matches;
+    std::vector<int32_t> c(nq * N), sc(nq * N * M), rs(nq * N * M);
+    std::vector<int8_t> mp(ssemaps ? nq * N * M * SAT_MAXDIM : 0);
+    HIP_TRY(hipMemcpy(c.data(), ctx->d_mcounts, c.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sc.data(), ctx->d_mscores, sc.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rs.data(), ctx->d_mrestarts, rs.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (ssemaps) HIP_TRY(hipMemcpy(mp.data(), ctx->d_mmaps, mp.size(), hipMemcpyDeviceToHost));
+    ctx->d2h_bytes += (c.size() + sc.size() + rs.size()) * sizeof(int32_t) + mp.size();
+    // device rows are by descriptor index: the queries grouped by size class (refresh_descriptors)
+    std::vector<size_t> desc_query;
+    for (int cl = 0; cl < 4; cl++)
+        for (size_t qi = 0; qi < nq; qi++)
+            if (ctx->queries[qi].n1p == kClassN1P[cl]) desc_query.push_back(qi);
+    for (size_t d = 0; d < nq; d++) {
+        const size_t qi = desc_query[d];
+        const int n1 = ctx->queries[qi].n1;
+        for (size_t e = 0; e < N; e++) {
+            const size_t src = d * N + e, dst = qi * total + offset + e;
+            counts[dst] = c[src];
+            for (size_t m = 0; m < M; m++) {
+                scores[dst * M + m] = sc[src * M + m];
+                restarts[dst * M + m] = rs[src * M + m];
+                if (!ssemaps) continue;
+                int32_t *out = ssemaps + (dst * M + m) * SAT_MAXDIM;
+                const int8_t *in = mp.data() + (src * M + m) * SAT_MAXDIM;
+                const bool used = (int)m < c[src];
+                for (int i = 0; i < SAT_MAXDIM; i++) out[i] = (used && i < n1) ? in[i] : -1;
+            }
+        }
+    }
+    return SAT_OK;
+}
+
+extern "C" {
+
+int sat_search_matches(sat_ctx *ctx, int lorder, int maxstart, int max_matches, int32_t *counts, int32_t *scores,
+                       int32_t *restarts, int32_t *ssemaps, double *kernel_ms)
+{
+    if (!ctx) return fail(SAT_EINVAL, "null context");
+    if (!counts || !scores || !restarts) return fail(SAT_EINVAL, "counts / scores / restarts buffer is null");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    int rc = sat_matches_launch(ctx, lorder, maxstart, max_matches, ssemaps != nullptr);
+    if (rc != SAT_OK) return rc;
+    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (kernel_ms) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+        *kernel_ms = ms;
+    }
+    return sat_matches_collect(ctx, max_matches, counts, scores, restarts, ssemaps, (size_t)ctx->n_entries, 0);
 }
 
 int sat_search_timed(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int repeats,

@@ -75,6 +75,10 @@ struct sat_ctx {
     size_t ssemaps_cap = 0;
     uint32_t *d_bmap_slabs = nullptr;        // LSOLN scratch: one best-map slab per workgroup of a launch
     size_t bmap_slabs_cap = 0;               // in 32-bit words
+    // several matches per entry (sat_search_matches): outputs by descriptor index d, rows d * n_entries + e
+    int32_t *d_mcounts = nullptr, *d_mscores = nullptr, *d_mrestarts = nullptr;
+    int8_t *d_mmaps = nullptr;               // [ndesc][N][M][SAT_MAXDIM]
+    size_t mcounts_cap = 0, mslots_cap = 0, mmaps_cap = 0;   // elements: rows / rows x M / map bytes
 
     // best-k selection (sat_topk.hip): context-owned scratch that only grows; capacities in elements
     unsigned long long *d_keys = nullptr, *d_sorted = nullptr;
@@ -99,3 +103,10 @@ struct sat_ctx {
 
 // sets sat_last_error() text and returns `code`
 int sat_fail(int code, const char *fmt, ...);
+
+// The two halves of sat_search_matches (sat_capi.hip), for sat_multi_search_matches: queue both passes on the
+// context's stream, then wait and copy query q's row of entry e to row q * total + offset + e of the caller's arrays
+// (maps may be NULL: no replay pass, none copied).
+int sat_matches_launch(sat_ctx *ctx, int lorder, int maxstart, int max_matches, bool maps);
+int sat_matches_collect(sat_ctx *ctx, int max_matches, int32_t *counts, int32_t *scores, int32_t *restarts,
+                        int32_t *ssemaps, size_t total, size_t offset);

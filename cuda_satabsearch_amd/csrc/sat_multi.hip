@@ -457,6 +457,28 @@ int sat_multi_search_topk(sat_multi *m, int lorder, int lsoln, int maxstart, int
     return k;
 }
 
+int sat_multi_search_matches(sat_multi *m, int lorder, int maxstart, int max_matches, int32_t *counts,
+                             int32_t *scores, int32_t *restarts, int32_t *ssemaps, double *wall_ms)
+{
+    if (!m) return sat_fail(SAT_EINVAL, "null context");
+    if (!counts || !scores || !restarts) return sat_fail(SAT_EINVAL, "counts / scores / restarts buffer is null");
+    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
+    const auto t0 = std::chrono::steady_clock::now();
+    auto bail = [&](int rc) { const std::string msg = sat_last_error(); sync_all(m); return sat_fail(rc, "%s", msg.c_str()); };
+    // both passes queued on every GPU, then each shard's rows copied to its place in database order
+    for (int g = 0; g < m->ndev; g++) {
+        const int rc = sat_matches_launch(m->ctx[(size_t)g], lorder, maxstart, max_matches, ssemaps != nullptr);
+        if (rc != SAT_OK) return bail(rc);
+    }
+    for (int g = 0; g < m->ndev; g++) {
+        const int rc = sat_matches_collect(m->ctx[(size_t)g], max_matches, counts, scores, restarts, ssemaps,
+                                           (size_t)m->n_entries, (size_t)m->begin[(size_t)g]);
+        if (rc != SAT_OK) return bail(rc);
+    }
+    if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return SAT_OK;
+}
+
 unsigned long long sat_multi_stat_d2h_bytes(const sat_multi *m)
 {
     if (!m) return 0ull;

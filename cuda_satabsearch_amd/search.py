@@ -21,6 +21,18 @@ def device_count():
     return int(_native.device_lib().sat_device_count())
 
 
+def _search_matches(obj, fn, handle, max_matches, lorder, maxstart, maps):
+    nq, n, m = obj.n_queries, obj.n_entries, max(int(max_matches), 1)
+    counts = np.zeros((nq, n), np.int32)
+    scores = np.zeros((nq, n, m), np.int32)
+    restarts = np.zeros((nq, n, m), np.int32)
+    ssemaps = np.full((nq, n, m, MAXDIM), -1, np.int32) if maps else None
+    ms = C.c_double(0.0)
+    obj._check(fn(handle, int(bool(lorder)), int(maxstart), int(max_matches), counts.ctypes.data, scores.ctypes.data,
+                  restarts.ctypes.data, ssemaps.ctypes.data if maps else None, C.byref(ms)))
+    return counts, scores, restarts, (ssemaps[..., :obj.n1max] if maps else None), ms.value
+
+
 class Searcher:
     """One HIP device, one resident database shard, one current query."""
 
@@ -114,6 +126,7 @@ class Searcher:
         self._check(self._lib.sat_query_set(self._ctx, n1, qtab.ctypes.data, qdmat.ctypes.data, pitch,
                                             qssetypes.ctypes.data, int(query_ordinal)))
         self.n1 = n1
+        self.n1max = n1
         self.n_queries = 1
         self._batch = False
 
@@ -139,6 +152,7 @@ class Searcher:
         self._check(self._lib.sat_queries_set(self._ctx, nq, n1s.ctypes.data, tabs.ctypes.data, dmats.ctypes.data,
                                               pitch, types.ctypes.data, int(first_query_ordinal)))
         self.n1 = int(n1s[0])
+        self.n1max = int(n1s.max())
         self.n_queries = nq
         self._batch = True
 
@@ -159,6 +173,13 @@ class Searcher:
         if not getattr(self, "_batch", False):
             return scores[0], (ssemaps[0] if lsoln else None), ms.value
         return scores, ssemaps, ms.value
+
+    def search_matches(self, max_matches, lorder=True, maxstart=DEFAULT_MAXSTART, maps=True):
+        """Up to `max_matches` non-overlapping matches per (query, entry) (sat_search_matches): returns
+        (counts int32[nq, N], scores int32[nq, N, M], restarts int32[nq, N, M],
+        maps int32[nq, N, M, n1max] or None, kernel_ms) - always with the query axis, n1max = the largest
+        query order.  Match 0 is search()'s score and LSOLN map; slots past the count hold 0, -1, all -1."""
+        return _search_matches(self, self._lib.sat_search_matches, self._ctx, max_matches, lorder, maxstart, maps)
 
     def use_stream(self, stream_handle):
         """Queue all further work on the caller's HIP stream (0 / None = default stream),
@@ -313,6 +334,7 @@ class MultiSearcher:
         self._check(self._lib.sat_multi_queries_set(self._m, nq, n1s.ctypes.data, tabs.ctypes.data, dmats.ctypes.data,
                                                     pitch, types.ctypes.data, int(first_query_ordinal)))
         self.n_queries = nq
+        self.n1max = int(n1s.max())
 
     def search(self, lorder=True, lsoln=False, maxstart=DEFAULT_MAXSTART):
         """Returns (scores int32[nq, N], ssemaps int32[nq, N, 111] or None, wall_ms), database order."""
@@ -322,6 +344,10 @@ class MultiSearcher:
         self._check(self._lib.sat_multi_search(self._m, int(bool(lorder)), int(bool(lsoln)), int(maxstart), scores.ctypes.data,
                                                ssemaps.ctypes.data if lsoln else None, C.byref(ms)))
         return scores, ssemaps, ms.value
+
+    def search_matches(self, max_matches, lorder=True, maxstart=DEFAULT_MAXSTART, maps=True):
+        """Searcher.search_matches over every shard, database order (wall_ms instead of kernel_ms)."""
+        return _search_matches(self, self._lib.sat_multi_search_matches, self._m, max_matches, lorder, maxstart, maps)
 
     def search_topk(self, k, lorder=True, lsoln=False, maxstart=DEFAULT_MAXSTART):
         k = min(int(k), self.n_entries)

@@ -29,6 +29,7 @@ extern "C" {
 #define SAT_MAXDIM        111    /* saparams.h:15 (MAXDIM): largest structure order        */
 #define SAT_MAXITER       100    /* saparams.h:33 (MAXITER): SA steps per restart           */
 #define SAT_DEFAULT_SEED  1234   /* H.cu:263, :871                                           */
+#define SAT_MAX_MATCHES   8      /* largest max_matches of sat_search_matches                */
 
 #define SAT_OK          0
 #define SAT_EINVAL     -1   /* bad argument (order out of range, bad type code, ...)        */
@@ -159,6 +160,28 @@ int sat_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart,
                int32_t *scores, int32_t *ssemaps, double *kernel_ms);
 
 /*
+ * Several matches per entry: up to max_matches non-overlapping placements of the query in every database
+ * structure (a motif that occurs twice in a chain is found twice).  Every (query, entry) runs the maxstart
+ * restarts of sat_search, with the same streams.  Restart r's own best s_r is the largest of its initial
+ * full score and its 100 proposed scores, map_r the state where s_r is first reached (strict >, the proposed
+ * state, as for the LSOLN map), D_r the db SSEs map_r matches, key_r = (s_r, -r).  Walking the restarts by
+ * descending key, the first is taken - exactly sat_search's score and LSOLN map - and each later r is taken
+ * iff s_r > 0 and D_r is disjoint from the D of everything taken before, up to max_matches
+ * (1..SAT_MAX_MATCHES, else SAT_EINVAL).  Results do not depend on the launch shape or the sharding.
+ *   counts    [nq][n_entries]              matches found, 1..max_matches
+ *   scores    [nq][n_entries][M]           s_r of match m; 0 past the count
+ *   restarts  [nq][n_entries][M]           r of match m; -1 past the count
+ *   ssemaps   [nq][n_entries][M][SAT_MAXDIM] map_r of match m as sat_search lays out a map, all -1 past
+ *             the count; or NULL: the maps are not computed (their pass is skipped)
+ *   kernel_ms as sat_search
+ * Everything else sat_search rejects is rejected the same way.  The call leaves the buffers behind
+ * sat_results / sat_topk / sat_topk_hits / sat_device_scores holding match 0's scores, as after
+ * sat_search(lsoln = 0): ranking those gives the entries as a plain search ranks them.
+ */
+int sat_search_matches(sat_ctx *ctx, int lorder, int maxstart, int max_matches,
+                       int32_t *counts, int32_t *scores, int32_t *restarts, int32_t *ssemaps,
+                       double *kernel_ms);
+/*
  * Queue all further work of this context on the caller's stream (`hip_stream` is a
  * hipStream_t passed as void*; NULL selects the device's default stream).  A context
  * starts on a private non-blocking stream; sat_use_own_stream() goes back to it.
@@ -237,7 +260,8 @@ int sat_topk_hits(sat_ctx *ctx, int k, sat_hit *hits, int32_t *ssemaps);
 unsigned long long sat_stat_d2h_bytes(const sat_ctx *ctx);
 
 /* Diagnostics: the kernel instantiations (template arguments as rocprofv3 prints them), grids, block
- * sizes and LDS bytes of the launches of this context's last search, "; "-separated. */
+ * sizes and LDS bytes of the launches of this context's last search, "; "-separated.  After sat_search_matches:
+ * "record pass: <launches>", followed by " | replay pass: <launches>" when maps were asked for. */
 const char *sat_last_launch_info(const sat_ctx *ctx);
 
 /*
@@ -294,6 +318,11 @@ int sat_multi_search(sat_multi *m, int lorder, int lsoln, int maxstart, int32_t 
                      double *wall_ms);
 int sat_multi_search_topk(sat_multi *m, int lorder, int lsoln, int maxstart, int k, sat_hit *hits,
                           int32_t *ssemaps, double *wall_ms);
+/* sat_search_matches over every shard: counts [nq][n_entries], scores / restarts [nq][n_entries][M],
+ * ssemaps [nq][n_entries][M][SAT_MAXDIM] or NULL, in database order; wall_ms as sat_multi_search.
+ * Leaves every shard's context as sat_search_matches leaves it. */
+int sat_multi_search_matches(sat_multi *m, int lorder, int maxstart, int max_matches, int32_t *counts,
+                             int32_t *scores, int32_t *restarts, int32_t *ssemaps, double *wall_ms);
 unsigned long long sat_multi_stat_d2h_bytes(const sat_multi *m);
 
 /*
