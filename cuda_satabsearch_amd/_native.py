@@ -25,6 +25,7 @@ ABI_SYMBOLS = (
     "sat_multi_create", "sat_multi_destroy", "sat_multi_device_count", "sat_multi_gather_kind", "sat_multi_db_upload_packed",
     "sat_multi_shards", "sat_multi_queries_set", "sat_multi_search", "sat_multi_search_topk", "sat_multi_stat_d2h_bytes",
     "sat_search_matches", "sat_multi_search_matches",
+    "sat_search_pairs", "sat_search_refine", "sat_multi_search_refine",
 )
 
 
@@ -111,6 +112,13 @@ def device_lib():
                                            C.c_void_p, C.POINTER(C.c_double)]
         lib.sat_multi_search_matches.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+        lib.sat_search_pairs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+        lib.sat_search_refine.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.sat_multi_search_refine.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
+                                                C.POINTER(C.c_double)]
         lib.sat_multi_stat_d2h_bytes.argtypes = [C.c_void_p]
         lib.sat_multi_stat_d2h_bytes.restype = C.c_uint64
         lib.sat_device_scores.argtypes = [C.c_void_p]

@@ -49,13 +49,15 @@ static double now_ms(void)
 }
 
 /* The sanitizer build of the host code links this file against stubs of the device library
- * (tests/native/gpu_stubs.c) that have no several-matches entry point: a weak reference keeps that link
- * working, and -m reports the missing entry point instead of calling it. */
+ * (tests/native/gpu_stubs.c) that have no several-matches or refine entry point: weak references keep that
+ * link working, and -m / -R report the missing entry point instead of calling it. */
 #pragma weak sat_multi_search_matches
+#pragma weak sat_multi_search_refine
 
 static void usage(const char *prog)
 {
-    fprintf(stderr, "Usage: %s [-c] [-q dbfile] [-r restarts] [-g gpus] [-G gpu,gpu,...] [-s seed] [-k K] [-m M] [-b]\n", prog);
+    fprintf(stderr, "Usage: %s [-c] [-q dbfile] [-r restarts] [-g gpus] [-G gpu,gpu,...] [-s seed] [-k K] [-m M]\n"
+                    "       [-R restarts [-C C]] [-b]\n", prog);
     fprintf(stderr, "  -c : run on host CPU not GPU card\n");
     fprintf(stderr, "  -q dbfile : database is read from dbfile, list of query\n"
                     "              ids is read from stdin\n");
@@ -66,6 +68,9 @@ static void usage(const char *prog)
     fprintf(stderr, "  -k K : print only the K best rows per query (GPU mode)\n");
     fprintf(stderr, "  -m M : up to M (1..%d) non-overlapping matches per structure: after an entry's row,\n"
                     "         matches 2..M as rows named name:k (GPU mode)\n", SAT_MAX_MATCHES);
+    fprintf(stderr, "  -R restarts : re-score each query's C best entries (by -r) with this many restarts;\n"
+                    "                rows as -k, with the new scores (GPU mode, needs -k)\n");
+    fprintf(stderr, "  -C C : candidates per query re-scored by -R. Default K\n");
     fprintf(stderr, "  -b : cache the parsed database as dbfile.satbin\n");
     exit(1);
 }
@@ -227,13 +232,14 @@ int main(int argc, char *argv[])
     char dbfile[SAT_MAX_LINE_LEN] = "";
     char buf[SAT_MAX_LINE_LEN];
     int use_gpu = 1, querydbmode = 0, maxstart = 128, want_gpus = 1, bincache = 0, topk = 0, nmatch = 0;
+    int refine = 0, ncand = 0;                      /* -R restarts of the second stage, -C candidates per query */
     unsigned long long seed = SAT_DEFAULT_SEED;
     int ltype = 0, lorder = 0, lsoln = 0;
     char cltype = 'F', clorder = 'F', clsoln = 'F';
     int c;
 
     int dev_list[64], ndev_list = 0;
-    while ((c = getopt(argc, argv, "cq:r:g:G:s:bk:m:")) != -1) {
+    while ((c = getopt(argc, argv, "cq:r:g:G:s:bk:m:R:C:")) != -1) {
         switch (c) {
         case 'c': use_gpu = 0; break;
         case 'q': querydbmode = 1; strncpy(dbfile, optarg, sizeof(dbfile) - 1); break;
@@ -254,8 +260,46 @@ int main(int argc, char *argv[])
             nmatch = (int)v;
             break;
         }
+        case 'R':
+        case 'C': {
+            /* positive, digits only */
+            char *end = NULL;
+            const long v = strtol(optarg, &end, 10);
+            if (end == optarg || *end != '\0' || v < 1 || v > 0x7FFFFFFFL) {
+                fprintf(stderr, "ERROR: -%c needs a positive integer (got '%s')\n", c, optarg);
+                usage(argv[0]);
+            }
+            if (c == 'R') refine = (int)v;
+            else ncand = (int)v;
+            break;
+        }
         default: usage(argv[0]);
         }
+    }
+    if (refine && !use_gpu) {
+        fprintf(stderr, "ERROR: -R needs the GPU path\n");
+        exit(1);
+    }
+    if (refine && nmatch) {
+        fprintf(stderr, "ERROR: -R cannot be combined with -m\n");
+        exit(1);
+    }
+    if (refine && topk <= 0) {
+        fprintf(stderr, "ERROR: -R needs -k K\n");
+        exit(1);
+    }
+    if (ncand && !refine) {
+        fprintf(stderr, "ERROR: -C needs -R\n");
+        exit(1);
+    }
+    if (refine && !ncand) ncand = topk;
+    if (refine && topk > ncand) {
+        fprintf(stderr, "ERROR: -k K (%d) exceeds -C C (%d)\n", topk, ncand);
+        exit(1);
+    }
+    if (refine && !sat_multi_search_refine) {
+        fprintf(stderr, "ERROR: this library has no sat_multi_search_refine\n");
+        exit(1);
     }
     if (nmatch && !use_gpu) {
         fprintf(stderr, "ERROR: -m needs the GPU path\n");
@@ -541,7 +585,10 @@ int main(int argc, char *argv[])
                 nqb, nqb == 1 ? "y" : "ies", sat_set_name(qsrc, qindex[q0]));
         double ms = 0.0;
         int rc = sat_multi_queries_set(multi, nqb, n1s, qtabs, qdmats, SAT_MAXDIM, qtypes, (uint32_t)q0);
-        if (rc == SAT_OK && !nmatch)
+        double ms_stage2 = 0.0;
+        if (rc == SAT_OK && refine)
+            rc = sat_multi_search_refine(multi, lorder, lsoln, maxstart, ncand, refine, kk, hits, hit_maps, NULL, &ms, &ms_stage2);
+        else if (rc == SAT_OK && !nmatch)
             rc = topk > 0 ? sat_multi_search_topk(multi, lorder, lsoln, maxstart, kk, hits, hit_maps, &ms)
                           : sat_multi_search(multi, lorder, lsoln, maxstart, scores, ssemaps, &ms);
         if (rc == SAT_OK && nmatch) {
@@ -560,6 +607,9 @@ int main(int argc, char *argv[])
             goto bye;
         }
         fprintf(stderr, "GPU execution time %f ms\n", ms);
+        if (refine)
+            fprintf(stderr, "refine: stage 2 %f ms, %d candidates per query x %d restarts\n", ms_stage2,
+                    ncand < total ? ncand : total, refine);
         fprintf(stderr, "%f million iterations/sec\n",
                 ((double)total * nqb * ((double)maxstart * SAT_MAXITER) / (ms / 1000)) / 1.0e6);
         if (topk > 0) {

@@ -347,6 +347,71 @@ int pick_epw(const void *fn, int threads, size_t lds_stride)
     return best;
 }
 
+// The workgroup of one launch: restart chains (one per restart up to 256, fewer where the LDS would not fit them),
+// lanes per chain, where the query cells live, whether the SA step compacts its work, and the LDS bytes of one
+// entry slot.  plan_starts = the most restarts one entry slot runs.
+struct WgShape { int chains, lpc_shift, threads; bool qlds, compact; size_t lds; };
+int size_workgroup(const sat_ctx *ctx, int plan_starts, int n1max, int n1p, int n2max, bool lsoln, bool lorder, WgShape &out)
+{
+    // chains: one per restart up to 256; shrink until the workgroup fits the LDS.
+    // query cells: through L1/L2 for 32-SSE-class queries and up (frees 8+ KB of LDS per
+    // workgroup: more resident waves), in LDS for the small class
+    int chains = (plan_starts + 63) / 64 * 64;
+    if (chains > 256) chains = 256;
+    if (ctx->tune.chains >= 64 && ctx->tune.chains < chains) chains = ctx->tune.chains / 64 * 64;
+    // work compaction needs sparse maps: with LORDER = F almost every step proposes a real
+    // new image, the static loops win and the tables would only cost LDS
+    bool compact = lorder != 0;
+    if (ctx->tune.compact >= 0) compact = ctx->tune.compact != 0;
+    bool qlds = n1p < 32;
+    if (ctx->tune.qlds >= 0) qlds = ctx->tune.qlds != 0 || n1p < 32;
+    size_t lds = 0;
+    for (;;) {
+        lds = satk::lds_bytes(n1max, n1p, n2max, chains, chains, lsoln, qlds, compact);
+        if (lds <= kLdsLimit) break;
+        if (chains > 64) { chains -= 64; continue; }
+        if (qlds) {                                    // query cells stay in L1/L2 instead
+            qlds = false;
+            chains = (plan_starts + 63) / 64 * 64;
+            if (chains > 256) chains = 256;
+            continue;
+        }
+        return fail(SAT_EINVAL, "workgroup does not fit in LDS (n1=%d n2=%d)", n1max, n2max);
+    }
+    // lanes per chain: when LDS leaves fewer than 2 waves per SIMD, let 2 or 4 adjacent lanes
+    // share a chain (same cells in LDS, 2-4x the waves; they split the pair loops).  Measured:
+    // the smallest sharing that reaches 8 waves per CU wins (one lane per chain also runs the
+    // option-specialised kernels); beyond that, sharing only adds redundant bookkeeping.
+    int lpc_shift = 0;
+    for (int l = 0; l <= 2; l++) {
+        if ((chains << l) > 1024 || (l > 0 && n1max <= (8 << (l - 1)))) break;
+        const size_t lds_l = satk::lds_bytes(n1max, n1p, n2max, chains, chains << l, lsoln, qlds, compact);
+        if (lds_l > kLdsLimit) break;
+        lpc_shift = l;
+        // (target: 8 resident waves per CU; 12 for the 101-SSE query class, whose steps are the longest
+        // dependent chains - measured with the triangle cells: configs[4] 2.31 -> 2.45 M scorings/s, the
+        // 101-SSE probe 2.48 -> 2.65 M, while 96-SSE entries under a 32-SSE query lose 5 % at 12)
+        const int want_waves = ctx->tune.lpc_waves > 0 ? ctx->tune.lpc_waves : (n1p == 112 ? 12 : 8);
+        if (resident_by_lds(lds_l) * ((chains << l) / 64) >= want_waves) break;
+    }
+    if (ctx->tune.lpc >= 0 && ctx->tune.lpc <= 2 && (chains << ctx->tune.lpc) <= 1024) lpc_shift = ctx->tune.lpc;
+    // the per-wave tables grow with the lanes: re-size, backing off if that no longer fits
+    for (;; lpc_shift--) {
+        lds = satk::lds_bytes(n1max, n1p, n2max, chains, chains << lpc_shift, lsoln, qlds, compact);
+        if (lds <= kLdsLimit || lpc_shift == 0) break;
+    }
+    const int threads = chains << lpc_shift;
+    // experiment knob: extra (unused) LDS bytes per workgroup, to lower the occupancy
+    if (ctx->tune.lds_pad && lds + ctx->tune.lds_pad <= kLdsLimit) lds += ctx->tune.lds_pad;
+    out.chains = chains;
+    out.lpc_shift = lpc_shift;
+    out.threads = threads;
+    out.qlds = qlds;
+    out.compact = compact;
+    out.lds = lds;
+    return SAT_OK;
+}
+
 // The entries a set of launches covers: indices into the resident shard grouped by order bucket.  A search
 // covers the whole shard (the context's lists); the overlapped upload (sat_db_upload_search) searches the
 // shard piece by piece, each piece with lists of its own.
@@ -419,57 +484,13 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
             const int m2w = n2max <= 32 ? 1 : (n2max <= 64 ? 2 : 4);
             const int cells = satk::cell_layout(n2max);           // (lds_bytes sizes the workgroup for the same layout)
 
-            // chains: one per restart up to 256; shrink until the workgroup fits the LDS.
-            // query cells: through L1/L2 for 32-SSE-class queries and up (frees 8+ KB of LDS per
-            // workgroup: more resident waves), in LDS for the small class
             const int plan_starts = (mx && mx->replay) ? mx->max_matches : maxstart;
-            int chains = (plan_starts + 63) / 64 * 64;
-            if (chains > 256) chains = 256;
-            if (ctx->tune.chains >= 64 && ctx->tune.chains < chains) chains = ctx->tune.chains / 64 * 64;
-            // work compaction needs sparse maps: with LORDER = F almost every step proposes a real
-            // new image, the static loops win and the tables would only cost LDS
-            bool compact = lorder != 0;
-            if (ctx->tune.compact >= 0) compact = ctx->tune.compact != 0;
-            bool qlds = n1p < 32;
-            if (ctx->tune.qlds >= 0) qlds = ctx->tune.qlds != 0 || n1p < 32;
-            size_t lds = 0;
-            for (;;) {
-                lds = satk::lds_bytes(n1max, n1p, n2max, chains, chains, lsoln != 0, qlds, compact);
-                if (lds <= kLdsLimit) break;
-                if (chains > 64) { chains -= 64; continue; }
-                if (qlds) {                                    // query cells stay in L1/L2 instead
-                    qlds = false;
-                    chains = (plan_starts + 63) / 64 * 64;
-                    if (chains > 256) chains = 256;
-                    continue;
-                }
-                return fail(SAT_EINVAL, "workgroup does not fit in LDS (n1=%d n2=%d)", n1max, n2max);
-            }
-            // lanes per chain: when LDS leaves fewer than 2 waves per SIMD, let 2 or 4 adjacent lanes
-            // share a chain (same cells in LDS, 2-4x the waves; they split the pair loops).  Measured:
-            // the smallest sharing that reaches 8 waves per CU wins (one lane per chain also runs the
-            // option-specialised kernels); beyond that, sharing only adds redundant bookkeeping.
-            int lpc_shift = 0;
-            for (int l = 0; l <= 2; l++) {
-                if ((chains << l) > 1024 || (l > 0 && n1max <= (8 << (l - 1)))) break;
-                const size_t lds_l = satk::lds_bytes(n1max, n1p, n2max, chains, chains << l, lsoln != 0, qlds, compact);
-                if (lds_l > kLdsLimit) break;
-                lpc_shift = l;
-                // (target: 8 resident waves per CU; 12 for the 101-SSE query class, whose steps are the longest
-                // dependent chains - measured with the triangle cells: configs[4] 2.31 -> 2.45 M scorings/s, the
-                // 101-SSE probe 2.48 -> 2.65 M, while 96-SSE entries under a 32-SSE query lose 5 % at 12)
-                const int want_waves = ctx->tune.lpc_waves > 0 ? ctx->tune.lpc_waves : (n1p == 112 ? 12 : 8);
-                if (resident_by_lds(lds_l) * ((chains << l) / 64) >= want_waves) break;
-            }
-            if (ctx->tune.lpc >= 0 && ctx->tune.lpc <= 2 && (chains << ctx->tune.lpc) <= 1024) lpc_shift = ctx->tune.lpc;
-            // the per-wave tables grow with the lanes: re-size, backing off if that no longer fits
-            for (;; lpc_shift--) {
-                lds = satk::lds_bytes(n1max, n1p, n2max, chains, chains << lpc_shift, lsoln != 0, qlds, compact);
-                if (lds <= kLdsLimit || lpc_shift == 0) break;
-            }
-            const int threads = chains << lpc_shift;
-            // experiment knob: extra (unused) LDS bytes per workgroup, to lower the occupancy
-            if (ctx->tune.lds_pad && lds + ctx->tune.lds_pad <= kLdsLimit) lds += ctx->tune.lds_pad;
+            WgShape w;
+            rc = size_workgroup(ctx, plan_starts, n1max, n1p, n2max, lsoln != 0, lorder != 0, w);
+            if (rc != SAT_OK) return rc;
+            const int chains = w.chains, lpc_shift = w.lpc_shift, threads = w.threads;
+            const bool compact = w.compact, qlds = w.qlds;
+            const size_t lds = w.lds;
             a.lpc_shift = lpc_shift;
             a.compact = compact ? 1 : 0;
             // option-specialised instantiation when the layout is the default one for these options
@@ -614,6 +635,313 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
     return SAT_OK;
 }
 
+// ---------------------------------------------------------------- pair mode (sat_search_pairs)
+
+typedef void (*pair_kernel_fn)(const SatKernelArgs, const SatPairArgs);
+// the pair kernel of a launch's size class and layout: the option-specialised LSOLN-off instantiations for
+// the default layout of LORDER F and T (opt 0 / 1), the general one (opt -1) for everything else and for the
+// map pass
+template <int N1P, bool QLDS, int OPT> pair_kernel_fn pick_pair_m2w(int m2w, int cells)
+{
+    if (m2w == 1) return sat_sa_pair_kernel<N1P, 1, QLDS, OPT, SAT_CELLS_FULL8>;
+    if (m2w == 2) return cells == SAT_CELLS_FULL5 ? sat_sa_pair_kernel<N1P, 2, QLDS, OPT, SAT_CELLS_FULL5>
+                                                   : sat_sa_pair_kernel<N1P, 2, QLDS, OPT, SAT_CELLS_TRI5>;
+    return sat_sa_pair_kernel<N1P, 4, QLDS, OPT, SAT_CELLS_TRI5>;
+}
+template <int N1P> pair_kernel_fn pick_pair_n1p(int m2w, int cells, bool qlds, int opt)
+{
+    constexpr bool kQ = N1P < 32;
+    if (opt == 0 && qlds == kQ) return pick_pair_m2w<N1P, kQ, 0>(m2w, cells);
+    if (opt == 1 && qlds == kQ) return pick_pair_m2w<N1P, kQ, 1>(m2w, cells);
+    return qlds ? pick_pair_m2w<N1P, true, -1>(m2w, cells) : pick_pair_m2w<N1P, false, -1>(m2w, cells);
+}
+pair_kernel_fn pick_pair_kernel(int n1p, int m2w, int cells, bool qlds, int opt)
+{
+    switch (n1p) {
+    case 16: return pick_pair_n1p<16>(m2w, cells, qlds, opt);
+    case 32: return pick_pair_n1p<32>(m2w, cells, qlds, opt);
+    case 64: return pick_pair_n1p<64>(m2w, cells, qlds, opt);
+    default: return pick_pair_n1p<112>(m2w, cells, qlds, opt);
+    }
+}
+
+int order_bucket(int n2)
+{
+    int b = 0;
+    while (b < kNumBuckets - 1 && n2 > kBucketMax[b]) b++;
+    return b;
+}
+
+// the map pass's items name the winning restart of their pair: the low word of its key
+__global__ void __launch_bounds__(256) pair_winners(SatPairItem *items, int n, const unsigned long long *keys)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int r = (int)(0xFFFFFFFFu - (uint32_t)(keys[items[i].pair] & 0xFFFFFFFFu));
+    items[i].r0 = r;
+    items[i].r1 = r + 1;
+}
+
+__global__ void __launch_bounds__(256) pair_scores(const unsigned long long *keys, int n, int32_t *scores)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) scores[i] = (int32_t)(uint32_t)(keys[i] >> 32) - 0x40000000;
+}
+
+template <typename T> int grow_scratch(sat_ctx *ctx, T *&p, size_t &cap, size_t need)
+{
+    if (need <= cap) return SAT_OK;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    dev_free(p);
+    cap = 0;
+    HIP_TRY(hipMalloc(&p, need * sizeof(T)));
+    cap = need;
+    return SAT_OK;
+}
+
+// One pass of the pair mode: the item groups [goff[g], goff[g + 1]) of d_items, group g holding queries of class
+// gcls[g] and entries of up to gn2[g] SSEs.  Score pass (map_pass = false): the option-specialised LSOLN-off
+// kernels, restarts per item at most `starts`.  Map pass: one restart per item, the general kernel with LSOLN,
+// cut into launches whose best-map slabs stay under 256 MiB (one stream: a launch reuses the region).
+int launch_pair_pass(sat_ctx *ctx, int lorder, bool map_pass, int starts, const SatPairItem *d_items,
+                     const std::vector<size_t> &goff, const std::vector<int> &gcls, const std::vector<int> &gn2, std::string &info)
+{
+    hipStream_t stream = ctx->stream;
+    SatPairArgs px;
+    px.items = nullptr;
+    px.keys = ctx->d_pkeys;
+    px.maps = ctx->d_pmaps;
+    for (size_t g = 0; g < gcls.size(); g++) {
+        const int count = (int)(goff[g + 1] - goff[g]);
+        if (count == 0) continue;
+        const int c = gcls[g], n1p = kClassN1P[c], n1max = ctx->class_n1max[c], n2max = gn2[g];
+        const int m2w = n2max <= 32 ? 1 : (n2max <= 64 ? 2 : 4);
+        const int cells = satk::cell_layout(n2max);
+        WgShape w;
+        int rc = size_workgroup(ctx, map_pass ? 1 : starts, n1max, n1p, n2max, map_pass, lorder != 0, w);
+        if (rc != SAT_OK) return rc;
+        const bool special = !map_pass && w.lpc_shift == 0 && w.compact == (lorder != 0) && !ctx->tune.general;
+        const int opt = special ? (lorder ? 1 : 0) : -1;
+        pair_kernel_fn fn = pick_pair_kernel(n1p, m2w, cells, w.qlds, opt);
+        const int opt_used = (special && w.qlds == (n1p < 32)) ? opt : -1;
+        const void *fn_ptr = reinterpret_cast<const void *>(fn);
+        if (ctx->lds_attr_done.insert(fn_ptr).second)
+            HIP_TRY(hipFuncSetAttribute(fn_ptr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));
+        const size_t lds_stride = (w.lds + 15) & ~(size_t)15;
+        // entries per workgroup: the score pass as a plain launch; the map pass keeps one item per workgroup (its one
+        // restart per item gains nothing from packing, and its best-map slabs are counted per item)
+        int epw = 1;
+        if (!map_pass && count >= 8192) {
+            const auto key = std::make_tuple(fn_ptr, w.threads, lds_stride);
+            auto it = ctx->epw_choice.find(key);
+            if (it == ctx->epw_choice.end()) it = ctx->epw_choice.emplace(key, pick_epw(fn_ptr, w.threads, lds_stride)).first;
+            epw = it->second;
+        }
+        if (!map_pass && ctx->tune.epw >= 1 && (size_t)ctx->tune.epw * lds_stride <= kLdsLimit && ctx->tune.epw * w.threads <= 1024)
+            epw = ctx->tune.epw;
+        SatKernelArgs a;
+        a.orders = ctx->d_orders;
+        a.cell_off = ctx->d_cell_off;
+        a.tab_tri = ctx->d_tab;
+        a.dist_tri = ctx->d_dist;
+        a.ordinal = ctx->d_ordinal;
+        a.entry_list = nullptr;
+        a.epw = epw;
+        a.tpe = w.threads;
+        a.lds_stride = (uint32_t)lds_stride;
+        a.queries = ctx->d_qdesc;                       // items carry descriptor indices
+        a.lorder = lorder ? 1 : 0;
+        a.lsoln = map_pass ? 1 : 0;
+        a.maxstart = starts;                            // (unused by the pair mode's restart loop)
+        a.lpc_shift = w.lpc_shift;
+        a.compact = w.compact ? 1 : 0;
+        a.bmap_slabs = nullptr;
+        a.bmap_slab_words = 0;
+        a.ptab = ctx->d_ptab;
+        a.prow = ctx->d_prow;
+#ifdef SAT_DIAG
+        HIP_TRY(satdiag::begin(stream, a.diag));
+#endif
+        int per_launch = count;
+        if (map_pass) {
+            const size_t slab_words = (size_t)((n1max + 3) / 4) * (size_t)w.chains;
+            const size_t budget = ((size_t)1 << 28) / 4;
+            per_launch = (int)std::min<size_t>((size_t)count, std::max<size_t>(1, budget / slab_words));
+            // one slab per entry slot of a launch, the spare slots of its last workgroup included (the kernel indexes
+            // the slab by slot; with epw = 1 there are none)
+            const size_t slabs = (size_t)per_launch + (size_t)epw - 1;
+            if ((rc = grow_scratch(ctx, ctx->d_bmap_slabs, ctx->bmap_slabs_cap, slab_words * slabs)) != SAT_OK) return rc;
+            a.bmap_slabs = ctx->d_bmap_slabs;
+            a.bmap_slab_words = (uint32_t)slab_words;
+        }
+        const size_t lds_launch = epw > 1 ? (size_t)epw * lds_stride : w.lds;
+        for (int i0 = 0; i0 < count; i0 += per_launch) {
+            const int n = count - i0 < per_launch ? count - i0 : per_launch;
+            a.n_list = n;
+            px.items = d_items + goff[g] + (size_t)i0;
+            hipLaunchKernelGGL(fn, dim3((n + epw - 1) / epw, 1), dim3(w.threads * epw), lds_launch, stream, a, px);
+            HIP_TRY(hipGetLastError());
+        }
+        char buf[200];
+        snprintf(buf, sizeof buf, "%ssat_sa_pair_kernel<%d, %d, %s, %d, %d> items %d grid %d x 1 block %d x %d lds %zu",
+                 info.empty() ? "" : "; ", n1p, m2w, w.qlds ? "true" : "false", opt_used, cells, count,
+                 (count + epw - 1) / epw, epw, w.threads, w.lds);
+        info += buf;
+#ifdef SAT_DIAG
+        HIP_TRY(satdiag::end(stream));
+#endif
+    }
+    return SAT_OK;
+}
+
+}  // namespace
+
+// sat_ctx.hpp: queue a pair search (both passes) on the context's stream
+int sat_pairs_launch(sat_ctx *ctx, int lorder, int maxstart, bool maps, const int32_t *query, const int32_t *entry, int npairs)
+{
+    if (!ctx) return fail(SAT_EINVAL, "null context");
+    if (ctx->n_entries <= 0) return fail(SAT_ESTATE, "no database uploaded");
+    if (ctx->queries.empty()) return fail(SAT_ESTATE, "no query set");
+    if (maxstart < 1) return fail(SAT_EINVAL, "maxstart must be >= 1 (got %d)", maxstart);
+    if (npairs < 0 || (npairs > 0 && (!query || !entry))) return fail(SAT_EINVAL, "bad pair list");
+    const int nq = (int)ctx->queries.size();
+    for (int p = 0; p < npairs; p++) {
+        if (query[p] < 0 || query[p] >= nq) return fail(SAT_EINVAL, "pair %d: query %d out of range", p, query[p]);
+        if (entry[p] < 0 || entry[p] >= ctx->n_entries) return fail(SAT_EINVAL, "pair %d: entry %d out of range", p, entry[p]);
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    int rc = refresh_descriptors(ctx, false, ctx->stream);
+    if (rc != SAT_OK) return rc;
+    ctx->last_launch_info.clear();
+    if (npairs == 0) return SAT_OK;
+
+    // descriptor index and size class of every query (descriptors are grouped by class, input order inside)
+    std::vector<int> desc_of((size_t)nq), cls_of((size_t)nq);
+    for (int c = 0, d = 0; c < 4; c++)
+        for (int q = 0; q < nq; q++)
+            if (ctx->queries[(size_t)q].n1p == kClassN1P[c]) { desc_of[(size_t)q] = d++; cls_of[(size_t)q] = c; }
+
+    // Restarts per item.  A pair's R restarts on one workgroup of T chains take ceil(R / T) rounds at the latency
+    // of one workgroup: a few hundred pairs cannot fill the GPU that way.  Cut each pair into about
+    // kTargetItems / pairs items of whole rounds, never below one round (and no more items than rounds).
+    int split;
+    if (ctx->tune.refine_split > 0) {
+        split = ctx->tune.refine_split < maxstart ? ctx->tune.refine_split : maxstart;
+    } else {
+        constexpr long long kTargetItems = 2048;        // 256 CUs x 8 workgroups
+        const int t0 = std::min(256, (maxstart + 63) / 64 * 64);
+        const long long rounds = (maxstart + t0 - 1) / t0;
+        long long items = (kTargetItems + npairs - 1) / npairs;
+        if (items > rounds) items = rounds;
+        if (items < 1) items = 1;
+        const long long per = (rounds + items - 1) / items;
+        split = (int)std::min<long long>(maxstart, per * t0);
+    }
+    const int per_pair = (maxstart + split - 1) / split;
+
+    // groups by (query class, entry order bucket): the launch's LDS is sized for the class and the bucket's largest entry
+    std::vector<std::vector<int>> members(4 * kNumBuckets);
+    std::vector<int> n2max(4 * kNumBuckets, 0);
+    for (int p = 0; p < npairs; p++) {
+        const int n2 = ctx->h_orders[(size_t)entry[p]];
+        const int g = cls_of[(size_t)query[p]] * kNumBuckets + order_bucket(n2);
+        members[(size_t)g].push_back(p);
+        if (n2 > n2max[(size_t)g]) n2max[(size_t)g] = n2;
+    }
+    std::vector<SatPairItem> &items = ctx->h_pitems;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));      // the previous pair search's upload has read the table
+    items.clear();
+    items.reserve((size_t)npairs * (size_t)per_pair + (maps ? (size_t)npairs : 0));
+    std::vector<size_t> goff{ 0 }, moff;
+    std::vector<int> gcls, gn2;
+    for (int g = 0; g < 4 * kNumBuckets; g++) {
+        if (members[(size_t)g].empty()) continue;
+        for (int p : members[(size_t)g])
+            for (int r0 = 0; r0 < maxstart; r0 += split) {
+                SatPairItem it{};
+                it.pair = p;
+                it.desc = desc_of[(size_t)query[p]];
+                it.entry = entry[p];
+                it.r0 = r0;
+                it.r1 = maxstart - r0 < split ? maxstart : r0 + split;
+                items.push_back(it);
+            }
+        goff.push_back(items.size());
+        gcls.push_back(g / kNumBuckets);
+        gn2.push_back(n2max[(size_t)g]);
+    }
+    const size_t n_score = items.size();
+    if (maps) {
+        // map pass: one item per pair, the same groups; the restart is filled in on the device (pair_winners)
+        moff.push_back(n_score);
+        for (int g = 0; g < 4 * kNumBuckets; g++) {
+            if (members[(size_t)g].empty()) continue;
+            for (int p : members[(size_t)g]) {
+                SatPairItem it{};
+                it.pair = p;
+                it.desc = desc_of[(size_t)query[p]];
+                it.entry = entry[p];
+                items.push_back(it);
+            }
+            moff.push_back(items.size());
+        }
+    }
+    if ((rc = grow_scratch(ctx, ctx->d_pitems, ctx->pitems_cap, items.size())) != SAT_OK) return rc;
+    if ((rc = grow_scratch(ctx, ctx->d_pkeys, ctx->pkeys_cap, (size_t)npairs)) != SAT_OK) return rc;
+    if (maps && (rc = grow_scratch(ctx, ctx->d_pmaps, ctx->pmaps_cap, (size_t)npairs * SAT_MAXDIM)) != SAT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->d_pitems, items.data(), items.size() * sizeof(SatPairItem), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->d_pkeys, 0, (size_t)npairs * sizeof(unsigned long long), ctx->stream));
+    std::string info;
+    rc = launch_pair_pass(ctx, lorder, false, split, ctx->d_pitems, goff, gcls, gn2, info);
+    if (rc != SAT_OK) return rc;
+    char head[96];
+    snprintf(head, sizeof head, "score pass (%d restarts, %d per item): ", maxstart, split);
+    ctx->last_launch_info = head + info;
+    if (maps) {
+        const int n_map = (int)(items.size() - n_score);
+        HIP_TRY(hipMemsetAsync(ctx->d_pmaps, 0xFF, (size_t)npairs * SAT_MAXDIM, ctx->stream));
+        hipLaunchKernelGGL(pair_winners, dim3((unsigned)((n_map + 255) / 256)), dim3(256), 0, ctx->stream,
+                           ctx->d_pitems + n_score, n_map, ctx->d_pkeys);
+        HIP_TRY(hipGetLastError());
+        info.clear();
+        rc = launch_pair_pass(ctx, lorder, true, 1, ctx->d_pitems, moff, gcls, gn2, info);
+        if (rc != SAT_OK) return rc;
+        ctx->last_launch_info += " | map pass: " + info;
+    }
+    return SAT_OK;
+}
+
+int sat_launch_plain(sat_ctx *ctx, int lorder, int maxstart)
+{
+    return launch_search(ctx, lorder, 0, maxstart, ctx->stream);
+}
+
+int sat_pairs_collect(sat_ctx *ctx, int npairs, int32_t *scores, int32_t *ssemaps, const int32_t *query)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (npairs == 0) return SAT_OK;
+    int rc;
+    if ((rc = grow_scratch(ctx, ctx->d_pscores, ctx->pscores_cap, (size_t)npairs)) != SAT_OK) return rc;
+    hipLaunchKernelGGL(pair_scores, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_pkeys, npairs, ctx->d_pscores);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(scores, ctx->d_pscores, (size_t)npairs * sizeof(int32_t), hipMemcpyDeviceToHost));
+    ctx->d2h_bytes += (size_t)npairs * sizeof(int32_t);
+    if (ssemaps) {
+        std::vector<int8_t> mp((size_t)npairs * SAT_MAXDIM);
+        HIP_TRY(hipMemcpy(mp.data(), ctx->d_pmaps, mp.size(), hipMemcpyDeviceToHost));
+        ctx->d2h_bytes += mp.size();
+        for (int p = 0; p < npairs; p++) {
+            const int n1 = ctx->queries[(size_t)query[p]].n1;
+            for (int i = 0; i < SAT_MAXDIM; i++)
+                ssemaps[(size_t)p * SAT_MAXDIM + i] = i < n1 ? mp[(size_t)p * SAT_MAXDIM + i] : -1;
+        }
+    }
+    return SAT_OK;
+}
+
+namespace {
+
 // Upload validation: one wave per db entry reads the entry's packed triangle where the search will
 // read it and flags cells outside the kernel's domain; the lowest flagged entry index survives.
 // (entries e_begin .. e_end - 1: the overlapped upload checks the shard piece by piece)
@@ -695,6 +1023,7 @@ sat_ctx *sat_ctx_create(int device, uint64_t seed)
         ctx->tune.epw = env_int("SAT_EXP_EPW", 0);
         ctx->tune.lpc_waves = env_int("SAT_EXP_LPC_WAVES", 0);
         ctx->tune.chains = env_int("SAT_EXP_CHAINS", 0);
+        ctx->tune.refine_split = env_int("SAT_EXP_REFINE_SPLIT", 0);
         const int pad = env_int("SAT_EXP_LDS_PAD", 0);
         ctx->tune.lds_pad = pad > 0 ? (size_t)pad : 0;
         if (ctx->tune.streams != 0) {
@@ -733,6 +1062,17 @@ void sat_ctx_destroy(sat_ctx *ctx)
     dev_free(ctx->d_mscores);
     dev_free(ctx->d_mrestarts);
     dev_free(ctx->d_mmaps);
+    dev_free(ctx->d_pitems);
+    dev_free(ctx->d_pkeys);
+    dev_free(ctx->d_pmaps);
+    dev_free(ctx->d_pscores);
+    dev_free(ctx->d_rkeys);
+    dev_free(ctx->d_rsorted);
+    dev_free(ctx->d_rvals);
+    dev_free(ctx->d_rvals_sorted);
+    dev_free(ctx->d_rfirst);
+    dev_free(ctx->d_rmaps);
+    dev_free(ctx->d_rhits);
     dev_free(ctx->d_ptab);
     dev_free(ctx->d_prow);
     dev_free(ctx->d_keys);
@@ -1365,6 +1705,26 @@ int sat_search_matches(sat_ctx *ctx, int lorder, int maxstart, int max_matches, 
         *kernel_ms = ms;
     }
     return sat_matches_collect(ctx, max_matches, counts, scores, restarts, ssemaps, (size_t)ctx->n_entries, 0);
+}
+
+int sat_search_pairs(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int npairs, const int32_t *query,
+                     const int32_t *entry, int32_t *scores, int32_t *ssemaps, double *kernel_ms)
+{
+    if (!ctx) return fail(SAT_EINVAL, "null context");
+    if (npairs > 0 && !scores) return fail(SAT_EINVAL, "scores buffer is null");
+    if (lsoln && npairs > 0 && !ssemaps) return fail(SAT_EINVAL, "lsoln set but ssemaps buffer is null");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    int rc = sat_pairs_launch(ctx, lorder, maxstart, lsoln != 0, query, entry, npairs);
+    if (rc != SAT_OK) return rc;
+    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (kernel_ms) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+        *kernel_ms = ms;
+    }
+    return sat_pairs_collect(ctx, npairs, scores, lsoln ? ssemaps : nullptr, query);
 }
 
 int sat_search_timed(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int repeats,

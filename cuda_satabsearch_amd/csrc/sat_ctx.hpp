@@ -50,7 +50,7 @@ struct sat_ctx {
     int32_t *d_prow = nullptr;
 
     // launch-heuristic overrides (SAT_EXP_* in satabsearch.h), read ONCE when the context is created
-    struct Tuning { int compact = -1, qlds = -1, lpc = -1, general = 0, streams = -1, upload_threads = 0, upload_timing = 0, upload_pieces = 0, epw = 0, lpc_waves = 0, chains = 0; size_t lds_pad = 0; } tune;
+    struct Tuning { int compact = -1, qlds = -1, lpc = -1, general = 0, streams = -1, upload_threads = 0, upload_timing = 0, upload_pieces = 0, epw = 0, lpc_waves = 0, chains = 0, refine_split = 0; size_t lds_pad = 0; } tune;
     // kernel instantiations whose dynamic-LDS limit has been raised on this device
     std::unordered_set<const void *> lds_attr_done;
     // entries per workgroup chosen for (instantiation, threads per entry, LDS bytes per entry): asked once
@@ -79,6 +79,23 @@ struct sat_ctx {
     int32_t *d_mcounts = nullptr, *d_mscores = nullptr, *d_mrestarts = nullptr;
     int8_t *d_mmaps = nullptr;               // [ndesc][N][M][SAT_MAXDIM]
     size_t mcounts_cap = 0, mslots_cap = 0, mmaps_cap = 0;   // elements: rows / rows x M / map bytes
+
+    // pair mode (sat_search_pairs): work items (host copy kept until the next pair search: the upload is
+    // asynchronous), one 64-bit arg-max key and one map per pair, the scores the keys give
+    std::vector<SatPairItem> h_pitems;
+    SatPairItem *d_pitems = nullptr;
+    size_t pitems_cap = 0;
+    unsigned long long *d_pkeys = nullptr;
+    size_t pkeys_cap = 0;
+    int8_t *d_pmaps = nullptr;               // [pairs][SAT_MAXDIM], -1 past n1
+    size_t pmaps_cap = 0;
+    int32_t *d_pscores = nullptr;
+    size_t pscores_cap = 0;
+    // refine (sat_search_refine, sat_topk.hip): the final ranking of the nq x C re-scored candidates
+    unsigned long long *d_rkeys = nullptr, *d_rsorted = nullptr;
+    int32_t *d_rvals = nullptr, *d_rvals_sorted = nullptr, *d_rfirst = nullptr, *d_rmaps = nullptr;
+    sat_hit *d_rhits = nullptr;
+    size_t rkeys_cap = 0, rsorted_cap = 0, rvals_cap = 0, rvals_sorted_cap = 0, rfirst_cap = 0, rmaps_cap = 0, rhits_cap = 0;
 
     // best-k selection (sat_topk.hip): context-owned scratch that only grows; capacities in elements
     unsigned long long *d_keys = nullptr, *d_sorted = nullptr;
@@ -110,3 +127,12 @@ int sat_fail(int code, const char *fmt, ...);
 int sat_matches_launch(sat_ctx *ctx, int lorder, int maxstart, int max_matches, bool maps);
 int sat_matches_collect(sat_ctx *ctx, int max_matches, int32_t *counts, int32_t *scores, int32_t *restarts,
                         int32_t *ssemaps, size_t total, size_t offset);
+
+// Pair mode (sat_capi.hip).  sat_pairs_launch queues both passes of a pair search on the context's stream (pair p:
+// batch query query[p], shard entry entry[p], restarts 0 .. maxstart - 1; maps: also the map pass); the keys land in
+// ctx->d_pkeys, the maps in ctx->d_pmaps.  sat_pairs_collect waits and copies scores (and maps, -1 past the query's
+// order) to the host.
+int sat_pairs_launch(sat_ctx *ctx, int lorder, int maxstart, bool maps, const int32_t *query, const int32_t *entry, int npairs);
+int sat_pairs_collect(sat_ctx *ctx, int npairs, int32_t *scores, int32_t *ssemaps, const int32_t *query);
+// stage 1 of sat_search_refine: a plain search without LSOLN queued on the context's stream
+int sat_launch_plain(sat_ctx *ctx, int lorder, int maxstart);

@@ -18,6 +18,7 @@
 
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -28,6 +29,7 @@
 #include <vector>
 
 #include "sat_ctx.hpp"
+#include "host/sat_gumbel.h"
 #include "host/sat_shard.h"
 
 #define HIP_TRY(expr)                                                                       \
@@ -477,6 +479,111 @@ int sat_multi_search_matches(sat_multi *m, int lorder, int maxstart, int max_mat
     }
     if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return SAT_OK;
+}
+
+int sat_multi_search_refine(sat_multi *m, int lorder, int lsoln, int maxstart, int candidates, int refine_maxstart, int k,
+                            sat_hit *hits, int32_t *ssemaps, int32_t *first_scores, double *wall_ms, double *stage2_ms)
+{
+    if (!m) return sat_fail(SAT_EINVAL, "null context");
+    if (!hits || k < 1) return sat_fail(SAT_EINVAL, "bad top-k arguments");
+    if (candidates < 1) return sat_fail(SAT_EINVAL, "candidates must be >= 1 (got %d)", candidates);
+    if (refine_maxstart < 1) return sat_fail(SAT_EINVAL, "refine_maxstart must be >= 1 (got %d)", refine_maxstart);
+    if (k > candidates) return sat_fail(SAT_EINVAL, "k (%d) exceeds the candidates per query (%d)", k, candidates);
+    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
+    const auto t0 = std::chrono::steady_clock::now();
+    auto bail = [&](int rc) { const std::string msg = sat_last_error(); sync_all(m); return sat_fail(rc, "%s", msg.c_str()); };
+    // stage 1 on every shard, each ranking its own best C
+    for (int g = 0; g < m->ndev; g++) {
+        int rc = sat_search_async(m->ctx[(size_t)g], lorder, 0, maxstart);
+        if (rc != SAT_OK) return bail(rc);
+    }
+    const int c = candidates < m->n_entries ? candidates : m->n_entries;
+    if (k > c) k = c;
+    const int nq = (int)m->ctx[0]->queries.size();
+    std::vector<std::vector<sat_hit>> cand((size_t)m->ndev);
+    std::vector<int> got((size_t)m->ndev, 0);
+    for (int g = 0; g < m->ndev; g++) {
+        cand[(size_t)g].resize((size_t)nq * c);
+        const int r = sat_topk_hits(m->ctx[(size_t)g], c, cand[(size_t)g].data(), nullptr);
+        if (r < 0) return bail(r);
+        got[(size_t)g] = r;
+    }
+    // the global best C of every query (ties in database order: the lower shard first), filed by shard as pairs
+    struct Cand { int g, local, first, second; };
+    std::vector<std::vector<Cand>> per_q((size_t)nq);
+    std::vector<std::vector<int32_t>> pq((size_t)m->ndev), pe((size_t)m->ndev);
+    std::vector<std::vector<std::pair<int, int>>> slot((size_t)m->ndev);     // (query, index in per_q) of each pair
+    for (int q = 0; q < nq; q++) {
+        std::vector<int> head((size_t)m->ndev, 0);
+        for (int r = 0; r < c; r++) {
+            int bg = -1;
+            for (int g = 0; g < m->ndev; g++) {
+                if (head[(size_t)g] >= got[(size_t)g]) continue;
+                if (bg < 0 || cand[(size_t)g][(size_t)q * got[(size_t)g] + head[(size_t)g]].score >
+                                  cand[(size_t)bg][(size_t)q * got[(size_t)bg] + head[(size_t)bg]].score)
+                    bg = g;
+            }
+            const sat_hit &h = cand[(size_t)bg][(size_t)q * got[(size_t)bg] + head[(size_t)bg]];
+            pq[(size_t)bg].push_back(q);
+            pe[(size_t)bg].push_back(h.entry);
+            slot[(size_t)bg].push_back({ q, (int)per_q[(size_t)q].size() });
+            per_q[(size_t)q].push_back({ bg, h.entry, h.score, 0 });
+            head[(size_t)bg]++;
+        }
+    }
+    // stage 2: every shard re-scores its candidates (queued on all, then collected)
+    const auto t2 = std::chrono::steady_clock::now();
+    const bool maps = lsoln && ssemaps;
+    for (int g = 0; g < m->ndev; g++) {
+        const int rc = sat_pairs_launch(m->ctx[(size_t)g], lorder, refine_maxstart, maps, pq[(size_t)g].data(), pe[(size_t)g].data(),
+                                        (int)pq[(size_t)g].size());
+        if (rc != SAT_OK) return bail(rc);
+    }
+    std::vector<std::vector<int32_t>> cmaps((size_t)nq);
+    if (maps)
+        for (int q = 0; q < nq; q++) cmaps[(size_t)q].resize(per_q[(size_t)q].size() * SAT_MAXDIM);
+    for (int g = 0; g < m->ndev; g++) {
+        const size_t np = pq[(size_t)g].size();
+        std::vector<int32_t> sc(np), mp(maps ? np * SAT_MAXDIM : 0);
+        const int rc = sat_pairs_collect(m->ctx[(size_t)g], (int)np, sc.data(), maps ? mp.data() : nullptr, pq[(size_t)g].data());
+        if (rc != SAT_OK) return bail(rc);
+        for (size_t p = 0; p < np; p++) {
+            const auto &sl = slot[(size_t)g][p];
+            per_q[(size_t)sl.first][(size_t)sl.second].second = sc[p];
+            if (maps) memcpy(cmaps[(size_t)sl.first].data() + (size_t)sl.second * SAT_MAXDIM, mp.data() + p * SAT_MAXDIM, sizeof(int32_t) * SAT_MAXDIM);
+        }
+    }
+    if (stage2_ms) *stage2_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count();
+    // the final rows: stage-2 score descending, ties in database order; statistics as the device table holds them
+    for (int q = 0; q < nq; q++) {
+        auto &v = per_q[(size_t)q];
+        std::vector<int> order(v.size());
+        for (size_t i = 0; i < v.size(); i++) order[i] = (int)i;
+        auto gidx = [&](const Cand &x) { return m->begin[(size_t)x.g] + x.local; };
+        std::sort(order.begin(), order.end(), [&](int a, int b) {
+            if (v[(size_t)a].second != v[(size_t)b].second) return v[(size_t)a].second > v[(size_t)b].second;
+            return gidx(v[(size_t)a]) < gidx(v[(size_t)b]);
+        });
+        const int n1 = m->ctx[0]->queries[(size_t)q].n1;
+        for (int r = 0; r < k; r++) {
+            const Cand &x = v[(size_t)order[(size_t)r]];
+            const int n2 = m->ctx[(size_t)x.g]->h_orders[(size_t)x.local];
+            sat_hit h;
+            h.entry = gidx(x);
+            h.score = x.second;
+            h.norm2 = sat_norm2(x.second, n1, n2);
+            int t = (int)h.norm2;
+            t = t < -128 ? -128 : (t > 127 ? 127 : t);
+            h.zscore = sat_z_gumbel_trunc((double)t);
+            h.pvalue = sat_pv_gumbel(h.zscore);
+            hits[(size_t)q * k + r] = h;
+            if (first_scores) first_scores[(size_t)q * k + r] = x.first;
+            if (maps) memcpy(ssemaps + ((size_t)q * k + r) * SAT_MAXDIM, cmaps[(size_t)q].data() + (size_t)order[(size_t)r] * SAT_MAXDIM,
+                             sizeof(int32_t) * SAT_MAXDIM);
+        }
+    }
+    if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return k;
 }
 
 unsigned long long sat_multi_stat_d2h_bytes(const sat_multi *m)

@@ -1,9 +1,10 @@
-// sat_sa_body.inc - the body of the SA kernel (sat_sa_kernel.hpp), included by its two kernels: the plain one
-// (sat_sa_kernel: MATCH = false, the option-specialised and general instantiations) and the match mode's
-// (sat_sa_match_kernel: MATCH = true, options from the arguments).  Kept as ONE text inside each kernel rather
+// sat_sa_body.inc - the body of the SA kernel (sat_sa_kernel.hpp), included by its three kernels: the plain one
+// (sat_sa_kernel: MATCH = PAIRS = false, the option-specialised and general instantiations), the match mode's
+// (sat_sa_match_kernel: MATCH = true, options from the arguments) and the pair mode's (sat_sa_pair_kernel:
+// PAIRS = true).  Kept as ONE text inside each kernel rather
 // than a device function the kernels call: an inlined callee reads the kernel arguments through a reference and
 // came out as different code for the plain kernels.  Not a header: it expects the kernel's own scope (template
-// parameters N1P, M2W, QLDS, OPT, WPL, CELLS, the arguments `a` and `mx`, and MATCH).
+// parameters N1P, M2W, QLDS, OPT, WPL, CELLS, the arguments `a`, `mx` and `px`, MATCH and PAIRS).
     using namespace satk;
     constexpr int M1W = (N1P + 31) / 32;
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -26,10 +27,14 @@
     const int tid = lane_id >> lpc_shift;         // chain index inside the workgroup
     const int part = lane_id & (lpc - 1);
     const int T = nthreads >> lpc_shift;          // chains per workgroup
-    // the last workgroup's spare slots repeat the last entry (same result, written twice)
+    // the last workgroup's spare slots repeat the last entry (same result, written twice).  Pair mode: the slot's
+    // work item names the query (a descriptor of the launch's class), the entry and the restarts; spare slots
+    // repeat the last item (the same key folded in twice)
     const int list_pos = (int)blockIdx.x * a.epw + slot;
-    const int e = a.entry_list[min(list_pos, a.n_list - 1)];
-    const SatQuery Q = a.queries[blockIdx.y];
+    SatPairItem pit{};
+    if constexpr (PAIRS) pit = px.items[min(list_pos, a.n_list - 1)];
+    const int e = PAIRS ? pit.entry : a.entry_list[min(list_pos, a.n_list - 1)];
+    const SatQuery Q = PAIRS ? a.queries[pit.desc] : a.queries[blockIdx.y];
     const int n1 = Q.n1;
     const int n2 = a.orders[e];
     const int n2p = n2 + 1;
@@ -286,6 +291,10 @@
     size_t mrow = 0;
     uint32_t *mrec = nullptr;
     int r_begin = tid, r_end = a.maxstart;
+    if constexpr (PAIRS) {
+        r_begin = pit.r0 + tid;
+        r_end = pit.r1;
+    }
     int rbest = SAT_K_NO_SCORE;
     Bits<M2W> rset = bits_zero<M2W>();
     if constexpr (MATCH) {
@@ -973,10 +982,16 @@
     for (int w = 1; w < nwaves; w++) win = *red_key(w) > win ? *red_key(w) : win;
 
     const uint32_t win_restart = 0xFFFFFFFFu - (uint32_t)(win & 0xFFFFFFFFu);
-    if (lane_id == 0) Q.scores[e] = (int)(uint32_t)(win >> 32) - 0x40000000;
+    // pair mode: the item's key folds into its pair's (restart ranges of one pair in any order, any workgroups);
+    // its map pass re-runs the pair's winning restart alone and writes only the map
+    if constexpr (PAIRS) {
+        if (lane_id == 0 && !lsoln) atomicMax(px.keys + pit.pair, win);
+    } else {
+        if (lane_id == 0) Q.scores[e] = (int)(uint32_t)(win >> 32) - 0x40000000;
+    }
     if (lsoln && any && part == 0 && best_restart == win_restart &&
         ((((unsigned long long)(uint32_t)(best + 0x40000000)) << 32) | (0xFFFFFFFFu - best_restart)) == win) {
-        int8_t *out = Q.ssemaps + (size_t)e * n1;
+        int8_t *out = PAIRS ? px.maps + (size_t)pit.pair * SAT_K_MAXDIM : Q.ssemaps + (size_t)e * n1;
         for (int i = 0; i < n1; i++) {
             int j = bmap_b[bmap_byte_addr(i)];
             out[i] = (int8_t)(j == NULLJ ? -1 : j);

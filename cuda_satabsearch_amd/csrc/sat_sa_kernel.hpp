@@ -149,6 +149,7 @@
 #define SAT_FS_TEAMS 1
 #endif
 #define SAT_K_MAXITER 100
+#define SAT_K_MAXDIM 111              // SAT_MAXDIM of satabsearch.h: the pitch of a pair's map
 #define SAT_FS_UNROLL 2               // pairs per lane and round of the full score of an initial map
 #define SAT_K_STEP_BLOCK0 32          // Philox block of SA step 0 (oracle/sa_oracle.h)
 #define SAT_K_EPS 1.1e-7              // K.cu:67
@@ -217,6 +218,24 @@ struct SatMatchArgs {
     int32_t        *scores;       // [ndesc][N][M]        0 past the count
     int32_t        *restarts;     // [ndesc][N][M]        -1 past the count
     int8_t         *maps;         // [ndesc][N][M][map_pitch] replay pass: the picked restarts' own-best maps
+};
+
+// Pair mode (sat_search_pairs, sat_sa_pair_kernel; DESIGN.md "Re-scoring candidates").  A work item is one
+// (query descriptor, entry) pair and a range [r0, r1) of its restarts; the launch's entry slots take items in
+// turn (the slot's n_list bounds the table).  Restart r of a pair is the same Philox stream wherever it runs,
+// so the items of one pair fold their arg-max keys (score, ~restart) into keys[pair] by atomicMax and the
+// largest is exactly sat_search's.  The map pass re-runs each pair's winning restart as one item with LSOLN.
+struct SatPairItem {
+    int32_t pair;                 // output index
+    int32_t desc;                 // descriptor index (into SatKernelArgs::queries) of the query
+    int32_t entry;                // index in the resident shard
+    int32_t r0, r1;               // restarts r0 .. r1 - 1
+    int32_t pad_[3];
+};
+struct SatPairArgs {
+    const SatPairItem   *items;   // [n_list]
+    unsigned long long  *keys;    // [pairs] zeroed before the score pass
+    int8_t              *maps;    // [pairs][SAT_K_MAXDIM] map pass: the winning restart's map (bytes past n1 untouched)
 };
 
 namespace satk {
@@ -604,13 +623,15 @@ __host__ __device__ inline size_t lds_bytes(int n1, int n1p, int n2, int chains,
 // WPL: map words per lane in the compacted rounds (satk::compaction_shape) when every query of
 // the launch has the same; 0 = read it from the query (a four-way switch per step).
 // CELLS: the launch's cell layout (SAT_CELLS_*, satk::cell_layout of its largest entry).
-// MATCH: the match mode (SatMatchArgs), only in sat_sa_match_kernel; the plain kernels compile without any of it.
+// MATCH: the match mode (SatMatchArgs), only in sat_sa_match_kernel; PAIRS: the pair mode (SatPairArgs), only in
+// sat_sa_pair_kernel; the plain kernels compile without any of it.
 template <int N1P, int M2W, bool QLDS, int OPT, int WPL, int CELLS>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu((OPT < 0 || OPT >= 4) ? 4 : SAT_FAST_WAVES)))
 sat_sa_kernel(const SatKernelArgs a)
 {
-    constexpr bool MATCH = false;
+    constexpr bool MATCH = false, PAIRS = false;
     const SatMatchArgs mx{};
+    const SatPairArgs px{};
 #include "sat_sa_body.inc"
 }
 
@@ -619,7 +640,21 @@ template <int N1P, int M2W, bool QLDS, int CELLS>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4)))
 sat_sa_match_kernel(const SatKernelArgs a, const SatMatchArgs mx)
 {
-    constexpr bool MATCH = true;
+    constexpr bool MATCH = true, PAIRS = false;
     constexpr int OPT = -1, WPL = 0;
+    const SatPairArgs px{};
+#include "sat_sa_body.inc"
+}
+
+// The pair mode's kernel (SatPairArgs): grid.x covers the item table, grid.y is 1.  OPT as in sat_sa_kernel, with
+// LSOLN off in the option-specialised instantiations (the map pass runs the general one); map words per lane read
+// per query.
+template <int N1P, int M2W, bool QLDS, int OPT, int CELLS>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu((OPT < 0 || OPT >= 4) ? 4 : SAT_FAST_WAVES)))
+sat_sa_pair_kernel(const SatKernelArgs a, const SatPairArgs px)
+{
+    constexpr bool MATCH = false, PAIRS = true;
+    constexpr int WPL = 0;
+    const SatMatchArgs mx{};
 #include "sat_sa_body.inc"
 }

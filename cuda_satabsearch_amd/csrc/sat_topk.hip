@@ -48,6 +48,21 @@ struct HitQuery {
     const int8_t *ssemaps;     // this query's [N][n1] maps, or null
 };
 
+// the row of (entry, score) for a query of n1 SSEs against an entry of n2
+__device__ __forceinline__ sat_hit hit_row(int32_t entry, int32_t score, int n1, int n2, const double *ztab, const double *ptab)
+{
+    const double norm2 = 2.0 * score / ((double)(n1 + n2));            // sat_norm2
+    int x = (int)norm2;                                                // the reference's double -> int
+    x = x < -128 ? -128 : (x > 127 ? 127 : x);                         // |norm2| <= 110 for every legal score
+    sat_hit h;
+    h.entry = entry;
+    h.score = score;
+    h.norm2 = norm2;
+    h.zscore = ztab[x + 128];
+    h.pvalue = ptab[x + 128];
+    return h;
+}
+
 // one thread per (query, rank): decode the key, look the statistics up, gather the map
 __global__ void finish_hits(const unsigned long long *sorted, int n, int k, int nq, const int32_t *orders,
                             const HitQuery *queries, const double *ztab, const double *ptab,
@@ -60,16 +75,7 @@ __global__ void finish_hits(const unsigned long long *sorted, int n, int k, int 
     const int32_t entry = (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFu));
     const int32_t score = (int32_t)(uint32_t)(key >> 32) - 0x40000000;
     const int n1 = queries[q].n1, n2 = orders[entry];
-    const double norm2 = 2.0 * score / ((double)(n1 + n2));            // sat_norm2
-    int x = (int)norm2;                                                // the reference's double -> int
-    x = x < -128 ? -128 : (x > 127 ? 127 : x);                         // |norm2| <= 110 for every legal score
-    sat_hit h;
-    h.entry = entry;
-    h.score = score;
-    h.norm2 = norm2;
-    h.zscore = ztab[x + 128];
-    h.pvalue = ptab[x + 128];
-    hits[t] = h;
+    hits[t] = hit_row(entry, score, n1, n2, ztab, ptab);
     if (maps) {
         int32_t *out = maps + (size_t)t * SAT_MAXDIM;
         const int8_t *src = queries[q].ssemaps ? queries[q].ssemaps + (size_t)entry * n1 : nullptr;
@@ -143,6 +149,38 @@ int select_hits(sat_ctx *ctx, int q0, int nq, int k, bool want_maps, size_t out_
     return SAT_OK;
 }
 
+// refine: pair p = q * C + c is candidate c of query q (stage-1 row p of ctx->d_hits); its final key is the
+// stage-2 score over the inverted entry index, as pack_keys builds them, its value the pair
+__global__ void pack_refined(const unsigned long long *pkeys, const sat_hit *cand, int npairs, unsigned long long *keys, int32_t *vals)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npairs) return;
+    keys[p] = (pkeys[p] & 0xFFFFFFFF00000000ull) | (0xFFFFFFFFu - (uint32_t)cand[p].entry);
+    vals[p] = p;
+}
+
+// one thread per (query, rank) of the refined rows: the statistics of the stage-2 score, the stage-1 score and map
+__global__ void finish_refined(const unsigned long long *sorted, const int32_t *vals, int c, int k, int nq, const int32_t *orders,
+                               const HitQuery *queries, const double *ztab, const double *ptab, const sat_hit *cand,
+                               const int8_t *pmaps, sat_hit *hits, int32_t *first, int32_t *maps)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nq * k) return;
+    const int q = t / k, r = t - q * k;
+    const unsigned long long key = sorted[(size_t)q * c + r];
+    const int p = vals[(size_t)q * c + r];
+    const int32_t entry = (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFu));
+    const int32_t score = (int32_t)(uint32_t)(key >> 32) - 0x40000000;
+    const int n1 = queries[q].n1;
+    hits[t] = hit_row(entry, score, n1, orders[entry], ztab, ptab);
+    first[t] = cand[p].score;
+    if (maps) {
+        int32_t *out = maps + (size_t)t * SAT_MAXDIM;
+        const int8_t *src = pmaps + (size_t)p * SAT_MAXDIM;
+        for (int i = 0; i < SAT_MAXDIM; i++) out[i] = i < n1 ? (int32_t)src[i] : -1;
+    }
+}
+
 int check_searched(sat_ctx *ctx)
 {
     if (!ctx) return sat_fail(SAT_EINVAL, "null context");
@@ -191,5 +229,89 @@ extern "C" int sat_topk_hits(sat_ctx *ctx, int k, sat_hit *hits, int32_t *ssemap
         HIP_TRY(hipMemcpy(ssemaps, ctx->d_hit_maps, (size_t)nq * k * SAT_MAXDIM * sizeof(int32_t), hipMemcpyDeviceToHost));
         ctx->d2h_bytes += (size_t)nq * k * SAT_MAXDIM * sizeof(int32_t);
     }
+    return k;
+}
+
+extern "C" int sat_search_refine(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int candidates, int refine_maxstart,
+                                 int k, sat_hit *hits, int32_t *ssemaps, int32_t *first_scores)
+{
+    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
+    if (!hits || k < 1) return sat_fail(SAT_EINVAL, "bad top-k arguments");
+    if (candidates < 1) return sat_fail(SAT_EINVAL, "candidates must be >= 1 (got %d)", candidates);
+    if (refine_maxstart < 1) return sat_fail(SAT_EINVAL, "refine_maxstart must be >= 1 (got %d)", refine_maxstart);
+    if (k > candidates) return sat_fail(SAT_EINVAL, "k (%d) exceeds the candidates per query (%d)", k, candidates);
+    HIP_TRY(hipSetDevice(ctx->device));
+    // stage 1: the plain search at maxstart, without LSOLN
+    int rc = sat_launch_plain(ctx, lorder, maxstart);
+    if (rc != SAT_OK) return rc;
+    const std::string stage1_info = ctx->last_launch_info;
+    const int n = ctx->n_entries, nq = (int)ctx->queries.size();
+    const int c = candidates < n ? candidates : n;
+    if (k > c) k = c;
+    if ((long long)nq * c > 0x7FFFFFFFll) return sat_fail(SAT_EINVAL, "queries x candidates exceed 2^31 - 1");
+    const int npairs = nq * c;
+    // the best c entries of every query, ranked on the device (rows stay there); only their indices come back
+    const int per_chunk = (int)(0x7FFFFFFFll / n) < 1 ? 1 : (int)(0x7FFFFFFFll / n);
+    for (int q0 = 0; q0 < nq; q0 += per_chunk) {
+        const int nqc = nq - q0 < per_chunk ? nq - q0 : per_chunk;
+        if ((rc = select_hits(ctx, q0, nqc, c, false, (size_t)q0 * c, (size_t)npairs)) != SAT_OK) return rc;
+    }
+    std::vector<int32_t> query((size_t)npairs), entry((size_t)npairs);
+    HIP_TRY(hipMemcpy2D(entry.data(), sizeof(int32_t), ctx->d_hits, sizeof(sat_hit), sizeof(int32_t), (size_t)npairs,
+                        hipMemcpyDeviceToHost));
+    ctx->d2h_bytes += (size_t)npairs * sizeof(int32_t);
+    for (int p = 0; p < npairs; p++) query[(size_t)p] = p / c;
+    // stage 2: the candidates at refine_maxstart (and their maps)
+    const bool maps = lsoln && ssemaps;
+    if ((rc = sat_pairs_launch(ctx, lorder, refine_maxstart, maps, query.data(), entry.data(), npairs)) != SAT_OK) return rc;
+    const std::string stage2_info = ctx->last_launch_info;
+    // the final ranking: segments of c keys, one per query
+    if ((rc = grow(ctx->d_rkeys, ctx->rkeys_cap, (size_t)npairs)) != SAT_OK) return rc;
+    if ((rc = grow(ctx->d_rsorted, ctx->rsorted_cap, (size_t)npairs)) != SAT_OK) return rc;
+    if ((rc = grow(ctx->d_rvals, ctx->rvals_cap, (size_t)npairs)) != SAT_OK) return rc;
+    if ((rc = grow(ctx->d_rvals_sorted, ctx->rvals_sorted_cap, (size_t)npairs)) != SAT_OK) return rc;
+    if ((rc = grow(ctx->d_rhits, ctx->rhits_cap, (size_t)nq * k)) != SAT_OK) return rc;
+    if ((rc = grow(ctx->d_rfirst, ctx->rfirst_cap, (size_t)nq * k)) != SAT_OK) return rc;
+    if (maps && (rc = grow(ctx->d_rmaps, ctx->rmaps_cap, (size_t)nq * k * SAT_MAXDIM)) != SAT_OK) return rc;
+    if ((rc = grow(ctx->d_seg, ctx->seg_cap, (size_t)nq + 1)) != SAT_OK) return rc;
+    if ((rc = grow(ctx->d_hitq, ctx->hitq_cap, (size_t)nq * sizeof(HitQuery))) != SAT_OK) return rc;
+    std::vector<int> seg((size_t)nq + 1);
+    std::vector<HitQuery> hq((size_t)nq);
+    for (int q = 0; q <= nq; q++) seg[(size_t)q] = q * c;
+    for (int q = 0; q < nq; q++) {
+        hq[(size_t)q].n1 = ctx->queries[(size_t)q].n1;
+        hq[(size_t)q].pad_ = 0;
+        hq[(size_t)q].ssemaps = nullptr;
+    }
+    HIP_TRY(hipMemcpyAsync(ctx->d_seg, seg.data(), seg.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->d_hitq, hq.data(), hq.size() * sizeof(HitQuery), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(pack_refined, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_pkeys, ctx->d_hits,
+                       npairs, ctx->d_rkeys, ctx->d_rvals);
+    HIP_TRY(hipGetLastError());
+    size_t temp_bytes = 0;
+    HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortPairsDescending(nullptr, temp_bytes, ctx->d_rkeys, ctx->d_rsorted, ctx->d_rvals,
+                                                                 ctx->d_rvals_sorted, npairs, nq, ctx->d_seg, ctx->d_seg + 1, 0, 64,
+                                                                 ctx->stream));
+    if ((rc = grow(ctx->d_sort_temp, ctx->sort_temp_cap, temp_bytes ? temp_bytes : 1)) != SAT_OK) return rc;
+    HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortPairsDescending(ctx->d_sort_temp, temp_bytes, ctx->d_rkeys, ctx->d_rsorted, ctx->d_rvals,
+                                                                 ctx->d_rvals_sorted, npairs, nq, ctx->d_seg, ctx->d_seg + 1, 0, 64,
+                                                                 ctx->stream));
+    hipLaunchKernelGGL(finish_refined, dim3((unsigned)((nq * k + 127) / 128)), dim3(128), 0, ctx->stream, ctx->d_rsorted,
+                       ctx->d_rvals_sorted, c, k, nq, ctx->d_orders, reinterpret_cast<const HitQuery *>(ctx->d_hitq), ctx->d_gumbel_z,
+                       ctx->d_gumbel_p, ctx->d_hits, ctx->d_pmaps, ctx->d_rhits, ctx->d_rfirst, maps ? ctx->d_rmaps : nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const size_t rows = (size_t)nq * k;
+    HIP_TRY(hipMemcpy(hits, ctx->d_rhits, rows * sizeof(sat_hit), hipMemcpyDeviceToHost));
+    ctx->d2h_bytes += rows * sizeof(sat_hit);
+    if (first_scores) {
+        HIP_TRY(hipMemcpy(first_scores, ctx->d_rfirst, rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+        ctx->d2h_bytes += rows * sizeof(int32_t);
+    }
+    if (maps) {
+        HIP_TRY(hipMemcpy(ssemaps, ctx->d_rmaps, rows * SAT_MAXDIM * sizeof(int32_t), hipMemcpyDeviceToHost));
+        ctx->d2h_bytes += rows * SAT_MAXDIM * sizeof(int32_t);
+    }
+    ctx->last_launch_info = "stage 1: " + stage1_info + " || stage 2: " + stage2_info;
     return k;
 }

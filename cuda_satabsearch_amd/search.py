@@ -33,6 +33,25 @@ def _search_matches(obj, fn, handle, max_matches, lorder, maxstart, maps):
     return counts, scores, restarts, (ssemaps[..., :obj.n1max] if maps else None), ms.value
 
 
+# struct sat_hit (include/satabsearch.h) as a numpy record: the rows of topk_hits, search_topk and search_refine
+_HIT_DTYPE = np.dtype([("entry", np.int32), ("score", np.int32), ("norm2", np.float64), ("zscore", np.float64),
+                       ("pvalue", np.float64)], align=True)
+assert _HIT_DTYPE.itemsize == C.sizeof(_native.Hit)
+
+
+def _search_refine(obj, call, k, candidates, refine_maxstart, lsoln):
+    """shared by Searcher / MultiSearcher.search_refine: `call(hits, maps, first)` runs the C entry point"""
+    nq = getattr(obj, "n_queries", 1)
+    kk = max(1, min(int(k), int(candidates), obj.n_entries))
+    hits = np.zeros((nq, kk), _HIT_DTYPE)
+    maps = np.full((nq, kk, MAXDIM), -1, np.int32) if lsoln else None
+    first = np.zeros((nq, kk), np.int32)
+    n = call(hits.ctypes.data, maps.ctypes.data if lsoln else None, first.ctypes.data)
+    if n < 0:
+        obj._check(n)
+    return hits, maps, first
+
+
 class Searcher:
     """One HIP device, one resident database shard, one current query."""
 
@@ -181,6 +200,30 @@ class Searcher:
         query order.  Match 0 is search()'s score and LSOLN map; slots past the count hold 0, -1, all -1."""
         return _search_matches(self, self._lib.sat_search_matches, self._ctx, max_matches, lorder, maxstart, maps)
 
+    def search_pairs(self, queries, entries, lorder=True, lsoln=False, maxstart=DEFAULT_MAXSTART):
+        """Scores of chosen (query, entry) pairs only (sat_search_pairs): queries[p] indexes the current batch,
+        entries[p] the resident shard.  Returns (scores int32[P], maps int32[P, 111] or None): exactly what
+        search() gives for those rows at the same maxstart."""
+        q = np.ascontiguousarray(queries, dtype=np.int32).ravel()
+        e = np.ascontiguousarray(entries, dtype=np.int32).ravel()
+        if q.shape != e.shape:
+            raise ValueError("queries and entries differ in length")
+        scores = np.zeros(len(q), np.int32)
+        maps = np.full((len(q), MAXDIM), -1, np.int32) if lsoln else None
+        ms = C.c_double(0.0)
+        self._check(self._lib.sat_search_pairs(self._ctx, int(bool(lorder)), int(bool(lsoln)), int(maxstart), len(q),
+                                               q.ctypes.data, e.ctypes.data, scores.ctypes.data,
+                                               maps.ctypes.data if lsoln else None, C.byref(ms)))
+        return scores, maps
+
+    def search_refine(self, k, candidates, refine_maxstart, lorder=True, lsoln=False, maxstart=DEFAULT_MAXSTART):
+        """Two-stage search (sat_search_refine): every entry at maxstart, then each query's best `candidates`
+        at refine_maxstart.  Returns (hits [nq, k'] shaped like topk_hits with stage-2 scores, maps int32[nq, k', 111]
+        or None, stage-1 scores int32[nq, k']), k' = min(k, candidates, N)."""
+        return _search_refine(self, lambda h, m, f: self._lib.sat_search_refine(
+            self._ctx, int(bool(lorder)), int(bool(lsoln)), int(maxstart), int(candidates), int(refine_maxstart), int(k),
+            h, m, f), k, candidates, refine_maxstart, lsoln)
+
     def use_stream(self, stream_handle):
         """Queue all further work on the caller's HIP stream (0 / None = default stream),
         e.g. torch.cuda.current_stream().cuda_stream."""
@@ -221,10 +264,7 @@ class Searcher:
         solution maps int32[nq, k', 111] when lsoln)."""
         nq = getattr(self, "n_queries", 1)
         k = min(int(k), self.n_entries)
-        dt = np.dtype([("entry", np.int32), ("score", np.int32), ("norm2", np.float64), ("zscore", np.float64),
-                       ("pvalue", np.float64)], align=True)
-        assert dt.itemsize == C.sizeof(_native.Hit)
-        hits = np.zeros((nq, k), dt)
+        hits = np.zeros((nq, k), _HIT_DTYPE)
         maps = np.full((nq, k, MAXDIM), -1, np.int32) if lsoln else None
         n = self._lib.sat_topk_hits(self._ctx, k, hits.ctypes.data, maps.ctypes.data if lsoln else None)
         if n < 0:
@@ -351,14 +391,19 @@ class MultiSearcher:
 
     def search_topk(self, k, lorder=True, lsoln=False, maxstart=DEFAULT_MAXSTART):
         k = min(int(k), self.n_entries)
-        dt = np.dtype([("entry", np.int32), ("score", np.int32), ("norm2", np.float64), ("zscore", np.float64),
-                       ("pvalue", np.float64)], align=True)
-        hits = np.zeros((self.n_queries, k), dt)
+        hits = np.zeros((self.n_queries, k), _HIT_DTYPE)
         maps = np.full((self.n_queries, k, MAXDIM), -1, np.int32) if lsoln else None
         ms = C.c_double(0.0)
         self._check(self._lib.sat_multi_search_topk(self._m, int(bool(lorder)), int(bool(lsoln)), int(maxstart), k,
                                                     hits.ctypes.data, maps.ctypes.data if lsoln else None, C.byref(ms)))
         return hits, maps, ms.value
+
+    def search_refine(self, k, candidates, refine_maxstart, lorder=True, lsoln=False, maxstart=DEFAULT_MAXSTART):
+        """Searcher.search_refine over every shard (sat_multi_search_refine); hits name entries of the whole database."""
+        ms = C.c_double(0.0)
+        return _search_refine(self, lambda h, m, f: self._lib.sat_multi_search_refine(
+            self._m, int(bool(lorder)), int(bool(lsoln)), int(maxstart), int(candidates), int(refine_maxstart), int(k),
+            h, m, f, C.byref(ms), None), k, candidates, refine_maxstart, lsoln)
 
     def d2h_bytes(self):
         return int(self._lib.sat_multi_stat_d2h_bytes(self._m))

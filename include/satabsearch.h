@@ -182,6 +182,20 @@ int sat_search_matches(sat_ctx *ctx, int lorder, int maxstart, int max_matches,
                        int32_t *counts, int32_t *scores, int32_t *restarts, int32_t *ssemaps,
                        double *kernel_ms);
 /*
+ * Pair search: one score per (query, entry) pair instead of the whole database.  query[p] is an index into the
+ * current batch (sat_queries_set), entry[p] an index into the resident shard; pairs may come in any order, repeat,
+ * and mix query size classes and entry sizes.  scores[p] is exactly what sat_search(lorder, lsoln, maxstart) writes
+ * for row query[p], entry entry[p]; with lsoln, ssemaps[p * SAT_MAXDIM ..] is exactly that row's map (-1 past the
+ * query's order).  Restart r of a pair is the same random stream wherever it runs, so the pair's restarts are cut
+ * into ranges that run in parallel (SAT_EXP_REFINE_SPLIT in satabsearch_debug.h; results do not depend on the cut)
+ * and their arg-max keys (score, -restart) are combined.  With lsoln the winning restart runs once more for its
+ * map.  npairs == 0 does nothing.  kernel_ms as sat_search.  Leaves the buffers of sat_results / sat_topk /
+ * sat_topk_hits untouched.
+ */
+int sat_search_pairs(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int npairs, const int32_t *query,
+                     const int32_t *entry, int32_t *scores, int32_t *ssemaps, double *kernel_ms);
+
+/*
  * Queue all further work of this context on the caller's stream (`hip_stream` is a
  * hipStream_t passed as void*; NULL selects the device's default stream).  A context
  * starts on a private non-blocking stream; sat_use_own_stream() goes back to it.
@@ -255,13 +269,33 @@ typedef struct sat_hit {
  */
 int sat_topk_hits(sat_ctx *ctx, int k, sat_hit *hits, int32_t *ssemaps);
 
+/*
+ * Refine: a cheap search of every entry, then a long search of each query's best candidates only.
+ *   1. stage 1: sat_search(lorder, lsoln = 0, maxstart); the candidates of query q are its best C entries in
+ *      sat_topk_hits order (descending score, ties in database order), C = min(candidates, n_entries)
+ *   2. stage 2: sat_search_pairs over those candidates with refine_maxstart restarts (and lsoln)
+ *   3. hits[q * K + r], K = min(k, C): the best K candidates of query q by stage-2 score, ties in database
+ *      order, with norm2 / z / p of the stage-2 score from the same table as sat_topk_hits
+ * ssemaps (may be NULL; written when lsoln): [n_queries * K * SAT_MAXDIM] the stage-2 maps of those rows.
+ * first_scores (may be NULL): [n_queries * K] each row's stage-1 score.  Returns K or a negative SAT_E* code;
+ * k < 1, candidates < 1, refine_maxstart < 1 and k > candidates are SAT_EINVAL.  Every stage-2 score is exactly
+ * sat_search's at refine_maxstart, so refine_maxstart == maxstart gives exactly sat_topk_hits' rows.  Only the
+ * K rows and the n_queries * C candidate indices are copied to the host.  The buffers of sat_results / sat_topk /
+ * sat_topk_hits hold the stage-1 search afterwards.
+ */
+int sat_search_refine(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int candidates, int refine_maxstart,
+                      int k, sat_hit *hits, int32_t *ssemaps, int32_t *first_scores);
+
+
 /* Bytes this context's result calls (sat_results, sat_search, sat_topk, sat_topk_hits) have copied
  * from the device to the host since it was created (diagnostics: the best-k path moves O(k) rows). */
 unsigned long long sat_stat_d2h_bytes(const sat_ctx *ctx);
 
 /* Diagnostics: the kernel instantiations (template arguments as rocprofv3 prints them), grids, block
  * sizes and LDS bytes of the launches of this context's last search, "; "-separated.  After sat_search_matches:
- * "record pass: <launches>", followed by " | replay pass: <launches>" when maps were asked for. */
+ * "record pass: <launches>", followed by " | replay pass: <launches>" when maps were asked for.  After
+ * sat_search_pairs: "score pass (R restarts, S per item): <launches>", followed by " | map pass: <launches>" with
+ * lsoln; after sat_search_refine: "stage 1: <launches> || stage 2: <the pair search's>". */
 const char *sat_last_launch_info(const sat_ctx *ctx);
 
 /*
@@ -323,6 +357,14 @@ int sat_multi_search_topk(sat_multi *m, int lorder, int lsoln, int maxstart, int
  * Leaves every shard's context as sat_search_matches leaves it. */
 int sat_multi_search_matches(sat_multi *m, int lorder, int maxstart, int max_matches, int32_t *counts,
                              int32_t *scores, int32_t *restarts, int32_t *ssemaps, double *wall_ms);
+/* sat_search_refine over every shard, exactly what one context holding the whole database returns: each shard
+ * ranks its own best C (as sat_multi_search_topk), the host merges them into the global best C of every query,
+ * each shard re-scores the candidates in its range, the host merges the final rows (hits[].entry is the index in
+ * the whole database).  wall_ms as sat_multi_search; stage2_ms (may be NULL) the part of it from the merged
+ * candidates to the re-scored rows on the host.  Leaves every shard's context holding its stage-1 search. */
+int sat_multi_search_refine(sat_multi *m, int lorder, int lsoln, int maxstart, int candidates, int refine_maxstart,
+                            int k, sat_hit *hits, int32_t *ssemaps, int32_t *first_scores, double *wall_ms,
+                            double *stage2_ms);
 unsigned long long sat_multi_stat_d2h_bytes(const sat_multi *m);
 
 /*
