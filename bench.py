@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - db-structure scorings/sec of the SA tableau search on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json configs[3] / north_star target shape): one 32-SSE synthetic query against a
@@ -29,9 +29,17 @@ the whole database would exceed 64 MB.
 
 Prints ONE JSON line (rank 0).  `value` = (entries of the whole database x K) / max-over-ranks time.
 Extra objects: `roofline` (HBM-nominal, see DESIGN.md section 4: the path is VALU/LDS bound, the HBM
-fraction is reported because the contract asks for it) and, at N = 1, `cpu_baseline` (the oracle's
-restatement of the reference's host path timed on this box's CPU on a bounded sample; the reference's
-own objects, when oracle/_ref travelled, under `cpu_baseline_reference`).
+fraction is reported because the contract asks for it; from the timed steps' own kernel events and the
+committed counter file, no run of its own).
+
+A plain run does only what `value` needs: inputs, upload, warm-up, the K timed steps, --dump-outputs, the
+line.  `--full` adds everything that takes work of its own, before or after the timed steps as it always
+did: `oracle_sample_ok` (16 entries of the whole database scored again by the CPU oracle; exit code 1 on a
+difference), at N = 1 the overlapped upload + search probe, `other_regimes` (all-hit / planted-query side
+rates) and `cpu_baseline` (the oracle's restatement of the reference's host path timed on this box's CPU
+on a bounded sample; the reference's own objects, when oracle/_ref is there, under
+`cpu_baseline_reference`), at N > 1 `gather_ms_alone` and the check of rank 0's gathered shard.
+`--no-upload-probe`, `--no-regimes` and `--no-cpu-baseline` drop single legs of a --full run.
 """
 import argparse
 import json
@@ -244,10 +252,12 @@ def parse_args(argv):
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
     ap.add_argument("--entries", type=int, default=PER_GPU_ENTRIES, help="weak scaling: db entries per GPU")
     ap.add_argument("--total", type=int, default=STRONG_TOTAL, help="strong scaling: entries of the whole database")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-upload-probe", action="store_true", help="skip the one-off upload + first search measurement "
-                    "(profiler runs: its piece-wise launches would be averaged into the kernel's counters)")
-    ap.add_argument("--no-regimes", action="store_true", help="skip the all-hit / planted-query side rates")
+    ap.add_argument("--full", action="store_true", help="also the oracle spot check, the upload probe, the side regimes, "
+                    "the CPU baselines and the gather alone (a plain run times the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-upload-probe", action="store_true", help="--full without the one-off upload + first search "
+                    "measurement (profiler runs: its piece-wise launches would be averaged into the kernel's counters)")
+    ap.add_argument("--no-regimes", action="store_true", help="--full without the all-hit / planted-query side rates")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse "
                     "the N > 1 flow on a box with fewer GPUs than ranks)")
     ap.add_argument("--all-ranks-on-device0", action="store_true", help="rehearsal only: every rank uses GPU 0")
@@ -310,14 +320,16 @@ def run_single_process(args):
             scores, _, ms = m.search(True, False, MAXSTART)
             wall.append(ms)
         elapsed = time.perf_counter() - t0
-        ok, sample = oracle_sample_ok(scores[0], total, q)
+        ok = True
         out = result_header(args, ndev, total, elapsed)
         out["config"]["parallelism"] = "db-shard x%d, one process (sat_multi_*, gather: %s)" % (ndev, m.gather_kind)
         out["ranks_seen"] = ndev
         out["shards"] = [int(b) for b in m.shards()]
         out["search_wall_ms_avg"] = float(np.mean(wall))
-        out["oracle_sample_ok"] = bool(ok)
-        out["oracle_sample"] = sample
+        if args.full:
+            ok, sample = oracle_sample_ok(scores[0], total, q)
+            out["oracle_sample_ok"] = bool(ok)
+            out["oracle_sample"] = sample
         out["note"] = "value includes the device-0 -> host copy of the rows and their re-ordering (sat_multi_search returns host rows)"
         if args.dump_outputs:
             out["dump_outputs"] = dump_outputs(args.dump_outputs, scores[0])
@@ -403,7 +415,7 @@ def main():
     # (sat_db_upload_search: each piece of the shard is searched while the next one is copied), on a
     # context of its own; wall time of the call, which returns when the scores are complete on the GPU
     overlapped_ms = None
-    if world == 1 and not args.no_upload_probe:
+    if args.full and world == 1 and not args.no_upload_probe:
         with sat.Searcher(local_rank) as one_shot:
             one_shot.set_query(qt, qd, qtypes, 0)
             one_shot.upload_search(db, True, False, MAXSTART, db_ordinal=np.arange(n_local))     # first call of the process
@@ -467,22 +479,24 @@ def main():
         dist.all_gather(every, mine)
         kernel_ms_by_rank = [float(x.item()) for x in every]
         ranks_seen = dist.get_world_size()
-        # the gather on its own (no search to hide behind): barrier, G gathers, device sync
-        fence()
-        tg = time.perf_counter()
-        for _ in range(10):
-            s_ = gather.start(scores_dev)
-            gather.wait(s_)
-        torch.cuda.synchronize()
-        gather_ms = (time.perf_counter() - tg) / 10 * 1e3
-        rows = gather.rows(s_)
+        if args.full:
+            # the gather on its own (no search to hide behind): barrier, G gathers, device sync
+            fence()
+            tg = time.perf_counter()
+            for _ in range(10):
+                slot = gather.start(scores_dev)
+                gather.wait(slot)
+            torch.cuda.synchronize()
+            gather_ms = (time.perf_counter() - tg) / 10 * 1e3
+        rows = gather.rows(slot)                           # the scores of the last timed search
         if rank == 0:
             whole = rows.cpu().numpy()
             gathered_len = int(whole.shape[0])
-            # the gathered array is the whole database in file order: shard 0 must be rank 0's own scores
             assert gathered_len == total
-            own, _ = searcher.results()                    # rank 0's shard, copied by the library itself
-            assert np.array_equal(whole[:n_local], own)
+            if args.full:
+                # the gathered array is the whole database in file order: shard 0 must be rank 0's own scores
+                own, _ = searcher.results()                # rank 0's shard, copied by the library itself
+                assert np.array_equal(whole[:n_local], own)
     elif rank == 0:
         whole, _ = searcher.results()
     if rank == 0 and overlapped_ms is not None:
@@ -491,7 +505,7 @@ def main():
     rc = 0
     if rank == 0:
         out = result_header(args, world, total, elapsed)
-        ok, sample = oracle_sample_ok(whole, total, q)
+        ok = True
         abytes = algorithmic_bytes_per_scoring(ORDER) * n_local
         achieved = abytes / (kavg_ms * 1e-3) / 1e9
         kernel_info = searcher.last_launch_info()
@@ -501,7 +515,6 @@ def main():
             "ranks_seen": ranks_seen, "gathered_scores": gathered_len,
             "kernel_ms_by_rank": {"max": max(kernel_ms_by_rank), "min": min(kernel_ms_by_rank), "all": kernel_ms_by_rank},
             "gather_ms_alone": gather_ms,
-            "oracle_sample_ok": bool(ok), "oracle_sample": sample,
             # the boundary takes host buffers: one-off H->D of the shard, and the rate a single
             # query would see with that copy included (never `value`)
             "h2d_upload_ms": upload_ms,
@@ -525,12 +538,16 @@ def main():
                 "note": "VALU wave-instructions per launch from the committed rocprofv3 PMC pass / live kernel time; "
                         "the mix is ~55 % half-rate opcodes (profiles/r01_gfx950_valu_opcode_cost.txt), so ~0.65 "
                         "of this nominal peak is the practical ceiling"}
+        if args.full:
+            ok, sample = oracle_sample_ok(whole, total, q)
+            out["oracle_sample_ok"] = bool(ok)
+            out["oracle_sample"] = sample
         if overlapped_ms is not None:
             out["upload_and_search_overlapped_ms"] = overlapped_ms
             out["scorings_per_sec_incl_upload_single_query"] = total / (overlapped_ms * 1e-3)
-        if world == 1 and not args.no_regimes:
+        if args.full and world == 1 and not args.no_regimes:
             out["other_regimes"] = regimes(sat, np, local_rank)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"], n_cpu = cpu_baseline(db, q)
             ref = cpu_baseline_reference(db, q, n_cpu)
             if ref:

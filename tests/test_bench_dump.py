@@ -1,5 +1,5 @@
-"""bench.py's --dump-outputs writer and its step arguments, without a GPU (the GPU run of the same flag is
-tests/test_gpu_bench.py::test_dump_outputs_are_the_timed_scores)."""
+"""bench.py's --dump-outputs writer, its step arguments and --full, without a GPU (the GPU runs of these flags are
+tests/test_gpu_bench.py::test_dump_outputs_are_the_timed_scores and ::test_plain_run_is_the_headline_only)."""
 import numpy as np
 import pytest
 
@@ -36,3 +36,9 @@ def test_steps_and_dump_arguments():
     for bad in (["--steps", "0"], ["--warmup", "-1"]):
         with pytest.raises(SystemExit):
             bench.parse_args(bad)
+
+
+def test_full_is_off_by_default():
+    assert bench.parse_args([]).full is False
+    a = bench.parse_args(["--full", "--no-regimes"])
+    assert a.full is True and a.no_regimes is True and a.no_cpu_baseline is False
