@@ -26,6 +26,7 @@ ABI_SYMBOLS = (
     "sat_multi_shards", "sat_multi_queries_set", "sat_multi_search", "sat_multi_search_topk", "sat_multi_stat_d2h_bytes",
     "sat_search_matches", "sat_multi_search_matches",
     "sat_search_pairs", "sat_search_refine", "sat_multi_search_refine",
+    "sat_hits_cutoff", "sat_multi_search_cutoff", "sat_multi_hits_cutoff",
 )
 
 
@@ -119,6 +120,10 @@ def device_lib():
         lib.sat_multi_search_refine.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
                                                 C.POINTER(C.c_double)]
+        lib.sat_hits_cutoff.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        lib.sat_multi_search_cutoff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
+                                                C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+        lib.sat_multi_hits_cutoff.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         lib.sat_multi_stat_d2h_bytes.argtypes = [C.c_void_p]
         lib.sat_multi_stat_d2h_bytes.restype = C.c_uint64
         lib.sat_device_scores.argtypes = [C.c_void_p]

@@ -73,7 +73,7 @@ def build_device(force=False):
     srcs = [os.path.join(CSRC, "sat_capi.hip"), os.path.join(CSRC, "sat_topk.hip"), os.path.join(CSRC, "sat_multi.hip")]
     host_o = _host_objects(force)
     deps = srcs + host_o + [os.path.join(CSRC, "sat_sa_kernel.hpp"), os.path.join(CSRC, "sat_sa_body.inc"),
-                            os.path.join(CSRC, "sat_ctx.hpp"),
+                            os.path.join(CSRC, "sat_ctx.hpp"), os.path.join(CSRC, "sat_cutoff.hpp"),
                             os.path.join(INC, "satabsearch.h")]
     if force or _stale(out, deps):
         # -Wl,: hipcc would compile a bare .o as HIP source.  librccl is NOT linked: sat_multi.hip loads it on demand
@@ -115,6 +115,7 @@ def build_test_native(force=False):
     out3 = os.path.join(tdir, "libsat_selfcheck.so")
     dsrcs = [os.path.join(CSRC, f) for f in ("sat_capi.hip", "sat_topk.hip", "sat_multi.hip")]
     ddeps = dsrcs + [os.path.join(CSRC, "sat_sa_kernel.hpp"), os.path.join(CSRC, "sat_sa_body.inc"), os.path.join(CSRC, "sat_ctx.hpp"),
+                     os.path.join(CSRC, "sat_cutoff.hpp"),
                      os.path.join(CSRC, "diag", "sat_diag.hpp"), os.path.join(INC, "satabsearch.h")]
     if force or _stale(out3, ddeps):
         _run([HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared", "-DSAT_DIAG",

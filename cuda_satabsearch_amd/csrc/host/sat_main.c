@@ -25,8 +25,10 @@
  * -k K (print only the K best rows per query, ranked on the GPU by raw score, ties in
  * database order - the `sort -k 2,2nr | head` users run on the reference's output),
  * -b (keep a binary image `dbfile.satbin` beside the database and load it instead of
- * parsing when it is newer than the ASCII file).
+ * parsing when it is newer than the ASCII file), -p P (print only the rows whose p-value is <= P, selected on the
+ * GPU and ranked as -k; with -k K at most K of them per query).
  */
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -49,15 +51,17 @@ static double now_ms(void)
 }
 
 /* The sanitizer build of the host code links this file against stubs of the device library
- * (tests/native/gpu_stubs.c) that have no several-matches or refine entry point: weak references keep that
- * link working, and -m / -R report the missing entry point instead of calling it. */
+ * (tests/native/gpu_stubs.c) that have no several-matches, refine or cutoff entry point: weak references keep that
+ * link working, and -m / -R / -p report the missing entry point instead of calling it. */
 #pragma weak sat_multi_search_matches
 #pragma weak sat_multi_search_refine
+#pragma weak sat_multi_search_cutoff
+#pragma weak sat_multi_hits_cutoff
 
 static void usage(const char *prog)
 {
-    fprintf(stderr, "Usage: %s [-c] [-q dbfile] [-r restarts] [-g gpus] [-G gpu,gpu,...] [-s seed] [-k K] [-m M]\n"
-                    "       [-R restarts [-C C]] [-b]\n", prog);
+    fprintf(stderr, "Usage: %s [-c] [-q dbfile] [-r restarts] [-g gpus] [-G gpu,gpu,...] [-s seed] [-k K] [-p P]\n"
+                    "       [-m M] [-R restarts [-C C]] [-b]\n", prog);
     fprintf(stderr, "  -c : run on host CPU not GPU card\n");
     fprintf(stderr, "  -q dbfile : database is read from dbfile, list of query\n"
                     "              ids is read from stdin\n");
@@ -66,6 +70,7 @@ static void usage(const char *prog)
     fprintf(stderr, "  -G list : the GPUs to use, e.g. 0,2,3 (a GPU named twice holds two shards)\n");
     fprintf(stderr, "  -s seed : seed of the GPU random streams. Default %d\n", SAT_DEFAULT_SEED);
     fprintf(stderr, "  -k K : print only the K best rows per query (GPU mode)\n");
+    fprintf(stderr, "  -p P : print only rows whose p-value is <= P, ranked as -k (GPU mode)\n");
     fprintf(stderr, "  -m M : up to M (1..%d) non-overlapping matches per structure: after an entry's row,\n"
                     "         matches 2..M as rows named name:k (GPU mode)\n", SAT_MAX_MATCHES);
     fprintf(stderr, "  -R restarts : re-score each query's C best entries (by -r) with this many restarts;\n"
@@ -233,13 +238,15 @@ int main(int argc, char *argv[])
     char buf[SAT_MAX_LINE_LEN];
     int use_gpu = 1, querydbmode = 0, maxstart = 128, want_gpus = 1, bincache = 0, topk = 0, nmatch = 0;
     int refine = 0, ncand = 0;                      /* -R restarts of the second stage, -C candidates per query */
+    int cutoff = 0;                                 /* -p given: pmax is the largest p-value printed */
+    double pmax = 0.0;
     unsigned long long seed = SAT_DEFAULT_SEED;
     int ltype = 0, lorder = 0, lsoln = 0;
     char cltype = 'F', clorder = 'F', clsoln = 'F';
     int c;
 
     int dev_list[64], ndev_list = 0;
-    while ((c = getopt(argc, argv, "cq:r:g:G:s:bk:m:R:C:")) != -1) {
+    while ((c = getopt(argc, argv, "cq:r:g:G:s:bk:p:m:R:C:")) != -1) {
         switch (c) {
         case 'c': use_gpu = 0; break;
         case 'q': querydbmode = 1; strncpy(dbfile, optarg, sizeof(dbfile) - 1); break;
@@ -252,6 +259,18 @@ int main(int argc, char *argv[])
         case 's': seed = strtoull(optarg, NULL, 0); break;
         case 'b': bincache = 1; break;
         case 'k': topk = atoi(optarg); break;
+        case 'p': {
+            /* the whole argument, a finite number >= 0 */
+            char *end = NULL;
+            const double v = strtod(optarg, &end);
+            if (end == optarg || *end != '\0' || !isfinite(v) || v < 0.0) {
+                fprintf(stderr, "ERROR: -p needs a p-value >= 0 (got '%s')\n", optarg);
+                usage(argv[0]);
+            }
+            cutoff = 1;
+            pmax = v;
+            break;
+        }
         case 'm': {
             /* 1 .. SAT_MAX_MATCHES, digits only: anything else (0, a sign, text) is a usage error */
             char *end = NULL;
@@ -275,6 +294,22 @@ int main(int argc, char *argv[])
         }
         default: usage(argv[0]);
         }
+    }
+    if (cutoff && !use_gpu) {
+        fprintf(stderr, "ERROR: -p needs the GPU path\n");
+        exit(1);
+    }
+    if (cutoff && nmatch) {
+        fprintf(stderr, "ERROR: -p cannot be combined with -m\n");
+        exit(1);
+    }
+    if (cutoff && refine) {
+        fprintf(stderr, "ERROR: -p cannot be combined with -R\n");
+        exit(1);
+    }
+    if (cutoff && (!sat_multi_search_cutoff || !sat_multi_hits_cutoff)) {
+        fprintf(stderr, "ERROR: this library has no sat_multi_search_cutoff\n");
+        exit(1);
     }
     if (refine && !use_gpu) {
         fprintf(stderr, "ERROR: -R needs the GPU path\n");
@@ -514,7 +549,7 @@ int main(int argc, char *argv[])
     /* -m: M slots per row (nm = 1 without -m); the large class keeps every slot for its late rows */
     const int nm = nmatch > 0 ? nmatch : 1;
     int32_t *large_counts = NULL;
-    if (cls_count[1] > 0 && topk <= 0) {
+    if (cls_count[1] > 0 && topk <= 0 && !cutoff) {
         large_scores = (int32_t *)malloc(sizeof(int32_t) * (size_t)cls_count[1] * num_queries * nm);
         if (lsoln) large_maps = (int32_t *)malloc(sizeof(int32_t) * SAT_MAXDIM * (size_t)cls_count[1] * num_queries * nm);
         if (nmatch) large_counts = (int32_t *)malloc(sizeof(int32_t) * (size_t)cls_count[1] * num_queries);
@@ -526,7 +561,7 @@ int main(int argc, char *argv[])
      * query list long (-q).  The batch size is bounded by the host result buffers: every entry's row (and map)
      * without -k, and with -m every entry's M slots also under -k (the device holds the same slots, maps as bytes). */
     int batch = 256;
-    if (topk <= 0 || nmatch) {
+    if ((topk <= 0 && !cutoff) || nmatch) {
         size_t per_query = 0;
         if (!nmatch) per_query = (size_t)total * (lsoln ? (SAT_MAXDIM + 1) : 1) * sizeof(int32_t);
         else per_query = (size_t)total * (1 + 2 * (size_t)nm + (lsoln ? (size_t)nm * SAT_MAXDIM : 0)) * sizeof(int32_t);
@@ -542,7 +577,15 @@ int main(int argc, char *argv[])
     const int kk = topk < total ? topk : total;
     sat_hit *hits = NULL;
     int32_t *hit_maps = NULL;
-    if (topk > 0) {
+    int32_t *pcounts = NULL;                         /* -p: rows of each query of the batch */
+    int hits_cap = 0;                                /* -p: rows hits (and hit_maps) hold; grown to the batch's total */
+    if (cutoff) {
+        hits_cap = 1024;
+        pcounts = (int32_t *)malloc(sizeof(int32_t) * (size_t)batch);
+        hits = (sat_hit *)malloc(sizeof(sat_hit) * (size_t)hits_cap);
+        hit_maps = lsoln ? (int32_t *)malloc(sizeof(int32_t) * SAT_MAXDIM * (size_t)hits_cap) : NULL;
+        if (!pcounts || !hits || (lsoln && !hit_maps)) { fprintf(stderr, "malloc failed\n"); exit(1); }
+    } else if (topk > 0) {
         /* best K per query: only K rows per query (and GPU) ever leave the GPUs */
         hits = (sat_hit *)malloc(sizeof(sat_hit) * (size_t)kk * batch);
         hit_maps = lsoln ? (int32_t *)malloc(sizeof(int32_t) * SAT_MAXDIM * (size_t)kk * batch) : NULL;
@@ -586,7 +629,19 @@ int main(int argc, char *argv[])
         double ms = 0.0;
         int rc = sat_multi_queries_set(multi, nqb, n1s, qtabs, qdmats, SAT_MAXDIM, qtypes, (uint32_t)q0);
         double ms_stage2 = 0.0;
-        if (rc == SAT_OK && refine)
+        if (rc == SAT_OK && cutoff) {
+            /* every row of the batch under the cutoff; a short buffer is grown and the rows selected again */
+            rc = sat_multi_search_cutoff(multi, lorder, lsoln, maxstart, pmax, topk, pcounts, hits_cap, hits, hit_maps, &ms);
+            if (rc > hits_cap) {
+                free(hits);
+                free(hit_maps);
+                hits_cap = rc;
+                hits = (sat_hit *)malloc(sizeof(sat_hit) * (size_t)hits_cap);
+                hit_maps = lsoln ? (int32_t *)malloc(sizeof(int32_t) * SAT_MAXDIM * (size_t)hits_cap) : NULL;
+                if (!hits || (lsoln && !hit_maps)) { fprintf(stderr, "malloc failed\n"); exit(1); }
+                rc = sat_multi_hits_cutoff(multi, pmax, topk, pcounts, hits_cap, hits, hit_maps);
+            }
+        } else if (rc == SAT_OK && refine)
             rc = sat_multi_search_refine(multi, lorder, lsoln, maxstart, ncand, refine, kk, hits, hit_maps, NULL, &ms, &ms_stage2);
         else if (rc == SAT_OK && !nmatch)
             rc = topk > 0 ? sat_multi_search_topk(multi, lorder, lsoln, maxstart, kk, hits, hit_maps, &ms)
@@ -612,15 +667,18 @@ int main(int argc, char *argv[])
                     ncand < total ? ncand : total, refine);
         fprintf(stderr, "%f million iterations/sec\n",
                 ((double)total * nqb * ((double)maxstart * SAT_MAXITER) / (ms / 1000)) / 1.0e6);
-        if (topk > 0) {
+        if (topk > 0 || cutoff) {
+            /* -k: rc rows per query; -p: pcounts[b] rows of query b, after those of the queries before it */
+            size_t first = 0;
             for (int b = 0; b < nqb; b++) {
                 const int qs = qindex[q0 + b], n1 = n1s[b];
+                const int nrows = cutoff ? pcounts[b] : rc;
                 print_header(ltype, lorder, lsoln, sat_set_name(qsrc, qs), dbfile);
-                for (int r = 0; r < rc; r++) {
-                    const sat_hit *h = hits + (size_t)b * rc + r;
+                for (int r = 0; r < nrows; r++) {
+                    const sat_hit *h = hits + first + r;
                     out_row(sat_set_name(&db, h->entry), h->score, h->norm2, h->zscore, h->pvalue, n1 + db.order[h->entry], 0, 0);
                     if (lsoln) {
-                        const int32_t *map = hit_maps + ((size_t)b * rc + r) * SAT_MAXDIM;
+                        const int32_t *map = hit_maps + (first + r) * SAT_MAXDIM;
                         for (int k2 = 0; k2 < n1; k2++)
                             if (map[k2] >= 0)
                                 out_map_line(k2 + 1, map[k2] + 1);
@@ -631,6 +689,7 @@ int main(int argc, char *argv[])
                                            mscores + row * nm, mmaps ? mmaps + row * nm * SAT_MAXDIM : NULL, lsoln, 0);
                     }
                 }
+                first += (size_t)nrows;
             }
             continue;
         }
@@ -661,7 +720,7 @@ int main(int argc, char *argv[])
             }
         }
     }
-    if (cls_count[1] > 0 && topk <= 0)
+    if (cls_count[1] > 0 && topk <= 0 && !cutoff)
         for (int qi = 0; qi < num_queries; qi++) {
             const int qs = qindex[qi], n1 = qsrc->order[qs];
             print_header(ltype, lorder, lsoln, sat_set_name(qsrc, qs), dbfile);
@@ -683,6 +742,7 @@ bye:
     free(ssemaps);
     free(hits);
     free(hit_maps);
+    free(pcounts);
     free(large_scores);
     free(large_maps);
     free(large_counts);

@@ -20,6 +20,8 @@
 
 #include <algorithm>
 #include <chrono>
+#include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -29,6 +31,7 @@
 #include <vector>
 
 #include "sat_ctx.hpp"
+#include "sat_cutoff.hpp"
 #include "host/sat_gumbel.h"
 #include "host/sat_shard.h"
 
@@ -584,6 +587,83 @@ int sat_multi_search_refine(sat_multi *m, int lorder, int lsoln, int maxstart, i
     }
     if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return k;
+}
+
+int sat_multi_hits_cutoff(sat_multi *m, double max_pvalue, int max_rows, int32_t *counts, int capacity, sat_hit *hits,
+                          int32_t *ssemaps)
+{
+    if (!m) return sat_fail(SAT_EINVAL, "null context");
+    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
+    if (!counts) return sat_fail(SAT_EINVAL, "counts buffer is null");
+    if (!std::isfinite(max_pvalue) || max_pvalue < 0.0) return sat_fail(SAT_EINVAL, "max_pvalue must be finite and >= 0");
+    const int nq = (int)m->ctx[0]->queries.size();
+    auto cap = [&](int32_t c) { return max_rows > 0 && c > max_rows ? max_rows : c; };
+    // every shard counts its qualifying rows; a query's rows are the sum, cut to max_rows
+    std::vector<std::vector<int32_t>> raw((size_t)m->ndev, std::vector<int32_t>((size_t)nq));
+    for (int g = 0; g < m->ndev; g++) {
+        const int rc = sat_cutoff_count(m->ctx[(size_t)g], max_pvalue, ssemaps != nullptr, raw[(size_t)g].data());
+        if (rc != SAT_OK) return rc;
+    }
+    size_t total = 0;
+    for (int q = 0; q < nq; q++) {
+        long long c = 0;
+        for (int g = 0; g < m->ndev; g++) c += raw[(size_t)g][(size_t)q];
+        counts[q] = cap(c > INT_MAX ? INT_MAX : (int32_t)c);
+        total += (size_t)counts[q];
+    }
+    if (total > (size_t)INT_MAX) return sat_fail(SAT_EINVAL, "%zu rows qualify: more than one call can return", total);
+    if (!hits || (long long)total > (long long)capacity) return (int)total;
+    // each shard's rows (max_rows per query at most), merged per query: score descending, ties in database order
+    std::vector<std::vector<sat_hit>> rows((size_t)m->ndev);
+    std::vector<std::vector<int32_t>> rmaps((size_t)m->ndev);
+    std::vector<std::vector<size_t>> off((size_t)m->ndev, std::vector<size_t>((size_t)nq + 1, 0));
+    for (int g = 0; g < m->ndev; g++) {
+        for (int q = 0; q < nq; q++) off[(size_t)g][(size_t)q + 1] = off[(size_t)g][(size_t)q] + (size_t)cap(raw[(size_t)g][(size_t)q]);
+        rows[(size_t)g].resize(off[(size_t)g][(size_t)nq]);
+        if (ssemaps) rmaps[(size_t)g].resize(off[(size_t)g][(size_t)nq] * SAT_MAXDIM);
+        const int rc = sat_cutoff_rows(m->ctx[(size_t)g], max_pvalue, max_rows, raw[(size_t)g].data(), rows[(size_t)g].data(),
+                                       ssemaps ? rmaps[(size_t)g].data() : nullptr);
+        if (rc != SAT_OK) return rc;
+    }
+    size_t out = 0;
+    for (int q = 0; q < nq; q++) {
+        std::vector<size_t> head((size_t)m->ndev);
+        for (int g = 0; g < m->ndev; g++) head[(size_t)g] = off[(size_t)g][(size_t)q];
+        for (int r = 0; r < counts[q]; r++, out++) {
+            int bg = -1;
+            for (int g = 0; g < m->ndev; g++) {
+                if (head[(size_t)g] >= off[(size_t)g][(size_t)q + 1]) continue;
+                // shards are contiguous: on a tie the lower shard holds the lower entry
+                if (bg < 0 || rows[(size_t)g][head[(size_t)g]].score > rows[(size_t)bg][head[(size_t)bg]].score) bg = g;
+            }
+            sat_hit h = rows[(size_t)bg][head[(size_t)bg]];
+            h.entry += m->begin[(size_t)bg];
+            hits[out] = h;
+            if (ssemaps)
+                memcpy(ssemaps + out * SAT_MAXDIM, rmaps[(size_t)bg].data() + head[(size_t)bg] * SAT_MAXDIM, sizeof(int32_t) * SAT_MAXDIM);
+            head[(size_t)bg]++;
+        }
+    }
+    return (int)total;
+}
+
+int sat_multi_search_cutoff(sat_multi *m, int lorder, int lsoln, int maxstart, double max_pvalue, int max_rows, int32_t *counts,
+                            int capacity, sat_hit *hits, int32_t *ssemaps, double *wall_ms)
+{
+    if (!m) return sat_fail(SAT_EINVAL, "null context");
+    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
+    if (!counts) return sat_fail(SAT_EINVAL, "counts buffer is null");
+    if (!std::isfinite(max_pvalue) || max_pvalue < 0.0) return sat_fail(SAT_EINVAL, "max_pvalue must be finite and >= 0");
+    const auto t0 = std::chrono::steady_clock::now();
+    auto bail = [&](int rc) { const std::string msg = sat_last_error(); sync_all(m); return sat_fail(rc, "%s", msg.c_str()); };
+    for (int g = 0; g < m->ndev; g++) {
+        int rc = sat_search_async(m->ctx[(size_t)g], lorder, lsoln, maxstart);
+        if (rc != SAT_OK) return bail(rc);
+    }
+    const int r = sat_multi_hits_cutoff(m, max_pvalue, max_rows, counts, capacity, hits, ssemaps);
+    if (r < 0) return bail(r);
+    if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return r;
 }
 
 unsigned long long sat_multi_stat_d2h_bytes(const sat_multi *m)

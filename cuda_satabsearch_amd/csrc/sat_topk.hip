@@ -17,9 +17,12 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include <climits>
+#include <cmath>
 #include <vector>
 
 #include "sat_ctx.hpp"
+#include "sat_cutoff.hpp"
 
 #define HIP_TRY(expr)                                                                       \
     do {                                                                                    \
@@ -189,6 +192,127 @@ int check_searched(sat_ctx *ctx)
     return SAT_OK;
 }
 
+// ---- p-value cutoff (sat_hits_cutoff).  Blocks of 1024 rows, `bpq` blocks per query, so that a block holds rows of
+// one query only: each wave counts its qualifying rows with a ballot, the block sums its 16 waves' counts in LDS and
+// counts (or claims) them with ONE atomic.  (Every query's counter sits in a few cache lines: at P = 1 one atomic per
+// wave took 170 us of the q200 shape's flag pass)  A row qualifies iff the p-value hit_row gives it is
+// <= max_p: the same double, from the same table index.
+
+constexpr int kCutoffBlock = 1024, kCutoffWaves = kCutoffBlock / 64;
+
+__device__ __forceinline__ bool cutoff_row(const int32_t *scores, int n, int bpq, const int32_t *orders, const HitQuery *queries,
+                                           const double *ztab, const double *ptab, double max_p, int &q, int &e, int32_t &score)
+{
+    q = (int)(blockIdx.x / (unsigned)bpq);
+    e = (int)(blockIdx.x - (unsigned)q * bpq) * kCutoffBlock + (int)threadIdx.x;
+    if (e >= n) return false;
+    score = scores[(size_t)q * n + e];
+    return hit_row(e, score, queries[q].n1, orders[e], ztab, ptab).pvalue <= max_p;
+}
+
+// counts[q] += qualifying rows of query q
+__global__ void __launch_bounds__(kCutoffBlock) cutoff_count(const int32_t *scores, int n, int bpq, const int32_t *orders,
+                                                              const HitQuery *queries, const double *ztab, const double *ptab,
+                                                              double max_p, int32_t *counts)
+{
+    int q, e;
+    int32_t score = 0;
+    const bool hit = cutoff_row(scores, n, bpq, orders, queries, ztab, ptab, max_p, q, e, score);
+    __shared__ int32_t wave_count[kCutoffWaves];
+    const unsigned long long mask = __ballot(hit);
+    if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = (int32_t)__popcll(mask);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int32_t c = 0;
+        for (int w = 0; w < kCutoffWaves; w++) c += wave_count[w];
+        if (c) atomicAdd(counts + q, c);
+    }
+}
+
+// the qualifying rows' keys (pack_keys' layout) into their query's segment seg[q] .. seg[q + 1], in any order: each
+// block claims a run of its segment through cursor[q], the same predicate as cutoff_count keeps it inside
+__global__ void __launch_bounds__(kCutoffBlock) cutoff_compact(const int32_t *scores, int n, int bpq, const int32_t *orders,
+                                                                const HitQuery *queries, const double *ztab, const double *ptab,
+                                                                double max_p, const int32_t *seg, int32_t *cursor,
+                                                                unsigned long long *keys)
+{
+    int q, e;
+    int32_t score = 0;
+    const bool hit = cutoff_row(scores, n, bpq, orders, queries, ztab, ptab, max_p, q, e, score);
+    __shared__ int32_t wave_base[kCutoffWaves + 1];                     // each wave's offset in the block's run, the run
+    const unsigned long long mask = __ballot(hit);
+    const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+    if (lane == 0) wave_base[wave] = (int32_t)__popcll(mask);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int32_t c = 0;
+        for (int w = 0; w < kCutoffWaves; w++) {
+            const int32_t v = wave_base[w];
+            wave_base[w] = c;
+            c += v;
+        }
+        wave_base[kCutoffWaves] = c ? atomicAdd(cursor + q, c) : 0;
+    }
+    __syncthreads();
+    if (hit) {
+        const int slot = seg[q] + wave_base[kCutoffWaves] + wave_base[wave] + (int)__popcll(mask & ((1ull << lane) - 1ull));
+        keys[slot] = ((unsigned long long)(uint32_t)(score + 0x40000000) << 32) | (0xFFFFFFFFu - (uint32_t)e);
+    }
+}
+
+// one thread per output row t: query q holds rows out_off[q] .. out_off[q + 1] - 1, its rank r is sorted key seg[q] + r
+__global__ void cutoff_finish(const unsigned long long *sorted, const int32_t *seg, const int32_t *out_off, int nq, int rows,
+                              const int32_t *orders, const HitQuery *queries, const double *ztab, const double *ptab,
+                              sat_hit *hits, int32_t *maps)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= rows) return;
+    int lo = 0, hi = nq - 1;                                            // the last q with out_off[q] <= t
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (out_off[mid] <= t) lo = mid;
+        else hi = mid - 1;
+    }
+    const int q = lo, r = t - out_off[q];
+    const unsigned long long key = sorted[seg[q] + r];
+    const int32_t entry = (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFu));
+    const int32_t score = (int32_t)(uint32_t)(key >> 32) - 0x40000000;
+    const int n1 = queries[q].n1;
+    hits[t] = hit_row(entry, score, n1, orders[entry], ztab, ptab);
+    if (maps) {
+        int32_t *out = maps + (size_t)t * SAT_MAXDIM;
+        const int8_t *src = queries[q].ssemaps ? queries[q].ssemaps + (size_t)entry * n1 : nullptr;
+        for (int i = 0; i < SAT_MAXDIM; i++) out[i] = (src && i < n1) ? (int32_t)src[i] : -1;
+    }
+}
+
+// queries per chunk: under 2^31 keys per sort (as sat_topk_hits) and under 2^31 threads per launch
+int cutoff_chunk(int n)
+{
+    const long long bpq = (n + kCutoffBlock - 1) / kCutoffBlock;
+    long long per = 0x7FFFFFFFll / n;
+    if (0x7FFFFFFFll / (bpq * kCutoffBlock) < per) per = 0x7FFFFFFFll / (bpq * kCutoffBlock);
+    return per < 1 ? 1 : (int)per;
+}
+
+// the HitQuery rows of queries [0, nq) into ctx->d_hitq
+int upload_hit_queries(sat_ctx *ctx, bool maps)
+{
+    const int nq = (int)ctx->queries.size();
+    int rc;
+    if ((rc = grow(ctx->d_hitq, ctx->hitq_cap, (size_t)nq * sizeof(HitQuery))) != SAT_OK) return rc;
+    std::vector<HitQuery> hq((size_t)nq);
+    for (int q = 0; q < nq; q++) {
+        const auto &info = ctx->queries[(size_t)q];
+        hq[(size_t)q].n1 = info.n1;
+        hq[(size_t)q].pad_ = 0;
+        hq[(size_t)q].ssemaps = maps ? ctx->d_ssemaps + info.ssemap_off : nullptr;
+    }
+    HIP_TRY(hipMemcpyAsync(ctx->d_hitq, hq.data(), hq.size() * sizeof(HitQuery), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));             // hq dies at return
+    return SAT_OK;
+}
+
 }  // namespace
 
 extern "C" int sat_topk(sat_ctx *ctx, int query, int k, int32_t *entry_index, int32_t *scores_out)
@@ -314,4 +438,134 @@ extern "C" int sat_search_refine(sat_ctx *ctx, int lorder, int lsoln, int maxsta
     }
     ctx->last_launch_info = "stage 1: " + stage1_info + " || stage 2: " + stage2_info;
     return k;
+}
+
+// ---- p-value cutoff.  ctx->d_seg holds, in ints: [nq] the count pass's counts, then for the chunk at hand its
+// segment offsets [nqc + 1], its output offsets [nqc + 1] and its claim cursors [nqc].
+
+int sat_cutoff_count(sat_ctx *ctx, double max_pvalue, bool maps, int32_t *counts)
+{
+    int rc = check_searched(ctx);
+    if (rc != SAT_OK) return rc;
+    if (maps && !ctx->searched_lsoln) return sat_fail(SAT_ESTATE, "the last search ran without lsoln");
+    const int n = ctx->n_entries, nq = (int)ctx->queries.size();
+    const int per_chunk = cutoff_chunk(n), pc = per_chunk < nq ? per_chunk : nq;
+    const int bpq = (n + kCutoffBlock - 1) / kCutoffBlock;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = grow(ctx->d_seg, ctx->seg_cap, (size_t)nq + 3 * (size_t)pc + 2)) != SAT_OK) return rc;
+    if ((rc = upload_hit_queries(ctx, maps)) != SAT_OK) return rc;
+    const HitQuery *hq = reinterpret_cast<const HitQuery *>(ctx->d_hitq);
+    HIP_TRY(hipMemsetAsync(ctx->d_seg, 0, (size_t)nq * sizeof(int32_t), ctx->stream));
+    for (int q0 = 0; q0 < nq; q0 += per_chunk) {
+        const int nqc = nq - q0 < per_chunk ? nq - q0 : per_chunk;
+        hipLaunchKernelGGL(cutoff_count, dim3((unsigned)nqc * (unsigned)bpq), dim3(kCutoffBlock), 0, ctx->stream,
+                           ctx->d_scores + (size_t)q0 * n, n, bpq, ctx->d_orders, hq + q0, ctx->d_gumbel_z, ctx->d_gumbel_p,
+                           max_pvalue, ctx->d_seg + q0);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(counts, ctx->d_seg, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->d2h_bytes += (size_t)nq * sizeof(int32_t);
+    return SAT_OK;
+}
+
+int sat_cutoff_rows(sat_ctx *ctx, double max_pvalue, int max_rows, const int32_t *counts, sat_hit *hits, int32_t *ssemaps)
+{
+    const int n = ctx->n_entries, nq = (int)ctx->queries.size();
+    const int per_chunk = cutoff_chunk(n);
+    const int bpq = (n + kCutoffBlock - 1) / kCutoffBlock;
+    const bool maps = ssemaps != nullptr;
+    size_t rows_total = 0, keys_max = 0;
+    for (int q0 = 0; q0 < nq; q0 += per_chunk) {
+        const int nqc = nq - q0 < per_chunk ? nq - q0 : per_chunk;
+        size_t keys = 0;
+        for (int q = q0; q < q0 + nqc; q++) {
+            keys += (size_t)counts[q];
+            rows_total += (size_t)(max_rows > 0 && counts[q] > max_rows ? max_rows : counts[q]);
+        }
+        if (keys > keys_max) keys_max = keys;
+    }
+    if (rows_total == 0) return SAT_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = grow(ctx->d_keys, ctx->keys_cap, keys_max)) != SAT_OK) return rc;
+    if ((rc = grow(ctx->d_sorted, ctx->sorted_cap, keys_max)) != SAT_OK) return rc;
+    if ((rc = grow(ctx->d_hits, ctx->hits_cap, rows_total)) != SAT_OK) return rc;
+    if (maps && (rc = grow(ctx->d_hit_maps, ctx->hit_maps_cap, rows_total * SAT_MAXDIM)) != SAT_OK) return rc;
+    const HitQuery *hq = reinterpret_cast<const HitQuery *>(ctx->d_hitq);      // as sat_cutoff_count left them
+    size_t out_row = 0;
+    std::vector<int32_t> out_off;
+    for (int q0 = 0; q0 < nq; q0 += per_chunk) {
+        const int nqc = nq - q0 < per_chunk ? nq - q0 : per_chunk;
+        int32_t *seg = ctx->d_seg + nq, *d_out = seg + nqc + 1, *cursor = d_out + nqc + 1;
+        // the chunk's output offsets (each query cut to max_rows); its segment offsets: a scan of its counts
+        out_off.assign((size_t)nqc + 1, 0);
+        int keys = 0;
+        for (int q = 0; q < nqc; q++) {
+            const int c = counts[q0 + q];
+            keys += c;
+            out_off[(size_t)q + 1] = out_off[(size_t)q] + (max_rows > 0 && c > max_rows ? max_rows : c);
+        }
+        const int rows = out_off[(size_t)nqc];
+        if (rows == 0) continue;
+        HIP_TRY(hipMemcpyAsync(d_out, out_off.data(), out_off.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemsetAsync(seg, 0, sizeof(int32_t), ctx->stream));
+        HIP_TRY(hipMemsetAsync(cursor, 0, (size_t)nqc * sizeof(int32_t), ctx->stream));
+        size_t scan_bytes = 0, sort_bytes = 0;
+        HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, ctx->d_seg + q0, seg + 1, nqc, ctx->stream));
+        if (nqc == 1) {
+            HIP_TRY(hipcub::DeviceRadixSort::SortKeysDescending(nullptr, sort_bytes, ctx->d_keys, ctx->d_sorted, keys, 0, 64, ctx->stream));
+        } else {
+            HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeysDescending(nullptr, sort_bytes, ctx->d_keys, ctx->d_sorted, keys, nqc,
+                                                                        seg, seg + 1, 0, 64, ctx->stream));
+        }
+        const size_t temp_bytes = scan_bytes > sort_bytes ? scan_bytes : sort_bytes;
+        if ((rc = grow(ctx->d_sort_temp, ctx->sort_temp_cap, temp_bytes ? temp_bytes : 1)) != SAT_OK) return rc;
+        HIP_TRY(hipcub::DeviceScan::InclusiveSum(ctx->d_sort_temp, scan_bytes, ctx->d_seg + q0, seg + 1, nqc, ctx->stream));
+        hipLaunchKernelGGL(cutoff_compact, dim3((unsigned)nqc * (unsigned)bpq), dim3(kCutoffBlock), 0, ctx->stream,
+                           ctx->d_scores + (size_t)q0 * n, n, bpq, ctx->d_orders, hq + q0, ctx->d_gumbel_z, ctx->d_gumbel_p,
+                           max_pvalue, seg, cursor, ctx->d_keys);
+        HIP_TRY(hipGetLastError());
+        if (nqc == 1) {
+            HIP_TRY(hipcub::DeviceRadixSort::SortKeysDescending(ctx->d_sort_temp, sort_bytes, ctx->d_keys, ctx->d_sorted, keys, 0, 64,
+                                                                ctx->stream));
+        } else {
+            HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeysDescending(ctx->d_sort_temp, sort_bytes, ctx->d_keys, ctx->d_sorted, keys,
+                                                                        nqc, seg, seg + 1, 0, 64, ctx->stream));
+        }
+        hipLaunchKernelGGL(cutoff_finish, dim3((unsigned)((rows + 127) / 128)), dim3(128), 0, ctx->stream, ctx->d_sorted, seg, d_out,
+                           nqc, rows, ctx->d_orders, hq + q0, ctx->d_gumbel_z, ctx->d_gumbel_p, ctx->d_hits + out_row,
+                           maps ? ctx->d_hit_maps + out_row * SAT_MAXDIM : nullptr);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(ctx->stream));                     // out_off is reused by the next chunk
+        out_row += (size_t)rows;
+    }
+    HIP_TRY(hipMemcpy(hits, ctx->d_hits, rows_total * sizeof(sat_hit), hipMemcpyDeviceToHost));
+    ctx->d2h_bytes += rows_total * sizeof(sat_hit);
+    if (maps) {
+        HIP_TRY(hipMemcpy(ssemaps, ctx->d_hit_maps, rows_total * SAT_MAXDIM * sizeof(int32_t), hipMemcpyDeviceToHost));
+        ctx->d2h_bytes += rows_total * SAT_MAXDIM * sizeof(int32_t);
+    }
+    return SAT_OK;
+}
+
+extern "C" int sat_hits_cutoff(sat_ctx *ctx, double max_pvalue, int max_rows, int32_t *counts, int capacity, sat_hit *hits,
+                               int32_t *ssemaps)
+{
+    int rc = check_searched(ctx);
+    if (rc != SAT_OK) return rc;
+    if (!counts) return sat_fail(SAT_EINVAL, "counts buffer is null");
+    if (!std::isfinite(max_pvalue) || max_pvalue < 0.0) return sat_fail(SAT_EINVAL, "max_pvalue must be finite and >= 0");
+    const int nq = (int)ctx->queries.size();
+    std::vector<int32_t> raw((size_t)nq);
+    if ((rc = sat_cutoff_count(ctx, max_pvalue, ssemaps != nullptr, raw.data())) != SAT_OK) return rc;
+    size_t total = 0;
+    for (int q = 0; q < nq; q++) {
+        counts[q] = max_rows > 0 && raw[(size_t)q] > max_rows ? max_rows : raw[(size_t)q];
+        total += (size_t)counts[q];
+    }
+    if (total > (size_t)INT_MAX) return sat_fail(SAT_EINVAL, "%zu rows qualify: more than one call can return", total);
+    if (!hits || (long long)total > (long long)capacity) return (int)total;
+    if ((rc = sat_cutoff_rows(ctx, max_pvalue, max_rows, raw.data(), hits, ssemaps)) != SAT_OK) return rc;
+    return (int)total;
 }

@@ -52,6 +52,27 @@ def _search_refine(obj, call, k, candidates, refine_maxstart, lsoln):
     return hits, maps, first
 
 
+def _hits_cutoff(obj, nq, lsoln, first, again):
+    """shared by Searcher.hits_cutoff / MultiSearcher.search_cutoff: `first(counts, capacity, hits, maps)` runs the C
+    entry point once; when the rows did not fit, `again` (same arguments) selects them again into a buffer of the
+    returned size.  Returns (list of nq hit arrays, list of nq int32[rows, 111] map arrays or None)."""
+    counts = np.zeros(nq, np.int32)
+    cap = max(int(getattr(obj, "_cutoff_cap", 0)), 256)
+    for call in (first, again):
+        hits = np.zeros(cap, _HIT_DTYPE)
+        maps = np.full((cap, MAXDIM), -1, np.int32) if lsoln else None
+        n = call(counts.ctypes.data, cap, hits.ctypes.data, maps.ctypes.data if lsoln else None)
+        if n < 0:
+            obj._check(n)
+        if n <= cap:
+            break
+        cap = n
+    obj._cutoff_cap = cap
+    cuts = np.cumsum(counts)[:-1]
+    rows = np.split(hits[:n], cuts)
+    return rows, (np.split(maps[:n], cuts) if lsoln else None)
+
+
 class Searcher:
     """One HIP device, one resident database shard, one current query."""
 
@@ -271,6 +292,15 @@ class Searcher:
             self._check(n)
         return (hits, maps) if lsoln else hits
 
+    def hits_cutoff(self, max_pvalue, k=None, lsoln=False):
+        """Every row of the last search whose p-value is <= max_pvalue (sat_hits_cutoff), selected on the device:
+        a list of nq structured arrays shaped like topk_hits' rows, each in topk_hits order and cut to its first k
+        (k None or <= 0: no cut); with lsoln also a list of nq int32[rows, 111] map arrays."""
+        nq = getattr(self, "n_queries", 1)
+        call = lambda c, cap, h, m: self._lib.sat_hits_cutoff(self._ctx, float(max_pvalue), int(k or 0), c, cap, h, m)
+        rows, maps = _hits_cutoff(self, nq, lsoln, call, call)
+        return (rows, maps) if lsoln else rows
+
     def d2h_bytes(self):
         """Bytes this context's result calls have copied device -> host so far."""
         return int(self._lib.sat_stat_d2h_bytes(self._ctx))
@@ -404,6 +434,24 @@ class MultiSearcher:
         return _search_refine(self, lambda h, m, f: self._lib.sat_multi_search_refine(
             self._m, int(bool(lorder)), int(bool(lsoln)), int(maxstart), int(candidates), int(refine_maxstart), int(k),
             h, m, f, C.byref(ms), None), k, candidates, refine_maxstart, lsoln)
+
+    def search_cutoff(self, max_pvalue, k=None, lorder=True, lsoln=False, maxstart=DEFAULT_MAXSTART):
+        """Search every shard, then Searcher.hits_cutoff over the whole database (sat_multi_search_cutoff; a short
+        buffer is refilled by sat_multi_hits_cutoff, without a new search): (rows, maps or None, wall_ms), entries
+        indexed in the whole database."""
+        ms = C.c_double(0.0)
+        rows, maps = _hits_cutoff(
+            self, self.n_queries, lsoln,
+            lambda c, cap, h, m: self._lib.sat_multi_search_cutoff(self._m, int(bool(lorder)), int(bool(lsoln)), int(maxstart),
+                                                                   float(max_pvalue), int(k or 0), c, cap, h, m, C.byref(ms)),
+            lambda c, cap, h, m: self._lib.sat_multi_hits_cutoff(self._m, float(max_pvalue), int(k or 0), c, cap, h, m))
+        return rows, maps, ms.value
+
+    def hits_cutoff(self, max_pvalue, k=None, lsoln=False):
+        """The rows of search_cutoff selected again from every shard's last search (sat_multi_hits_cutoff)."""
+        call = lambda c, cap, h, m: self._lib.sat_multi_hits_cutoff(self._m, float(max_pvalue), int(k or 0), c, cap, h, m)
+        rows, maps = _hits_cutoff(self, self.n_queries, lsoln, call, call)
+        return (rows, maps) if lsoln else rows
 
     def d2h_bytes(self):
         return int(self._lib.sat_multi_stat_d2h_bytes(self._m))

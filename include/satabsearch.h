@@ -270,6 +270,25 @@ typedef struct sat_hit {
 int sat_topk_hits(sat_ctx *ctx, int k, sat_hit *hits, int32_t *ssemaps);
 
 /*
+ * Every row of the last search whose p-value is <= max_pvalue (finite, >= 0; else SAT_EINVAL), selected on the
+ * device.  A row qualifies iff the pvalue sat_topk_hits would give it - the same double, from the same table - is
+ * <= max_pvalue; max_pvalue >= 1 takes every row.  Query q's rows are sat_topk_hits(n_entries)'s rows of q without
+ * the ones that do not qualify (descending score, ties in database order, every field and map byte-equal), cut to
+ * their first max_rows (max_rows <= 0: no cut).  The result is CSR:
+ *   counts    [n_queries] rows of each query; always written (NULL is SAT_EINVAL)
+ *   hits      query q's rows start at hits[counts[0] + .. + counts[q - 1]]
+ *   ssemaps   (may be NULL) the rows' maps at the same row index times SAT_MAXDIM; after a search without lsoln
+ *             SAT_ESTATE
+ * Returns the total row count T or a negative SAT_E* code.  With hits == NULL or T > capacity only counts is written
+ * (and T returned): grow the buffers and call again - that costs a selection, not a search, as does asking again with
+ * another max_pvalue.  Never searches (SAT_ESTATE before the first search).  Cost: one flag / count pass over the
+ * n_queries x n_entries scores, then compaction, a segmented sort and the rows of the qualifying rows only.  Copies
+ * 4 * n_queries + 32 * T bytes (+ 444 * T with ssemaps) to the host; 4 * n_queries when only counts is written.
+ */
+int sat_hits_cutoff(sat_ctx *ctx, double max_pvalue, int max_rows, int32_t *counts, int capacity, sat_hit *hits,
+                    int32_t *ssemaps);
+
+/*
  * Refine: a cheap search of every entry, then a long search of each query's best candidates only.
  *   1. stage 1: sat_search(lorder, lsoln = 0, maxstart); the candidates of query q are its best C entries in
  *      sat_topk_hits order (descending score, ties in database order), C = min(candidates, n_entries)
@@ -287,7 +306,7 @@ int sat_search_refine(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int can
                       int k, sat_hit *hits, int32_t *ssemaps, int32_t *first_scores);
 
 
-/* Bytes this context's result calls (sat_results, sat_search, sat_topk, sat_topk_hits) have copied
+/* Bytes this context's result calls (sat_results, sat_search, sat_topk, sat_topk_hits, sat_hits_cutoff) have copied
  * from the device to the host since it was created (diagnostics: the best-k path moves O(k) rows). */
 unsigned long long sat_stat_d2h_bytes(const sat_ctx *ctx);
 
@@ -365,6 +384,16 @@ int sat_multi_search_matches(sat_multi *m, int lorder, int maxstart, int max_mat
 int sat_multi_search_refine(sat_multi *m, int lorder, int lsoln, int maxstart, int candidates, int refine_maxstart,
                             int k, sat_hit *hits, int32_t *ssemaps, int32_t *first_scores, double *wall_ms,
                             double *stage2_ms);
+/* sat_hits_cutoff over every shard, exactly what one context holding the whole database returns: each shard selects
+ * its own rows (max_rows per query at most), the host merges them per query by score descending, then entry index in
+ * the whole database ascending (hits[].entry), and cuts to max_rows.  Same CSR output, capacity contract and return
+ * value; only counts and rows cross to the host, nothing proportional to n_entries.  sat_multi_search_cutoff searches
+ * every shard first (wall_ms as sat_multi_search); sat_multi_hits_cutoff selects from every shard's last search again,
+ * e.g. after a short capacity, without a new search. */
+int sat_multi_search_cutoff(sat_multi *m, int lorder, int lsoln, int maxstart, double max_pvalue, int max_rows,
+                            int32_t *counts, int capacity, sat_hit *hits, int32_t *ssemaps, double *wall_ms);
+int sat_multi_hits_cutoff(sat_multi *m, double max_pvalue, int max_rows, int32_t *counts, int capacity, sat_hit *hits,
+                          int32_t *ssemaps);
 unsigned long long sat_multi_stat_d2h_bytes(const sat_multi *m);
 
 /*
