@@ -17,6 +17,7 @@
 #include <cstring>
 #include <new>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "satabsearch.h"
@@ -31,15 +32,6 @@ namespace {
 
 thread_local char g_err[512] = "";
 
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
 }  // namespace
 
 int sat_fail(int code, const char *fmt, ...)
@@ -53,28 +45,10 @@ int sat_fail(int code, const char *fmt, ...)
 
 namespace {
 
-#define HIP_TRY(expr)                                                                   \
-    do {                                                                                \
-        hipError_t err__ = (expr);                                                      \
-        if (err__ != hipSuccess)                                                        \
-            return fail(err__ == hipErrorOutOfMemory ? SAT_ENOMEM : SAT_EDEVICE,        \
-                        "%s failed: %s", #expr, hipGetErrorString(err__));              \
-    } while (0)
-
 // db entries are launched in classes of similar order so that every launch sizes its
 // LDS for the largest member of the class only
 const int kBucketMax[kNumBuckets] = { 16, 32, 48, 64, 80, 96, 111 };
 constexpr size_t kLdsLimit = 160 * 1024;
-
-template <typename T> void dev_free(T *&p)
-{
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
-}  // namespace
-
-namespace {
 
 int build_metropolis_table(sat_ctx *ctx)
 {
@@ -105,10 +79,10 @@ int build_metropolis_table(sat_ctx *ctx)
         tab.push_back(0.0f);
         temp = temp * 0.95f;
     }
-    HIP_TRY(hipMalloc(&ctx->d_ptab, tab.size() * sizeof(float)));
-    HIP_TRY(hipMalloc(&ctx->d_prow, rows.size() * sizeof(int32_t)));
-    HIP_TRY(hipMemcpy(ctx->d_ptab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ctx->d_prow, rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    int rc;
+    if ((rc = ctx->d_ptab.grow(tab.size())) != SAT_OK || (rc = ctx->d_prow.grow(rows.size())) != SAT_OK) return rc;
+    HIP_TRY(hipMemcpy(ctx->d_ptab.get(), tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ctx->d_prow.get(), rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     return SAT_OK;
 }
 
@@ -122,25 +96,23 @@ int build_gumbel_tables(sat_ctx *ctx)
         z[x + 128] = sat_z_gumbel_trunc((double)x);
         p[x + 128] = sat_pv_gumbel(z[x + 128]);
     }
-    HIP_TRY(hipMalloc(&ctx->d_gumbel_z, sizeof z));
-    HIP_TRY(hipMalloc(&ctx->d_gumbel_p, sizeof p));
-    HIP_TRY(hipMemcpy(ctx->d_gumbel_z, z, sizeof z, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ctx->d_gumbel_p, p, sizeof p, hipMemcpyHostToDevice));
+    int rc;
+    if ((rc = ctx->d_gumbel_z.grow(256)) != SAT_OK || (rc = ctx->d_gumbel_p.grow(256)) != SAT_OK) return rc;
+    HIP_TRY(hipMemcpy(ctx->d_gumbel_z.get(), z, sizeof z, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ctx->d_gumbel_p.get(), p, sizeof p, hipMemcpyHostToDevice));
     return SAT_OK;
 }
 
 void free_db(sat_ctx *ctx)
 {
-    dev_free(ctx->d_orders);
-    dev_free(ctx->d_cell_off);
-    dev_free(ctx->d_tab);
-    dev_free(ctx->d_dist);
-    dev_free(ctx->d_ordinal);
-    dev_free(ctx->d_lists);
-    dev_free(ctx->d_scores);
-    dev_free(ctx->d_ssemaps);
-    ctx->scores_cap = 0;
-    ctx->ssemaps_cap = 0;
+    ctx->d_orders.reset();
+    ctx->d_cell_off.reset();
+    ctx->d_tab.reset();
+    ctx->d_dist.reset();
+    ctx->d_ordinal.reset();
+    ctx->d_lists.reset();
+    ctx->d_scores.reset();
+    ctx->d_ssemaps.reset();
     ctx->desc_dirty = true;
     ctx->n_entries = 0;
     ctx->min_rows = 0;
@@ -148,105 +120,114 @@ void free_db(sat_ctx *ctx)
     ctx->h_orders.clear();
 }
 
+// ---- kernel choice.  The three kernel families are instantiated over the same size classes and db layouts: the
+// dispatch below calls f with std::integral_constant arguments, so that each family names its instantiations once.
+template <int V> using Int = std::integral_constant<int, V>;
+
+// f(Int<N1P>) for a query size class
+template <typename F> auto by_class(int n1p, F f)
+{
+    switch (n1p) {
+    case 16: return f(Int<16>{});
+    case 32: return f(Int<32>{});
+    case 64: return f(Int<64>{});
+    default: return f(Int<112>{});
+    }
+}
+
+// f(std::bool_constant<b>)
+template <typename F> auto by_flag(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+// f(Int<V>) for v in First .. Last, Last for anything above
+template <int First, int Last, typename F> auto by_value(int v, F f)
+{
+    if constexpr (First == Last) return f(Int<Last>{});
+    else return v == First ? f(Int<First>{}) : by_value<First + 1, Last>(v, f);
+}
+
+// f(Int<M2W>, Int<CELLS>): db-side set width and cell layout (satk::cell_layout of the launch's largest entry).
+// One-word sets go with the 8-byte cells, two-word sets with either split layout (entries of up to 48 SSEs: full
+// matrix, above: triangle), four-word sets with the triangle.
+template <typename F> auto by_layout(int m2w, int cells, F f)
+{
+    if (m2w == 1) return f(Int<1>{}, Int<SAT_CELLS_FULL8>{});
+    if (m2w == 2) return cells == SAT_CELLS_FULL5 ? f(Int<2>{}, Int<SAT_CELLS_FULL5>{}) : f(Int<2>{}, Int<SAT_CELLS_TRI5>{});
+    return f(Int<4>{}, Int<SAT_CELLS_TRI5>{});
+}
+
 typedef void (*kernel_fn)(const SatKernelArgs);
 
-// db-side set width and cell layout (satk::cell_layout of the launch's largest entry): one-word sets go with the
-// 8-byte cells, two-word sets with either split layout (entries of up to 48 SSEs: full matrix, above: triangle),
-// four-word sets with the triangle
-template <int N1P, bool QLDS, int OPT, int WPL> kernel_fn pick_m2w(int m2w, int cells)
+// The plain kernel.  opt >= 0: an instantiation with the options as compile-time facts (bit 0 LORDER, bit 1 LSOLN,
+// bits 2-3 log2 of the lanes per chain; compaction tables exactly when LORDER); with LORDER and one lane per chain
+// also `wpl`, the words per lane of the compacted rounds when every query of the launch has the same, else 0 (see
+// the kernel's OPT and WPL parameters).  These exist for the default placement of the query cells only (LDS for the
+// 16 class, L1/L2 for the others), for the wpl values a class can have (satk::compaction_shape), and with several
+// lanes per chain for the largest entries only (M2W = 4, words per lane read per query); anything else runs the
+// general instantiation (opt = -1).
+kernel_fn pick_kernel(int n1p, int m2w, int cells, bool qlds, int opt, int wpl)
 {
-    if (m2w == 1) return sat_sa_kernel<N1P, 1, QLDS, OPT, WPL, SAT_CELLS_FULL8>;
-    if (m2w == 2) return cells == SAT_CELLS_FULL5 ? sat_sa_kernel<N1P, 2, QLDS, OPT, WPL, SAT_CELLS_FULL5>
-                                                   : sat_sa_kernel<N1P, 2, QLDS, OPT, WPL, SAT_CELLS_TRI5>;
-    return sat_sa_kernel<N1P, 4, QLDS, OPT, WPL, SAT_CELLS_TRI5>;
-}
-
-// opt >= 0: an instantiation with the options as compile-time facts (bit 0 LORDER, bit 1 LSOLN; one
-// lane per chain, compaction tables exactly when LORDER); with LORDER also `wpl`, the words per
-// lane of the compacted rounds when every query of the launch has the same, else 0 (see the
-// kernel's OPT and WPL parameters).  These exist for the default placement of the query cells only (LDS for the
-// 16 class, L1/L2 for the others) and for the wpl values a class can have
-// (satk::compaction_shape); anything else runs the general instantiation.
-template <int N1P, int OPT> kernel_fn pick_wpl(int m2w, int cells, int wpl)
-{
-    constexpr bool kQ = N1P < 32;
-    if constexpr ((OPT & 1) == 0) return pick_m2w<N1P, kQ, OPT, 0>(m2w, cells);     // no compaction: wpl unused
-    else {
-        if (wpl == 4) return pick_m2w<N1P, kQ, OPT, 4>(m2w, cells);
-        if constexpr (N1P <= 64)
-            if (wpl == 3) return pick_m2w<N1P, kQ, OPT, 3>(m2w, cells);
-        if constexpr (N1P == 16) {
-            if (wpl == 2) return pick_m2w<N1P, kQ, OPT, 2>(m2w, cells);
-            if (wpl == 1) return pick_m2w<N1P, kQ, OPT, 1>(m2w, cells);
-        }
-        return pick_m2w<N1P, kQ, OPT, 0>(m2w, cells);       // queries of different shapes: wpl read per query
-    }
-}
-
-// several lanes per chain with the options as compile-time facts: only for the largest entries (M2W = 4),
-// words per lane read per query
-template <int N1P, bool QLDS> kernel_fn pick_lpc(int opt)
-{
-    switch (opt) {
-    case 4: return sat_sa_kernel<N1P, 4, QLDS, 4, 0, SAT_CELLS_TRI5>;
-    case 5: return sat_sa_kernel<N1P, 4, QLDS, 5, 0, SAT_CELLS_TRI5>;
-    case 6: return sat_sa_kernel<N1P, 4, QLDS, 6, 0, SAT_CELLS_TRI5>;
-    case 7: return sat_sa_kernel<N1P, 4, QLDS, 7, 0, SAT_CELLS_TRI5>;
-    case 8: return sat_sa_kernel<N1P, 4, QLDS, 8, 0, SAT_CELLS_TRI5>;
-    case 9: return sat_sa_kernel<N1P, 4, QLDS, 9, 0, SAT_CELLS_TRI5>;
-    case 10: return sat_sa_kernel<N1P, 4, QLDS, 10, 0, SAT_CELLS_TRI5>;
-    default: return sat_sa_kernel<N1P, 4, QLDS, 11, 0, SAT_CELLS_TRI5>;
-    }
-}
-
-template <int N1P> kernel_fn pick_n1p(int m2w, int cells, bool qlds, int opt, int wpl)
-{
-    constexpr bool kQ = N1P < 32;
-    kernel_fn fn = nullptr;
-    if (opt >= 4 && qlds == kQ && m2w == 4) return pick_lpc<N1P, kQ>(opt);
-    if (opt >= 0 && opt < 4 && qlds == kQ) {
-        switch (opt) {
-        case 0: fn = pick_wpl<N1P, 0>(m2w, cells, wpl); break;
-        case 1: fn = pick_wpl<N1P, 1>(m2w, cells, wpl); break;
-        case 2: fn = pick_wpl<N1P, 2>(m2w, cells, wpl); break;
-        default: fn = pick_wpl<N1P, 3>(m2w, cells, wpl); break;
-        }
-    }
-    if (fn) return fn;
-    return qlds ? pick_m2w<N1P, true, -1, 0>(m2w, cells) : pick_m2w<N1P, false, -1, 0>(m2w, cells);
+    return by_class(n1p, [&](auto c) -> kernel_fn {
+        constexpr int N1P = decltype(c)::value;
+        constexpr bool kQ = N1P < 32;
+        auto layout = [&](auto q, auto o, auto w) {
+            return by_layout(m2w, cells, [&](auto m, auto l) -> kernel_fn {
+                return sat_sa_kernel<N1P, decltype(m)::value, decltype(q)::value, decltype(o)::value, decltype(w)::value,
+                                     decltype(l)::value>;
+            });
+        };
+        const std::bool_constant<kQ> q{};
+        if (opt >= 4 && qlds == kQ && m2w == 4)
+            return by_value<4, 11>(opt, [&](auto o) -> kernel_fn { return sat_sa_kernel<N1P, 4, kQ, decltype(o)::value, 0, SAT_CELLS_TRI5>; });
+        if (opt >= 0 && opt < 4 && qlds == kQ)
+            return by_value<0, 3>(opt, [&](auto o) -> kernel_fn {
+                if constexpr ((decltype(o)::value & 1) == 0) return layout(q, o, Int<0>{});     // no compaction: wpl unused
+                else {
+                    if (wpl == 4) return layout(q, o, Int<4>{});
+                    if constexpr (N1P <= 64)
+                        if (wpl == 3) return layout(q, o, Int<3>{});
+                    if constexpr (N1P == 16) {
+                        if (wpl == 2) return layout(q, o, Int<2>{});
+                        if (wpl == 1) return layout(q, o, Int<1>{});
+                    }
+                    return layout(q, o, Int<0>{});           // queries of different shapes: wpl read per query
+                }
+            });
+        return by_flag(qlds, [&](auto qg) { return layout(qg, Int<-1>{}, Int<0>{}); });
+    });
 }
 
 // the match mode's kernel (sat_sa_match_kernel: options from the arguments) for a launch's size class and layout
 typedef void (*match_kernel_fn)(const SatKernelArgs, const SatMatchArgs);
-template <int N1P, bool QLDS> match_kernel_fn pick_match_m2w(int m2w, int cells)
-{
-    if (m2w == 1) return sat_sa_match_kernel<N1P, 1, QLDS, SAT_CELLS_FULL8>;
-    if (m2w == 2) return cells == SAT_CELLS_FULL5 ? sat_sa_match_kernel<N1P, 2, QLDS, SAT_CELLS_FULL5>
-                                                   : sat_sa_match_kernel<N1P, 2, QLDS, SAT_CELLS_TRI5>;
-    return sat_sa_match_kernel<N1P, 4, QLDS, SAT_CELLS_TRI5>;
-}
-template <int N1P> match_kernel_fn pick_match_n1p(int m2w, int cells, bool qlds)
-{
-    return qlds ? pick_match_m2w<N1P, true>(m2w, cells) : pick_match_m2w<N1P, false>(m2w, cells);
-}
 match_kernel_fn pick_match_kernel(int n1p, int m2w, int cells, bool qlds)
 {
-    switch (n1p) {
-    case 16: return pick_match_n1p<16>(m2w, cells, qlds);
-    case 32: return pick_match_n1p<32>(m2w, cells, qlds);
-    case 64: return pick_match_n1p<64>(m2w, cells, qlds);
-    default: return pick_match_n1p<112>(m2w, cells, qlds);
-    }
+    return by_class(n1p, [&](auto c) {
+        return by_flag(qlds, [&](auto q) {
+            return by_layout(m2w, cells, [&](auto m, auto l) -> match_kernel_fn {
+                return sat_sa_match_kernel<decltype(c)::value, decltype(m)::value, decltype(q)::value, decltype(l)::value>;
+            });
+        });
+    });
 }
 
-kernel_fn pick_kernel(int n1p, int m2w, int cells, bool qlds, int opt, int wpl)
+// the pair kernel of a launch's size class and layout: the option-specialised LSOLN-off instantiations for
+// the default layout of LORDER F and T (opt 0 / 1), the general one (opt -1) for everything else and for the
+// map pass
+typedef void (*pair_kernel_fn)(const SatKernelArgs, const SatPairArgs);
+pair_kernel_fn pick_pair_kernel(int n1p, int m2w, int cells, bool qlds, int opt)
 {
-    switch (n1p) {
-    case 16: return pick_n1p<16>(m2w, cells, qlds, opt, wpl);
-    case 32: return pick_n1p<32>(m2w, cells, qlds, opt, wpl);
-    case 64: return pick_n1p<64>(m2w, cells, qlds, opt, wpl);
-    default: return pick_n1p<112>(m2w, cells, qlds, opt, wpl);
-    }
+    return by_class(n1p, [&](auto c) {
+        constexpr int N1P = decltype(c)::value;
+        constexpr bool kQ = N1P < 32;
+        auto layout = [&](auto q, auto o) {
+            return by_layout(m2w, cells, [&](auto m, auto l) -> pair_kernel_fn {
+                return sat_sa_pair_kernel<N1P, decltype(m)::value, decltype(q)::value, decltype(o)::value, decltype(l)::value>;
+            });
+        };
+        const std::bool_constant<kQ> q{};
+        if (opt == 0 && qlds == kQ) return layout(q, Int<0>{});
+        if (opt == 1 && qlds == kQ) return layout(q, Int<1>{});
+        return by_flag(qlds, [&](auto qg) { return layout(qg, Int<-1>{}); });
+    });
 }
 
 const int kClassN1P[4] = { 16, 32, 64, 112 };
@@ -257,13 +238,10 @@ int refresh_descriptors(sat_ctx *ctx, bool lsoln, hipStream_t stream)
 {
     const size_t nq = ctx->queries.size();
     const size_t rows = (size_t)(ctx->n_entries > ctx->min_rows ? ctx->n_entries : ctx->min_rows);    // capacity only
-    const size_t need_scores = nq * rows;
-    if (need_scores > ctx->scores_cap) {
-        dev_free(ctx->d_scores);
-        HIP_TRY(hipMalloc(&ctx->d_scores, need_scores * sizeof(int32_t)));
-        ctx->scores_cap = need_scores;
-        ctx->desc_dirty = true;
-    }
+    bool moved = false;
+    int rc = ctx->d_scores.grow(nq * rows, &moved);
+    if (rc != SAT_OK) return rc;
+    if (moved) ctx->desc_dirty = true;
     if (lsoln) {
         size_t need = 0, n1sum = 0;
         for (auto &q : ctx->queries) {
@@ -272,13 +250,8 @@ int refresh_descriptors(sat_ctx *ctx, bool lsoln, hipStream_t stream)
             n1sum += (size_t)q.n1;
         }
         if (rows * n1sum > need) need = rows * n1sum;
-        if (need > ctx->ssemaps_cap) {
-            dev_free(ctx->d_ssemaps);
-            HIP_TRY(hipMalloc(&ctx->d_ssemaps, need));
-            ctx->ssemaps_cap = need;
-            ctx->desc_dirty = true;
-        }
-        if (!ctx->desc_lsoln) ctx->desc_dirty = true;
+        if ((rc = ctx->d_ssemaps.grow(need, &moved)) != SAT_OK) return rc;
+        if (moved || !ctx->desc_lsoln) ctx->desc_dirty = true;
     }
     if (!ctx->desc_dirty) return SAT_OK;
 
@@ -289,19 +262,22 @@ int refresh_descriptors(sat_ctx *ctx, bool lsoln, hipStream_t stream)
         ctx->class_n1max[c] = 0;
         ctx->class_wpl[c] = -1;                       // -1: no query yet, 0: mixed
         for (size_t qi = 0; qi < nq; qi++) {
-            const auto &q = ctx->queries[qi];
+            auto &q = ctx->queries[qi];
             if (q.n1p != kClassN1P[c]) continue;
+            q.cls = c;
+            q.desc = (int)desc.size();
+            const uint8_t *blob = ctx->d_qblob.get() + q.blob_off;
             const size_t groups = (size_t)q.n1p / 4 * q.n1p;
             SatQuery d;
-            d.qdist = reinterpret_cast<const float4 *>(ctx->d_qblob + q.blob_off);
-            d.qcode = reinterpret_cast<const uint32_t *>(ctx->d_qblob + q.blob_off + groups * 16);
-            d.qtypes = ctx->d_qblob + q.blob_off + groups * 20;
-            d.qpair = reinterpret_cast<const uint2 *>(ctx->d_qblob + q.blob_off + ((groups * 20 + (size_t)q.n1p + 15) & ~(size_t)15));
+            d.qdist = reinterpret_cast<const float4 *>(blob);
+            d.qcode = reinterpret_cast<const uint32_t *>(blob + groups * 16);
+            d.qtypes = blob + groups * 20;
+            d.qpair = reinterpret_cast<const uint2 *>(blob + ((groups * 20 + (size_t)q.n1p + 15) & ~(size_t)15));
             d.n1 = q.n1;
             d.pad_ = 0;
             d.seed_q = ctx->seed + ((uint64_t)q.ordinal << 32);
-            d.scores = ctx->d_scores + qi * (size_t)ctx->n_entries;
-            d.ssemaps = lsoln ? ctx->d_ssemaps + q.ssemap_off : nullptr;
+            d.scores = ctx->d_scores.get() + qi * (size_t)ctx->n_entries;
+            d.ssemaps = lsoln ? ctx->d_ssemaps.get() + q.ssemap_off : nullptr;
             desc.push_back(d);
             if (q.n1 > ctx->class_n1max[c]) ctx->class_n1max[c] = q.n1;
             int lpi, wpl;
@@ -312,7 +288,7 @@ int refresh_descriptors(sat_ctx *ctx, bool lsoln, hipStream_t stream)
     }
     ctx->class_begin[4] = (int)desc.size();
     // ordered after earlier launches on the stream; the host vector dies at return, so wait
-    HIP_TRY(hipMemcpyAsync(ctx->d_qdesc, desc.data(), desc.size() * sizeof(SatQuery), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(ctx->d_qdesc.get(), desc.data(), desc.size() * sizeof(SatQuery), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     ctx->desc_dirty = false;
     ctx->desc_lsoln = lsoln;
@@ -347,6 +323,57 @@ int pick_epw(const void *fn, int threads, size_t lds_stride)
     return best;
 }
 
+// Before a launch of `fn` with `threads` per entry slot and `lds_stride` LDS bytes per slot: raise the
+// instantiation's dynamic-LDS limit (once per context), then *epw = its entries per workgroup (see pick_epw; asked
+// once per shape).  Launches of under 8192 entry-query pairs (`work`) keep one, for the most workgroups;
+// SAT_EXP_EPW overrides where it fits.  epw = null: the caller keeps one entry per workgroup.
+int launch_setup(sat_ctx *ctx, const void *fn, int threads, size_t lds_stride, long long work, int *epw)
+{
+    if (ctx->lds_attr_done.insert(fn).second)
+        HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));
+    if (!epw) return SAT_OK;
+    *epw = 1;
+    if (work >= 8192) {
+        const auto key = std::make_tuple(fn, threads, lds_stride);
+        auto it = ctx->epw_choice.find(key);
+        if (it == ctx->epw_choice.end()) it = ctx->epw_choice.emplace(key, pick_epw(fn, threads, lds_stride)).first;
+        *epw = it->second;
+    }
+    if (ctx->tune.epw >= 1 && (size_t)ctx->tune.epw * lds_stride <= kLdsLimit && ctx->tune.epw * threads <= 1024)
+        *epw = ctx->tune.epw;
+    return SAT_OK;
+}
+
+// the SatKernelArgs fields every launch shares: the database shard, the options, the Metropolis table; no slabs
+SatKernelArgs base_args(const sat_ctx *ctx, int lorder, int lsoln, int maxstart)
+{
+    SatKernelArgs a;
+    a.orders = ctx->d_orders.get();
+    a.cell_off = ctx->d_cell_off.get();
+    a.tab_tri = ctx->d_tab.get();
+    a.dist_tri = ctx->d_dist.get();
+    a.ordinal = ctx->d_ordinal.get();
+    a.lorder = lorder ? 1 : 0;
+    a.lsoln = lsoln ? 1 : 0;
+    a.maxstart = maxstart;
+    a.ptab = ctx->d_ptab.get();
+    a.prow = ctx->d_prow.get();
+    a.bmap_slabs = nullptr;
+    a.bmap_slab_words = 0;
+    return a;
+}
+
+// The preconditions of queuing a search, checked in this order: a context, a database (need_db), a query batch,
+// maxstart >= 1.
+int check_ready(const sat_ctx *ctx, bool need_db, int maxstart)
+{
+    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
+    if (need_db && ctx->n_entries <= 0) return sat_fail(SAT_ESTATE, "no database uploaded");
+    if (ctx->queries.empty()) return sat_fail(SAT_ESTATE, "no query set");
+    if (maxstart < 1) return sat_fail(SAT_EINVAL, "maxstart must be >= 1 (got %d)", maxstart);
+    return SAT_OK;
+}
+
 // The workgroup of one launch: restart chains (one per restart up to 256, fewer where the LDS would not fit them),
 // lanes per chain, where the query cells live, whether the SA step compacts its work, and the LDS bytes of one
 // entry slot.  plan_starts = the most restarts one entry slot runs.
@@ -376,7 +403,7 @@ int size_workgroup(const sat_ctx *ctx, int plan_starts, int n1max, int n1p, int 
             if (chains > 256) chains = 256;
             continue;
         }
-        return fail(SAT_EINVAL, "workgroup does not fit in LDS (n1=%d n2=%d)", n1max, n2max);
+        return sat_fail(SAT_EINVAL, "workgroup does not fit in LDS (n1=%d n2=%d)", n1max, n2max);
     }
     // lanes per chain: when LDS leaves fewer than 2 waves per SIMD, let 2 or 4 adjacent lanes
     // share a chain (same cells in LDS, 2-4x the waves; they split the pair loops).  Measured:
@@ -428,29 +455,14 @@ struct ListView {
 int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t stream, const ListView *piece = nullptr,
                   const SatMatchArgs *mx = nullptr)
 {
-    if (!ctx) return fail(SAT_EINVAL, "null context");
-    if (ctx->n_entries <= 0) return fail(SAT_ESTATE, "no database uploaded");
-    const ListView whole = { ctx->d_lists, ctx->bucket_begin, ctx->bucket_n2max, ctx->n_entries };
-    const ListView &view = piece ? *piece : whole;
-    if (ctx->queries.empty()) return fail(SAT_ESTATE, "no query set");
-    if (maxstart < 1) return fail(SAT_EINVAL, "maxstart must be >= 1 (got %d)", maxstart);
-    HIP_TRY(hipSetDevice(ctx->device));
-    int rc = refresh_descriptors(ctx, lsoln != 0, stream);
+    int rc = check_ready(ctx, true, maxstart);
     if (rc != SAT_OK) return rc;
+    const ListView whole = { ctx->d_lists.get(), ctx->bucket_begin, ctx->bucket_n2max, ctx->n_entries };
+    const ListView &view = piece ? *piece : whole;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = refresh_descriptors(ctx, lsoln != 0, stream)) != SAT_OK) return rc;
 
-    SatKernelArgs a;
-    a.orders = ctx->d_orders;
-    a.cell_off = ctx->d_cell_off;
-    a.tab_tri = ctx->d_tab;
-    a.dist_tri = ctx->d_dist;
-    a.ordinal = ctx->d_ordinal;
-    a.lorder = lorder ? 1 : 0;
-    a.lsoln = lsoln ? 1 : 0;
-    a.maxstart = maxstart;
-    a.ptab = ctx->d_ptab;
-    a.prow = ctx->d_prow;
-    a.bmap_slabs = nullptr;
-    a.bmap_slab_words = 0;
+    SatKernelArgs a = base_args(ctx, lorder, lsoln, maxstart);
 #ifdef SAT_DIAG
     HIP_TRY(satdiag::begin(stream, a.diag));
 #endif
@@ -464,7 +476,7 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
         const int nqc = ctx->class_begin[c + 1] - ctx->class_begin[c];
         if (nqc == 0) continue;
         const int n1p = kClassN1P[c], n1max = ctx->class_n1max[c];
-        a.queries = ctx->d_qdesc + ctx->class_begin[c];
+        a.queries = ctx->d_qdesc.get() + ctx->class_begin[c];
         // A small problem cannot fill the GPU: its run time is the latency of one workgroup per
         // launch, so all order buckets go into ONE launch sized for the largest entry instead of
         // one launch per bucket queued behind each other.
@@ -499,21 +511,11 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
             kernel_fn fn = mx ? nullptr : pick_kernel(n1p, m2w, cells, qlds, opt, ctx->class_wpl[c]);
             match_kernel_fn mfn = mx ? pick_match_kernel(n1p, m2w, cells, qlds) : nullptr;
             const void *fn_ptr = mx ? reinterpret_cast<const void *>(mfn) : reinterpret_cast<const void *>(fn);
-            if (!fn_ptr) return fail(SAT_EDEVICE, "no kernel variant for n1p=%d m2w=%d", n1p, m2w);
-            if (ctx->lds_attr_done.insert(fn_ptr).second)
-                HIP_TRY(hipFuncSetAttribute(fn_ptr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));
+            if (!fn_ptr) return sat_fail(SAT_EDEVICE, "no kernel variant for n1p=%d m2w=%d", n1p, m2w);
             a.entry_list = view.d_list + (one_launch ? view.begin[0] : view.begin[b]);
-            // entries per workgroup (see pick_epw); small launches keep one, for the most workgroups
             const size_t lds_stride = (lds + 15) & ~(size_t)15;
-            int epw = 1;
-            if ((long long)count * nqc >= 8192) {
-                const auto key = std::make_tuple(fn_ptr, threads, lds_stride);
-                auto it = ctx->epw_choice.find(key);
-                if (it == ctx->epw_choice.end()) it = ctx->epw_choice.emplace(key, pick_epw(fn_ptr, threads, lds_stride)).first;
-                epw = it->second;
-            }
-            if (ctx->tune.epw >= 1 && (size_t)ctx->tune.epw * lds_stride <= kLdsLimit && ctx->tune.epw * threads <= 1024)
-                epw = ctx->tune.epw;
+            int epw;
+            if ((rc = launch_setup(ctx, fn_ptr, threads, lds_stride, (long long)count * nqc, &epw)) != SAT_OK) return rc;
             a.epw = epw;
             a.tpe = threads;
             a.lds_stride = (uint32_t)lds_stride;
@@ -570,14 +572,9 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
             if (need > need_total) need_total = need;
         }
         need_total *= (size_t)nlanes;                                  // one region per lane of launches
-        if (need_total > ctx->bmap_slabs_cap) {
-            HIP_TRY(hipStreamSynchronize(stream));
-            dev_free(ctx->d_bmap_slabs);
-            HIP_TRY(hipMalloc(&ctx->d_bmap_slabs, need_total * sizeof(uint32_t)));
-            ctx->bmap_slabs_cap = need_total;
-        }
+        if ((rc = ctx->d_bmap_slabs.grow_after(stream, need_total)) != SAT_OK) return rc;
     }
-    const size_t lane_region_words = slabs ? ctx->bmap_slabs_cap / (size_t)nlanes : 0;
+    const size_t lane_region_words = slabs ? ctx->d_bmap_slabs.capacity() / (size_t)nlanes : 0;
     for (size_t i = 0; i < plan.size(); i++) {
         const Planned &pl = plan[i];
         const int lane = fork ? (int)(i % (size_t)nlanes) : 0;
@@ -593,10 +590,10 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
                 part.entry_list = pl.args.entry_list + e0;
                 SatMatchArgs mpart = mx ? *mx : SatMatchArgs{};
                 if (lsoln || (mx && mx->replay)) {
-                    part.bmap_slabs = ctx->d_bmap_slabs + (size_t)lane * lane_region_words;
+                    part.bmap_slabs = ctx->d_bmap_slabs.get() + (size_t)lane * lane_region_words;
                     part.bmap_slab_words = (uint32_t)pl.slab_words;
                 } else if (mx) {
-                    mpart.rec_slabs = ctx->d_bmap_slabs + (size_t)lane * lane_region_words;
+                    mpart.rec_slabs = ctx->d_bmap_slabs.get() + (size_t)lane * lane_region_words;
                     mpart.rec_slab_words = (uint32_t)pl.slab_words;
                 }
                 part.n_list = en;
@@ -637,34 +634,6 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
 
 // ---------------------------------------------------------------- pair mode (sat_search_pairs)
 
-typedef void (*pair_kernel_fn)(const SatKernelArgs, const SatPairArgs);
-// the pair kernel of a launch's size class and layout: the option-specialised LSOLN-off instantiations for
-// the default layout of LORDER F and T (opt 0 / 1), the general one (opt -1) for everything else and for the
-// map pass
-template <int N1P, bool QLDS, int OPT> pair_kernel_fn pick_pair_m2w(int m2w, int cells)
-{
-    if (m2w == 1) return sat_sa_pair_kernel<N1P, 1, QLDS, OPT, SAT_CELLS_FULL8>;
-    if (m2w == 2) return cells == SAT_CELLS_FULL5 ? sat_sa_pair_kernel<N1P, 2, QLDS, OPT, SAT_CELLS_FULL5>
-                                                   : sat_sa_pair_kernel<N1P, 2, QLDS, OPT, SAT_CELLS_TRI5>;
-    return sat_sa_pair_kernel<N1P, 4, QLDS, OPT, SAT_CELLS_TRI5>;
-}
-template <int N1P> pair_kernel_fn pick_pair_n1p(int m2w, int cells, bool qlds, int opt)
-{
-    constexpr bool kQ = N1P < 32;
-    if (opt == 0 && qlds == kQ) return pick_pair_m2w<N1P, kQ, 0>(m2w, cells);
-    if (opt == 1 && qlds == kQ) return pick_pair_m2w<N1P, kQ, 1>(m2w, cells);
-    return qlds ? pick_pair_m2w<N1P, true, -1>(m2w, cells) : pick_pair_m2w<N1P, false, -1>(m2w, cells);
-}
-pair_kernel_fn pick_pair_kernel(int n1p, int m2w, int cells, bool qlds, int opt)
-{
-    switch (n1p) {
-    case 16: return pick_pair_n1p<16>(m2w, cells, qlds, opt);
-    case 32: return pick_pair_n1p<32>(m2w, cells, qlds, opt);
-    case 64: return pick_pair_n1p<64>(m2w, cells, qlds, opt);
-    default: return pick_pair_n1p<112>(m2w, cells, qlds, opt);
-    }
-}
-
 int order_bucket(int n2)
 {
     int b = 0;
@@ -688,17 +657,6 @@ __global__ void __launch_bounds__(256) pair_scores(const unsigned long long *key
     if (i < n) scores[i] = (int32_t)(uint32_t)(keys[i] >> 32) - 0x40000000;
 }
 
-template <typename T> int grow_scratch(sat_ctx *ctx, T *&p, size_t &cap, size_t need)
-{
-    if (need <= cap) return SAT_OK;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    dev_free(p);
-    cap = 0;
-    HIP_TRY(hipMalloc(&p, need * sizeof(T)));
-    cap = need;
-    return SAT_OK;
-}
-
 // One pass of the pair mode: the item groups [goff[g], goff[g + 1]) of d_items, group g holding queries of class
 // gcls[g] and entries of up to gn2[g] SSEs.  Score pass (map_pass = false): the option-specialised LSOLN-off
 // kernels, restarts per item at most `starts`.  Map pass: one restart per item, the general kernel with LSOLN,
@@ -709,8 +667,8 @@ int launch_pair_pass(sat_ctx *ctx, int lorder, bool map_pass, int starts, const 
     hipStream_t stream = ctx->stream;
     SatPairArgs px;
     px.items = nullptr;
-    px.keys = ctx->d_pkeys;
-    px.maps = ctx->d_pmaps;
+    px.keys = ctx->d_pkeys.get();
+    px.maps = ctx->d_pmaps.get();
     for (size_t g = 0; g < gcls.size(); g++) {
         const int count = (int)(goff[g + 1] - goff[g]);
         if (count == 0) continue;
@@ -724,41 +682,21 @@ int launch_pair_pass(sat_ctx *ctx, int lorder, bool map_pass, int starts, const 
         const int opt = special ? (lorder ? 1 : 0) : -1;
         pair_kernel_fn fn = pick_pair_kernel(n1p, m2w, cells, w.qlds, opt);
         const int opt_used = (special && w.qlds == (n1p < 32)) ? opt : -1;
-        const void *fn_ptr = reinterpret_cast<const void *>(fn);
-        if (ctx->lds_attr_done.insert(fn_ptr).second)
-            HIP_TRY(hipFuncSetAttribute(fn_ptr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));
         const size_t lds_stride = (w.lds + 15) & ~(size_t)15;
         // entries per workgroup: the score pass as a plain launch; the map pass keeps one item per workgroup (its one
         // restart per item gains nothing from packing, and its best-map slabs are counted per item)
         int epw = 1;
-        if (!map_pass && count >= 8192) {
-            const auto key = std::make_tuple(fn_ptr, w.threads, lds_stride);
-            auto it = ctx->epw_choice.find(key);
-            if (it == ctx->epw_choice.end()) it = ctx->epw_choice.emplace(key, pick_epw(fn_ptr, w.threads, lds_stride)).first;
-            epw = it->second;
-        }
-        if (!map_pass && ctx->tune.epw >= 1 && (size_t)ctx->tune.epw * lds_stride <= kLdsLimit && ctx->tune.epw * w.threads <= 1024)
-            epw = ctx->tune.epw;
-        SatKernelArgs a;
-        a.orders = ctx->d_orders;
-        a.cell_off = ctx->d_cell_off;
-        a.tab_tri = ctx->d_tab;
-        a.dist_tri = ctx->d_dist;
-        a.ordinal = ctx->d_ordinal;
+        if ((rc = launch_setup(ctx, reinterpret_cast<const void *>(fn), w.threads, lds_stride, count, map_pass ? nullptr : &epw)) != SAT_OK)
+            return rc;
+        // (maxstart is unused by the pair mode's restart loop)
+        SatKernelArgs a = base_args(ctx, lorder, map_pass, starts);
         a.entry_list = nullptr;
         a.epw = epw;
         a.tpe = w.threads;
         a.lds_stride = (uint32_t)lds_stride;
-        a.queries = ctx->d_qdesc;                       // items carry descriptor indices
-        a.lorder = lorder ? 1 : 0;
-        a.lsoln = map_pass ? 1 : 0;
-        a.maxstart = starts;                            // (unused by the pair mode's restart loop)
+        a.queries = ctx->d_qdesc.get();                 // items carry descriptor indices
         a.lpc_shift = w.lpc_shift;
         a.compact = w.compact ? 1 : 0;
-        a.bmap_slabs = nullptr;
-        a.bmap_slab_words = 0;
-        a.ptab = ctx->d_ptab;
-        a.prow = ctx->d_prow;
 #ifdef SAT_DIAG
         HIP_TRY(satdiag::begin(stream, a.diag));
 #endif
@@ -770,8 +708,8 @@ int launch_pair_pass(sat_ctx *ctx, int lorder, bool map_pass, int starts, const 
             // one slab per entry slot of a launch, the spare slots of its last workgroup included (the kernel indexes
             // the slab by slot; with epw = 1 there are none)
             const size_t slabs = (size_t)per_launch + (size_t)epw - 1;
-            if ((rc = grow_scratch(ctx, ctx->d_bmap_slabs, ctx->bmap_slabs_cap, slab_words * slabs)) != SAT_OK) return rc;
-            a.bmap_slabs = ctx->d_bmap_slabs;
+            if ((rc = ctx->d_bmap_slabs.grow_after(stream, slab_words * slabs)) != SAT_OK) return rc;
+            a.bmap_slabs = ctx->d_bmap_slabs.get();
             a.bmap_slab_words = (uint32_t)slab_words;
         }
         const size_t lds_launch = epw > 1 ? (size_t)epw * lds_stride : w.lds;
@@ -799,27 +737,18 @@ int launch_pair_pass(sat_ctx *ctx, int lorder, bool map_pass, int starts, const 
 // sat_ctx.hpp: queue a pair search (both passes) on the context's stream
 int sat_pairs_launch(sat_ctx *ctx, int lorder, int maxstart, bool maps, const int32_t *query, const int32_t *entry, int npairs)
 {
-    if (!ctx) return fail(SAT_EINVAL, "null context");
-    if (ctx->n_entries <= 0) return fail(SAT_ESTATE, "no database uploaded");
-    if (ctx->queries.empty()) return fail(SAT_ESTATE, "no query set");
-    if (maxstart < 1) return fail(SAT_EINVAL, "maxstart must be >= 1 (got %d)", maxstart);
-    if (npairs < 0 || (npairs > 0 && (!query || !entry))) return fail(SAT_EINVAL, "bad pair list");
+    int rc = check_ready(ctx, true, maxstart);
+    if (rc != SAT_OK) return rc;
+    if (npairs < 0 || (npairs > 0 && (!query || !entry))) return sat_fail(SAT_EINVAL, "bad pair list");
     const int nq = (int)ctx->queries.size();
     for (int p = 0; p < npairs; p++) {
-        if (query[p] < 0 || query[p] >= nq) return fail(SAT_EINVAL, "pair %d: query %d out of range", p, query[p]);
-        if (entry[p] < 0 || entry[p] >= ctx->n_entries) return fail(SAT_EINVAL, "pair %d: entry %d out of range", p, entry[p]);
+        if (query[p] < 0 || query[p] >= nq) return sat_fail(SAT_EINVAL, "pair %d: query %d out of range", p, query[p]);
+        if (entry[p] < 0 || entry[p] >= ctx->n_entries) return sat_fail(SAT_EINVAL, "pair %d: entry %d out of range", p, entry[p]);
     }
     HIP_TRY(hipSetDevice(ctx->device));
-    int rc = refresh_descriptors(ctx, false, ctx->stream);
-    if (rc != SAT_OK) return rc;
+    if ((rc = refresh_descriptors(ctx, false, ctx->stream)) != SAT_OK) return rc;
     ctx->last_launch_info.clear();
     if (npairs == 0) return SAT_OK;
-
-    // descriptor index and size class of every query (descriptors are grouped by class, input order inside)
-    std::vector<int> desc_of((size_t)nq), cls_of((size_t)nq);
-    for (int c = 0, d = 0; c < 4; c++)
-        for (int q = 0; q < nq; q++)
-            if (ctx->queries[(size_t)q].n1p == kClassN1P[c]) { desc_of[(size_t)q] = d++; cls_of[(size_t)q] = c; }
 
     // Restarts per item.  A pair's R restarts on one workgroup of T chains take ceil(R / T) rounds at the latency
     // of one workgroup: a few hundred pairs cannot fill the GPU that way.  Cut each pair into about
@@ -844,7 +773,7 @@ int sat_pairs_launch(sat_ctx *ctx, int lorder, int maxstart, bool maps, const in
     std::vector<int> n2max(4 * kNumBuckets, 0);
     for (int p = 0; p < npairs; p++) {
         const int n2 = ctx->h_orders[(size_t)entry[p]];
-        const int g = cls_of[(size_t)query[p]] * kNumBuckets + order_bucket(n2);
+        const int g = ctx->queries[(size_t)query[p]].cls * kNumBuckets + order_bucket(n2);
         members[(size_t)g].push_back(p);
         if (n2 > n2max[(size_t)g]) n2max[(size_t)g] = n2;
     }
@@ -860,7 +789,7 @@ int sat_pairs_launch(sat_ctx *ctx, int lorder, int maxstart, bool maps, const in
             for (int r0 = 0; r0 < maxstart; r0 += split) {
                 SatPairItem it{};
                 it.pair = p;
-                it.desc = desc_of[(size_t)query[p]];
+                it.desc = ctx->queries[(size_t)query[p]].desc;
                 it.entry = entry[p];
                 it.r0 = r0;
                 it.r1 = maxstart - r0 < split ? maxstart : r0 + split;
@@ -879,32 +808,32 @@ int sat_pairs_launch(sat_ctx *ctx, int lorder, int maxstart, bool maps, const in
             for (int p : members[(size_t)g]) {
                 SatPairItem it{};
                 it.pair = p;
-                it.desc = desc_of[(size_t)query[p]];
+                it.desc = ctx->queries[(size_t)query[p]].desc;
                 it.entry = entry[p];
                 items.push_back(it);
             }
             moff.push_back(items.size());
         }
     }
-    if ((rc = grow_scratch(ctx, ctx->d_pitems, ctx->pitems_cap, items.size())) != SAT_OK) return rc;
-    if ((rc = grow_scratch(ctx, ctx->d_pkeys, ctx->pkeys_cap, (size_t)npairs)) != SAT_OK) return rc;
-    if (maps && (rc = grow_scratch(ctx, ctx->d_pmaps, ctx->pmaps_cap, (size_t)npairs * SAT_MAXDIM)) != SAT_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->d_pitems, items.data(), items.size() * sizeof(SatPairItem), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemsetAsync(ctx->d_pkeys, 0, (size_t)npairs * sizeof(unsigned long long), ctx->stream));
+    if ((rc = ctx->d_pitems.grow_after(ctx->stream, items.size())) != SAT_OK) return rc;
+    if ((rc = ctx->d_pkeys.grow_after(ctx->stream, (size_t)npairs)) != SAT_OK) return rc;
+    if (maps && (rc = ctx->d_pmaps.grow_after(ctx->stream, (size_t)npairs * SAT_MAXDIM)) != SAT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->d_pitems.get(), items.data(), items.size() * sizeof(SatPairItem), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->d_pkeys.get(), 0, (size_t)npairs * sizeof(unsigned long long), ctx->stream));
     std::string info;
-    rc = launch_pair_pass(ctx, lorder, false, split, ctx->d_pitems, goff, gcls, gn2, info);
+    rc = launch_pair_pass(ctx, lorder, false, split, ctx->d_pitems.get(), goff, gcls, gn2, info);
     if (rc != SAT_OK) return rc;
     char head[96];
     snprintf(head, sizeof head, "score pass (%d restarts, %d per item): ", maxstart, split);
     ctx->last_launch_info = head + info;
     if (maps) {
         const int n_map = (int)(items.size() - n_score);
-        HIP_TRY(hipMemsetAsync(ctx->d_pmaps, 0xFF, (size_t)npairs * SAT_MAXDIM, ctx->stream));
+        HIP_TRY(hipMemsetAsync(ctx->d_pmaps.get(), 0xFF, (size_t)npairs * SAT_MAXDIM, ctx->stream));
         hipLaunchKernelGGL(pair_winners, dim3((unsigned)((n_map + 255) / 256)), dim3(256), 0, ctx->stream,
-                           ctx->d_pitems + n_score, n_map, ctx->d_pkeys);
+                           ctx->d_pitems.get() + n_score, n_map, ctx->d_pkeys.get());
         HIP_TRY(hipGetLastError());
         info.clear();
-        rc = launch_pair_pass(ctx, lorder, true, 1, ctx->d_pitems, moff, gcls, gn2, info);
+        rc = launch_pair_pass(ctx, lorder, true, 1, ctx->d_pitems.get(), moff, gcls, gn2, info);
         if (rc != SAT_OK) return rc;
         ctx->last_launch_info += " | map pass: " + info;
     }
@@ -920,16 +849,17 @@ int sat_pairs_collect(sat_ctx *ctx, int npairs, int32_t *scores, int32_t *ssemap
 {
     HIP_TRY(hipSetDevice(ctx->device));
     if (npairs == 0) return SAT_OK;
-    int rc;
-    if ((rc = grow_scratch(ctx, ctx->d_pscores, ctx->pscores_cap, (size_t)npairs)) != SAT_OK) return rc;
-    hipLaunchKernelGGL(pair_scores, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_pkeys, npairs, ctx->d_pscores);
+    const int rc = ctx->d_pscores.grow_after(ctx->stream, (size_t)npairs);
+    if (rc != SAT_OK) return rc;
+    hipLaunchKernelGGL(pair_scores, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_pkeys.get(), npairs,
+                       ctx->d_pscores.get());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(scores, ctx->d_pscores, (size_t)npairs * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(scores, ctx->d_pscores.get(), (size_t)npairs * sizeof(int32_t), hipMemcpyDeviceToHost));
     ctx->d2h_bytes += (size_t)npairs * sizeof(int32_t);
     if (ssemaps) {
         std::vector<int8_t> mp((size_t)npairs * SAT_MAXDIM);
-        HIP_TRY(hipMemcpy(mp.data(), ctx->d_pmaps, mp.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(mp.data(), ctx->d_pmaps.get(), mp.size(), hipMemcpyDeviceToHost));
         ctx->d2h_bytes += mp.size();
         for (int p = 0; p < npairs; p++) {
             const int n1 = ctx->queries[(size_t)query[p]].n1;
@@ -971,6 +901,24 @@ __global__ void __launch_bounds__(256) validate_cells(int e_begin, int e_end, co
     if (__builtin_amdgcn_ballot_w64(bad) != 0ull && lane == 0) atomicMin(first_bad, e);
 }
 
+// queue `launch` on the context's stream between its two timing events, wait for it, *kernel_ms (may be null) = the
+// time between the events
+template <typename F> int timed(sat_ctx *ctx, double *kernel_ms, F launch)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    const int rc = launch();
+    if (rc != SAT_OK) return rc;
+    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (kernel_ms) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+        *kernel_ms = ms;
+    }
+    return SAT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -990,16 +938,16 @@ sat_ctx *sat_ctx_create(int device, uint64_t seed)
 {
     int n = sat_device_count();
     if (n <= 0) {
-        fail(SAT_ENODEVICE, "no HIP device available (this library has no CPU path)");
+        sat_fail(SAT_ENODEVICE, "no HIP device available (this library has no CPU path)");
         return nullptr;
     }
     if (device < 0 || device >= n) {
-        fail(SAT_ENODEVICE, "device %d out of range (0..%d)", device, n - 1);
+        sat_fail(SAT_ENODEVICE, "device %d out of range (0..%d)", device, n - 1);
         return nullptr;
     }
     sat_ctx *ctx = new (std::nothrow) sat_ctx();
     if (!ctx) {
-        fail(SAT_ENOMEM, "out of host memory");
+        sat_fail(SAT_ENOMEM, "out of host memory");
         return nullptr;
     }
     ctx->device = device;
@@ -1054,45 +1002,16 @@ void sat_ctx_destroy(sat_ctx *ctx)
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    free_db(ctx);
-    dev_free(ctx->d_qblob);
-    dev_free(ctx->d_qdesc);
-    dev_free(ctx->d_bmap_slabs);
-    dev_free(ctx->d_mcounts);
-    dev_free(ctx->d_mscores);
-    dev_free(ctx->d_mrestarts);
-    dev_free(ctx->d_mmaps);
-    dev_free(ctx->d_pitems);
-    dev_free(ctx->d_pkeys);
-    dev_free(ctx->d_pmaps);
-    dev_free(ctx->d_pscores);
-    dev_free(ctx->d_rkeys);
-    dev_free(ctx->d_rsorted);
-    dev_free(ctx->d_rvals);
-    dev_free(ctx->d_rvals_sorted);
-    dev_free(ctx->d_rfirst);
-    dev_free(ctx->d_rmaps);
-    dev_free(ctx->d_rhits);
-    dev_free(ctx->d_ptab);
-    dev_free(ctx->d_prow);
-    dev_free(ctx->d_keys);
-    dev_free(ctx->d_sorted);
-    dev_free(ctx->d_sort_temp);
-    dev_free(ctx->d_hitq);
-    dev_free(ctx->d_seg);
-    dev_free(ctx->d_hits);
-    dev_free(ctx->d_hit_maps);
-    dev_free(ctx->d_gumbel_z);
-    dev_free(ctx->d_gumbel_p);
-    if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-    if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-    if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
-    for (int b = 0; b < kNumBuckets; b++) {
-        if (ctx->ev_join[b]) (void)hipEventDestroy(ctx->ev_join[b]);
-        if (ctx->side_stream[b]) (void)hipStreamDestroy(ctx->side_stream[b]);
-    }
-    if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
+    // the device buffers go with the context, freed with its device current; then its events and streams
+    std::vector<hipEvent_t> events = { ctx->ev0, ctx->ev1, ctx->ev_fork };
+    events.insert(events.end(), ctx->ev_join, ctx->ev_join + kNumBuckets);
+    std::vector<hipStream_t> streams(ctx->side_stream, ctx->side_stream + kNumBuckets);
+    streams.push_back(ctx->own_stream);
     delete ctx;
+    for (hipEvent_t e : events)
+        if (e) (void)hipEventDestroy(e);
+    for (hipStream_t st : streams)
+        if (st) (void)hipStreamDestroy(st);
 }
 
 // What sat_db_upload_search asks of the upload: the first search of the current query batch, queued piece
@@ -1127,12 +1046,12 @@ static int upload_impl(sat_ctx *ctx, int n_entries, const int32_t *orders,
                        const int64_t *cell_off, const uint8_t *tab_tri,
                        const float *dist_tri, const int64_t *db_ordinal, const FirstSearch *first)
 {
-    if (!ctx) return fail(SAT_EINVAL, "null context");
+    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
     if (n_entries <= 0 || !orders || !cell_off || !tab_tri || !dist_tri)
-        return fail(SAT_EINVAL, "empty database or null array");
+        return sat_fail(SAT_EINVAL, "empty database or null array");
     if (first) {
-        if (ctx->queries.empty()) return fail(SAT_ESTATE, "no query set");
-        if (first->maxstart < 1) return fail(SAT_EINVAL, "maxstart must be >= 1 (got %d)", first->maxstart);
+        const int rc = check_ready(ctx, false, first->maxstart);
+        if (rc != SAT_OK) return rc;
     }
     // header pass on the host (orders, offsets, ordinals: a few bytes per entry).  The CELLS - every
     // code byte and distance, 331 MB for the bench shard - are checked on the GPU after the copy, at
@@ -1142,13 +1061,13 @@ static int upload_impl(sat_ctx *ctx, int n_entries, const int32_t *orders,
     for (int e = 0; e < n_entries; e++) {
         const int n = orders[e];
         if (n < 1 || n > SAT_MAXDIM)
-            return fail(SAT_EINVAL, "entry %d: order %d outside 1..%d", e, n, SAT_MAXDIM);
-        if (cell_off[e] < 0) return fail(SAT_EINVAL, "entry %d: negative cell offset", e);
+            return sat_fail(SAT_EINVAL, "entry %d: order %d outside 1..%d", e, n, SAT_MAXDIM);
+        if (cell_off[e] < 0) return sat_fail(SAT_EINVAL, "entry %d: negative cell offset", e);
         if (cell_off[e] < cells_end) ascending = false;
         int64_t end = cell_off[e] + (int64_t)n * (n + 1) / 2;
         if (end > cells_end) cells_end = end;
         if (db_ordinal && (db_ordinal[e] < 0 || db_ordinal[e] > 0xFFFFFFFFll))
-            return fail(SAT_EINVAL, "entry %d: db ordinal out of range", e);
+            return sat_fail(SAT_EINVAL, "entry %d: db ordinal out of range", e);
     }
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1202,28 +1121,27 @@ static int upload_impl(sat_ctx *ctx, int n_entries, const int32_t *orders,
     for (int e = 0; e < n_entries; e++) ord[e] = db_ordinal ? (uint32_t)db_ordinal[e] : (uint32_t)e;
 
     lap("host lists");
-    int32_t *d_bad = nullptr;
+    DevBuf<int32_t> d_bad;
     const int32_t none = 0x7FFFFFFF;
     // any failure below leaves the context without a database
     auto body = [&]() -> int {
-        HIP_TRY(hipMalloc(&ctx->d_orders, (size_t)n_entries * sizeof(int32_t)));
-        HIP_TRY(hipMalloc(&ctx->d_cell_off, (size_t)n_entries * sizeof(int64_t)));
-        HIP_TRY(hipMalloc(&ctx->d_ordinal, (size_t)n_entries * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(&ctx->d_lists, lists.size() * sizeof(int32_t)));
-        HIP_TRY(hipMalloc(&ctx->d_tab, (size_t)cells_end));
-        HIP_TRY(hipMalloc(&ctx->d_dist, (size_t)cells_end * sizeof(float)));
-        HIP_TRY(hipMalloc(&ctx->d_scores, (size_t)n_entries * sizeof(int32_t)));
-        HIP_TRY(hipMalloc(&d_bad, sizeof(int32_t)));
+        const size_t n = (size_t)n_entries;
+        int rc;
+        // (scores: one row, so that the first search of one query does not re-allocate them - refresh_descriptors)
+        if ((rc = ctx->d_orders.grow(n)) != SAT_OK || (rc = ctx->d_cell_off.grow(n)) != SAT_OK ||
+            (rc = ctx->d_ordinal.grow(n)) != SAT_OK || (rc = ctx->d_lists.grow(lists.size())) != SAT_OK ||
+            (rc = ctx->d_tab.grow((size_t)cells_end)) != SAT_OK || (rc = ctx->d_dist.grow((size_t)cells_end)) != SAT_OK ||
+            (rc = ctx->d_scores.grow(n)) != SAT_OK || (rc = d_bad.grow(1)) != SAT_OK)
+            return rc;
         lap("hipMalloc");
         // the headers first: the piece-wise checks and searches read them
-        HIP_TRY(hipMemcpy(ctx->d_orders, orders, (size_t)n_entries * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(ctx->d_cell_off, cell_off, (size_t)n_entries * sizeof(int64_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(ctx->d_ordinal, ord.data(), (size_t)n_entries * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(ctx->d_lists, lists.data(), lists.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(ctx->d_scores, 0, (size_t)n_entries * sizeof(int32_t)));
-        HIP_TRY(hipMemcpy(d_bad, &none, sizeof none, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(ctx->d_orders.get(), orders, n * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(ctx->d_cell_off.get(), cell_off, n * sizeof(int64_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(ctx->d_ordinal.get(), ord.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(ctx->d_lists.get(), lists.data(), lists.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(ctx->d_scores.get(), 0, n * sizeof(int32_t)));
+        HIP_TRY(hipMemcpy(d_bad.get(), &none, sizeof none, hipMemcpyHostToDevice));
         lap("header copies");
-        ctx->scores_cap = (size_t)n_entries;     // what refresh_descriptors compares with: no re-allocation for one query
         ctx->n_entries = n_entries;
 
         // The two big arrays go up in slices from a few host threads (each slice a synchronous copy out
@@ -1247,8 +1165,8 @@ static int upload_impl(sat_ctx *ctx, int n_entries, const int32_t *orders,
                 if (hi > lo && err[(size_t)t] == hipSuccess)
                     err[(size_t)t] = hipMemcpy((char *)dst + base + lo, (const char *)src + base + lo, hi - lo, hipMemcpyHostToDevice);
             };
-            part(dist_tri, ctx->d_dist, sizeof(float));
-            part(tab_tri, ctx->d_tab, 1);
+            part(dist_tri, ctx->d_dist.get(), sizeof(float));
+            part(tab_tri, ctx->d_tab.get(), 1);
             landed[(size_t)c].fetch_add(1, std::memory_order_release);
         };
         // (the runtime takes the copies of all threads through one queue: a thread running ahead into piece
@@ -1266,7 +1184,7 @@ static int upload_impl(sat_ctx *ctx, int n_entries, const int32_t *orders,
         };
         std::vector<std::thread> pool;
         for (int t = 1; t < nthreads; t++) pool.emplace_back(helper, t);
-        int rc = SAT_OK;
+        rc = SAT_OK;
         for (int c = 0; c < npieces; c++) {
             copy_piece(0, c);
             piece_complete(c);
@@ -1278,11 +1196,11 @@ static int upload_impl(sat_ctx *ctx, int n_entries, const int32_t *orders,
             const int e0 = piece_e[(size_t)c], e1 = piece_e[(size_t)c + 1];
             if (e1 <= e0) continue;
             hipLaunchKernelGGL(validate_cells, dim3((unsigned)((e1 - e0 + 3) / 4)), dim3(256), 0, ctx->stream,
-                               e0, e1, ctx->d_orders, ctx->d_cell_off, ctx->d_tab, ctx->d_dist, d_bad);
-            if (hipGetLastError() != hipSuccess) { rc = fail(SAT_EDEVICE, "launch of the cell check failed"); continue; }
+                               e0, e1, ctx->d_orders.get(), ctx->d_cell_off.get(), ctx->d_tab.get(), ctx->d_dist.get(), d_bad.get());
+            if (hipGetLastError() != hipSuccess) { rc = sat_fail(SAT_EDEVICE, "launch of the cell check failed"); continue; }
             if (first) {
                 if (npieces > 1) {
-                    const ListView piece = { ctx->d_lists, &piece_begin[(size_t)c * (kNumBuckets + 1)],
+                    const ListView piece = { ctx->d_lists.get(), &piece_begin[(size_t)c * (kNumBuckets + 1)],
                                              &piece_n2max[(size_t)c * kNumBuckets], e1 - e0 };
                     rc = launch_search(ctx, first->lorder, first->lsoln, first->maxstart, ctx->stream, &piece);
                 } else {
@@ -1296,7 +1214,7 @@ static int upload_impl(sat_ctx *ctx, int n_entries, const int32_t *orders,
         lap(first ? "cell copies, checks and the search queued" : "cell copies");
         int32_t bad = none;
         HIP_TRY(hipStreamSynchronize(ctx->stream));          // a non-blocking stream: the copy below does not wait for it
-        HIP_TRY(hipMemcpy(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&bad, d_bad.get(), sizeof bad, hipMemcpyDeviceToHost));
         lap(first ? "search + validate on GPU" : "validate on GPU");
         if (bad != none) {
             // the earliest flagged entry is looked at again on the host, cell by cell, for the message
@@ -1304,21 +1222,21 @@ static int upload_impl(sat_ctx *ctx, int n_entries, const int32_t *orders,
             for (int i = 0; i < n; i++) {
                 const int64_t rowbase = cell_off[e] + (int64_t)i * (i + 1) / 2;
                 uint8_t ty = tab_tri[rowbase + i];
-                if (ty > 3) return fail(SAT_EINVAL, "entry %d: SSE %d has type code %u (0..3 expected)", e, i, ty);
+                if (ty > 3) return sat_fail(SAT_EINVAL, "entry %d: SSE %d has type code %u (0..3 expected)", e, i, ty);
                 for (int j = 0; j < i; j++) {
                     if (tab_tri[rowbase + j] & 0x88)
-                        return fail(SAT_EINVAL, "entry %d: tableau code 0x%02x at (%d,%d) has a nibble above 7", e, tab_tri[rowbase + j], i, j);
+                        return sat_fail(SAT_EINVAL, "entry %d: tableau code 0x%02x at (%d,%d) has a nibble above 7", e, tab_tri[rowbase + j], i, j);
                     float d = dist_tri[rowbase + j];
                     if (std::isfinite(d) && std::fabs(d) >= 1.0e29f)
-                        return fail(SAT_EINVAL, "entry %d: distance %g at (%d,%d) out of range", e, d, i, j);
+                        return sat_fail(SAT_EINVAL, "entry %d: distance %g at (%d,%d) out of range", e, d, i, j);
                 }
             }
-            return fail(SAT_EINVAL, "entry %d: invalid cell", e);     // not reached: the scan and the re-check agree
+            return sat_fail(SAT_EINVAL, "entry %d: invalid cell", e);     // not reached: the scan and the re-check agree
         }
         return SAT_OK;
     };
     const int rc = body();
-    if (d_bad) (void)hipFree(d_bad);
+    d_bad.reset();
     if (rc != SAT_OK) {
         (void)hipStreamSynchronize(ctx->stream);
         free_db(ctx);
@@ -1348,14 +1266,14 @@ int sat_db_upload_dense(sat_ctx *ctx, int n_entries, const int32_t *orders,
                         const uint8_t *tabs, const float *dmats, int pitch,
                         const int64_t *db_ordinal)
 {
-    if (!ctx) return fail(SAT_EINVAL, "null context");
+    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
     if (n_entries <= 0 || !orders || !tabs || !dmats || pitch < 1)
-        return fail(SAT_EINVAL, "empty database or null array");
+        return sat_fail(SAT_EINVAL, "empty database or null array");
     std::vector<int64_t> off(n_entries);
     int64_t cells = 0;
     for (int e = 0; e < n_entries; e++) {
         if (orders[e] < 1 || orders[e] > SAT_MAXDIM || orders[e] > pitch)
-            return fail(SAT_EINVAL, "entry %d: order %d outside 1..min(%d, pitch %d)", e, orders[e], SAT_MAXDIM, pitch);
+            return sat_fail(SAT_EINVAL, "entry %d: order %d outside 1..min(%d, pitch %d)", e, orders[e], SAT_MAXDIM, pitch);
         off[e] = cells;
         cells += (int64_t)orders[e] * (orders[e] + 1) / 2;
     }
@@ -1379,15 +1297,15 @@ int sat_db_size(const sat_ctx *ctx) { return ctx ? ctx->n_entries : 0; }
 int sat_queries_set(sat_ctx *ctx, int n_queries, const int32_t *n1s, const uint8_t *qtabs,
                     const float *qdmats, int pitch, const uint8_t *qssetypes, uint32_t first_query_ordinal)
 {
-    if (!ctx) return fail(SAT_EINVAL, "null context");
+    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
     if (n_queries < 1 || !n1s || !qtabs || !qdmats || !qssetypes || pitch < 1)
-        return fail(SAT_EINVAL, "bad query batch (n_queries=%d pitch=%d)", n_queries, pitch);
+        return sat_fail(SAT_EINVAL, "bad query batch (n_queries=%d pitch=%d)", n_queries, pitch);
     std::vector<sat_ctx::QueryInfo> infos((size_t)n_queries);
     size_t blob_bytes = 0;
     for (int qi = 0; qi < n_queries; qi++) {
         const int n1 = n1s[qi];
         if (n1 < 1 || n1 > SAT_MAXDIM || n1 > pitch)
-            return fail(SAT_EINVAL, "query %d: order %d outside 1..min(%d, pitch %d)", qi, n1, SAT_MAXDIM, pitch);
+            return sat_fail(SAT_EINVAL, "query %d: order %d outside 1..min(%d, pitch %d)", qi, n1, SAT_MAXDIM, pitch);
         auto &q = infos[(size_t)qi];
         q.n1 = n1;
         q.n1p = n1 <= 16 ? 16 : (n1 <= 32 ? 32 : (n1 <= 64 ? 64 : 112));
@@ -1428,7 +1346,7 @@ int sat_queries_set(sat_ctx *ctx, int n_queries, const int32_t *n1s, const uint8
             }
         for (int i = 0; i < n1; i++) {
             if (types[i] > 3)
-                return fail(SAT_EINVAL, "query %d: SSE %d has type code %u (0..3 expected)", qi, i, types[i]);
+                return sat_fail(SAT_EINVAL, "query %d: SSE %d has type code %u (0..3 expected)", qi, i, types[i]);
             qtypes[i] = types[i];
         }
         for (int kw = 0; kw < groups; kw++)
@@ -1442,10 +1360,10 @@ int sat_queries_set(sat_ctx *ctx, int n_queries, const int32_t *n1s, const uint8
                         const float v = qdmat[(size_t)i * pitch + k];
                         const uint32_t code = qtab[(size_t)i * pitch + k];
                         if (code & 0x88)
-                            return fail(SAT_EINVAL, "query %d: tableau code 0x%02x at (%d,%d) has a nibble above 7", qi, code, i, k);
+                            return sat_fail(SAT_EINVAL, "query %d: tableau code 0x%02x at (%d,%d) has a nibble above 7", qi, code, i, k);
                         if (std::isfinite(v)) {
                             if (std::fabs(v) >= 1.0e29f)
-                                return fail(SAT_EINVAL, "query %d: distance %g at (%d,%d) out of range", qi, v, i, k);
+                                return sat_fail(SAT_EINVAL, "query %d: distance %g at (%d,%d) out of range", qi, v, i, k);
                             d[sidx] = v;
                         }
                         codes |= code << (8 * sidx);
@@ -1457,11 +1375,11 @@ int sat_queries_set(sat_ctx *ctx, int n_queries, const int32_t *n1s, const uint8
     }
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    dev_free(ctx->d_qblob);
-    dev_free(ctx->d_qdesc);
-    HIP_TRY(hipMalloc(&ctx->d_qblob, blob_bytes));
-    HIP_TRY(hipMalloc(&ctx->d_qdesc, (size_t)n_queries * sizeof(SatQuery)));
-    HIP_TRY(hipMemcpy(ctx->d_qblob, blob.data(), blob_bytes, hipMemcpyHostToDevice));
+    ctx->d_qblob.reset();
+    ctx->d_qdesc.reset();
+    int rc;
+    if ((rc = ctx->d_qblob.grow(blob_bytes)) != SAT_OK || (rc = ctx->d_qdesc.grow((size_t)n_queries)) != SAT_OK) return rc;
+    HIP_TRY(hipMemcpy(ctx->d_qblob.get(), blob.data(), blob_bytes, hipMemcpyHostToDevice));
     ctx->queries.swap(infos);
     ctx->desc_dirty = true;
     ctx->searched_nq = 0;                     // the result buffers no longer belong to the current batch
@@ -1471,9 +1389,9 @@ int sat_queries_set(sat_ctx *ctx, int n_queries, const int32_t *n1s, const uint8
 int sat_query_set(sat_ctx *ctx, int n1, const uint8_t *qtab, const float *qdmat,
                   int pitch, const uint8_t *qssetypes, uint32_t query_ordinal)
 {
-    if (!ctx) return fail(SAT_EINVAL, "null context");
+    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
     if (n1 < 1 || n1 > SAT_MAXDIM || !qtab || !qdmat || !qssetypes || pitch < n1)
-        return fail(SAT_EINVAL, "bad query (n1=%d pitch=%d)", n1, pitch);
+        return sat_fail(SAT_EINVAL, "bad query (n1=%d pitch=%d)", n1, pitch);
     // a batch of one; the type vector is only read up to n1, so its stride does not matter
     const int32_t n1s[1] = { n1 };
     return sat_queries_set(ctx, 1, n1s, qtab, qdmat, pitch, qssetypes, query_ordinal);
@@ -1483,7 +1401,7 @@ int sat_query_count(const sat_ctx *ctx) { return ctx ? (int)ctx->queries.size() 
 
 int sat_use_stream(sat_ctx *ctx, void *hip_stream)
 {
-    if (!ctx) return fail(SAT_EINVAL, "null context");
+    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->stream = static_cast<hipStream_t>(hip_stream);
@@ -1492,7 +1410,7 @@ int sat_use_stream(sat_ctx *ctx, void *hip_stream)
 
 int sat_use_own_stream(sat_ctx *ctx)
 {
-    if (!ctx) return fail(SAT_EINVAL, "null context");
+    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->stream = ctx->own_stream;
@@ -1501,12 +1419,12 @@ int sat_use_own_stream(sat_ctx *ctx)
 
 int sat_search_async(sat_ctx *ctx, int lorder, int lsoln, int maxstart)
 {
-    if (!ctx) return fail(SAT_EINVAL, "null context");
+    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
     return launch_search(ctx, lorder, lsoln, maxstart, ctx->stream);
 }
 
-void *sat_device_scores(sat_ctx *ctx) { return ctx ? ctx->d_scores : nullptr; }
-void *sat_device_ssemaps(sat_ctx *ctx) { return ctx ? ctx->d_ssemaps : nullptr; }
+void *sat_device_scores(sat_ctx *ctx) { return ctx ? ctx->d_scores.get() : nullptr; }
+void *sat_device_ssemaps(sat_ctx *ctx) { return ctx ? ctx->d_ssemaps.get() : nullptr; }
 int sat_query_order(const sat_ctx *ctx) { return (ctx && !ctx->queries.empty()) ? ctx->queries[0].n1 : 0; }
 
 unsigned long long sat_stat_d2h_bytes(const sat_ctx *ctx) { return ctx ? ctx->d2h_bytes : 0ull; }
@@ -1528,7 +1446,7 @@ void sat_debug_lds_layout(int m2w, int n1, int n1p, int n2, int chains, int thre
 
 int sat_sync(sat_ctx *ctx)
 {
-    if (!ctx) return fail(SAT_EINVAL, "null context");
+    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return SAT_OK;
@@ -1536,24 +1454,24 @@ int sat_sync(sat_ctx *ctx)
 
 int sat_results(sat_ctx *ctx, int lsoln, int32_t *scores, int32_t *ssemaps)
 {
-    if (!ctx) return fail(SAT_EINVAL, "null context");
-    if (!scores) return fail(SAT_EINVAL, "scores buffer is null");
-    if (lsoln && !ssemaps) return fail(SAT_EINVAL, "lsoln set but ssemaps buffer is null");
-    if (ctx->n_entries <= 0) return fail(SAT_ESTATE, "no database uploaded");
-    if (ctx->queries.empty() || !ctx->d_scores || ctx->searched_nq != ctx->queries.size())
-        return fail(SAT_ESTATE, "no search has run since the last database upload / query change");
+    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
+    if (!scores) return sat_fail(SAT_EINVAL, "scores buffer is null");
+    if (lsoln && !ssemaps) return sat_fail(SAT_EINVAL, "lsoln set but ssemaps buffer is null");
+    if (ctx->n_entries <= 0) return sat_fail(SAT_ESTATE, "no database uploaded");
+    if (ctx->queries.empty() || !ctx->d_scores.get() || ctx->searched_nq != ctx->queries.size())
+        return sat_fail(SAT_ESTATE, "no search has run since the last database upload / query change");
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     const size_t nq = ctx->queries.size(), N = (size_t)ctx->n_entries;
-    HIP_TRY(hipMemcpy(scores, ctx->d_scores, nq * N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(scores, ctx->d_scores.get(), nq * N * sizeof(int32_t), hipMemcpyDeviceToHost));
     ctx->d2h_bytes += nq * N * sizeof(int32_t);
     if (lsoln) {
-        if (!ctx->d_ssemaps || !ctx->searched_lsoln) return fail(SAT_ESTATE, "the last search ran without lsoln");
+        if (!ctx->d_ssemaps.get() || !ctx->searched_lsoln) return sat_fail(SAT_ESTATE, "the last search ran without lsoln");
         std::vector<int8_t> packed;
         for (size_t qi = 0; qi < nq; qi++) {
             const auto &q = ctx->queries[qi];
             packed.resize(N * q.n1);
-            HIP_TRY(hipMemcpy(packed.data(), ctx->d_ssemaps + q.ssemap_off, packed.size(), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(packed.data(), ctx->d_ssemaps.get() + q.ssemap_off, packed.size(), hipMemcpyDeviceToHost));
             ctx->d2h_bytes += packed.size();
             int32_t *out = ssemaps + qi * N * SAT_MAXDIM;
             for (size_t e = 0; e < N; e++)
@@ -1567,20 +1485,11 @@ int sat_results(sat_ctx *ctx, int lsoln, int32_t *scores, int32_t *ssemaps)
 int sat_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart,
                int32_t *scores, int32_t *ssemaps, double *kernel_ms)
 {
-    if (!ctx) return fail(SAT_EINVAL, "null context");
-    if (!scores) return fail(SAT_EINVAL, "scores buffer is null");
-    if (lsoln && !ssemaps) return fail(SAT_EINVAL, "lsoln set but ssemaps buffer is null");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    int rc = launch_search(ctx, lorder, lsoln, maxstart, ctx->stream);
+    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
+    if (!scores) return sat_fail(SAT_EINVAL, "scores buffer is null");
+    if (lsoln && !ssemaps) return sat_fail(SAT_EINVAL, "lsoln set but ssemaps buffer is null");
+    const int rc = timed(ctx, kernel_ms, [&] { return launch_search(ctx, lorder, lsoln, maxstart, ctx->stream); });
     if (rc != SAT_OK) return rc;
-    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (kernel_ms) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-        *kernel_ms = ms;
-    }
     return sat_results(ctx, lsoln, scores, ssemaps);
 }
 
@@ -1588,53 +1497,29 @@ int sat_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart,
 
 int sat_matches_launch(sat_ctx *ctx, int lorder, int maxstart, int max_matches, bool maps)
 {
-    if (!ctx) return fail(SAT_EINVAL, "null context");
+    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
     if (max_matches < 1 || max_matches > SAT_MAX_MATCHES)
-        return fail(SAT_EINVAL, "max_matches must be 1..%d (got %d)", SAT_MAX_MATCHES, max_matches);
-    if (ctx->n_entries <= 0) return fail(SAT_ESTATE, "no database uploaded");
-    if (ctx->queries.empty()) return fail(SAT_ESTATE, "no query set");
-    if (maxstart < 1) return fail(SAT_EINVAL, "maxstart must be >= 1 (got %d)", maxstart);
+        return sat_fail(SAT_EINVAL, "max_matches must be 1..%d (got %d)", SAT_MAX_MATCHES, max_matches);
+    int rc = check_ready(ctx, true, maxstart);
+    if (rc != SAT_OK) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t rows = ctx->queries.size() * (size_t)ctx->n_entries;
-    // each buffer against its own capacity in elements (counts: one per row, scores / restarts: M per row, maps:
-    // M x SAT_MAXDIM bytes per row); a capacity is reset before its buffer is replaced, so a failed allocation
-    // leaves none that claims more than it holds
-    const size_t slots = rows * (size_t)max_matches;
-    if (rows > ctx->mcounts_cap) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        dev_free(ctx->d_mcounts);
-        ctx->mcounts_cap = 0;
-        HIP_TRY(hipMalloc(&ctx->d_mcounts, rows * sizeof(int32_t)));
-        ctx->mcounts_cap = rows;
-    }
-    if (slots > ctx->mslots_cap) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        dev_free(ctx->d_mscores);
-        dev_free(ctx->d_mrestarts);
-        ctx->mslots_cap = 0;
-        HIP_TRY(hipMalloc(&ctx->d_mscores, slots * sizeof(int32_t)));
-        HIP_TRY(hipMalloc(&ctx->d_mrestarts, slots * sizeof(int32_t)));
-        ctx->mslots_cap = slots;
-    }
-    const size_t map_bytes = maps ? slots * SAT_MAXDIM : 0;
-    if (map_bytes > ctx->mmaps_cap) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        dev_free(ctx->d_mmaps);
-        ctx->mmaps_cap = 0;
-        HIP_TRY(hipMalloc(&ctx->d_mmaps, map_bytes));
-        ctx->mmaps_cap = map_bytes;
-    }
+    // counts: one per row, scores / restarts: M per row, maps: M x SAT_MAXDIM bytes per row
+    const size_t rows = ctx->queries.size() * (size_t)ctx->n_entries, slots = rows * (size_t)max_matches;
+    if ((rc = ctx->d_mcounts.grow_after(ctx->stream, rows)) != SAT_OK || (rc = ctx->d_mscores.grow_after(ctx->stream, slots)) != SAT_OK ||
+        (rc = ctx->d_mrestarts.grow_after(ctx->stream, slots)) != SAT_OK ||
+        (rc = ctx->d_mmaps.grow_after(ctx->stream, maps ? slots * SAT_MAXDIM : 0)) != SAT_OK)
+        return rc;
     SatMatchArgs mx{};
-    mx.desc_base = ctx->d_qdesc;
+    mx.desc_base = ctx->d_qdesc.get();
     mx.n_entries = ctx->n_entries;
     mx.max_matches = max_matches;
     mx.replay = 0;
     mx.map_pitch = SAT_MAXDIM;
-    mx.counts = ctx->d_mcounts;
-    mx.scores = ctx->d_mscores;
-    mx.restarts = ctx->d_mrestarts;
-    mx.maps = ctx->d_mmaps;
-    int rc = launch_search(ctx, lorder, 0, maxstart, ctx->stream, nullptr, &mx);
+    mx.counts = ctx->d_mcounts.get();
+    mx.scores = ctx->d_mscores.get();
+    mx.restarts = ctx->d_mrestarts.get();
+    mx.maps = ctx->d_mmaps.get();
+    rc = launch_search(ctx, lorder, 0, maxstart, ctx->stream, nullptr, &mx);
     if (rc != SAT_OK) return rc;
     // sat_last_launch_info names both passes
     const std::string record_info = ctx->last_launch_info;
@@ -1656,18 +1541,14 @@ int sat_matches_collect(sat_ctx *ctx, int max_matches, int32_t *counts, int32_t 
     const size_t nq = ctx->queries.size(), N = (size_t)ctx->n_entries, M = (size_t)max_matches;
     std::vector<int32_t> c(nq * N), sc(nq * N * M), rs(nq * N * M);
     std::vector<int8_t> mp(ssemaps ? nq * N * M * SAT_MAXDIM : 0);
-    HIP_TRY(hipMemcpy(c.data(), ctx->d_mcounts, c.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(sc.data(), ctx->d_mscores, sc.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(rs.data(), ctx->d_mrestarts, rs.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (ssemaps) HIP_TRY(hipMemcpy(mp.data(), ctx->d_mmaps, mp.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(c.data(), ctx->d_mcounts.get(), c.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sc.data(), ctx->d_mscores.get(), sc.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rs.data(), ctx->d_mrestarts.get(), rs.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (ssemaps) HIP_TRY(hipMemcpy(mp.data(), ctx->d_mmaps.get(), mp.size(), hipMemcpyDeviceToHost));
     ctx->d2h_bytes += (c.size() + sc.size() + rs.size()) * sizeof(int32_t) + mp.size();
     // device rows are by descriptor index: the queries grouped by size class (refresh_descriptors)
-    std::vector<size_t> desc_query;
-    for (int cl = 0; cl < 4; cl++)
-        for (size_t qi = 0; qi < nq; qi++)
-            if (ctx->queries[qi].n1p == kClassN1P[cl]) desc_query.push_back(qi);
-    for (size_t d = 0; d < nq; d++) {
-        const size_t qi = desc_query[d];
+    for (size_t qi = 0; qi < nq; qi++) {
+        const size_t d = (size_t)ctx->queries[qi].desc;
         const int n1 = ctx->queries[qi].n1;
         for (size_t e = 0; e < N; e++) {
             const size_t src = d * N + e, dst = qi * total + offset + e;
@@ -1691,47 +1572,29 @@ extern "C" {
 int sat_search_matches(sat_ctx *ctx, int lorder, int maxstart, int max_matches, int32_t *counts, int32_t *scores,
                        int32_t *restarts, int32_t *ssemaps, double *kernel_ms)
 {
-    if (!ctx) return fail(SAT_EINVAL, "null context");
-    if (!counts || !scores || !restarts) return fail(SAT_EINVAL, "counts / scores / restarts buffer is null");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    int rc = sat_matches_launch(ctx, lorder, maxstart, max_matches, ssemaps != nullptr);
+    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
+    if (!counts || !scores || !restarts) return sat_fail(SAT_EINVAL, "counts / scores / restarts buffer is null");
+    const int rc = timed(ctx, kernel_ms, [&] { return sat_matches_launch(ctx, lorder, maxstart, max_matches, ssemaps != nullptr); });
     if (rc != SAT_OK) return rc;
-    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (kernel_ms) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-        *kernel_ms = ms;
-    }
     return sat_matches_collect(ctx, max_matches, counts, scores, restarts, ssemaps, (size_t)ctx->n_entries, 0);
 }
 
 int sat_search_pairs(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int npairs, const int32_t *query,
                      const int32_t *entry, int32_t *scores, int32_t *ssemaps, double *kernel_ms)
 {
-    if (!ctx) return fail(SAT_EINVAL, "null context");
-    if (npairs > 0 && !scores) return fail(SAT_EINVAL, "scores buffer is null");
-    if (lsoln && npairs > 0 && !ssemaps) return fail(SAT_EINVAL, "lsoln set but ssemaps buffer is null");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    int rc = sat_pairs_launch(ctx, lorder, maxstart, lsoln != 0, query, entry, npairs);
+    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
+    if (npairs > 0 && !scores) return sat_fail(SAT_EINVAL, "scores buffer is null");
+    if (lsoln && npairs > 0 && !ssemaps) return sat_fail(SAT_EINVAL, "lsoln set but ssemaps buffer is null");
+    const int rc = timed(ctx, kernel_ms, [&] { return sat_pairs_launch(ctx, lorder, maxstart, lsoln != 0, query, entry, npairs); });
     if (rc != SAT_OK) return rc;
-    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (kernel_ms) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-        *kernel_ms = ms;
-    }
     return sat_pairs_collect(ctx, npairs, scores, lsoln ? ssemaps : nullptr, query);
 }
 
 int sat_search_timed(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int repeats,
                      double *total_ms, double *kernel_ms)
 {
-    if (!ctx) return fail(SAT_EINVAL, "null context");
-    if (repeats < 1) return fail(SAT_EINVAL, "repeats must be >= 1");
+    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
+    if (repeats < 1) return sat_fail(SAT_EINVAL, "repeats must be >= 1");
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));

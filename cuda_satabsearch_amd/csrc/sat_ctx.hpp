@@ -8,10 +8,81 @@
 #include <string>
 #include <tuple>
 #include <unordered_set>
+#include <utility>
 #include <vector>
 
 #include "satabsearch.h"
 #include "sat_sa_kernel.hpp"
+
+// sets sat_last_error() text and returns `code`
+int sat_fail(int code, const char *fmt, ...);
+
+// a failed HIP call: sat_fail with its text, SAT_ENOMEM or SAT_EDEVICE
+#define HIP_TRY(expr)                                                                       \
+    do {                                                                                    \
+        hipError_t err__ = (expr);                                                          \
+        if (err__ != hipSuccess)                                                            \
+            return sat_fail(err__ == hipErrorOutOfMemory ? SAT_ENOMEM : SAT_EDEVICE,        \
+                            "%s failed: %s", #expr, hipGetErrorString(err__));              \
+    } while (0)
+
+// A device array of T that owns its allocation: the pointer and its capacity in elements live and die together.
+// Freed on destruction or reset(), on whatever device is current then (the owners make theirs current first).
+template <typename T> class DevBuf {
+  public:
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        if (this != &o) {
+            reset();
+            std::swap(p_, o.p_);
+            std::swap(cap_, o.cap_);
+        }
+        return *this;
+    }
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { reset(); }
+
+    T *get() const { return p_; }
+    size_t capacity() const { return cap_; }
+    void reset()
+    {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+        cap_ = 0;
+    }
+    // Room for `need` elements, contents not kept: when the capacity is smaller, the old allocation is replaced by
+    // one of exactly `need`.  *moved tells whether the pointer changed.  A failed allocation leaves the buffer empty.
+    int grow(size_t need, bool *moved = nullptr)
+    {
+        if (moved) *moved = need > cap_;
+        if (need <= cap_) return SAT_OK;
+        reset();
+        T *p = nullptr;
+        HIP_TRY(hipMalloc(&p, need * sizeof(T)));
+        p_ = p;
+        cap_ = need;
+        return SAT_OK;
+    }
+    // grow() that waits for `stream` before replacing the allocation: work queued there may still use it
+    int grow_after(hipStream_t stream, size_t need)
+    {
+        if (need > cap_) HIP_TRY(hipStreamSynchronize(stream));
+        return grow(need);
+    }
+    // a fresh allocation of exactly `n` elements
+    int alloc(size_t n)
+    {
+        reset();
+        return grow(n);
+    }
+
+  private:
+    T *p_ = nullptr;
+    size_t cap_ = 0;
+};
 
 constexpr int kNumBuckets = 7;
 
@@ -24,21 +95,23 @@ struct sat_ctx {
 
     // database shard
     int n_entries = 0;
-    int32_t *d_orders = nullptr;
-    int64_t *d_cell_off = nullptr;
-    uint8_t *d_tab = nullptr;
-    float *d_dist = nullptr;
-    uint32_t *d_ordinal = nullptr;
-    int32_t *d_lists = nullptr;             // entry indices grouped by bucket
+    DevBuf<int32_t> d_orders;
+    DevBuf<int64_t> d_cell_off;
+    DevBuf<uint8_t> d_tab;
+    DevBuf<float> d_dist;
+    DevBuf<uint32_t> d_ordinal;
+    DevBuf<int32_t> d_lists;                // entry indices grouped by bucket
     int bucket_begin[kNumBuckets + 1] = { 0 };
     int bucket_n2max[kNumBuckets] = { 0 };
     std::vector<int32_t> h_orders;
 
     // queries (a batch; one query is a batch of 1), input order
-    struct QueryInfo { int n1, n1p; uint32_t ordinal; size_t blob_off; size_t ssemap_off; };
+    // cls, desc: the query's size class and descriptor index (the descriptors are grouped by class, input order
+    // inside), set where the descriptors are built
+    struct QueryInfo { int n1, n1p; uint32_t ordinal; size_t blob_off; size_t ssemap_off; int cls, desc; };
     std::vector<QueryInfo> queries;
-    uint8_t *d_qblob = nullptr;             // per query: qdist | qcode | qtypes
-    SatQuery *d_qdesc = nullptr;            // descriptors grouped by size class
+    DevBuf<uint8_t> d_qblob;                // per query: qdist | qcode | qtypes
+    DevBuf<SatQuery> d_qdesc;               // descriptors grouped by size class
     int class_begin[5] = { 0, 0, 0, 0, 0 };  // classes: n1p = 16, 32, 64, 112
     int class_n1max[4] = { 0, 0, 0, 0 };
     int class_wpl[4] = { 0, 0, 0, 0 };       // map words per lane shared by the class's queries, 0 = mixed
@@ -46,8 +119,8 @@ struct sat_ctx {
     bool desc_lsoln = false;
 
     // Metropolis table
-    float *d_ptab = nullptr;
-    int32_t *d_prow = nullptr;
+    DevBuf<float> d_ptab;
+    DevBuf<int32_t> d_prow;
 
     // launch-heuristic overrides (SAT_EXP_* in satabsearch.h), read ONCE when the context is created
     struct Tuning { int compact = -1, qlds = -1, lpc = -1, general = 0, streams = -1, upload_threads = 0, upload_timing = 0, upload_pieces = 0, epw = 0, lpc_waves = 0, chains = 0, refine_split = 0; size_t lds_pad = 0; } tune;
@@ -69,47 +142,33 @@ struct sat_ctx {
     int min_rows = 0;
 
     // results: scores [nq][N]; ssemaps: query q's [N][n1_q] block at queries[q].ssemap_off
-    int32_t *d_scores = nullptr;
-    size_t scores_cap = 0;
-    int8_t *d_ssemaps = nullptr;
-    size_t ssemaps_cap = 0;
-    uint32_t *d_bmap_slabs = nullptr;        // LSOLN scratch: one best-map slab per workgroup of a launch
-    size_t bmap_slabs_cap = 0;               // in 32-bit words
+    DevBuf<int32_t> d_scores;
+    DevBuf<int8_t> d_ssemaps;
+    DevBuf<uint32_t> d_bmap_slabs;           // LSOLN scratch: one best-map slab per workgroup of a launch
     // several matches per entry (sat_search_matches): outputs by descriptor index d, rows d * n_entries + e
-    int32_t *d_mcounts = nullptr, *d_mscores = nullptr, *d_mrestarts = nullptr;
-    int8_t *d_mmaps = nullptr;               // [ndesc][N][M][SAT_MAXDIM]
-    size_t mcounts_cap = 0, mslots_cap = 0, mmaps_cap = 0;   // elements: rows / rows x M / map bytes
+    DevBuf<int32_t> d_mcounts, d_mscores, d_mrestarts;
+    DevBuf<int8_t> d_mmaps;                  // [ndesc][N][M][SAT_MAXDIM]
 
     // pair mode (sat_search_pairs): work items (host copy kept until the next pair search: the upload is
     // asynchronous), one 64-bit arg-max key and one map per pair, the scores the keys give
     std::vector<SatPairItem> h_pitems;
-    SatPairItem *d_pitems = nullptr;
-    size_t pitems_cap = 0;
-    unsigned long long *d_pkeys = nullptr;
-    size_t pkeys_cap = 0;
-    int8_t *d_pmaps = nullptr;               // [pairs][SAT_MAXDIM], -1 past n1
-    size_t pmaps_cap = 0;
-    int32_t *d_pscores = nullptr;
-    size_t pscores_cap = 0;
+    DevBuf<SatPairItem> d_pitems;
+    DevBuf<unsigned long long> d_pkeys;
+    DevBuf<int8_t> d_pmaps;                  // [pairs][SAT_MAXDIM], -1 past n1
+    DevBuf<int32_t> d_pscores;
     // refine (sat_search_refine, sat_topk.hip): the final ranking of the nq x C re-scored candidates
-    unsigned long long *d_rkeys = nullptr, *d_rsorted = nullptr;
-    int32_t *d_rvals = nullptr, *d_rvals_sorted = nullptr, *d_rfirst = nullptr, *d_rmaps = nullptr;
-    sat_hit *d_rhits = nullptr;
-    size_t rkeys_cap = 0, rsorted_cap = 0, rvals_cap = 0, rvals_sorted_cap = 0, rfirst_cap = 0, rmaps_cap = 0, rhits_cap = 0;
+    DevBuf<unsigned long long> d_rkeys, d_rsorted;
+    DevBuf<int32_t> d_rvals, d_rvals_sorted, d_rfirst, d_rmaps;
+    DevBuf<sat_hit> d_rhits;
 
-    // best-k selection (sat_topk.hip): context-owned scratch that only grows; capacities in elements
-    unsigned long long *d_keys = nullptr, *d_sorted = nullptr;
-    size_t keys_cap = 0, sorted_cap = 0;
-    unsigned char *d_sort_temp = nullptr, *d_hitq = nullptr;
-    size_t sort_temp_cap = 0, hitq_cap = 0;
-    int *d_seg = nullptr;
-    size_t seg_cap = 0;
-    sat_hit *d_hits = nullptr;
-    size_t hits_cap = 0;
-    int32_t *d_hit_maps = nullptr;
-    size_t hit_maps_cap = 0;
+    // best-k selection (sat_topk.hip): context-owned scratch that only grows
+    DevBuf<unsigned long long> d_keys, d_sorted;
+    DevBuf<unsigned char> d_sort_temp, d_hitq;
+    DevBuf<int> d_seg;
+    DevBuf<sat_hit> d_hits;
+    DevBuf<int32_t> d_hit_maps;
     // z and p of every truncated norm2 score -128 .. 127, computed by the HOST's libm (sat_gumbel.c)
-    double *d_gumbel_z = nullptr, *d_gumbel_p = nullptr;
+    DevBuf<double> d_gumbel_z, d_gumbel_p;
 
     // bytes copied device -> host by this context's result calls (sat_stat_d2h_bytes)
     unsigned long long d2h_bytes = 0;
@@ -117,9 +176,6 @@ struct sat_ctx {
     std::string last_launch_info;
 };
 
-
-// sets sat_last_error() text and returns `code`
-int sat_fail(int code, const char *fmt, ...);
 
 // The two halves of sat_search_matches (sat_capi.hip), for sat_multi_search_matches: queue both passes on the
 // context's stream, then wait and copy query q's row of entry e to row q * total + offset + e of the caller's arrays

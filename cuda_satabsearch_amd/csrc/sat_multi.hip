@@ -28,20 +28,14 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <tuple>
+#include <utility>
 #include <vector>
 
 #include "sat_ctx.hpp"
 #include "sat_cutoff.hpp"
 #include "host/sat_gumbel.h"
 #include "host/sat_shard.h"
-
-#define HIP_TRY(expr)                                                                       \
-    do {                                                                                    \
-        hipError_t err__ = (expr);                                                          \
-        if (err__ != hipSuccess)                                                            \
-            return sat_fail(err__ == hipErrorOutOfMemory ? SAT_ENOMEM : SAT_EDEVICE,        \
-                            "%s failed: %s", #expr, hipGetErrorString(err__));              \
-    } while (0)
 
 namespace {
 
@@ -86,10 +80,8 @@ struct sat_multi {
     bool rccl_required = false;                 // SAT_MULTI_GATHER=rccl: an RCCL failure is an error, no peer-copy fallback
     std::vector<ncclComm_t> comm;
     // gathered rows on device 0: [ndev][nq * pad_rows] scores, [ndev][pad_rows * sum(n1)] map bytes
-    int32_t *d_all_scores = nullptr;
-    size_t all_scores_cap = 0;
-    int8_t *d_all_maps = nullptr;
-    size_t all_maps_cap = 0;
+    DevBuf<int32_t> d_all_scores;
+    DevBuf<int8_t> d_all_maps;
     // pinned landing zone of the one device-to-host copy
     void *h_stage = nullptr;
     size_t h_stage_cap = 0;
@@ -102,17 +94,6 @@ namespace {
 int rccl_fail(ncclResult_t r, const char *what)
 {
     return sat_fail(SAT_EDEVICE, "%s failed: %s", what, g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "RCCL error");
-}
-
-template <typename T> int grow_dev(T *&p, size_t &cap, size_t need)
-{
-    if (need <= cap) return SAT_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    HIP_TRY(hipMalloc(&p, need * sizeof(T)));
-    cap = need;
-    return SAT_OK;
 }
 
 int grow_stage(sat_multi *m, size_t bytes)
@@ -147,6 +128,41 @@ void sync_all(sat_multi *m)
     for (int g = 0; g < m->ndev; g++) {
         if (hipSetDevice(m->devices[(size_t)g]) == hipSuccess) (void)hipStreamSynchronize(m->ctx[(size_t)g]->stream);
         (void)hipGetLastError();
+    }
+}
+
+// the error return of a call that has queued work on the GPUs: wait for all of them, keep the message
+int bail(sat_multi *m, int rc)
+{
+    const std::string msg = sat_last_error();
+    sync_all(m);
+    return sat_fail(rc, "%s", msg.c_str());
+}
+
+// step(g) for every shard g in turn (queue work on its GPU, or collect it); the first error bails
+template <typename F> int each_shard(sat_multi *m, F step)
+{
+    for (int g = 0; g < m->ndev; g++) {
+        const int rc = step(g);
+        if (rc != SAT_OK) return bail(m, rc);
+    }
+    return SAT_OK;
+}
+
+// The k-way merge of one query's per-shard runs, each ranked by score (descending): shard g's run is rows[g][lo] ..
+// rows[g][hi - 1] with {lo, hi} = run(g).  take(g, row) receives the first `count` rows of the merged order.  Equal
+// scores: the lower shard first - shards are contiguous, so that is database order.
+template <typename Run, typename Take>
+void merge_shards(const std::vector<std::vector<sat_hit>> &rows, size_t count, Run run, Take take)
+{
+    const size_t ndev = rows.size();
+    std::vector<size_t> head(ndev), end(ndev);
+    for (size_t g = 0; g < ndev; g++) std::tie(head[g], end[g]) = run((int)g);
+    for (size_t r = 0; r < count; r++) {
+        size_t bg = ndev;
+        for (size_t g = 0; g < ndev; g++)
+            if (head[g] < end[g] && (bg == ndev || rows[g][head[g]].score > rows[bg][head[bg]].score)) bg = g;
+        take((int)bg, head[bg]++);
     }
 }
 
@@ -255,8 +271,8 @@ void sat_multi_destroy(sat_multi *m)
     for (size_t g = 0; g < m->comm.size(); g++)
         if (m->comm[g]) (void)g_rccl.CommDestroy(m->comm[g]);
     if (!m->devices.empty()) (void)hipSetDevice(m->devices[0]);
-    if (m->d_all_scores) (void)hipFree(m->d_all_scores);
-    if (m->d_all_maps) (void)hipFree(m->d_all_maps);
+    m->d_all_scores.reset();
+    m->d_all_maps.reset();
     if (m->h_stage) (void)hipHostFree(m->h_stage);
     for (size_t g = 0; g < m->done.size(); g++)
         if (m->done[g]) (void)hipEventDestroy(m->done[g]);
@@ -351,15 +367,12 @@ int sat_multi_search(sat_multi *m, int lorder, int lsoln, int maxstart, int32_t 
     if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
     const auto t0 = std::chrono::steady_clock::now();
     // (an error below waits for the searches already queued on the other GPUs before it is returned)
-    auto bail = [&](int rc) { const std::string msg = sat_last_error(); sync_all(m); return sat_fail(rc, "%s", msg.c_str()); };
-    for (int g = 0; g < m->ndev; g++) {
-        int rc = sat_search_async(m->ctx[(size_t)g], lorder, lsoln, maxstart);
-        if (rc != SAT_OK) return bail(rc);
-    }
+    int rc = each_shard(m, [&](int g) { return sat_search_async(m->ctx[(size_t)g], lorder, lsoln, maxstart); });
+    if (rc != SAT_OK) return rc;
     sat_ctx *root = m->ctx[0];
     const size_t nq = root->queries.size(), N = (size_t)m->n_entries, pad = (size_t)m->pad_rows;
     if (m->ndev == 1 && !m->force_gather) {
-        int rc = sat_results(root, lsoln, scores, ssemaps);
+        rc = sat_results(root, lsoln, scores, ssemaps);
         if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         return rc;
     }
@@ -367,22 +380,23 @@ int sat_multi_search(sat_multi *m, int lorder, int lsoln, int maxstart, int32_t 
     size_t map_bytes_per_row = 0;
     for (const auto &q : root->queries) map_bytes_per_row += (size_t)q.n1;
     const size_t score_count = nq * pad, map_count = pad * map_bytes_per_row;
-    int rc;
-    if (hipSetDevice(m->devices[0]) != hipSuccess) return bail(sat_fail(SAT_EDEVICE, "hipSetDevice failed"));
-    if ((rc = grow_dev(m->d_all_scores, m->all_scores_cap, score_count * (size_t)m->ndev)) != SAT_OK) return bail(rc);
-    if (lsoln && (rc = grow_dev(m->d_all_maps, m->all_maps_cap, map_count * (size_t)m->ndev)) != SAT_OK) return bail(rc);
+    if (hipSetDevice(m->devices[0]) != hipSuccess) return bail(m, sat_fail(SAT_EDEVICE, "hipSetDevice failed"));
+    if ((rc = m->d_all_scores.grow(score_count * (size_t)m->ndev)) != SAT_OK) return bail(m, rc);
+    if (lsoln && (rc = m->d_all_maps.grow(map_count * (size_t)m->ndev)) != SAT_OK) return bail(m, rc);
     const size_t stage_bytes = score_count * (size_t)m->ndev * sizeof(int32_t) + (lsoln ? map_count * (size_t)m->ndev : 0);
-    if ((rc = grow_stage(m, stage_bytes)) != SAT_OK) return bail(rc);
-    if ((rc = gather_to_device0(m, m->d_all_scores, score_count, ncclInt32,
-                                [&](int g) { return (const int32_t *)m->ctx[(size_t)g]->d_scores; })) != SAT_OK) return bail(rc);
-    if (lsoln && (rc = gather_to_device0(m, m->d_all_maps, map_count, ncclInt8,
-                                         [&](int g) { return (const int8_t *)m->ctx[(size_t)g]->d_ssemaps; })) != SAT_OK) return bail(rc);
+    if ((rc = grow_stage(m, stage_bytes)) != SAT_OK) return bail(m, rc);
+    if ((rc = gather_to_device0(m, m->d_all_scores.get(), score_count, ncclInt32,
+                                [&](int g) { return (const int32_t *)m->ctx[(size_t)g]->d_scores.get(); })) != SAT_OK)
+        return bail(m, rc);
+    if (lsoln && (rc = gather_to_device0(m, m->d_all_maps.get(), map_count, ncclInt8,
+                                         [&](int g) { return (const int8_t *)m->ctx[(size_t)g]->d_ssemaps.get(); })) != SAT_OK)
+        return bail(m, rc);
     int32_t *h_scores = static_cast<int32_t *>(m->h_stage);
     int8_t *h_maps = reinterpret_cast<int8_t *>(h_scores + score_count * (size_t)m->ndev);
     auto to_host = [&]() -> int {
         HIP_TRY(hipSetDevice(m->devices[0]));
-        HIP_TRY(hipMemcpyAsync(h_scores, m->d_all_scores, score_count * (size_t)m->ndev * sizeof(int32_t), hipMemcpyDeviceToHost, root->stream));
-        if (lsoln) HIP_TRY(hipMemcpyAsync(h_maps, m->d_all_maps, map_count * (size_t)m->ndev, hipMemcpyDeviceToHost, root->stream));
+        HIP_TRY(hipMemcpyAsync(h_scores, m->d_all_scores.get(), score_count * (size_t)m->ndev * sizeof(int32_t), hipMemcpyDeviceToHost, root->stream));
+        if (lsoln) HIP_TRY(hipMemcpyAsync(h_maps, m->d_all_maps.get(), map_count * (size_t)m->ndev, hipMemcpyDeviceToHost, root->stream));
         HIP_TRY(hipStreamSynchronize(root->stream));
         for (int g = 1; g < m->ndev; g++) {                            // the senders' streams are done too
             HIP_TRY(hipSetDevice(m->devices[(size_t)g]));
@@ -390,7 +404,7 @@ int sat_multi_search(sat_multi *m, int lorder, int lsoln, int maxstart, int32_t 
         }
         return SAT_OK;
     };
-    if ((rc = to_host()) != SAT_OK) return bail(rc);
+    if ((rc = to_host()) != SAT_OK) return bail(m, rc);
     m->d2h_bytes += stage_bytes;
     // rows of shard g: scores [nq][n_g] at block g; maps: query q's [n_g][n1_q] block after those of queries 0..q-1
     for (int g = 0; g < m->ndev; g++) {
@@ -421,43 +435,32 @@ int sat_multi_search_topk(sat_multi *m, int lorder, int lsoln, int maxstart, int
     if (!hits || k < 1) return sat_fail(SAT_EINVAL, "bad top-k arguments");
     if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
     const auto t0 = std::chrono::steady_clock::now();
-    auto bail = [&](int rc) { const std::string msg = sat_last_error(); sync_all(m); return sat_fail(rc, "%s", msg.c_str()); };
-    for (int g = 0; g < m->ndev; g++) {
-        int rc = sat_search_async(m->ctx[(size_t)g], lorder, lsoln, maxstart);
-        if (rc != SAT_OK) return bail(rc);
-    }
+    int rc = each_shard(m, [&](int g) { return sat_search_async(m->ctx[(size_t)g], lorder, lsoln, maxstart); });
+    if (rc != SAT_OK) return rc;
     if (k > m->n_entries) k = m->n_entries;
     const int nq = (int)m->ctx[0]->queries.size();
     // every GPU ranks its own shard (k rows per query leave each GPU), the host merges ndev x k candidates
     std::vector<std::vector<sat_hit>> cand((size_t)m->ndev);
     std::vector<std::vector<int32_t>> cmaps((size_t)m->ndev);
-    std::vector<int> got((size_t)m->ndev, 0);
-    for (int g = 0; g < m->ndev; g++) {
+    std::vector<size_t> got((size_t)m->ndev, 0);
+    rc = each_shard(m, [&](int g) {
         cand[(size_t)g].resize((size_t)nq * k);
         if (ssemaps) cmaps[(size_t)g].resize((size_t)nq * k * SAT_MAXDIM);
         const int r = sat_topk_hits(m->ctx[(size_t)g], k, cand[(size_t)g].data(), ssemaps ? cmaps[(size_t)g].data() : nullptr);
-        if (r < 0) return bail(r);
-        got[(size_t)g] = r;
-    }
-    for (int q = 0; q < nq; q++) {
-        std::vector<int> head((size_t)m->ndev, 0);
-        for (int r = 0; r < k; r++) {
-            int bg = -1;
-            for (int g = 0; g < m->ndev; g++) {
-                if (head[(size_t)g] >= got[(size_t)g]) continue;
-                // ties in database order: shards are contiguous, so the lower GPU wins a tie
-                if (bg < 0 || cand[(size_t)g][(size_t)q * got[(size_t)g] + head[(size_t)g]].score >
-                                  cand[(size_t)bg][(size_t)q * got[(size_t)bg] + head[(size_t)bg]].score)
-                    bg = g;
-            }
-            const size_t row = (size_t)q * got[(size_t)bg] + head[(size_t)bg];
-            sat_hit h = cand[(size_t)bg][row];
-            h.entry += m->begin[(size_t)bg];
-            hits[(size_t)q * k + r] = h;
-            if (ssemaps) memcpy(ssemaps + ((size_t)q * k + r) * SAT_MAXDIM, cmaps[(size_t)bg].data() + row * SAT_MAXDIM, sizeof(int32_t) * SAT_MAXDIM);
-            head[(size_t)bg]++;
-        }
-    }
+        got[(size_t)g] = r < 0 ? 0 : (size_t)r;
+        return r < 0 ? r : SAT_OK;
+    });
+    if (rc != SAT_OK) return rc;
+    size_t out = 0;
+    for (size_t q = 0; q < (size_t)nq; q++)
+        merge_shards(cand, (size_t)k, [&](int g) { return std::make_pair(q * got[(size_t)g], (q + 1) * got[(size_t)g]); },
+                     [&](int g, size_t row) {
+                         hits[out] = cand[(size_t)g][row];
+                         hits[out].entry += m->begin[(size_t)g];
+                         if (ssemaps)
+                             memcpy(ssemaps + out * SAT_MAXDIM, cmaps[(size_t)g].data() + row * SAT_MAXDIM, sizeof(int32_t) * SAT_MAXDIM);
+                         out++;
+                     });
     if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return k;
 }
@@ -469,17 +472,14 @@ int sat_multi_search_matches(sat_multi *m, int lorder, int maxstart, int max_mat
     if (!counts || !scores || !restarts) return sat_fail(SAT_EINVAL, "counts / scores / restarts buffer is null");
     if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
     const auto t0 = std::chrono::steady_clock::now();
-    auto bail = [&](int rc) { const std::string msg = sat_last_error(); sync_all(m); return sat_fail(rc, "%s", msg.c_str()); };
     // both passes queued on every GPU, then each shard's rows copied to its place in database order
-    for (int g = 0; g < m->ndev; g++) {
-        const int rc = sat_matches_launch(m->ctx[(size_t)g], lorder, maxstart, max_matches, ssemaps != nullptr);
-        if (rc != SAT_OK) return bail(rc);
-    }
-    for (int g = 0; g < m->ndev; g++) {
-        const int rc = sat_matches_collect(m->ctx[(size_t)g], max_matches, counts, scores, restarts, ssemaps,
-                                           (size_t)m->n_entries, (size_t)m->begin[(size_t)g]);
-        if (rc != SAT_OK) return bail(rc);
-    }
+    int rc = each_shard(m, [&](int g) { return sat_matches_launch(m->ctx[(size_t)g], lorder, maxstart, max_matches, ssemaps != nullptr); });
+    if (rc != SAT_OK) return rc;
+    rc = each_shard(m, [&](int g) {
+        return sat_matches_collect(m->ctx[(size_t)g], max_matches, counts, scores, restarts, ssemaps, (size_t)m->n_entries,
+                                   (size_t)m->begin[(size_t)g]);
+    });
+    if (rc != SAT_OK) return rc;
     if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return SAT_OK;
 }
@@ -494,68 +494,59 @@ int sat_multi_search_refine(sat_multi *m, int lorder, int lsoln, int maxstart, i
     if (k > candidates) return sat_fail(SAT_EINVAL, "k (%d) exceeds the candidates per query (%d)", k, candidates);
     if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
     const auto t0 = std::chrono::steady_clock::now();
-    auto bail = [&](int rc) { const std::string msg = sat_last_error(); sync_all(m); return sat_fail(rc, "%s", msg.c_str()); };
     // stage 1 on every shard, each ranking its own best C
-    for (int g = 0; g < m->ndev; g++) {
-        int rc = sat_search_async(m->ctx[(size_t)g], lorder, 0, maxstart);
-        if (rc != SAT_OK) return bail(rc);
-    }
+    int rc = each_shard(m, [&](int g) { return sat_search_async(m->ctx[(size_t)g], lorder, 0, maxstart); });
+    if (rc != SAT_OK) return rc;
     const int c = candidates < m->n_entries ? candidates : m->n_entries;
     if (k > c) k = c;
     const int nq = (int)m->ctx[0]->queries.size();
     std::vector<std::vector<sat_hit>> cand((size_t)m->ndev);
-    std::vector<int> got((size_t)m->ndev, 0);
-    for (int g = 0; g < m->ndev; g++) {
+    std::vector<size_t> got((size_t)m->ndev, 0);
+    rc = each_shard(m, [&](int g) {
         cand[(size_t)g].resize((size_t)nq * c);
         const int r = sat_topk_hits(m->ctx[(size_t)g], c, cand[(size_t)g].data(), nullptr);
-        if (r < 0) return bail(r);
-        got[(size_t)g] = r;
-    }
-    // the global best C of every query (ties in database order: the lower shard first), filed by shard as pairs
+        got[(size_t)g] = r < 0 ? 0 : (size_t)r;
+        return r < 0 ? r : SAT_OK;
+    });
+    if (rc != SAT_OK) return rc;
+    // the global best C of every query, filed by shard as pairs
     struct Cand { int g, local, first, second; };
     std::vector<std::vector<Cand>> per_q((size_t)nq);
     std::vector<std::vector<int32_t>> pq((size_t)m->ndev), pe((size_t)m->ndev);
     std::vector<std::vector<std::pair<int, int>>> slot((size_t)m->ndev);     // (query, index in per_q) of each pair
-    for (int q = 0; q < nq; q++) {
-        std::vector<int> head((size_t)m->ndev, 0);
-        for (int r = 0; r < c; r++) {
-            int bg = -1;
-            for (int g = 0; g < m->ndev; g++) {
-                if (head[(size_t)g] >= got[(size_t)g]) continue;
-                if (bg < 0 || cand[(size_t)g][(size_t)q * got[(size_t)g] + head[(size_t)g]].score >
-                                  cand[(size_t)bg][(size_t)q * got[(size_t)bg] + head[(size_t)bg]].score)
-                    bg = g;
-            }
-            const sat_hit &h = cand[(size_t)bg][(size_t)q * got[(size_t)bg] + head[(size_t)bg]];
-            pq[(size_t)bg].push_back(q);
-            pe[(size_t)bg].push_back(h.entry);
-            slot[(size_t)bg].push_back({ q, (int)per_q[(size_t)q].size() });
-            per_q[(size_t)q].push_back({ bg, h.entry, h.score, 0 });
-            head[(size_t)bg]++;
-        }
-    }
+    for (int q = 0; q < nq; q++)
+        merge_shards(cand, (size_t)c, [&](int g) { return std::make_pair((size_t)q * got[(size_t)g], (size_t)(q + 1) * got[(size_t)g]); },
+                     [&](int g, size_t row) {
+                         const sat_hit &h = cand[(size_t)g][row];
+                         pq[(size_t)g].push_back(q);
+                         pe[(size_t)g].push_back(h.entry);
+                         slot[(size_t)g].push_back({ q, (int)per_q[(size_t)q].size() });
+                         per_q[(size_t)q].push_back({ g, h.entry, h.score, 0 });
+                     });
     // stage 2: every shard re-scores its candidates (queued on all, then collected)
     const auto t2 = std::chrono::steady_clock::now();
     const bool maps = lsoln && ssemaps;
-    for (int g = 0; g < m->ndev; g++) {
-        const int rc = sat_pairs_launch(m->ctx[(size_t)g], lorder, refine_maxstart, maps, pq[(size_t)g].data(), pe[(size_t)g].data(),
-                                        (int)pq[(size_t)g].size());
-        if (rc != SAT_OK) return bail(rc);
-    }
+    rc = each_shard(m, [&](int g) {
+        return sat_pairs_launch(m->ctx[(size_t)g], lorder, refine_maxstart, maps, pq[(size_t)g].data(), pe[(size_t)g].data(),
+                                (int)pq[(size_t)g].size());
+    });
+    if (rc != SAT_OK) return rc;
     std::vector<std::vector<int32_t>> cmaps((size_t)nq);
     if (maps)
         for (int q = 0; q < nq; q++) cmaps[(size_t)q].resize(per_q[(size_t)q].size() * SAT_MAXDIM);
-    for (int g = 0; g < m->ndev; g++) {
+    rc = each_shard(m, [&](int g) {
         const size_t np = pq[(size_t)g].size();
         std::vector<int32_t> sc(np), mp(maps ? np * SAT_MAXDIM : 0);
-        const int rc = sat_pairs_collect(m->ctx[(size_t)g], (int)np, sc.data(), maps ? mp.data() : nullptr, pq[(size_t)g].data());
-        if (rc != SAT_OK) return bail(rc);
+        const int r = sat_pairs_collect(m->ctx[(size_t)g], (int)np, sc.data(), maps ? mp.data() : nullptr, pq[(size_t)g].data());
+        if (r != SAT_OK) return r;
         for (size_t p = 0; p < np; p++) {
             const auto &sl = slot[(size_t)g][p];
             per_q[(size_t)sl.first][(size_t)sl.second].second = sc[p];
             if (maps) memcpy(cmaps[(size_t)sl.first].data() + (size_t)sl.second * SAT_MAXDIM, mp.data() + p * SAT_MAXDIM, sizeof(int32_t) * SAT_MAXDIM);
         }
-    }
+        return SAT_OK;
+    });
+    if (rc != SAT_OK) return rc;
     if (stage2_ms) *stage2_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count();
     // the final rows: stage-2 score descending, ties in database order; statistics as the device table holds them
     for (int q = 0; q < nq; q++) {
@@ -626,24 +617,15 @@ int sat_multi_hits_cutoff(sat_multi *m, double max_pvalue, int max_rows, int32_t
         if (rc != SAT_OK) return rc;
     }
     size_t out = 0;
-    for (int q = 0; q < nq; q++) {
-        std::vector<size_t> head((size_t)m->ndev);
-        for (int g = 0; g < m->ndev; g++) head[(size_t)g] = off[(size_t)g][(size_t)q];
-        for (int r = 0; r < counts[q]; r++, out++) {
-            int bg = -1;
-            for (int g = 0; g < m->ndev; g++) {
-                if (head[(size_t)g] >= off[(size_t)g][(size_t)q + 1]) continue;
-                // shards are contiguous: on a tie the lower shard holds the lower entry
-                if (bg < 0 || rows[(size_t)g][head[(size_t)g]].score > rows[(size_t)bg][head[(size_t)bg]].score) bg = g;
-            }
-            sat_hit h = rows[(size_t)bg][head[(size_t)bg]];
-            h.entry += m->begin[(size_t)bg];
-            hits[out] = h;
-            if (ssemaps)
-                memcpy(ssemaps + out * SAT_MAXDIM, rmaps[(size_t)bg].data() + head[(size_t)bg] * SAT_MAXDIM, sizeof(int32_t) * SAT_MAXDIM);
-            head[(size_t)bg]++;
-        }
-    }
+    for (int q = 0; q < nq; q++)
+        merge_shards(rows, (size_t)counts[q], [&](int g) { return std::make_pair(off[(size_t)g][(size_t)q], off[(size_t)g][(size_t)q + 1]); },
+                     [&](int g, size_t row) {
+                         hits[out] = rows[(size_t)g][row];
+                         hits[out].entry += m->begin[(size_t)g];
+                         if (ssemaps)
+                             memcpy(ssemaps + out * SAT_MAXDIM, rmaps[(size_t)g].data() + row * SAT_MAXDIM, sizeof(int32_t) * SAT_MAXDIM);
+                         out++;
+                     });
     return (int)total;
 }
 
@@ -655,13 +637,10 @@ int sat_multi_search_cutoff(sat_multi *m, int lorder, int lsoln, int maxstart, d
     if (!counts) return sat_fail(SAT_EINVAL, "counts buffer is null");
     if (!std::isfinite(max_pvalue) || max_pvalue < 0.0) return sat_fail(SAT_EINVAL, "max_pvalue must be finite and >= 0");
     const auto t0 = std::chrono::steady_clock::now();
-    auto bail = [&](int rc) { const std::string msg = sat_last_error(); sync_all(m); return sat_fail(rc, "%s", msg.c_str()); };
-    for (int g = 0; g < m->ndev; g++) {
-        int rc = sat_search_async(m->ctx[(size_t)g], lorder, lsoln, maxstart);
-        if (rc != SAT_OK) return bail(rc);
-    }
+    const int rc = each_shard(m, [&](int g) { return sat_search_async(m->ctx[(size_t)g], lorder, lsoln, maxstart); });
+    if (rc != SAT_OK) return rc;
     const int r = sat_multi_hits_cutoff(m, max_pvalue, max_rows, counts, capacity, hits, ssemaps);
-    if (r < 0) return bail(r);
+    if (r < 0) return bail(m, r);
     if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return r;
 }

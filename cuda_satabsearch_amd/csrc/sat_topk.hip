@@ -24,14 +24,6 @@
 #include "sat_ctx.hpp"
 #include "sat_cutoff.hpp"
 
-#define HIP_TRY(expr)                                                                       \
-    do {                                                                                    \
-        hipError_t err__ = (expr);                                                          \
-        if (err__ != hipSuccess)                                                            \
-            return sat_fail(err__ == hipErrorOutOfMemory ? SAT_ENOMEM : SAT_EDEVICE,        \
-                            "%s failed: %s", #expr, hipGetErrorString(err__));              \
-    } while (0)
-
 namespace {
 
 // key = biased score in the high word, inverted entry index in the low word: a descending
@@ -86,15 +78,32 @@ __global__ void finish_hits(const unsigned long long *sorted, int n, int k, int 
     }
 }
 
-template <typename T> int grow(T *&p, size_t &cap, size_t need)
+// The HitQuery rows of queries [q0, q0 + nq) into ctx->d_hitq (maps: their solution maps of the last search), queued
+// on the context's stream from `hq`, which the caller keeps until the stream has passed the copy.
+int upload_hit_queries(sat_ctx *ctx, int q0, int nq, bool maps, std::vector<HitQuery> &hq)
 {
-    if (need <= cap) return SAT_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    HIP_TRY(hipMalloc(&p, need * sizeof(T)));
-    cap = need;
+    const int rc = ctx->d_hitq.grow((size_t)nq * sizeof(HitQuery));
+    if (rc != SAT_OK) return rc;
+    hq.resize((size_t)nq);
+    for (int q = 0; q < nq; q++) {
+        const auto &info = ctx->queries[(size_t)(q0 + q)];
+        hq[(size_t)q].n1 = info.n1;
+        hq[(size_t)q].pad_ = 0;
+        hq[(size_t)q].ssemaps = maps ? ctx->d_ssemaps.get() + info.ssemap_off : nullptr;
+    }
+    HIP_TRY(hipMemcpyAsync(ctx->d_hitq.get(), hq.data(), hq.size() * sizeof(HitQuery), hipMemcpyHostToDevice, ctx->stream));
     return SAT_OK;
+}
+
+const HitQuery *hit_queries(const sat_ctx *ctx) { return reinterpret_cast<const HitQuery *>(ctx->d_hitq.get()); }
+
+// n keys sorted descending from `in` to `out` on `stream`: one segment, or nseg segments seg[s] .. seg[s + 1] - 1 (a
+// device array).  temp = null: only sets temp_bytes to the space the sort needs (hipcub's two-phase call).
+hipError_t sort_keys_desc(void *temp, size_t &temp_bytes, const unsigned long long *in, unsigned long long *out, int n, int nseg,
+                          int *seg, hipStream_t stream)
+{
+    if (nseg == 1) return hipcub::DeviceRadixSort::SortKeysDescending(temp, temp_bytes, in, out, n, 0, 64, stream);
+    return hipcub::DeviceSegmentedRadixSort::SortKeysDescending(temp, temp_bytes, in, out, n, nseg, seg, seg + 1, 0, 64, stream);
 }
 
 // rank queries [q0, q0 + nq) of the last search; rows land at row `out_row` of ctx->d_hits (and
@@ -105,50 +114,49 @@ int select_hits(sat_ctx *ctx, int q0, int nq, int k, bool want_maps, size_t out_
     const size_t total = (size_t)nq * n;
     HIP_TRY(hipSetDevice(ctx->device));
     int rc;
-    if ((rc = grow(ctx->d_keys, ctx->keys_cap, total)) != SAT_OK) return rc;
-    if ((rc = grow(ctx->d_sorted, ctx->sorted_cap, total)) != SAT_OK) return rc;
+    if ((rc = ctx->d_keys.grow(total)) != SAT_OK) return rc;
+    if ((rc = ctx->d_sorted.grow(total)) != SAT_OK) return rc;
     if (out_row == 0) {                                   // first chunk: size the row buffers for the whole batch
-        if ((rc = grow(ctx->d_hits, ctx->hits_cap, rows_total)) != SAT_OK) return rc;
-        if (want_maps && (rc = grow(ctx->d_hit_maps, ctx->hit_maps_cap, rows_total * SAT_MAXDIM)) != SAT_OK) return rc;
+        if ((rc = ctx->d_hits.grow(rows_total)) != SAT_OK) return rc;
+        if (want_maps && (rc = ctx->d_hit_maps.grow(rows_total * SAT_MAXDIM)) != SAT_OK) return rc;
     }
-    if ((rc = grow(ctx->d_seg, ctx->seg_cap, (size_t)nq + 1)) != SAT_OK) return rc;
-    if ((rc = grow(ctx->d_hitq, ctx->hitq_cap, (size_t)nq * sizeof(HitQuery))) != SAT_OK) return rc;
+    if ((rc = ctx->d_seg.grow((size_t)nq + 1)) != SAT_OK) return rc;
 
     std::vector<int> seg((size_t)nq + 1);
-    std::vector<HitQuery> hq((size_t)nq);
+    std::vector<HitQuery> hq;
     for (int q = 0; q <= nq; q++) seg[(size_t)q] = q * n;            // nq * n < 2^31: the callers cut the batch
-    for (int q = 0; q < nq; q++) {
-        const auto &info = ctx->queries[(size_t)(q0 + q)];
-        hq[(size_t)q].n1 = info.n1;
-        hq[(size_t)q].pad_ = 0;
-        hq[(size_t)q].ssemaps = want_maps ? ctx->d_ssemaps + info.ssemap_off : nullptr;
-    }
-    HIP_TRY(hipMemcpyAsync(ctx->d_seg, seg.data(), seg.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->d_hitq, hq.data(), hq.size() * sizeof(HitQuery), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->d_seg.get(), seg.data(), seg.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = upload_hit_queries(ctx, q0, nq, want_maps, hq)) != SAT_OK) return rc;
 
-    const int32_t *scores = ctx->d_scores + (size_t)q0 * n;
-    hipLaunchKernelGGL(pack_keys, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, scores, (long long)total, n, ctx->d_keys);
+    const int32_t *scores = ctx->d_scores.get() + (size_t)q0 * n;
+    hipLaunchKernelGGL(pack_keys, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, scores, (long long)total, n,
+                       ctx->d_keys.get());
     HIP_TRY(hipGetLastError());
     size_t temp_bytes = 0;
-    if (nq == 1) {
-        HIP_TRY(hipcub::DeviceRadixSort::SortKeysDescending(nullptr, temp_bytes, ctx->d_keys, ctx->d_sorted, (int)total, 0, 64, ctx->stream));
-    } else {
-        HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeysDescending(nullptr, temp_bytes, ctx->d_keys, ctx->d_sorted, (int)total, nq,
-                                                                    ctx->d_seg, ctx->d_seg + 1, 0, 64, ctx->stream));
-    }
-    if ((rc = grow(ctx->d_sort_temp, ctx->sort_temp_cap, temp_bytes ? temp_bytes : 1)) != SAT_OK) return rc;
-    if (nq == 1) {
-        HIP_TRY(hipcub::DeviceRadixSort::SortKeysDescending(ctx->d_sort_temp, temp_bytes, ctx->d_keys, ctx->d_sorted, (int)total, 0, 64, ctx->stream));
-    } else {
-        HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeysDescending(ctx->d_sort_temp, temp_bytes, ctx->d_keys, ctx->d_sorted, (int)total, nq,
-                                                                    ctx->d_seg, ctx->d_seg + 1, 0, 64, ctx->stream));
-    }
-    hipLaunchKernelGGL(finish_hits, dim3((unsigned)((nq * k + 127) / 128)), dim3(128), 0, ctx->stream, ctx->d_sorted, n, k, nq,
-                       ctx->d_orders, reinterpret_cast<const HitQuery *>(ctx->d_hitq), ctx->d_gumbel_z, ctx->d_gumbel_p,
-                       ctx->d_hits + out_row, want_maps ? ctx->d_hit_maps + out_row * SAT_MAXDIM : nullptr);
+    HIP_TRY(sort_keys_desc(nullptr, temp_bytes, ctx->d_keys.get(), ctx->d_sorted.get(), (int)total, nq, ctx->d_seg.get(), ctx->stream));
+    if ((rc = ctx->d_sort_temp.grow(temp_bytes ? temp_bytes : 1)) != SAT_OK) return rc;
+    HIP_TRY(sort_keys_desc(ctx->d_sort_temp.get(), temp_bytes, ctx->d_keys.get(), ctx->d_sorted.get(), (int)total, nq, ctx->d_seg.get(),
+                           ctx->stream));
+    hipLaunchKernelGGL(finish_hits, dim3((unsigned)((nq * k + 127) / 128)), dim3(128), 0, ctx->stream, ctx->d_sorted.get(), n, k, nq,
+                       ctx->d_orders.get(), hit_queries(ctx), ctx->d_gumbel_z.get(), ctx->d_gumbel_p.get(), ctx->d_hits.get() + out_row,
+                       want_maps ? ctx->d_hit_maps.get() + out_row * SAT_MAXDIM : nullptr);
     HIP_TRY(hipGetLastError());
     // the host vectors die at return
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SAT_OK;
+}
+
+// every query of the last search ranked: its best k rows at row q * k of ctx->d_hits (and ctx->d_hit_maps).  One
+// segmented sort handles up to 2^31 - 1 keys: long query lists over large databases go in chunks.
+int select_all_hits(sat_ctx *ctx, int k, bool want_maps)
+{
+    const int nq = (int)ctx->queries.size(), n = ctx->n_entries;
+    const int per_chunk = (int)(0x7FFFFFFFll / n) < 1 ? 1 : (int)(0x7FFFFFFFll / n);
+    for (int q0 = 0; q0 < nq; q0 += per_chunk) {
+        const int nqc = nq - q0 < per_chunk ? nq - q0 : per_chunk;
+        const int rc = select_hits(ctx, q0, nqc, k, want_maps, (size_t)q0 * k, (size_t)nq * k);
+        if (rc != SAT_OK) return rc;
+    }
     return SAT_OK;
 }
 
@@ -187,7 +195,7 @@ __global__ void finish_refined(const unsigned long long *sorted, const int32_t *
 int check_searched(sat_ctx *ctx)
 {
     if (!ctx) return sat_fail(SAT_EINVAL, "null context");
-    if (ctx->n_entries <= 0 || ctx->queries.empty() || !ctx->d_scores || ctx->searched_nq != ctx->queries.size())
+    if (ctx->n_entries <= 0 || ctx->queries.empty() || !ctx->d_scores.get() || ctx->searched_nq != ctx->queries.size())
         return sat_fail(SAT_ESTATE, "no search has run since the last database upload / query change");
     return SAT_OK;
 }
@@ -295,24 +303,6 @@ int cutoff_chunk(int n)
     return per < 1 ? 1 : (int)per;
 }
 
-// the HitQuery rows of queries [0, nq) into ctx->d_hitq
-int upload_hit_queries(sat_ctx *ctx, bool maps)
-{
-    const int nq = (int)ctx->queries.size();
-    int rc;
-    if ((rc = grow(ctx->d_hitq, ctx->hitq_cap, (size_t)nq * sizeof(HitQuery))) != SAT_OK) return rc;
-    std::vector<HitQuery> hq((size_t)nq);
-    for (int q = 0; q < nq; q++) {
-        const auto &info = ctx->queries[(size_t)q];
-        hq[(size_t)q].n1 = info.n1;
-        hq[(size_t)q].pad_ = 0;
-        hq[(size_t)q].ssemaps = maps ? ctx->d_ssemaps + info.ssemap_off : nullptr;
-    }
-    HIP_TRY(hipMemcpyAsync(ctx->d_hitq, hq.data(), hq.size() * sizeof(HitQuery), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));             // hq dies at return
-    return SAT_OK;
-}
-
 }  // namespace
 
 extern "C" int sat_topk(sat_ctx *ctx, int query, int k, int32_t *entry_index, int32_t *scores_out)
@@ -324,7 +314,7 @@ extern "C" int sat_topk(sat_ctx *ctx, int query, int k, int32_t *entry_index, in
     if (k > ctx->n_entries) k = ctx->n_entries;
     if ((rc = select_hits(ctx, query, 1, k, false, 0, (size_t)k)) != SAT_OK) return rc;
     std::vector<sat_hit> rows((size_t)k);
-    HIP_TRY(hipMemcpy(rows.data(), ctx->d_hits, rows.size() * sizeof(sat_hit), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rows.data(), ctx->d_hits.get(), rows.size() * sizeof(sat_hit), hipMemcpyDeviceToHost));
     ctx->d2h_bytes += rows.size() * sizeof(sat_hit);
     for (int i = 0; i < k; i++) {
         entry_index[i] = rows[(size_t)i].entry;
@@ -341,16 +331,11 @@ extern "C" int sat_topk_hits(sat_ctx *ctx, int k, sat_hit *hits, int32_t *ssemap
     if (ssemaps && !ctx->searched_lsoln) return sat_fail(SAT_ESTATE, "the last search ran without lsoln");
     if (k > ctx->n_entries) k = ctx->n_entries;
     const int nq = (int)ctx->queries.size();
-    // one segmented sort handles up to 2^31 - 1 keys: long query lists over large databases go in chunks
-    const int per_chunk = (int)(0x7FFFFFFFll / ctx->n_entries) < 1 ? 1 : (int)(0x7FFFFFFFll / ctx->n_entries);
-    for (int q0 = 0; q0 < nq; q0 += per_chunk) {
-        const int nqc = nq - q0 < per_chunk ? nq - q0 : per_chunk;
-        if ((rc = select_hits(ctx, q0, nqc, k, ssemaps != nullptr, (size_t)q0 * k, (size_t)nq * k)) != SAT_OK) return rc;
-    }
-    HIP_TRY(hipMemcpy(hits, ctx->d_hits, (size_t)nq * k * sizeof(sat_hit), hipMemcpyDeviceToHost));
+    if ((rc = select_all_hits(ctx, k, ssemaps != nullptr)) != SAT_OK) return rc;
+    HIP_TRY(hipMemcpy(hits, ctx->d_hits.get(), (size_t)nq * k * sizeof(sat_hit), hipMemcpyDeviceToHost));
     ctx->d2h_bytes += (size_t)nq * k * sizeof(sat_hit);
     if (ssemaps) {
-        HIP_TRY(hipMemcpy(ssemaps, ctx->d_hit_maps, (size_t)nq * k * SAT_MAXDIM * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ssemaps, ctx->d_hit_maps.get(), (size_t)nq * k * SAT_MAXDIM * sizeof(int32_t), hipMemcpyDeviceToHost));
         ctx->d2h_bytes += (size_t)nq * k * SAT_MAXDIM * sizeof(int32_t);
     }
     return k;
@@ -375,13 +360,9 @@ extern "C" int sat_search_refine(sat_ctx *ctx, int lorder, int lsoln, int maxsta
     if ((long long)nq * c > 0x7FFFFFFFll) return sat_fail(SAT_EINVAL, "queries x candidates exceed 2^31 - 1");
     const int npairs = nq * c;
     // the best c entries of every query, ranked on the device (rows stay there); only their indices come back
-    const int per_chunk = (int)(0x7FFFFFFFll / n) < 1 ? 1 : (int)(0x7FFFFFFFll / n);
-    for (int q0 = 0; q0 < nq; q0 += per_chunk) {
-        const int nqc = nq - q0 < per_chunk ? nq - q0 : per_chunk;
-        if ((rc = select_hits(ctx, q0, nqc, c, false, (size_t)q0 * c, (size_t)npairs)) != SAT_OK) return rc;
-    }
+    if ((rc = select_all_hits(ctx, c, false)) != SAT_OK) return rc;
     std::vector<int32_t> query((size_t)npairs), entry((size_t)npairs);
-    HIP_TRY(hipMemcpy2D(entry.data(), sizeof(int32_t), ctx->d_hits, sizeof(sat_hit), sizeof(int32_t), (size_t)npairs,
+    HIP_TRY(hipMemcpy2D(entry.data(), sizeof(int32_t), ctx->d_hits.get(), sizeof(sat_hit), sizeof(int32_t), (size_t)npairs,
                         hipMemcpyDeviceToHost));
     ctx->d2h_bytes += (size_t)npairs * sizeof(int32_t);
     for (int p = 0; p < npairs; p++) query[(size_t)p] = p / c;
@@ -390,50 +371,45 @@ extern "C" int sat_search_refine(sat_ctx *ctx, int lorder, int lsoln, int maxsta
     if ((rc = sat_pairs_launch(ctx, lorder, refine_maxstart, maps, query.data(), entry.data(), npairs)) != SAT_OK) return rc;
     const std::string stage2_info = ctx->last_launch_info;
     // the final ranking: segments of c keys, one per query
-    if ((rc = grow(ctx->d_rkeys, ctx->rkeys_cap, (size_t)npairs)) != SAT_OK) return rc;
-    if ((rc = grow(ctx->d_rsorted, ctx->rsorted_cap, (size_t)npairs)) != SAT_OK) return rc;
-    if ((rc = grow(ctx->d_rvals, ctx->rvals_cap, (size_t)npairs)) != SAT_OK) return rc;
-    if ((rc = grow(ctx->d_rvals_sorted, ctx->rvals_sorted_cap, (size_t)npairs)) != SAT_OK) return rc;
-    if ((rc = grow(ctx->d_rhits, ctx->rhits_cap, (size_t)nq * k)) != SAT_OK) return rc;
-    if ((rc = grow(ctx->d_rfirst, ctx->rfirst_cap, (size_t)nq * k)) != SAT_OK) return rc;
-    if (maps && (rc = grow(ctx->d_rmaps, ctx->rmaps_cap, (size_t)nq * k * SAT_MAXDIM)) != SAT_OK) return rc;
-    if ((rc = grow(ctx->d_seg, ctx->seg_cap, (size_t)nq + 1)) != SAT_OK) return rc;
-    if ((rc = grow(ctx->d_hitq, ctx->hitq_cap, (size_t)nq * sizeof(HitQuery))) != SAT_OK) return rc;
+    if ((rc = ctx->d_rkeys.grow((size_t)npairs)) != SAT_OK) return rc;
+    if ((rc = ctx->d_rsorted.grow((size_t)npairs)) != SAT_OK) return rc;
+    if ((rc = ctx->d_rvals.grow((size_t)npairs)) != SAT_OK) return rc;
+    if ((rc = ctx->d_rvals_sorted.grow((size_t)npairs)) != SAT_OK) return rc;
+    if ((rc = ctx->d_rhits.grow((size_t)nq * k)) != SAT_OK) return rc;
+    if ((rc = ctx->d_rfirst.grow((size_t)nq * k)) != SAT_OK) return rc;
+    if (maps && (rc = ctx->d_rmaps.grow((size_t)nq * k * SAT_MAXDIM)) != SAT_OK) return rc;
+    if ((rc = ctx->d_seg.grow((size_t)nq + 1)) != SAT_OK) return rc;
     std::vector<int> seg((size_t)nq + 1);
-    std::vector<HitQuery> hq((size_t)nq);
+    std::vector<HitQuery> hq;
     for (int q = 0; q <= nq; q++) seg[(size_t)q] = q * c;
-    for (int q = 0; q < nq; q++) {
-        hq[(size_t)q].n1 = ctx->queries[(size_t)q].n1;
-        hq[(size_t)q].pad_ = 0;
-        hq[(size_t)q].ssemaps = nullptr;
-    }
-    HIP_TRY(hipMemcpyAsync(ctx->d_seg, seg.data(), seg.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->d_hitq, hq.data(), hq.size() * sizeof(HitQuery), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(pack_refined, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_pkeys, ctx->d_hits,
-                       npairs, ctx->d_rkeys, ctx->d_rvals);
+    HIP_TRY(hipMemcpyAsync(ctx->d_seg.get(), seg.data(), seg.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = upload_hit_queries(ctx, 0, nq, false, hq)) != SAT_OK) return rc;
+    hipLaunchKernelGGL(pack_refined, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_pkeys.get(), ctx->d_hits.get(),
+                       npairs, ctx->d_rkeys.get(), ctx->d_rvals.get());
     HIP_TRY(hipGetLastError());
     size_t temp_bytes = 0;
-    HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortPairsDescending(nullptr, temp_bytes, ctx->d_rkeys, ctx->d_rsorted, ctx->d_rvals,
-                                                                 ctx->d_rvals_sorted, npairs, nq, ctx->d_seg, ctx->d_seg + 1, 0, 64,
-                                                                 ctx->stream));
-    if ((rc = grow(ctx->d_sort_temp, ctx->sort_temp_cap, temp_bytes ? temp_bytes : 1)) != SAT_OK) return rc;
-    HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortPairsDescending(ctx->d_sort_temp, temp_bytes, ctx->d_rkeys, ctx->d_rsorted, ctx->d_rvals,
-                                                                 ctx->d_rvals_sorted, npairs, nq, ctx->d_seg, ctx->d_seg + 1, 0, 64,
-                                                                 ctx->stream));
-    hipLaunchKernelGGL(finish_refined, dim3((unsigned)((nq * k + 127) / 128)), dim3(128), 0, ctx->stream, ctx->d_rsorted,
-                       ctx->d_rvals_sorted, c, k, nq, ctx->d_orders, reinterpret_cast<const HitQuery *>(ctx->d_hitq), ctx->d_gumbel_z,
-                       ctx->d_gumbel_p, ctx->d_hits, ctx->d_pmaps, ctx->d_rhits, ctx->d_rfirst, maps ? ctx->d_rmaps : nullptr);
+    HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortPairsDescending(nullptr, temp_bytes, ctx->d_rkeys.get(), ctx->d_rsorted.get(),
+                                                                 ctx->d_rvals.get(), ctx->d_rvals_sorted.get(), npairs, nq,
+                                                                 ctx->d_seg.get(), ctx->d_seg.get() + 1, 0, 64, ctx->stream));
+    if ((rc = ctx->d_sort_temp.grow(temp_bytes ? temp_bytes : 1)) != SAT_OK) return rc;
+    HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortPairsDescending(ctx->d_sort_temp.get(), temp_bytes, ctx->d_rkeys.get(),
+                                                                 ctx->d_rsorted.get(), ctx->d_rvals.get(), ctx->d_rvals_sorted.get(),
+                                                                 npairs, nq, ctx->d_seg.get(), ctx->d_seg.get() + 1, 0, 64, ctx->stream));
+    hipLaunchKernelGGL(finish_refined, dim3((unsigned)((nq * k + 127) / 128)), dim3(128), 0, ctx->stream, ctx->d_rsorted.get(),
+                       ctx->d_rvals_sorted.get(), c, k, nq, ctx->d_orders.get(), hit_queries(ctx), ctx->d_gumbel_z.get(),
+                       ctx->d_gumbel_p.get(), ctx->d_hits.get(), ctx->d_pmaps.get(), ctx->d_rhits.get(), ctx->d_rfirst.get(),
+                       maps ? ctx->d_rmaps.get() : nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     const size_t rows = (size_t)nq * k;
-    HIP_TRY(hipMemcpy(hits, ctx->d_rhits, rows * sizeof(sat_hit), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(hits, ctx->d_rhits.get(), rows * sizeof(sat_hit), hipMemcpyDeviceToHost));
     ctx->d2h_bytes += rows * sizeof(sat_hit);
     if (first_scores) {
-        HIP_TRY(hipMemcpy(first_scores, ctx->d_rfirst, rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(first_scores, ctx->d_rfirst.get(), rows * sizeof(int32_t), hipMemcpyDeviceToHost));
         ctx->d2h_bytes += rows * sizeof(int32_t);
     }
     if (maps) {
-        HIP_TRY(hipMemcpy(ssemaps, ctx->d_rmaps, rows * SAT_MAXDIM * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ssemaps, ctx->d_rmaps.get(), rows * SAT_MAXDIM * sizeof(int32_t), hipMemcpyDeviceToHost));
         ctx->d2h_bytes += rows * SAT_MAXDIM * sizeof(int32_t);
     }
     ctx->last_launch_info = "stage 1: " + stage1_info + " || stage 2: " + stage2_info;
@@ -452,18 +428,20 @@ int sat_cutoff_count(sat_ctx *ctx, double max_pvalue, bool maps, int32_t *counts
     const int per_chunk = cutoff_chunk(n), pc = per_chunk < nq ? per_chunk : nq;
     const int bpq = (n + kCutoffBlock - 1) / kCutoffBlock;
     HIP_TRY(hipSetDevice(ctx->device));
-    if ((rc = grow(ctx->d_seg, ctx->seg_cap, (size_t)nq + 3 * (size_t)pc + 2)) != SAT_OK) return rc;
-    if ((rc = upload_hit_queries(ctx, maps)) != SAT_OK) return rc;
-    const HitQuery *hq = reinterpret_cast<const HitQuery *>(ctx->d_hitq);
-    HIP_TRY(hipMemsetAsync(ctx->d_seg, 0, (size_t)nq * sizeof(int32_t), ctx->stream));
+    if ((rc = ctx->d_seg.grow((size_t)nq + 3 * (size_t)pc + 2)) != SAT_OK) return rc;
+    std::vector<HitQuery> hq_host;
+    if ((rc = upload_hit_queries(ctx, 0, nq, maps, hq_host)) != SAT_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));             // hq_host dies at return
+    const HitQuery *hq = hit_queries(ctx);
+    HIP_TRY(hipMemsetAsync(ctx->d_seg.get(), 0, (size_t)nq * sizeof(int32_t), ctx->stream));
     for (int q0 = 0; q0 < nq; q0 += per_chunk) {
         const int nqc = nq - q0 < per_chunk ? nq - q0 : per_chunk;
         hipLaunchKernelGGL(cutoff_count, dim3((unsigned)nqc * (unsigned)bpq), dim3(kCutoffBlock), 0, ctx->stream,
-                           ctx->d_scores + (size_t)q0 * n, n, bpq, ctx->d_orders, hq + q0, ctx->d_gumbel_z, ctx->d_gumbel_p,
-                           max_pvalue, ctx->d_seg + q0);
+                           ctx->d_scores.get() + (size_t)q0 * n, n, bpq, ctx->d_orders.get(), hq + q0, ctx->d_gumbel_z.get(),
+                           ctx->d_gumbel_p.get(), max_pvalue, ctx->d_seg.get() + q0);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipMemcpyAsync(counts, ctx->d_seg, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(counts, ctx->d_seg.get(), (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->d2h_bytes += (size_t)nq * sizeof(int32_t);
     return SAT_OK;
@@ -488,16 +466,16 @@ int sat_cutoff_rows(sat_ctx *ctx, double max_pvalue, int max_rows, const int32_t
     if (rows_total == 0) return SAT_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     int rc;
-    if ((rc = grow(ctx->d_keys, ctx->keys_cap, keys_max)) != SAT_OK) return rc;
-    if ((rc = grow(ctx->d_sorted, ctx->sorted_cap, keys_max)) != SAT_OK) return rc;
-    if ((rc = grow(ctx->d_hits, ctx->hits_cap, rows_total)) != SAT_OK) return rc;
-    if (maps && (rc = grow(ctx->d_hit_maps, ctx->hit_maps_cap, rows_total * SAT_MAXDIM)) != SAT_OK) return rc;
-    const HitQuery *hq = reinterpret_cast<const HitQuery *>(ctx->d_hitq);      // as sat_cutoff_count left them
+    if ((rc = ctx->d_keys.grow(keys_max)) != SAT_OK) return rc;
+    if ((rc = ctx->d_sorted.grow(keys_max)) != SAT_OK) return rc;
+    if ((rc = ctx->d_hits.grow(rows_total)) != SAT_OK) return rc;
+    if (maps && (rc = ctx->d_hit_maps.grow(rows_total * SAT_MAXDIM)) != SAT_OK) return rc;
+    const HitQuery *hq = hit_queries(ctx);                                    // as sat_cutoff_count left them
     size_t out_row = 0;
     std::vector<int32_t> out_off;
     for (int q0 = 0; q0 < nq; q0 += per_chunk) {
         const int nqc = nq - q0 < per_chunk ? nq - q0 : per_chunk;
-        int32_t *seg = ctx->d_seg + nq, *d_out = seg + nqc + 1, *cursor = d_out + nqc + 1;
+        int32_t *seg = ctx->d_seg.get() + nq, *d_out = seg + nqc + 1, *cursor = d_out + nqc + 1;
         // the chunk's output offsets (each query cut to max_rows); its segment offsets: a scan of its counts
         out_off.assign((size_t)nqc + 1, 0);
         int keys = 0;
@@ -512,38 +490,27 @@ int sat_cutoff_rows(sat_ctx *ctx, double max_pvalue, int max_rows, const int32_t
         HIP_TRY(hipMemsetAsync(seg, 0, sizeof(int32_t), ctx->stream));
         HIP_TRY(hipMemsetAsync(cursor, 0, (size_t)nqc * sizeof(int32_t), ctx->stream));
         size_t scan_bytes = 0, sort_bytes = 0;
-        HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, ctx->d_seg + q0, seg + 1, nqc, ctx->stream));
-        if (nqc == 1) {
-            HIP_TRY(hipcub::DeviceRadixSort::SortKeysDescending(nullptr, sort_bytes, ctx->d_keys, ctx->d_sorted, keys, 0, 64, ctx->stream));
-        } else {
-            HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeysDescending(nullptr, sort_bytes, ctx->d_keys, ctx->d_sorted, keys, nqc,
-                                                                        seg, seg + 1, 0, 64, ctx->stream));
-        }
+        HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, ctx->d_seg.get() + q0, seg + 1, nqc, ctx->stream));
+        HIP_TRY(sort_keys_desc(nullptr, sort_bytes, ctx->d_keys.get(), ctx->d_sorted.get(), keys, nqc, seg, ctx->stream));
         const size_t temp_bytes = scan_bytes > sort_bytes ? scan_bytes : sort_bytes;
-        if ((rc = grow(ctx->d_sort_temp, ctx->sort_temp_cap, temp_bytes ? temp_bytes : 1)) != SAT_OK) return rc;
-        HIP_TRY(hipcub::DeviceScan::InclusiveSum(ctx->d_sort_temp, scan_bytes, ctx->d_seg + q0, seg + 1, nqc, ctx->stream));
+        if ((rc = ctx->d_sort_temp.grow(temp_bytes ? temp_bytes : 1)) != SAT_OK) return rc;
+        HIP_TRY(hipcub::DeviceScan::InclusiveSum(ctx->d_sort_temp.get(), scan_bytes, ctx->d_seg.get() + q0, seg + 1, nqc, ctx->stream));
         hipLaunchKernelGGL(cutoff_compact, dim3((unsigned)nqc * (unsigned)bpq), dim3(kCutoffBlock), 0, ctx->stream,
-                           ctx->d_scores + (size_t)q0 * n, n, bpq, ctx->d_orders, hq + q0, ctx->d_gumbel_z, ctx->d_gumbel_p,
-                           max_pvalue, seg, cursor, ctx->d_keys);
+                           ctx->d_scores.get() + (size_t)q0 * n, n, bpq, ctx->d_orders.get(), hq + q0, ctx->d_gumbel_z.get(),
+                           ctx->d_gumbel_p.get(), max_pvalue, seg, cursor, ctx->d_keys.get());
         HIP_TRY(hipGetLastError());
-        if (nqc == 1) {
-            HIP_TRY(hipcub::DeviceRadixSort::SortKeysDescending(ctx->d_sort_temp, sort_bytes, ctx->d_keys, ctx->d_sorted, keys, 0, 64,
-                                                                ctx->stream));
-        } else {
-            HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeysDescending(ctx->d_sort_temp, sort_bytes, ctx->d_keys, ctx->d_sorted, keys,
-                                                                        nqc, seg, seg + 1, 0, 64, ctx->stream));
-        }
-        hipLaunchKernelGGL(cutoff_finish, dim3((unsigned)((rows + 127) / 128)), dim3(128), 0, ctx->stream, ctx->d_sorted, seg, d_out,
-                           nqc, rows, ctx->d_orders, hq + q0, ctx->d_gumbel_z, ctx->d_gumbel_p, ctx->d_hits + out_row,
-                           maps ? ctx->d_hit_maps + out_row * SAT_MAXDIM : nullptr);
+        HIP_TRY(sort_keys_desc(ctx->d_sort_temp.get(), sort_bytes, ctx->d_keys.get(), ctx->d_sorted.get(), keys, nqc, seg, ctx->stream));
+        hipLaunchKernelGGL(cutoff_finish, dim3((unsigned)((rows + 127) / 128)), dim3(128), 0, ctx->stream, ctx->d_sorted.get(), seg, d_out,
+                           nqc, rows, ctx->d_orders.get(), hq + q0, ctx->d_gumbel_z.get(), ctx->d_gumbel_p.get(),
+                           ctx->d_hits.get() + out_row, maps ? ctx->d_hit_maps.get() + out_row * SAT_MAXDIM : nullptr);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(ctx->stream));                     // out_off is reused by the next chunk
         out_row += (size_t)rows;
     }
-    HIP_TRY(hipMemcpy(hits, ctx->d_hits, rows_total * sizeof(sat_hit), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(hits, ctx->d_hits.get(), rows_total * sizeof(sat_hit), hipMemcpyDeviceToHost));
     ctx->d2h_bytes += rows_total * sizeof(sat_hit);
     if (maps) {
-        HIP_TRY(hipMemcpy(ssemaps, ctx->d_hit_maps, rows_total * SAT_MAXDIM * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ssemaps, ctx->d_hit_maps.get(), rows_total * SAT_MAXDIM * sizeof(int32_t), hipMemcpyDeviceToHost));
         ctx->d2h_bytes += rows_total * SAT_MAXDIM * sizeof(int32_t);
     }
     return SAT_OK;
