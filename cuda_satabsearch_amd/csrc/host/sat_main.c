@@ -29,6 +29,7 @@
  * GPU and ranked as -k; with -k K at most K of them per query).
  */
 #include <math.h>
+#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -101,18 +102,6 @@ static inline void out_bytes(const char *p, size_t n)
     if (n > sizeof(out_buf)) { fwrite(p, 1, n, stdout); return; }
     memcpy(out_buf + out_len, p, n);
     out_len += n;
-}
-
-static void print_header(int ltype, int lorder, int lsoln, const char *qid, const char *dbfile)
-{
-    char line[SAT_MAX_LINE_LEN + 64];
-    int n = snprintf(line, sizeof line, "# cudaSaTabsearch LTYPE = %c LORDER = %c LSOLN = %c\n",
-                     ltype ? 'T' : 'F', lorder ? 'T' : 'F', lsoln ? 'T' : 'F');
-    out_bytes(line, (size_t)n);
-    n = snprintf(line, sizeof line, "# QUERY ID = %-8s\n", qid);
-    out_bytes(line, (size_t)n);
-    n = snprintf(line, sizeof line, "# DBFILE = %-80s\n", dbfile);
-    out_bytes(line, (size_t)n);
 }
 
 /* cached printf("%g") texts */
@@ -199,567 +188,567 @@ static inline void out_map_line(int a, int b)
     out_bytes(t, 8);
 }
 
-static void print_row(const char *name, int score, int n1, int n2, const int32_t *map, int lsoln,
-                      int wide_gap);
-
-/* -m: matches 2 .. count of one entry (scores / maps of its M slots) as rows "name:k", each followed by its map
- * lines with LSOLN */
-static void print_more_matches(const char *name, int n1, int n2, int count, const int32_t *mscores,
-                               const int32_t *mmaps, int lsoln, int wide_gap)
+/* Report to stderr and end the run with status 1 */
+__attribute__((format(printf, 1, 2), noreturn))
+static void die(const char *fmt, ...)
 {
+    va_list ap;
+    va_start(ap, fmt);
+    vfprintf(stderr, fmt, ap);
+    va_end(ap);
+    exit(1);
+}
+
+static void *checked(void *p)
+{
+    if (!p)
+        die("malloc failed\n");
+    return p;
+}
+
+typedef struct {
+    int use_gpu, maxstart, want_gpus, bincache, topk, nmatch, refine, ncand, cutoff;
+    double pmax;                      /* -p: the largest p-value printed */
+    unsigned long long seed;
+    const char *qfile;                /* -q: the database; stdin lists the query SIDs */
+    int dev_list[64], ndev_list;
+    /* what the run prints, derived once the options are checked */
+    int ranked;                       /* -k / -p / -R: each query's ranked rows; else the listing in class order */
+    int nm;                           /* slots per entry: M of -m, else 1 */
+} options;
+
+typedef struct {
+    char dbfile[SAT_MAX_LINE_LEN];
+    int ltype, lorder, lsoln;
+    sat_struct_set queries, db;
+    char *sids;                       /* -q: num_queries SIDs of SAT_LABELSIZE + 1 bytes */
+    int num_queries;
+    const sat_struct_set *qsrc;       /* where the queries' structures are: queries, or db with -q */
+    int *qindex;                      /* query i is structure qindex[i] of qsrc */
+    int *cls_index[2], cls_count[2];  /* db entries of the small (order <= 96) and the large class, file order */
+} input;
+
+/* Per-entry results on the host: slot m of row r at r * nm + m (nm = M of -m, else 1).  counts: each row's matches
+ * (-m), or NULL: one.  maps: SAT_MAXDIM ints a slot with LSOLN, else NULL. */
+typedef struct {
+    int nm;
+    int32_t *counts, *scores, *maps;
+} slots;
+
+/* Database entry e's row and map lines, then with -m its matches 2..count as rows "name:k" with theirs, from row r of
+ * s.  A ranked row h (statistics from the device, map hmap) stands in for slot 0; the other rows get the host's. */
+static void print_entry(const input *in, int e, int n1, const sat_hit *h, const int32_t *hmap, const slots *s,
+                        size_t r, int wide_gap)
+{
+    const char *name = sat_set_name(&in->db, e);
+    const int n2 = in->db.order[e], count = s->counts ? s->counts[r] : 1;
     char mname[SAT_MAX_LINE_LEN + 16];
-    for (int m = 1; m < count; m++) {
-        snprintf(mname, sizeof mname, "%s:%d", name, m + 1);
-        print_row(mname, mscores[m], n1, n2, lsoln ? mmaps + (size_t)m * SAT_MAXDIM : NULL, lsoln, wide_gap);
+    for (int m = 0; m < count; m++) {
+        const size_t slot = r * (size_t)s->nm + (size_t)m;
+        const int32_t *map = hmap;
+        if (m == 0 && h) {
+            out_row(name, h->score, h->norm2, h->zscore, h->pvalue, n1 + n2, wide_gap, 0);
+        } else {
+            const int score = s->scores[slot];
+            const double norm2score = sat_norm2(score, n1, n2);
+            /* z and p only when their cached text is missing */
+            const int x = (int)norm2score;
+            double zscore = 0.0, pvalue = 0.0;
+            if (!(x >= -256 && x < 256 && zp_cache[wide_gap ? 1 : 0][x + 256].len)) {
+                zscore = sat_z_gumbel_trunc(norm2score);
+                pvalue = sat_pv_gumbel(zscore);
+            }
+            if (m)
+                snprintf(mname, sizeof mname, "%s:%d", name, m + 1);
+            out_row(m ? mname : name, score, norm2score, zscore, pvalue, n1 + n2, wide_gap, 1);
+            map = s->maps ? s->maps + slot * SAT_MAXDIM : NULL;
+        }
+        if (map)
+            for (int k = 0; k < n1; k++)
+                if (map[k] >= 0)
+                    out_map_line(k + 1, map[k] + 1);
     }
 }
 
-static void print_row(const char *name, int score, int n1, int n2, const int32_t *map, int lsoln,
-                      int wide_gap)
+/* The three '#' lines that open a block of query qi */
+static void print_header(const input *in, int qi)
 {
-    double norm2score = sat_norm2(score, n1, n2);
-    /* z and p only when their cached text is missing */
-    const int x = (int)norm2score;
-    double zscore = 0.0, pvalue = 0.0;
-    if (!(x >= -256 && x < 256 && zp_cache[wide_gap ? 1 : 0][x + 256].len)) {
-        zscore = sat_z_gumbel_trunc(norm2score);
-        pvalue = sat_pv_gumbel(zscore);
-    }
-    out_row(name, score, norm2score, zscore, pvalue, n1 + n2, wide_gap, 1);
-    if (lsoln)
-        for (int k = 0; k < n1; k++)
-            if (map[k] >= 0)
-                out_map_line(k + 1, map[k] + 1);
+    char line[SAT_MAX_LINE_LEN + 64];
+    int n = snprintf(line, sizeof line, "# cudaSaTabsearch LTYPE = %c LORDER = %c LSOLN = %c\n",
+                     in->ltype ? 'T' : 'F', in->lorder ? 'T' : 'F', in->lsoln ? 'T' : 'F');
+    out_bytes(line, (size_t)n);
+    n = snprintf(line, sizeof line, "# QUERY ID = %-8s\n", sat_set_name(in->qsrc, in->qindex[qi]));
+    out_bytes(line, (size_t)n);
+    n = snprintf(line, sizeof line, "# DBFILE = %-80s\n", in->dbfile);
+    out_bytes(line, (size_t)n);
 }
 
-int main(int argc, char *argv[])
+/* The options, then the refusals in a fixed order (the tests pin it), all before the banner and any device call */
+static void parse_options(int argc, char *argv[], options *o)
 {
-    char dbfile[SAT_MAX_LINE_LEN] = "";
-    char buf[SAT_MAX_LINE_LEN];
-    int use_gpu = 1, querydbmode = 0, maxstart = 128, want_gpus = 1, bincache = 0, topk = 0, nmatch = 0;
-    int refine = 0, ncand = 0;                      /* -R restarts of the second stage, -C candidates per query */
-    int cutoff = 0;                                 /* -p given: pmax is the largest p-value printed */
-    double pmax = 0.0;
-    unsigned long long seed = SAT_DEFAULT_SEED;
-    int ltype = 0, lorder = 0, lsoln = 0;
-    char cltype = 'F', clorder = 'F', clsoln = 'F';
+    *o = (options){ .use_gpu = 1, .maxstart = 128, .want_gpus = 1, .seed = SAT_DEFAULT_SEED };
     int c;
-
-    int dev_list[64], ndev_list = 0;
     while ((c = getopt(argc, argv, "cq:r:g:G:s:bk:p:m:R:C:")) != -1) {
+        char *end = NULL;
+        long v;
         switch (c) {
-        case 'c': use_gpu = 0; break;
-        case 'q': querydbmode = 1; strncpy(dbfile, optarg, sizeof(dbfile) - 1); break;
-        case 'r': maxstart = atoi(optarg); break;
-        case 'g': want_gpus = atoi(optarg); break;
+        case 'c': o->use_gpu = 0; break;
+        case 'q': o->qfile = optarg; break;
+        case 'r': o->maxstart = atoi(optarg); break;
+        case 'g': o->want_gpus = atoi(optarg); break;
         case 'G':
-            for (char *tok = strtok(optarg, ","); tok && ndev_list < 64; tok = strtok(NULL, ","))
-                dev_list[ndev_list++] = atoi(tok);
+            for (char *tok = strtok(optarg, ","); tok && o->ndev_list < 64; tok = strtok(NULL, ","))
+                o->dev_list[o->ndev_list++] = atoi(tok);
             break;
-        case 's': seed = strtoull(optarg, NULL, 0); break;
-        case 'b': bincache = 1; break;
-        case 'k': topk = atoi(optarg); break;
-        case 'p': {
+        case 's': o->seed = strtoull(optarg, NULL, 0); break;
+        case 'b': o->bincache = 1; break;
+        case 'k': o->topk = atoi(optarg); break;
+        case 'p':
             /* the whole argument, a finite number >= 0 */
-            char *end = NULL;
-            const double v = strtod(optarg, &end);
-            if (end == optarg || *end != '\0' || !isfinite(v) || v < 0.0) {
+            o->pmax = strtod(optarg, &end);
+            if (end == optarg || *end != '\0' || !isfinite(o->pmax) || o->pmax < 0.0) {
                 fprintf(stderr, "ERROR: -p needs a p-value >= 0 (got '%s')\n", optarg);
                 usage(argv[0]);
             }
-            cutoff = 1;
-            pmax = v;
+            o->cutoff = 1;
             break;
-        }
-        case 'm': {
+        case 'm':
             /* 1 .. SAT_MAX_MATCHES, digits only: anything else (0, a sign, text) is a usage error */
-            char *end = NULL;
-            const long v = strtol(optarg, &end, 10);
+            v = strtol(optarg, &end, 10);
             if (end == optarg || *end != '\0' || v < 1 || v > SAT_MAX_MATCHES) usage(argv[0]);
-            nmatch = (int)v;
+            o->nmatch = (int)v;
             break;
-        }
         case 'R':
-        case 'C': {
+        case 'C':
             /* positive, digits only */
-            char *end = NULL;
-            const long v = strtol(optarg, &end, 10);
+            v = strtol(optarg, &end, 10);
             if (end == optarg || *end != '\0' || v < 1 || v > 0x7FFFFFFFL) {
                 fprintf(stderr, "ERROR: -%c needs a positive integer (got '%s')\n", c, optarg);
                 usage(argv[0]);
             }
-            if (c == 'R') refine = (int)v;
-            else ncand = (int)v;
+            if (c == 'R') o->refine = (int)v;
+            else o->ncand = (int)v;
             break;
-        }
         default: usage(argv[0]);
         }
     }
-    if (cutoff && !use_gpu) {
-        fprintf(stderr, "ERROR: -p needs the GPU path\n");
-        exit(1);
-    }
-    if (cutoff && nmatch) {
-        fprintf(stderr, "ERROR: -p cannot be combined with -m\n");
-        exit(1);
-    }
-    if (cutoff && refine) {
-        fprintf(stderr, "ERROR: -p cannot be combined with -R\n");
-        exit(1);
-    }
-    if (cutoff && (!sat_multi_search_cutoff || !sat_multi_hits_cutoff)) {
-        fprintf(stderr, "ERROR: this library has no sat_multi_search_cutoff\n");
-        exit(1);
-    }
-    if (refine && !use_gpu) {
-        fprintf(stderr, "ERROR: -R needs the GPU path\n");
-        exit(1);
-    }
-    if (refine && nmatch) {
-        fprintf(stderr, "ERROR: -R cannot be combined with -m\n");
-        exit(1);
-    }
-    if (refine && topk <= 0) {
-        fprintf(stderr, "ERROR: -R needs -k K\n");
-        exit(1);
-    }
-    if (ncand && !refine) {
-        fprintf(stderr, "ERROR: -C needs -R\n");
-        exit(1);
-    }
-    if (refine && !ncand) ncand = topk;
-    if (refine && topk > ncand) {
-        fprintf(stderr, "ERROR: -k K (%d) exceeds -C C (%d)\n", topk, ncand);
-        exit(1);
-    }
-    if (refine && !sat_multi_search_refine) {
-        fprintf(stderr, "ERROR: this library has no sat_multi_search_refine\n");
-        exit(1);
-    }
-    if (nmatch && !use_gpu) {
-        fprintf(stderr, "ERROR: -m needs the GPU path\n");
-        exit(1);
-    }
-    if (nmatch && !sat_multi_search_matches) {
-        fprintf(stderr, "ERROR: this library has no sat_multi_search_matches\n");
-        exit(1);
-    }
-    fprintf(stderr, "MAXDIM = %d\n", SAT_MAXDIM);
-    atexit(out_flush);                                   /* every exit path, exit(1) included */
+    if (o->cutoff && !o->use_gpu) die("ERROR: -p needs the GPU path\n");
+    if (o->cutoff && o->nmatch) die("ERROR: -p cannot be combined with -m\n");
+    if (o->cutoff && o->refine) die("ERROR: -p cannot be combined with -R\n");
+    if (o->cutoff && (!sat_multi_search_cutoff || !sat_multi_hits_cutoff))
+        die("ERROR: this library has no sat_multi_search_cutoff\n");
+    if (o->refine && !o->use_gpu) die("ERROR: -R needs the GPU path\n");
+    if (o->refine && o->nmatch) die("ERROR: -R cannot be combined with -m\n");
+    if (o->refine && o->topk <= 0) die("ERROR: -R needs -k K\n");
+    if (o->ncand && !o->refine) die("ERROR: -C needs -R\n");
+    if (o->refine && !o->ncand) o->ncand = o->topk;
+    if (o->refine && o->topk > o->ncand) die("ERROR: -k K (%d) exceeds -C C (%d)\n", o->topk, o->ncand);
+    if (o->refine && !sat_multi_search_refine) die("ERROR: this library has no sat_multi_search_refine\n");
+    if (o->nmatch && !o->use_gpu) die("ERROR: -m needs the GPU path\n");
+    if (o->nmatch && !sat_multi_search_matches) die("ERROR: this library has no sat_multi_search_matches\n");
+    o->ranked = o->topk > 0 || o->cutoff;                /* (-R needs -k) */
+    o->nm = o->nmatch > 0 ? o->nmatch : 1;
+}
 
-    sat_struct_set queries, db;
-    sat_set_init(&queries);
-    sat_set_init(&db);
-    char *sid_list = NULL;
-    int num_queries = 0;
-
-    if (querydbmode) {
-        cltype = 'T'; ltype = 1;
-        clorder = 'T'; lorder = 1;
-        clsoln = 'F'; lsoln = 0;
-        while (!feof(stdin)) {
-            if (!fgets(buf, SAT_MAX_LINE_LEN, stdin))
-                break;
-            char *grown = (char *)realloc(sid_list, (size_t)(num_queries + 1) * (SAT_LABELSIZE + 1));
-            if (!grown) { fprintf(stderr, "realloc queryid_list failed\n"); exit(1); }
-            sid_list = grown;
-            char *sid = sid_list + (size_t)num_queries * (SAT_LABELSIZE + 1);
+/* -q: query SIDs on stdin, one a line (cut to 7 characters), options T T F; else the database name, the options and
+ * the query structures on stdin */
+static void read_queries(const options *o, input *in)
+{
+    if (o->qfile) {
+        strncpy(in->dbfile, o->qfile, sizeof in->dbfile - 1);
+        in->ltype = in->lorder = 1;
+        char buf[SAT_MAX_LINE_LEN];
+        while (!feof(stdin) && fgets(buf, SAT_MAX_LINE_LEN, stdin)) {
+            in->sids = checked(realloc(in->sids, (size_t)(in->num_queries + 1) * (SAT_LABELSIZE + 1)));
+            char *sid = in->sids + (size_t)in->num_queries++ * (SAT_LABELSIZE + 1);
             memset(sid, 0, SAT_LABELSIZE + 1);
             strncpy(sid, buf, SAT_LABELSIZE);
             sid[SAT_LABELSIZE - 1] = '\0';
             size_t len = strlen(sid);
             if (len && sid[len - 1] == '\n') sid[len - 1] = '\0';
-            num_queries++;
         }
     } else {
-        if (fscanf(stdin, "%s\n", dbfile) != 1) {
-            fprintf(stderr, "ERROR reading dbfilename from stdin\n");
-            exit(1);
-        }
-        if (fscanf(stdin, "%c %c %c\n", &cltype, &clorder, &clsoln) != 3) {
-            fprintf(stderr, "ERROR reading options from stdin\n");
-            exit(1);
-        }
-        ltype = cltype == 'T';
-        lorder = clorder == 'T';
-        lsoln = clsoln == 'T';
-        num_queries = sat_read_structures(stdin, &queries, "query");
-        if (num_queries < 0) {
-            fprintf(stderr, "ERROR loading query structures from stdin\n");
-            exit(1);
-        } else if (num_queries == 0) {
-            fprintf(stderr, "ERROR: no query structures found on stdin\n");
-            exit(1);
-        }
-        fprintf(stderr, "Read %d query structures\n", num_queries);
+        char cltype, clorder, clsoln;
+        if (fscanf(stdin, "%s\n", in->dbfile) != 1)
+            die("ERROR reading dbfilename from stdin\n");
+        if (fscanf(stdin, "%c %c %c\n", &cltype, &clorder, &clsoln) != 3)
+            die("ERROR reading options from stdin\n");
+        in->ltype = cltype == 'T';
+        in->lorder = clorder == 'T';
+        in->lsoln = clsoln == 'T';
+        in->num_queries = sat_read_structures(stdin, &in->queries, "query");
+        if (in->num_queries < 0)
+            die("ERROR loading query structures from stdin\n");
+        if (in->num_queries == 0)
+            die("ERROR: no query structures found on stdin\n");
+        fprintf(stderr, "Read %d query structures\n", in->num_queries);
     }
-    if (!ltype) {
+    if (!in->ltype) {
         fprintf(stderr, "WARNING: LTYPE is always set to T\n");
-        ltype = 1;
+        in->ltype = 1;
     }
+}
 
-    FILE *dbfp = fopen(dbfile, "r");
-    if (!dbfp) {
-        fprintf(stderr, "ERROR opening db file %s\n", dbfile);
-        exit(1);
-    }
+/* The database (-b: its binary image when that is newer than the file), split into the two size classes; then each
+ * query's structure: the inline ones in turn, or with -q the database entry of its SID (small class first) */
+static void load_database(const options *o, input *in)
+{
+    FILE *dbfp = fopen(in->dbfile, "r");
+    if (!dbfp)
+        die("ERROR opening db file %s\n", in->dbfile);
     fclose(dbfp);
     fprintf(stderr, "Loading database...\n");
-    double t0 = now_ms();
+    const double t0 = now_ms();
     int total = -1;
     char binpath[SAT_MAX_LINE_LEN + 16];
-    snprintf(binpath, sizeof(binpath), "%s.satbin", dbfile);
-    if (bincache) {
+    snprintf(binpath, sizeof(binpath), "%s.satbin", in->dbfile);
+    if (o->bincache) {
         struct stat sa, sb;
-        if (stat(dbfile, &sa) == 0 && stat(binpath, &sb) == 0 && sb.st_mtime >= sa.st_mtime &&
-            sat_set_load_binary(binpath, &db) == 0) {
-            total = db.count;
+        if (stat(in->dbfile, &sa) == 0 && stat(binpath, &sb) == 0 && sb.st_mtime >= sa.st_mtime &&
+            sat_set_load_binary(binpath, &in->db) == 0) {
+            total = in->db.count;
             fprintf(stderr, "(binary image %s)\n", binpath);
         }
     }
     if (total < 0) {
-        total = sat_read_structures_file(dbfile, &db, "database");     /* mmap reader, same semantics */
-        if (total >= 0 && bincache && sat_set_save_binary(&db, binpath) != 0)
+        total = sat_read_structures_file(in->dbfile, &in->db, "database");     /* mmap reader, same semantics */
+        if (total >= 0 && o->bincache && sat_set_save_binary(&in->db, binpath) != 0)
             fprintf(stderr, "WARNING: could not write %s\n", binpath);
     }
-    if (total < 0) {
-        fprintf(stderr, "ERROR loading database\n");
-        exit(1);
-    }
+    if (total < 0)
+        die("ERROR loading database\n");
     /* the two passes of the reference: small class then large class, file order inside */
-    int *cls_index[2], cls_count[2] = { 0, 0 };
-    cls_index[0] = (int *)malloc(sizeof(int) * (size_t)(total + 1));
-    cls_index[1] = (int *)malloc(sizeof(int) * (size_t)(total + 1));
-    if (!cls_index[0] || !cls_index[1]) { fprintf(stderr, "malloc failed\n"); exit(1); }
-    for (int s = 0; s < db.count; s++) {
-        int k = db.order[s] > SAT_MAXDIM_SMALL;
-        cls_index[k][cls_count[k]++] = s;
+    for (int k = 0; k < 2; k++)
+        in->cls_index[k] = checked(malloc(sizeof(int) * (size_t)(total + 1)));
+    for (int s = 0; s < in->db.count; s++) {
+        const int k = in->db.order[s] > SAT_MAXDIM_SMALL;
+        in->cls_index[k][in->cls_count[k]++] = s;
     }
     fprintf(stderr, "Loaded %d db entries (%d order > %d) in %f ms\n",
-            total, cls_count[1], SAT_MAXDIM_SMALL, now_ms() - t0);
-    if (total == 0) {
-        fprintf(stderr, "ERROR: empty database\n");
-        exit(1);
-    }
+            total, in->cls_count[1], SAT_MAXDIM_SMALL, now_ms() - t0);
+    if (total == 0)
+        die("ERROR: empty database\n");
 
-    /* -q: SID -> db structure (small class searched first) */
-    const sat_struct_set *qsrc = querydbmode ? &db : &queries;
-    int *qindex = (int *)malloc(sizeof(int) * (size_t)(num_queries + 1));
-    for (int i = 0; i < num_queries; i++) {
-        qindex[i] = i;
-        if (!querydbmode)
+    in->qsrc = o->qfile ? &in->db : &in->queries;
+    in->qindex = checked(malloc(sizeof(int) * (size_t)(in->num_queries + 1)));
+    for (int i = 0; i < in->num_queries; i++) {
+        in->qindex[i] = i;
+        if (!o->qfile)
             continue;
-        const char *sid = sid_list + (size_t)i * (SAT_LABELSIZE + 1);
+        const char *sid = in->sids + (size_t)i * (SAT_LABELSIZE + 1);
         int found = -1;
         for (int k = 0; k < 2 && found < 0; k++)
-            for (int d = 0; d < cls_count[k]; d++)
-                if (!strcasecmp(sid, sat_set_name(&db, cls_index[k][d]))) {
-                    found = cls_index[k][d];
+            for (int d = 0; d < in->cls_count[k]; d++)
+                if (!strcasecmp(sid, sat_set_name(&in->db, in->cls_index[k][d]))) {
+                    found = in->cls_index[k][d];
                     break;
                 }
-        if (found < 0) {
-            fprintf(stderr, "ERROR: query %s not found\n", sid);
-            exit(1);
+        if (found < 0)
+            die("ERROR: query %s not found\n", sid);
+        in->qindex[i] = found;
+    }
+}
+
+static void free_input(input *in)
+{
+    free(in->qindex);
+    free(in->sids);
+    free(in->cls_index[0]);
+    free(in->cls_index[1]);
+    sat_set_free(&in->queries);
+    sat_set_free(&in->db);
+}
+
+/* ---- host mode: class by class, query by query, ONE stream for everything */
+static int run_host(const options *o, const input *in)
+{
+    const size_t total = (size_t)in->db.count;
+    slots one = { 1, NULL, checked(malloc(sizeof(int32_t) * total)),
+                  in->lsoln ? checked(malloc(sizeof(int32_t) * SAT_MAXDIM * total)) : NULL };
+    sat_host_stream stream;
+    sat_host_stream_seed(&stream, 1234);
+    const int passes = in->cls_count[1] > 0 ? 2 : 1;
+    for (int k = 0; k < passes; k++)
+        for (int qi = 0; qi < in->num_queries; qi++) {
+            const int qs = in->qindex[qi];
+            print_header(in, qi);
+            fprintf(stderr, "Executing simulated annealing tableaux match kernel on host for query %s...\n",
+                    sat_set_name(in->qsrc, qs));
+            double t1 = now_ms();
+            if (sat_host_search(&in->db, in->cls_index[k], in->cls_count[k], in->qsrc, qs, in->lorder, in->lsoln,
+                                o->maxstart, &stream, one.scores, one.maps) != 0)
+                die("malloc failed in host search\n");
+            double ms = now_ms() - t1;
+            fprintf(stderr, "host execution time %f ms\n", ms);
+            fprintf(stderr, "%f million iterations/sec\n",
+                    ((double)in->cls_count[k] * ((double)o->maxstart * SAT_MAXITER) / (ms / 1000)) / 1.0e6);
+            for (int d = 0; d < in->cls_count[k]; d++)
+                print_entry(in, in->cls_index[k][d], in->qsrc->order[qs], NULL, NULL, &one, (size_t)d, 0);
         }
-        qindex[i] = found;
-    }
-    fprintf(stderr, "maxstart = %d\n", maxstart);
+    free(one.scores);
+    free(one.maps);
+    return 0;
+}
 
-    int32_t *scores = (int32_t *)malloc(sizeof(int32_t) * (size_t)total);
-    int32_t *ssemaps = lsoln ? (int32_t *)malloc(sizeof(int32_t) * SAT_MAXDIM * (size_t)total) : NULL;
-    if (!scores || (lsoln && !ssemaps)) { fprintf(stderr, "malloc scores failed\n"); exit(1); }
+/* ---- GPU mode */
 
-    if (!use_gpu) {
-        /* ---- host mode: class by class, query by query, ONE stream for everything ---- */
-        sat_host_stream stream;
-        sat_host_stream_seed(&stream, 1234);
-        for (int k = 0; k < 2; k++) {
-            if (k == 1 && cls_count[1] == 0)
-                break;
-            for (int qi = 0; qi < num_queries; qi++) {
-                const int qs = qindex[qi], n1 = qsrc->order[qs];
-                print_header(ltype, lorder, lsoln, sat_set_name(qsrc, qs), dbfile);
-                fprintf(stderr, "Executing simulated annealing tableaux match kernel on host for query %s...\n",
-                        sat_set_name(qsrc, qs));
-                double t1 = now_ms();
-                if (sat_host_search(&db, cls_index[k], cls_count[k], qsrc, qs, lorder, lsoln, maxstart,
-                                    &stream, scores, ssemaps) != 0) {
-                    fprintf(stderr, "malloc failed in host search\n");
-                    exit(1);
-                }
-                double ms = now_ms() - t1;
-                fprintf(stderr, "host execution time %f ms\n", ms);
-                fprintf(stderr, "%f million iterations/sec\n",
-                        ((double)cls_count[k] * ((double)maxstart * SAT_MAXITER) / (ms / 1000)) / 1.0e6);
-                for (int d = 0; d < cls_count[k]; d++)
-                    print_row(sat_set_name(&db, cls_index[k][d]), scores[d], n1, db.order[cls_index[k][d]],
-                              ssemaps ? ssemaps + (size_t)d * SAT_MAXDIM : NULL, lsoln, 0);
-            }
-        }
-        /* main owns every host array (as H.cu:1314-1324) */
-        free(scores);
-        free(ssemaps);
-        free(qindex);
-        free(sid_list);
-        free(cls_index[0]);
-        free(cls_index[1]);
-        free(norm2_cache);
-        sat_set_free(&queries);
-        sat_set_free(&db);
-        return 0;
-    }
+/* The host side of the GPU path, sized once for the mode */
+typedef struct {
+    int batch;                        /* queries a search scores */
+    int kk;                           /* -k: rows per query, min(K, entries) */
+    int32_t *n1s;                     /* the batch's queries: orders, codes, types and distances at pitch SAT_MAXDIM */
+    uint8_t *qtabs, *qtypes;
+    float *qdmats;
+    slots all;                        /* listing, -m: every entry's slots, row b * entries + e */
+    int32_t *restarts;                /* -m: each slot's restart (asked for, not printed) */
+    slots large;                      /* listing: the large class's slots of every query, row qi * large + d */
+    sat_hit *hits;                    /* -k / -p / -R: the batch's ranked rows, and with LSOLN their maps */
+    int32_t *hit_maps;
+    int32_t *pcounts;                 /* -p: rows of each query of the batch */
+    int hits_cap;                     /* -p: rows hits holds */
+} gpu_bufs;
 
-    /* ---- GPU mode ---- */
-    int ndev = sat_device_count();
-    if (ndev <= 0) {
-        fprintf(stderr, "There is no usable HIP device (use -c for the host mode).\n");
-        exit(1);
+static void alloc_slots(slots *s, size_t rows, int nm, int with_counts, int lsoln)
+{
+    s->nm = nm;
+    s->counts = with_counts ? checked(malloc(sizeof(int32_t) * rows)) : NULL;
+    s->scores = checked(malloc(sizeof(int32_t) * rows * (size_t)nm));
+    s->maps = lsoln ? checked(malloc(sizeof(int32_t) * SAT_MAXDIM * rows * (size_t)nm)) : NULL;
+}
+
+static void alloc_hits(gpu_bufs *B, size_t rows, int lsoln)
+{
+    free(B->hits);
+    free(B->hit_maps);
+    B->hits = checked(malloc(sizeof(sat_hit) * rows));
+    B->hit_maps = lsoln ? checked(malloc(sizeof(int32_t) * SAT_MAXDIM * rows)) : NULL;
+}
+
+static void alloc_gpu_bufs(const options *o, const input *in, gpu_bufs *B)
+{
+    const int total = in->db.count, nm = o->nm, lsoln = in->lsoln;
+    const int entry_slots = !o->ranked || o->nmatch;     /* every entry's slots come to the host */
+    *B = (gpu_bufs){ .batch = 256, .kk = o->topk < total ? o->topk : total };
+    /* Queries go to the GPUs in batches: one set of launches scores a whole batch (grid = entries x queries), which
+     * is what fills the machine when the database is small and the query list long (-q).  The batch size is bounded
+     * by the host slots of every entry: score and map, with -m also count and restarts (the device holds the same
+     * slots, maps as bytes). */
+    if (entry_slots) {
+        const size_t per_entry = (size_t)nm * (lsoln ? SAT_MAXDIM + 1 : 1) + (o->nmatch ? 1 + (size_t)nm : 0);
+        const size_t per_query = (size_t)total * per_entry * sizeof(int32_t);
+        const size_t budget = (size_t)1 << 30;
+        if ((size_t)B->batch * per_query > budget) B->batch = (int)(budget / per_query);
     }
+    if (B->batch < 1) B->batch = 1;
+    if (B->batch > in->num_queries) B->batch = in->num_queries;
+    const size_t rows = (size_t)total * B->batch;
+    if (entry_slots)
+        alloc_slots(&B->all, rows, nm, o->nmatch, lsoln);
+    if (o->nmatch)
+        B->restarts = checked(malloc(sizeof(int32_t) * rows * nm));
+    if (!o->ranked && in->cls_count[1] > 0)
+        alloc_slots(&B->large, (size_t)in->cls_count[1] * in->num_queries, nm, o->nmatch, lsoln);
+    if (o->cutoff) {
+        B->hits_cap = 1024;
+        B->pcounts = checked(malloc(sizeof(int32_t) * (size_t)B->batch));
+        alloc_hits(B, (size_t)B->hits_cap, lsoln);
+    } else if (o->topk > 0) {
+        alloc_hits(B, (size_t)B->kk * B->batch, lsoln);  /* only K rows per query (and GPU) ever leave the GPUs */
+    }
+    B->n1s = checked(malloc(sizeof(int32_t) * (size_t)B->batch));
+    B->qtabs = checked(calloc((size_t)B->batch * SAT_MAXDIM * SAT_MAXDIM, 1));
+    B->qdmats = checked(calloc((size_t)B->batch * SAT_MAXDIM * SAT_MAXDIM, sizeof(float)));
+    B->qtypes = checked(calloc((size_t)B->batch * SAT_MAXDIM, 1));
+}
+
+static void free_slots(slots *s)
+{
+    free(s->counts);
+    free(s->scores);
+    free(s->maps);
+}
+
+static void free_gpu_bufs(gpu_bufs *B)
+{
+    free(B->n1s);
+    free(B->qtabs);
+    free(B->qtypes);
+    free(B->qdmats);
+    free_slots(&B->all);
+    free(B->restarts);
+    free_slots(&B->large);
+    free(B->hits);
+    free(B->hit_maps);
+    free(B->pcounts);
+}
+
+/* One multi-GPU context holding the database: it is cut into contiguous shards of equal COST (entries of a
+ * size-sorted database differ several-fold in cost, sat_shard.h), every GPU holds its shard, a search is queued on
+ * all of them and one gather (RCCL over xGMI) brings the rows to device 0. */
+static sat_multi *open_multi(const options *o, const input *in)
+{
+    const int total = in->db.count, ndev = sat_device_count();
+    if (ndev <= 0)
+        die("There is no usable HIP device (use -c for the host mode).\n");
     fprintf(stderr, "found %d HIP devices\n", ndev);
-    int ngpu = want_gpus > 0 ? want_gpus : ndev;
+    int ngpu = o->want_gpus > 0 ? o->want_gpus : ndev;
     if (ngpu > ndev) ngpu = ndev;
-    if (ndev_list > 0) ngpu = ndev_list;
+    if (o->ndev_list > 0) ngpu = o->ndev_list;
     if (ngpu > total) ngpu = total;
-
-    /* One multi-GPU context: the database is cut into contiguous shards of equal COST (entries of a
-     * size-sorted database differ several-fold in cost, sat_shard.h), every GPU holds its shard, a
-     * search is queued on all of them and one gather (RCCL over xGMI) brings the rows to device 0. */
-    t0 = now_ms();
-    sat_multi *multi = sat_multi_create(ngpu, ndev_list > 0 ? dev_list : NULL, seed);
-    if (!multi) {
-        fprintf(stderr, "sat_multi_create(%d) failed: %s\n", ngpu, sat_last_error());
-        exit(1);
-    }
-    if (sat_multi_db_upload_packed(multi, total, db.order, db.cell_off, db.tab, db.dist) != SAT_OK) {
-        fprintf(stderr, "database upload failed: %s\n", sat_last_error());
-        exit(1);
-    }
+    const double t0 = now_ms();
+    sat_multi *multi = sat_multi_create(ngpu, o->ndev_list > 0 ? o->dev_list : NULL, o->seed);
+    if (!multi)
+        die("sat_multi_create(%d) failed: %s\n", ngpu, sat_last_error());
+    if (sat_multi_db_upload_packed(multi, total, in->db.order, in->db.cell_off, in->db.tab, in->db.dist) != SAT_OK)
+        die("database upload failed: %s\n", sat_last_error());
     fprintf(stderr, "Copied %d entries to %d GPU(s) in %f ms (gather: %s)\n", total, ngpu, now_ms() - t0,
             sat_multi_gather_kind(multi));
     if (ngpu > 1) {
-        int32_t *begin = (int32_t *)malloc(sizeof(int32_t) * (size_t)(ngpu + 1));
-        if (begin && sat_multi_shards(multi, begin) == SAT_OK)
+        int32_t *begin = checked(malloc(sizeof(int32_t) * (size_t)(ngpu + 1)));
+        if (sat_multi_shards(multi, begin) == SAT_OK)
             for (int g = 0; g < ngpu; g++)
                 fprintf(stderr, "  GPU %d: entries %d .. %d\n", g, begin[g], begin[g + 1] - 1);
         free(begin);
     }
+    return multi;
+}
 
-    /* rows of the large class are printed after every query's small-class block */
-    int32_t *large_scores = NULL, *large_maps = NULL;
-    /* -m: M slots per row (nm = 1 without -m); the large class keeps every slot for its late rows */
-    const int nm = nmatch > 0 ? nmatch : 1;
-    int32_t *large_counts = NULL;
-    if (cls_count[1] > 0 && topk <= 0 && !cutoff) {
-        large_scores = (int32_t *)malloc(sizeof(int32_t) * (size_t)cls_count[1] * num_queries * nm);
-        if (lsoln) large_maps = (int32_t *)malloc(sizeof(int32_t) * SAT_MAXDIM * (size_t)cls_count[1] * num_queries * nm);
-        if (nmatch) large_counts = (int32_t *)malloc(sizeof(int32_t) * (size_t)cls_count[1] * num_queries);
-        if (!large_scores || (lsoln && !large_maps) || (nmatch && !large_counts)) { fprintf(stderr, "malloc failed\n"); exit(1); }
-    }
-
-    /* Queries go to the GPUs in batches: one set of launches scores a whole batch (grid =
-     * entries x queries), which is what fills the machine when the database is small and the
-     * query list long (-q).  The batch size is bounded by the host result buffers: every entry's row (and map)
-     * without -k, and with -m every entry's M slots also under -k (the device holds the same slots, maps as bytes). */
-    int batch = 256;
-    if ((topk <= 0 && !cutoff) || nmatch) {
-        size_t per_query = 0;
-        if (!nmatch) per_query = (size_t)total * (lsoln ? (SAT_MAXDIM + 1) : 1) * sizeof(int32_t);
-        else per_query = (size_t)total * (1 + 2 * (size_t)nm + (lsoln ? (size_t)nm * SAT_MAXDIM : 0)) * sizeof(int32_t);
-        const size_t budget = (size_t)1 << 30;
-        if ((size_t)batch * per_query > budget) batch = (int)(budget / per_query);
-    }
-    if (batch < 1) batch = 1;
-    if (batch > num_queries) batch = num_queries;
-    free(scores);
-    free(ssemaps);
-    scores = NULL;
-    ssemaps = NULL;
-    const int kk = topk < total ? topk : total;
-    sat_hit *hits = NULL;
-    int32_t *hit_maps = NULL;
-    int32_t *pcounts = NULL;                         /* -p: rows of each query of the batch */
-    int hits_cap = 0;                                /* -p: rows hits (and hit_maps) hold; grown to the batch's total */
-    if (cutoff) {
-        hits_cap = 1024;
-        pcounts = (int32_t *)malloc(sizeof(int32_t) * (size_t)batch);
-        hits = (sat_hit *)malloc(sizeof(sat_hit) * (size_t)hits_cap);
-        hit_maps = lsoln ? (int32_t *)malloc(sizeof(int32_t) * SAT_MAXDIM * (size_t)hits_cap) : NULL;
-        if (!pcounts || !hits || (lsoln && !hit_maps)) { fprintf(stderr, "malloc failed\n"); exit(1); }
-    } else if (topk > 0) {
-        /* best K per query: only K rows per query (and GPU) ever leave the GPUs */
-        hits = (sat_hit *)malloc(sizeof(sat_hit) * (size_t)kk * batch);
-        hit_maps = lsoln ? (int32_t *)malloc(sizeof(int32_t) * SAT_MAXDIM * (size_t)kk * batch) : NULL;
-        if (!hits || (lsoln && !hit_maps)) { fprintf(stderr, "malloc failed\n"); exit(1); }
-    } else if (!nmatch) {                              /* (-m: the rows come from the match slots) */
-        scores = (int32_t *)malloc(sizeof(int32_t) * (size_t)total * batch);
-        ssemaps = lsoln ? (int32_t *)malloc(sizeof(int32_t) * SAT_MAXDIM * (size_t)total * batch) : NULL;
-        if (!scores || (lsoln && !ssemaps)) { fprintf(stderr, "malloc failed\n"); exit(1); }
-    }
-    /* -m: every entry's M slots (counts, scores, restarts, maps) of the batch */
-    int32_t *mcounts = NULL, *mscores = NULL, *mrestarts = NULL, *mmaps = NULL;
-    if (nmatch) {
-        mcounts = (int32_t *)malloc(sizeof(int32_t) * (size_t)total * batch);
-        mscores = (int32_t *)malloc(sizeof(int32_t) * (size_t)total * batch * nm);
-        mrestarts = (int32_t *)malloc(sizeof(int32_t) * (size_t)total * batch * nm);
-        mmaps = lsoln ? (int32_t *)malloc(sizeof(int32_t) * SAT_MAXDIM * (size_t)total * batch * nm) : NULL;
-        if (!mcounts || !mscores || !mrestarts || (lsoln && !mmaps)) { fprintf(stderr, "malloc failed\n"); exit(1); }
-    }
-    uint8_t *qtabs = (uint8_t *)calloc((size_t)batch * SAT_MAXDIM * SAT_MAXDIM, 1);
-    float *qdmats = (float *)calloc((size_t)batch * SAT_MAXDIM * SAT_MAXDIM, sizeof(float));
-    uint8_t *qtypes = (uint8_t *)calloc((size_t)batch * SAT_MAXDIM, 1);
-    int32_t *n1s = (int32_t *)malloc(sizeof(int32_t) * (size_t)batch);
-    if (!qtabs || !qdmats || !qtypes || !n1s) {
-        fprintf(stderr, "malloc failed\n");
-        exit(1);
-    }
-    int exit_status = 0;
-
-    for (int q0 = 0; q0 < num_queries; q0 += batch) {
-        const int nqb = num_queries - q0 < batch ? num_queries - q0 : batch;
-        for (int b = 0; b < nqb; b++) {
-            const int qs = qindex[q0 + b];
-            n1s[b] = qsrc->order[qs];
-            sat_set_expand(qsrc, qs, SAT_MAXDIM, qtabs + (size_t)b * SAT_MAXDIM * SAT_MAXDIM,
-                           qdmats + (size_t)b * SAT_MAXDIM * SAT_MAXDIM);
-            for (int i = 0; i < n1s[b]; i++)
-                qtypes[(size_t)b * SAT_MAXDIM + i] = qtabs[(size_t)b * SAT_MAXDIM * SAT_MAXDIM + i * SAT_MAXDIM + i];
+/* The mode's search of the batch set last.  Returns rows per query (-k, -R), the batch's rows (-p), 0 (listing, -m)
+ * or a negative SAT_E* code. */
+static int search_batch(const options *o, const input *in, sat_multi *multi, gpu_bufs *B, double *ms,
+                        double *ms_stage2)
+{
+    const int lorder = in->lorder, lsoln = in->lsoln, maxstart = o->maxstart;
+    if (o->cutoff) {
+        /* every row of the batch under the cutoff; a short buffer is grown and the rows selected again */
+        int rc = sat_multi_search_cutoff(multi, lorder, lsoln, maxstart, o->pmax, o->topk, B->pcounts, B->hits_cap,
+                                         B->hits, B->hit_maps, ms);
+        if (rc > B->hits_cap) {
+            B->hits_cap = rc;
+            alloc_hits(B, (size_t)rc, lsoln);
+            rc = sat_multi_hits_cutoff(multi, o->pmax, o->topk, B->pcounts, B->hits_cap, B->hits, B->hit_maps);
         }
-        fprintf(stderr, "Executing simulated annealing tableaux match kernel on GPU for %d quer%s (from %s)...\n",
-                nqb, nqb == 1 ? "y" : "ies", sat_set_name(qsrc, qindex[q0]));
-        double ms = 0.0;
-        int rc = sat_multi_queries_set(multi, nqb, n1s, qtabs, qdmats, SAT_MAXDIM, qtypes, (uint32_t)q0);
-        double ms_stage2 = 0.0;
-        if (rc == SAT_OK && cutoff) {
-            /* every row of the batch under the cutoff; a short buffer is grown and the rows selected again */
-            rc = sat_multi_search_cutoff(multi, lorder, lsoln, maxstart, pmax, topk, pcounts, hits_cap, hits, hit_maps, &ms);
-            if (rc > hits_cap) {
-                free(hits);
-                free(hit_maps);
-                hits_cap = rc;
-                hits = (sat_hit *)malloc(sizeof(sat_hit) * (size_t)hits_cap);
-                hit_maps = lsoln ? (int32_t *)malloc(sizeof(int32_t) * SAT_MAXDIM * (size_t)hits_cap) : NULL;
-                if (!hits || (lsoln && !hit_maps)) { fprintf(stderr, "malloc failed\n"); exit(1); }
-                rc = sat_multi_hits_cutoff(multi, pmax, topk, pcounts, hits_cap, hits, hit_maps);
-            }
-        } else if (rc == SAT_OK && refine)
-            rc = sat_multi_search_refine(multi, lorder, lsoln, maxstart, ncand, refine, kk, hits, hit_maps, NULL, &ms, &ms_stage2);
-        else if (rc == SAT_OK && !nmatch)
-            rc = topk > 0 ? sat_multi_search_topk(multi, lorder, lsoln, maxstart, kk, hits, hit_maps, &ms)
-                          : sat_multi_search(multi, lorder, lsoln, maxstart, scores, ssemaps, &ms);
-        if (rc == SAT_OK && nmatch) {
-            /* match 0 of every entry is the plain search's score and map: the entry rows come from the match
-             * slots; -k ranks the entries as without -m (its own search), the extra rows from the slots */
+        return rc;
+    }
+    if (o->refine)
+        return sat_multi_search_refine(multi, lorder, lsoln, maxstart, o->ncand, o->refine, B->kk, B->hits,
+                                       B->hit_maps, NULL, ms, ms_stage2);
+    if (o->nmatch) {
+        /* match 0 of every entry is the plain search's score and map: the listing's rows come from the match slots;
+         * -k ranks the entries as without -m (its own search), the extra rows from the slots */
+        int rc = sat_multi_search_matches(multi, lorder, maxstart, o->nm, B->all.counts, B->all.scores, B->restarts,
+                                          B->all.maps, ms);
+        if (rc == SAT_OK && o->topk > 0) {
             double ms2 = 0.0;
-            rc = sat_multi_search_matches(multi, lorder, maxstart, nm, mcounts, mscores, mrestarts, mmaps, &ms);
-            if (rc == SAT_OK && topk > 0) {
-                rc = sat_multi_search_topk(multi, lorder, lsoln, maxstart, kk, hits, hit_maps, &ms2);
-                ms += ms2;
-            }
+            rc = sat_multi_search_topk(multi, lorder, lsoln, maxstart, B->kk, B->hits, B->hit_maps, &ms2);
+            *ms += ms2;
         }
-        if (rc < 0) {
-            fprintf(stderr, "kernel launch failed: %s\n", sat_last_error());
-            exit_status = 1;
-            goto bye;
-        }
-        fprintf(stderr, "GPU execution time %f ms\n", ms);
-        if (refine)
-            fprintf(stderr, "refine: stage 2 %f ms, %d candidates per query x %d restarts\n", ms_stage2,
-                    ncand < total ? ncand : total, refine);
-        fprintf(stderr, "%f million iterations/sec\n",
-                ((double)total * nqb * ((double)maxstart * SAT_MAXITER) / (ms / 1000)) / 1.0e6);
-        if (topk > 0 || cutoff) {
-            /* -k: rc rows per query; -p: pcounts[b] rows of query b, after those of the queries before it */
-            size_t first = 0;
-            for (int b = 0; b < nqb; b++) {
-                const int qs = qindex[q0 + b], n1 = n1s[b];
-                const int nrows = cutoff ? pcounts[b] : rc;
-                print_header(ltype, lorder, lsoln, sat_set_name(qsrc, qs), dbfile);
-                for (int r = 0; r < nrows; r++) {
-                    const sat_hit *h = hits + first + r;
-                    out_row(sat_set_name(&db, h->entry), h->score, h->norm2, h->zscore, h->pvalue, n1 + db.order[h->entry], 0, 0);
-                    if (lsoln) {
-                        const int32_t *map = hit_maps + (first + r) * SAT_MAXDIM;
-                        for (int k2 = 0; k2 < n1; k2++)
-                            if (map[k2] >= 0)
-                                out_map_line(k2 + 1, map[k2] + 1);
-                    }
-                    if (nmatch) {
-                        const size_t row = (size_t)b * total + (size_t)h->entry;
-                        print_more_matches(sat_set_name(&db, h->entry), n1, db.order[h->entry], mcounts[row],
-                                           mscores + row * nm, mmaps ? mmaps + row * nm * SAT_MAXDIM : NULL, lsoln, 0);
-                    }
-                }
-                first += (size_t)nrows;
-            }
+        return rc;
+    }
+    if (o->topk > 0)
+        return sat_multi_search_topk(multi, lorder, lsoln, maxstart, B->kk, B->hits, B->hit_maps, ms);
+    return sat_multi_search(multi, lorder, lsoln, maxstart, B->all.scores, B->all.maps, ms);
+}
+
+/* The blocks of queries q0 .. q0 + nqb - 1.  Ranked: each query's rows (-p: pcounts[b] rows of query b after those of
+ * the queries before it, else rc a query).  Listing: each query's small-class rows; its large-class slots are kept
+ * for the deferred block. */
+static void print_batch(const options *o, const input *in, gpu_bufs *B, int q0, int nqb, int rc)
+{
+    const slots *all = &B->all, *large = &B->large;
+    const size_t nm = (size_t)all->nm;
+    size_t first = 0;
+    for (int b = 0; b < nqb; b++) {
+        const size_t row0 = (size_t)b * in->db.count;
+        print_header(in, q0 + b);
+        if (o->ranked) {
+            const size_t nrows = (size_t)(o->cutoff ? B->pcounts[b] : rc);
+            for (size_t r = first; r < first + nrows; r++)
+                print_entry(in, B->hits[r].entry, B->n1s[b], &B->hits[r],
+                            B->hit_maps ? B->hit_maps + r * SAT_MAXDIM : NULL, all, row0 + B->hits[r].entry, 0);
+            first += nrows;
             continue;
         }
-        for (int b = 0; b < nqb; b++) {
-            const int qi = q0 + b, qs = qindex[qi], n1 = n1s[b];
-            /* -m: entry s's slot m at (b * total + s) * nm + m; slot 0 is the plain row */
-            const size_t stride = (size_t)nm;
-            const int32_t *qscores = nmatch ? mscores + (size_t)b * total * nm : scores + (size_t)b * total;
-            const int32_t *qmaps = nmatch ? (mmaps ? mmaps + (size_t)b * total * nm * SAT_MAXDIM : NULL)
-                                          : (ssemaps ? ssemaps + (size_t)b * total * SAT_MAXDIM : NULL);
-            print_header(ltype, lorder, lsoln, sat_set_name(qsrc, qs), dbfile);
-            for (int d = 0; d < cls_count[0]; d++) {
-                int s = cls_index[0][d];
-                print_row(sat_set_name(&db, s), qscores[s * stride], n1, db.order[s],
-                          qmaps ? qmaps + (size_t)s * stride * SAT_MAXDIM : NULL, lsoln, 0);
-                if (nmatch)
-                    print_more_matches(sat_set_name(&db, s), n1, db.order[s], mcounts[(size_t)b * total + s],
-                                       qscores + s * stride, qmaps ? qmaps + (size_t)s * stride * SAT_MAXDIM : NULL, lsoln, 0);
-            }
-            for (int d = 0; d < cls_count[1]; d++) {
-                int s = cls_index[1][d];
-                const size_t row = (size_t)qi * cls_count[1] + d;
-                memcpy(large_scores + row * stride, qscores + s * stride, sizeof(int32_t) * stride);
-                if (nmatch) large_counts[row] = mcounts[(size_t)b * total + s];
-                if (lsoln)
-                    memcpy(large_maps + row * stride * SAT_MAXDIM,
-                           qmaps + (size_t)s * stride * SAT_MAXDIM, sizeof(int32_t) * SAT_MAXDIM * stride);
-            }
+        for (int d = 0; d < in->cls_count[0]; d++)
+            print_entry(in, in->cls_index[0][d], B->n1s[b], NULL, NULL, all, row0 + in->cls_index[0][d], 0);
+        for (int d = 0; d < in->cls_count[1]; d++) {
+            const size_t to = (size_t)(q0 + b) * in->cls_count[1] + d, from = row0 + in->cls_index[1][d];
+            memcpy(large->scores + to * nm, all->scores + from * nm, sizeof(int32_t) * nm);
+            if (all->counts)
+                large->counts[to] = all->counts[from];
+            if (all->maps)
+                memcpy(large->maps + to * nm * SAT_MAXDIM, all->maps + from * nm * SAT_MAXDIM,
+                       sizeof(int32_t) * SAT_MAXDIM * nm);
         }
     }
-    if (cls_count[1] > 0 && topk <= 0 && !cutoff)
-        for (int qi = 0; qi < num_queries; qi++) {
-            const int qs = qindex[qi], n1 = qsrc->order[qs];
-            print_header(ltype, lorder, lsoln, sat_set_name(qsrc, qs), dbfile);
-            for (int d = 0; d < cls_count[1]; d++) {
-                int s = cls_index[1][d];
-                const size_t row = (size_t)qi * cls_count[1] + d;
-                print_row(sat_set_name(&db, s), large_scores[row * nm], n1, db.order[s],
-                          lsoln ? large_maps + row * nm * SAT_MAXDIM : NULL, lsoln, 1);
-                if (nmatch)
-                    print_more_matches(sat_set_name(&db, s), n1, db.order[s], large_counts[row], large_scores + row * nm,
-                                       lsoln ? large_maps + row * nm * SAT_MAXDIM : NULL, lsoln, 1);
-            }
+}
+
+static int run_gpu(const options *o, const input *in)
+{
+    sat_multi *multi = open_multi(o, in);
+    gpu_bufs B;
+    alloc_gpu_bufs(o, in, &B);
+    const int total = in->db.count;
+    int status = 0;
+    for (int q0 = 0; q0 < in->num_queries; q0 += B.batch) {
+        const int nqb = in->num_queries - q0 < B.batch ? in->num_queries - q0 : B.batch;
+        for (int b = 0; b < nqb; b++) {
+            const int qs = in->qindex[q0 + b];
+            uint8_t *tab = B.qtabs + (size_t)b * SAT_MAXDIM * SAT_MAXDIM;
+            B.n1s[b] = in->qsrc->order[qs];
+            sat_set_expand(in->qsrc, qs, SAT_MAXDIM, tab, B.qdmats + (size_t)b * SAT_MAXDIM * SAT_MAXDIM);
+            for (int i = 0; i < B.n1s[b]; i++)
+                B.qtypes[(size_t)b * SAT_MAXDIM + i] = tab[i * SAT_MAXDIM + i];
         }
-bye:
+        fprintf(stderr, "Executing simulated annealing tableaux match kernel on GPU for %d quer%s (from %s)...\n",
+                nqb, nqb == 1 ? "y" : "ies", sat_set_name(in->qsrc, in->qindex[q0]));
+        double ms = 0.0, ms_stage2 = 0.0;
+        int rc = sat_multi_queries_set(multi, nqb, B.n1s, B.qtabs, B.qdmats, SAT_MAXDIM, B.qtypes, (uint32_t)q0);
+        if (rc == SAT_OK)
+            rc = search_batch(o, in, multi, &B, &ms, &ms_stage2);
+        if (rc < 0) {
+            fprintf(stderr, "kernel launch failed: %s\n", sat_last_error());
+            status = 1;
+            break;
+        }
+        fprintf(stderr, "GPU execution time %f ms\n", ms);
+        if (o->refine)
+            fprintf(stderr, "refine: stage 2 %f ms, %d candidates per query x %d restarts\n", ms_stage2,
+                    o->ncand < total ? o->ncand : total, o->refine);
+        fprintf(stderr, "%f million iterations/sec\n",
+                ((double)total * nqb * ((double)o->maxstart * SAT_MAXITER) / (ms / 1000)) / 1.0e6);
+        print_batch(o, in, &B, q0, nqb, rc);
+    }
+    /* the listing's deferred block: every query's large-class rows, after all small-class blocks, with the reference
+     * GPU path's two blanks before the p-value */
+    if (!status && !o->ranked && in->cls_count[1] > 0)
+        for (int qi = 0; qi < in->num_queries; qi++) {
+            print_header(in, qi);
+            for (int d = 0; d < in->cls_count[1]; d++)
+                print_entry(in, in->cls_index[1][d], in->qsrc->order[in->qindex[qi]], NULL, NULL, &B.large,
+                            (size_t)qi * in->cls_count[1] + d, 1);
+        }
     fprintf(stderr, "copied %llu bytes of results from the GPU(s)\n", sat_multi_stat_d2h_bytes(multi));
     sat_multi_destroy(multi);
-    (void)cltype; (void)clorder; (void)clsoln;
-    free(scores);
-    free(ssemaps);
-    free(hits);
-    free(hit_maps);
-    free(pcounts);
-    free(large_scores);
-    free(large_maps);
-    free(large_counts);
-    free(mcounts);
-    free(mscores);
-    free(mrestarts);
-    free(mmaps);
-    free(qtabs);
-    free(qdmats);
-    free(qtypes);
-    free(n1s);
-    free(qindex);
-    free(sid_list);
-    free(cls_index[0]);
-    free(cls_index[1]);
+    free_gpu_bufs(&B);
+    return status;
+}
+
+int main(int argc, char *argv[])
+{
+    options o;
+    parse_options(argc, argv, &o);
+    fprintf(stderr, "MAXDIM = %d\n", SAT_MAXDIM);
+    atexit(out_flush);                                   /* every exit path, exit(1) included */
+    input in;
+    memset(&in, 0, sizeof in);
+    sat_set_init(&in.queries);
+    sat_set_init(&in.db);
+    read_queries(&o, &in);
+    load_database(&o, &in);
+    fprintf(stderr, "maxstart = %d\n", o.maxstart);
+    const int status = o.use_gpu ? run_gpu(&o, &in) : run_host(&o, &in);
+    free_input(&in);
     free(norm2_cache);
-    sat_set_free(&queries);
-    sat_set_free(&db);
-    return exit_status;
+    return status;
 }

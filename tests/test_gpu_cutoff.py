@@ -293,17 +293,23 @@ def _copied(stderr):
     return int(re.search(rb"copied (\d+) bytes", stderr).group(1))
 
 
-@pytest.mark.parametrize("name", ["d2phlb1_TTT", "multiquery", "qmode"])
-def test_cli_cutoff(golden_dir, name):
+@pytest.mark.parametrize("name", ["d2phlb1_TTT", "multiquery", "qmode", "mixed"])
+def test_cli_cutoff(golden_dir, tmp_path, name):
+    cwd, args = golden_dir, []
     if name == "qmode":
         stdin = open(os.path.join(golden_dir, "qmode_sids.txt"), "rb").read()
         args = ["-q", "tableauxdistmatrixdb.small.ascii"]
+    elif name == "mixed":
+        # both size classes, inline LSOLN queries: one query from each class
+        db = sat.synth.make_db(60, 70, 111, sort=False, seed=11)
+        sat.synth.write_ascii(db, tmp_path / "mix.ascii")
+        db.subset([int(np.argmax(db.orders <= 96)), int(np.argmax(db.orders > 96))]).write_ascii(tmp_path / "q.body")
+        stdin, cwd = b"mix.ascii\nT T T\n" + (tmp_path / "q.body").read_bytes(), str(tmp_path)
     else:
         stdin = open(os.path.join(golden_dir, name + ".input"), "rb").read()
-        args = []
 
     def run(*extra):
-        p = subprocess.run([CLI, *args, *extra], input=stdin, cwd=golden_dir, capture_output=True)
+        p = subprocess.run([CLI, *args, *extra], input=stdin, cwd=cwd, capture_output=True)
         assert p.returncode == 0, p.stderr.decode()[-400:]
         return p
 

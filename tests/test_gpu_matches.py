@@ -3,6 +3,7 @@
 every size class, query batches, forced execution layouts and the command line's -m."""
 import ctypes as C
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -274,16 +275,67 @@ def _strip_more_matches(text):
     return "".join(kept), extra
 
 
-@pytest.mark.parametrize("name,args", [("d2phlb1_TTT", []), ("d2phlb1_TFT", []), ("d2phlb1_TTT", ["-k", "400"]), ("multiquery", ["-G", "0,0,0"])])
-def test_cli_more_matches(golden_dir, small_db, name, args):
-    stdin = open(os.path.join(golden_dir, name + ".input"), "rb").read()
-    base = subprocess.run([CLI, "-r", "64", *args], input=stdin, cwd=golden_dir, capture_output=True)
-    more = subprocess.run([CLI, "-r", "64", "-m", "3", *args], input=stdin, cwd=golden_dir, capture_output=True)
+def _assert_mixed_matches(text, db, picks):
+    """-m 3 over both size classes, two queries: each (query, class) block's name:k rows are exactly search_matches'
+    matches 2..count of that class's entries, each with its LSOLN map lines; the large class's come in the deferred
+    blocks after every query's small-class block, with that pass's two blanks before the p-value."""
+    qs = db.subset(picks)
+    with sat.Searcher(0) as s:
+        s.upload(db)
+        s.set_queries([(*qs.dense(q), qs.ssetypes(q)) for q in range(len(picks))])
+        counts, scores, _, maps, _ = s.search_matches(3, True, 64)
+    blocks = text.split("# cudaSaTabsearch")[1:]
+    assert len(blocks) == 2 * len(picks)
+    large_rows = 0
+    for b, block in enumerate(blocks):
+        q, large = b % len(picks), b >= len(picks)
+        n1 = int(qs.orders[q])
+        row = re.compile(r"^\S+:\d -?\d+ \S+ \S+%s\S+$" % ("  " if large else " "))
+        got, cur = {}, None
+        for line in block.splitlines()[3:]:
+            if line[:1] == " " or line.split()[0].isdigit():           # a map line
+                if cur:
+                    got[cur].append(tuple(int(v) for v in line.split()))
+                continue
+            cur = None
+            if ":" in line.split()[0]:
+                assert row.match(line), line
+                base, k = line.split()[0].rsplit(":", 1)
+                cur = (base, int(k), int(line.split()[1]))
+                got[cur] = []
+        want = {}
+        for e in np.nonzero((db.orders > 96) == large)[0]:
+            for k in range(1, int(counts[q, e])):
+                m = maps[q, e, k, :n1]
+                want[(db.names[e], k + 1, int(scores[q, e, k]))] = [(i + 1, int(m[i]) + 1) for i in range(n1) if m[i] >= 0]
+        assert got == want, (q, large)
+        large_rows += len(want) if large else 0
+    assert large_rows, "no large-class entry had a second match"
+
+
+@pytest.mark.parametrize("name,args", [("d2phlb1_TTT", []), ("d2phlb1_TFT", []), ("d2phlb1_TTT", ["-k", "400"]), ("multiquery", ["-G", "0,0,0"]),
+                                       ("mixed", [])])
+def test_cli_more_matches(golden_dir, small_db, tmp_path, name, args):
+    cwd = golden_dir
+    if name == "mixed":
+        # both size classes, inline LSOLN queries (-q would turn LSOLN off): one query from each class
+        db = sat.synth.make_db(60, 70, 111, sort=False, seed=11)
+        assert (db.orders > 96).sum() > 3 and (db.orders <= 96).sum() > 3
+        sat.synth.write_ascii(db, tmp_path / "mix.ascii")
+        picks = [int(np.argmax(db.orders <= 96)), int(np.argmax(db.orders > 96))]
+        db.subset(picks).write_ascii(tmp_path / "q.body")
+        stdin, cwd = b"mix.ascii\nT T T\n" + (tmp_path / "q.body").read_bytes(), str(tmp_path)
+    else:
+        stdin = open(os.path.join(golden_dir, name + ".input"), "rb").read()
+    base = subprocess.run([CLI, "-r", "64", *args], input=stdin, cwd=cwd, capture_output=True)
+    more = subprocess.run([CLI, "-r", "64", "-m", "3", *args], input=stdin, cwd=cwd, capture_output=True)
     assert base.returncode == 0 and more.returncode == 0, more.stderr.decode()[-400:]
     kept, extra = _strip_more_matches(more.stdout.decode())
     assert kept == base.stdout.decode()
     assert extra, "no entry had a second match"
-    if name == "multiquery":
+    if name == "mixed":
+        _assert_mixed_matches(more.stdout.decode(), db, picks)
+    if name in ("multiquery", "mixed"):
         return
     lines = stdin.decode().splitlines()
     lorder = lines[1].split()[1] == "T"
