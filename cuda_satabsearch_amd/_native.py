@@ -27,6 +27,7 @@ ABI_SYMBOLS = (
     "sat_search_matches", "sat_multi_search_matches",
     "sat_search_pairs", "sat_search_refine", "sat_multi_search_refine",
     "sat_hits_cutoff", "sat_multi_search_cutoff", "sat_multi_hits_cutoff",
+    "sat_search_pairs_matches", "sat_multi_search_pairs_matches",
 )
 
 
@@ -115,6 +116,9 @@ def device_lib():
                                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
         lib.sat_search_pairs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+        lib.sat_search_pairs_matches.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+        lib.sat_multi_search_pairs_matches.argtypes = lib.sat_search_pairs_matches.argtypes
         lib.sat_search_refine.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p, C.c_void_p, C.c_void_p]
         lib.sat_multi_search_refine.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

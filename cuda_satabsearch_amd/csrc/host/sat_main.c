@@ -26,7 +26,8 @@
  * database order - the `sort -k 2,2nr | head` users run on the reference's output),
  * -b (keep a binary image `dbfile.satbin` beside the database and load it instead of
  * parsing when it is newer than the ASCII file), -p P (print only the rows whose p-value is <= P, selected on the
- * GPU and ranked as -k; with -k K at most K of them per query).
+ * GPU and ranked as -k; with -k K at most K of them per query), -M M (matches 2..M of the rows that -k / -p / -R print,
+ * in -m's format: a pair-match search of those rows only, after the search that chose them).
  */
 #include <math.h>
 #include <stdarg.h>
@@ -52,17 +53,18 @@ static double now_ms(void)
 }
 
 /* The sanitizer build of the host code links this file against stubs of the device library
- * (tests/native/gpu_stubs.c) that have no several-matches, refine or cutoff entry point: weak references keep that
- * link working, and -m / -R / -p report the missing entry point instead of calling it. */
+ * (tests/native/gpu_stubs.c) that have no several-matches, refine, cutoff or pair-match entry point: weak references
+ * keep that link working, and -m / -R / -p / -M report the missing entry point instead of calling it. */
 #pragma weak sat_multi_search_matches
 #pragma weak sat_multi_search_refine
 #pragma weak sat_multi_search_cutoff
 #pragma weak sat_multi_hits_cutoff
+#pragma weak sat_multi_search_pairs_matches
 
 static void usage(const char *prog)
 {
     fprintf(stderr, "Usage: %s [-c] [-q dbfile] [-r restarts] [-g gpus] [-G gpu,gpu,...] [-s seed] [-k K] [-p P]\n"
-                    "       [-m M] [-R restarts [-C C]] [-b]\n", prog);
+                    "       [-m M] [-M M] [-R restarts [-C C]] [-b]\n", prog);
     fprintf(stderr, "  -c : run on host CPU not GPU card\n");
     fprintf(stderr, "  -q dbfile : database is read from dbfile, list of query\n"
                     "              ids is read from stdin\n");
@@ -74,6 +76,9 @@ static void usage(const char *prog)
     fprintf(stderr, "  -p P : print only rows whose p-value is <= P, ranked as -k (GPU mode)\n");
     fprintf(stderr, "  -m M : up to M (1..%d) non-overlapping matches per structure: after an entry's row,\n"
                     "         matches 2..M as rows named name:k (GPU mode)\n", SAT_MAX_MATCHES);
+    fprintf(stderr, "  -M M : as -m for the rows that -k, -p or -R print only: matches 2..M (1..%d) of each printed\n"
+                    "         row as rows named name:k, found by a search of those rows alone; with -R at its\n"
+                    "         restarts (GPU mode, needs -k or -p)\n", SAT_MAX_MATCHES);
     fprintf(stderr, "  -R restarts : re-score each query's C best entries (by -r) with this many restarts;\n"
                     "                rows as -k, with the new scores (GPU mode, needs -k)\n");
     fprintf(stderr, "  -C C : candidates per query re-scored by -R. Default K\n");
@@ -208,6 +213,7 @@ static void *checked(void *p)
 
 typedef struct {
     int use_gpu, maxstart, want_gpus, bincache, topk, nmatch, refine, ncand, cutoff;
+    int rowmatch;                     /* -M: matches of each printed row */
     double pmax;                      /* -p: the largest p-value printed */
     unsigned long long seed;
     const char *qfile;                /* -q: the database; stdin lists the query SIDs */
@@ -288,7 +294,7 @@ static void parse_options(int argc, char *argv[], options *o)
 {
     *o = (options){ .use_gpu = 1, .maxstart = 128, .want_gpus = 1, .seed = SAT_DEFAULT_SEED };
     int c;
-    while ((c = getopt(argc, argv, "cq:r:g:G:s:bk:p:m:R:C:")) != -1) {
+    while ((c = getopt(argc, argv, "cq:r:g:G:s:bk:p:m:M:R:C:")) != -1) {
         char *end = NULL;
         long v;
         switch (c) {
@@ -317,6 +323,15 @@ static void parse_options(int argc, char *argv[], options *o)
             v = strtol(optarg, &end, 10);
             if (end == optarg || *end != '\0' || v < 1 || v > SAT_MAX_MATCHES) usage(argv[0]);
             o->nmatch = (int)v;
+            break;
+        case 'M':
+            /* 1 .. SAT_MAX_MATCHES, digits only */
+            v = strtol(optarg, &end, 10);
+            if (end == optarg || *end != '\0' || v < 1 || v > SAT_MAX_MATCHES) {
+                fprintf(stderr, "ERROR: -M needs an integer 1..%d (got '%s')\n", SAT_MAX_MATCHES, optarg);
+                usage(argv[0]);
+            }
+            o->rowmatch = (int)v;
             break;
         case 'R':
         case 'C':
@@ -347,6 +362,11 @@ static void parse_options(int argc, char *argv[], options *o)
     if (o->nmatch && !o->use_gpu) die("ERROR: -m needs the GPU path\n");
     if (o->nmatch && !sat_multi_search_matches) die("ERROR: this library has no sat_multi_search_matches\n");
     o->ranked = o->topk > 0 || o->cutoff;                /* (-R needs -k) */
+    if (o->rowmatch && !o->use_gpu) die("ERROR: -M needs the GPU path\n");
+    if (o->rowmatch && o->nmatch) die("ERROR: -M cannot be combined with -m\n");
+    if (o->rowmatch && !o->ranked) die("ERROR: -M needs -k K, -p P or -R restarts -k K\n");
+    if (o->rowmatch && !sat_multi_search_pairs_matches)
+        die("ERROR: this library has no sat_multi_search_pairs_matches\n");
     o->nm = o->nmatch > 0 ? o->nmatch : 1;
 }
 
@@ -506,6 +526,9 @@ typedef struct {
     int32_t *hit_maps;
     int32_t *pcounts;                 /* -p: rows of each query of the batch */
     int hits_cap;                     /* -p: rows hits holds */
+    slots rowm;                       /* -M: the slots of the batch's ranked rows, row r of hits */
+    int32_t *rowm_restarts, *pair_q, *pair_e;   /* -M: each slot's restart; the rows as (query, entry) pairs */
+    size_t rowm_cap;                  /* -M: rows they hold */
 } gpu_bufs;
 
 static void alloc_slots(slots *s, size_t rows, int nm, int with_counts, int lsoln)
@@ -568,6 +591,22 @@ static void free_slots(slots *s)
     free(s->maps);
 }
 
+/* -M: room for the slots of `rows` ranked rows */
+static void alloc_rowm(gpu_bufs *B, size_t rows, int nm, int lsoln)
+{
+    if (rows <= B->rowm_cap)
+        return;
+    free_slots(&B->rowm);
+    free(B->rowm_restarts);
+    free(B->pair_q);
+    free(B->pair_e);
+    alloc_slots(&B->rowm, rows, nm, 1, lsoln);
+    B->rowm_restarts = checked(malloc(sizeof(int32_t) * rows * (size_t)nm));
+    B->pair_q = checked(malloc(sizeof(int32_t) * rows));
+    B->pair_e = checked(malloc(sizeof(int32_t) * rows));
+    B->rowm_cap = rows;
+}
+
 static void free_gpu_bufs(gpu_bufs *B)
 {
     free(B->n1s);
@@ -580,6 +619,10 @@ static void free_gpu_bufs(gpu_bufs *B)
     free(B->hits);
     free(B->hit_maps);
     free(B->pcounts);
+    free_slots(&B->rowm);
+    free(B->rowm_restarts);
+    free(B->pair_q);
+    free(B->pair_e);
 }
 
 /* One multi-GPU context holding the database: it is cut into contiguous shards of equal COST (entries of a
@@ -650,6 +693,27 @@ static int search_batch(const options *o, const input *in, sat_multi *multi, gpu
     return sat_multi_search(multi, lorder, lsoln, maxstart, B->all.scores, B->all.maps, ms);
 }
 
+/* -M: the matches of the batch's ranked rows and of nothing else - a pair-match search of the rows search_batch chose
+ * (rc of them per query, with -p pcounts[b]), at the restarts their scores come from (-R: stage 2's), so that slot 0 of
+ * a row is the row itself.  Only these rows' slots come to the host. */
+static int match_ranked_rows(const options *o, const input *in, sat_multi *multi, gpu_bufs *B, int nqb, int rc,
+                             double *ms)
+{
+    size_t rows = 0;
+    for (int b = 0; b < nqb; b++)
+        rows += (size_t)(o->cutoff ? B->pcounts[b] : rc);
+    alloc_rowm(B, rows ? rows : 1, o->rowmatch, in->lsoln);
+    size_t r = 0;
+    for (int b = 0; b < nqb; b++)
+        for (size_t n = (size_t)(o->cutoff ? B->pcounts[b] : rc); n > 0; n--, r++) {
+            B->pair_q[r] = b;
+            B->pair_e[r] = B->hits[r].entry;
+        }
+    return sat_multi_search_pairs_matches(multi, in->lorder, o->refine ? o->refine : o->maxstart, o->rowmatch, (int)rows,
+                                          B->pair_q, B->pair_e, B->rowm.counts, B->rowm.scores, B->rowm_restarts,
+                                          B->rowm.maps, ms);
+}
+
 /* The blocks of queries q0 .. q0 + nqb - 1.  Ranked: each query's rows (-p: pcounts[b] rows of query b after those of
  * the queries before it, else rc a query).  Listing: each query's small-class rows; its large-class slots are kept
  * for the deferred block. */
@@ -665,7 +729,8 @@ static void print_batch(const options *o, const input *in, gpu_bufs *B, int q0, 
             const size_t nrows = (size_t)(o->cutoff ? B->pcounts[b] : rc);
             for (size_t r = first; r < first + nrows; r++)
                 print_entry(in, B->hits[r].entry, B->n1s[b], &B->hits[r],
-                            B->hit_maps ? B->hit_maps + r * SAT_MAXDIM : NULL, all, row0 + B->hits[r].entry, 0);
+                            B->hit_maps ? B->hit_maps + r * SAT_MAXDIM : NULL, o->rowmatch ? &B->rowm : all,
+                            o->rowmatch ? r : row0 + B->hits[r].entry, 0);
             first += nrows;
             continue;
         }
@@ -710,6 +775,15 @@ static int run_gpu(const options *o, const input *in)
             fprintf(stderr, "kernel launch failed: %s\n", sat_last_error());
             status = 1;
             break;
+        }
+        if (o->rowmatch) {
+            double ms_rows = 0.0;
+            if (match_ranked_rows(o, in, multi, &B, nqb, rc, &ms_rows) != SAT_OK) {
+                fprintf(stderr, "kernel launch failed: %s\n", sat_last_error());
+                status = 1;
+                break;
+            }
+            fprintf(stderr, "matches of the printed rows: %f ms\n", ms_rows);
         }
         fprintf(stderr, "GPU execution time %f ms\n", ms);
         if (o->refine)

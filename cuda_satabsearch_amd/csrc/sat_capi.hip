@@ -230,6 +230,19 @@ pair_kernel_fn pick_pair_kernel(int n1p, int m2w, int cells, bool qlds, int opt)
     });
 }
 
+// the pair-match mode's kernel (sat_sa_pair_match_kernel: options from the arguments, as the match kernel)
+typedef void (*pair_match_kernel_fn)(const SatKernelArgs, const SatPairArgs, const SatMatchArgs);
+pair_match_kernel_fn pick_pair_match_kernel(int n1p, int m2w, int cells, bool qlds)
+{
+    return by_class(n1p, [&](auto c) {
+        return by_flag(qlds, [&](auto q) {
+            return by_layout(m2w, cells, [&](auto m, auto l) -> pair_match_kernel_fn {
+                return sat_sa_pair_match_kernel<decltype(c)::value, decltype(m)::value, decltype(q)::value, decltype(l)::value>;
+            });
+        });
+    });
+}
+
 const int kClassN1P[4] = { 16, 32, 64, 112 };
 
 // (re)build the device query descriptors: pointers into the query blob and into the result
@@ -657,12 +670,77 @@ __global__ void __launch_bounds__(256) pair_scores(const unsigned long long *key
     if (i < n) scores[i] = (int32_t)(uint32_t)(keys[i] >> 32) - 0x40000000;
 }
 
+// Pair-match mode, the selection over the records of one pair (one workgroup per pair of a launch): the
+// pair's slab holds, restart-major, the own best s_r of each of its R restarts and behind them the `setw[pair]` words
+// of its db set D_r (the layout of the match kernel's slab; the items of the pair wrote them from several workgroups).
+// Round 0 takes the largest key (s_r, ~r) - the pair's arg-max, which the record pass also folded into keys[pair]; a
+// count of -1 reports a disagreement -, each later round the largest key with s_r > 0 whose set misses the union of
+// the sets taken so far.  Writes counts[pair], scores / restarts [pair][M] (0 / -1 past the count).
+__global__ void __launch_bounds__(256) pair_match_select(int pair0, int R, int M, const uint32_t *slabs, uint32_t slab_words,
+                                                         const uint8_t *setw, const unsigned long long *keys, int32_t *counts,
+                                                         int32_t *scores, int32_t *restarts)
+{
+    __shared__ unsigned long long red[4];
+    __shared__ uint32_t uni[4];
+    const int p = pair0 + (int)blockIdx.x;
+    const uint32_t *rec = slabs + (size_t)blockIdx.x * slab_words;
+    const int W = setw[p];
+    const int t = (int)threadIdx.x, wave = t >> 6;
+    if (t < 4) uni[t] = 0u;
+    int m = 0;
+    unsigned long long first = 0ull;
+    for (int round = 0; round < M; round++) {
+        __syncthreads();                               // the union of the round before; `red` is free again
+        unsigned long long k = 0ull;
+        for (int r = t; r < R; r += 256) {
+            const int s = (int)rec[r];
+            uint32_t hit = 0u;
+            for (int w = 0; w < W; w++) hit |= rec[(size_t)(w + 1) * (size_t)R + (size_t)r] & uni[w];
+            const unsigned long long rk = (((unsigned long long)(uint32_t)(s + 0x40000000)) << 32) | (0xFFFFFFFFu - (uint32_t)r);
+            k = ((round == 0 || (s > 0 && hit == 0u)) && rk > k) ? rk : k;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const unsigned long long other = __shfl_xor(k, off, 64);
+            k = other > k ? other : k;
+        }
+        if ((t & 63) == 0) red[wave] = k;
+        __syncthreads();
+        unsigned long long cur = red[0];
+        for (int w = 1; w < 4; w++) cur = red[w] > cur ? red[w] : cur;
+        if (cur == 0ull) break;                        // (the same for every thread: nothing left to take)
+        if (round == 0) first = cur;
+        const uint32_t r = 0xFFFFFFFFu - (uint32_t)(cur & 0xFFFFFFFFu);
+        if (t == 0) {
+            scores[(size_t)p * M + m] = (int32_t)(uint32_t)(cur >> 32) - 0x40000000;
+            restarts[(size_t)p * M + m] = (int32_t)r;
+        }
+        if (t < W) uni[t] |= rec[(size_t)(t + 1) * (size_t)R + (size_t)r];
+        m++;
+    }
+    if (t == 0) {
+        counts[p] = first == keys[p] ? m : -1;
+        for (int x = m; x < M; x++) {
+            scores[(size_t)p * M + x] = 0;
+            restarts[(size_t)p * M + x] = -1;
+        }
+    }
+}
+
+// The two passes of the pair-match mode that run the SA kernel (launch_pair_pass): the match arguments and the
+// restarts of a pair (the row length of its record slab).
+struct PairMatchPass { SatMatchArgs mx; int maxstart; };
+
 // One pass of the pair mode: the item groups [goff[g], goff[g + 1]) of d_items, group g holding queries of class
 // gcls[g] and entries of up to gn2[g] SSEs.  Score pass (map_pass = false): the option-specialised LSOLN-off
 // kernels, restarts per item at most `starts`.  Map pass: one restart per item, the general kernel with LSOLN,
 // cut into launches whose best-map slabs stay under 256 MiB (one stream: a launch reuses the region).
+// pm: the pair-match mode's kernel instead (options from the arguments).  Its record pass (map_pass = false) is a score
+// pass that also files the records (pm->mx.rec_slabs, set by the caller); its map pass runs the picked restarts of a
+// pair as the chains of one item (workgroups sized for max_matches chains).
 int launch_pair_pass(sat_ctx *ctx, int lorder, bool map_pass, int starts, const SatPairItem *d_items,
-                     const std::vector<size_t> &goff, const std::vector<int> &gcls, const std::vector<int> &gn2, std::string &info)
+                     const std::vector<size_t> &goff, const std::vector<int> &gcls, const std::vector<int> &gn2, std::string &info,
+                     const PairMatchPass *pm = nullptr)
 {
     hipStream_t stream = ctx->stream;
     SatPairArgs px;
@@ -676,20 +754,22 @@ int launch_pair_pass(sat_ctx *ctx, int lorder, bool map_pass, int starts, const 
         const int m2w = n2max <= 32 ? 1 : (n2max <= 64 ? 2 : 4);
         const int cells = satk::cell_layout(n2max);
         WgShape w;
-        int rc = size_workgroup(ctx, map_pass ? 1 : starts, n1max, n1p, n2max, map_pass, lorder != 0, w);
+        int rc = size_workgroup(ctx, map_pass ? (pm ? pm->mx.max_matches : 1) : starts, n1max, n1p, n2max, map_pass, lorder != 0, w);
         if (rc != SAT_OK) return rc;
-        const bool special = !map_pass && w.lpc_shift == 0 && w.compact == (lorder != 0) && !ctx->tune.general;
+        const bool special = !pm && !map_pass && w.lpc_shift == 0 && w.compact == (lorder != 0) && !ctx->tune.general;
         const int opt = special ? (lorder ? 1 : 0) : -1;
-        pair_kernel_fn fn = pick_pair_kernel(n1p, m2w, cells, w.qlds, opt);
+        const pair_kernel_fn pfn = pm ? nullptr : pick_pair_kernel(n1p, m2w, cells, w.qlds, opt);
+        const pair_match_kernel_fn mfn = pm ? pick_pair_match_kernel(n1p, m2w, cells, w.qlds) : nullptr;
+        const void *fn = pm ? reinterpret_cast<const void *>(mfn) : reinterpret_cast<const void *>(pfn);
         const int opt_used = (special && w.qlds == (n1p < 32)) ? opt : -1;
         const size_t lds_stride = (w.lds + 15) & ~(size_t)15;
         // entries per workgroup: the score pass as a plain launch; the map pass keeps one item per workgroup (its one
         // restart per item gains nothing from packing, and its best-map slabs are counted per item)
         int epw = 1;
-        if ((rc = launch_setup(ctx, reinterpret_cast<const void *>(fn), w.threads, lds_stride, count, map_pass ? nullptr : &epw)) != SAT_OK)
+        if ((rc = launch_setup(ctx, fn, w.threads, lds_stride, count, map_pass ? nullptr : &epw)) != SAT_OK)
             return rc;
-        // (maxstart is unused by the pair mode's restart loop)
-        SatKernelArgs a = base_args(ctx, lorder, map_pass, starts);
+        // (maxstart is unused by the pair mode's restart loop; the pair-match mode's records are laid out by it)
+        SatKernelArgs a = base_args(ctx, lorder, map_pass && !pm, pm ? pm->maxstart : starts);
         a.entry_list = nullptr;
         a.epw = epw;
         a.tpe = w.threads;
@@ -717,10 +797,21 @@ int launch_pair_pass(sat_ctx *ctx, int lorder, bool map_pass, int starts, const 
             const int n = count - i0 < per_launch ? count - i0 : per_launch;
             a.n_list = n;
             px.items = d_items + goff[g] + (size_t)i0;
-            hipLaunchKernelGGL(fn, dim3((n + epw - 1) / epw, 1), dim3(w.threads * epw), lds_launch, stream, a, px);
+            if (pm) {
+                SatMatchArgs mpart = pm->mx;
+                mpart.replay = map_pass ? 1 : 0;
+                hipLaunchKernelGGL(mfn, dim3((n + epw - 1) / epw, 1), dim3(w.threads * epw), lds_launch, stream, a, px, mpart);
+            } else {
+                hipLaunchKernelGGL(pfn, dim3((n + epw - 1) / epw, 1), dim3(w.threads * epw), lds_launch, stream, a, px);
+            }
             HIP_TRY(hipGetLastError());
         }
         char buf[200];
+        if (pm)
+            snprintf(buf, sizeof buf, "%ssat_sa_pair_match_kernel<%d, %d, %s, %d> items %d grid %d x 1 block %d x %d lds %zu",
+                     info.empty() ? "" : "; ", n1p, m2w, w.qlds ? "true" : "false", cells, count, (count + epw - 1) / epw, epw,
+                     w.threads, w.lds);
+        else
         snprintf(buf, sizeof buf, "%ssat_sa_pair_kernel<%d, %d, %s, %d, %d> items %d grid %d x 1 block %d x %d lds %zu",
                  info.empty() ? "" : "; ", n1p, m2w, w.qlds ? "true" : "false", opt_used, cells, count,
                  (count + epw - 1) / epw, epw, w.threads, w.lds);
@@ -732,6 +823,34 @@ int launch_pair_pass(sat_ctx *ctx, int lorder, bool map_pass, int starts, const 
     return SAT_OK;
 }
 
+// a pair list as sat_search_pairs takes it: indices into the current batch and the resident shard
+int check_pairs(const sat_ctx *ctx, const int32_t *query, const int32_t *entry, int npairs)
+{
+    if (npairs < 0 || (npairs > 0 && (!query || !entry))) return sat_fail(SAT_EINVAL, "bad pair list");
+    const int nq = (int)ctx->queries.size();
+    for (int p = 0; p < npairs; p++) {
+        if (query[p] < 0 || query[p] >= nq) return sat_fail(SAT_EINVAL, "pair %d: query %d out of range", p, query[p]);
+        if (entry[p] < 0 || entry[p] >= ctx->n_entries) return sat_fail(SAT_EINVAL, "pair %d: entry %d out of range", p, entry[p]);
+    }
+    return SAT_OK;
+}
+
+// Restarts per item.  A pair's R restarts on one workgroup of T chains take ceil(R / T) rounds at the latency
+// of one workgroup: a few hundred pairs cannot fill the GPU that way.  Cut each pair into about
+// kTargetItems / pairs items of whole rounds, never below one round (and no more items than rounds).
+int pair_split(const sat_ctx *ctx, int maxstart, int npairs)
+{
+    if (ctx->tune.refine_split > 0) return ctx->tune.refine_split < maxstart ? ctx->tune.refine_split : maxstart;
+    constexpr long long kTargetItems = 2048;        // 256 CUs x 8 workgroups
+    const int t0 = std::min(256, (maxstart + 63) / 64 * 64);
+    const long long rounds = (maxstart + t0 - 1) / t0;
+    long long items = (kTargetItems + npairs - 1) / npairs;
+    if (items > rounds) items = rounds;
+    if (items < 1) items = 1;
+    const long long per = (rounds + items - 1) / items;
+    return (int)std::min<long long>(maxstart, per * t0);
+}
+
 }  // namespace
 
 // sat_ctx.hpp: queue a pair search (both passes) on the context's stream
@@ -739,33 +858,13 @@ int sat_pairs_launch(sat_ctx *ctx, int lorder, int maxstart, bool maps, const in
 {
     int rc = check_ready(ctx, true, maxstart);
     if (rc != SAT_OK) return rc;
-    if (npairs < 0 || (npairs > 0 && (!query || !entry))) return sat_fail(SAT_EINVAL, "bad pair list");
-    const int nq = (int)ctx->queries.size();
-    for (int p = 0; p < npairs; p++) {
-        if (query[p] < 0 || query[p] >= nq) return sat_fail(SAT_EINVAL, "pair %d: query %d out of range", p, query[p]);
-        if (entry[p] < 0 || entry[p] >= ctx->n_entries) return sat_fail(SAT_EINVAL, "pair %d: entry %d out of range", p, entry[p]);
-    }
+    if ((rc = check_pairs(ctx, query, entry, npairs)) != SAT_OK) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     if ((rc = refresh_descriptors(ctx, false, ctx->stream)) != SAT_OK) return rc;
     ctx->last_launch_info.clear();
     if (npairs == 0) return SAT_OK;
 
-    // Restarts per item.  A pair's R restarts on one workgroup of T chains take ceil(R / T) rounds at the latency
-    // of one workgroup: a few hundred pairs cannot fill the GPU that way.  Cut each pair into about
-    // kTargetItems / pairs items of whole rounds, never below one round (and no more items than rounds).
-    int split;
-    if (ctx->tune.refine_split > 0) {
-        split = ctx->tune.refine_split < maxstart ? ctx->tune.refine_split : maxstart;
-    } else {
-        constexpr long long kTargetItems = 2048;        // 256 CUs x 8 workgroups
-        const int t0 = std::min(256, (maxstart + 63) / 64 * 64);
-        const long long rounds = (maxstart + t0 - 1) / t0;
-        long long items = (kTargetItems + npairs - 1) / npairs;
-        if (items > rounds) items = rounds;
-        if (items < 1) items = 1;
-        const long long per = (rounds + items - 1) / items;
-        split = (int)std::min<long long>(maxstart, per * t0);
-    }
+    const int split = pair_split(ctx, maxstart, npairs);
     const int per_pair = (maxstart + split - 1) / split;
 
     // groups by (query class, entry order bucket): the launch's LDS is sized for the class and the bucket's largest entry
@@ -865,6 +964,168 @@ int sat_pairs_collect(sat_ctx *ctx, int npairs, int32_t *scores, int32_t *ssemap
             const int n1 = ctx->queries[(size_t)query[p]].n1;
             for (int i = 0; i < SAT_MAXDIM; i++)
                 ssemaps[(size_t)p * SAT_MAXDIM + i] = i < n1 ? mp[(size_t)p * SAT_MAXDIM + i] : -1;
+        }
+    }
+    return SAT_OK;
+}
+
+// sat_ctx.hpp: queue a pair-match search on the context's stream.  The pair list is cut into launches of at most
+// `chunk` pairs whose record slabs stay under the 1 GiB scratch budget; each runs its record pass, the selection and
+// (maps) its map pass before the next one reuses the scratch.
+int sat_pair_matches_launch(sat_ctx *ctx, int lorder, int maxstart, int max_matches, bool maps, const int32_t *query,
+                            const int32_t *entry, int npairs)
+{
+    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
+    if (max_matches < 1 || max_matches > SAT_MAX_MATCHES)
+        return sat_fail(SAT_EINVAL, "max_matches must be 1..%d (got %d)", SAT_MAX_MATCHES, max_matches);
+    int rc = check_ready(ctx, true, maxstart);
+    if (rc != SAT_OK) return rc;
+    if ((rc = check_pairs(ctx, query, entry, npairs)) != SAT_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = refresh_descriptors(ctx, false, ctx->stream)) != SAT_OK) return rc;
+    ctx->last_launch_info.clear();
+    if (npairs == 0) return SAT_OK;
+    const size_t M = (size_t)max_matches;
+    const int split = pair_split(ctx, maxstart, npairs);
+
+    // a pair's slab: the scores and the set words of its restarts, as wide as the widest set of the list
+    int n2_all = 0;
+    for (int p = 0; p < npairs; p++) n2_all = std::max(n2_all, ctx->h_orders[(size_t)entry[p]]);
+    const size_t slab_words = (size_t)(1 + (n2_all <= 32 ? 1 : (n2_all <= 64 ? 2 : 4))) * (size_t)maxstart;
+    const size_t budget_words = ((size_t)1 << 30) / 4;
+    const int chunk = (int)std::min<size_t>((size_t)npairs, std::max<size_t>(1, budget_words / slab_words));
+
+    // items of every launch: its record items by (query class, entry order bucket), then one map item per pair in the
+    // same groups
+    struct Chunk { int p0, n; std::vector<size_t> goff, moff; std::vector<int> gcls, gn2; };
+    std::vector<Chunk> chunks;
+    std::vector<SatPairItem> &items = ctx->h_pitems;
+    std::vector<uint8_t> &setw = ctx->h_psetw;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));      // the previous pair search's uploads have read the tables
+    items.clear();
+    setw.assign((size_t)npairs, 0);
+    for (int p0 = 0; p0 < npairs; p0 += chunk) {
+        Chunk ch;
+        ch.p0 = p0;
+        ch.n = std::min(chunk, npairs - p0);
+        std::vector<std::vector<int>> members(4 * kNumBuckets);
+        std::vector<int> n2max(4 * kNumBuckets, 0);
+        for (int p = p0; p < p0 + ch.n; p++) {
+            const int n2 = ctx->h_orders[(size_t)entry[p]];
+            const int g = ctx->queries[(size_t)query[p]].cls * kNumBuckets + order_bucket(n2);
+            members[(size_t)g].push_back(p);
+            n2max[(size_t)g] = std::max(n2max[(size_t)g], n2);
+        }
+        auto item_of = [&](int p) {
+            SatPairItem it{};
+            it.pair = p;
+            it.desc = ctx->queries[(size_t)query[p]].desc;
+            it.entry = entry[p];
+            it.slab = p - p0;
+            return it;
+        };
+        ch.goff.push_back(items.size());
+        for (int g = 0; g < 4 * kNumBuckets; g++) {
+            if (members[(size_t)g].empty()) continue;
+            const int n2 = n2max[(size_t)g];
+            for (int p : members[(size_t)g]) {
+                setw[(size_t)p] = (uint8_t)(n2 <= 32 ? 1 : (n2 <= 64 ? 2 : 4));      // the M2W of the group's launch
+                for (int r0 = 0; r0 < maxstart; r0 += split) {
+                    SatPairItem it = item_of(p);
+                    it.r0 = r0;
+                    it.r1 = maxstart - r0 < split ? maxstart : r0 + split;
+                    items.push_back(it);
+                }
+            }
+            ch.goff.push_back(items.size());
+            ch.gcls.push_back(g / kNumBuckets);
+            ch.gn2.push_back(n2);
+        }
+        if (maps) {
+            ch.moff.push_back(items.size());
+            for (int g = 0; g < 4 * kNumBuckets; g++) {
+                if (members[(size_t)g].empty()) continue;
+                for (int p : members[(size_t)g]) items.push_back(item_of(p));
+                ch.moff.push_back(items.size());
+            }
+        }
+        chunks.push_back(std::move(ch));
+    }
+    // outputs: counts [pairs], scores [pairs][M], restarts [pairs][M] in one array (one copy to the host), the maps
+    if ((rc = ctx->d_pitems.grow_after(ctx->stream, items.size())) != SAT_OK ||
+        (rc = ctx->d_pkeys.grow_after(ctx->stream, (size_t)npairs)) != SAT_OK ||
+        (rc = ctx->d_psetw.grow_after(ctx->stream, (size_t)npairs)) != SAT_OK ||
+        (rc = ctx->d_pmout.grow_after(ctx->stream, (size_t)npairs * (1 + 2 * M))) != SAT_OK ||
+        (rc = ctx->d_bmap_slabs.grow_after(ctx->stream, slab_words * (size_t)chunk)) != SAT_OK ||
+        (maps && (rc = ctx->d_pmaps.grow_after(ctx->stream, (size_t)npairs * M * SAT_MAXDIM)) != SAT_OK))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->d_pitems.get(), items.data(), items.size() * sizeof(SatPairItem), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->d_psetw.get(), setw.data(), setw.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->d_pkeys.get(), 0, (size_t)npairs * sizeof(unsigned long long), ctx->stream));
+    if (maps) HIP_TRY(hipMemsetAsync(ctx->d_pmaps.get(), 0xFF, (size_t)npairs * M * SAT_MAXDIM, ctx->stream));
+
+    PairMatchPass pm{};
+    pm.maxstart = maxstart;
+    pm.mx.desc_base = ctx->d_qdesc.get();
+    pm.mx.n_entries = 0;                                 // (rows are pairs)
+    pm.mx.max_matches = max_matches;
+    pm.mx.map_pitch = SAT_MAXDIM;
+    pm.mx.rec_slab_words = (uint32_t)slab_words;
+    pm.mx.counts = ctx->d_pmout.get();
+    pm.mx.scores = pm.mx.counts + npairs;
+    pm.mx.restarts = pm.mx.scores + (size_t)npairs * M;
+    pm.mx.maps = ctx->d_pmaps.get();
+    std::string rec_info, map_info;
+    for (const Chunk &ch : chunks) {
+        // (the map pass of the launch before may have replaced the scratch with a larger one)
+        pm.mx.rec_slabs = ctx->d_bmap_slabs.get();
+        if ((rc = launch_pair_pass(ctx, lorder, false, split, ctx->d_pitems.get(), ch.goff, ch.gcls, ch.gn2, rec_info, &pm)) != SAT_OK)
+            return rc;
+        hipLaunchKernelGGL(pair_match_select, dim3((unsigned)ch.n), dim3(256), 0, ctx->stream, ch.p0, maxstart, max_matches,
+                           (const uint32_t *)ctx->d_bmap_slabs.get(), (uint32_t)slab_words, (const uint8_t *)ctx->d_psetw.get(),
+                           (const unsigned long long *)ctx->d_pkeys.get(), pm.mx.counts, pm.mx.scores, pm.mx.restarts);
+        HIP_TRY(hipGetLastError());
+        if (maps && (rc = launch_pair_pass(ctx, lorder, true, 1, ctx->d_pitems.get(), ch.moff, ch.gcls, ch.gn2, map_info, &pm)) != SAT_OK)
+            return rc;
+    }
+    char head[128];
+    snprintf(head, sizeof head, "record pass (%d restarts, %d per item, %zu launches of up to %d pairs): ", maxstart, split,
+             chunks.size(), chunk);
+    ctx->last_launch_info = head + rec_info + " | select";
+    if (maps) ctx->last_launch_info += " | map pass: " + map_info;
+    return SAT_OK;
+}
+
+// sat_ctx.hpp: wait for the pair-match search and copy its rows: 4 * npairs * (1 + 2 M) bytes, + 111 * npairs * M
+// with maps
+int sat_pair_matches_collect(sat_ctx *ctx, int max_matches, int npairs, int32_t *counts, int32_t *scores, int32_t *restarts,
+                             int32_t *ssemaps, const int32_t *query)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (npairs == 0) return SAT_OK;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const size_t P = (size_t)npairs, M = (size_t)max_matches;
+    std::vector<int32_t> out(P * (1 + 2 * M));
+    HIP_TRY(hipMemcpy(out.data(), ctx->d_pmout.get(), out.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    ctx->d2h_bytes += out.size() * sizeof(int32_t);
+    for (size_t p = 0; p < P; p++)
+        if (out[p] < 1 || out[p] > (int32_t)M)
+            return sat_fail(SAT_EDEVICE, "pair %zu: the records and the arg-max key of the record pass disagree", p);
+    memcpy(counts, out.data(), P * sizeof(int32_t));
+    memcpy(scores, out.data() + P, P * M * sizeof(int32_t));
+    memcpy(restarts, out.data() + P + P * M, P * M * sizeof(int32_t));
+    if (ssemaps) {
+        std::vector<int8_t> mp(P * M * SAT_MAXDIM);
+        HIP_TRY(hipMemcpy(mp.data(), ctx->d_pmaps.get(), mp.size(), hipMemcpyDeviceToHost));
+        ctx->d2h_bytes += mp.size();
+        for (size_t p = 0; p < P; p++) {
+            const int n1 = ctx->queries[(size_t)query[p]].n1;
+            for (size_t m = 0; m < M; m++) {
+                const bool used = (int32_t)m < counts[p];
+                const int8_t *in = mp.data() + (p * M + m) * SAT_MAXDIM;
+                int32_t *o = ssemaps + (p * M + m) * SAT_MAXDIM;
+                for (int i = 0; i < SAT_MAXDIM; i++) o[i] = (used && i < n1) ? in[i] : -1;
+            }
         }
     }
     return SAT_OK;
@@ -1588,6 +1849,19 @@ int sat_search_pairs(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int npai
     const int rc = timed(ctx, kernel_ms, [&] { return sat_pairs_launch(ctx, lorder, maxstart, lsoln != 0, query, entry, npairs); });
     if (rc != SAT_OK) return rc;
     return sat_pairs_collect(ctx, npairs, scores, lsoln ? ssemaps : nullptr, query);
+}
+
+int sat_search_pairs_matches(sat_ctx *ctx, int lorder, int maxstart, int max_matches, int npairs, const int32_t *query,
+                             const int32_t *entry, int32_t *counts, int32_t *scores, int32_t *restarts, int32_t *ssemaps,
+                             double *kernel_ms)
+{
+    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
+    if (npairs > 0 && (!counts || !scores || !restarts)) return sat_fail(SAT_EINVAL, "counts / scores / restarts buffer is null");
+    const int rc = timed(ctx, kernel_ms, [&] {
+        return sat_pair_matches_launch(ctx, lorder, maxstart, max_matches, ssemaps != nullptr, query, entry, npairs);
+    });
+    if (rc != SAT_OK) return rc;
+    return sat_pair_matches_collect(ctx, max_matches, npairs, counts, scores, restarts, ssemaps, query);
 }
 
 int sat_search_timed(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int repeats,

@@ -156,6 +156,11 @@ struct sat_ctx {
     DevBuf<unsigned long long> d_pkeys;
     DevBuf<int8_t> d_pmaps;                  // [pairs][SAT_MAXDIM], -1 past n1
     DevBuf<int32_t> d_pscores;
+    // pair-match mode (sat_search_pairs_matches): per pair the words of a db set in its launch; counts [pairs],
+    // scores [pairs][M], restarts [pairs][M] in one array; the maps go to d_pmaps as [pairs][M][SAT_MAXDIM]
+    std::vector<uint8_t> h_psetw;
+    DevBuf<uint8_t> d_psetw;
+    DevBuf<int32_t> d_pmout;
     // refine (sat_search_refine, sat_topk.hip): the final ranking of the nq x C re-scored candidates
     DevBuf<unsigned long long> d_rkeys, d_rsorted;
     DevBuf<int32_t> d_rvals, d_rvals_sorted, d_rfirst, d_rmaps;
@@ -190,5 +195,12 @@ int sat_matches_collect(sat_ctx *ctx, int max_matches, int32_t *counts, int32_t 
 // order) to the host.
 int sat_pairs_launch(sat_ctx *ctx, int lorder, int maxstart, bool maps, const int32_t *query, const int32_t *entry, int npairs);
 int sat_pairs_collect(sat_ctx *ctx, int npairs, int32_t *scores, int32_t *ssemaps, const int32_t *query);
+// Pair-match mode (sat_capi.hip), the two halves of sat_search_pairs_matches for sat_multi_search_pairs_matches: queue
+// the record pass, the selection and (maps) the map pass of every launch of the pair list on the context's stream;
+// then wait and copy the rows of pairs 0 .. npairs - 1 (ssemaps may be NULL).
+int sat_pair_matches_launch(sat_ctx *ctx, int lorder, int maxstart, int max_matches, bool maps, const int32_t *query,
+                            const int32_t *entry, int npairs);
+int sat_pair_matches_collect(sat_ctx *ctx, int max_matches, int npairs, int32_t *counts, int32_t *scores, int32_t *restarts,
+                             int32_t *ssemaps, const int32_t *query);
 // stage 1 of sat_search_refine: a plain search without LSOLN queued on the context's stream
 int sat_launch_plain(sat_ctx *ctx, int lorder, int maxstart);

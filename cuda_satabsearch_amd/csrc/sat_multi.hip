@@ -484,6 +484,57 @@ int sat_multi_search_matches(sat_multi *m, int lorder, int maxstart, int max_mat
     return SAT_OK;
 }
 
+int sat_multi_search_pairs_matches(sat_multi *m, int lorder, int maxstart, int max_matches, int npairs, const int32_t *query,
+                                   const int32_t *entry, int32_t *counts, int32_t *scores, int32_t *restarts, int32_t *ssemaps,
+                                   double *wall_ms)
+{
+    if (!m) return sat_fail(SAT_EINVAL, "null context");
+    if (npairs > 0 && (!counts || !scores || !restarts)) return sat_fail(SAT_EINVAL, "counts / scores / restarts buffer is null");
+    if (max_matches < 1 || max_matches > SAT_MAX_MATCHES)
+        return sat_fail(SAT_EINVAL, "max_matches must be 1..%d (got %d)", SAT_MAX_MATCHES, max_matches);
+    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
+    if (m->ctx[0]->queries.empty()) return sat_fail(SAT_ESTATE, "no query set");
+    if (maxstart < 1) return sat_fail(SAT_EINVAL, "maxstart must be >= 1 (got %d)", maxstart);
+    if (npairs < 0 || (npairs > 0 && (!query || !entry))) return sat_fail(SAT_EINVAL, "bad pair list");
+    const int nq = (int)m->ctx[0]->queries.size();
+    const auto t0 = std::chrono::steady_clock::now();
+    // every pair goes to the shard that holds its entry, under the entry's index there
+    std::vector<std::vector<int32_t>> pq((size_t)m->ndev), pe((size_t)m->ndev), where((size_t)m->ndev);
+    for (int p = 0; p < npairs; p++) {
+        if (query[p] < 0 || query[p] >= nq) return sat_fail(SAT_EINVAL, "pair %d: query %d out of range", p, query[p]);
+        if (entry[p] < 0 || entry[p] >= m->n_entries) return sat_fail(SAT_EINVAL, "pair %d: entry %d out of range", p, entry[p]);
+        const int g = (int)(std::upper_bound(m->begin.begin(), m->begin.end(), entry[p]) - m->begin.begin()) - 1;
+        pq[(size_t)g].push_back(query[p]);
+        pe[(size_t)g].push_back(entry[p] - m->begin[(size_t)g]);
+        where[(size_t)g].push_back(p);
+    }
+    // queued on every GPU, then each shard's rows scattered back into the caller's order
+    int rc = each_shard(m, [&](int g) {
+        return sat_pair_matches_launch(m->ctx[(size_t)g], lorder, maxstart, max_matches, ssemaps != nullptr, pq[(size_t)g].data(),
+                                       pe[(size_t)g].data(), (int)pq[(size_t)g].size());
+    });
+    if (rc != SAT_OK) return rc;
+    const size_t M = (size_t)max_matches;
+    rc = each_shard(m, [&](int g) {
+        const size_t np = pq[(size_t)g].size();
+        std::vector<int32_t> c(np), sc(np * M), rs(np * M), mp(ssemaps ? np * M * SAT_MAXDIM : 0);
+        const int r = sat_pair_matches_collect(m->ctx[(size_t)g], max_matches, (int)np, c.data(), sc.data(), rs.data(),
+                                               ssemaps ? mp.data() : nullptr, pq[(size_t)g].data());
+        if (r != SAT_OK) return r;
+        for (size_t i = 0; i < np; i++) {
+            const size_t p = (size_t)where[(size_t)g][i];
+            counts[p] = c[i];
+            memcpy(scores + p * M, sc.data() + i * M, M * sizeof(int32_t));
+            memcpy(restarts + p * M, rs.data() + i * M, M * sizeof(int32_t));
+            if (ssemaps) memcpy(ssemaps + p * M * SAT_MAXDIM, mp.data() + i * M * SAT_MAXDIM, M * SAT_MAXDIM * sizeof(int32_t));
+        }
+        return SAT_OK;
+    });
+    if (rc != SAT_OK) return rc;
+    if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return SAT_OK;
+}
+
 int sat_multi_search_refine(sat_multi *m, int lorder, int lsoln, int maxstart, int candidates, int refine_maxstart, int k,
                             sat_hit *hits, int32_t *ssemaps, int32_t *first_scores, double *wall_ms, double *stage2_ms)
 {

@@ -1,7 +1,7 @@
-// sat_sa_body.inc - the body of the SA kernel (sat_sa_kernel.hpp), included by its three kernels: the plain one
+// sat_sa_body.inc - the body of the SA kernel (sat_sa_kernel.hpp), included by its four kernels: the plain one
 // (sat_sa_kernel: MATCH = PAIRS = false, the option-specialised and general instantiations), the match mode's
-// (sat_sa_match_kernel: MATCH = true, options from the arguments) and the pair mode's (sat_sa_pair_kernel:
-// PAIRS = true).  Kept as ONE text inside each kernel rather
+// (sat_sa_match_kernel: MATCH = true, options from the arguments), the pair mode's (sat_sa_pair_kernel:
+// PAIRS = true) and the pair-match mode's (sat_sa_pair_match_kernel: both).  Kept as ONE text inside each kernel rather
 // than a device function the kernels call: an inlined callee reads the kernel arguments through a reference and
 // came out as different code for the plain kernels.  Not a header: it expects the kernel's own scope (template
 // parameters N1P, M2W, QLDS, OPT, WPL, CELLS, the arguments `a`, `mx` and `px`, MATCH and PAIRS).
@@ -298,8 +298,15 @@
     int rbest = SAT_K_NO_SCORE;
     Bits<M2W> rset = bits_zero<M2W>();
     if constexpr (MATCH) {
-        mrow = (size_t)(&a.queries[blockIdx.y] - mx.desc_base) * (size_t)mx.n_entries + (size_t)e;
-        mrec = mx.rec_slabs + ((size_t)blockIdx.y * gridDim.x * a.epw + list_pos) * mx.rec_slab_words;
+        if constexpr (PAIRS) {
+            // pair-match mode: the outputs' row is the pair, the records go to the pair's slab (the items of one pair
+            // run in several workgroups); the record pass keeps the item's restarts [r0, r1) set above
+            mrow = (size_t)pit.pair;
+            mrec = mx.rec_slabs + (size_t)pit.slab * mx.rec_slab_words;
+        } else {
+            mrow = (size_t)(&a.queries[blockIdx.y] - mx.desc_base) * (size_t)mx.n_entries + (size_t)e;
+            mrec = mx.rec_slabs + ((size_t)blockIdx.y * gridDim.x * a.epw + list_pos) * mx.rec_slab_words;
+        }
         if (replay) {
             const int cnt = mx.counts[mrow];
             r_begin = tid < cnt ? mx.restarts[mrow * mx.max_matches + tid] : 0;
@@ -998,7 +1005,8 @@
         }
     }
 
-    if constexpr (MATCH) {
+    // (pair-match mode: the records of a pair are complete only when all its items have run - pair_match_select)
+    if constexpr (MATCH && !PAIRS) {
         // ---- greedy selection: match 0 is the arg-max above; each further round takes the largest key among the
         // records with a positive score whose db set misses the union of the sets taken so far.  The union lives in
         // the type masks' LDS words (no wave reads those after the barrier above); only the lane that ran a restart

@@ -225,12 +225,19 @@ struct SatMatchArgs {
 // turn (the slot's n_list bounds the table).  Restart r of a pair is the same Philox stream wherever it runs,
 // so the items of one pair fold their arg-max keys (score, ~restart) into keys[pair] by atomicMax and the
 // largest is exactly sat_search's.  The map pass re-runs each pair's winning restart as one item with LSOLN.
+// Pair-match mode (sat_search_pairs_matches, sat_sa_pair_match_kernel): the same items with the match
+// mode's per-restart records.  Record pass: an item files {s_r, D_r} of its restarts in its PAIR's slab (slab index
+// `slab`, restart-major over all maxstart restarts, as the match kernel lays a slab out) and folds its key into
+// keys[pair]; the selection over a pair's records is a kernel of its own (pair_match_select, sat_capi.hip), because
+// the records of one pair come from several workgroups.  Map pass: one item per pair, chain c re-runs the pair's c-th
+// picked restart; the match outputs are then indexed by the pair (row = item.pair).
 struct SatPairItem {
     int32_t pair;                 // output index
     int32_t desc;                 // descriptor index (into SatKernelArgs::queries) of the query
     int32_t entry;                // index in the resident shard
     int32_t r0, r1;               // restarts r0 .. r1 - 1
-    int32_t pad_[3];
+    int32_t slab;                 // pair-match record pass: the pair's record slab in its launch (SatMatchArgs::rec_slabs)
+    int32_t pad_[2];
 };
 struct SatPairArgs {
     const SatPairItem   *items;   // [n_list]
@@ -624,7 +631,7 @@ __host__ __device__ inline size_t lds_bytes(int n1, int n1p, int n2, int chains,
 // the launch has the same; 0 = read it from the query (a four-way switch per step).
 // CELLS: the launch's cell layout (SAT_CELLS_*, satk::cell_layout of its largest entry).
 // MATCH: the match mode (SatMatchArgs), only in sat_sa_match_kernel; PAIRS: the pair mode (SatPairArgs), only in
-// sat_sa_pair_kernel; the plain kernels compile without any of it.
+// sat_sa_pair_kernel; both: sat_sa_pair_match_kernel; the plain kernels compile without any of it.
 template <int N1P, int M2W, bool QLDS, int OPT, int WPL, int CELLS>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu((OPT < 0 || OPT >= 4) ? 4 : SAT_FAST_WAVES)))
 sat_sa_kernel(const SatKernelArgs a)
@@ -656,5 +663,16 @@ sat_sa_pair_kernel(const SatKernelArgs a, const SatPairArgs px)
     constexpr bool MATCH = false, PAIRS = true;
     constexpr int WPL = 0;
     const SatMatchArgs mx{};
+#include "sat_sa_body.inc"
+}
+
+// The pair-match mode's record and map passes (SatPairArgs items, SatMatchArgs records and outputs): options read from
+// the arguments, one instantiation per query class / db set width / cell layout, as the match kernel.
+template <int N1P, int M2W, bool QLDS, int CELLS>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4)))
+sat_sa_pair_match_kernel(const SatKernelArgs a, const SatPairArgs px, const SatMatchArgs mx)
+{
+    constexpr bool MATCH = true, PAIRS = true;
+    constexpr int OPT = -1, WPL = 0;
 #include "sat_sa_body.inc"
 }

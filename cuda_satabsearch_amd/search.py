@@ -33,6 +33,24 @@ def _search_matches(obj, fn, handle, max_matches, lorder, maxstart, maps):
     return counts, scores, restarts, (ssemaps[..., :obj.n1max] if maps else None), ms.value
 
 
+def _search_pairs_matches(obj, fn, handle, queries, entries, max_matches, lorder, maxstart, maps):
+    """shared by Searcher / MultiSearcher.search_pairs_matches"""
+    q = np.ascontiguousarray(queries, dtype=np.int32).ravel()
+    e = np.ascontiguousarray(entries, dtype=np.int32).ravel()
+    if q.shape != e.shape:
+        raise ValueError("queries and entries differ in length")
+    p, m = len(q), max(int(max_matches), 1)
+    counts = np.zeros(p, np.int32)
+    scores = np.zeros((p, m), np.int32)
+    restarts = np.zeros((p, m), np.int32)
+    ssemaps = np.full((p, m, MAXDIM), -1, np.int32) if maps else None
+    ms = C.c_double(0.0)
+    obj._check(fn(handle, int(bool(lorder)), int(maxstart), int(max_matches), p, q.ctypes.data, e.ctypes.data,
+                  counts.ctypes.data, scores.ctypes.data, restarts.ctypes.data, ssemaps.ctypes.data if maps else None,
+                  C.byref(ms)))
+    return counts, scores, restarts, (ssemaps[..., :obj.n1max] if maps else None), ms.value
+
+
 # struct sat_hit (include/satabsearch.h) as a numpy record: the rows of topk_hits, search_topk and search_refine
 _HIT_DTYPE = np.dtype([("entry", np.int32), ("score", np.int32), ("norm2", np.float64), ("zscore", np.float64),
                        ("pvalue", np.float64)], align=True)
@@ -237,6 +255,14 @@ class Searcher:
                                                maps.ctypes.data if lsoln else None, C.byref(ms)))
         return scores, maps
 
+    def search_pairs_matches(self, queries, entries, max_matches, lorder=True, maxstart=DEFAULT_MAXSTART, maps=True):
+        """The matches of chosen (query, entry) pairs only (sat_search_pairs_matches): queries[p] indexes the current
+        batch, entries[p] the resident shard.  Returns (counts int32[P], scores int32[P, M], restarts int32[P, M],
+        maps int32[P, M, n1max] or None, kernel_ms): exactly search_matches()' rows (queries[p], entries[p]) at the
+        same maxstart and max_matches."""
+        return _search_pairs_matches(self, self._lib.sat_search_pairs_matches, self._ctx, queries, entries, max_matches,
+                                     lorder, maxstart, maps)
+
     def search_refine(self, k, candidates, refine_maxstart, lorder=True, lsoln=False, maxstart=DEFAULT_MAXSTART):
         """Two-stage search (sat_search_refine): every entry at maxstart, then each query's best `candidates`
         at refine_maxstart.  Returns (hits [nq, k'] shaped like topk_hits with stage-2 scores, maps int32[nq, k', 111]
@@ -418,6 +444,12 @@ class MultiSearcher:
     def search_matches(self, max_matches, lorder=True, maxstart=DEFAULT_MAXSTART, maps=True):
         """Searcher.search_matches over every shard, database order (wall_ms instead of kernel_ms)."""
         return _search_matches(self, self._lib.sat_multi_search_matches, self._m, max_matches, lorder, maxstart, maps)
+
+    def search_pairs_matches(self, queries, entries, max_matches, lorder=True, maxstart=DEFAULT_MAXSTART, maps=True):
+        """Searcher.search_pairs_matches with entries[p] an index into the whole database: every pair runs on the shard
+        that holds its entry (wall_ms instead of kernel_ms)."""
+        return _search_pairs_matches(self, self._lib.sat_multi_search_pairs_matches, self._m, queries, entries, max_matches,
+                                     lorder, maxstart, maps)
 
     def search_topk(self, k, lorder=True, lsoln=False, maxstart=DEFAULT_MAXSTART):
         k = min(int(k), self.n_entries)

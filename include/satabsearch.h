@@ -196,6 +196,30 @@ int sat_search_pairs(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int npai
                      const int32_t *entry, int32_t *scores, int32_t *ssemaps, double *kernel_ms);
 
 /*
+ * Pair-match search: the matches of sat_search_matches for a list of (query, entry) pairs instead of the whole
+ * database.  query[p] / entry[p] as sat_search_pairs takes them (any order, repeats allowed, mixed size classes).
+ *   counts    [npairs]                  \
+ *   scores    [npairs][M]                | exactly what sat_search_matches(lorder, maxstart, max_matches) writes for
+ *   restarts  [npairs][M]                | row (query[p], entry[p]): same greedy rule, same unused-slot values
+ *   ssemaps   [npairs][M][SAT_MAXDIM]   /  (score 0, restart -1, map all -1); or NULL: no map pass
+ * so slot 0 is sat_search's score and LSOLN map of the row.  Three passes: the pair kernel with the match mode's
+ * per-restart record {s_r, D_r} (the restarts of a pair cut into items as in sat_search_pairs, SAT_EXP_REFINE_SPLIT;
+ * the records go to the pair's slab in device memory), a selection kernel (one workgroup per pair: the greedy walk
+ * over the pair's records), and with ssemaps a map pass that re-runs the picked restarts of each pair.  Results do not
+ * depend on the cut into items, entries per workgroup, lanes per chain, cell layout, forced modes or sharding.  A slab
+ * is (1 + set words) x 4 x maxstart bytes (set words: 1, 2 or 4 by the largest entry of the list); the list is cut
+ * into launches whose slabs stay under 1 GiB.  npairs == 0 does nothing.  max_matches outside 1..SAT_MAX_MATCHES and
+ * indices out of range are SAT_EINVAL, no database / no query SAT_ESTATE, as sat_search_matches and sat_search_pairs
+ * reject them.  Leaves the buffers behind sat_results / sat_topk / sat_topk_hits / sat_hits_cutoff untouched: it runs
+ * after them, on the rows they chose.  kernel_ms as sat_search.
+ * Copies to the host exactly 4 * npairs * (1 + 2 * max_matches) bytes, + SAT_MAXDIM * npairs * max_matches with
+ * ssemaps - nothing that depends on the database size.
+ */
+int sat_search_pairs_matches(sat_ctx *ctx, int lorder, int maxstart, int max_matches, int npairs, const int32_t *query,
+                             const int32_t *entry, int32_t *counts, int32_t *scores, int32_t *restarts, int32_t *ssemaps,
+                             double *kernel_ms);
+
+/*
  * Queue all further work of this context on the caller's stream (`hip_stream` is a
  * hipStream_t passed as void*; NULL selects the device's default stream).  A context
  * starts on a private non-blocking stream; sat_use_own_stream() goes back to it.
@@ -306,7 +330,7 @@ int sat_search_refine(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int can
                       int k, sat_hit *hits, int32_t *ssemaps, int32_t *first_scores);
 
 
-/* Bytes this context's result calls (sat_results, sat_search, sat_topk, sat_topk_hits, sat_hits_cutoff) have copied
+/* Bytes this context's result calls (sat_results, sat_search, sat_topk, sat_topk_hits, sat_hits_cutoff, the pair searches) have copied
  * from the device to the host since it was created (diagnostics: the best-k path moves O(k) rows). */
 unsigned long long sat_stat_d2h_bytes(const sat_ctx *ctx);
 
@@ -314,7 +338,9 @@ unsigned long long sat_stat_d2h_bytes(const sat_ctx *ctx);
  * sizes and LDS bytes of the launches of this context's last search, "; "-separated.  After sat_search_matches:
  * "record pass: <launches>", followed by " | replay pass: <launches>" when maps were asked for.  After
  * sat_search_pairs: "score pass (R restarts, S per item): <launches>", followed by " | map pass: <launches>" with
- * lsoln; after sat_search_refine: "stage 1: <launches> || stage 2: <the pair search's>". */
+ * lsoln; after sat_search_refine: "stage 1: <launches> || stage 2: <the pair search's>"; after sat_search_pairs_matches:
+ * "record pass (R restarts, S per item, L launches of up to P pairs): <launches> | select", followed by
+ * " | map pass: <launches>" when maps were asked for. */
 const char *sat_last_launch_info(const sat_ctx *ctx);
 
 /*
@@ -384,6 +410,13 @@ int sat_multi_search_matches(sat_multi *m, int lorder, int maxstart, int max_mat
 int sat_multi_search_refine(sat_multi *m, int lorder, int lsoln, int maxstart, int candidates, int refine_maxstart,
                             int k, sat_hit *hits, int32_t *ssemaps, int32_t *first_scores, double *wall_ms,
                             double *stage2_ms);
+/* sat_search_pairs_matches with entry[p] an index into the WHOLE database, exactly what one context holding it returns:
+ * the host routes every pair to the shard that holds its entry (sat_multi_shards), every shard runs its own pairs, the
+ * host puts the rows back in the caller's order.  Only the pairs' rows cross to the host.  wall_ms as sat_multi_search.
+ * Leaves every shard's last search as it was. */
+int sat_multi_search_pairs_matches(sat_multi *m, int lorder, int maxstart, int max_matches, int npairs, const int32_t *query,
+                                   const int32_t *entry, int32_t *counts, int32_t *scores, int32_t *restarts,
+                                   int32_t *ssemaps, double *wall_ms);
 /* sat_hits_cutoff over every shard, exactly what one context holding the whole database returns: each shard selects
  * its own rows (max_rows per query at most), the host merges them per query by score descending, then entry index in
  * the whole database ascending (hits[].entry), and cuts to max_rows.  Same CSR output, capacity contract and return

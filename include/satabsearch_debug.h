@@ -12,8 +12,9 @@
  *   SAT_EXP_LDS_PAD = bytes      unused LDS added per db entry (occupancy experiments)
  *   SAT_EXP_EPW = 1..8           db entries per workgroup (default: chosen per launch from the CU's LDS granules)
  *   SAT_EXP_GENERAL = 1          the general kernel instantiation instead of the option-specialised ones
- *   SAT_EXP_REFINE_SPLIT = n     restarts per work item of a pair search (sat_search_pairs, stage 2 of sat_search_refine;
- *                                default: chosen so that the pairs x items fill the GPU, whole rounds of the chains)
+ *   SAT_EXP_REFINE_SPLIT = n     restarts per work item of a pair search (sat_search_pairs, sat_search_pairs_matches,
+ *                                stage 2 of sat_search_refine; default: chosen so that the pairs x items fill the GPU,
+ *                                whole rounds of the chains)
  *   SAT_EXP_STREAMS = 0          queue the order buckets of a search one after the other instead of concurrently
  *   SAT_EXP_UPLOAD_THREADS = n   host threads slicing the database copy (default 4)
  *   SAT_EXP_UPLOAD_TIMING = 1    per-phase upload times on stderr
