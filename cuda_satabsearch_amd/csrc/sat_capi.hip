@@ -120,8 +120,9 @@ void free_db(sat_ctx *ctx)
     ctx->h_orders.clear();
 }
 
-// ---- kernel choice.  The three kernel families are instantiated over the same size classes and db layouts: the
-// dispatch below calls f with std::integral_constant arguments, so that each family names its instantiations once.
+// ---- kernel choice.  The four kernel families are instantiated over the same size classes and db layouts: the
+// dispatch below calls f with std::integral_constant arguments, so that one walk of the tree (pick_sa_kernel) names every
+// instantiation once.
 template <int V> using Int = std::integral_constant<int, V>;
 
 // f(Int<N1P>) for a query size class
@@ -155,92 +156,106 @@ template <typename F> auto by_layout(int m2w, int cells, F f)
     return f(Int<4>{}, Int<SAT_CELLS_TRI5>{});
 }
 
-typedef void (*kernel_fn)(const SatKernelArgs);
+// The four kernel families (sat_sa_kernel.hpp): bit 0 = the match arguments, bit 1 = the pair arguments
+enum SaMode { kPlain = 0, kMatch = 1, kPair = 2, kPairMatch = 3 };
 
-// The plain kernel.  opt >= 0: an instantiation with the options as compile-time facts (bit 0 LORDER, bit 1 LSOLN,
-// bits 2-3 log2 of the lanes per chain; compaction tables exactly when LORDER); with LORDER and one lane per chain
-// also `wpl`, the words per lane of the compacted rounds when every query of the launch has the same, else 0 (see
-// the kernel's OPT and WPL parameters).  These exist for the default placement of the query cells only (LDS for the
-// 16 class, L1/L2 for the others), for the wpl values a class can have (satk::compaction_shape), and with several
-// lanes per chain for the largest entries only (M2W = 4, words per lane read per query); anything else runs the
-// general instantiation (opt = -1).
-kernel_fn pick_kernel(int n1p, int m2w, int cells, bool qlds, int opt, int wpl)
+// A chosen SA kernel: the instantiation's address and the template arguments it was instantiated with (opt = -1, wpl = 0:
+// the general instantiation).  What is launched (launch_sa) and what sat_last_launch_info names (launch_info) both come
+// from this one record.
+struct SaKernel { const void *fn; int mode, n1p, m2w, cells; bool qlds; int opt, wpl; };
+
+// the instantiation of family MODE; only the plain family has WPL, only the plain and the pair family have OPT
+template <int MODE, int N1P, int M2W, bool QLDS, int OPT, int WPL, int CELLS> const void *sa_instance()
 {
-    return by_class(n1p, [&](auto c) -> kernel_fn {
-        constexpr int N1P = decltype(c)::value;
-        constexpr bool kQ = N1P < 32;
-        auto layout = [&](auto q, auto o, auto w) {
-            return by_layout(m2w, cells, [&](auto m, auto l) -> kernel_fn {
-                return sat_sa_kernel<N1P, decltype(m)::value, decltype(q)::value, decltype(o)::value, decltype(w)::value,
-                                     decltype(l)::value>;
-            });
-        };
-        const std::bool_constant<kQ> q{};
-        if (opt >= 4 && qlds == kQ && m2w == 4)
-            return by_value<4, 11>(opt, [&](auto o) -> kernel_fn { return sat_sa_kernel<N1P, 4, kQ, decltype(o)::value, 0, SAT_CELLS_TRI5>; });
-        if (opt >= 0 && opt < 4 && qlds == kQ)
-            return by_value<0, 3>(opt, [&](auto o) -> kernel_fn {
-                if constexpr ((decltype(o)::value & 1) == 0) return layout(q, o, Int<0>{});     // no compaction: wpl unused
-                else {
-                    if (wpl == 4) return layout(q, o, Int<4>{});
-                    if constexpr (N1P <= 64)
-                        if (wpl == 3) return layout(q, o, Int<3>{});
-                    if constexpr (N1P == 16) {
-                        if (wpl == 2) return layout(q, o, Int<2>{});
-                        if (wpl == 1) return layout(q, o, Int<1>{});
-                    }
-                    return layout(q, o, Int<0>{});           // queries of different shapes: wpl read per query
-                }
-            });
-        return by_flag(qlds, [&](auto qg) { return layout(qg, Int<-1>{}, Int<0>{}); });
-    });
+    static_assert(MODE == kPlain || WPL == 0, "words per lane are an argument of the plain kernel only");
+    static_assert(MODE == kPlain || MODE == kPair || OPT == -1, "the match families read their options from the arguments");
+    if constexpr (MODE == kPlain) return reinterpret_cast<const void *>(sat_sa_kernel<N1P, M2W, QLDS, OPT, WPL, CELLS>);
+    else if constexpr (MODE == kPair) return reinterpret_cast<const void *>(sat_sa_pair_kernel<N1P, M2W, QLDS, OPT, CELLS>);
+    else if constexpr (MODE == kMatch) return reinterpret_cast<const void *>(sat_sa_match_kernel<N1P, M2W, QLDS, CELLS>);
+    else return reinterpret_cast<const void *>(sat_sa_pair_match_kernel<N1P, M2W, QLDS, CELLS>);
 }
 
-// the match mode's kernel (sat_sa_match_kernel: options from the arguments) for a launch's size class and layout
-typedef void (*match_kernel_fn)(const SatKernelArgs, const SatMatchArgs);
-match_kernel_fn pick_match_kernel(int n1p, int m2w, int cells, bool qlds)
+// The kernel of a launch's family, size class and layout.  opt >= 0 asks for an instantiation with the options as
+// compile-time facts (bit 0 LORDER, bit 1 LSOLN, bits 2-3 log2 of the lanes per chain; compaction tables exactly when
+// LORDER); these exist for the default placement of the query cells only (LDS for the 16 class, L1/L2 for the others):
+//   plain       opt 0-3, and with LORDER also `wpl`, the words per lane of the compacted rounds when every query of the
+//               launch has the same, for the values a class can have (satk::compaction_shape), else 0 (see the kernel's
+//               OPT and WPL parameters); opt 4-11 (several lanes per chain) for the largest entries only (M2W = 4, words
+//               per lane read per query);
+//   pair        opt 0 / 1 (LSOLN off, one lane per chain, words per lane read per query);
+//   match, pair-match   none.
+// Anything else runs the general instantiation.
+SaKernel pick_sa_kernel(int mode, int n1p, int m2w, int cells, bool qlds, int opt, int wpl)
 {
-    return by_class(n1p, [&](auto c) {
-        return by_flag(qlds, [&](auto q) {
-            return by_layout(m2w, cells, [&](auto m, auto l) -> match_kernel_fn {
-                return sat_sa_match_kernel<decltype(c)::value, decltype(m)::value, decltype(q)::value, decltype(l)::value>;
-            });
+    SaKernel k = { nullptr, mode, n1p, m2w, cells, qlds, -1, 0 };
+    by_value<kPlain, kPairMatch>(mode, [&](auto md) {
+        by_class(n1p, [&](auto c) {
+            constexpr int MODE = decltype(md)::value, N1P = decltype(c)::value;
+            constexpr bool kQ = N1P < 32;
+            // the instantiation <q, o, w> for the launch's layout
+            auto take = [&](auto q, auto o, auto w) {
+                k.opt = decltype(o)::value;
+                k.wpl = decltype(w)::value;
+                k.fn = by_layout(m2w, cells, [](auto m, auto l) {
+                    return sa_instance<MODE, N1P, decltype(m)::value, decltype(q)::value, decltype(o)::value, decltype(w)::value,
+                                       decltype(l)::value>();
+                });
+            };
+            const std::bool_constant<kQ> q{};
+            if constexpr (MODE == kPlain) {
+                if (opt >= 4 && qlds == kQ && m2w == 4)
+                    return by_value<4, 11>(opt, [&](auto o) {
+                        k.opt = decltype(o)::value;
+                        k.fn = sa_instance<kPlain, N1P, 4, kQ, decltype(o)::value, 0, SAT_CELLS_TRI5>();
+                    });
+                if (opt >= 0 && opt < 4 && qlds == kQ)
+                    return by_value<0, 3>(opt, [&](auto o) {
+                        if constexpr ((decltype(o)::value & 1) == 0) take(q, o, Int<0>{});     // no compaction: wpl unused
+                        else {
+                            if (wpl == 4) return take(q, o, Int<4>{});
+                            if constexpr (N1P <= 64)
+                                if (wpl == 3) return take(q, o, Int<3>{});
+                            if constexpr (N1P == 16) {
+                                if (wpl == 2) return take(q, o, Int<2>{});
+                                if (wpl == 1) return take(q, o, Int<1>{});
+                            }
+                            take(q, o, Int<0>{});               // queries of different shapes: wpl read per query
+                        }
+                    });
+            }
+            if constexpr (MODE == kPair)
+                if ((opt == 0 || opt == 1) && qlds == kQ) return by_value<0, 1>(opt, [&](auto o) { take(q, o, Int<0>{}); });
+            by_flag(qlds, [&](auto qg) { take(qg, Int<-1>{}, Int<0>{}); });
         });
     });
+    return k;
 }
 
-// the pair kernel of a launch's size class and layout: the option-specialised LSOLN-off instantiations for
-// the default layout of LORDER F and T (opt 0 / 1), the general one (opt -1) for everything else and for the
-// map pass
-typedef void (*pair_kernel_fn)(const SatKernelArgs, const SatPairArgs);
-pair_kernel_fn pick_pair_kernel(int n1p, int m2w, int cells, bool qlds, int opt)
+// Launch `k`: the kernel's parameters are the SatKernelArgs, then the pair arguments (pair families), then the match
+// arguments (match families).  The only place that knows which family takes which.
+hipError_t launch_sa(const SaKernel &k, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const SatKernelArgs &a,
+                     const SatPairArgs *px, const SatMatchArgs *mx)
 {
-    return by_class(n1p, [&](auto c) {
-        constexpr int N1P = decltype(c)::value;
-        constexpr bool kQ = N1P < 32;
-        auto layout = [&](auto q, auto o) {
-            return by_layout(m2w, cells, [&](auto m, auto l) -> pair_kernel_fn {
-                return sat_sa_pair_kernel<N1P, decltype(m)::value, decltype(q)::value, decltype(o)::value, decltype(l)::value>;
-            });
-        };
-        const std::bool_constant<kQ> q{};
-        if (opt == 0 && qlds == kQ) return layout(q, Int<0>{});
-        if (opt == 1 && qlds == kQ) return layout(q, Int<1>{});
-        return by_flag(qlds, [&](auto qg) { return layout(qg, Int<-1>{}); });
-    });
+    void *args[3] = { const_cast<SatKernelArgs *>(&a), nullptr, nullptr };
+    int n = 1;
+    if (k.mode & kPair) args[n++] = const_cast<SatPairArgs *>(px);
+    if (k.mode & kMatch) args[n++] = const_cast<SatMatchArgs *>(mx);
+    (void)hipLaunchKernel(k.fn, grid, block, args, lds, stream);
+    return hipGetLastError();
 }
 
-// the pair-match mode's kernel (sat_sa_pair_match_kernel: options from the arguments, as the match kernel)
-typedef void (*pair_match_kernel_fn)(const SatKernelArgs, const SatPairArgs, const SatMatchArgs);
-pair_match_kernel_fn pick_pair_match_kernel(int n1p, int m2w, int cells, bool qlds)
+// One launch as sat_last_launch_info names it: "kernel<template arguments> [items N] grid X x Y block E x T lds B"
+// (items: the pair families' item count; E entry slots of T threads; B the LDS bytes of one slot).
+std::string launch_info(const SaKernel &k, int items, int grid_x, int grid_y, int epw, int threads, size_t lds)
 {
-    return by_class(n1p, [&](auto c) {
-        return by_flag(qlds, [&](auto q) {
-            return by_layout(m2w, cells, [&](auto m, auto l) -> pair_match_kernel_fn {
-                return sat_sa_pair_match_kernel<decltype(c)::value, decltype(m)::value, decltype(q)::value, decltype(l)::value>;
-            });
-        });
-    });
+    static const char *const kName[4] = { "sat_sa_kernel", "sat_sa_match_kernel", "sat_sa_pair_kernel", "sat_sa_pair_match_kernel" };
+    char targs[48] = "", count[32] = "", buf[200];
+    if (k.mode == kPlain) snprintf(targs, sizeof targs, "%d, %d, ", k.opt, k.wpl);
+    if (k.mode == kPair) snprintf(targs, sizeof targs, "%d, ", k.opt);
+    if (k.mode & kPair) snprintf(count, sizeof count, " items %d", items);
+    snprintf(buf, sizeof buf, "%s<%d, %d, %s, %s%d>%s grid %d x %d block %d x %d lds %zu", kName[k.mode], k.n1p, k.m2w,
+             k.qlds ? "true" : "false", targs, k.cells, count, grid_x, grid_y, epw, threads, lds);
+    return buf;
 }
 
 const int kClassN1P[4] = { 16, 32, 64, 112 };
@@ -452,6 +467,39 @@ int size_workgroup(const sat_ctx *ctx, int plan_starts, int n1max, int n1p, int 
     return SAT_OK;
 }
 
+// What a launch of the SA kernel needs beyond its work list: the workgroup, the kernel, the entry slots per workgroup
+// (epw), the LDS bytes between two slots and of the whole workgroup, and the arguments with the shape fields filled
+// (the caller adds the work list, the queries and the slabs).
+struct SaLaunch { WgShape w; SaKernel k; int epw; size_t lds_stride, lds_launch; SatKernelArgs args; };
+
+// Prepare the launches of family `mode` for queries of class c and entries of up to n2max SSEs: the workgroup sized for
+// plan_starts restarts, the kernel - option-specialised when the workgroup has the default layout for these options
+// (which of them exist is pick_sa_kernel's business) -, its LDS limit and, with `pack`, the entry slots per workgroup
+// for `work` entry-query pairs (else one).
+int prepare_sa(sat_ctx *ctx, int mode, int lorder, int lsoln, int maxstart, int plan_starts, int c, int n2max, long long work,
+               bool pack, SaLaunch &out)
+{
+    const int n1p = kClassN1P[c], m2w = satk::set_words(n2max);
+    WgShape &w = out.w;                       // (lds_bytes sizes it for the same set width and cell layout)
+    int rc = size_workgroup(ctx, plan_starts, ctx->class_n1max[c], n1p, n2max, lsoln != 0, lorder != 0, w);
+    if (rc != SAT_OK) return rc;
+    const bool special = (w.lpc_shift == 0 || m2w == 4) && w.compact == (lorder != 0) && !ctx->tune.general && !(mode & kMatch);
+    const int opt = special ? (lorder ? 1 : 0) | (lsoln ? 2 : 0) | (w.lpc_shift << 2) : -1;
+    out.k = pick_sa_kernel(mode, n1p, m2w, satk::cell_layout(n2max), w.qlds, opt, ctx->class_wpl[c]);
+    if (!out.k.fn) return sat_fail(SAT_EDEVICE, "no kernel variant for n1p=%d m2w=%d", n1p, m2w);
+    out.lds_stride = (w.lds + 15) & ~(size_t)15;
+    out.epw = 1;
+    if ((rc = launch_setup(ctx, out.k.fn, w.threads, out.lds_stride, work, pack ? &out.epw : nullptr)) != SAT_OK) return rc;
+    out.lds_launch = out.epw > 1 ? (size_t)out.epw * out.lds_stride : w.lds;
+    out.args = base_args(ctx, lorder, lsoln, maxstart);
+    out.args.epw = out.epw;
+    out.args.tpe = w.threads;
+    out.args.lds_stride = (uint32_t)out.lds_stride;
+    out.args.lpc_shift = w.lpc_shift;
+    out.args.compact = w.compact ? 1 : 0;
+    return SAT_OK;
+}
+
 // The entries a set of launches covers: indices into the resident shard grouped by order bucket.  A search
 // covers the whole shard (the context's lists); the overlapped upload (sat_db_upload_search) searches the
 // shard piece by piece, each piece with lists of its own.
@@ -474,22 +522,17 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
     const ListView &view = piece ? *piece : whole;
     HIP_TRY(hipSetDevice(ctx->device));
     if ((rc = refresh_descriptors(ctx, lsoln != 0, stream)) != SAT_OK) return rc;
-
-    SatKernelArgs a = base_args(ctx, lorder, lsoln, maxstart);
 #ifdef SAT_DIAG
-    HIP_TRY(satdiag::begin(stream, a.diag));
+    unsigned long long *diag = nullptr;
+    HIP_TRY(satdiag::begin(stream, diag));
 #endif
 
-    struct Planned {
-        kernel_fn fn; match_kernel_fn mfn; SatKernelArgs args; int count, nqc, threads, n2max, max_entries, epw; size_t lds, slab_words;
-        int n1p, m2w, qlds, opt, wpl, cells;     // the instantiation's template arguments (sat_last_launch_info)
-    };
+    const bool replay = mx && mx->replay;
+    struct Planned { SaLaunch l; int count, nqc, n2max, max_entries; size_t slab_words; };
     std::vector<Planned> plan;
     for (int c = 0; c < 4; c++) {
         const int nqc = ctx->class_begin[c + 1] - ctx->class_begin[c];
         if (nqc == 0) continue;
-        const int n1p = kClassN1P[c], n1max = ctx->class_n1max[c];
-        a.queries = ctx->d_qdesc.get() + ctx->class_begin[c];
         // A small problem cannot fill the GPU: its run time is the latency of one workgroup per
         // launch, so all order buckets go into ONE launch sized for the largest entry instead of
         // one launch per bucket queued behind each other.
@@ -498,61 +541,26 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
         for (int b = 0; b < kNumBuckets; b++)
             if (view.n2max[b] > overall_n2max) overall_n2max = view.n2max[b];
         for (int b = 0; b < kNumBuckets; b++) {
-            int count = view.begin[b + 1] - view.begin[b];
-            int n2max = view.n2max[b];
+            Planned pl;
+            pl.count = view.begin[b + 1] - view.begin[b];
+            pl.n2max = view.n2max[b];
             if (one_launch) {
                 if (b > 0) break;
-                count = view.n;
-                n2max = overall_n2max;
+                pl.count = view.n;
+                pl.n2max = overall_n2max;
             }
-            if (count == 0) continue;
-            const int m2w = n2max <= 32 ? 1 : (n2max <= 64 ? 2 : 4);
-            const int cells = satk::cell_layout(n2max);           // (lds_bytes sizes the workgroup for the same layout)
-
-            const int plan_starts = (mx && mx->replay) ? mx->max_matches : maxstart;
-            WgShape w;
-            rc = size_workgroup(ctx, plan_starts, n1max, n1p, n2max, lsoln != 0, lorder != 0, w);
-            if (rc != SAT_OK) return rc;
-            const int chains = w.chains, lpc_shift = w.lpc_shift, threads = w.threads;
-            const bool compact = w.compact, qlds = w.qlds;
-            const size_t lds = w.lds;
-            a.lpc_shift = lpc_shift;
-            a.compact = compact ? 1 : 0;
-            // option-specialised instantiation when the layout is the default one for these options
-            const bool special = (lpc_shift == 0 || m2w == 4) && compact == (lorder != 0) && !ctx->tune.general && !mx;
-            const int opt = special ? (lorder ? 1 : 0) | (lsoln ? 2 : 0) | (lpc_shift << 2) : -1;
-            kernel_fn fn = mx ? nullptr : pick_kernel(n1p, m2w, cells, qlds, opt, ctx->class_wpl[c]);
-            match_kernel_fn mfn = mx ? pick_match_kernel(n1p, m2w, cells, qlds) : nullptr;
-            const void *fn_ptr = mx ? reinterpret_cast<const void *>(mfn) : reinterpret_cast<const void *>(fn);
-            if (!fn_ptr) return sat_fail(SAT_EDEVICE, "no kernel variant for n1p=%d m2w=%d", n1p, m2w);
-            a.entry_list = view.d_list + (one_launch ? view.begin[0] : view.begin[b]);
-            const size_t lds_stride = (lds + 15) & ~(size_t)15;
-            int epw;
-            if ((rc = launch_setup(ctx, fn_ptr, threads, lds_stride, (long long)count * nqc, &epw)) != SAT_OK) return rc;
-            a.epw = epw;
-            a.tpe = threads;
-            a.lds_stride = (uint32_t)lds_stride;
-            Planned pl;
-            pl.epw = epw;
-            pl.fn = fn;
-            pl.mfn = mfn;
-            pl.args = a;
-            pl.count = count;
+            if (pl.count == 0) continue;
             pl.nqc = nqc;
-            pl.threads = threads;
-            pl.lds = lds;
-            pl.n2max = n2max;
-            pl.slab_words = (lsoln || (mx && mx->replay)) ? (size_t)((n1max + 3) / 4) * chains
-                          : (mx ? (size_t)(1 + m2w) * (size_t)maxstart : 0);
-            pl.n1p = n1p;
-            pl.m2w = m2w;
-            pl.cells = cells;
-            pl.qlds = qlds ? 1 : 0;
-            pl.opt = opt;
-            // the words-per-lane argument as pick_kernel resolves it (0 = read per query)
-            pl.wpl = (opt >= 0 && opt < 4 && (opt & 1) && qlds == (n1p < 32)) ? ctx->class_wpl[c] : 0;
-            if (pl.wpl && !((pl.wpl == 4) || (pl.wpl == 3 && n1p <= 64) || (n1p == 16))) pl.wpl = 0;
-            if (opt < 0 || qlds != (n1p < 32)) pl.opt = -1;
+            rc = prepare_sa(ctx, mx ? kMatch : kPlain, lorder, lsoln, maxstart, replay ? mx->max_matches : maxstart, c, pl.n2max,
+                            (long long)pl.count * nqc, true, pl.l);
+            if (rc != SAT_OK) return rc;
+            pl.l.args.queries = ctx->d_qdesc.get() + ctx->class_begin[c];
+            pl.l.args.entry_list = view.d_list + (one_launch ? view.begin[0] : view.begin[b]);
+#ifdef SAT_DIAG
+            pl.l.args.diag = diag;
+#endif
+            pl.slab_words = (lsoln || replay) ? (size_t)((ctx->class_n1max[c] + 3) / 4) * pl.l.w.chains
+                          : (mx ? (size_t)(1 + pl.l.k.m2w) * (size_t)maxstart : 0);
             plan.push_back(pl);
         }
     }
@@ -581,7 +589,7 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
             if (pl.max_entries < 1) pl.max_entries = 1;
             if (pl.max_entries > pl.count) pl.max_entries = pl.count;
             // (the spare slots of a launch's last workgroup have slabs too)
-            const size_t need = pl.slab_words * (size_t)(pl.max_entries + pl.epw - 1) * (size_t)qn_cap;
+            const size_t need = pl.slab_words * (size_t)(pl.max_entries + pl.l.epw - 1) * (size_t)qn_cap;
             if (need > need_total) need_total = need;
         }
         need_total *= (size_t)nlanes;                                  // one region per lane of launches
@@ -593,29 +601,26 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
         const int lane = fork ? (int)(i % (size_t)nlanes) : 0;
         hipStream_t s = fork ? ctx->side_stream[lane] : stream;
         if (fork && i < (size_t)nlanes) HIP_TRY(hipStreamWaitEvent(s, ctx->ev_fork, 0));
-        const int max_entries = slabs ? pl.max_entries : pl.count;
+        const int max_entries = slabs ? pl.max_entries : pl.count, epw = pl.l.epw;
         for (int q0 = 0; q0 < pl.nqc; q0 += 65535) {
             const int qn = pl.nqc - q0 < 65535 ? pl.nqc - q0 : 65535;
             for (int e0 = 0; e0 < pl.count; e0 += max_entries) {
                 const int en = pl.count - e0 < max_entries ? pl.count - e0 : max_entries;
-                SatKernelArgs part = pl.args;
-                part.queries = pl.args.queries + q0;
-                part.entry_list = pl.args.entry_list + e0;
+                SatKernelArgs part = pl.l.args;
+                part.queries += q0;
+                part.entry_list += e0;
+                part.n_list = en;
+                // the lane's scratch region: best maps (LSOLN, replay pass) or the record pass's records
                 SatMatchArgs mpart = mx ? *mx : SatMatchArgs{};
-                if (lsoln || (mx && mx->replay)) {
+                if (lsoln || replay) {
                     part.bmap_slabs = ctx->d_bmap_slabs.get() + (size_t)lane * lane_region_words;
                     part.bmap_slab_words = (uint32_t)pl.slab_words;
                 } else if (mx) {
                     mpart.rec_slabs = ctx->d_bmap_slabs.get() + (size_t)lane * lane_region_words;
                     mpart.rec_slab_words = (uint32_t)pl.slab_words;
                 }
-                part.n_list = en;
-                const size_t lds_launch = pl.epw > 1 ? (size_t)pl.epw * pl.args.lds_stride : pl.lds;
-                if (mx)
-                    hipLaunchKernelGGL(pl.mfn, dim3((en + pl.epw - 1) / pl.epw, qn), dim3(pl.threads * pl.epw), lds_launch, s, part, mpart);
-                else
-                    hipLaunchKernelGGL(pl.fn, dim3((en + pl.epw - 1) / pl.epw, qn), dim3(pl.threads * pl.epw), lds_launch, s, part);
-                HIP_TRY(hipGetLastError());
+                HIP_TRY(launch_sa(pl.l.k, dim3((en + epw - 1) / epw, qn), dim3(pl.l.w.threads * epw), pl.l.lds_launch, s, part, nullptr,
+                                  &mpart));
             }
         }
     }
@@ -628,16 +633,9 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
     ctx->searched_lsoln = lsoln != 0;
     ctx->last_launch_info.clear();
     for (size_t i = 0; i < plan.size(); i++) {
-        char buf[160];
-        if (mx)
-            snprintf(buf, sizeof buf, "%ssat_sa_match_kernel<%d, %d, %s, %d> grid %d x %d block %d x %d lds %zu", i ? "; " : "", plan[i].n1p,
-                     plan[i].m2w, plan[i].qlds ? "true" : "false", plan[i].cells,
-                     (plan[i].count + plan[i].epw - 1) / plan[i].epw, plan[i].nqc, plan[i].epw, plan[i].threads, plan[i].lds);
-        else
-        snprintf(buf, sizeof buf, "%ssat_sa_kernel<%d, %d, %s, %d, %d, %d> grid %d x %d block %d x %d lds %zu", i ? "; " : "", plan[i].n1p,
-                 plan[i].m2w, plan[i].qlds ? "true" : "false", plan[i].opt, plan[i].wpl, plan[i].cells,
-                 (plan[i].count + plan[i].epw - 1) / plan[i].epw, plan[i].nqc, plan[i].epw, plan[i].threads, plan[i].lds);
-        ctx->last_launch_info += buf;
+        const Planned &pl = plan[i];
+        if (i) ctx->last_launch_info += "; ";
+        ctx->last_launch_info += launch_info(pl.l.k, 0, (pl.count + pl.l.epw - 1) / pl.l.epw, pl.nqc, pl.l.epw, pl.l.w.threads, pl.l.w.lds);
     }
 #ifdef SAT_DIAG
     HIP_TRY(satdiag::end(stream));
@@ -731,91 +729,64 @@ __global__ void __launch_bounds__(256) pair_match_select(int pair0, int R, int M
 // restarts of a pair (the row length of its record slab).
 struct PairMatchPass { SatMatchArgs mx; int maxstart; };
 
-// One pass of the pair mode: the item groups [goff[g], goff[g + 1]) of d_items, group g holding queries of class
-// gcls[g] and entries of up to gn2[g] SSEs.  Score pass (map_pass = false): the option-specialised LSOLN-off
-// kernels, restarts per item at most `starts`.  Map pass: one restart per item, the general kernel with LSOLN,
-// cut into launches whose best-map slabs stay under 256 MiB (one stream: a launch reuses the region).
+// The item groups of a pair list or of one chunk of it (build_pair_items): score items [goff[g], goff[g + 1]) and, with
+// maps, map items [moff[g], moff[g + 1]) of the item table hold queries of class gcls[g] and entries of up to gn2[g] SSEs.
+struct PairGroups { std::vector<size_t> goff, moff; std::vector<int> gcls, gn2; };
+
+// One pass of the pair mode over the item groups of `grp` in d_items: its score items (map_pass = false) or its map
+// items.  Score pass: the option-specialised LSOLN-off kernels, restarts per item at most `starts`.  Map pass: one restart per
+// item, the general kernel with LSOLN, cut into launches whose best-map slabs stay under 256 MiB (one stream: a launch
+// reuses the region).
 // pm: the pair-match mode's kernel instead (options from the arguments).  Its record pass (map_pass = false) is a score
 // pass that also files the records (pm->mx.rec_slabs, set by the caller); its map pass runs the picked restarts of a
 // pair as the chains of one item (workgroups sized for max_matches chains).
-int launch_pair_pass(sat_ctx *ctx, int lorder, bool map_pass, int starts, const SatPairItem *d_items,
-                     const std::vector<size_t> &goff, const std::vector<int> &gcls, const std::vector<int> &gn2, std::string &info,
-                     const PairMatchPass *pm = nullptr)
+int launch_pair_pass(sat_ctx *ctx, int lorder, bool map_pass, int starts, const SatPairItem *d_items, const PairGroups &grp,
+                     std::string &info, const PairMatchPass *pm = nullptr)
 {
     hipStream_t stream = ctx->stream;
+    const std::vector<size_t> &off = map_pass ? grp.moff : grp.goff;
     SatPairArgs px;
     px.items = nullptr;
     px.keys = ctx->d_pkeys.get();
     px.maps = ctx->d_pmaps.get();
-    for (size_t g = 0; g < gcls.size(); g++) {
-        const int count = (int)(goff[g + 1] - goff[g]);
+    SatMatchArgs mpart = pm ? pm->mx : SatMatchArgs{};
+    mpart.replay = map_pass ? 1 : 0;
+    for (size_t g = 0; g < grp.gcls.size(); g++) {
+        const int count = (int)(off[g + 1] - off[g]);
         if (count == 0) continue;
-        const int c = gcls[g], n1p = kClassN1P[c], n1max = ctx->class_n1max[c], n2max = gn2[g];
-        const int m2w = n2max <= 32 ? 1 : (n2max <= 64 ? 2 : 4);
-        const int cells = satk::cell_layout(n2max);
-        WgShape w;
-        int rc = size_workgroup(ctx, map_pass ? (pm ? pm->mx.max_matches : 1) : starts, n1max, n1p, n2max, map_pass, lorder != 0, w);
+        // (the arguments' maxstart is unused by the pair mode's restart loop; the pair-match mode's records are laid out
+        // by it.)  Entries per workgroup: the score pass as a plain launch; the map pass keeps one item per workgroup (its
+        // one restart per item gains nothing from packing, and its best-map slabs are counted per item)
+        SaLaunch l;
+        int rc = prepare_sa(ctx, pm ? kPairMatch : kPair, lorder, map_pass && !pm, pm ? pm->maxstart : starts,
+                            map_pass ? (pm ? pm->mx.max_matches : 1) : starts, grp.gcls[g], grp.gn2[g], count, !map_pass, l);
         if (rc != SAT_OK) return rc;
-        const bool special = !pm && !map_pass && w.lpc_shift == 0 && w.compact == (lorder != 0) && !ctx->tune.general;
-        const int opt = special ? (lorder ? 1 : 0) : -1;
-        const pair_kernel_fn pfn = pm ? nullptr : pick_pair_kernel(n1p, m2w, cells, w.qlds, opt);
-        const pair_match_kernel_fn mfn = pm ? pick_pair_match_kernel(n1p, m2w, cells, w.qlds) : nullptr;
-        const void *fn = pm ? reinterpret_cast<const void *>(mfn) : reinterpret_cast<const void *>(pfn);
-        const int opt_used = (special && w.qlds == (n1p < 32)) ? opt : -1;
-        const size_t lds_stride = (w.lds + 15) & ~(size_t)15;
-        // entries per workgroup: the score pass as a plain launch; the map pass keeps one item per workgroup (its one
-        // restart per item gains nothing from packing, and its best-map slabs are counted per item)
-        int epw = 1;
-        if ((rc = launch_setup(ctx, fn, w.threads, lds_stride, count, map_pass ? nullptr : &epw)) != SAT_OK)
-            return rc;
-        // (maxstart is unused by the pair mode's restart loop; the pair-match mode's records are laid out by it)
-        SatKernelArgs a = base_args(ctx, lorder, map_pass && !pm, pm ? pm->maxstart : starts);
+        SatKernelArgs &a = l.args;
         a.entry_list = nullptr;
-        a.epw = epw;
-        a.tpe = w.threads;
-        a.lds_stride = (uint32_t)lds_stride;
         a.queries = ctx->d_qdesc.get();                 // items carry descriptor indices
-        a.lpc_shift = w.lpc_shift;
-        a.compact = w.compact ? 1 : 0;
 #ifdef SAT_DIAG
         HIP_TRY(satdiag::begin(stream, a.diag));
 #endif
         int per_launch = count;
         if (map_pass) {
-            const size_t slab_words = (size_t)((n1max + 3) / 4) * (size_t)w.chains;
+            const size_t slab_words = (size_t)((ctx->class_n1max[grp.gcls[g]] + 3) / 4) * (size_t)l.w.chains;
             const size_t budget = ((size_t)1 << 28) / 4;
             per_launch = (int)std::min<size_t>((size_t)count, std::max<size_t>(1, budget / slab_words));
             // one slab per entry slot of a launch, the spare slots of its last workgroup included (the kernel indexes
             // the slab by slot; with epw = 1 there are none)
-            const size_t slabs = (size_t)per_launch + (size_t)epw - 1;
+            const size_t slabs = (size_t)per_launch + (size_t)l.epw - 1;
             if ((rc = ctx->d_bmap_slabs.grow_after(stream, slab_words * slabs)) != SAT_OK) return rc;
             a.bmap_slabs = ctx->d_bmap_slabs.get();
             a.bmap_slab_words = (uint32_t)slab_words;
         }
-        const size_t lds_launch = epw > 1 ? (size_t)epw * lds_stride : w.lds;
         for (int i0 = 0; i0 < count; i0 += per_launch) {
             const int n = count - i0 < per_launch ? count - i0 : per_launch;
             a.n_list = n;
-            px.items = d_items + goff[g] + (size_t)i0;
-            if (pm) {
-                SatMatchArgs mpart = pm->mx;
-                mpart.replay = map_pass ? 1 : 0;
-                hipLaunchKernelGGL(mfn, dim3((n + epw - 1) / epw, 1), dim3(w.threads * epw), lds_launch, stream, a, px, mpart);
-            } else {
-                hipLaunchKernelGGL(pfn, dim3((n + epw - 1) / epw, 1), dim3(w.threads * epw), lds_launch, stream, a, px);
-            }
-            HIP_TRY(hipGetLastError());
+            px.items = d_items + off[g] + (size_t)i0;
+            HIP_TRY(launch_sa(l.k, dim3((n + l.epw - 1) / l.epw, 1), dim3(l.w.threads * l.epw), l.lds_launch, stream, a, &px, &mpart));
         }
-        char buf[200];
-        if (pm)
-            snprintf(buf, sizeof buf, "%ssat_sa_pair_match_kernel<%d, %d, %s, %d> items %d grid %d x 1 block %d x %d lds %zu",
-                     info.empty() ? "" : "; ", n1p, m2w, w.qlds ? "true" : "false", cells, count, (count + epw - 1) / epw, epw,
-                     w.threads, w.lds);
-        else
-        snprintf(buf, sizeof buf, "%ssat_sa_pair_kernel<%d, %d, %s, %d, %d> items %d grid %d x 1 block %d x %d lds %zu",
-                 info.empty() ? "" : "; ", n1p, m2w, w.qlds ? "true" : "false", opt_used, cells, count,
-                 (count + epw - 1) / epw, epw, w.threads, w.lds);
-        info += buf;
+        if (!info.empty()) info += "; ";
+        info += launch_info(l.k, count, (count + l.epw - 1) / l.epw, 1, l.epw, l.w.threads, l.w.lds);
 #ifdef SAT_DIAG
         HIP_TRY(satdiag::end(stream));
 #endif
@@ -851,6 +822,83 @@ int pair_split(const sat_ctx *ctx, int maxstart, int npairs)
     return (int)std::min<long long>(maxstart, per * t0);
 }
 
+// the items build_pair_items makes of a whole pair list (the callers reserve their table once)
+size_t pair_item_count(int npairs, int maxstart, int split, bool maps)
+{
+    return (size_t)npairs * (size_t)((maxstart + split - 1) / split) + (maps ? (size_t)npairs : 0);
+}
+
+// Append the items of pairs p0 .. p0 + n - 1 to `items`, grouped by (query class, entry order bucket) - a launch's LDS
+// is sized for the class and the group's largest entry: the score items, each pair cut into items of `split` restarts,
+// then (maps) one map item per pair in the same groups, its restarts filled in on the device.  SatPairItem::slab, read
+// by the pair-match kernel only, numbers the pairs from p0.  setw (pair-match mode, else null): setw[p] = the set
+// words of pair p's launch.
+PairGroups build_pair_items(const sat_ctx *ctx, const int32_t *query, const int32_t *entry, int p0, int n, int maxstart, int split,
+                            bool maps, std::vector<SatPairItem> &items, uint8_t *setw)
+{
+    std::vector<std::vector<int>> members(4 * kNumBuckets);
+    std::vector<int> n2max(4 * kNumBuckets, 0);
+    for (int p = p0; p < p0 + n; p++) {
+        const int n2 = ctx->h_orders[(size_t)entry[p]];
+        const int g = ctx->queries[(size_t)query[p]].cls * kNumBuckets + order_bucket(n2);
+        members[(size_t)g].push_back(p);
+        n2max[(size_t)g] = std::max(n2max[(size_t)g], n2);
+    }
+    auto item_of = [&](int p, int r0, int r1) {
+        SatPairItem it{};
+        it.pair = p;
+        it.desc = ctx->queries[(size_t)query[p]].desc;
+        it.entry = entry[p];
+        it.r0 = r0;
+        it.r1 = r1;
+        it.slab = p - p0;
+        return it;
+    };
+    PairGroups grp;
+    grp.goff.push_back(items.size());
+    for (int g = 0; g < 4 * kNumBuckets; g++) {
+        if (members[(size_t)g].empty()) continue;
+        for (int p : members[(size_t)g]) {
+            if (setw) setw[p] = (uint8_t)satk::set_words(n2max[(size_t)g]);
+            for (int r0 = 0; r0 < maxstart; r0 += split) items.push_back(item_of(p, r0, maxstart - r0 < split ? maxstart : r0 + split));
+        }
+        grp.goff.push_back(items.size());
+        grp.gcls.push_back(g / kNumBuckets);
+        grp.gn2.push_back(n2max[(size_t)g]);
+    }
+    if (maps) {
+        grp.moff.push_back(items.size());
+        for (int g = 0; g < 4 * kNumBuckets; g++) {
+            if (members[(size_t)g].empty()) continue;
+            for (int p : members[(size_t)g]) items.push_back(item_of(p, 0, 0));
+            grp.moff.push_back(items.size());
+        }
+    }
+    return grp;
+}
+
+// One map of the device's outputs (int8, SAT_MAXDIM bytes) as the caller's int32 row: the images of the query's n1
+// SSEs, -1 behind them, all -1 for an unused match slot
+void expand_map(const int8_t *in, int n1, bool used, int32_t *out)
+{
+    for (int i = 0; i < SAT_MAXDIM; i++) out[i] = (used && i < n1) ? in[i] : -1;
+}
+
+// The head of both match searches: a context, max_matches in range, then the SatMatchArgs fields they share (the record
+// pass; maps of SAT_MAXDIM bytes).  The caller adds the row length and the outputs once its buffers stand.  (The
+// descriptor table is taken before the caller's refresh_descriptors: only sat_set_queries reallocates it.)
+int match_args(const sat_ctx *ctx, int max_matches, SatMatchArgs &mx)
+{
+    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
+    if (max_matches < 1 || max_matches > SAT_MAX_MATCHES)
+        return sat_fail(SAT_EINVAL, "max_matches must be 1..%d (got %d)", SAT_MAX_MATCHES, max_matches);
+    mx = SatMatchArgs{};
+    mx.desc_base = ctx->d_qdesc.get();
+    mx.max_matches = max_matches;
+    mx.map_pitch = SAT_MAXDIM;
+    return SAT_OK;
+}
+
 }  // namespace
 
 // sat_ctx.hpp: queue a pair search (both passes) on the context's stream
@@ -865,74 +913,32 @@ int sat_pairs_launch(sat_ctx *ctx, int lorder, int maxstart, bool maps, const in
     if (npairs == 0) return SAT_OK;
 
     const int split = pair_split(ctx, maxstart, npairs);
-    const int per_pair = (maxstart + split - 1) / split;
-
-    // groups by (query class, entry order bucket): the launch's LDS is sized for the class and the bucket's largest entry
-    std::vector<std::vector<int>> members(4 * kNumBuckets);
-    std::vector<int> n2max(4 * kNumBuckets, 0);
-    for (int p = 0; p < npairs; p++) {
-        const int n2 = ctx->h_orders[(size_t)entry[p]];
-        const int g = ctx->queries[(size_t)query[p]].cls * kNumBuckets + order_bucket(n2);
-        members[(size_t)g].push_back(p);
-        if (n2 > n2max[(size_t)g]) n2max[(size_t)g] = n2;
-    }
     std::vector<SatPairItem> &items = ctx->h_pitems;
     HIP_TRY(hipStreamSynchronize(ctx->stream));      // the previous pair search's upload has read the table
     items.clear();
-    items.reserve((size_t)npairs * (size_t)per_pair + (maps ? (size_t)npairs : 0));
-    std::vector<size_t> goff{ 0 }, moff;
-    std::vector<int> gcls, gn2;
-    for (int g = 0; g < 4 * kNumBuckets; g++) {
-        if (members[(size_t)g].empty()) continue;
-        for (int p : members[(size_t)g])
-            for (int r0 = 0; r0 < maxstart; r0 += split) {
-                SatPairItem it{};
-                it.pair = p;
-                it.desc = ctx->queries[(size_t)query[p]].desc;
-                it.entry = entry[p];
-                it.r0 = r0;
-                it.r1 = maxstart - r0 < split ? maxstart : r0 + split;
-                items.push_back(it);
-            }
-        goff.push_back(items.size());
-        gcls.push_back(g / kNumBuckets);
-        gn2.push_back(n2max[(size_t)g]);
-    }
-    const size_t n_score = items.size();
-    if (maps) {
-        // map pass: one item per pair, the same groups; the restart is filled in on the device (pair_winners)
-        moff.push_back(n_score);
-        for (int g = 0; g < 4 * kNumBuckets; g++) {
-            if (members[(size_t)g].empty()) continue;
-            for (int p : members[(size_t)g]) {
-                SatPairItem it{};
-                it.pair = p;
-                it.desc = ctx->queries[(size_t)query[p]].desc;
-                it.entry = entry[p];
-                items.push_back(it);
-            }
-            moff.push_back(items.size());
-        }
-    }
+    items.reserve(pair_item_count(npairs, maxstart, split, maps));
+    const PairGroups grp = build_pair_items(ctx, query, entry, 0, npairs, maxstart, split, maps, items, nullptr);
     if ((rc = ctx->d_pitems.grow_after(ctx->stream, items.size())) != SAT_OK) return rc;
     if ((rc = ctx->d_pkeys.grow_after(ctx->stream, (size_t)npairs)) != SAT_OK) return rc;
     if (maps && (rc = ctx->d_pmaps.grow_after(ctx->stream, (size_t)npairs * SAT_MAXDIM)) != SAT_OK) return rc;
     HIP_TRY(hipMemcpyAsync(ctx->d_pitems.get(), items.data(), items.size() * sizeof(SatPairItem), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemsetAsync(ctx->d_pkeys.get(), 0, (size_t)npairs * sizeof(unsigned long long), ctx->stream));
     std::string info;
-    rc = launch_pair_pass(ctx, lorder, false, split, ctx->d_pitems.get(), goff, gcls, gn2, info);
+    rc = launch_pair_pass(ctx, lorder, false, split, ctx->d_pitems.get(), grp, info);
     if (rc != SAT_OK) return rc;
     char head[96];
     snprintf(head, sizeof head, "score pass (%d restarts, %d per item): ", maxstart, split);
     ctx->last_launch_info = head + info;
     if (maps) {
+        // the map items name the winning restart of their pair
+        const size_t n_score = grp.moff[0];
         const int n_map = (int)(items.size() - n_score);
         HIP_TRY(hipMemsetAsync(ctx->d_pmaps.get(), 0xFF, (size_t)npairs * SAT_MAXDIM, ctx->stream));
         hipLaunchKernelGGL(pair_winners, dim3((unsigned)((n_map + 255) / 256)), dim3(256), 0, ctx->stream,
                            ctx->d_pitems.get() + n_score, n_map, ctx->d_pkeys.get());
         HIP_TRY(hipGetLastError());
         info.clear();
-        rc = launch_pair_pass(ctx, lorder, true, 1, ctx->d_pitems.get(), moff, gcls, gn2, info);
+        rc = launch_pair_pass(ctx, lorder, true, 1, ctx->d_pitems.get(), grp, info);
         if (rc != SAT_OK) return rc;
         ctx->last_launch_info += " | map pass: " + info;
     }
@@ -960,11 +966,8 @@ int sat_pairs_collect(sat_ctx *ctx, int npairs, int32_t *scores, int32_t *ssemap
         std::vector<int8_t> mp((size_t)npairs * SAT_MAXDIM);
         HIP_TRY(hipMemcpy(mp.data(), ctx->d_pmaps.get(), mp.size(), hipMemcpyDeviceToHost));
         ctx->d2h_bytes += mp.size();
-        for (int p = 0; p < npairs; p++) {
-            const int n1 = ctx->queries[(size_t)query[p]].n1;
-            for (int i = 0; i < SAT_MAXDIM; i++)
-                ssemaps[(size_t)p * SAT_MAXDIM + i] = i < n1 ? mp[(size_t)p * SAT_MAXDIM + i] : -1;
-        }
+        for (size_t p = 0; p < (size_t)npairs; p++)
+            expand_map(mp.data() + p * SAT_MAXDIM, ctx->queries[(size_t)query[p]].n1, true, ssemaps + p * SAT_MAXDIM);
     }
     return SAT_OK;
 }
@@ -975,11 +978,10 @@ int sat_pairs_collect(sat_ctx *ctx, int npairs, int32_t *scores, int32_t *ssemap
 int sat_pair_matches_launch(sat_ctx *ctx, int lorder, int maxstart, int max_matches, bool maps, const int32_t *query,
                             const int32_t *entry, int npairs)
 {
-    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
-    if (max_matches < 1 || max_matches > SAT_MAX_MATCHES)
-        return sat_fail(SAT_EINVAL, "max_matches must be 1..%d (got %d)", SAT_MAX_MATCHES, max_matches);
-    int rc = check_ready(ctx, true, maxstart);
+    PairMatchPass pm{};
+    int rc = match_args(ctx, max_matches, pm.mx);
     if (rc != SAT_OK) return rc;
+    if ((rc = check_ready(ctx, true, maxstart)) != SAT_OK) return rc;
     if ((rc = check_pairs(ctx, query, entry, npairs)) != SAT_OK) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     if ((rc = refresh_descriptors(ctx, false, ctx->stream)) != SAT_OK) return rc;
@@ -991,65 +993,22 @@ int sat_pair_matches_launch(sat_ctx *ctx, int lorder, int maxstart, int max_matc
     // a pair's slab: the scores and the set words of its restarts, as wide as the widest set of the list
     int n2_all = 0;
     for (int p = 0; p < npairs; p++) n2_all = std::max(n2_all, ctx->h_orders[(size_t)entry[p]]);
-    const size_t slab_words = (size_t)(1 + (n2_all <= 32 ? 1 : (n2_all <= 64 ? 2 : 4))) * (size_t)maxstart;
+    const size_t slab_words = (size_t)(1 + satk::set_words(n2_all)) * (size_t)maxstart;
     const size_t budget_words = ((size_t)1 << 30) / 4;
     const int chunk = (int)std::min<size_t>((size_t)npairs, std::max<size_t>(1, budget_words / slab_words));
 
-    // items of every launch: its record items by (query class, entry order bucket), then one map item per pair in the
-    // same groups
-    struct Chunk { int p0, n; std::vector<size_t> goff, moff; std::vector<int> gcls, gn2; };
+    // the items of every launch of `chunk` pairs, one behind the other in the table
+    struct Chunk { int p0, n; PairGroups grp; };
     std::vector<Chunk> chunks;
     std::vector<SatPairItem> &items = ctx->h_pitems;
     std::vector<uint8_t> &setw = ctx->h_psetw;
     HIP_TRY(hipStreamSynchronize(ctx->stream));      // the previous pair search's uploads have read the tables
     items.clear();
+    items.reserve(pair_item_count(npairs, maxstart, split, maps));
     setw.assign((size_t)npairs, 0);
     for (int p0 = 0; p0 < npairs; p0 += chunk) {
-        Chunk ch;
-        ch.p0 = p0;
-        ch.n = std::min(chunk, npairs - p0);
-        std::vector<std::vector<int>> members(4 * kNumBuckets);
-        std::vector<int> n2max(4 * kNumBuckets, 0);
-        for (int p = p0; p < p0 + ch.n; p++) {
-            const int n2 = ctx->h_orders[(size_t)entry[p]];
-            const int g = ctx->queries[(size_t)query[p]].cls * kNumBuckets + order_bucket(n2);
-            members[(size_t)g].push_back(p);
-            n2max[(size_t)g] = std::max(n2max[(size_t)g], n2);
-        }
-        auto item_of = [&](int p) {
-            SatPairItem it{};
-            it.pair = p;
-            it.desc = ctx->queries[(size_t)query[p]].desc;
-            it.entry = entry[p];
-            it.slab = p - p0;
-            return it;
-        };
-        ch.goff.push_back(items.size());
-        for (int g = 0; g < 4 * kNumBuckets; g++) {
-            if (members[(size_t)g].empty()) continue;
-            const int n2 = n2max[(size_t)g];
-            for (int p : members[(size_t)g]) {
-                setw[(size_t)p] = (uint8_t)(n2 <= 32 ? 1 : (n2 <= 64 ? 2 : 4));      // the M2W of the group's launch
-                for (int r0 = 0; r0 < maxstart; r0 += split) {
-                    SatPairItem it = item_of(p);
-                    it.r0 = r0;
-                    it.r1 = maxstart - r0 < split ? maxstart : r0 + split;
-                    items.push_back(it);
-                }
-            }
-            ch.goff.push_back(items.size());
-            ch.gcls.push_back(g / kNumBuckets);
-            ch.gn2.push_back(n2);
-        }
-        if (maps) {
-            ch.moff.push_back(items.size());
-            for (int g = 0; g < 4 * kNumBuckets; g++) {
-                if (members[(size_t)g].empty()) continue;
-                for (int p : members[(size_t)g]) items.push_back(item_of(p));
-                ch.moff.push_back(items.size());
-            }
-        }
-        chunks.push_back(std::move(ch));
+        const int n = std::min(chunk, npairs - p0);
+        chunks.push_back({ p0, n, build_pair_items(ctx, query, entry, p0, n, maxstart, split, maps, items, setw.data()) });
     }
     // outputs: counts [pairs], scores [pairs][M], restarts [pairs][M] in one array (one copy to the host), the maps
     if ((rc = ctx->d_pitems.grow_after(ctx->stream, items.size())) != SAT_OK ||
@@ -1064,12 +1023,8 @@ int sat_pair_matches_launch(sat_ctx *ctx, int lorder, int maxstart, int max_matc
     HIP_TRY(hipMemsetAsync(ctx->d_pkeys.get(), 0, (size_t)npairs * sizeof(unsigned long long), ctx->stream));
     if (maps) HIP_TRY(hipMemsetAsync(ctx->d_pmaps.get(), 0xFF, (size_t)npairs * M * SAT_MAXDIM, ctx->stream));
 
-    PairMatchPass pm{};
     pm.maxstart = maxstart;
-    pm.mx.desc_base = ctx->d_qdesc.get();
     pm.mx.n_entries = 0;                                 // (rows are pairs)
-    pm.mx.max_matches = max_matches;
-    pm.mx.map_pitch = SAT_MAXDIM;
     pm.mx.rec_slab_words = (uint32_t)slab_words;
     pm.mx.counts = ctx->d_pmout.get();
     pm.mx.scores = pm.mx.counts + npairs;
@@ -1079,13 +1034,13 @@ int sat_pair_matches_launch(sat_ctx *ctx, int lorder, int maxstart, int max_matc
     for (const Chunk &ch : chunks) {
         // (the map pass of the launch before may have replaced the scratch with a larger one)
         pm.mx.rec_slabs = ctx->d_bmap_slabs.get();
-        if ((rc = launch_pair_pass(ctx, lorder, false, split, ctx->d_pitems.get(), ch.goff, ch.gcls, ch.gn2, rec_info, &pm)) != SAT_OK)
+        if ((rc = launch_pair_pass(ctx, lorder, false, split, ctx->d_pitems.get(), ch.grp, rec_info, &pm)) != SAT_OK)
             return rc;
         hipLaunchKernelGGL(pair_match_select, dim3((unsigned)ch.n), dim3(256), 0, ctx->stream, ch.p0, maxstart, max_matches,
                            (const uint32_t *)ctx->d_bmap_slabs.get(), (uint32_t)slab_words, (const uint8_t *)ctx->d_psetw.get(),
                            (const unsigned long long *)ctx->d_pkeys.get(), pm.mx.counts, pm.mx.scores, pm.mx.restarts);
         HIP_TRY(hipGetLastError());
-        if (maps && (rc = launch_pair_pass(ctx, lorder, true, 1, ctx->d_pitems.get(), ch.moff, ch.gcls, ch.gn2, map_info, &pm)) != SAT_OK)
+        if (maps && (rc = launch_pair_pass(ctx, lorder, true, 1, ctx->d_pitems.get(), ch.grp, map_info, &pm)) != SAT_OK)
             return rc;
     }
     char head[128];
@@ -1118,15 +1073,10 @@ int sat_pair_matches_collect(sat_ctx *ctx, int max_matches, int npairs, int32_t 
         std::vector<int8_t> mp(P * M * SAT_MAXDIM);
         HIP_TRY(hipMemcpy(mp.data(), ctx->d_pmaps.get(), mp.size(), hipMemcpyDeviceToHost));
         ctx->d2h_bytes += mp.size();
-        for (size_t p = 0; p < P; p++) {
-            const int n1 = ctx->queries[(size_t)query[p]].n1;
-            for (size_t m = 0; m < M; m++) {
-                const bool used = (int32_t)m < counts[p];
-                const int8_t *in = mp.data() + (p * M + m) * SAT_MAXDIM;
-                int32_t *o = ssemaps + (p * M + m) * SAT_MAXDIM;
-                for (int i = 0; i < SAT_MAXDIM; i++) o[i] = (used && i < n1) ? in[i] : -1;
-            }
-        }
+        for (size_t p = 0; p < P; p++)
+            for (size_t m = 0; m < M; m++)
+                expand_map(mp.data() + (p * M + m) * SAT_MAXDIM, ctx->queries[(size_t)query[p]].n1, (int32_t)m < counts[p],
+                           ssemaps + (p * M + m) * SAT_MAXDIM);
     }
     return SAT_OK;
 }
@@ -1758,11 +1708,10 @@ int sat_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart,
 
 int sat_matches_launch(sat_ctx *ctx, int lorder, int maxstart, int max_matches, bool maps)
 {
-    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
-    if (max_matches < 1 || max_matches > SAT_MAX_MATCHES)
-        return sat_fail(SAT_EINVAL, "max_matches must be 1..%d (got %d)", SAT_MAX_MATCHES, max_matches);
-    int rc = check_ready(ctx, true, maxstart);
+    SatMatchArgs mx;
+    int rc = match_args(ctx, max_matches, mx);
     if (rc != SAT_OK) return rc;
+    if ((rc = check_ready(ctx, true, maxstart)) != SAT_OK) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     // counts: one per row, scores / restarts: M per row, maps: M x SAT_MAXDIM bytes per row
     const size_t rows = ctx->queries.size() * (size_t)ctx->n_entries, slots = rows * (size_t)max_matches;
@@ -1770,12 +1719,7 @@ int sat_matches_launch(sat_ctx *ctx, int lorder, int maxstart, int max_matches, 
         (rc = ctx->d_mrestarts.grow_after(ctx->stream, slots)) != SAT_OK ||
         (rc = ctx->d_mmaps.grow_after(ctx->stream, maps ? slots * SAT_MAXDIM : 0)) != SAT_OK)
         return rc;
-    SatMatchArgs mx{};
-    mx.desc_base = ctx->d_qdesc.get();
     mx.n_entries = ctx->n_entries;
-    mx.max_matches = max_matches;
-    mx.replay = 0;
-    mx.map_pitch = SAT_MAXDIM;
     mx.counts = ctx->d_mcounts.get();
     mx.scores = ctx->d_mscores.get();
     mx.restarts = ctx->d_mrestarts.get();
@@ -1817,11 +1761,7 @@ int sat_matches_collect(sat_ctx *ctx, int max_matches, int32_t *counts, int32_t 
             for (size_t m = 0; m < M; m++) {
                 scores[dst * M + m] = sc[src * M + m];
                 restarts[dst * M + m] = rs[src * M + m];
-                if (!ssemaps) continue;
-                int32_t *out = ssemaps + (dst * M + m) * SAT_MAXDIM;
-                const int8_t *in = mp.data() + (src * M + m) * SAT_MAXDIM;
-                const bool used = (int)m < c[src];
-                for (int i = 0; i < SAT_MAXDIM; i++) out[i] = (used && i < n1) ? in[i] : -1;
+                if (ssemaps) expand_map(mp.data() + (src * M + m) * SAT_MAXDIM, n1, (int)m < c[src], ssemaps + (dst * M + m) * SAT_MAXDIM);
             }
         }
     }

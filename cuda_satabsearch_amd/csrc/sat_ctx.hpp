@@ -177,7 +177,8 @@ struct sat_ctx {
 
     // bytes copied device -> host by this context's result calls (sat_stat_d2h_bytes)
     unsigned long long d2h_bytes = 0;
-    // kernel instantiations and launch geometry of the last search (sat_last_launch_info)
+    // kernel instantiations and launch geometry of the last search (sat_last_launch_info; one launch_info() of
+    // sat_capi.hip per launch, from the SaKernel that was launched)
     std::string last_launch_info;
 };
 

@@ -4,7 +4,7 @@
 // an independent restart chain (lane = restart, as the reference maps threadIdx to restarts,
 // K.cu:1012-1015), 100 Metropolis steps each.  A workgroup is one slot, or several side by side
 // (own threads, own LDS carve, shared barriers only) where that packs more entries into the CU's
-// 128 LDS granules of 1280 bytes - the host decides per launch (sat_capi.hip pick_epw).  Written from scratch for
+// 128 LDS granules of 1280 bytes - the host decides per launch (sat_capi.hip: prepare_sa, pick_epw).  Written from scratch for
 // 64-wide wavefronts and the 160 KB LDS; what it computes follows the reference
 // kernel body K.cu:924-1233 (K.cu = nvcc_src_current/cudaSaTabsearch_kernel.cu).
 //
@@ -415,6 +415,9 @@ template <> struct DbRow<SAT_CELLS_FULL8> { const uint2 *cells; };
 template <> struct DbRow<SAT_CELLS_FULL5> { const float *dist; const uint8_t *code; };
 template <> struct DbRow<SAT_CELLS_TRI5> { const float *dist; const uint8_t *code; int j; };
 __host__ __device__ inline int cell_layout(int n2max) { return n2max <= 32 ? SAT_CELLS_FULL8 : (n2max <= 48 ? SAT_CELLS_FULL5 : SAT_CELLS_TRI5); }
+// 32-bit words of a db-side bit set (the kernels' M2W) for entries of up to n2 SSEs: the launch's template argument, the
+// record slabs' row count and the selection kernel's set width all come from here
+__host__ __device__ inline int set_words(int n2) { return n2 <= 32 ? 1 : (n2 <= 64 ? 2 : 4); }
 // cell (j, l) of the lower triangle: row max(j, l), column min(j, l)
 __device__ __forceinline__ int tri_index(int j, int l)
 {
@@ -613,7 +616,7 @@ __host__ __device__ inline size_t lds_bytes(int n1, int n1p, int n2, int chains,
                                              bool compact)
 {
     (void)lsoln;                                              // the best maps live in global memory
-    return lds_layout(n2 <= 32 ? 1 : (n2 <= 64 ? 2 : 4), cell_layout(n2), n2, map_words((n1 + 3) >> 2), n1p, chains, threads, q_in_lds, compact).total;
+    return lds_layout(set_words(n2), cell_layout(n2), n2, map_words((n1 + 3) >> 2), n1p, chains, threads, q_in_lds, compact).total;
 }
 
 }  // namespace satk
