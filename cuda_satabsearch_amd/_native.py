@@ -28,7 +28,12 @@ ABI_SYMBOLS = (
     "sat_search_pairs", "sat_search_refine", "sat_multi_search_refine",
     "sat_hits_cutoff", "sat_multi_search_cutoff", "sat_multi_hits_cutoff",
     "sat_search_pairs_matches", "sat_multi_search_pairs_matches",
+    "sat_score_histogram", "sat_stats_fit", "sat_stats_set",
+    "sat_multi_score_histogram", "sat_multi_stats_set", "sat_multi_search_fit",
 )
+
+STAT_BINS = 4096
+STAT_BINS_PER_UNIT = 256
 
 
 class SatError(RuntimeError):
@@ -39,6 +44,12 @@ class Hit(C.Structure):
     """struct sat_hit of include/satabsearch.h"""
     _fields_ = [("entry", C.c_int32), ("score", C.c_int32), ("norm2", C.c_double), ("zscore", C.c_double),
                 ("pvalue", C.c_double)]
+
+
+class Fit(C.Structure):
+    """struct sat_fit of include/satabsearch.h"""
+    _fields_ = [("a", C.c_double), ("b", C.c_double), ("rows", C.c_int32), ("censored", C.c_int32),
+                ("below", C.c_int32), ("fitted", C.c_int32)]
 
 
 class StructSetC(C.Structure):
@@ -130,6 +141,14 @@ def device_lib():
         lib.sat_multi_hits_cutoff.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         lib.sat_multi_stat_d2h_bytes.argtypes = [C.c_void_p]
         lib.sat_multi_stat_d2h_bytes.restype = C.c_uint64
+        lib.sat_score_histogram.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.sat_stats_fit.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
+        lib.sat_stats_set.argtypes = [C.c_void_p, C.c_void_p]
+        lib.sat_multi_score_histogram.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.sat_multi_stats_set.argtypes = [C.c_void_p, C.c_void_p]
+        lib.sat_multi_search_fit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p,
+                                             C.POINTER(C.c_double)]
+        lib.sat_debug_set_scores.argtypes = [C.c_void_p, C.c_void_p]          # include/satabsearch_debug.h
         lib.sat_device_scores.argtypes = [C.c_void_p]
         lib.sat_device_scores.restype = C.c_void_p
         lib.sat_device_ssemaps.argtypes = [C.c_void_p]
@@ -168,6 +187,14 @@ def host_lib():
         lib.sat_z_gumbel_trunc.restype = C.c_double
         lib.sat_pv_gumbel.argtypes = [C.c_double]
         lib.sat_pv_gumbel.restype = C.c_double
+        lib.sat_stat_bin.argtypes = [C.c_int, C.c_int, C.c_int]
+        lib.sat_stat_bin.restype = C.c_int
+        lib.sat_stat_histogram.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.sat_stat_histogram.restype = None
+        lib.sat_gumbel_fit_binned.argtypes = [C.c_void_p, C.c_double, C.POINTER(Fit)]
+        lib.sat_gumbel_fit_binned.restype = C.c_int
+        lib.sat_gumbel_fit_table.argtypes = [C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+        lib.sat_gumbel_fit_table.restype = None
         lib.sat_entry_cost.argtypes = [C.c_int]
         lib.sat_entry_cost.restype = C.c_double
         lib.sat_shard_cuts.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]

@@ -51,7 +51,7 @@ def kernel_source_hash():
 def build_host(force=False):
     out = os.path.join(PKG, "libsathost.so")
     srcs = [os.path.join(HOST, f) for f in ("sat_parse.c", "sat_gumbel.c", "sat_shard.c")]
-    deps = srcs + [os.path.join(HOST, f) for f in ("sat_parse.h", "sat_gumbel.h", "sat_shard.h")]
+    deps = srcs + [os.path.join(HOST, f) for f in ("sat_parse.h", "sat_gumbel.h", "sat_stats.h", "sat_shard.h")]
     if force or _stale(out, deps):
         _run([CC, "-O2", "-fPIC", "-shared", "-Wall", "-Wextra", "-I", HOST, "-o", out] + srcs + ["-lm", "-lpthread"])
     return out
@@ -63,7 +63,7 @@ def _host_objects(force=False):
     host_c = [os.path.join(HOST, "sat_gumbel.c"), os.path.join(HOST, "sat_shard.c")]
     host_o = [os.path.join(PKG, "sat_gumbel.o"), os.path.join(PKG, "sat_shard.o")]
     for c, o in zip(host_c, host_o):
-        if force or _stale(o, [c, os.path.join(HOST, "sat_gumbel.h"), os.path.join(HOST, "sat_shard.h")]):
+        if force or _stale(o, [c, os.path.join(HOST, "sat_gumbel.h"), os.path.join(HOST, "sat_stats.h"), os.path.join(HOST, "sat_shard.h")]):
             _run([CC, "-O2", "-fPIC", "-ffp-contract=off", "-Wall", "-Wextra", "-I", HOST, "-c", "-o", o, c])
     return host_o
 
@@ -74,6 +74,7 @@ def build_device(force=False):
     host_o = _host_objects(force)
     deps = srcs + host_o + [os.path.join(CSRC, "sat_sa_kernel.hpp"), os.path.join(CSRC, "sat_sa_body.inc"),
                             os.path.join(CSRC, "sat_ctx.hpp"), os.path.join(CSRC, "sat_cutoff.hpp"),
+                            os.path.join(HOST, "sat_gumbel.h"), os.path.join(HOST, "sat_stats.h"),
                             os.path.join(INC, "satabsearch.h")]
     if force or _stale(out, deps):
         # -Wl,: hipcc would compile a bare .o as HIP source.  librccl is NOT linked: sat_multi.hip loads it on demand
@@ -115,7 +116,7 @@ def build_test_native(force=False):
     out3 = os.path.join(tdir, "libsat_selfcheck.so")
     dsrcs = [os.path.join(CSRC, f) for f in ("sat_capi.hip", "sat_topk.hip", "sat_multi.hip")]
     ddeps = dsrcs + [os.path.join(CSRC, "sat_sa_kernel.hpp"), os.path.join(CSRC, "sat_sa_body.inc"), os.path.join(CSRC, "sat_ctx.hpp"),
-                     os.path.join(CSRC, "sat_cutoff.hpp"),
+                     os.path.join(CSRC, "sat_cutoff.hpp"), os.path.join(HOST, "sat_gumbel.h"), os.path.join(HOST, "sat_stats.h"),
                      os.path.join(CSRC, "diag", "sat_diag.hpp"), os.path.join(INC, "satabsearch.h")]
     if force or _stale(out3, ddeps):
         _run([HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared", "-DSAT_DIAG",

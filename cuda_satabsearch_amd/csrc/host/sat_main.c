@@ -27,7 +27,10 @@
  * -b (keep a binary image `dbfile.satbin` beside the database and load it instead of
  * parsing when it is newer than the ASCII file), -p P (print only the rows whose p-value is <= P, selected on the
  * GPU and ranked as -k; with -k K at most K of them per query), -M M (matches 2..M of the rows that -k / -p / -R print,
- * in -m's format: a pair-match search of those rows only, after the search that chose them).
+ * in -m's format: a pair-match search of those rows only, after the search that chose them), -F censor (fit each
+ * query's Gumbel parameters to its own scores and print z and p from the fit: a fourth header line "# GUMBEL ...", see
+ * sat_gumbel.h; the listing fits on the host, -k / -p on the GPUs from a histogram, so that still only the printed rows
+ * leave them).
  */
 #include <math.h>
 #include <stdarg.h>
@@ -60,11 +63,12 @@ static double now_ms(void)
 #pragma weak sat_multi_search_cutoff
 #pragma weak sat_multi_hits_cutoff
 #pragma weak sat_multi_search_pairs_matches
+#pragma weak sat_multi_search_fit
 
 static void usage(const char *prog)
 {
     fprintf(stderr, "Usage: %s [-c] [-q dbfile] [-r restarts] [-g gpus] [-G gpu,gpu,...] [-s seed] [-k K] [-p P]\n"
-                    "       [-m M] [-M M] [-R restarts [-C C]] [-b]\n", prog);
+                    "       [-m M] [-M M] [-R restarts [-C C]] [-F censor] [-b]\n", prog);
     fprintf(stderr, "  -c : run on host CPU not GPU card\n");
     fprintf(stderr, "  -q dbfile : database is read from dbfile, list of query\n"
                     "              ids is read from stdin\n");
@@ -82,6 +86,8 @@ static void usage(const char *prog)
     fprintf(stderr, "  -R restarts : re-score each query's C best entries (by -r) with this many restarts;\n"
                     "                rows as -k, with the new scores (GPU mode, needs -k)\n");
     fprintf(stderr, "  -C C : candidates per query re-scored by -R. Default K\n");
+    fprintf(stderr, "  -F censor : fit each query's Gumbel parameters to its own scores, the top `censor` (0..0.5) of them\n"
+                    "              right-censored; z and p come from the fit (header line # GUMBEL)\n");
     fprintf(stderr, "  -b : cache the parsed database as dbfile.satbin\n");
     exit(1);
 }
@@ -120,6 +126,16 @@ typedef struct { unsigned char len; char text[47]; } zp_text;         /* " %g  %
 static zp_text zp_cache[2][ZP_SLOTS];      /* [wide gap]["z p" of the integer] */
 static g_text *norm2_cache = NULL;         /* [score - lo][n1 + n2], allocated on first use */
 
+/* -F: the statistics of the query whose block is being printed - z and p of every histogram bin from the query's
+ * fitted (a, b) (sat_gumbel_fit_table, as the device's tables), and the cached " z p" text per bin.  They are a
+ * query's own: begin_query_stats sets them up afresh at each header. */
+typedef struct {
+    double z[SAT_STAT_BINS], p[SAT_STAT_BINS];
+    zp_text text[2][SAT_STAT_BINS];        /* [wide gap][bin] */
+} fit_stats;
+static fit_stats *fit_store = NULL;        /* allocated on first use */
+static fit_stats *fit_cur = NULL;          /* NULL: the built-in constants */
+
 static inline void out_int(int v)
 {
     char tmp[12];
@@ -131,8 +147,10 @@ static inline void out_int(int v)
     while (n) out_buf[out_len++] = tmp[--n];
 }
 
+/* c: where the row's " z p" text is cached (a function of the truncated norm2 score or, with a fit, of the bin), or
+ * NULL: formatted from zscore and pvalue */
 static void out_row(const char *name, int score, double norm2score, double zscore, double pvalue, int sum, int wide_gap,
-                    int stats_from_host)
+                    zp_text *c)
 {
     /* "%-8s " */
     char nm[9];
@@ -162,10 +180,8 @@ static void out_row(const char *name, int score, double norm2score, double zscor
         char t[32];
         out_bytes(t, (size_t)snprintf(t, sizeof t, "%g", norm2score));
     }
-    /* " z p\n": a function of the truncated norm2 score */
-    const int x = (int)norm2score;
-    if (stats_from_host && x >= -256 && x < 256) {
-        zp_text *c = &zp_cache[wide_gap ? 1 : 0][x + 256];
+    /* " z p\n" */
+    if (c) {
         if (!c->len) {
             const int n = snprintf(c->text, sizeof c->text, wide_gap ? " %g  %g\n" : " %g %g\n", zscore, pvalue);
             if (n > 0 && (size_t)n < sizeof c->text) c->len = (unsigned char)n;
@@ -214,12 +230,15 @@ static void *checked(void *p)
 typedef struct {
     int use_gpu, maxstart, want_gpus, bincache, topk, nmatch, refine, ncand, cutoff;
     int rowmatch;                     /* -M: matches of each printed row */
+    int fit;                          /* -F: statistics fitted to each query's own scores */
+    double censor;                    /* -F: the right-censored fraction of the rows */
     double pmax;                      /* -p: the largest p-value printed */
     unsigned long long seed;
     const char *qfile;                /* -q: the database; stdin lists the query SIDs */
     int dev_list[64], ndev_list;
     /* what the run prints, derived once the options are checked */
     int ranked;                       /* -k / -p / -R: each query's ranked rows; else the listing in class order */
+    int csr;                          /* -p, and -k with -F: a row count per query (pcounts) instead of K rows each */
     int nm;                           /* slots per entry: M of -m, else 1 */
 } options;
 
@@ -253,20 +272,31 @@ static void print_entry(const input *in, int e, int n1, const sat_hit *h, const 
         const size_t slot = r * (size_t)s->nm + (size_t)m;
         const int32_t *map = hmap;
         if (m == 0 && h) {
-            out_row(name, h->score, h->norm2, h->zscore, h->pvalue, n1 + n2, wide_gap, 0);
+            out_row(name, h->score, h->norm2, h->zscore, h->pvalue, n1 + n2, wide_gap, NULL);
         } else {
             const int score = s->scores[slot];
             const double norm2score = sat_norm2(score, n1, n2);
-            /* z and p only when their cached text is missing */
             const int x = (int)norm2score;
             double zscore = 0.0, pvalue = 0.0;
-            if (!(x >= -256 && x < 256 && zp_cache[wide_gap ? 1 : 0][x + 256].len)) {
-                zscore = sat_z_gumbel_trunc(norm2score);
-                pvalue = sat_pv_gumbel(zscore);
+            zp_text *c = NULL;
+            if (fit_cur) {
+                /* the query's fitted table at the row's bin, as the device indexes it */
+                const int bin = score < 0 ? 0 : sat_stat_bin_of(score, n1 + n2);
+                zscore = fit_cur->z[bin];
+                pvalue = fit_cur->p[bin];
+                c = &fit_cur->text[wide_gap ? 1 : 0][bin];
+            } else {
+                /* z and p only when their cached text is missing */
+                if (x >= -256 && x < 256)
+                    c = &zp_cache[wide_gap ? 1 : 0][x + 256];
+                if (!(c && c->len)) {
+                    zscore = sat_z_gumbel_trunc(norm2score);
+                    pvalue = sat_pv_gumbel(zscore);
+                }
             }
             if (m)
                 snprintf(mname, sizeof mname, "%s:%d", name, m + 1);
-            out_row(m ? mname : name, score, norm2score, zscore, pvalue, n1 + n2, wide_gap, 1);
+            out_row(m ? mname : name, score, norm2score, zscore, pvalue, n1 + n2, wide_gap, c);
             map = s->maps ? s->maps + slot * SAT_MAXDIM : NULL;
         }
         if (map)
@@ -276,8 +306,22 @@ static void print_entry(const input *in, int e, int n1, const sat_hit *h, const 
     }
 }
 
-/* The three '#' lines that open a block of query qi */
-static void print_header(const input *in, int qi)
+/* -F: the rows that follow are query `f`'s - its tables and an empty text cache; no fit (or NULL): the built-ins */
+static void begin_query_stats(const sat_fit *f)
+{
+    fit_cur = NULL;
+    if (!f || !f->fitted)
+        return;
+    if (!fit_store)
+        fit_store = checked(malloc(sizeof *fit_store));
+    fit_cur = fit_store;
+    sat_gumbel_fit_table(f->a, f->b, fit_cur->z, fit_cur->p);
+    memset(fit_cur->text, 0, sizeof fit_cur->text);
+}
+
+/* The three '#' lines that open a block of query qi; with -F (f: the query's fit) a fourth, and the statistics of the
+ * rows that follow are f's */
+static void print_header(const input *in, int qi, const sat_fit *f)
 {
     char line[SAT_MAX_LINE_LEN + 64];
     int n = snprintf(line, sizeof line, "# cudaSaTabsearch LTYPE = %c LORDER = %c LSOLN = %c\n",
@@ -287,6 +331,18 @@ static void print_header(const input *in, int qi)
     out_bytes(line, (size_t)n);
     n = snprintf(line, sizeof line, "# DBFILE = %-80s\n", in->dbfile);
     out_bytes(line, (size_t)n);
+    begin_query_stats(f);
+    if (!f)
+        return;
+    if (f->fitted) {
+        n = snprintf(line, sizeof line, "# GUMBEL a = %.17g b = %.17g rows = %d censored = %d below = %d\n", f->a, f->b,
+                     f->rows, f->censored, f->below);
+    } else {
+        n = snprintf(line, sizeof line, "# GUMBEL not fitted\n");
+        fprintf(stderr, "WARNING: no Gumbel fit for query %s: its rows keep the built-in statistics\n",
+                sat_set_name(in->qsrc, in->qindex[qi]));
+    }
+    out_bytes(line, (size_t)n);
 }
 
 /* The options, then the refusals in a fixed order (the tests pin it), all before the banner and any device call */
@@ -294,7 +350,7 @@ static void parse_options(int argc, char *argv[], options *o)
 {
     *o = (options){ .use_gpu = 1, .maxstart = 128, .want_gpus = 1, .seed = SAT_DEFAULT_SEED };
     int c;
-    while ((c = getopt(argc, argv, "cq:r:g:G:s:bk:p:m:M:R:C:")) != -1) {
+    while ((c = getopt(argc, argv, "cq:r:g:G:s:bk:p:m:M:R:C:F:")) != -1) {
         char *end = NULL;
         long v;
         switch (c) {
@@ -317,6 +373,15 @@ static void parse_options(int argc, char *argv[], options *o)
                 usage(argv[0]);
             }
             o->cutoff = 1;
+            break;
+        case 'F':
+            /* the whole argument, a number in [0, 0.5] */
+            o->censor = strtod(optarg, &end);
+            if (end == optarg || *end != '\0' || !(o->censor >= 0.0 && o->censor <= 0.5)) {
+                fprintf(stderr, "ERROR: -F needs a censored fraction in [0, 0.5] (got '%s')\n", optarg);
+                usage(argv[0]);
+            }
+            o->fit = 1;
             break;
         case 'm':
             /* 1 .. SAT_MAX_MATCHES, digits only: anything else (0, a sign, text) is a usage error */
@@ -367,6 +432,11 @@ static void parse_options(int argc, char *argv[], options *o)
     if (o->rowmatch && !o->ranked) die("ERROR: -M needs -k K, -p P or -R restarts -k K\n");
     if (o->rowmatch && !sat_multi_search_pairs_matches)
         die("ERROR: this library has no sat_multi_search_pairs_matches\n");
+    if (o->fit && o->refine) die("ERROR: -F cannot be combined with -R\n");
+    if (o->fit && o->nmatch) die("ERROR: -F cannot be combined with -m\n");
+    if (o->fit && o->ranked && (!sat_multi_search_fit || !sat_multi_hits_cutoff))
+        die("ERROR: this library has no sat_multi_search_fit\n");
+    o->csr = o->cutoff || (o->fit && o->topk > 0);
     o->nm = o->nmatch > 0 ? o->nmatch : 1;
 }
 
@@ -479,19 +549,35 @@ static void free_input(input *in)
     sat_set_free(&in->db);
 }
 
+/* -F where every score is on the host: the histogram and the fit of one query's n rows */
+static sat_fit fit_scores(const int32_t *scores, int n, int n1, const int32_t *orders, double censor)
+{
+    uint32_t *counts = checked(calloc(SAT_STAT_BINS, sizeof(uint32_t)));
+    int32_t below = 0;
+    sat_fit f;
+    sat_stat_histogram(scores, n, n1, orders, counts, &below);
+    if (sat_gumbel_fit_binned(counts, censor, &f) != 0)
+        die("ERROR: -F censor out of range\n");
+    f.below = below;
+    free(counts);
+    return f;
+}
+
 /* ---- host mode: class by class, query by query, ONE stream for everything */
 static int run_host(const options *o, const input *in)
 {
     const size_t total = (size_t)in->db.count;
     slots one = { 1, NULL, checked(malloc(sizeof(int32_t) * total)),
                   in->lsoln ? checked(malloc(sizeof(int32_t) * SAT_MAXDIM * total)) : NULL };
+    int32_t *fit_orders = o->fit ? checked(malloc(sizeof(int32_t) * (total + 1))) : NULL;
     sat_host_stream stream;
     sat_host_stream_seed(&stream, 1234);
     const int passes = in->cls_count[1] > 0 ? 2 : 1;
     for (int k = 0; k < passes; k++)
         for (int qi = 0; qi < in->num_queries; qi++) {
             const int qs = in->qindex[qi];
-            print_header(in, qi);
+            if (!o->fit)
+                print_header(in, qi, NULL);
             fprintf(stderr, "Executing simulated annealing tableaux match kernel on host for query %s...\n",
                     sat_set_name(in->qsrc, qs));
             double t1 = now_ms();
@@ -502,11 +588,19 @@ static int run_host(const options *o, const input *in)
             fprintf(stderr, "host execution time %f ms\n", ms);
             fprintf(stderr, "%f million iterations/sec\n",
                     ((double)in->cls_count[k] * ((double)o->maxstart * SAT_MAXITER) / (ms / 1000)) / 1.0e6);
+            if (o->fit) {
+                /* the block's own rows: the one stream runs class after class, so a block is fitted when it is printed */
+                for (int d = 0; d < in->cls_count[k]; d++)
+                    fit_orders[d] = in->db.order[in->cls_index[k][d]];
+                sat_fit f = fit_scores(one.scores, in->cls_count[k], in->qsrc->order[qs], fit_orders, o->censor);
+                print_header(in, qi, &f);
+            }
             for (int d = 0; d < in->cls_count[k]; d++)
                 print_entry(in, in->cls_index[k][d], in->qsrc->order[qs], NULL, NULL, &one, (size_t)d, 0);
         }
     free(one.scores);
     free(one.maps);
+    free(fit_orders);
     return 0;
 }
 
@@ -571,8 +665,8 @@ static void alloc_gpu_bufs(const options *o, const input *in, gpu_bufs *B)
         B->restarts = checked(malloc(sizeof(int32_t) * rows * nm));
     if (!o->ranked && in->cls_count[1] > 0)
         alloc_slots(&B->large, (size_t)in->cls_count[1] * in->num_queries, nm, o->nmatch, lsoln);
-    if (o->cutoff) {
-        B->hits_cap = 1024;
+    if (o->csr) {
+        B->hits_cap = o->cutoff ? 1024 : B->kk * B->batch;
         B->pcounts = checked(malloc(sizeof(int32_t) * (size_t)B->batch));
         alloc_hits(B, (size_t)B->hits_cap, lsoln);
     } else if (o->topk > 0) {
@@ -658,10 +752,25 @@ static sat_multi *open_multi(const options *o, const input *in)
 
 /* The mode's search of the batch set last.  Returns rows per query (-k, -R), the batch's rows (-p), 0 (listing, -m)
  * or a negative SAT_E* code. */
-static int search_batch(const options *o, const input *in, sat_multi *multi, gpu_bufs *B, double *ms,
+static int search_batch(const options *o, const input *in, sat_multi *multi, gpu_bufs *B, sat_fit *fits, double *ms,
                         double *ms_stage2)
 {
     const int lorder = in->lorder, lsoln = in->lsoln, maxstart = o->maxstart;
+    if (o->fit && o->ranked) {
+        /* search, histogram and fit on the GPUs (fits: the batch's), then the rows by the fitted p-values: those under
+         * -p's cutoff, or with -k alone (every p-value is <= 1) the K best */
+        int rc = sat_multi_search_fit(multi, lorder, lsoln, maxstart, o->censor, fits, ms);
+        if (rc != SAT_OK)
+            return rc;
+        const double pmax = o->cutoff ? o->pmax : 1.0;
+        rc = sat_multi_hits_cutoff(multi, pmax, o->topk, B->pcounts, B->hits_cap, B->hits, B->hit_maps);
+        if (rc > B->hits_cap) {
+            B->hits_cap = rc;
+            alloc_hits(B, (size_t)rc, lsoln);
+            rc = sat_multi_hits_cutoff(multi, pmax, o->topk, B->pcounts, B->hits_cap, B->hits, B->hit_maps);
+        }
+        return rc;
+    }
     if (o->cutoff) {
         /* every row of the batch under the cutoff; a short buffer is grown and the rows selected again */
         int rc = sat_multi_search_cutoff(multi, lorder, lsoln, maxstart, o->pmax, o->topk, B->pcounts, B->hits_cap,
@@ -701,11 +810,11 @@ static int match_ranked_rows(const options *o, const input *in, sat_multi *multi
 {
     size_t rows = 0;
     for (int b = 0; b < nqb; b++)
-        rows += (size_t)(o->cutoff ? B->pcounts[b] : rc);
+        rows += (size_t)(o->csr ? B->pcounts[b] : rc);
     alloc_rowm(B, rows ? rows : 1, o->rowmatch, in->lsoln);
     size_t r = 0;
     for (int b = 0; b < nqb; b++)
-        for (size_t n = (size_t)(o->cutoff ? B->pcounts[b] : rc); n > 0; n--, r++) {
+        for (size_t n = (size_t)(o->csr ? B->pcounts[b] : rc); n > 0; n--, r++) {
             B->pair_q[r] = b;
             B->pair_e[r] = B->hits[r].entry;
         }
@@ -717,16 +826,16 @@ static int match_ranked_rows(const options *o, const input *in, sat_multi *multi
 /* The blocks of queries q0 .. q0 + nqb - 1.  Ranked: each query's rows (-p: pcounts[b] rows of query b after those of
  * the queries before it, else rc a query).  Listing: each query's small-class rows; its large-class slots are kept
  * for the deferred block. */
-static void print_batch(const options *o, const input *in, gpu_bufs *B, int q0, int nqb, int rc)
+static void print_batch(const options *o, const input *in, gpu_bufs *B, const sat_fit *fits, int q0, int nqb, int rc)
 {
     const slots *all = &B->all, *large = &B->large;
     const size_t nm = (size_t)all->nm;
     size_t first = 0;
     for (int b = 0; b < nqb; b++) {
         const size_t row0 = (size_t)b * in->db.count;
-        print_header(in, q0 + b);
+        print_header(in, q0 + b, fits ? &fits[q0 + b] : NULL);
         if (o->ranked) {
-            const size_t nrows = (size_t)(o->cutoff ? B->pcounts[b] : rc);
+            const size_t nrows = (size_t)(o->csr ? B->pcounts[b] : rc);
             for (size_t r = first; r < first + nrows; r++)
                 print_entry(in, B->hits[r].entry, B->n1s[b], &B->hits[r],
                             B->hit_maps ? B->hit_maps + r * SAT_MAXDIM : NULL, o->rowmatch ? &B->rowm : all,
@@ -755,6 +864,9 @@ static int run_gpu(const options *o, const input *in)
     alloc_gpu_bufs(o, in, &B);
     const int total = in->db.count;
     int status = 0;
+    /* -F: every query's fit - from the GPUs with -k / -p, else made here from the listing's scores (the whole
+     * database's, both size classes: a query's two blocks carry the same line) */
+    sat_fit *fits = o->fit ? checked(calloc((size_t)in->num_queries, sizeof(sat_fit))) : NULL;
     for (int q0 = 0; q0 < in->num_queries; q0 += B.batch) {
         const int nqb = in->num_queries - q0 < B.batch ? in->num_queries - q0 : B.batch;
         for (int b = 0; b < nqb; b++) {
@@ -770,7 +882,7 @@ static int run_gpu(const options *o, const input *in)
         double ms = 0.0, ms_stage2 = 0.0;
         int rc = sat_multi_queries_set(multi, nqb, B.n1s, B.qtabs, B.qdmats, SAT_MAXDIM, B.qtypes, (uint32_t)q0);
         if (rc == SAT_OK)
-            rc = search_batch(o, in, multi, &B, &ms, &ms_stage2);
+            rc = search_batch(o, in, multi, &B, fits ? fits + q0 : NULL, &ms, &ms_stage2);
         if (rc < 0) {
             fprintf(stderr, "kernel launch failed: %s\n", sat_last_error());
             status = 1;
@@ -791,13 +903,16 @@ static int run_gpu(const options *o, const input *in)
                     o->ncand < total ? o->ncand : total, o->refine);
         fprintf(stderr, "%f million iterations/sec\n",
                 ((double)total * nqb * ((double)o->maxstart * SAT_MAXITER) / (ms / 1000)) / 1.0e6);
-        print_batch(o, in, &B, q0, nqb, rc);
+        if (o->fit && !o->ranked)
+            for (int b = 0; b < nqb; b++)
+                fits[q0 + b] = fit_scores(B.all.scores + (size_t)b * total, total, B.n1s[b], in->db.order, o->censor);
+        print_batch(o, in, &B, fits, q0, nqb, rc);
     }
     /* the listing's deferred block: every query's large-class rows, after all small-class blocks, with the reference
      * GPU path's two blanks before the p-value */
     if (!status && !o->ranked && in->cls_count[1] > 0)
         for (int qi = 0; qi < in->num_queries; qi++) {
-            print_header(in, qi);
+            print_header(in, qi, fits ? &fits[qi] : NULL);
             for (int d = 0; d < in->cls_count[1]; d++)
                 print_entry(in, in->cls_index[1][d], in->qsrc->order[in->qindex[qi]], NULL, NULL, &B.large,
                             (size_t)qi * in->cls_count[1] + d, 1);
@@ -805,6 +920,7 @@ static int run_gpu(const options *o, const input *in)
     fprintf(stderr, "copied %llu bytes of results from the GPU(s)\n", sat_multi_stat_d2h_bytes(multi));
     sat_multi_destroy(multi);
     free_gpu_bufs(&B);
+    free(fits);
     return status;
 }
 
@@ -824,5 +940,6 @@ int main(int argc, char *argv[])
     const int status = o.use_gpu ? run_gpu(&o, &in) : run_host(&o, &in);
     free_input(&in);
     free(norm2_cache);
+    free(fit_store);
     return status;
 }

@@ -117,6 +117,7 @@ void free_db(sat_ctx *ctx)
     ctx->n_entries = 0;
     ctx->min_rows = 0;
     ctx->searched_nq = 0;
+    ctx->fits.clear();
     ctx->h_orders.clear();
 }
 
@@ -631,6 +632,7 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
         }
     ctx->searched_nq = ctx->queries.size();
     ctx->searched_lsoln = lsoln != 0;
+    ctx->fits.clear();                                   // a fit belongs to the scores it was made from
     ctx->last_launch_info.clear();
     for (size_t i = 0; i < plan.size(); i++) {
         const Planned &pl = plan[i];
@@ -1594,6 +1596,7 @@ int sat_queries_set(sat_ctx *ctx, int n_queries, const int32_t *n1s, const uint8
     ctx->queries.swap(infos);
     ctx->desc_dirty = true;
     ctx->searched_nq = 0;                     // the result buffers no longer belong to the current batch
+    ctx->fits.clear();
     return SAT_OK;
 }
 

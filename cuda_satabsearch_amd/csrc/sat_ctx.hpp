@@ -174,6 +174,13 @@ struct sat_ctx {
     DevBuf<int32_t> d_hit_maps;
     // z and p of every truncated norm2 score -128 .. 127, computed by the HOST's libm (sat_gumbel.c)
     DevBuf<double> d_gumbel_z, d_gumbel_p;
+    // Fitted statistics (sat_stats_fit / sat_stats_set, sat_topk.hip): fits[q] of the searched state, empty = every query
+    // on the built-in constants.  They belong to the scores in d_scores: whatever replaces those (a search, an upload, a
+    // query change) empties them.  d_fit_tabs: query q's z[SAT_STAT_BINS] then p[SAT_STAT_BINS] at q * 2 * SAT_STAT_BINS,
+    // filled by the host's libm for the fitted queries; d_hist: the score histogram, counts [nq][SAT_STAT_BINS] then below [nq]
+    std::vector<sat_fit> fits;
+    DevBuf<double> d_fit_tabs;
+    DevBuf<uint32_t> d_hist;
 
     // bytes copied device -> host by this context's result calls (sat_stat_d2h_bytes)
     unsigned long long d2h_bytes = 0;

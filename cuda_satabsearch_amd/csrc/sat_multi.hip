@@ -696,6 +696,62 @@ int sat_multi_search_cutoff(sat_multi *m, int lorder, int lsoln, int maxstart, d
     return r;
 }
 
+int sat_multi_score_histogram(sat_multi *m, uint32_t *counts, int32_t *below)
+{
+    if (!m) return sat_fail(SAT_EINVAL, "null context");
+    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
+    if (!counts || !below) return sat_fail(SAT_EINVAL, "histogram buffer is null");
+    const size_t nq = m->ctx[0]->queries.size();
+    // integer counts add up across the shards, in any order
+    std::vector<uint32_t> c(nq * SAT_STAT_BINS);
+    std::vector<int32_t> b(nq);
+    std::fill(counts, counts + nq * SAT_STAT_BINS, 0u);
+    std::fill(below, below + nq, 0);
+    for (int g = 0; g < m->ndev; g++) {
+        const int rc = sat_score_histogram(m->ctx[(size_t)g], c.data(), b.data());
+        if (rc != SAT_OK) return rc;
+        for (size_t i = 0; i < c.size(); i++) counts[i] += c[i];
+        for (size_t q = 0; q < nq; q++) below[q] += b[q];
+    }
+    return SAT_OK;
+}
+
+int sat_multi_stats_set(sat_multi *m, const sat_fit *fits)
+{
+    if (!m) return sat_fail(SAT_EINVAL, "null context");
+    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
+    for (int g = 0; g < m->ndev; g++) {
+        const int rc = sat_stats_set(m->ctx[(size_t)g], fits);
+        if (rc != SAT_OK) return rc;
+    }
+    return SAT_OK;
+}
+
+int sat_multi_search_fit(sat_multi *m, int lorder, int lsoln, int maxstart, double censor, sat_fit *fits, double *wall_ms)
+{
+    if (!m) return sat_fail(SAT_EINVAL, "null context");
+    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
+    if (!(censor >= 0.0 && censor <= 0.5)) return sat_fail(SAT_EINVAL, "censor must lie in [0, 0.5]");
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = each_shard(m, [&](int g) { return sat_search_async(m->ctx[(size_t)g], lorder, lsoln, maxstart); });
+    if (rc != SAT_OK) return rc;
+    // no gather: each shard's scores stay where they are, only the histograms cross to the host
+    const size_t nq = m->ctx[0]->queries.size();
+    std::vector<uint32_t> counts(nq * SAT_STAT_BINS);
+    std::vector<int32_t> below(nq);
+    if ((rc = sat_multi_score_histogram(m, counts.data(), below.data())) != SAT_OK) return bail(m, rc);
+    std::vector<sat_fit> fit(nq);
+    for (size_t q = 0; q < nq; q++) {
+        if (sat_gumbel_fit_binned(counts.data() + q * SAT_STAT_BINS, censor, &fit[q]) != 0)
+            return bail(m, sat_fail(SAT_EINVAL, "censor must lie in [0, 0.5]"));
+        fit[q].below = below[q];
+    }
+    if ((rc = sat_multi_stats_set(m, fit.data())) != SAT_OK) return bail(m, rc);
+    if (fits) std::copy(fit.begin(), fit.end(), fits);
+    if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return SAT_OK;
+}
+
 unsigned long long sat_multi_stat_d2h_bytes(const sat_multi *m)
 {
     if (!m) return 0ull;

@@ -17,12 +17,14 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include <algorithm>
 #include <climits>
 #include <cmath>
 #include <vector>
 
 #include "sat_ctx.hpp"
 #include "sat_cutoff.hpp"
+#include "host/sat_gumbel.h"
 
 namespace {
 
@@ -39,20 +41,29 @@ __global__ void pack_keys(const int32_t *scores, long long total, int n, unsigne
 
 struct HitQuery {
     int32_t n1;
-    int32_t pad_;
+    int32_t fitted;            // 1: the query's rows take their statistics from `fit`
     const int8_t *ssemaps;     // this query's [N][n1] maps, or null
+    const double *fit;         // fitted: z[SAT_STAT_BINS] then p[SAT_STAT_BINS] of the query (sat_stats_set), else null
 };
 
-// the row of (entry, score) for a query of n1 SSEs against an entry of n2
-__device__ __forceinline__ sat_hit hit_row(int32_t entry, int32_t score, int n1, int n2, const double *ztab, const double *ptab)
+// the row of (entry, score) for a query of n1 SSEs against an entry of n2.  fit = null: the built-in statistics, z and p
+// of norm2 truncated to an int; else the query's fitted tables at the row's histogram bin (a negative score: bin 0)
+__device__ __forceinline__ sat_hit hit_row(int32_t entry, int32_t score, int n1, int n2, const double *ztab, const double *ptab,
+                                           const double *fit)
 {
     const double norm2 = 2.0 * score / ((double)(n1 + n2));            // sat_norm2
-    int x = (int)norm2;                                                // the reference's double -> int
-    x = x < -128 ? -128 : (x > 127 ? 127 : x);                         // |norm2| <= 110 for every legal score
     sat_hit h;
     h.entry = entry;
     h.score = score;
     h.norm2 = norm2;
+    if (fit) {
+        const int bin = score < 0 ? 0 : sat_stat_bin_of(score, n1 + n2);
+        h.zscore = fit[bin];
+        h.pvalue = fit[SAT_STAT_BINS + bin];
+        return h;
+    }
+    int x = (int)norm2;                                                // the reference's double -> int
+    x = x < -128 ? -128 : (x > 127 ? 127 : x);                         // |norm2| <= 110 for every legal score
     h.zscore = ztab[x + 128];
     h.pvalue = ptab[x + 128];
     return h;
@@ -70,7 +81,7 @@ __global__ void finish_hits(const unsigned long long *sorted, int n, int k, int 
     const int32_t entry = (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFu));
     const int32_t score = (int32_t)(uint32_t)(key >> 32) - 0x40000000;
     const int n1 = queries[q].n1, n2 = orders[entry];
-    hits[t] = hit_row(entry, score, n1, n2, ztab, ptab);
+    hits[t] = hit_row(entry, score, n1, n2, ztab, ptab, queries[q].fit);
     if (maps) {
         int32_t *out = maps + (size_t)t * SAT_MAXDIM;
         const int8_t *src = queries[q].ssemaps ? queries[q].ssemaps + (size_t)entry * n1 : nullptr;
@@ -78,7 +89,8 @@ __global__ void finish_hits(const unsigned long long *sorted, int n, int k, int 
     }
 }
 
-// The HitQuery rows of queries [q0, q0 + nq) into ctx->d_hitq (maps: their solution maps of the last search), queued
+// The HitQuery rows of queries [q0, q0 + nq) into ctx->d_hitq (maps: their solution maps of the last search; the fitted
+// tables of the queries that have a fit), queued
 // on the context's stream from `hq`, which the caller keeps until the stream has passed the copy.
 int upload_hit_queries(sat_ctx *ctx, int q0, int nq, bool maps, std::vector<HitQuery> &hq)
 {
@@ -88,8 +100,10 @@ int upload_hit_queries(sat_ctx *ctx, int q0, int nq, bool maps, std::vector<HitQ
     for (int q = 0; q < nq; q++) {
         const auto &info = ctx->queries[(size_t)(q0 + q)];
         hq[(size_t)q].n1 = info.n1;
-        hq[(size_t)q].pad_ = 0;
+        const bool fitted = !ctx->fits.empty() && ctx->fits[(size_t)(q0 + q)].fitted;
+        hq[(size_t)q].fitted = fitted ? 1 : 0;
         hq[(size_t)q].ssemaps = maps ? ctx->d_ssemaps.get() + info.ssemap_off : nullptr;
+        hq[(size_t)q].fit = fitted ? ctx->d_fit_tabs.get() + (size_t)(q0 + q) * 2 * SAT_STAT_BINS : nullptr;
     }
     HIP_TRY(hipMemcpyAsync(ctx->d_hitq.get(), hq.data(), hq.size() * sizeof(HitQuery), hipMemcpyHostToDevice, ctx->stream));
     return SAT_OK;
@@ -183,7 +197,7 @@ __global__ void finish_refined(const unsigned long long *sorted, const int32_t *
     const int32_t entry = (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFu));
     const int32_t score = (int32_t)(uint32_t)(key >> 32) - 0x40000000;
     const int n1 = queries[q].n1;
-    hits[t] = hit_row(entry, score, n1, orders[entry], ztab, ptab);
+    hits[t] = hit_row(entry, score, n1, orders[entry], ztab, ptab, queries[q].fit);
     first[t] = cand[p].score;
     if (maps) {
         int32_t *out = maps + (size_t)t * SAT_MAXDIM;
@@ -215,7 +229,7 @@ __device__ __forceinline__ bool cutoff_row(const int32_t *scores, int n, int bpq
     e = (int)(blockIdx.x - (unsigned)q * bpq) * kCutoffBlock + (int)threadIdx.x;
     if (e >= n) return false;
     score = scores[(size_t)q * n + e];
-    return hit_row(e, score, queries[q].n1, orders[e], ztab, ptab).pvalue <= max_p;
+    return hit_row(e, score, queries[q].n1, orders[e], ztab, ptab, queries[q].fit).pvalue <= max_p;
 }
 
 // counts[q] += qualifying rows of query q
@@ -286,11 +300,54 @@ __global__ void cutoff_finish(const unsigned long long *sorted, const int32_t *s
     const int32_t entry = (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFu));
     const int32_t score = (int32_t)(uint32_t)(key >> 32) - 0x40000000;
     const int n1 = queries[q].n1;
-    hits[t] = hit_row(entry, score, n1, orders[entry], ztab, ptab);
+    hits[t] = hit_row(entry, score, n1, orders[entry], ztab, ptab, queries[q].fit);
     if (maps) {
         int32_t *out = maps + (size_t)t * SAT_MAXDIM;
         const int8_t *src = queries[q].ssemaps ? queries[q].ssemaps + (size_t)entry * n1 : nullptr;
         for (int i = 0; i < SAT_MAXDIM; i++) out[i] = (src && i < n1) ? (int32_t)src[i] : -1;
+    }
+}
+
+
+// ---- score histogram (sat_score_histogram).  Blocks of kHistRows rows, `bpq` blocks per query, so that a block holds
+// rows of one query only (as the cutoff kernels): the block counts its rows in a 16 KB LDS histogram with LDS integer
+// atomics, then adds its NON-ZERO bins to counts[q][bin] with global integer atomics - a query's scores crowd into a
+// few hundred bins, so a block of several thousand rows flushes a few hundred atomics.  Negative scores are summed
+// with a ballot per pass and one atomic per block.  Integers only: the result does not depend on the launch shape.
+constexpr int kHistBlock = 1024, kHistWaves = kHistBlock / 64, kHistPasses = 8, kHistRows = kHistBlock * kHistPasses;
+
+__global__ void __launch_bounds__(kHistBlock) score_histogram(const int32_t *scores, int n, int bpq, const int32_t *orders,
+                                                              const HitQuery *queries, uint32_t *counts, int32_t *below)
+{
+    __shared__ uint32_t hist[SAT_STAT_BINS];
+    __shared__ int32_t wave_below[kHistWaves];
+    const int q = (int)(blockIdx.x / (unsigned)bpq);
+    const int e0 = (int)(blockIdx.x - (unsigned)q * bpq) * kHistRows;
+    const int n1 = queries[q].n1;
+    for (int k = (int)threadIdx.x; k < SAT_STAT_BINS; k += kHistBlock) hist[k] = 0u;
+    __syncthreads();
+    int32_t neg = 0;                                                    // (meaningful in lane 0 of each wave)
+    for (int pass = 0; pass < kHistPasses; pass++) {
+        const int e = e0 + pass * kHistBlock + (int)threadIdx.x;        // e0 + kHistRows <= n + kHistRows: no overflow, n < 2^31 - 2^13
+        bool is_neg = false;
+        if (e < n) {
+            const int32_t score = scores[(size_t)q * n + e];
+            is_neg = score < 0;
+            if (!is_neg) atomicAdd(&hist[sat_stat_bin_of(score, n1 + orders[e])], 1u);
+        }
+        neg += (int32_t)__popcll(__ballot(is_neg));
+    }
+    if ((threadIdx.x & 63) == 0) wave_below[threadIdx.x >> 6] = neg;
+    __syncthreads();
+    uint32_t *out = counts + (size_t)q * SAT_STAT_BINS;
+    for (int k = (int)threadIdx.x; k < SAT_STAT_BINS; k += kHistBlock) {
+        const uint32_t c = hist[k];
+        if (c) atomicAdd(out + k, c);
+    }
+    if (threadIdx.x == 0) {
+        int32_t c = 0;
+        for (int w = 0; w < kHistWaves; w++) c += wave_below[w];
+        if (c) atomicAdd(below + q, c);
     }
 }
 
@@ -304,6 +361,105 @@ int cutoff_chunk(int n)
 }
 
 }  // namespace
+
+// The histogram of every query of the last search into ctx->d_hist (counts [nq][SAT_STAT_BINS], then below [nq]) and
+// from there to the host.  The query lists go in cutoff_chunk's chunks: fewer blocks per query here, so a chunk that
+// fits the cutoff kernels' grid fits this one.
+extern "C" int sat_score_histogram(sat_ctx *ctx, uint32_t *counts, int32_t *below)
+{
+    int rc = check_searched(ctx);
+    if (rc != SAT_OK) return rc;
+    if (!counts || !below) return sat_fail(SAT_EINVAL, "histogram buffer is null");
+    const int n = ctx->n_entries, nq = (int)ctx->queries.size();
+    if (n > 0x7FFFFFFF - kHistRows) return sat_fail(SAT_EINVAL, "too many entries for the histogram pass");
+    const int per_chunk = cutoff_chunk(n);
+    const int bpq = (n + kHistRows - 1) / kHistRows;
+    const size_t words = (size_t)nq * (SAT_STAT_BINS + 1);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = ctx->d_hist.grow(words)) != SAT_OK) return rc;
+    std::vector<HitQuery> hq_host;
+    if ((rc = upload_hit_queries(ctx, 0, nq, false, hq_host)) != SAT_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));             // hq_host dies at return
+    const HitQuery *hq = hit_queries(ctx);
+    uint32_t *d_counts = ctx->d_hist.get();
+    int32_t *d_below = reinterpret_cast<int32_t *>(d_counts + (size_t)nq * SAT_STAT_BINS);
+    HIP_TRY(hipMemsetAsync(d_counts, 0, words * sizeof(uint32_t), ctx->stream));
+    for (int q0 = 0; q0 < nq; q0 += per_chunk) {
+        const int nqc = nq - q0 < per_chunk ? nq - q0 : per_chunk;
+        hipLaunchKernelGGL(score_histogram, dim3((unsigned)nqc * (unsigned)bpq), dim3(kHistBlock), 0, ctx->stream,
+                           ctx->d_scores.get() + (size_t)q0 * n, n, bpq, ctx->d_orders.get(), hq + q0,
+                           d_counts + (size_t)q0 * SAT_STAT_BINS, d_below + q0);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(counts, d_counts, (size_t)nq * SAT_STAT_BINS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(below, d_below, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->d2h_bytes += words * sizeof(uint32_t);
+    return SAT_OK;
+}
+
+extern "C" int sat_stats_set(sat_ctx *ctx, const sat_fit *fits)
+{
+    int rc = check_searched(ctx);
+    if (rc != SAT_OK) return rc;
+    ctx->fits.clear();
+    if (!fits) return SAT_OK;
+    const size_t nq = ctx->queries.size();
+    bool any = false;
+    for (size_t q = 0; q < nq; q++) {
+        if (!fits[q].fitted) continue;
+        if (!std::isfinite(fits[q].a) || !std::isfinite(fits[q].b) || !(fits[q].b > 0.0))
+            return sat_fail(SAT_EINVAL, "query %zu: fitted parameters a = %g, b = %g are not usable", q, fits[q].a, fits[q].b);
+        any = true;
+    }
+    if (any) {
+        HIP_TRY(hipSetDevice(ctx->device));
+        // (rows selected earlier may still be read through the old tables on the stream)
+        if ((rc = ctx->d_fit_tabs.grow_after(ctx->stream, nq * 2 * SAT_STAT_BINS)) != SAT_OK) return rc;
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        std::vector<double> tab(2 * SAT_STAT_BINS);
+        for (size_t q = 0; q < nq; q++) {
+            if (!fits[q].fitted) continue;
+            sat_gumbel_fit_table(fits[q].a, fits[q].b, tab.data(), tab.data() + SAT_STAT_BINS);    // the host's libm
+            HIP_TRY(hipMemcpy(ctx->d_fit_tabs.get() + q * 2 * SAT_STAT_BINS, tab.data(), tab.size() * sizeof(double),
+                              hipMemcpyHostToDevice));
+        }
+    }
+    ctx->fits.assign(fits, fits + nq);
+    return SAT_OK;
+}
+
+extern "C" int sat_stats_fit(sat_ctx *ctx, double censor, sat_fit *fits)
+{
+    int rc = check_searched(ctx);
+    if (rc != SAT_OK) return rc;
+    if (!(censor >= 0.0 && censor <= 0.5)) return sat_fail(SAT_EINVAL, "censor must lie in [0, 0.5]");
+    const size_t nq = ctx->queries.size();
+    std::vector<uint32_t> counts(nq * SAT_STAT_BINS);
+    std::vector<int32_t> below(nq);
+    if ((rc = sat_score_histogram(ctx, counts.data(), below.data())) != SAT_OK) return rc;
+    std::vector<sat_fit> fit(nq);
+    for (size_t q = 0; q < nq; q++) {
+        if (sat_gumbel_fit_binned(counts.data() + q * SAT_STAT_BINS, censor, &fit[q]) != 0)
+            return sat_fail(SAT_EINVAL, "censor must lie in [0, 0.5]");
+        fit[q].below = below[q];
+    }
+    if ((rc = sat_stats_set(ctx, fit.data())) != SAT_OK) return rc;
+    if (fits) std::copy(fit.begin(), fit.end(), fits);
+    return SAT_OK;
+}
+
+extern "C" int sat_debug_set_scores(sat_ctx *ctx, const int32_t *scores)
+{
+    int rc = check_searched(ctx);
+    if (rc != SAT_OK) return rc;
+    if (!scores) return sat_fail(SAT_EINVAL, "scores buffer is null");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(ctx->d_scores.get(), scores, ctx->queries.size() * (size_t)ctx->n_entries * sizeof(int32_t), hipMemcpyHostToDevice));
+    ctx->fits.clear();
+    return SAT_OK;
+}
 
 extern "C" int sat_topk(sat_ctx *ctx, int query, int k, int32_t *entry_index, int32_t *scores_out)
 {

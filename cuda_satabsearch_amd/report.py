@@ -17,6 +17,19 @@ def stats(score, n1, n2):
     return norm2, z, p
 
 
+def stats_fitted(score, n1, n2, a, b):
+    """(norm2, z, p) of a row of a query whose Gumbel parameters were fitted to (a, b): z and p at the lower edge of
+    the row's histogram bin (sat_gumbel_fit_table; a negative score uses bin 0), as the device and the command line
+    print them under -F."""
+    import numpy as np
+    host = _native.host_lib()
+    z = np.empty(_native.STAT_BINS)
+    p = np.empty(_native.STAT_BINS)
+    host.sat_gumbel_fit_table(float(a), float(b), z.ctypes.data, p.ctypes.data)
+    k = max(host.sat_stat_bin(int(score), int(n1), int(n2)), 0)
+    return host.sat_norm2(int(score), int(n1), int(n2)), float(z[k]), float(p[k])
+
+
 def header_lines(qid, dbfile, ltype=True, lorder=True, lsoln=False):
     tf = lambda b: "T" if b else "F"
     return [f"# cudaSaTabsearch LTYPE = {tf(ltype)} LORDER = {tf(lorder)} LSOLN = {tf(lsoln)}",

@@ -57,6 +57,36 @@ _HIT_DTYPE = np.dtype([("entry", np.int32), ("score", np.int32), ("norm2", np.fl
 assert _HIT_DTYPE.itemsize == C.sizeof(_native.Hit)
 
 
+# struct sat_fit (include/satabsearch.h) as a numpy record: fit_statistics, set_statistics, search_fit
+_FIT_DTYPE = np.dtype([("a", np.float64), ("b", np.float64), ("rows", np.int32), ("censored", np.int32),
+                       ("below", np.int32), ("fitted", np.int32)], align=True)
+assert _FIT_DTYPE.itemsize == C.sizeof(_native.Fit)
+STAT_BINS = _native.STAT_BINS
+
+
+def _score_histogram(obj, fn, handle, nq):
+    """shared by Searcher / MultiSearcher.score_histogram: (counts uint32[nq, 4096], below int32[nq])"""
+    counts = np.zeros((nq, STAT_BINS), np.uint32)
+    below = np.zeros(nq, np.int32)
+    obj._check(fn(handle, counts.ctypes.data, below.ctypes.data))
+    return counts, below
+
+
+def _fit_records(fits, nq):
+    """set_statistics' argument as sat_fit records: a _FIT_DTYPE array, or a sequence of (a, b) pairs / None per
+    query (None: that query keeps the built-in constants)"""
+    if isinstance(fits, np.ndarray) and fits.dtype == _FIT_DTYPE:
+        rec = np.ascontiguousarray(fits).ravel()
+    else:
+        rec = np.zeros(len(fits), _FIT_DTYPE)
+        for q, f in enumerate(fits):
+            if f is not None:
+                rec[q]["a"], rec[q]["b"], rec[q]["fitted"] = float(f[0]), float(f[1]), 1
+    if len(rec) != nq:
+        raise ValueError("one fit per query is needed")
+    return rec
+
+
 def _search_refine(obj, call, k, candidates, refine_maxstart, lsoln):
     """shared by Searcher / MultiSearcher.search_refine: `call(hits, maps, first)` runs the C entry point"""
     nq = getattr(obj, "n_queries", 1)
@@ -327,6 +357,37 @@ class Searcher:
         rows, maps = _hits_cutoff(self, nq, lsoln, call, call)
         return (rows, maps) if lsoln else rows
 
+    def score_histogram(self):
+        """The histogram of the last search's norm2 scores, made on the device (sat_score_histogram):
+        (counts uint32[nq, 4096], below int32[nq]) - bin floor(norm2 * 256), the last bin the overflow; rows with a
+        negative score are counted in `below`."""
+        return _score_histogram(self, self._lib.sat_score_histogram, self._ctx, getattr(self, "n_queries", 1))
+
+    def fit_statistics(self, censor=0.0):
+        """Fit every query's Gumbel parameters to the last search's own scores (sat_stats_fit: histogram on the device,
+        maximum-likelihood fit with the top `censor` of the rows right-censored) and install them: topk_hits and
+        hits_cutoff then give z and p from the fit, until the next search.  Returns a record array [nq] with fields
+        a, b, rows, censored, below, fitted (fitted 0: no fit exists, that query keeps the built-in constants)."""
+        fits = np.zeros(getattr(self, "n_queries", 1), _FIT_DTYPE)
+        self._check(self._lib.sat_stats_fit(self._ctx, float(censor), fits.ctypes.data))
+        return fits
+
+    def set_statistics(self, fits):
+        """Install the caller's Gumbel parameters for the last search (sat_stats_set): a fit_statistics() array, or
+        one (a, b) pair / None per query; None puts every query back on the built-in constants."""
+        if fits is None:
+            self._check(self._lib.sat_stats_set(self._ctx, None))
+            return
+        rec = _fit_records(fits, getattr(self, "n_queries", 1))
+        self._check(self._lib.sat_stats_set(self._ctx, rec.ctypes.data))
+
+    def debug_set_scores(self, scores):
+        """Test hook (satabsearch_debug.h): overwrite the last search's device scores with int32[nq, N]."""
+        sc = np.ascontiguousarray(scores, dtype=np.int32)
+        if sc.size != getattr(self, "n_queries", 1) * self.n_entries:
+            raise ValueError("scores must be [n_queries, n_entries]")
+        self._check(self._lib.sat_debug_set_scores(self._ctx, sc.ctypes.data))
+
     def d2h_bytes(self):
         """Bytes this context's result calls have copied device -> host so far."""
         return int(self._lib.sat_stat_d2h_bytes(self._ctx))
@@ -484,6 +545,25 @@ class MultiSearcher:
         call = lambda c, cap, h, m: self._lib.sat_multi_hits_cutoff(self._m, float(max_pvalue), int(k or 0), c, cap, h, m)
         rows, maps = _hits_cutoff(self, self.n_queries, lsoln, call, call)
         return (rows, maps) if lsoln else rows
+
+    def score_histogram(self):
+        """Searcher.score_histogram summed over every shard's last search (sat_multi_score_histogram)."""
+        return _score_histogram(self, self._lib.sat_multi_score_histogram, self._m, self.n_queries)
+
+    def search_fit(self, censor=0.0, lorder=True, lsoln=False, maxstart=DEFAULT_MAXSTART):
+        """Search every shard without a gather, sum the shards' histograms, fit once and install the fit on every shard
+        (sat_multi_search_fit): (fits as Searcher.fit_statistics, wall_ms).  hits_cutoff then returns rows with the
+        fitted statistics, without a new search."""
+        fits = np.zeros(self.n_queries, _FIT_DTYPE)
+        ms = C.c_double(0.0)
+        self._check(self._lib.sat_multi_search_fit(self._m, int(bool(lorder)), int(bool(lsoln)), int(maxstart), float(censor),
+                                                   fits.ctypes.data, C.byref(ms)))
+        return fits, ms.value
+
+    def set_statistics(self, fits):
+        """Searcher.set_statistics on every shard (sat_multi_stats_set)."""
+        rec = None if fits is None else _fit_records(fits, self.n_queries)
+        self._check(self._lib.sat_multi_stats_set(self._m, rec.ctypes.data if rec is not None else None))
 
     def d2h_bytes(self):
         return int(self._lib.sat_multi_stat_d2h_bytes(self._m))

@@ -330,6 +330,61 @@ int sat_search_refine(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int can
                       int k, sat_hit *hits, int32_t *ssemaps, int32_t *first_scores);
 
 
+/*
+ * ---- Gumbel statistics fitted to the search's own scores.  Every z and p above comes from two
+ * constants fitted once to one database, one restart count and one mix of queries (gumbelstats.h:21-23); the
+ * reference's workflow re-fits them to the scores at hand (scripts/fitgumbeldist.r).  Here that happens on the
+ * device, from a per-query integer histogram of the norm2 scores - integer counts do not depend on the order they
+ * are added in and add up across shards, so the fit is identical for any launch shape and any sharding.
+ *
+ * Binning (one definition for host and device, csrc/host/sat_stats.h): a row with score >= 0 goes to bin
+ * min((512 * score) / (n1 + n2), SAT_STAT_BINS - 1) = floor(norm2 * 256), the last bin taking every
+ * norm2 >= 16 - 1/256; rows with score < 0 go into no bin and are counted in below[q].
+ */
+#define SAT_STAT_BINS           4096
+#define SAT_STAT_BINS_PER_UNIT  256
+
+#ifndef SAT_FIT_DEFINED
+#define SAT_FIT_DEFINED
+typedef struct sat_fit {
+    double  a, b;       /* location and scale; the built-in constants when fitted == 0                       */
+    int32_t rows;       /* rows in the histogram's bins                                                      */
+    int32_t censored;   /* of them, rows above the censoring point (the overflow bin included)               */
+    int32_t below;      /* rows with a negative score: in no bin, not fitted                                 */
+    int32_t fitted;     /* 0: no fit exists, the query keeps the built-in statistics                         */
+} sat_fit;
+#endif
+
+/*
+ * The histogram of the last search's scores, made on the device (one LDS histogram per block of rows, integer
+ * atomics only: bit-reproducible): counts [n_queries][SAT_STAT_BINS], below [n_queries].  As sat_hits_cutoff it
+ * never searches (SAT_ESTATE before the first search).  Copies exactly n_queries * (SAT_STAT_BINS + 1) * 4 bytes.
+ */
+int sat_score_histogram(sat_ctx *ctx, uint32_t *counts, int32_t *below);
+
+/*
+ * Histogram, fit, install: each query's histogram goes through sat_gumbel_fit_binned of csrc/host/sat_gumbel.h (the
+ * maximum-likelihood Gumbel of the bin midpoints, the top `censor` of the rows right-censored; censor in [0, 0.5],
+ * else SAT_EINVAL) and the result is installed as by sat_stats_set.  fits (may be NULL) [n_queries] receives the
+ * parameters; a query for which no fit exists (fewer than 2 occupied uncensored bins, no convergence) comes back
+ * with fitted == 0 and keeps the built-in statistics.
+ */
+int sat_stats_fit(sat_ctx *ctx, double censor, sat_fit *fits);
+
+/*
+ * Install the caller's parameters for the current searched state: fits [n_queries]; queries with fitted == 0 keep the
+ * built-ins, NULL puts every query back on them.  A query with a fit gets its own SAT_STAT_BINS-entry z / p tables on
+ * the device, filled by the host's libm (sat_gumbel_fit_table: z and p at the LOWER edge of the row's bin), and every
+ * row sat_topk_hits / sat_hits_cutoff give for it from then on - also the rows sat_hits_cutoff selects: a row still
+ * qualifies iff the same double from the same table is <= max_pvalue - carries table entry clamp(bin, 0, 4095); a row
+ * with score < 0 uses bin 0.  A fit belongs to the searched state: any new search (stage 1 of sat_search_refine and
+ * sat_search_matches included), database upload or query change drops the context back to the built-in constants.  The
+ * pair searches keep it: they leave the result buffers alone.  A fitted a or b that is not finite, or b <= 0, is
+ * SAT_EINVAL; SAT_ESTATE before the first search.  (This is how sat_multi_search_fit installs the merged fit, and how
+ * a calibration pooled over queries is installed.)
+ */
+int sat_stats_set(sat_ctx *ctx, const sat_fit *fits);
+
 /* Bytes this context's result calls (sat_results, sat_search, sat_topk, sat_topk_hits, sat_hits_cutoff, the pair searches) have copied
  * from the device to the host since it was created (diagnostics: the best-k path moves O(k) rows). */
 unsigned long long sat_stat_d2h_bytes(const sat_ctx *ctx);
@@ -427,6 +482,15 @@ int sat_multi_search_cutoff(sat_multi *m, int lorder, int lsoln, int maxstart, d
                             int32_t *counts, int capacity, sat_hit *hits, int32_t *ssemaps, double *wall_ms);
 int sat_multi_hits_cutoff(sat_multi *m, double max_pvalue, int max_rows, int32_t *counts, int capacity, sat_hit *hits,
                           int32_t *ssemaps);
+/* The fitted statistics over every shard, exactly what one context holding the whole database gives:
+ * sat_multi_score_histogram sums the shards' integer histograms on the host (ndev * nq * (SAT_STAT_BINS + 1) * 4 bytes
+ * cross to it), sat_multi_stats_set installs the same parameters on every shard, and sat_multi_search_fit searches
+ * every shard WITHOUT a gather, sums the histograms, fits once (sat_stats_fit's censor) and installs the fit
+ * everywhere; fits (may be NULL) [n_queries].  Afterwards sat_multi_hits_cutoff(P, K) returns the rows without a new
+ * search; P >= 1 with max_rows = K is the best K rows of every query.  wall_ms as sat_multi_search. */
+int sat_multi_score_histogram(sat_multi *m, uint32_t *counts, int32_t *below);
+int sat_multi_stats_set(sat_multi *m, const sat_fit *fits);
+int sat_multi_search_fit(sat_multi *m, int lorder, int lsoln, int maxstart, double censor, sat_fit *fits, double *wall_ms);
 unsigned long long sat_multi_stat_d2h_bytes(const sat_multi *m);
 
 /*

@@ -30,12 +30,20 @@
  */
 #ifndef SATABSEARCH_DEBUG_H
 #define SATABSEARCH_DEBUG_H
+#include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
 #endif
 /* diagnostic builds only: counters of the last search - [0..7] and [10] wave-cycles per phase of the kernel, [8] self-check
  * mismatches, [9] self-checks made */
 void sat_diag_counters(unsigned long long out[16]);
+
+/* Every build, a test hook: overwrite the device scores of the last search with the caller's [n_queries][n_entries]
+ * array (and drop any fitted statistics, which belonged to the scores replaced).  Tests use it to reach negative
+ * scores, the overflow bin and exact bin edges of the score histogram, which no real search produces on demand.
+ * SAT_ESTATE before the first search. */
+struct sat_ctx;
+int sat_debug_set_scores(struct sat_ctx *ctx, const int32_t *scores);
 #ifdef __cplusplus
 }
 #endif
