@@ -149,6 +149,10 @@ def device_lib():
         lib.sat_multi_search_fit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p,
                                              C.POINTER(C.c_double)]
         lib.sat_debug_set_scores.argtypes = [C.c_void_p, C.c_void_p]          # include/satabsearch_debug.h
+        # a test hook outside the ABI (include/satabsearch_debug.h): a build loaded through SAT_DEVICE_LIB may predate it
+        if hasattr(lib, "sat_debug_sa_instances"):
+            lib.sat_debug_sa_instances.argtypes = []
+            lib.sat_debug_sa_instances.restype = C.c_char_p
         lib.sat_device_scores.argtypes = [C.c_void_p]
         lib.sat_device_scores.restype = C.c_void_p
         lib.sat_device_ssemaps.argtypes = [C.c_void_p]

@@ -16,6 +16,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <set>
+#include <string>
 #include <thread>
 #include <type_traits>
 #include <vector>
@@ -245,18 +247,26 @@ hipError_t launch_sa(const SaKernel &k, dim3 grid, dim3 block, size_t lds, hipSt
     return hipGetLastError();
 }
 
+// An instantiation by name, "kernel<template arguments>" as the source spells it: the one formatter of
+// sat_last_launch_info (launch_info) and of the list of instantiations (sat_debug_sa_instances).
+std::string sa_kernel_name(const SaKernel &k)
+{
+    static const char *const kName[4] = { "sat_sa_kernel", "sat_sa_match_kernel", "sat_sa_pair_kernel", "sat_sa_pair_match_kernel" };
+    char targs[48] = "", buf[128];
+    if (k.mode == kPlain) snprintf(targs, sizeof targs, "%d, %d, ", k.opt, k.wpl);
+    if (k.mode == kPair) snprintf(targs, sizeof targs, "%d, ", k.opt);
+    snprintf(buf, sizeof buf, "%s<%d, %d, %s, %s%d>", kName[k.mode], k.n1p, k.m2w, k.qlds ? "true" : "false", targs, k.cells);
+    return buf;
+}
+
 // One launch as sat_last_launch_info names it: "kernel<template arguments> [items N] grid X x Y block E x T lds B"
 // (items: the pair families' item count; E entry slots of T threads; B the LDS bytes of one slot).
 std::string launch_info(const SaKernel &k, int items, int grid_x, int grid_y, int epw, int threads, size_t lds)
 {
-    static const char *const kName[4] = { "sat_sa_kernel", "sat_sa_match_kernel", "sat_sa_pair_kernel", "sat_sa_pair_match_kernel" };
-    char targs[48] = "", count[32] = "", buf[200];
-    if (k.mode == kPlain) snprintf(targs, sizeof targs, "%d, %d, ", k.opt, k.wpl);
-    if (k.mode == kPair) snprintf(targs, sizeof targs, "%d, ", k.opt);
+    char count[32] = "", buf[128];
     if (k.mode & kPair) snprintf(count, sizeof count, " items %d", items);
-    snprintf(buf, sizeof buf, "%s<%d, %d, %s, %s%d>%s grid %d x %d block %d x %d lds %zu", kName[k.mode], k.n1p, k.m2w,
-             k.qlds ? "true" : "false", targs, k.cells, count, grid_x, grid_y, epw, threads, lds);
-    return buf;
+    snprintf(buf, sizeof buf, "%s grid %d x %d block %d x %d lds %zu", count, grid_x, grid_y, epw, threads, lds);
+    return sa_kernel_name(k) + buf;
 }
 
 const int kClassN1P[4] = { 16, 32, 64, 112 };
@@ -1656,6 +1666,29 @@ void sat_debug_lds_layout(int m2w, int n1, int n1p, int n2, int chains, int thre
                                                q_in_lds != 0, compact != 0);
     const uint32_t v[11] = { L.code, L.qdist, L.qcode, L.smap, L.tmask, L.qtypes, L.leader, L.red, L.red_stride, L.items, L.total };
     for (int i = 0; i < 11; i++) out[i] = v[i];
+}
+
+// satabsearch_debug.h: every instantiation pick_sa_kernel can choose, named as sat_last_launch_info names it, one per
+// line in the order of the walk (family, class, set width and layout, QLDS, OPT, WPL).  Host only: the walk takes the
+// addresses of the kernels' host stubs, which also tell two instantiations apart.
+const char *sat_debug_sa_instances(void)
+{
+    static const std::string list = [] {
+        const int layouts[4][2] = { { 1, SAT_CELLS_FULL8 }, { 2, SAT_CELLS_FULL5 }, { 2, SAT_CELLS_TRI5 }, { 4, SAT_CELLS_TRI5 } };
+        std::set<const void *> seen;
+        std::string out;
+        for (int mode = kPlain; mode <= kPairMatch; mode++)
+            for (int n1p : kClassN1P)
+                for (const auto &l : layouts)
+                    for (int qlds = 0; qlds < 2; qlds++)
+                        for (int opt = -1; opt <= 11; opt++)
+                            for (int wpl = 0; wpl <= 4; wpl++) {
+                                const SaKernel k = pick_sa_kernel(mode, n1p, l[0], l[1], qlds != 0, opt, wpl);
+                                if (seen.insert(k.fn).second) out += sa_kernel_name(k) + "\n";
+                            }
+        return out;
+    }();
+    return list.c_str();
 }
 
 int sat_sync(sat_ctx *ctx)

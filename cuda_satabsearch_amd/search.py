@@ -21,6 +21,15 @@ def device_count():
     return int(_native.device_lib().sat_device_count())
 
 
+def sa_kernel_instances():
+    """Test hook (satabsearch_debug.h): the names of every SA kernel instantiation the library can launch, spelled as
+    last_launch_info() spells them.  Needs no device."""
+    lib = _native.device_lib()
+    if not hasattr(lib, "sat_debug_sa_instances"):
+        raise SatError(f"{_native.DEVICE_LIB} does not export sat_debug_sa_instances (a build from before the hook)")
+    return lib.sat_debug_sa_instances().decode().splitlines()
+
+
 def _search_matches(obj, fn, handle, max_matches, lorder, maxstart, maps):
     nq, n, m = obj.n_queries, obj.n_entries, max(int(max_matches), 1)
     counts = np.zeros((nq, n), np.int32)

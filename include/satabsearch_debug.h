@@ -44,6 +44,13 @@ void sat_diag_counters(unsigned long long out[16]);
  * SAT_ESTATE before the first search. */
 struct sat_ctx;
 int sat_debug_set_scores(struct sat_ctx *ctx, const int32_t *scores);
+
+/* Every build, a test hook: the instantiations of the SA kernel the library can launch - the distinct kernels its
+ * dispatcher chooses over its whole argument domain (family, query class, set width and cell layout, query cells in
+ * LDS or not, option code -1..11, words per lane 0..4) -, one name per line, each spelled exactly as
+ * sat_last_launch_info spells it: "sat_sa_kernel<32, 1, false, 1, 4, 0>", "sat_sa_pair_kernel<...>", ...  Needs no
+ * context and no device, and does not depend on the SAT_EXP_* environment.  The string lives as long as the library. */
+const char *sat_debug_sa_instances(void);
 #ifdef __cplusplus
 }
 #endif

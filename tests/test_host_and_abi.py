@@ -22,6 +22,50 @@ def test_abi_library_loads_and_exports_every_declared_symbol():
     assert _native.device_lib().sat_abi_version() == 1
 
 
+def test_the_dispatcher_lists_its_328_instantiations():
+    """sat_debug_sa_instances walks pick_sa_kernel over its whole argument domain without a device: 200 plain, 32
+    match, 64 pair and 32 pair-match instantiations, each named once, in the spelling of
+    sat_last_launch_info; the SAT_EXP_* overrides, which belong to a context, do not change the list."""
+    import subprocess
+    import sys
+    names = sat.sa_kernel_instances()
+    assert len(names) == len(set(names)) == 328
+    count = {}
+    for n in names:
+        m = re.fullmatch(r"(sat_sa_(?:pair_|match_|pair_match_)?kernel)<(16|32|64|112), ([124]), (true|false), (?:(-?\d+), )?(?:([0-4]), )?([012])>", n)
+        assert m, n
+        family, opt, wpl = m.group(1), m.group(5), m.group(6)
+        count[family] = count.get(family, 0) + 1
+        # the template arguments a family has: plain OPT and WPL, pair OPT, the match families neither
+        assert (opt is not None, wpl is not None) == {"sat_sa_kernel": (True, True), "sat_sa_pair_kernel": (True, False)}.get(
+            family, (False, False)), n
+        assert (int(m.group(3)), int(m.group(7))) in ((1, 0), (2, 1), (2, 2), (4, 2)), n       # set width and cell layout
+    assert count == {"sat_sa_kernel": 200, "sat_sa_match_kernel": 32, "sat_sa_pair_kernel": 64, "sat_sa_pair_match_kernel": 32}
+    assert "sat_sa_kernel<32, 1, false, 1, 4, 0>" in names and "sat_sa_kernel<112, 4, false, 11, 0, 2>" in names
+    env = dict(os.environ, SAT_EXP_GENERAL="1", SAT_EXP_LPC="2", SAT_EXP_QLDS="1", SAT_EXP_COMPACT="0", SAT_EXP_EPW="3")
+    out = subprocess.run([sys.executable, "-c", "import cuda_satabsearch_amd as sat; print('\\n'.join(sat.sa_kernel_instances()))"],
+                         cwd=ROOT, env=env, check=True, capture_output=True, text=True).stdout
+    assert out.splitlines() == names
+
+
+def test_a_build_without_the_instance_hook_still_loads(monkeypatch):
+    """SAT_DEVICE_LIB loads other builds of the ABI (A/B runs, the diagnostic twin): the hook of satabsearch_debug.h is
+    not part of the ABI, so a library from before it must load, and only asking for the list fails."""
+    real = ctypes.CDLL(_native.DEVICE_LIB)
+
+    class WithoutHook:
+        def __getattr__(self, name):
+            if name == "sat_debug_sa_instances":
+                raise AttributeError(name)
+            return getattr(real, name)
+
+    monkeypatch.setattr(_native, "_device", None)
+    monkeypatch.setattr(_native.C, "CDLL", lambda path: WithoutHook())
+    assert _native.device_lib().sat_abi_version() == 1
+    with pytest.raises(sat.SatError, match="sat_debug_sa_instances"):
+        sat.sa_kernel_instances()
+
+
 def test_no_device_fails_loudly():
     """Without a HIP device the product refuses to run; it never computes on the CPU."""
     if sat.device_count() > 0:
