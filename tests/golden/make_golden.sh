@@ -60,3 +60,6 @@ sed -n 43,49p /root/reference/README_example_usage.txt | sed 's/^    //' > "$her
 # replay of main's -q branch
 printf 'd1kcul1\nD1NLDL1xyz\nd1lfwa2\n' > "$here/inputs/qmode_sids.txt"
 "$repo/oracle/_ref/ref_oracle" -c -r16 -q tableauxdistmatrixdb.small.ascii < "$here/inputs/qmode_sids.txt" > "$here/expected/qmode_small.r16.out" 2>/dev/null
+
+# the edge database (both size classes, ? codes, >= 100 A cells, -q across classes): inputs and recordings
+python3 "$here/make_edge_golden.py"

@@ -4,6 +4,12 @@ expected/*.out were produced by the reference's sources compiled in place
 (oracle/_ref, tests/golden/make_golden.sh); recorded_2013_* is the stdout the reference
 ships from a real 2013 run.  Byte-for-byte equality pins search + reader + statistics +
 printing of the restatement.
+
+What is pinned where: this file holds the reference's EXAMPLE database (586 entries of 1..67 SSEs) - 13 recorded
+outputs, one -q recording and one step trace.  What that database cannot reach (entries above 96 SSEs and the
+reference's second pass, half-unknown codes, distances >= 100 A in a search, LORDER = F and large-class step
+traces, a -q list that mixes the classes) is pinned by the edge database's recordings in
+tests/test_reference_edges.py, which also compares random inputs live against oracle/_ref where that is built.
 """
 import os
 import subprocess
