@@ -30,6 +30,7 @@ ABI_SYMBOLS = (
     "sat_search_pairs_matches", "sat_multi_search_pairs_matches",
     "sat_score_histogram", "sat_stats_fit", "sat_stats_set",
     "sat_multi_score_histogram", "sat_multi_stats_set", "sat_multi_search_fit",
+    "sat_search_pairs_polish", "sat_search_refine_polish", "sat_multi_search_pairs_polish", "sat_multi_search_refine_polish",
 )
 
 STAT_BINS = 4096
@@ -135,6 +136,12 @@ def device_lib():
         lib.sat_multi_search_refine.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
                                                 C.POINTER(C.c_double)]
+        lib.sat_search_pairs_polish.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+        lib.sat_multi_search_pairs_polish.argtypes = lib.sat_search_pairs_polish.argtypes
+        lib.sat_search_refine_polish.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.sat_multi_search_refine_polish.argtypes = lib.sat_search_refine_polish.argtypes + [C.POINTER(C.c_double)]
         lib.sat_hits_cutoff.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         lib.sat_multi_search_cutoff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                                 C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]

@@ -70,7 +70,7 @@ def _host_objects(force=False):
 
 def build_device(force=False):
     out = os.path.join(PKG, "libsatabsearch.so")
-    srcs = [os.path.join(CSRC, "sat_capi.hip"), os.path.join(CSRC, "sat_topk.hip"), os.path.join(CSRC, "sat_multi.hip")]
+    srcs = [os.path.join(CSRC, f) for f in ("sat_capi.hip", "sat_topk.hip", "sat_multi.hip", "sat_polish.hip")]
     host_o = _host_objects(force)
     deps = srcs + host_o + [os.path.join(CSRC, "sat_sa_kernel.hpp"), os.path.join(CSRC, "sat_sa_body.inc"),
                             os.path.join(CSRC, "sat_ctx.hpp"), os.path.join(CSRC, "sat_cutoff.hpp"),
@@ -114,7 +114,7 @@ def build_test_native(force=False):
     # -DSAT_DIAG_SELFCHECK: every proposed move's score against a full recomputation) - loaded only by
     # tests/test_gpu_parity.py::test_every_move_passes_the_references_self_check, through SAT_DEVICE_LIB
     out3 = os.path.join(tdir, "libsat_selfcheck.so")
-    dsrcs = [os.path.join(CSRC, f) for f in ("sat_capi.hip", "sat_topk.hip", "sat_multi.hip")]
+    dsrcs = [os.path.join(CSRC, f) for f in ("sat_capi.hip", "sat_topk.hip", "sat_multi.hip", "sat_polish.hip")]
     ddeps = dsrcs + [os.path.join(CSRC, "sat_sa_kernel.hpp"), os.path.join(CSRC, "sat_sa_body.inc"), os.path.join(CSRC, "sat_ctx.hpp"),
                      os.path.join(CSRC, "sat_cutoff.hpp"), os.path.join(HOST, "sat_gumbel.h"), os.path.join(HOST, "sat_stats.h"),
                      os.path.join(CSRC, "diag", "sat_diag.hpp"), os.path.join(INC, "satabsearch.h")]

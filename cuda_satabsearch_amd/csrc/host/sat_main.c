@@ -30,7 +30,9 @@
  * in -m's format: a pair-match search of those rows only, after the search that chose them), -F censor (fit each
  * query's Gumbel parameters to its own scores and print z and p from the fit: a fourth header line "# GUMBEL ...", see
  * sat_gumbel.h; the listing fits on the host, -k / -p on the GPUs from a histogram, so that still only the printed rows
- * leave them).
+ * leave them), -P T (polish: the rows of -k K are the K best of each query's C best entries after the own-best maps of
+ * every candidate's T best restarts were climbed to local optima of the search's neighbourhood on the GPU; a fourth header
+ * line "# POLISH ...").
  */
 #include <math.h>
 #include <stdarg.h>
@@ -64,11 +66,12 @@ static double now_ms(void)
 #pragma weak sat_multi_hits_cutoff
 #pragma weak sat_multi_search_pairs_matches
 #pragma weak sat_multi_search_fit
+#pragma weak sat_multi_search_refine_polish
 
 static void usage(const char *prog)
 {
     fprintf(stderr, "Usage: %s [-c] [-q dbfile] [-r restarts] [-g gpus] [-G gpu,gpu,...] [-s seed] [-k K] [-p P]\n"
-                    "       [-m M] [-M M] [-R restarts [-C C]] [-F censor] [-b]\n", prog);
+                    "       [-m M] [-M M] [-R restarts [-C C]] [-F censor] [-P T] [-b]\n", prog);
     fprintf(stderr, "  -c : run on host CPU not GPU card\n");
     fprintf(stderr, "  -q dbfile : database is read from dbfile, list of query\n"
                     "              ids is read from stdin\n");
@@ -88,6 +91,9 @@ static void usage(const char *prog)
     fprintf(stderr, "  -C C : candidates per query re-scored by -R. Default K\n");
     fprintf(stderr, "  -F censor : fit each query's Gumbel parameters to its own scores, the top `censor` (0..0.5) of them\n"
                     "              right-censored; z and p come from the fit (header line # GUMBEL)\n");
+    fprintf(stderr, "  -P T : polish: rank each query's C best entries (-C, default K) after the maps of their T (1..%d)\n"
+                    "         best restarts (of -R restarts, default -r) were climbed to local optima; rows as -k, with\n"
+                    "         the polished scores and maps (GPU mode, needs -k)\n", SAT_MAX_MATCHES);
     fprintf(stderr, "  -b : cache the parsed database as dbfile.satbin\n");
     exit(1);
 }
@@ -231,6 +237,7 @@ typedef struct {
     int use_gpu, maxstart, want_gpus, bincache, topk, nmatch, refine, ncand, cutoff;
     int rowmatch;                     /* -M: matches of each printed row */
     int fit;                          /* -F: statistics fitted to each query's own scores */
+    int polish;                       /* -P: maps polished per candidate */
     double censor;                    /* -F: the right-censored fraction of the rows */
     double pmax;                      /* -p: the largest p-value printed */
     unsigned long long seed;
@@ -307,6 +314,8 @@ static void print_entry(const input *in, int e, int n1, const sat_hit *h, const 
 }
 
 /* -F: the rows that follow are query `f`'s - its tables and an empty text cache; no fit (or NULL): the built-ins */
+static char polish_header[128];      /* -P: the fourth header line of every block, else empty */
+
 static void begin_query_stats(const sat_fit *f)
 {
     fit_cur = NULL;
@@ -331,6 +340,7 @@ static void print_header(const input *in, int qi, const sat_fit *f)
     out_bytes(line, (size_t)n);
     n = snprintf(line, sizeof line, "# DBFILE = %-80s\n", in->dbfile);
     out_bytes(line, (size_t)n);
+    out_bytes(polish_header, strlen(polish_header));
     begin_query_stats(f);
     if (!f)
         return;
@@ -350,7 +360,7 @@ static void parse_options(int argc, char *argv[], options *o)
 {
     *o = (options){ .use_gpu = 1, .maxstart = 128, .want_gpus = 1, .seed = SAT_DEFAULT_SEED };
     int c;
-    while ((c = getopt(argc, argv, "cq:r:g:G:s:bk:p:m:M:R:C:F:")) != -1) {
+    while ((c = getopt(argc, argv, "cq:r:g:G:s:bk:p:m:M:R:C:F:P:")) != -1) {
         char *end = NULL;
         long v;
         switch (c) {
@@ -398,6 +408,15 @@ static void parse_options(int argc, char *argv[], options *o)
             }
             o->rowmatch = (int)v;
             break;
+        case 'P':
+            /* 1 .. SAT_MAX_MATCHES, digits only */
+            v = strtol(optarg, &end, 10);
+            if (end == optarg || *end != '\0' || v < 1 || v > SAT_MAX_MATCHES) {
+                fprintf(stderr, "ERROR: -P needs an integer 1..%d (got '%s')\n", SAT_MAX_MATCHES, optarg);
+                usage(argv[0]);
+            }
+            o->polish = (int)v;
+            break;
         case 'R':
         case 'C':
             /* positive, digits only */
@@ -412,6 +431,13 @@ static void parse_options(int argc, char *argv[], options *o)
         default: usage(argv[0]);
         }
     }
+    if (o->polish && !o->use_gpu) die("ERROR: -P needs the GPU path\n");
+    if (o->polish && o->nmatch) die("ERROR: -P cannot be combined with -m\n");
+    if (o->polish && o->rowmatch) die("ERROR: -P cannot be combined with -M\n");
+    if (o->polish && o->cutoff) die("ERROR: -P cannot be combined with -p\n");
+    if (o->polish && o->fit) die("ERROR: -P cannot be combined with -F\n");
+    if (o->polish && o->topk <= 0) die("ERROR: -P needs -k K\n");
+    if (o->polish && !sat_multi_search_refine_polish) die("ERROR: this library has no sat_multi_search_refine_polish\n");
     if (o->cutoff && !o->use_gpu) die("ERROR: -p needs the GPU path\n");
     if (o->cutoff && o->nmatch) die("ERROR: -p cannot be combined with -m\n");
     if (o->cutoff && o->refine) die("ERROR: -p cannot be combined with -R\n");
@@ -420,9 +446,9 @@ static void parse_options(int argc, char *argv[], options *o)
     if (o->refine && !o->use_gpu) die("ERROR: -R needs the GPU path\n");
     if (o->refine && o->nmatch) die("ERROR: -R cannot be combined with -m\n");
     if (o->refine && o->topk <= 0) die("ERROR: -R needs -k K\n");
-    if (o->ncand && !o->refine) die("ERROR: -C needs -R\n");
-    if (o->refine && !o->ncand) o->ncand = o->topk;
-    if (o->refine && o->topk > o->ncand) die("ERROR: -k K (%d) exceeds -C C (%d)\n", o->topk, o->ncand);
+    if (o->ncand && !o->refine && !o->polish) die("ERROR: -C needs -R\n");
+    if ((o->refine || o->polish) && !o->ncand) o->ncand = o->topk;
+    if ((o->refine || o->polish) && o->topk > o->ncand) die("ERROR: -k K (%d) exceeds -C C (%d)\n", o->topk, o->ncand);
     if (o->refine && !sat_multi_search_refine) die("ERROR: this library has no sat_multi_search_refine\n");
     if (o->nmatch && !o->use_gpu) die("ERROR: -m needs the GPU path\n");
     if (o->nmatch && !sat_multi_search_matches) die("ERROR: this library has no sat_multi_search_matches\n");
@@ -782,6 +808,9 @@ static int search_batch(const options *o, const input *in, sat_multi *multi, gpu
         }
         return rc;
     }
+    if (o->polish)
+        return sat_multi_search_refine_polish(multi, lorder, lsoln, maxstart, o->ncand, o->refine ? o->refine : maxstart, o->polish,
+                                              B->kk, B->hits, B->hit_maps, NULL, NULL, ms);
     if (o->refine)
         return sat_multi_search_refine(multi, lorder, lsoln, maxstart, o->ncand, o->refine, B->kk, B->hits,
                                        B->hit_maps, NULL, ms, ms_stage2);
@@ -864,6 +893,9 @@ static int run_gpu(const options *o, const input *in)
     alloc_gpu_bufs(o, in, &B);
     const int total = in->db.count;
     int status = 0;
+    if (o->polish)
+        snprintf(polish_header, sizeof polish_header, "# POLISH tops = %d restarts = %d candidates = %d\n", o->polish,
+                 o->refine ? o->refine : o->maxstart, o->ncand);
     /* -F: every query's fit - from the GPUs with -k / -p, else made here from the listing's scores (the whole
      * database's, both size classes: a query's two blocks carry the same line) */
     sat_fit *fits = o->fit ? checked(calloc((size_t)in->num_queries, sizeof(sat_fit))) : NULL;
@@ -898,7 +930,10 @@ static int run_gpu(const options *o, const input *in)
             fprintf(stderr, "matches of the printed rows: %f ms\n", ms_rows);
         }
         fprintf(stderr, "GPU execution time %f ms\n", ms);
-        if (o->refine)
+        if (o->polish)
+            fprintf(stderr, "polish: %d candidates per query x %d restarts, %d maps each\n", o->ncand < total ? o->ncand : total,
+                    o->refine ? o->refine : o->maxstart, o->polish);
+        else if (o->refine)
             fprintf(stderr, "refine: stage 2 %f ms, %d candidates per query x %d restarts\n", ms_stage2,
                     o->ncand < total ? o->ncand : total, o->refine);
         fprintf(stderr, "%f million iterations/sec\n",

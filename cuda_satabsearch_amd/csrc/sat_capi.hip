@@ -987,8 +987,9 @@ int sat_pairs_collect(sat_ctx *ctx, int npairs, int32_t *scores, int32_t *ssemap
 // sat_ctx.hpp: queue a pair-match search on the context's stream.  The pair list is cut into launches of at most
 // `chunk` pairs whose record slabs stay under the 1 GiB scratch budget; each runs its record pass, the selection and
 // (maps) its map pass before the next one reuses the scratch.
+// polish (sat_polish.hip): the selection without the set test, and behind the map pass the polish of the picked maps.
 int sat_pair_matches_launch(sat_ctx *ctx, int lorder, int maxstart, int max_matches, bool maps, const int32_t *query,
-                            const int32_t *entry, int npairs)
+                            const int32_t *entry, int npairs, bool polish)
 {
     PairMatchPass pm{};
     int rc = match_args(ctx, max_matches, pm.mx);
@@ -1028,7 +1029,8 @@ int sat_pair_matches_launch(sat_ctx *ctx, int lorder, int maxstart, int max_matc
         (rc = ctx->d_psetw.grow_after(ctx->stream, (size_t)npairs)) != SAT_OK ||
         (rc = ctx->d_pmout.grow_after(ctx->stream, (size_t)npairs * (1 + 2 * M))) != SAT_OK ||
         (rc = ctx->d_bmap_slabs.grow_after(ctx->stream, slab_words * (size_t)chunk)) != SAT_OK ||
-        (maps && (rc = ctx->d_pmaps.grow_after(ctx->stream, (size_t)npairs * M * SAT_MAXDIM)) != SAT_OK))
+        (maps && (rc = ctx->d_pmaps.grow_after(ctx->stream, (size_t)npairs * M * SAT_MAXDIM)) != SAT_OK) ||
+        (polish && (rc = sat_polish_reserve(ctx, npairs)) != SAT_OK))
         return rc;
     HIP_TRY(hipMemcpyAsync(ctx->d_pitems.get(), items.data(), items.size() * sizeof(SatPairItem), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(ctx->d_psetw.get(), setw.data(), setw.size(), hipMemcpyHostToDevice, ctx->stream));
@@ -1048,11 +1050,21 @@ int sat_pair_matches_launch(sat_ctx *ctx, int lorder, int maxstart, int max_matc
         pm.mx.rec_slabs = ctx->d_bmap_slabs.get();
         if ((rc = launch_pair_pass(ctx, lorder, false, split, ctx->d_pitems.get(), ch.grp, rec_info, &pm)) != SAT_OK)
             return rc;
-        hipLaunchKernelGGL(pair_match_select, dim3((unsigned)ch.n), dim3(256), 0, ctx->stream, ch.p0, maxstart, max_matches,
-                           (const uint32_t *)ctx->d_bmap_slabs.get(), (uint32_t)slab_words, (const uint8_t *)ctx->d_psetw.get(),
-                           (const unsigned long long *)ctx->d_pkeys.get(), pm.mx.counts, pm.mx.scores, pm.mx.restarts);
-        HIP_TRY(hipGetLastError());
+        if (polish) {
+            if ((rc = sat_polish_select(ctx, ch.p0, ch.n, maxstart, max_matches, (uint32_t)slab_words, pm.mx.counts, pm.mx.scores,
+                                        pm.mx.restarts)) != SAT_OK)
+                return rc;
+        } else {
+            hipLaunchKernelGGL(pair_match_select, dim3((unsigned)ch.n), dim3(256), 0, ctx->stream, ch.p0, maxstart, max_matches,
+                               (const uint32_t *)ctx->d_bmap_slabs.get(), (uint32_t)slab_words, (const uint8_t *)ctx->d_psetw.get(),
+                               (const unsigned long long *)ctx->d_pkeys.get(), pm.mx.counts, pm.mx.scores, pm.mx.restarts);
+            HIP_TRY(hipGetLastError());
+        }
         if (maps && (rc = launch_pair_pass(ctx, lorder, true, 1, ctx->d_pitems.get(), ch.grp, map_info, &pm)) != SAT_OK)
+            return rc;
+        // the polish walks the launch's map items: one per pair, with its descriptor and entry
+        if (polish && (rc = sat_polish_run(ctx, lorder, ctx->d_pitems.get() + ch.grp.moff.front(), ch.n, max_matches, n2_all, npairs,
+                                           pm.mx.counts, pm.mx.scores, pm.mx.restarts, pm.mx.maps)) != SAT_OK)
             return rc;
     }
     char head[128];
@@ -1060,6 +1072,7 @@ int sat_pair_matches_launch(sat_ctx *ctx, int lorder, int maxstart, int max_matc
              chunks.size(), chunk);
     ctx->last_launch_info = head + rec_info + " | select";
     if (maps) ctx->last_launch_info += " | map pass: " + map_info;
+    if (polish) ctx->last_launch_info += " | polish";
     return SAT_OK;
 }
 

@@ -161,6 +161,11 @@ struct sat_ctx {
     std::vector<uint8_t> h_psetw;
     DevBuf<uint8_t> d_psetw;
     DevBuf<int32_t> d_pmout;
+    // polish (sat_search_pairs_polish, sat_polish.hip): score, base score, restart, moves [4][pairs]; the polished score
+    // as the high word of a pair key [pairs]; the winner's polished map [pairs][SAT_MAXDIM]
+    DevBuf<int32_t> d_polout;
+    DevBuf<unsigned long long> d_polkeys;
+    DevBuf<int8_t> d_polmaps;
     // refine (sat_search_refine, sat_topk.hip): the final ranking of the nq x C re-scored candidates
     DevBuf<unsigned long long> d_rkeys, d_rsorted;
     DevBuf<int32_t> d_rvals, d_rvals_sorted, d_rfirst, d_rmaps;
@@ -207,8 +212,21 @@ int sat_pairs_collect(sat_ctx *ctx, int npairs, int32_t *scores, int32_t *ssemap
 // the record pass, the selection and (maps) the map pass of every launch of the pair list on the context's stream;
 // then wait and copy the rows of pairs 0 .. npairs - 1 (ssemaps may be NULL).
 int sat_pair_matches_launch(sat_ctx *ctx, int lorder, int maxstart, int max_matches, bool maps, const int32_t *query,
-                            const int32_t *entry, int npairs);
+                            const int32_t *entry, int npairs, bool polish = false);
 int sat_pair_matches_collect(sat_ctx *ctx, int max_matches, int npairs, int32_t *counts, int32_t *scores, int32_t *restarts,
                              int32_t *ssemaps, const int32_t *query);
 // stage 1 of sat_search_refine: a plain search without LSOLN queued on the context's stream
 int sat_launch_plain(sat_ctx *ctx, int lorder, int maxstart);
+// Polish (sat_polish.hip), the hooks of sat_pair_matches_launch(polish = true) - max_matches is then the number of maps
+// per pair, with maps - and the second half of sat_search_pairs_polish: room for the outputs of `npairs` pairs; the
+// selection of pairs pair0 .. pair0 + n - 1 from the record slabs in ctx->d_bmap_slabs (the ranks go to counts / scores
+// / restarts as pair_match_select lays them out); the polish of the n pairs named by the launch's map items, entries of
+// up to n2max SSEs (outputs in ctx->d_polout / d_polkeys / d_polmaps, rows indexed by the pair); wait and copy the rows
+// of pairs 0 .. npairs - 1 (every output but scores may be NULL).
+int sat_polish_reserve(sat_ctx *ctx, int npairs);
+int sat_polish_select(sat_ctx *ctx, int pair0, int n, int maxstart, int tops, uint32_t slab_words, int32_t *counts,
+                      int32_t *scores, int32_t *restarts);
+int sat_polish_run(sat_ctx *ctx, int lorder, const SatPairItem *d_map_items, int n, int tops, int n2max, int npairs,
+                   const int32_t *counts, const int32_t *scores, const int32_t *restarts, const int8_t *maps);
+int sat_polish_collect(sat_ctx *ctx, int npairs, int32_t *scores, int32_t *base_scores, int32_t *restarts, int32_t *moves,
+                       int32_t *ssemaps, const int32_t *query);

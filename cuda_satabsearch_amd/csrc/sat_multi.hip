@@ -535,8 +535,61 @@ int sat_multi_search_pairs_matches(sat_multi *m, int lorder, int maxstart, int m
     return SAT_OK;
 }
 
-int sat_multi_search_refine(sat_multi *m, int lorder, int lsoln, int maxstart, int candidates, int refine_maxstart, int k,
-                            sat_hit *hits, int32_t *ssemaps, int32_t *first_scores, double *wall_ms, double *stage2_ms)
+int sat_multi_search_pairs_polish(sat_multi *m, int lorder, int maxstart, int tops, int npairs, const int32_t *query,
+                                  const int32_t *entry, int32_t *scores, int32_t *base_scores, int32_t *restarts, int32_t *moves,
+                                  int32_t *ssemaps, double *wall_ms)
+{
+    if (!m) return sat_fail(SAT_EINVAL, "null context");
+    if (npairs > 0 && !scores) return sat_fail(SAT_EINVAL, "scores buffer is null");
+    if (tops < 1 || tops > SAT_MAX_MATCHES) return sat_fail(SAT_EINVAL, "tops must be 1..%d (got %d)", SAT_MAX_MATCHES, tops);
+    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
+    if (m->ctx[0]->queries.empty()) return sat_fail(SAT_ESTATE, "no query set");
+    if (maxstart < 1) return sat_fail(SAT_EINVAL, "maxstart must be >= 1 (got %d)", maxstart);
+    if (npairs < 0 || (npairs > 0 && (!query || !entry))) return sat_fail(SAT_EINVAL, "bad pair list");
+    const int nq = (int)m->ctx[0]->queries.size();
+    const auto t0 = std::chrono::steady_clock::now();
+    // routed and put back as sat_multi_search_pairs_matches does
+    std::vector<std::vector<int32_t>> pq((size_t)m->ndev), pe((size_t)m->ndev), where((size_t)m->ndev);
+    for (int p = 0; p < npairs; p++) {
+        if (query[p] < 0 || query[p] >= nq) return sat_fail(SAT_EINVAL, "pair %d: query %d out of range", p, query[p]);
+        if (entry[p] < 0 || entry[p] >= m->n_entries) return sat_fail(SAT_EINVAL, "pair %d: entry %d out of range", p, entry[p]);
+        const int g = (int)(std::upper_bound(m->begin.begin(), m->begin.end(), entry[p]) - m->begin.begin()) - 1;
+        pq[(size_t)g].push_back(query[p]);
+        pe[(size_t)g].push_back(entry[p] - m->begin[(size_t)g]);
+        where[(size_t)g].push_back(p);
+    }
+    int rc = each_shard(m, [&](int g) {
+        return sat_pair_matches_launch(m->ctx[(size_t)g], lorder, maxstart, tops, true, pq[(size_t)g].data(), pe[(size_t)g].data(),
+                                       (int)pq[(size_t)g].size(), true);
+    });
+    if (rc != SAT_OK) return rc;
+    rc = each_shard(m, [&](int g) {
+        const size_t np = pq[(size_t)g].size();
+        std::vector<int32_t> out(4 * np), mp(ssemaps ? np * SAT_MAXDIM : 0);
+        const int r = sat_polish_collect(m->ctx[(size_t)g], (int)np, out.data(), out.data() + np, out.data() + 2 * np,
+                                         out.data() + 3 * np, ssemaps ? mp.data() : nullptr, pq[(size_t)g].data());
+        if (r != SAT_OK) return r;
+        for (size_t i = 0; i < np; i++) {
+            const size_t p = (size_t)where[(size_t)g][i];
+            scores[p] = out[i];
+            if (base_scores) base_scores[p] = out[np + i];
+            if (restarts) restarts[p] = out[2 * np + i];
+            if (moves) moves[p] = out[3 * np + i];
+            if (ssemaps) memcpy(ssemaps + p * SAT_MAXDIM, mp.data() + i * SAT_MAXDIM, SAT_MAXDIM * sizeof(int32_t));
+        }
+        return SAT_OK;
+    });
+    if (rc != SAT_OK) return rc;
+    if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return SAT_OK;
+}
+
+}  // extern "C"
+
+// sat_multi_search_refine (tops = 0) and sat_multi_search_refine_polish (tops = maps polished per candidate)
+static int multi_refine(sat_multi *m, int lorder, int lsoln, int maxstart, int candidates, int refine_maxstart, int tops, int k,
+                        sat_hit *hits, int32_t *ssemaps, int32_t *first_scores, int32_t *base_scores, double *wall_ms,
+                        double *stage2_ms)
 {
     if (!m) return sat_fail(SAT_EINVAL, "null context");
     if (!hits || k < 1) return sat_fail(SAT_EINVAL, "bad top-k arguments");
@@ -561,7 +614,7 @@ int sat_multi_search_refine(sat_multi *m, int lorder, int lsoln, int maxstart, i
     });
     if (rc != SAT_OK) return rc;
     // the global best C of every query, filed by shard as pairs
-    struct Cand { int g, local, first, second; };
+    struct Cand { int g, local, first, second, base; };
     std::vector<std::vector<Cand>> per_q((size_t)nq);
     std::vector<std::vector<int32_t>> pq((size_t)m->ndev), pe((size_t)m->ndev);
     std::vector<std::vector<std::pair<int, int>>> slot((size_t)m->ndev);     // (query, index in per_q) of each pair
@@ -572,12 +625,15 @@ int sat_multi_search_refine(sat_multi *m, int lorder, int lsoln, int maxstart, i
                          pq[(size_t)g].push_back(q);
                          pe[(size_t)g].push_back(h.entry);
                          slot[(size_t)g].push_back({ q, (int)per_q[(size_t)q].size() });
-                         per_q[(size_t)q].push_back({ g, h.entry, h.score, 0 });
+                         per_q[(size_t)q].push_back({ g, h.entry, h.score, 0, 0 });
                      });
     // stage 2: every shard re-scores its candidates (queued on all, then collected)
     const auto t2 = std::chrono::steady_clock::now();
     const bool maps = lsoln && ssemaps;
     rc = each_shard(m, [&](int g) {
+        if (tops)
+            return sat_pair_matches_launch(m->ctx[(size_t)g], lorder, refine_maxstart, tops, true, pq[(size_t)g].data(),
+                                           pe[(size_t)g].data(), (int)pq[(size_t)g].size(), true);
         return sat_pairs_launch(m->ctx[(size_t)g], lorder, refine_maxstart, maps, pq[(size_t)g].data(), pe[(size_t)g].data(),
                                 (int)pq[(size_t)g].size());
     });
@@ -587,12 +643,15 @@ int sat_multi_search_refine(sat_multi *m, int lorder, int lsoln, int maxstart, i
         for (int q = 0; q < nq; q++) cmaps[(size_t)q].resize(per_q[(size_t)q].size() * SAT_MAXDIM);
     rc = each_shard(m, [&](int g) {
         const size_t np = pq[(size_t)g].size();
-        std::vector<int32_t> sc(np), mp(maps ? np * SAT_MAXDIM : 0);
-        const int r = sat_pairs_collect(m->ctx[(size_t)g], (int)np, sc.data(), maps ? mp.data() : nullptr, pq[(size_t)g].data());
+        std::vector<int32_t> sc(np), bs(tops ? np : 0), mp(maps ? np * SAT_MAXDIM : 0);
+        const int r = tops ? sat_polish_collect(m->ctx[(size_t)g], (int)np, sc.data(), bs.data(), nullptr, nullptr,
+                                                maps ? mp.data() : nullptr, pq[(size_t)g].data())
+                           : sat_pairs_collect(m->ctx[(size_t)g], (int)np, sc.data(), maps ? mp.data() : nullptr, pq[(size_t)g].data());
         if (r != SAT_OK) return r;
         for (size_t p = 0; p < np; p++) {
             const auto &sl = slot[(size_t)g][p];
             per_q[(size_t)sl.first][(size_t)sl.second].second = sc[p];
+            if (tops) per_q[(size_t)sl.first][(size_t)sl.second].base = bs[p];
             if (maps) memcpy(cmaps[(size_t)sl.first].data() + (size_t)sl.second * SAT_MAXDIM, mp.data() + p * SAT_MAXDIM, sizeof(int32_t) * SAT_MAXDIM);
         }
         return SAT_OK;
@@ -623,12 +682,31 @@ int sat_multi_search_refine(sat_multi *m, int lorder, int lsoln, int maxstart, i
             h.pvalue = sat_pv_gumbel(h.zscore);
             hits[(size_t)q * k + r] = h;
             if (first_scores) first_scores[(size_t)q * k + r] = x.first;
+            if (base_scores) base_scores[(size_t)q * k + r] = x.base;
             if (maps) memcpy(ssemaps + ((size_t)q * k + r) * SAT_MAXDIM, cmaps[(size_t)q].data() + (size_t)order[(size_t)r] * SAT_MAXDIM,
                              sizeof(int32_t) * SAT_MAXDIM);
         }
     }
     if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return k;
+}
+
+extern "C" {
+
+int sat_multi_search_refine(sat_multi *m, int lorder, int lsoln, int maxstart, int candidates, int refine_maxstart, int k,
+                            sat_hit *hits, int32_t *ssemaps, int32_t *first_scores, double *wall_ms, double *stage2_ms)
+{
+    return multi_refine(m, lorder, lsoln, maxstart, candidates, refine_maxstart, 0, k, hits, ssemaps, first_scores, nullptr, wall_ms,
+                        stage2_ms);
+}
+
+int sat_multi_search_refine_polish(sat_multi *m, int lorder, int lsoln, int maxstart, int candidates, int refine_maxstart, int tops,
+                                   int k, sat_hit *hits, int32_t *ssemaps, int32_t *first_scores, int32_t *base_scores,
+                                   double *wall_ms)
+{
+    if (tops < 1 || tops > SAT_MAX_MATCHES) return sat_fail(SAT_EINVAL, "tops must be 1..%d (got %d)", SAT_MAX_MATCHES, tops);
+    return multi_refine(m, lorder, lsoln, maxstart, candidates, refine_maxstart, tops, k, hits, ssemaps, first_scores, base_scores,
+                        wall_ms, nullptr);
 }
 
 int sat_multi_hits_cutoff(sat_multi *m, double max_pvalue, int max_rows, int32_t *counts, int capacity, sat_hit *hits,

@@ -1,0 +1,387 @@
+// sat_polish.hip - polish of the best restarts' maps (sat_search_pairs_polish and its refine / multi-GPU forms,
+// include/satabsearch.h).
+//
+// The pair-match mode's record pass files the own best s_r of every restart of a pair; its map pass re-runs chosen
+// restarts for their own-best maps.  Between the two, pair_polish_select takes the T largest keys (s_r, ~r) of a pair -
+// pair_match_select without the set test -, and behind them pair_polish climbs from each of the T maps to a local
+// optimum of the search's neighbourhood by best improvement and reports the best of the T results.  Both kernels and
+// their launch code live here; sat_capi.hip only calls them from sat_pair_matches_launch.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+#include <vector>
+
+#include "sat_ctx.hpp"
+
+namespace {
+
+// ---------------------------------------------------------------- selection
+// One workgroup per pair of a launch, over the pair's record slab (restart-major: the R own bests first; the set words
+// behind them are not read).  Round t takes the largest key below the one taken before - keys are distinct, their low
+// word is the restart - so rank t holds the t-th restart by descending (s_r, -r).  Same outputs as pair_match_select:
+// counts[pair] = min(T, R), or -1 when rank 0 is not the arg-max key the record pass folded into keys[pair]; scores /
+// restarts [pair][T], 0 / -1 past the count.
+__global__ void __launch_bounds__(256) pair_polish_select(int pair0, int R, int T, const uint32_t *slabs, uint32_t slab_words,
+                                                          const unsigned long long *keys, int32_t *counts, int32_t *scores,
+                                                          int32_t *restarts)
+{
+    __shared__ unsigned long long red[4];
+    const int p = pair0 + (int)blockIdx.x;
+    const uint32_t *rec = slabs + (size_t)blockIdx.x * slab_words;
+    const int t = (int)threadIdx.x, wave = t >> 6;
+    unsigned long long prev = ~0ull, first = 0ull;
+    int m = 0;
+    for (int round = 0; round < T; round++) {
+        __syncthreads();                               // `red` is free again
+        unsigned long long k = 0ull;
+        for (int r = t; r < R; r += 256) {
+            const int s = (int)rec[r];
+            const unsigned long long rk = (((unsigned long long)(uint32_t)(s + 0x40000000)) << 32) | (0xFFFFFFFFu - (uint32_t)r);
+            k = (rk < prev && rk > k) ? rk : k;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const unsigned long long other = __shfl_xor(k, off, 64);
+            k = other > k ? other : k;
+        }
+        if ((t & 63) == 0) red[wave] = k;
+        __syncthreads();
+        unsigned long long cur = red[0];
+        for (int w = 1; w < 4; w++) cur = red[w] > cur ? red[w] : cur;
+        if (cur == 0ull) break;                        // (the same for every thread: fewer than T restarts)
+        if (round == 0) first = cur;
+        if (t == 0) {
+            scores[(size_t)p * T + m] = (int32_t)(uint32_t)(cur >> 32) - 0x40000000;
+            restarts[(size_t)p * T + m] = (int32_t)(0xFFFFFFFFu - (uint32_t)(cur & 0xFFFFFFFFu));
+        }
+        prev = cur;
+        m++;
+    }
+    if (t == 0) {
+        counts[p] = first == keys[p] ? m : -1;
+        for (int x = m; x < T; x++) {
+            scores[(size_t)p * T + x] = 0;
+            restarts[(size_t)p * T + x] = -1;
+        }
+    }
+}
+
+// ---------------------------------------------------------------- polish
+struct PolishArgs {
+    const SatPairItem *items;     // the launch's map items: one per pair (pair, descriptor, entry)
+    const SatQuery *desc;
+    const int32_t *orders;
+    const int64_t *cell_off;
+    const uint8_t *tab_tri;
+    const float *dist_tri;
+    const int32_t *counts;        // [pairs]        ranks the selection filled
+    const int32_t *scores;        // [pairs][T]     s_r of rank t
+    const int32_t *restarts;      // [pairs][T]
+    const int8_t *maps;           // [pairs][T][SAT_MAXDIM] own-best map of rank t (the map pass)
+    int32_t T, lorder;
+    int32_t n2max;                // the LDS carve holds the triangle of an entry of up to n2max SSEs
+    int32_t npairs;               // row length of `out`
+    int32_t *out;                 // [4][npairs]: score, base score, restart, moves (-1: error)
+    unsigned long long *okeys;    // [pairs] (score + 2^30) << 32, the high word of a pair key (the refine ranking's)
+    int8_t *omaps;                // [pairs][SAT_MAXDIM] the winner's polished map, -1 = unmatched
+};
+
+constexpr int kListStride = 112;   // entries of a wave's map / matched list in LDS (SAT_MAXDIM rounded up)
+
+__host__ __device__ inline uint32_t polish_cells(int n2) { return ((uint32_t)n2 * (uint32_t)(n2 + 1) / 2u + 15u) & ~15u; }
+// LDS: distances [cells] f32 | codes [cells] | db types [112] | query types [112] | per wave: matched list, query
+// distances and query codes of the row in hand [3][112] u32 | per wave: map [112] i8 | per wave: polished score, moves
+__host__ __device__ inline uint32_t polish_lds_bytes(int n2max, int T)
+{
+    return polish_cells(n2max) * 5u + 2u * kListStride + (uint32_t)T * (kListStride * 13u + 8u);
+}
+
+// the lanes of a wave exchange data through LDS (DS operations of one wave execute in order)
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// One workgroup per pair, wave t polishes the map of rank t: the T maps of a pair share the entry, whose packed
+// triangle is staged once (cleaned as the SA kernel cleans it: NaN / inf become the sentinel that never passes the
+// distance test).  A round of a wave walks the query SSEs i (wave-uniform); the lanes are the db SSEs j (two trips
+// above 64) and sum row(i, j | m) over the matched list with satk::pair_term - the SA kernel's arithmetic for one
+// cell pair.  The query cells {distance, code} of row i against the matched list come from the blob's dense array: lane x
+// loads the cell of the list's x-th SSE one row ahead (the load of row i + 1 flies under the sums of row i) and files it
+// in LDS beside the list, so the sum reads three broadcast words per term and no load depends on another.  Every round
+// recomputes every row: a map costs (moves + 1) x n1 x matched terms per lane, and the waves of the slowest maps are
+// what a launch waits for (DESIGN.md 6h has the figures and the row table that would make later rounds cheap).
+// The diagonal cell of the dense array is the query's sentinel, so the list's own entry for i adds 0 and needs no test.
+// The old row is the lane j = m[i].  Each lane keeps its largest key (delta, ~i, ~(j + 1)) over the round, one
+// butterfly reduces them, the move is applied and the matched list rebuilt by ballot compaction.  No atomics, no 64-bit
+// LDS values.  Scores lie in [-n1 (n1 - 1), n1 (n1 - 1)] and every move gains at least 1, so 2 n1 (n1 - 1) + 1 rounds
+// always reach a round without a move; a wave that does not is reported (moves = -1) instead of spinning.
+__global__ void __launch_bounds__(64 * SAT_MAX_MATCHES) pair_polish(const PolishArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6, nthreads = (int)blockDim.x;
+    const int T = a.T;
+    const uint32_t cells = polish_cells(a.n2max);
+    float *distL = reinterpret_cast<float *>(lds);
+    uint8_t *codeL = lds + (size_t)cells * 4u;
+    uint8_t *type2 = codeL + cells;
+    uint8_t *qtypeL = type2 + kListStride;
+    uint32_t *listL = reinterpret_cast<uint32_t *>(qtypeL + kListStride) + (size_t)w * 3u * kListStride;
+    uint32_t *qdL = listL + kListStride, *qcL = qdL + kListStride;
+    int8_t *mapsL = reinterpret_cast<int8_t *>(qtypeL + kListStride + (size_t)T * kListStride * 12u);
+    int8_t *mapL = mapsL + (size_t)w * kListStride;
+    int32_t *resL = reinterpret_cast<int32_t *>(mapsL + (size_t)T * kListStride);       // [T] scores, [T] moves
+
+    const SatPairItem it = a.items[blockIdx.x];
+    const int p = it.pair;
+    const SatQuery Q = a.desc[it.desc];
+    const int n1 = Q.n1, n1p = n1 <= 16 ? 16 : (n1 <= 32 ? 32 : (n1 <= 64 ? 64 : 112));
+    const int e = it.entry, n2 = a.orders[e];
+    const int count = a.counts[p];
+    const bool sane = n2 >= 1 && n2 <= a.n2max && n1 >= 1 && n1 <= SAT_K_MAXDIM && count >= 1 && count <= T;
+
+    if (sane) {
+        const uint8_t *tt = a.tab_tri + a.cell_off[e];
+        const float *dd = a.dist_tri + a.cell_off[e];
+        const int ncell = (n2 * (n2 + 1)) >> 1;
+        for (int c = tid; c < ncell; c += nthreads) {
+            const float v = dd[c];
+            distL[c] = fabsf(v) <= 3.0e38f ? v : SAT_K_DSENT;
+            codeL[c] = tt[c];
+        }
+        for (int j = tid; j < n2; j += nthreads) type2[j] = tt[((j * (j + 1)) >> 1) + j] & 3u;
+        for (int i = tid; i < n1; i += nthreads) qtypeL[i] = Q.qtypes[i];
+    }
+    __syncthreads();
+
+    if (sane && w < count) {
+        const uint2 *qpair = Q.qpair;
+        const int8_t *src = a.maps + ((size_t)p * T + w) * SAT_MAXDIM;
+        for (int i = lane; i < kListStride; i += 64) mapL[i] = i < n1 ? src[i] : (int8_t)-1;
+        wave_sync();
+        // occupied db SSEs (wave-uniform): bit j of occ[j >> 6]
+        unsigned long long occ[2] = { 0ull, 0ull };
+        for (int i = 0; i < n1; i++) {
+            const int j = mapL[i];
+            if (j >= 0 && j < n2) occ[j >> 6] |= 1ull << (j & 63);
+        }
+        int score = a.scores[(size_t)p * T + w], moves = 0;
+        const int cap = 2 * n1 * (n1 - 1) + 1;
+        const bool two = n2 > 64;
+        const int j0 = lane, j1 = lane + 64;
+        const int a0 = min(j0, n2 - 1), a1 = min(j1, n2 - 1);              // addressing only: lanes past n2 are masked
+        const uint32_t t0 = type2[a0], t1 = type2[a1];
+        bool done = false;
+        for (int round = 0; round < cap && !done; round++) {
+            // the matched list (k, m[k]), ascending k
+            int nm = 0;
+            for (int trip = 0; trip < 2; trip++) {
+                const int k = lane + 64 * trip;
+                const int l = min((int)mapL[min(k, kListStride - 1)], n2 - 1);      // (an image is below n2: the clamp guards the cell index)
+                const bool on = k < n1 && l >= 0;
+                const unsigned long long mask = __builtin_amdgcn_ballot_w64(on);
+                const int pos = nm + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+                if (on) listL[pos] = (uint32_t)k | ((uint32_t)l << 8);
+                nm += __popcll(mask);
+            }
+            wave_sync();
+            // lane x serves the list's x-th and (x + 64)-th SSE: their cells of row 0 are on the way
+            const bool has0 = lane < nm, has1 = lane + 64 < nm;
+            const int kx0 = has0 ? (int)(listL[lane] & 0xFFu) : 0, kx1 = has1 ? (int)(listL[lane + 64] & 0xFFu) : 0;
+            uint2 nxt0 = qpair[kx0], nxt1 = qpair[kx1];
+            unsigned long long best = 0ull;
+            for (int i = 0; i < n1; i++) {
+                wave_sync();                               // the sums of the row before have read its cells
+                if (has0) { qdL[lane] = nxt0.x; qcL[lane] = nxt0.y; }
+                if (has1) { qdL[lane + 64] = nxt1.x; qcL[lane + 64] = nxt1.y; }
+                const int inext = min(i + 1, n1 - 1) * n1p;
+                nxt0 = qpair[inext + kx0];
+                nxt1 = qpair[inext + kx1];
+                wave_sync();
+                const int old = mapL[i];
+                const uint32_t qt = qtypeL[i];
+                int row0 = 0, row1 = 0, lo = -1, hi = n2;
+#pragma unroll 4
+                for (int x = 0; x < nm; x++) {
+                    const uint32_t ent = listL[x], qd = qdL[x], qc = qcL[x];
+                    const int k = (int)(ent & 0xFFu), l = (int)(ent >> 8);
+                    lo = k < i ? max(lo, l) : lo;
+                    hi = k > i ? min(hi, l) : hi;
+                    const int c0 = satk::tri_index(a0, l);
+                    row0 += satk::pair_term(qd, qc, __float_as_uint(distL[c0]), codeL[c0]);
+                    if (two) {
+                        const int c1 = satk::tri_index(a1, l);
+                        row1 += satk::pair_term(qd, qc, __float_as_uint(distL[c1]), codeL[c1]);
+                    }
+                }
+                const int from0 = __shfl(row0, old & 63, 64), from1 = __shfl(row1, old & 63, 64);
+                const int oldrow = old < 0 ? 0 : (old < 64 ? from0 : from1);
+                const bool window0 = !a.lorder || (j0 > lo && j0 < hi), window1 = !a.lorder || (j1 > lo && j1 < hi);
+                const bool ok0 = j0 < n2 && t0 == qt && !((occ[0] >> lane) & 1ull) && window0;
+                const bool ok1 = two && j1 < n2 && t1 == qt && !((occ[1] >> lane) & 1ull) && window1;
+                const unsigned long long ikey = (unsigned long long)(0xFFFFu - (uint32_t)i) << 16;
+                const int d0 = row0 - oldrow, d1 = row1 - oldrow, du = -oldrow;
+                unsigned long long key = 0ull;
+                if (old >= 0 && du > 0) key = ((unsigned long long)(uint32_t)du << 32) | ikey | 0xFFFFull;            // j = -1
+                if (ok0 && d0 > 0) {
+                    const unsigned long long k0 = ((unsigned long long)(uint32_t)d0 << 32) | ikey | (0xFFFFull - (unsigned)(j0 + 1));
+                    key = k0 > key ? k0 : key;
+                }
+                if (ok1 && d1 > 0) {
+                    const unsigned long long k1 = ((unsigned long long)(uint32_t)d1 << 32) | ikey | (0xFFFFull - (unsigned)(j1 + 1));
+                    key = k1 > key ? k1 : key;
+                }
+                best = key > best ? key : best;
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const unsigned long long other = __shfl_xor(best, off, 64);
+                best = other > best ? other : best;
+            }
+            if (best == 0ull) {
+                done = true;
+            } else {
+                const int bi = (int)(0xFFFFu - (uint32_t)((best >> 16) & 0xFFFFu));
+                const int bj = (int)(0xFFFFu - (uint32_t)(best & 0xFFFFu)) - 1;
+                const int old = mapL[bi];
+                if (old >= 0) occ[old >> 6] &= ~(1ull << (old & 63));
+                if (bj >= 0) occ[bj >> 6] |= 1ull << (bj & 63);
+                wave_sync();                               // every lane has read the old image
+                if (lane == 0) mapL[bi] = (int8_t)bj;
+                wave_sync();
+                score += (int)(uint32_t)(best >> 32);
+                moves++;
+            }
+        }
+        if (lane == 0) {
+            resL[w] = score;
+            resL[T + w] = done ? moves : -1;
+        }
+    }
+    __syncthreads();
+
+    // the pair's winner: the largest polished score, ties to the lowest rank
+    if (w == 0) {
+        int win = -1, bad = sane ? 0 : 1;
+        if (sane) {
+            win = 0;
+            for (int t = 0; t < count; t++) {
+                if (resL[T + t] < 0) bad = 1;
+                if (resL[t] > resL[win]) win = t;
+            }
+        }
+        const bool ok = !bad;
+        if (lane == 0) {
+            const int32_t s = ok ? resL[win] : 0;
+            a.out[p] = s;
+            a.out[(size_t)a.npairs + p] = ok ? a.scores[(size_t)p * T] : 0;
+            a.out[2 * (size_t)a.npairs + p] = ok ? a.restarts[(size_t)p * T + win] : -1;
+            a.out[3 * (size_t)a.npairs + p] = ok ? resL[T + win] : -1;
+            a.okeys[p] = ((unsigned long long)(uint32_t)(s + 0x40000000)) << 32;
+        }
+        const int8_t *wm = mapsL + (size_t)(ok ? win : 0) * kListStride;
+        for (int i = lane; i < SAT_MAXDIM; i += 64) a.omaps[(size_t)p * SAT_MAXDIM + i] = (ok && i < n1) ? wm[i] : (int8_t)-1;
+    }
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------- launch code (sat_ctx.hpp)
+
+int sat_polish_reserve(sat_ctx *ctx, int npairs)
+{
+    int rc;
+    if ((rc = ctx->d_polout.grow_after(ctx->stream, 4 * (size_t)npairs)) != SAT_OK ||
+        (rc = ctx->d_polkeys.grow_after(ctx->stream, (size_t)npairs)) != SAT_OK ||
+        (rc = ctx->d_polmaps.grow_after(ctx->stream, (size_t)npairs * SAT_MAXDIM)) != SAT_OK)
+        return rc;
+    return SAT_OK;
+}
+
+int sat_polish_select(sat_ctx *ctx, int pair0, int n, int maxstart, int tops, uint32_t slab_words, int32_t *counts,
+                      int32_t *scores, int32_t *restarts)
+{
+    hipLaunchKernelGGL(pair_polish_select, dim3((unsigned)n), dim3(256), 0, ctx->stream, pair0, maxstart, tops,
+                       (const uint32_t *)ctx->d_bmap_slabs.get(), slab_words, (const unsigned long long *)ctx->d_pkeys.get(),
+                       counts, scores, restarts);
+    HIP_TRY(hipGetLastError());
+    return SAT_OK;
+}
+
+int sat_polish_run(sat_ctx *ctx, int lorder, const SatPairItem *d_map_items, int n, int tops, int n2max, int npairs,
+                   const int32_t *counts, const int32_t *scores, const int32_t *restarts, const int8_t *maps)
+{
+    PolishArgs a{};
+    a.items = d_map_items;
+    a.desc = ctx->d_qdesc.get();
+    a.orders = ctx->d_orders.get();
+    a.cell_off = ctx->d_cell_off.get();
+    a.tab_tri = ctx->d_tab.get();
+    a.dist_tri = ctx->d_dist.get();
+    a.counts = counts;
+    a.scores = scores;
+    a.restarts = restarts;
+    a.maps = maps;
+    a.T = tops;
+    a.lorder = lorder ? 1 : 0;
+    a.n2max = n2max;
+    a.npairs = npairs;
+    a.out = ctx->d_polout.get();
+    a.okeys = ctx->d_polkeys.get();
+    a.omaps = ctx->d_polmaps.get();
+    hipLaunchKernelGGL(pair_polish, dim3((unsigned)n), dim3(64u * (unsigned)tops), polish_lds_bytes(n2max, tops), ctx->stream, a);
+    HIP_TRY(hipGetLastError());
+    return SAT_OK;
+}
+
+// wait for the polish and copy its rows: 16 * npairs bytes, + SAT_MAXDIM * npairs with maps
+int sat_polish_collect(sat_ctx *ctx, int npairs, int32_t *scores, int32_t *base_scores, int32_t *restarts, int32_t *moves,
+                       int32_t *ssemaps, const int32_t *query)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (npairs == 0) return SAT_OK;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const size_t P = (size_t)npairs;
+    std::vector<int32_t> out(4 * P);
+    HIP_TRY(hipMemcpy(out.data(), ctx->d_polout.get(), out.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    ctx->d2h_bytes += out.size() * sizeof(int32_t);
+    for (size_t p = 0; p < P; p++)
+        if (out[3 * P + p] < 0)
+            return sat_fail(SAT_EDEVICE, "pair %zu: the polish did not finish (records and arg-max key disagree, or the move cap was reached)", p);
+    memcpy(scores, out.data(), P * sizeof(int32_t));
+    if (base_scores) memcpy(base_scores, out.data() + P, P * sizeof(int32_t));
+    if (restarts) memcpy(restarts, out.data() + 2 * P, P * sizeof(int32_t));
+    if (moves) memcpy(moves, out.data() + 3 * P, P * sizeof(int32_t));
+    if (ssemaps) {
+        std::vector<int8_t> mp(P * SAT_MAXDIM);
+        HIP_TRY(hipMemcpy(mp.data(), ctx->d_polmaps.get(), mp.size(), hipMemcpyDeviceToHost));
+        ctx->d2h_bytes += mp.size();
+        for (size_t p = 0; p < P; p++) {
+            const int n1 = ctx->queries[(size_t)query[p]].n1;
+            for (int i = 0; i < SAT_MAXDIM; i++) ssemaps[p * SAT_MAXDIM + i] = i < n1 ? mp[p * SAT_MAXDIM + i] : -1;
+        }
+    }
+    return SAT_OK;
+}
+
+extern "C" int sat_search_pairs_polish(sat_ctx *ctx, int lorder, int maxstart, int tops, int npairs, const int32_t *query,
+                                       const int32_t *entry, int32_t *scores, int32_t *base_scores, int32_t *restarts,
+                                       int32_t *moves, int32_t *ssemaps, double *kernel_ms)
+{
+    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
+    if (npairs > 0 && !scores) return sat_fail(SAT_EINVAL, "scores buffer is null");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    const int rc = sat_pair_matches_launch(ctx, lorder, maxstart, tops, true, query, entry, npairs, true);
+    if (rc != SAT_OK) return rc;
+    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (kernel_ms) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+        *kernel_ms = ms;
+    }
+    return sat_polish_collect(ctx, npairs, scores, base_scores, restarts, moves, ssemaps, query);
+}

@@ -187,7 +187,8 @@ __global__ void pack_refined(const unsigned long long *pkeys, const sat_hit *can
 // one thread per (query, rank) of the refined rows: the statistics of the stage-2 score, the stage-1 score and map
 __global__ void finish_refined(const unsigned long long *sorted, const int32_t *vals, int c, int k, int nq, const int32_t *orders,
                                const HitQuery *queries, const double *ztab, const double *ptab, const sat_hit *cand,
-                               const int8_t *pmaps, sat_hit *hits, int32_t *first, int32_t *maps)
+                               const int8_t *pmaps, sat_hit *hits, int32_t *first, int32_t *maps, const int32_t *pbase,
+                               int32_t *base)
 {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nq * k) return;
@@ -199,6 +200,7 @@ __global__ void finish_refined(const unsigned long long *sorted, const int32_t *
     const int n1 = queries[q].n1;
     hits[t] = hit_row(entry, score, n1, orders[entry], ztab, ptab, queries[q].fit);
     first[t] = cand[p].score;
+    if (base) base[t] = pbase[p];                        // polish: the pair's score before it
     if (maps) {
         int32_t *out = maps + (size_t)t * SAT_MAXDIM;
         const int8_t *src = pmaps + (size_t)p * SAT_MAXDIM;
@@ -497,8 +499,10 @@ extern "C" int sat_topk_hits(sat_ctx *ctx, int k, sat_hit *hits, int32_t *ssemap
     return k;
 }
 
-extern "C" int sat_search_refine(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int candidates, int refine_maxstart,
-                                 int k, sat_hit *hits, int32_t *ssemaps, int32_t *first_scores)
+// sat_search_refine (tops = 0) and sat_search_refine_polish (tops = maps polished per candidate): the stage-2 keys and
+// maps come from the pair search or from the polish (sat_polish.hip), everything around them is shared
+static int refine(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int candidates, int refine_maxstart, int tops,
+                  int k, sat_hit *hits, int32_t *ssemaps, int32_t *first_scores, int32_t *base_scores)
 {
     if (!ctx) return sat_fail(SAT_EINVAL, "null context");
     if (!hits || k < 1) return sat_fail(SAT_EINVAL, "bad top-k arguments");
@@ -524,7 +528,11 @@ extern "C" int sat_search_refine(sat_ctx *ctx, int lorder, int lsoln, int maxsta
     for (int p = 0; p < npairs; p++) query[(size_t)p] = p / c;
     // stage 2: the candidates at refine_maxstart (and their maps)
     const bool maps = lsoln && ssemaps;
-    if ((rc = sat_pairs_launch(ctx, lorder, refine_maxstart, maps, query.data(), entry.data(), npairs)) != SAT_OK) return rc;
+    rc = tops ? sat_pair_matches_launch(ctx, lorder, refine_maxstart, tops, true, query.data(), entry.data(), npairs, true)
+              : sat_pairs_launch(ctx, lorder, refine_maxstart, maps, query.data(), entry.data(), npairs);
+    if (rc != SAT_OK) return rc;
+    const unsigned long long *pkeys = tops ? ctx->d_polkeys.get() : ctx->d_pkeys.get();
+    const int8_t *pmaps = tops ? ctx->d_polmaps.get() : ctx->d_pmaps.get();
     const std::string stage2_info = ctx->last_launch_info;
     // the final ranking: segments of c keys, one per query
     if ((rc = ctx->d_rkeys.grow((size_t)npairs)) != SAT_OK) return rc;
@@ -532,7 +540,7 @@ extern "C" int sat_search_refine(sat_ctx *ctx, int lorder, int lsoln, int maxsta
     if ((rc = ctx->d_rvals.grow((size_t)npairs)) != SAT_OK) return rc;
     if ((rc = ctx->d_rvals_sorted.grow((size_t)npairs)) != SAT_OK) return rc;
     if ((rc = ctx->d_rhits.grow((size_t)nq * k)) != SAT_OK) return rc;
-    if ((rc = ctx->d_rfirst.grow((size_t)nq * k)) != SAT_OK) return rc;
+    if ((rc = ctx->d_rfirst.grow(2 * (size_t)nq * k)) != SAT_OK) return rc;      // stage-1 scores, then (polish) base scores
     if (maps && (rc = ctx->d_rmaps.grow((size_t)nq * k * SAT_MAXDIM)) != SAT_OK) return rc;
     if ((rc = ctx->d_seg.grow((size_t)nq + 1)) != SAT_OK) return rc;
     std::vector<int> seg((size_t)nq + 1);
@@ -540,7 +548,7 @@ extern "C" int sat_search_refine(sat_ctx *ctx, int lorder, int lsoln, int maxsta
     for (int q = 0; q <= nq; q++) seg[(size_t)q] = q * c;
     HIP_TRY(hipMemcpyAsync(ctx->d_seg.get(), seg.data(), seg.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     if ((rc = upload_hit_queries(ctx, 0, nq, false, hq)) != SAT_OK) return rc;
-    hipLaunchKernelGGL(pack_refined, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_pkeys.get(), ctx->d_hits.get(),
+    hipLaunchKernelGGL(pack_refined, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, ctx->stream, pkeys, ctx->d_hits.get(),
                        npairs, ctx->d_rkeys.get(), ctx->d_rvals.get());
     HIP_TRY(hipGetLastError());
     size_t temp_bytes = 0;
@@ -553,11 +561,24 @@ extern "C" int sat_search_refine(sat_ctx *ctx, int lorder, int lsoln, int maxsta
                                                                  npairs, nq, ctx->d_seg.get(), ctx->d_seg.get() + 1, 0, 64, ctx->stream));
     hipLaunchKernelGGL(finish_refined, dim3((unsigned)((nq * k + 127) / 128)), dim3(128), 0, ctx->stream, ctx->d_rsorted.get(),
                        ctx->d_rvals_sorted.get(), c, k, nq, ctx->d_orders.get(), hit_queries(ctx), ctx->d_gumbel_z.get(),
-                       ctx->d_gumbel_p.get(), ctx->d_hits.get(), ctx->d_pmaps.get(), ctx->d_rhits.get(), ctx->d_rfirst.get(),
-                       maps ? ctx->d_rmaps.get() : nullptr);
+                       ctx->d_gumbel_p.get(), ctx->d_hits.get(), pmaps, ctx->d_rhits.get(), ctx->d_rfirst.get(),
+                       maps ? ctx->d_rmaps.get() : nullptr, tops ? (const int32_t *)ctx->d_polout.get() + npairs : nullptr,
+                       tops ? ctx->d_rfirst.get() + (size_t)nq * k : nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     const size_t rows = (size_t)nq * k;
+    if (tops) {
+        // a pair whose polish did not finish carries moves = -1 (sat_polish.hip): one flag row, npairs ints
+        std::vector<int32_t> mv((size_t)npairs);
+        HIP_TRY(hipMemcpy(mv.data(), ctx->d_polout.get() + 3 * (size_t)npairs, mv.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        ctx->d2h_bytes += mv.size() * sizeof(int32_t);
+        for (int p = 0; p < npairs; p++)
+            if (mv[(size_t)p] < 0) return sat_fail(SAT_EDEVICE, "pair %d: the polish did not finish", p);
+        if (base_scores) {
+            HIP_TRY(hipMemcpy(base_scores, ctx->d_rfirst.get() + rows, rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+            ctx->d2h_bytes += rows * sizeof(int32_t);
+        }
+    }
     HIP_TRY(hipMemcpy(hits, ctx->d_rhits.get(), rows * sizeof(sat_hit), hipMemcpyDeviceToHost));
     ctx->d2h_bytes += rows * sizeof(sat_hit);
     if (first_scores) {
@@ -570,6 +591,20 @@ extern "C" int sat_search_refine(sat_ctx *ctx, int lorder, int lsoln, int maxsta
     }
     ctx->last_launch_info = "stage 1: " + stage1_info + " || stage 2: " + stage2_info;
     return k;
+}
+
+extern "C" int sat_search_refine(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int candidates, int refine_maxstart,
+                                 int k, sat_hit *hits, int32_t *ssemaps, int32_t *first_scores)
+{
+    return refine(ctx, lorder, lsoln, maxstart, candidates, refine_maxstart, 0, k, hits, ssemaps, first_scores, nullptr);
+}
+
+extern "C" int sat_search_refine_polish(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int candidates, int refine_maxstart,
+                                        int tops, int k, sat_hit *hits, int32_t *ssemaps, int32_t *first_scores,
+                                        int32_t *base_scores)
+{
+    if (tops < 1 || tops > SAT_MAX_MATCHES) return sat_fail(SAT_EINVAL, "tops must be 1..%d (got %d)", SAT_MAX_MATCHES, tops);
+    return refine(ctx, lorder, lsoln, maxstart, candidates, refine_maxstart, tops, k, hits, ssemaps, first_scores, base_scores);
 }
 
 // ---- p-value cutoff.  ctx->d_seg holds, in ints: [nq] the count pass's counts, then for the chunk at hand its

@@ -60,6 +60,21 @@ def _search_pairs_matches(obj, fn, handle, queries, entries, max_matches, lorder
     return counts, scores, restarts, (ssemaps[..., :obj.n1max] if maps else None), ms.value
 
 
+def _search_pairs_polish(obj, fn, handle, queries, entries, tops, lorder, maxstart):
+    """shared by Searcher / MultiSearcher.search_pairs_polish"""
+    q = np.ascontiguousarray(queries, dtype=np.int32).ravel()
+    e = np.ascontiguousarray(entries, dtype=np.int32).ravel()
+    if q.shape != e.shape:
+        raise ValueError("queries and entries differ in length")
+    p = len(q)
+    scores, base, restarts, moves = (np.zeros(p, np.int32) for _ in range(4))
+    ssemaps = np.full((p, MAXDIM), -1, np.int32)
+    ms = C.c_double(0.0)
+    obj._check(fn(handle, int(bool(lorder)), int(maxstart), int(tops), p, q.ctypes.data, e.ctypes.data, scores.ctypes.data,
+                  base.ctypes.data, restarts.ctypes.data, moves.ctypes.data, ssemaps.ctypes.data, C.byref(ms)))
+    return scores, base, restarts, moves, ssemaps[:, :getattr(obj, "n1max", MAXDIM)], ms.value
+
+
 # struct sat_hit (include/satabsearch.h) as a numpy record: the rows of topk_hits, search_topk and search_refine
 _HIT_DTYPE = np.dtype([("entry", np.int32), ("score", np.int32), ("norm2", np.float64), ("zscore", np.float64),
                        ("pvalue", np.float64)], align=True)
@@ -107,6 +122,18 @@ def _search_refine(obj, call, k, candidates, refine_maxstart, lsoln):
     if n < 0:
         obj._check(n)
     return hits, maps, first
+
+
+def _search_refine_polish(obj, call, k, candidates, refine_maxstart, lsoln):
+    """shared by Searcher / MultiSearcher.search_refine_polish: `call(hits, maps, first, base)` runs the C entry point"""
+    base = []
+
+    def with_base(h, m, f):
+        base.append(np.zeros(max(1, min(int(k), int(candidates), obj.n_entries)) * getattr(obj, "n_queries", 1), np.int32))
+        return call(h, m, f, base[0].ctypes.data)
+
+    hits, maps, first = _search_refine(obj, with_base, k, candidates, refine_maxstart, lsoln)
+    return hits, maps, first, base[0].reshape(first.shape)
 
 
 def _hits_cutoff(obj, nq, lsoln, first, again):
@@ -309,6 +336,19 @@ class Searcher:
         return _search_refine(self, lambda h, m, f: self._lib.sat_search_refine(
             self._ctx, int(bool(lorder)), int(bool(lsoln)), int(maxstart), int(candidates), int(refine_maxstart), int(k),
             h, m, f), k, candidates, refine_maxstart, lsoln)
+
+    def search_pairs_polish(self, queries, entries, tops, lorder=True, maxstart=DEFAULT_MAXSTART):
+        """Chosen (query, entry) pairs with the own-best maps of their `tops` best restarts polished to local optima
+        (sat_search_pairs_polish).  Returns (scores int32[P], base_scores int32[P] = search_pairs' scores, restarts
+        int32[P], moves int32[P], maps int32[P, n1max], kernel_ms)."""
+        return _search_pairs_polish(self, self._lib.sat_search_pairs_polish, self._ctx, queries, entries, tops, lorder, maxstart)
+
+    def search_refine_polish(self, k, candidates, refine_maxstart, tops, lorder=True, lsoln=False, maxstart=DEFAULT_MAXSTART):
+        """search_refine with the polish as stage 2 (sat_search_refine_polish): returns (hits ranked by polished score,
+        polished maps or None, stage-1 scores, scores before the polish int32[nq, k'])."""
+        return _search_refine_polish(self, lambda h, m, f, b: self._lib.sat_search_refine_polish(
+            self._ctx, int(bool(lorder)), int(bool(lsoln)), int(maxstart), int(candidates), int(refine_maxstart), int(tops),
+            int(k), h, m, f, b), k, candidates, refine_maxstart, lsoln)
 
     def use_stream(self, stream_handle):
         """Queue all further work on the caller's HIP stream (0 / None = default stream),
@@ -520,6 +560,18 @@ class MultiSearcher:
         that holds its entry (wall_ms instead of kernel_ms)."""
         return _search_pairs_matches(self, self._lib.sat_multi_search_pairs_matches, self._m, queries, entries, max_matches,
                                      lorder, maxstart, maps)
+
+    def search_pairs_polish(self, queries, entries, tops, lorder=True, maxstart=DEFAULT_MAXSTART):
+        """Searcher.search_pairs_polish with entries[p] an index into the whole database (wall_ms instead of kernel_ms)."""
+        return _search_pairs_polish(self, self._lib.sat_multi_search_pairs_polish, self._m, queries, entries, tops, lorder,
+                                    maxstart)
+
+    def search_refine_polish(self, k, candidates, refine_maxstart, tops, lorder=True, lsoln=False, maxstart=DEFAULT_MAXSTART):
+        """Searcher.search_refine_polish over every shard (sat_multi_search_refine_polish)."""
+        ms = C.c_double(0.0)
+        return _search_refine_polish(self, lambda h, m, f, b: self._lib.sat_multi_search_refine_polish(
+            self._m, int(bool(lorder)), int(bool(lsoln)), int(maxstart), int(candidates), int(refine_maxstart), int(tops),
+            int(k), h, m, f, b, C.byref(ms)), k, candidates, refine_maxstart, lsoln)
 
     def search_topk(self, k, lorder=True, lsoln=False, maxstart=DEFAULT_MAXSTART):
         k = min(int(k), self.n_entries)

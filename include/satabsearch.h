@@ -220,6 +220,44 @@ int sat_search_pairs_matches(sat_ctx *ctx, int lorder, int maxstart, int max_mat
                              double *kernel_ms);
 
 /*
+ * Pair search with a polish of the best restarts' maps.  The state sat_search reports for a pair is the
+ * best one any restart VISITED, often not a local optimum of the search's own neighbourhood; this call climbs from the
+ * own-best maps of the pair's `tops` best restarts to local optima and reports the best of them.
+ *   Terms.  A map m gives every query SSE i an image m[i]: -1 or a db SSE, no db SSE twice.  term(i, j, k, l) is
+ *     tscord(qtab[i][k], tab[j][l]) if fabsf(qd[i][k] - d[j][l]) <= 4.0f, else 0 - f32, exactly the search's arithmetic,
+ *     and whatever the search scores 0 scores 0 here (NaN / inf cells, the sentinels).  row(i, j | m) is the sum of
+ *     term(i, j, k, m[k]) over the k != i with m[k] >= 0; row(i, -1 | m) = 0.
+ *   Moves from m.  (i, -1), unmatch, is allowed iff m[i] >= 0.  (i, j), j >= 0, is allowed iff type[j] == qtype[i] (type =
+ *     the entry's tableau diagonal), j is no image of m and, under lorder, lo < j < hi with lo the largest image of a
+ *     matched query SSE below i (-1 if none) and hi the smallest image of a matched query SSE above i (n2 if none).
+ *     delta(i, j) = row(i, j | m) - row(i, m[i] | m).
+ *   Polish of a map: apply the allowed move with the largest delta > 0 - ties to the smallest i, then the smallest j,
+ *     -1 being the smallest j - until no allowed move has delta > 0.  The polished score is the map's score plus the
+ *     deltas, i.e. the full score (tmscord) of the final map.  Every step gains at least 1 and scores are bounded, so it
+ *     ends; the result is injective and type consistent, and under lorder still order preserving.
+ *   Per pair: the maxstart restarts are ranked by the key (s_r, -r) exactly as sat_search_matches ranks them (s_r, map_r
+ *     as defined there); the own-best maps of the first min(tops, maxstart) are polished to p_t; the winner is the
+ *     largest p_t, ties to the lowest rank t.
+ *   scores       [npairs]  p of the winner; always >= base_scores
+ *   base_scores  [npairs]  s of rank 0: sat_search_pairs' score of the pair, bit for bit
+ *   restarts     [npairs]  the winner's restart r
+ *   moves        [npairs]  the moves its polish accepted
+ *   ssemaps      [npairs][SAT_MAXDIM] its polished map, laid out as sat_search_pairs lays out a map
+ * Every output except scores may be NULL.  tops is 1..SAT_MAX_MATCHES (the map pass runs at most that many chains per
+ * pair).  Pairs as sat_search_pairs takes them (any order, repeats, mixed classes); npairs == 0 does nothing; what the
+ * other pair searches reject is rejected the same way (SAT_EINVAL / SAT_ESTATE).  Passes per launch of the list (cut as
+ * sat_search_pairs_matches cuts it): the pair-match record pass, a selection of the `tops` largest keys (no set test),
+ * the pair-match map pass on those restarts, and the polish kernel - one workgroup per pair, one wave per map; a wave
+ * that has not finished within 2 n1 (n1 - 1) + 1 rounds (which cannot happen: scores lie in [-n1 (n1 - 1), n1 (n1 - 1)])
+ * makes the call fail with SAT_EDEVICE.  Nothing depends on the launch shape, cell layout, lanes per chain, entries per
+ * workgroup, the cut into items or the sharding.  Leaves the buffers behind sat_results / sat_topk* / sat_hits_cutoff
+ * alone and keeps an installed fit.  Copies 16 * npairs bytes to the host, + SAT_MAXDIM * npairs with ssemaps.
+ */
+int sat_search_pairs_polish(sat_ctx *ctx, int lorder, int maxstart, int tops, int npairs, const int32_t *query,
+                            const int32_t *entry, int32_t *scores, int32_t *base_scores, int32_t *restarts, int32_t *moves,
+                            int32_t *ssemaps, double *kernel_ms);
+
+/*
  * Queue all further work of this context on the caller's stream (`hip_stream` is a
  * hipStream_t passed as void*; NULL selects the device's default stream).  A context
  * starts on a private non-blocking stream; sat_use_own_stream() goes back to it.
@@ -329,6 +367,17 @@ int sat_hits_cutoff(sat_ctx *ctx, double max_pvalue, int max_rows, int32_t *coun
 int sat_search_refine(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int candidates, int refine_maxstart,
                       int k, sat_hit *hits, int32_t *ssemaps, int32_t *first_scores);
 
+/*
+ * sat_search_refine with stage 2 = sat_search_pairs_polish(refine_maxstart, tops) over the candidates:
+ * refine_maxstart == maxstart polishes only.  The rows are ranked by polished score, ties in database order, with norm2 /
+ * z / p of the polished score from the same table as sat_search_refine (the built-in constants: the statistics are not
+ * calibrated to polished scores).  ssemaps (may be NULL; written when lsoln): the polished maps.  base_scores (may be
+ * NULL) [n_queries * K]: each row's score before the polish, i.e. sat_search_refine's score of it.  Copies, beyond
+ * sat_search_refine's rows, 4 bytes per candidate (the polish's completion flags).
+ */
+int sat_search_refine_polish(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int candidates, int refine_maxstart,
+                             int tops, int k, sat_hit *hits, int32_t *ssemaps, int32_t *first_scores, int32_t *base_scores);
+
 
 /*
  * ---- Gumbel statistics fitted to the search's own scores.  Every z and p above comes from two
@@ -395,7 +444,7 @@ unsigned long long sat_stat_d2h_bytes(const sat_ctx *ctx);
  * sat_search_pairs: "score pass (R restarts, S per item): <launches>", followed by " | map pass: <launches>" with
  * lsoln; after sat_search_refine: "stage 1: <launches> || stage 2: <the pair search's>"; after sat_search_pairs_matches:
  * "record pass (R restarts, S per item, L launches of up to P pairs): <launches> | select", followed by
- * " | map pass: <launches>" when maps were asked for. */
+ * " | map pass: <launches>" when maps were asked for; after sat_search_pairs_polish the same with " | polish" at the end. */
 const char *sat_last_launch_info(const sat_ctx *ctx);
 
 /*
@@ -472,6 +521,15 @@ int sat_multi_search_refine(sat_multi *m, int lorder, int lsoln, int maxstart, i
 int sat_multi_search_pairs_matches(sat_multi *m, int lorder, int maxstart, int max_matches, int npairs, const int32_t *query,
                                    const int32_t *entry, int32_t *counts, int32_t *scores, int32_t *restarts,
                                    int32_t *ssemaps, double *wall_ms);
+/* sat_search_pairs_polish with entry[p] an index into the WHOLE database, and sat_search_refine_polish over every shard:
+ * exactly what one context holding the whole database returns, routed and merged as sat_multi_search_pairs_matches and
+ * sat_multi_search_refine do it.  wall_ms as sat_multi_search. */
+int sat_multi_search_pairs_polish(sat_multi *m, int lorder, int maxstart, int tops, int npairs, const int32_t *query,
+                                  const int32_t *entry, int32_t *scores, int32_t *base_scores, int32_t *restarts, int32_t *moves,
+                                  int32_t *ssemaps, double *wall_ms);
+int sat_multi_search_refine_polish(sat_multi *m, int lorder, int lsoln, int maxstart, int candidates, int refine_maxstart, int tops,
+                                   int k, sat_hit *hits, int32_t *ssemaps, int32_t *first_scores, int32_t *base_scores,
+                                   double *wall_ms);
 /* sat_hits_cutoff over every shard, exactly what one context holding the whole database returns: each shard selects
  * its own rows (max_rows per query at most), the host merges them per query by score descending, then entry index in
  * the whole database ascending (hits[].entry), and cuts to max_rows.  Same CSR output, capacity contract and return
