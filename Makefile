@@ -1,33 +1,15 @@
-# Top-level build for C users (the Python build in cuda_satabsearch_amd/build.py does the same):
+# Top-level build for C users, through the Python build in cuda_satabsearch_amd/build.py:
 #   make            libsatabsearch.so (HIP kernels + C ABI), libsathost.so (reader, statistics),
 #                   cuda_satabsearch_amd/bin/satabsearch (command line)
 #   make oracle     the CPU oracle used by the tests (oracle/), plus the reference build when
 #                   /root/reference is mounted
 #   make test       CPU test suite;  make test-gpu on a machine with an MI355X
-HIPCC   ?= hipcc
-CC      ?= gcc
+# The sources, flags and dependencies of all three are cuda_satabsearch_amd/build.py's alone (DEVICE_SOURCES: one object
+# per translation unit of the device library, re-made only when it or a header it includes changed).
 PKG      = cuda_satabsearch_amd
-CSRC     = $(PKG)/csrc
-HOST     = $(CSRC)/host
 
-all: $(PKG)/libsathost.so $(PKG)/libsatabsearch.so $(PKG)/bin/satabsearch
-
-$(PKG)/libsathost.so: $(HOST)/sat_parse.c $(HOST)/sat_gumbel.c $(HOST)/sat_shard.c $(HOST)/sat_parse.h $(HOST)/sat_gumbel.h $(HOST)/sat_shard.h
-	$(CC) -O2 -fPIC -shared -Wall -Wextra -I$(HOST) -o $@ $(HOST)/sat_parse.c $(HOST)/sat_gumbel.c $(HOST)/sat_shard.c -lm -lpthread
-
-$(PKG)/sat_shard.o: $(HOST)/sat_shard.c $(HOST)/sat_shard.h
-	$(CC) -O2 -fPIC -ffp-contract=off -Wall -Wextra -I$(HOST) -c -o $@ $(HOST)/sat_shard.c
-
-$(PKG)/sat_gumbel.o: $(HOST)/sat_gumbel.c $(HOST)/sat_gumbel.h
-	$(CC) -O2 -fPIC -ffp-contract=off -Wall -Wextra -I$(HOST) -c -o $@ $(HOST)/sat_gumbel.c
-
-$(PKG)/libsatabsearch.so: $(CSRC)/sat_capi.hip $(CSRC)/sat_topk.hip $(CSRC)/sat_multi.hip $(PKG)/sat_gumbel.o $(PKG)/sat_shard.o $(CSRC)/sat_sa_kernel.hpp $(CSRC)/sat_ctx.hpp include/satabsearch.h
-	$(HIPCC) --offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -fPIC -shared -Iinclude -I$(CSRC) -o $@ $(CSRC)/sat_capi.hip $(CSRC)/sat_topk.hip $(CSRC)/sat_multi.hip -Wl,$(PKG)/sat_gumbel.o -Wl,$(PKG)/sat_shard.o -lm -ldl
-
-$(PKG)/bin/satabsearch: $(HOST)/sat_main.c $(HOST)/sat_host_search.c $(PKG)/libsatabsearch.so $(PKG)/libsathost.so
-	mkdir -p $(PKG)/bin
-	$(CC) -O3 -ffp-contract=off -Wall -Wextra -Iinclude -I$(HOST) -o $@ $(HOST)/sat_main.c $(HOST)/sat_host_search.c \
-	    -L$(PKG) -lsatabsearch -lsathost -lm -Wl,-rpath,'$$ORIGIN/..'
+all:
+	python -m $(PKG).build
 
 oracle:
 	$(MAKE) -C oracle all
@@ -40,7 +22,8 @@ test-gpu: all oracle
 	python -m pytest tests -q -m gpu
 
 clean:
-	rm -f $(PKG)/libsathost.so $(PKG)/libsatabsearch.so $(PKG)/bin/satabsearch
+	rm -f $(PKG)/libsathost.so $(PKG)/libsatabsearch.so $(PKG)/bin/satabsearch $(PKG)/*.o
+	rm -rf $(PKG)/obj
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle test test-gpu clean

@@ -11,6 +11,7 @@ the product), `--ref` also its `ref` target when /root/reference is mounted.
 hipcc cross-compiles gfx950 code objects without a GPU present.
 """
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -37,15 +38,49 @@ def _stale(target, sources):
     return any(os.path.getmtime(s) > t for s in sources)
 
 
+# The device library's translation units, sat_launch.hip (every SA kernel instantiation: minutes) first.  The one list
+# of them: the library, its diagnostic twin, the Makefile and scripts/exp/variant_lib.sh all build from it.
+DEVICE_SOURCES = ("sat_launch.hip", "sat_capi.hip", "sat_db.hip", "sat_topk.hip", "sat_multi.hip", "sat_polish.hip")
+# sat_launch.hip and what it includes from csrc/ (diag/ apart, which only -DSAT_DIAG builds read)
+KERNEL_SOURCES = ("sat_sa_kernel.hpp", "sat_sa_body.inc", "sat_launch.hpp", "sat_launch.hip")
+HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "-I", INC, "-I", CSRC]
+# (library, directory of its objects, flags beyond HIPFLAGS).  The twin is the device library once more with the
+# reference's TESTING assertion compiled in (diag/sat_diag.hpp, -DSAT_DIAG_SELFCHECK: every proposed move's score against
+# a full recomputation) - loaded only by tests/test_gpu_parity.py::test_every_move_passes_the_references_self_check,
+# through SAT_DEVICE_LIB
+DEVICE_LIB = (os.path.join(PKG, "libsatabsearch.so"), os.path.join(PKG, "obj", "lib"), [])
+SELFCHECK_LIB = (os.path.join(ROOT, "tests", "native", "libsat_selfcheck.so"), os.path.join(PKG, "obj", "selfcheck"),
+                 ["-DSAT_DIAG", "-DSAT_DIAG_SELFCHECK"])
+JOBS = 16       # compile commands running at once, all libraries together
+
+
 def kernel_source_hash():
-    """sha256 over the sources of the SA kernel and its dispatch: profiles/bench_traffic.json carries it, so that
-    bench.py only reports committed counter figures that were measured on the kernel it is running."""
+    """sha256 over the sources of the SA kernels and of the code that picks one and sizes its workgroup - the translation
+    unit sat_launch.hip: profiles/bench_traffic.json carries it, so that bench.py only reports committed counter figures
+    that were measured on the kernel it is running."""
     import hashlib
     h = hashlib.sha256()
-    for f in ("sat_sa_kernel.hpp", "sat_sa_body.inc", "sat_capi.hip", "sat_ctx.hpp"):
+    for f in KERNEL_SOURCES:
         with open(os.path.join(CSRC, f), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()
+
+
+def include_closure(src):
+    """`src` and every file it reaches through #include "..." lines (the conditional ones too), each looked up beside
+    the including file, then in csrc/ and include/"""
+    seen, todo = [], [src]
+    while todo:
+        f = todo.pop()
+        if f in seen:
+            continue
+        seen.append(f)
+        with open(f) as fh:
+            names = re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', fh.read(), re.M)
+        for name in names:
+            hits = [p for p in (os.path.normpath(os.path.join(d, name)) for d in (os.path.dirname(f), CSRC, INC)) if os.path.exists(p)]
+            todo += hits[:1]
+    return seen
 
 
 def build_host(force=False):
@@ -68,19 +103,37 @@ def _host_objects(force=False):
     return host_o
 
 
-def build_device(force=False):
-    out = os.path.join(PKG, "libsatabsearch.so")
-    srcs = [os.path.join(CSRC, f) for f in ("sat_capi.hip", "sat_topk.hip", "sat_multi.hip", "sat_polish.hip")]
+def build_device_libs(libs, force=False):
+    """Each (library, object directory, flags) of `libs` from DEVICE_SOURCES: every translation unit to an object of its
+    own, re-made only when it or a file it includes is newer, all of them side by side; then the link.  A library newer
+    than everything it is made from is left alone, objects or not."""
+    host_c = [os.path.join(HOST, f) for f in ("sat_gumbel.c", "sat_shard.c", "sat_gumbel.h", "sat_stats.h", "sat_shard.h")]
+    srcs = [os.path.join(CSRC, f) for f in DEVICE_SOURCES]
+    deps = [include_closure(src) for src in srcs]
+    todo = [lib for lib in libs if force or _stale(lib[0], host_c + sum(deps, []))]
+    if not todo:
+        return
     host_o = _host_objects(force)
-    deps = srcs + host_o + [os.path.join(CSRC, "sat_sa_kernel.hpp"), os.path.join(CSRC, "sat_sa_body.inc"),
-                            os.path.join(CSRC, "sat_ctx.hpp"), os.path.join(CSRC, "sat_cutoff.hpp"),
-                            os.path.join(HOST, "sat_gumbel.h"), os.path.join(HOST, "sat_stats.h"),
-                            os.path.join(INC, "satabsearch.h")]
-    if force or _stale(out, deps):
+    compiles = []
+    for out, objdir, flags in todo:
+        os.makedirs(objdir, exist_ok=True)
+    for src, dep in zip(srcs, deps):
+        for out, objdir, flags in todo:
+            obj = os.path.join(objdir, os.path.splitext(os.path.basename(src))[0] + ".o")
+            if force or _stale(obj, dep):
+                compiles.append([HIPCC] + HIPFLAGS + flags + ["-c", "-o", obj, src])
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(JOBS) as ex:
+        list(ex.map(_run, compiles))
+    for out, objdir, flags in todo:
+        objs = [os.path.join(objdir, os.path.splitext(f)[0] + ".o") for f in DEVICE_SOURCES]
         # -Wl,: hipcc would compile a bare .o as HIP source.  librccl is NOT linked: sat_multi.hip loads it on demand
-        _run([HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared",
-              "-I", INC, "-I", CSRC, "-o", out] + srcs + ["-Wl," + o for o in host_o] + ["-lm", "-ldl"])
-    return out
+        _run([HIPCC, "--offload-arch=gfx950", "-fPIC", "-shared", "-o", out] + ["-Wl," + o for o in objs + host_o] + ["-lm", "-ldl"])
+
+
+def build_device(force=False):
+    build_device_libs([DEVICE_LIB], force)
+    return DEVICE_LIB[0]
 
 
 def build_cli(force=False):
@@ -100,9 +153,10 @@ def build_cli(force=False):
     return out
 
 
-def build_test_native(force=False):
+def build_test_native(force=False, twin=True):
     """tests/native/*.hip: GPU-side TEST helpers (e.g. the rocRAND device API beside the kernel's own
-    Philox block).  Test infrastructure like oracle/: never loaded by the product."""
+    Philox block) and (twin) the device library's diagnostic twin.  Test infrastructure like oracle/: never loaded by
+    the product."""
     tdir = os.path.join(ROOT, "tests", "native")
     src = os.path.join(tdir, "rocrand_check.hip")
     if not os.path.exists(src):
@@ -110,18 +164,8 @@ def build_test_native(force=False):
     out = os.path.join(tdir, "librocrand_check.so")
     if force or _stale(out, [src, os.path.join(CSRC, "sat_sa_kernel.hpp"), os.path.join(CSRC, "sat_sa_body.inc")]):
         _run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-I", INC, "-I", CSRC, "-o", out, src])
-    # the device library once more with the reference's TESTING assertion compiled in (diag/sat_diag.hpp,
-    # -DSAT_DIAG_SELFCHECK: every proposed move's score against a full recomputation) - loaded only by
-    # tests/test_gpu_parity.py::test_every_move_passes_the_references_self_check, through SAT_DEVICE_LIB
-    out3 = os.path.join(tdir, "libsat_selfcheck.so")
-    dsrcs = [os.path.join(CSRC, f) for f in ("sat_capi.hip", "sat_topk.hip", "sat_multi.hip", "sat_polish.hip")]
-    ddeps = dsrcs + [os.path.join(CSRC, "sat_sa_kernel.hpp"), os.path.join(CSRC, "sat_sa_body.inc"), os.path.join(CSRC, "sat_ctx.hpp"),
-                     os.path.join(CSRC, "sat_cutoff.hpp"), os.path.join(HOST, "sat_gumbel.h"), os.path.join(HOST, "sat_stats.h"),
-                     os.path.join(CSRC, "diag", "sat_diag.hpp"), os.path.join(INC, "satabsearch.h")]
-    if force or _stale(out3, ddeps):
-        _run([HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared", "-DSAT_DIAG",
-              "-DSAT_DIAG_SELFCHECK", "-I", INC, "-I", CSRC, "-o", out3] + dsrcs +
-             ["-Wl," + os.path.join(PKG, "sat_gumbel.o"), "-Wl," + os.path.join(PKG, "sat_shard.o"), "-lm", "-ldl"])
+    if twin:
+        build_device_libs([SELFCHECK_LIB], force)
     src2, out2 = os.path.join(tdir, "lds_residency.hip"), os.path.join(tdir, "liblds_residency.so")
     if os.path.exists(src2) and (force or _stale(out2, [src2])):
         _run([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", out2, src2])
@@ -137,16 +181,10 @@ def build_oracle(ref=False):
 
 def build_all(force=False, oracle=False, ref=False):
     build_host(force)
-    _host_objects(force)
     if oracle:
-        # the device library and its diagnostic twin (tests/native/libsat_selfcheck.so: the same sources with the
-        # reference's per-move assertion compiled in) take ~100 s of hipcc each: side by side
-        from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(2) as ex:
-            dev = ex.submit(build_device, False if not force else True)
-            nat = ex.submit(build_test_native, force)
-            dev.result()
-            nat.result()
+        # the device library and its diagnostic twin: their translation units compile side by side
+        build_device_libs([DEVICE_LIB, SELFCHECK_LIB], force)
+        build_test_native(force, twin=False)
         build_cli(force)
         build_oracle(ref)
     else:

@@ -1,25 +1,20 @@
 // sat_capi.hip - C ABI (include/satabsearch.h) over the gfx950 SA kernel.
 //
-// Host side of the drop-in boundary: device memory, the packed database store, the
-// query buffer, the Metropolis table, size-class dispatch and launches.  Replaces
-// the device glue of nvcc_src_current/cudaSaTabsearch.cu (init_rng :258-264,
-// copyQueryToConstantMemory :486-558, alloc/upload :896-984, launch/sync/download
-// :1036-1087 and :1128-1270).  No CPU search path exists in this library.
+// Host side of the drop-in boundary: the context, the Metropolis table, the search modes' plans and launches, results.
+// What goes up - the packed database store, the query buffer - is sat_db.hip; which SA kernel a launch runs and with
+// which workgroup is sat_launch.hip, reached through sat_launch.hpp only.  Together they replace the device glue of
+// nvcc_src_current/cudaSaTabsearch.cu (init_rng :258-264, copyQueryToConstantMemory :486-558, alloc/upload :896-984,
+// launch/sync/download :1036-1087 and :1128-1270).  No CPU search path exists in this library.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
-#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
-#include <set>
 #include <string>
-#include <thread>
-#include <type_traits>
 #include <vector>
 
 #include "satabsearch.h"
@@ -46,11 +41,6 @@ int sat_fail(int code, const char *fmt, ...)
 }
 
 namespace {
-
-// db entries are launched in classes of similar order so that every launch sizes its
-// LDS for the largest member of the class only
-const int kBucketMax[kNumBuckets] = { 16, 32, 48, 64, 80, 96, 111 };
-constexpr size_t kLdsLimit = 160 * 1024;
 
 int build_metropolis_table(sat_ctx *ctx)
 {
@@ -105,284 +95,6 @@ int build_gumbel_tables(sat_ctx *ctx)
     return SAT_OK;
 }
 
-void free_db(sat_ctx *ctx)
-{
-    ctx->d_orders.reset();
-    ctx->d_cell_off.reset();
-    ctx->d_tab.reset();
-    ctx->d_dist.reset();
-    ctx->d_ordinal.reset();
-    ctx->d_lists.reset();
-    ctx->d_scores.reset();
-    ctx->d_ssemaps.reset();
-    ctx->desc_dirty = true;
-    ctx->n_entries = 0;
-    ctx->min_rows = 0;
-    ctx->searched_nq = 0;
-    ctx->fits.clear();
-    ctx->h_orders.clear();
-}
-
-// ---- kernel choice.  The four kernel families are instantiated over the same size classes and db layouts: the
-// dispatch below calls f with std::integral_constant arguments, so that one walk of the tree (pick_sa_kernel) names every
-// instantiation once.
-template <int V> using Int = std::integral_constant<int, V>;
-
-// f(Int<N1P>) for a query size class
-template <typename F> auto by_class(int n1p, F f)
-{
-    switch (n1p) {
-    case 16: return f(Int<16>{});
-    case 32: return f(Int<32>{});
-    case 64: return f(Int<64>{});
-    default: return f(Int<112>{});
-    }
-}
-
-// f(std::bool_constant<b>)
-template <typename F> auto by_flag(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
-
-// f(Int<V>) for v in First .. Last, Last for anything above
-template <int First, int Last, typename F> auto by_value(int v, F f)
-{
-    if constexpr (First == Last) return f(Int<Last>{});
-    else return v == First ? f(Int<First>{}) : by_value<First + 1, Last>(v, f);
-}
-
-// f(Int<M2W>, Int<CELLS>): db-side set width and cell layout (satk::cell_layout of the launch's largest entry).
-// One-word sets go with the 8-byte cells, two-word sets with either split layout (entries of up to 48 SSEs: full
-// matrix, above: triangle), four-word sets with the triangle.
-template <typename F> auto by_layout(int m2w, int cells, F f)
-{
-    if (m2w == 1) return f(Int<1>{}, Int<SAT_CELLS_FULL8>{});
-    if (m2w == 2) return cells == SAT_CELLS_FULL5 ? f(Int<2>{}, Int<SAT_CELLS_FULL5>{}) : f(Int<2>{}, Int<SAT_CELLS_TRI5>{});
-    return f(Int<4>{}, Int<SAT_CELLS_TRI5>{});
-}
-
-// The four kernel families (sat_sa_kernel.hpp): bit 0 = the match arguments, bit 1 = the pair arguments
-enum SaMode { kPlain = 0, kMatch = 1, kPair = 2, kPairMatch = 3 };
-
-// A chosen SA kernel: the instantiation's address and the template arguments it was instantiated with (opt = -1, wpl = 0:
-// the general instantiation).  What is launched (launch_sa) and what sat_last_launch_info names (launch_info) both come
-// from this one record.
-struct SaKernel { const void *fn; int mode, n1p, m2w, cells; bool qlds; int opt, wpl; };
-
-// the instantiation of family MODE; only the plain family has WPL, only the plain and the pair family have OPT
-template <int MODE, int N1P, int M2W, bool QLDS, int OPT, int WPL, int CELLS> const void *sa_instance()
-{
-    static_assert(MODE == kPlain || WPL == 0, "words per lane are an argument of the plain kernel only");
-    static_assert(MODE == kPlain || MODE == kPair || OPT == -1, "the match families read their options from the arguments");
-    if constexpr (MODE == kPlain) return reinterpret_cast<const void *>(sat_sa_kernel<N1P, M2W, QLDS, OPT, WPL, CELLS>);
-    else if constexpr (MODE == kPair) return reinterpret_cast<const void *>(sat_sa_pair_kernel<N1P, M2W, QLDS, OPT, CELLS>);
-    else if constexpr (MODE == kMatch) return reinterpret_cast<const void *>(sat_sa_match_kernel<N1P, M2W, QLDS, CELLS>);
-    else return reinterpret_cast<const void *>(sat_sa_pair_match_kernel<N1P, M2W, QLDS, CELLS>);
-}
-
-// The kernel of a launch's family, size class and layout.  opt >= 0 asks for an instantiation with the options as
-// compile-time facts (bit 0 LORDER, bit 1 LSOLN, bits 2-3 log2 of the lanes per chain; compaction tables exactly when
-// LORDER); these exist for the default placement of the query cells only (LDS for the 16 class, L1/L2 for the others):
-//   plain       opt 0-3, and with LORDER also `wpl`, the words per lane of the compacted rounds when every query of the
-//               launch has the same, for the values a class can have (satk::compaction_shape), else 0 (see the kernel's
-//               OPT and WPL parameters); opt 4-11 (several lanes per chain) for the largest entries only (M2W = 4, words
-//               per lane read per query);
-//   pair        opt 0 / 1 (LSOLN off, one lane per chain, words per lane read per query);
-//   match, pair-match   none.
-// Anything else runs the general instantiation.
-SaKernel pick_sa_kernel(int mode, int n1p, int m2w, int cells, bool qlds, int opt, int wpl)
-{
-    SaKernel k = { nullptr, mode, n1p, m2w, cells, qlds, -1, 0 };
-    by_value<kPlain, kPairMatch>(mode, [&](auto md) {
-        by_class(n1p, [&](auto c) {
-            constexpr int MODE = decltype(md)::value, N1P = decltype(c)::value;
-            constexpr bool kQ = N1P < 32;
-            // the instantiation <q, o, w> for the launch's layout
-            auto take = [&](auto q, auto o, auto w) {
-                k.opt = decltype(o)::value;
-                k.wpl = decltype(w)::value;
-                k.fn = by_layout(m2w, cells, [](auto m, auto l) {
-                    return sa_instance<MODE, N1P, decltype(m)::value, decltype(q)::value, decltype(o)::value, decltype(w)::value,
-                                       decltype(l)::value>();
-                });
-            };
-            const std::bool_constant<kQ> q{};
-            if constexpr (MODE == kPlain) {
-                if (opt >= 4 && qlds == kQ && m2w == 4)
-                    return by_value<4, 11>(opt, [&](auto o) {
-                        k.opt = decltype(o)::value;
-                        k.fn = sa_instance<kPlain, N1P, 4, kQ, decltype(o)::value, 0, SAT_CELLS_TRI5>();
-                    });
-                if (opt >= 0 && opt < 4 && qlds == kQ)
-                    return by_value<0, 3>(opt, [&](auto o) {
-                        if constexpr ((decltype(o)::value & 1) == 0) take(q, o, Int<0>{});     // no compaction: wpl unused
-                        else {
-                            if (wpl == 4) return take(q, o, Int<4>{});
-                            if constexpr (N1P <= 64)
-                                if (wpl == 3) return take(q, o, Int<3>{});
-                            if constexpr (N1P == 16) {
-                                if (wpl == 2) return take(q, o, Int<2>{});
-                                if (wpl == 1) return take(q, o, Int<1>{});
-                            }
-                            take(q, o, Int<0>{});               // queries of different shapes: wpl read per query
-                        }
-                    });
-            }
-            if constexpr (MODE == kPair)
-                if ((opt == 0 || opt == 1) && qlds == kQ) return by_value<0, 1>(opt, [&](auto o) { take(q, o, Int<0>{}); });
-            by_flag(qlds, [&](auto qg) { take(qg, Int<-1>{}, Int<0>{}); });
-        });
-    });
-    return k;
-}
-
-// Launch `k`: the kernel's parameters are the SatKernelArgs, then the pair arguments (pair families), then the match
-// arguments (match families).  The only place that knows which family takes which.
-hipError_t launch_sa(const SaKernel &k, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const SatKernelArgs &a,
-                     const SatPairArgs *px, const SatMatchArgs *mx)
-{
-    void *args[3] = { const_cast<SatKernelArgs *>(&a), nullptr, nullptr };
-    int n = 1;
-    if (k.mode & kPair) args[n++] = const_cast<SatPairArgs *>(px);
-    if (k.mode & kMatch) args[n++] = const_cast<SatMatchArgs *>(mx);
-    (void)hipLaunchKernel(k.fn, grid, block, args, lds, stream);
-    return hipGetLastError();
-}
-
-// An instantiation by name, "kernel<template arguments>" as the source spells it: the one formatter of
-// sat_last_launch_info (launch_info) and of the list of instantiations (sat_debug_sa_instances).
-std::string sa_kernel_name(const SaKernel &k)
-{
-    static const char *const kName[4] = { "sat_sa_kernel", "sat_sa_match_kernel", "sat_sa_pair_kernel", "sat_sa_pair_match_kernel" };
-    char targs[48] = "", buf[128];
-    if (k.mode == kPlain) snprintf(targs, sizeof targs, "%d, %d, ", k.opt, k.wpl);
-    if (k.mode == kPair) snprintf(targs, sizeof targs, "%d, ", k.opt);
-    snprintf(buf, sizeof buf, "%s<%d, %d, %s, %s%d>", kName[k.mode], k.n1p, k.m2w, k.qlds ? "true" : "false", targs, k.cells);
-    return buf;
-}
-
-// One launch as sat_last_launch_info names it: "kernel<template arguments> [items N] grid X x Y block E x T lds B"
-// (items: the pair families' item count; E entry slots of T threads; B the LDS bytes of one slot).
-std::string launch_info(const SaKernel &k, int items, int grid_x, int grid_y, int epw, int threads, size_t lds)
-{
-    char count[32] = "", buf[128];
-    if (k.mode & kPair) snprintf(count, sizeof count, " items %d", items);
-    snprintf(buf, sizeof buf, "%s grid %d x %d block %d x %d lds %zu", count, grid_x, grid_y, epw, threads, lds);
-    return sa_kernel_name(k) + buf;
-}
-
-const int kClassN1P[4] = { 16, 32, 64, 112 };
-
-// (re)build the device query descriptors: pointers into the query blob and into the result
-// buffers, grouped by size class
-int refresh_descriptors(sat_ctx *ctx, bool lsoln, hipStream_t stream)
-{
-    const size_t nq = ctx->queries.size();
-    const size_t rows = (size_t)(ctx->n_entries > ctx->min_rows ? ctx->n_entries : ctx->min_rows);    // capacity only
-    bool moved = false;
-    int rc = ctx->d_scores.grow(nq * rows, &moved);
-    if (rc != SAT_OK) return rc;
-    if (moved) ctx->desc_dirty = true;
-    if (lsoln) {
-        size_t need = 0, n1sum = 0;
-        for (auto &q : ctx->queries) {
-            q.ssemap_off = need;
-            need += (size_t)ctx->n_entries * q.n1;
-            n1sum += (size_t)q.n1;
-        }
-        if (rows * n1sum > need) need = rows * n1sum;
-        if ((rc = ctx->d_ssemaps.grow(need, &moved)) != SAT_OK) return rc;
-        if (moved || !ctx->desc_lsoln) ctx->desc_dirty = true;
-    }
-    if (!ctx->desc_dirty) return SAT_OK;
-
-    std::vector<SatQuery> desc;
-    desc.reserve(nq);
-    for (int c = 0; c < 4; c++) {
-        ctx->class_begin[c] = (int)desc.size();
-        ctx->class_n1max[c] = 0;
-        ctx->class_wpl[c] = -1;                       // -1: no query yet, 0: mixed
-        for (size_t qi = 0; qi < nq; qi++) {
-            auto &q = ctx->queries[qi];
-            if (q.n1p != kClassN1P[c]) continue;
-            q.cls = c;
-            q.desc = (int)desc.size();
-            const uint8_t *blob = ctx->d_qblob.get() + q.blob_off;
-            const size_t groups = (size_t)q.n1p / 4 * q.n1p;
-            SatQuery d;
-            d.qdist = reinterpret_cast<const float4 *>(blob);
-            d.qcode = reinterpret_cast<const uint32_t *>(blob + groups * 16);
-            d.qtypes = blob + groups * 20;
-            d.qpair = reinterpret_cast<const uint2 *>(blob + ((groups * 20 + (size_t)q.n1p + 15) & ~(size_t)15));
-            d.n1 = q.n1;
-            d.pad_ = 0;
-            d.seed_q = ctx->seed + ((uint64_t)q.ordinal << 32);
-            d.scores = ctx->d_scores.get() + qi * (size_t)ctx->n_entries;
-            d.ssemaps = lsoln ? ctx->d_ssemaps.get() + q.ssemap_off : nullptr;
-            desc.push_back(d);
-            if (q.n1 > ctx->class_n1max[c]) ctx->class_n1max[c] = q.n1;
-            int lpi, wpl;
-            satk::compaction_shape((q.n1 + 3) >> 2, lpi, wpl);
-            ctx->class_wpl[c] = ctx->class_wpl[c] < 0 ? wpl : (ctx->class_wpl[c] == wpl ? wpl : 0);
-        }
-        if (ctx->class_wpl[c] < 0) ctx->class_wpl[c] = 0;
-    }
-    ctx->class_begin[4] = (int)desc.size();
-    // ordered after earlier launches on the stream; the host vector dies at return, so wait
-    HIP_TRY(hipMemcpyAsync(ctx->d_qdesc.get(), desc.data(), desc.size() * sizeof(SatQuery), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    ctx->desc_dirty = false;
-    ctx->desc_lsoln = lsoln;
-    return SAT_OK;
-}
-
-// Entries per workgroup.  A CU hands out its LDS in 128 granules of 1280 bytes (measured,
-// scripts/exp/lds_probe.hip: 128-thread workgroups drop from 12 to 11 to 10 per CU at 12 800 and 14 080
-// bytes, 384-thread ones from 4 to 3 at 40 960), so a workgroup of one entry wastes up to a granule plus
-// what is left over at the end of the CU.  k entries side by side round up once: the bench entry's
-// 13 320 bytes fit 11 times alone (11 granules each) and 6 x 2 times in pairs (21 granules a pair).
-// Picks the smallest k with the most resident entries, the register file's wave limit included.  Only
-// workgroups of a multiple of 4 waves and at most 512 threads are considered: measured on the bench,
-// 6-wave workgroups do not spread evenly over the 4 SIMDs (8.5 M scorings/s against 10.6 M), and 12-wave
-// ones lose to their own start-up and drain phases what the extra residency gains (10.4 M).
-int resident_by_lds(size_t bytes) { return (int)(128 / ((bytes + 1279) / 1280)); }
-
-int pick_epw(const void *fn, int threads, size_t lds_stride)
-{
-    int best = 1, best_entries = 0;
-    for (int k = 1; k * threads <= 512 && (size_t)k * lds_stride <= kLdsLimit; k++) {
-        if (k > 1 && (k * threads / 64) % 4 != 0) continue;
-        int by_regs = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&by_regs, fn, k * threads, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            return 1;
-        }
-        const int by_lds = resident_by_lds((size_t)k * lds_stride);
-        const int entries = (by_regs < by_lds ? by_regs : by_lds) * k;
-        if (entries > best_entries) { best_entries = entries; best = k; }
-    }
-    return best;
-}
-
-// Before a launch of `fn` with `threads` per entry slot and `lds_stride` LDS bytes per slot: raise the
-// instantiation's dynamic-LDS limit (once per context), then *epw = its entries per workgroup (see pick_epw; asked
-// once per shape).  Launches of under 8192 entry-query pairs (`work`) keep one, for the most workgroups;
-// SAT_EXP_EPW overrides where it fits.  epw = null: the caller keeps one entry per workgroup.
-int launch_setup(sat_ctx *ctx, const void *fn, int threads, size_t lds_stride, long long work, int *epw)
-{
-    if (ctx->lds_attr_done.insert(fn).second)
-        HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));
-    if (!epw) return SAT_OK;
-    *epw = 1;
-    if (work >= 8192) {
-        const auto key = std::make_tuple(fn, threads, lds_stride);
-        auto it = ctx->epw_choice.find(key);
-        if (it == ctx->epw_choice.end()) it = ctx->epw_choice.emplace(key, pick_epw(fn, threads, lds_stride)).first;
-        *epw = it->second;
-    }
-    if (ctx->tune.epw >= 1 && (size_t)ctx->tune.epw * lds_stride <= kLdsLimit && ctx->tune.epw * threads <= 1024)
-        *epw = ctx->tune.epw;
-    return SAT_OK;
-}
-
 // the SatKernelArgs fields every launch shares: the database shard, the options, the Metropolis table; no slabs
 SatKernelArgs base_args(const sat_ctx *ctx, int lorder, int lsoln, int maxstart)
 {
@@ -402,8 +114,17 @@ SatKernelArgs base_args(const sat_ctx *ctx, int lorder, int lsoln, int maxstart)
     return a;
 }
 
-// The preconditions of queuing a search, checked in this order: a context, a database (need_db), a query batch,
-// maxstart >= 1.
+// prepare_sa (sat_launch.hpp) for queries of class c of the current batch, with the arguments every launch shares
+int prepare_launch(sat_ctx *ctx, int mode, int lorder, int lsoln, int maxstart, int plan_starts, int c, int n2max, long long work,
+               bool pack, SaLaunch &out)
+{
+    out.args = base_args(ctx, lorder, lsoln, maxstart);
+    return prepare_sa(ctx->sa, mode, lorder, lsoln, plan_starts, c, ctx->class_n1max[c], ctx->class_wpl[c], n2max, work, pack, out);
+}
+
+}  // namespace
+
+// sat_ctx.hpp
 int check_ready(const sat_ctx *ctx, bool need_db, int maxstart)
 {
     if (!ctx) return sat_fail(SAT_EINVAL, "null context");
@@ -413,119 +134,10 @@ int check_ready(const sat_ctx *ctx, bool need_db, int maxstart)
     return SAT_OK;
 }
 
-// The workgroup of one launch: restart chains (one per restart up to 256, fewer where the LDS would not fit them),
-// lanes per chain, where the query cells live, whether the SA step compacts its work, and the LDS bytes of one
-// entry slot.  plan_starts = the most restarts one entry slot runs.
-struct WgShape { int chains, lpc_shift, threads; bool qlds, compact; size_t lds; };
-int size_workgroup(const sat_ctx *ctx, int plan_starts, int n1max, int n1p, int n2max, bool lsoln, bool lorder, WgShape &out)
-{
-    // chains: one per restart up to 256; shrink until the workgroup fits the LDS.
-    // query cells: through L1/L2 for 32-SSE-class queries and up (frees 8+ KB of LDS per
-    // workgroup: more resident waves), in LDS for the small class
-    int chains = (plan_starts + 63) / 64 * 64;
-    if (chains > 256) chains = 256;
-    if (ctx->tune.chains >= 64 && ctx->tune.chains < chains) chains = ctx->tune.chains / 64 * 64;
-    // work compaction needs sparse maps: with LORDER = F almost every step proposes a real
-    // new image, the static loops win and the tables would only cost LDS
-    bool compact = lorder != 0;
-    if (ctx->tune.compact >= 0) compact = ctx->tune.compact != 0;
-    bool qlds = n1p < 32;
-    if (ctx->tune.qlds >= 0) qlds = ctx->tune.qlds != 0 || n1p < 32;
-    size_t lds = 0;
-    for (;;) {
-        lds = satk::lds_bytes(n1max, n1p, n2max, chains, chains, lsoln, qlds, compact);
-        if (lds <= kLdsLimit) break;
-        if (chains > 64) { chains -= 64; continue; }
-        if (qlds) {                                    // query cells stay in L1/L2 instead
-            qlds = false;
-            chains = (plan_starts + 63) / 64 * 64;
-            if (chains > 256) chains = 256;
-            continue;
-        }
-        return sat_fail(SAT_EINVAL, "workgroup does not fit in LDS (n1=%d n2=%d)", n1max, n2max);
-    }
-    // lanes per chain: when LDS leaves fewer than 2 waves per SIMD, let 2 or 4 adjacent lanes
-    // share a chain (same cells in LDS, 2-4x the waves; they split the pair loops).  Measured:
-    // the smallest sharing that reaches 8 waves per CU wins (one lane per chain also runs the
-    // option-specialised kernels); beyond that, sharing only adds redundant bookkeeping.
-    int lpc_shift = 0;
-    for (int l = 0; l <= 2; l++) {
-        if ((chains << l) > 1024 || (l > 0 && n1max <= (8 << (l - 1)))) break;
-        const size_t lds_l = satk::lds_bytes(n1max, n1p, n2max, chains, chains << l, lsoln, qlds, compact);
-        if (lds_l > kLdsLimit) break;
-        lpc_shift = l;
-        // (target: 8 resident waves per CU; 12 for the 101-SSE query class, whose steps are the longest
-        // dependent chains - measured with the triangle cells: configs[4] 2.31 -> 2.45 M scorings/s, the
-        // 101-SSE probe 2.48 -> 2.65 M, while 96-SSE entries under a 32-SSE query lose 5 % at 12)
-        const int want_waves = ctx->tune.lpc_waves > 0 ? ctx->tune.lpc_waves : (n1p == 112 ? 12 : 8);
-        if (resident_by_lds(lds_l) * ((chains << l) / 64) >= want_waves) break;
-    }
-    if (ctx->tune.lpc >= 0 && ctx->tune.lpc <= 2 && (chains << ctx->tune.lpc) <= 1024) lpc_shift = ctx->tune.lpc;
-    // the per-wave tables grow with the lanes: re-size, backing off if that no longer fits
-    for (;; lpc_shift--) {
-        lds = satk::lds_bytes(n1max, n1p, n2max, chains, chains << lpc_shift, lsoln, qlds, compact);
-        if (lds <= kLdsLimit || lpc_shift == 0) break;
-    }
-    const int threads = chains << lpc_shift;
-    // experiment knob: extra (unused) LDS bytes per workgroup, to lower the occupancy
-    if (ctx->tune.lds_pad && lds + ctx->tune.lds_pad <= kLdsLimit) lds += ctx->tune.lds_pad;
-    out.chains = chains;
-    out.lpc_shift = lpc_shift;
-    out.threads = threads;
-    out.qlds = qlds;
-    out.compact = compact;
-    out.lds = lds;
-    return SAT_OK;
-}
-
-// What a launch of the SA kernel needs beyond its work list: the workgroup, the kernel, the entry slots per workgroup
-// (epw), the LDS bytes between two slots and of the whole workgroup, and the arguments with the shape fields filled
-// (the caller adds the work list, the queries and the slabs).
-struct SaLaunch { WgShape w; SaKernel k; int epw; size_t lds_stride, lds_launch; SatKernelArgs args; };
-
-// Prepare the launches of family `mode` for queries of class c and entries of up to n2max SSEs: the workgroup sized for
-// plan_starts restarts, the kernel - option-specialised when the workgroup has the default layout for these options
-// (which of them exist is pick_sa_kernel's business) -, its LDS limit and, with `pack`, the entry slots per workgroup
-// for `work` entry-query pairs (else one).
-int prepare_sa(sat_ctx *ctx, int mode, int lorder, int lsoln, int maxstart, int plan_starts, int c, int n2max, long long work,
-               bool pack, SaLaunch &out)
-{
-    const int n1p = kClassN1P[c], m2w = satk::set_words(n2max);
-    WgShape &w = out.w;                       // (lds_bytes sizes it for the same set width and cell layout)
-    int rc = size_workgroup(ctx, plan_starts, ctx->class_n1max[c], n1p, n2max, lsoln != 0, lorder != 0, w);
-    if (rc != SAT_OK) return rc;
-    const bool special = (w.lpc_shift == 0 || m2w == 4) && w.compact == (lorder != 0) && !ctx->tune.general && !(mode & kMatch);
-    const int opt = special ? (lorder ? 1 : 0) | (lsoln ? 2 : 0) | (w.lpc_shift << 2) : -1;
-    out.k = pick_sa_kernel(mode, n1p, m2w, satk::cell_layout(n2max), w.qlds, opt, ctx->class_wpl[c]);
-    if (!out.k.fn) return sat_fail(SAT_EDEVICE, "no kernel variant for n1p=%d m2w=%d", n1p, m2w);
-    out.lds_stride = (w.lds + 15) & ~(size_t)15;
-    out.epw = 1;
-    if ((rc = launch_setup(ctx, out.k.fn, w.threads, out.lds_stride, work, pack ? &out.epw : nullptr)) != SAT_OK) return rc;
-    out.lds_launch = out.epw > 1 ? (size_t)out.epw * out.lds_stride : w.lds;
-    out.args = base_args(ctx, lorder, lsoln, maxstart);
-    out.args.epw = out.epw;
-    out.args.tpe = w.threads;
-    out.args.lds_stride = (uint32_t)out.lds_stride;
-    out.args.lpc_shift = w.lpc_shift;
-    out.args.compact = w.compact ? 1 : 0;
-    return SAT_OK;
-}
-
-// The entries a set of launches covers: indices into the resident shard grouped by order bucket.  A search
-// covers the whole shard (the context's lists); the overlapped upload (sat_db_upload_search) searches the
-// shard piece by piece, each piece with lists of its own.
-struct ListView {
-    const int32_t *d_list;       // device array the `begin` offsets index
-    const int *begin;            // [kNumBuckets + 1]
-    const int *n2max;            // [kNumBuckets] largest order per bucket, 0 = empty
-    int n;                       // entries covered = begin[kNumBuckets] - begin[0]
-};
-
-// mx: one pass of the match mode (sat_search_matches) instead of a plain search; lsoln is 0 then.  Its record pass
+// sat_ctx.hpp.  mx: one pass of the match mode (sat_search_matches) instead of a plain search; lsoln is 0 then.  Its record pass
 // keeps one record slab per entry slot (scores and db sets of every restart) in the best-map scratch, its replay
 // pass a best-map slab per slot there and runs max_matches restarts per entry (workgroups sized for that).
-int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t stream, const ListView *piece = nullptr,
-                  const SatMatchArgs *mx = nullptr)
+int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t stream, const ListView *piece, const SatMatchArgs *mx)
 {
     int rc = check_ready(ctx, true, maxstart);
     if (rc != SAT_OK) return rc;
@@ -562,7 +174,7 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
             }
             if (pl.count == 0) continue;
             pl.nqc = nqc;
-            rc = prepare_sa(ctx, mx ? kMatch : kPlain, lorder, lsoln, maxstart, replay ? mx->max_matches : maxstart, c, pl.n2max,
+            rc = prepare_launch(ctx, mx ? kMatch : kPlain, lorder, lsoln, maxstart, replay ? mx->max_matches : maxstart, c, pl.n2max,
                             (long long)pl.count * nqc, true, pl.l);
             if (rc != SAT_OK) return rc;
             pl.l.args.queries = ctx->d_qdesc.get() + ctx->class_begin[c];
@@ -656,6 +268,8 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
 }
 
 // ---------------------------------------------------------------- pair mode (sat_search_pairs)
+
+namespace {
 
 int order_bucket(int n2)
 {
@@ -770,7 +384,7 @@ int launch_pair_pass(sat_ctx *ctx, int lorder, bool map_pass, int starts, const 
         // by it.)  Entries per workgroup: the score pass as a plain launch; the map pass keeps one item per workgroup (its
         // one restart per item gains nothing from packing, and its best-map slabs are counted per item)
         SaLaunch l;
-        int rc = prepare_sa(ctx, pm ? kPairMatch : kPair, lorder, map_pass && !pm, pm ? pm->maxstart : starts,
+        int rc = prepare_launch(ctx, pm ? kPairMatch : kPair, lorder, map_pass && !pm, pm ? pm->maxstart : starts,
                             map_pass ? (pm ? pm->mx.max_matches : 1) : starts, grp.gcls[g], grp.gn2[g], count, !map_pass, l);
         if (rc != SAT_OK) return rc;
         SatKernelArgs &a = l.args;
@@ -1108,35 +722,6 @@ int sat_pair_matches_collect(sat_ctx *ctx, int max_matches, int npairs, int32_t 
 
 namespace {
 
-// Upload validation: one wave per db entry reads the entry's packed triangle where the search will
-// read it and flags cells outside the kernel's domain; the lowest flagged entry index survives.
-// (entries e_begin .. e_end - 1: the overlapped upload checks the shard piece by piece)
-__global__ void __launch_bounds__(256) validate_cells(int e_begin, int e_end, const int32_t *orders, const int64_t *cell_off,
-                                                      const uint8_t *tab, const float *dist, int32_t *first_bad)
-{
-    const int e = e_begin + blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (e >= e_end) return;
-    const int n = orders[e];
-    const int64_t base = cell_off[e];
-    const int cells = n * (n + 1) / 2;
-    bool bad = false;
-    for (int c = lane; c < cells; c += 64) {
-        // row i of cell c: the largest i with i (i + 1) / 2 <= c; diagonal cells hold the SSE type
-        int i = (int)((sqrtf(8.0f * (float)c + 1.0f) - 1.0f) * 0.5f);
-        while ((i + 1) * (i + 2) / 2 <= c) i++;
-        while (i * (i + 1) / 2 > c) i--;
-        const bool diagonal = c == i * (i + 1) / 2 + i;
-        const uint8_t t = tab[base + c];
-        if (diagonal) {
-            bad |= t > 3;
-        } else {
-            const float ad = fabsf(dist[base + c]);
-            bad |= (t & 0x88u) != 0 || (ad >= 1.0e29f && ad <= 3.4028234e38f);      // finite and out of range
-        }
-    }
-    if (__builtin_amdgcn_ballot_w64(bad) != 0ull && lane == 0) atomicMin(first_bad, e);
-}
-
 // queue `launch` on the context's stream between its two timing events, wait for it, *kernel_ms (may be null) = the
 // time between the events
 template <typename F> int timed(sat_ctx *ctx, double *kernel_ms, F launch)
@@ -1196,20 +781,20 @@ sat_ctx *sat_ctx_create(int device, uint64_t seed)
         HIP_TRY(hipEventCreate(&ctx->ev1));
         // launch-heuristic overrides: read once here, never on the search path
         auto env_int = [](const char *name, int dflt) { const char *v = getenv(name); return v && *v ? atoi(v) : dflt; };
-        ctx->tune.compact = env_int("SAT_EXP_COMPACT", -1);
-        ctx->tune.qlds = env_int("SAT_EXP_QLDS", -1);
-        ctx->tune.lpc = env_int("SAT_EXP_LPC", -1);
-        ctx->tune.general = env_int("SAT_EXP_GENERAL", 0);
+        ctx->sa.compact = env_int("SAT_EXP_COMPACT", -1);
+        ctx->sa.qlds = env_int("SAT_EXP_QLDS", -1);
+        ctx->sa.lpc = env_int("SAT_EXP_LPC", -1);
+        ctx->sa.general = env_int("SAT_EXP_GENERAL", 0);
         ctx->tune.streams = env_int("SAT_EXP_STREAMS", -1);
         ctx->tune.upload_threads = env_int("SAT_EXP_UPLOAD_THREADS", 0);
         ctx->tune.upload_timing = env_int("SAT_EXP_UPLOAD_TIMING", 0);
         ctx->tune.upload_pieces = env_int("SAT_EXP_UPLOAD_PIECES", 0);
-        ctx->tune.epw = env_int("SAT_EXP_EPW", 0);
-        ctx->tune.lpc_waves = env_int("SAT_EXP_LPC_WAVES", 0);
-        ctx->tune.chains = env_int("SAT_EXP_CHAINS", 0);
+        ctx->sa.epw = env_int("SAT_EXP_EPW", 0);
+        ctx->sa.lpc_waves = env_int("SAT_EXP_LPC_WAVES", 0);
+        ctx->sa.chains = env_int("SAT_EXP_CHAINS", 0);
         ctx->tune.refine_split = env_int("SAT_EXP_REFINE_SPLIT", 0);
         const int pad = env_int("SAT_EXP_LDS_PAD", 0);
-        ctx->tune.lds_pad = pad > 0 ? (size_t)pad : 0;
+        ctx->sa.lds_pad = pad > 0 ? (size_t)pad : 0;
         if (ctx->tune.streams != 0) {
             for (int b = 0; b < kNumBuckets; b++) {
                 HIP_TRY(hipStreamCreateWithFlags(&ctx->side_stream[b], hipStreamNonBlocking));
@@ -1219,9 +804,12 @@ sat_ctx *sat_ctx_create(int device, uint64_t seed)
         }
         const int rc_tab = build_metropolis_table(ctx);
         if (rc_tab != SAT_OK) return rc_tab;
-        // load the library's code object now (an empty launch of its smallest kernel): the ~5 ms the
-        // first launch of a process pays for it belong to context creation, not to the first upload
-        hipLaunchKernelGGL(validate_cells, dim3(1), dim3(256), 0, ctx->stream, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
+        // load the code objects of the upload, the SA kernels and this file now (an empty launch of a small kernel, or
+        // a question about one): the ~5 ms the first launch of a process pays for them belong to context creation, not
+        // to the first upload or search
+        int rc_load;
+        if ((rc_load = sat_db_load_code(ctx)) != SAT_OK || (rc_load = sa_load_code()) != SAT_OK) return rc_load;
+        hipLaunchKernelGGL(pair_scores, dim3(1), dim3(256), 0, ctx->stream, nullptr, 0, nullptr);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         return build_gumbel_tables(ctx);
@@ -1248,390 +836,6 @@ void sat_ctx_destroy(sat_ctx *ctx)
         if (e) (void)hipEventDestroy(e);
     for (hipStream_t st : streams)
         if (st) (void)hipStreamDestroy(st);
-}
-
-// What sat_db_upload_search asks of the upload: the first search of the current query batch, queued piece
-// by piece behind the copies.
-struct FirstSearch { int lorder, lsoln, maxstart; };
-
-// Counting sort of entries e_begin .. e_end - 1 by order into `out` (appended at position `pos`): bucket after
-// bucket, inside a bucket the LARGEST entries first (file order among equals) - workgroups are dispatched in
-// list order and a larger entry runs longer, so a launch ends on its cheapest workgroups instead of its dearest
-// (real databases are sorted ascending).  begin[kNumBuckets + 1] / n2max[kNumBuckets] describe the result.
-// (two passes over the entries: seven filtered passes and a stable sort per bucket took 3 ms of an 11 ms
-// upload of the bench shard)
-static void bucket_lists(const int32_t *orders, int e_begin, int e_end, int32_t *out, int pos, int *begin, int *n2max)
-{
-    int count[SAT_MAXDIM + 1] = { 0 }, start[SAT_MAXDIM + 1] = { 0 };
-    for (int e = e_begin; e < e_end; e++) count[orders[e]]++;
-    for (int b = 0; b < kNumBuckets; b++) {
-        begin[b] = pos;
-        n2max[b] = 0;
-        const int lo = b == 0 ? 0 : kBucketMax[b - 1];
-        for (int n = kBucketMax[b] < SAT_MAXDIM ? kBucketMax[b] : SAT_MAXDIM; n > lo; n--) {
-            start[n] = pos;
-            pos += count[n];
-            if (count[n] && n2max[b] == 0) n2max[b] = n;
-        }
-    }
-    begin[kNumBuckets] = pos;
-    for (int e = e_begin; e < e_end; e++) out[(size_t)start[orders[e]]++] = e;
-}
-
-static int upload_impl(sat_ctx *ctx, int n_entries, const int32_t *orders,
-                       const int64_t *cell_off, const uint8_t *tab_tri,
-                       const float *dist_tri, const int64_t *db_ordinal, const FirstSearch *first)
-{
-    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
-    if (n_entries <= 0 || !orders || !cell_off || !tab_tri || !dist_tri)
-        return sat_fail(SAT_EINVAL, "empty database or null array");
-    if (first) {
-        const int rc = check_ready(ctx, false, first->maxstart);
-        if (rc != SAT_OK) return rc;
-    }
-    // header pass on the host (orders, offsets, ordinals: a few bytes per entry).  The CELLS - every
-    // code byte and distance, 331 MB for the bench shard - are checked on the GPU after the copy, at
-    // HBM speed (validate_cells): a host scan of them cost as much as the copy itself.
-    int64_t cells_end = 0;
-    bool ascending = true;                     // entry e + 1 starts at or after the end of entry e
-    for (int e = 0; e < n_entries; e++) {
-        const int n = orders[e];
-        if (n < 1 || n > SAT_MAXDIM)
-            return sat_fail(SAT_EINVAL, "entry %d: order %d outside 1..%d", e, n, SAT_MAXDIM);
-        if (cell_off[e] < 0) return sat_fail(SAT_EINVAL, "entry %d: negative cell offset", e);
-        if (cell_off[e] < cells_end) ascending = false;
-        int64_t end = cell_off[e] + (int64_t)n * (n + 1) / 2;
-        if (end > cells_end) cells_end = end;
-        if (db_ordinal && (db_ordinal[e] < 0 || db_ordinal[e] > 0xFFFFFFFFll))
-            return sat_fail(SAT_EINVAL, "entry %d: db ordinal out of range", e);
-    }
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    free_db(ctx);
-    const bool timing = ctx->tune.upload_timing != 0;
-    auto now_ms = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double t_mark = now_ms();
-    auto lap = [&](const char *what) {
-        if (timing) { const double t = now_ms(); fprintf(stderr, "upload: %-18s %7.3f ms\n", what, t - t_mark); t_mark = t; }
-    };
-
-    const size_t dist_bytes = (size_t)cells_end * sizeof(float), tab_bytes = (size_t)cells_end;
-    // Pieces: with a first search to overlap, the shard goes up in `npieces` runs of whole entries of about
-    // equal cell count, and every piece is checked and searched as soon as it has landed - the GPU works on
-    // piece c while the host threads copy piece c + 1 (the copies are synchronous calls out of the caller's
-    // pageable memory; the kernels run on the context's non-blocking stream).  Needs entries laid out in
-    // ascending order (a piece is then one contiguous cell range); small shards go up in one piece.
-    int npieces = 1;
-    if (first && ascending) {
-        // at least 24 MB of distances per piece (each host thread's slice of it is then still a copy of a
-        // useful size), at most 8: measured on the 331 MB bench shard, 19.4 ms for upload-then-search,
-        // 16.3 / 14.6 / 14.2 / 15.2 / 16.8 ms overlapped in 2 / 4 / 8 / 12 / 16 pieces
-        const size_t by_size = dist_bytes / ((size_t)24 << 20);
-        npieces = ctx->tune.upload_pieces > 0 ? ctx->tune.upload_pieces : (int)(by_size < 8 ? by_size : 8);
-        if (npieces > n_entries) npieces = n_entries;
-        if (npieces < 1) npieces = 1;
-    }
-    std::vector<int> piece_e((size_t)npieces + 1, n_entries);        // piece c = entries piece_e[c] .. piece_e[c+1]-1
-    piece_e[0] = 0;
-    for (int c = 1, e = 0; c < npieces; c++) {
-        const int64_t target = cells_end * c / npieces;
-        while (e < n_entries && cell_off[e] < target) e++;
-        piece_e[(size_t)c] = e > piece_e[(size_t)c - 1] ? e : piece_e[(size_t)c - 1];
-    }
-    auto piece_cell = [&](int c) -> int64_t { return c >= npieces || piece_e[(size_t)c] >= n_entries ? cells_end : (c == 0 ? 0 : cell_off[piece_e[(size_t)c]]); };
-
-    // bucket lists of the whole shard (every later search) and, behind them, of each piece
-    std::vector<int32_t> lists((size_t)n_entries * (npieces > 1 ? 2 : 1));
-    bucket_lists(orders, 0, n_entries, lists.data(), 0, ctx->bucket_begin, ctx->bucket_n2max);
-    std::vector<int> piece_begin((size_t)npieces * (kNumBuckets + 1)), piece_n2max((size_t)npieces * kNumBuckets);
-    if (npieces > 1) {
-        int pos = n_entries;
-        for (int c = 0; c < npieces; c++) {
-            bucket_lists(orders, piece_e[(size_t)c], piece_e[(size_t)c + 1], lists.data(), pos,
-                         &piece_begin[(size_t)c * (kNumBuckets + 1)], &piece_n2max[(size_t)c * kNumBuckets]);
-            pos += piece_e[(size_t)c + 1] - piece_e[(size_t)c];
-        }
-    }
-
-    std::vector<uint32_t> ord(n_entries);
-    for (int e = 0; e < n_entries; e++) ord[e] = db_ordinal ? (uint32_t)db_ordinal[e] : (uint32_t)e;
-
-    lap("host lists");
-    DevBuf<int32_t> d_bad;
-    const int32_t none = 0x7FFFFFFF;
-    // any failure below leaves the context without a database
-    auto body = [&]() -> int {
-        const size_t n = (size_t)n_entries;
-        int rc;
-        // (scores: one row, so that the first search of one query does not re-allocate them - refresh_descriptors)
-        if ((rc = ctx->d_orders.grow(n)) != SAT_OK || (rc = ctx->d_cell_off.grow(n)) != SAT_OK ||
-            (rc = ctx->d_ordinal.grow(n)) != SAT_OK || (rc = ctx->d_lists.grow(lists.size())) != SAT_OK ||
-            (rc = ctx->d_tab.grow((size_t)cells_end)) != SAT_OK || (rc = ctx->d_dist.grow((size_t)cells_end)) != SAT_OK ||
-            (rc = ctx->d_scores.grow(n)) != SAT_OK || (rc = d_bad.grow(1)) != SAT_OK)
-            return rc;
-        lap("hipMalloc");
-        // the headers first: the piece-wise checks and searches read them
-        HIP_TRY(hipMemcpy(ctx->d_orders.get(), orders, n * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(ctx->d_cell_off.get(), cell_off, n * sizeof(int64_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(ctx->d_ordinal.get(), ord.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(ctx->d_lists.get(), lists.data(), lists.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(ctx->d_scores.get(), 0, n * sizeof(int32_t)));
-        HIP_TRY(hipMemcpy(d_bad.get(), &none, sizeof none, hipMemcpyHostToDevice));
-        lap("header copies");
-        ctx->n_entries = n_entries;
-
-        // The two big arrays go up in slices from a few host threads (each slice a synchronous copy out
-        // of the caller's pageable memory: the runtime stages it through its pinned buffers, and several
-        // copies in flight keep the link busy while one thread waits for its staging buffer).  The threads
-        // walk the pieces together and count themselves off per piece; thread 0 queues the check of a
-        // complete piece and (sat_db_upload_search) its search, and goes on copying.
-        unsigned hw = std::thread::hardware_concurrency();
-        int nthreads = (int)(hw ? (hw < 4 ? hw : 4) : 1);
-        if (ctx->tune.upload_threads > 0) nthreads = ctx->tune.upload_threads;
-        if (dist_bytes < ((size_t)32 << 20)) nthreads = 1;
-        std::vector<hipError_t> err((size_t)nthreads, hipSuccess);
-        std::vector<std::atomic<int>> landed((size_t)npieces);
-        for (auto &x : landed) x.store(0);
-        auto copy_piece = [&](int t, int c) {
-            const size_t c0 = (size_t)piece_cell(c), c1 = (size_t)piece_cell(c + 1);
-            auto part = [&](const void *src, void *dst, size_t unit) {
-                const size_t bytes = (c1 - c0) * unit, base = c0 * unit;
-                const size_t lo = (bytes * (size_t)t / (size_t)nthreads) & ~(size_t)255;
-                const size_t hi = t + 1 == nthreads ? bytes : (bytes * (size_t)(t + 1) / (size_t)nthreads) & ~(size_t)255;
-                if (hi > lo && err[(size_t)t] == hipSuccess)
-                    err[(size_t)t] = hipMemcpy((char *)dst + base + lo, (const char *)src + base + lo, hi - lo, hipMemcpyHostToDevice);
-            };
-            part(dist_tri, ctx->d_dist.get(), sizeof(float));
-            part(tab_tri, ctx->d_tab.get(), 1);
-            landed[(size_t)c].fetch_add(1, std::memory_order_release);
-        };
-        // (the runtime takes the copies of all threads through one queue: a thread running ahead into piece
-        // c + 1 would delay the last slice of piece c, and with it the piece's search, so nobody starts a
-        // piece before the one before it is complete)
-        auto piece_complete = [&](int c) {
-            while (landed[(size_t)c].load(std::memory_order_acquire) < nthreads) std::this_thread::yield();
-        };
-        auto helper = [&](int t) {
-            (void)hipSetDevice(ctx->device);
-            for (int c = 0; c < npieces; c++) {
-                copy_piece(t, c);
-                if (c + 1 < npieces) piece_complete(c);
-            }
-        };
-        std::vector<std::thread> pool;
-        for (int t = 1; t < nthreads; t++) pool.emplace_back(helper, t);
-        rc = SAT_OK;
-        for (int c = 0; c < npieces; c++) {
-            copy_piece(0, c);
-            piece_complete(c);
-            if (rc != SAT_OK) continue;                      // (the helpers still finish their copies)
-            // ---- check every cell where it now lives: one wave per entry; the kernel's pair arithmetic needs
-            // tableau nibbles 0..7 (the reader produces 0..4), SSE types 0..3 and |distance| < 1e29 or non-finite.
-            // A search queued behind the check of a bad piece is memory-safe (orders and offsets were checked
-            // above; bad cells only give wrong sums) and its results are thrown away below.
-            const int e0 = piece_e[(size_t)c], e1 = piece_e[(size_t)c + 1];
-            if (e1 <= e0) continue;
-            hipLaunchKernelGGL(validate_cells, dim3((unsigned)((e1 - e0 + 3) / 4)), dim3(256), 0, ctx->stream,
-                               e0, e1, ctx->d_orders.get(), ctx->d_cell_off.get(), ctx->d_tab.get(), ctx->d_dist.get(), d_bad.get());
-            if (hipGetLastError() != hipSuccess) { rc = sat_fail(SAT_EDEVICE, "launch of the cell check failed"); continue; }
-            if (first) {
-                if (npieces > 1) {
-                    const ListView piece = { ctx->d_lists.get(), &piece_begin[(size_t)c * (kNumBuckets + 1)],
-                                             &piece_n2max[(size_t)c * kNumBuckets], e1 - e0 };
-                    rc = launch_search(ctx, first->lorder, first->lsoln, first->maxstart, ctx->stream, &piece);
-                } else {
-                    rc = launch_search(ctx, first->lorder, first->lsoln, first->maxstart, ctx->stream);
-                }
-            }
-        }
-        for (auto &th : pool) th.join();
-        if (rc != SAT_OK) return rc;
-        for (int t = 0; t < nthreads; t++) HIP_TRY(err[(size_t)t]);
-        lap(first ? "cell copies, checks and the search queued" : "cell copies");
-        int32_t bad = none;
-        HIP_TRY(hipStreamSynchronize(ctx->stream));          // a non-blocking stream: the copy below does not wait for it
-        HIP_TRY(hipMemcpy(&bad, d_bad.get(), sizeof bad, hipMemcpyDeviceToHost));
-        lap(first ? "search + validate on GPU" : "validate on GPU");
-        if (bad != none) {
-            // the earliest flagged entry is looked at again on the host, cell by cell, for the message
-            const int e = bad, n = orders[e];
-            for (int i = 0; i < n; i++) {
-                const int64_t rowbase = cell_off[e] + (int64_t)i * (i + 1) / 2;
-                uint8_t ty = tab_tri[rowbase + i];
-                if (ty > 3) return sat_fail(SAT_EINVAL, "entry %d: SSE %d has type code %u (0..3 expected)", e, i, ty);
-                for (int j = 0; j < i; j++) {
-                    if (tab_tri[rowbase + j] & 0x88)
-                        return sat_fail(SAT_EINVAL, "entry %d: tableau code 0x%02x at (%d,%d) has a nibble above 7", e, tab_tri[rowbase + j], i, j);
-                    float d = dist_tri[rowbase + j];
-                    if (std::isfinite(d) && std::fabs(d) >= 1.0e29f)
-                        return sat_fail(SAT_EINVAL, "entry %d: distance %g at (%d,%d) out of range", e, d, i, j);
-                }
-            }
-            return sat_fail(SAT_EINVAL, "entry %d: invalid cell", e);     // not reached: the scan and the re-check agree
-        }
-        return SAT_OK;
-    };
-    const int rc = body();
-    d_bad.reset();
-    if (rc != SAT_OK) {
-        (void)hipStreamSynchronize(ctx->stream);
-        free_db(ctx);
-        return rc;
-    }
-    ctx->h_orders.assign(orders, orders + n_entries);
-    return SAT_OK;
-}
-
-int sat_db_upload_packed(sat_ctx *ctx, int n_entries, const int32_t *orders,
-                         const int64_t *cell_off, const uint8_t *tab_tri,
-                         const float *dist_tri, const int64_t *db_ordinal)
-{
-    return upload_impl(ctx, n_entries, orders, cell_off, tab_tri, dist_tri, db_ordinal, nullptr);
-}
-
-int sat_db_upload_search(sat_ctx *ctx, int n_entries, const int32_t *orders,
-                         const int64_t *cell_off, const uint8_t *tab_tri,
-                         const float *dist_tri, const int64_t *db_ordinal,
-                         int lorder, int lsoln, int maxstart)
-{
-    const FirstSearch first = { lorder, lsoln, maxstart };
-    return upload_impl(ctx, n_entries, orders, cell_off, tab_tri, dist_tri, db_ordinal, &first);
-}
-
-int sat_db_upload_dense(sat_ctx *ctx, int n_entries, const int32_t *orders,
-                        const uint8_t *tabs, const float *dmats, int pitch,
-                        const int64_t *db_ordinal)
-{
-    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
-    if (n_entries <= 0 || !orders || !tabs || !dmats || pitch < 1)
-        return sat_fail(SAT_EINVAL, "empty database or null array");
-    std::vector<int64_t> off(n_entries);
-    int64_t cells = 0;
-    for (int e = 0; e < n_entries; e++) {
-        if (orders[e] < 1 || orders[e] > SAT_MAXDIM || orders[e] > pitch)
-            return sat_fail(SAT_EINVAL, "entry %d: order %d outside 1..min(%d, pitch %d)", e, orders[e], SAT_MAXDIM, pitch);
-        off[e] = cells;
-        cells += (int64_t)orders[e] * (orders[e] + 1) / 2;
-    }
-    std::vector<uint8_t> tt((size_t)cells);
-    std::vector<float> dd((size_t)cells);
-    for (int e = 0; e < n_entries; e++) {
-        const uint8_t *t = tabs + (size_t)e * pitch * pitch;
-        const float *d = dmats + (size_t)e * pitch * pitch;
-        int64_t c = off[e];
-        for (int i = 0; i < orders[e]; i++)
-            for (int j = 0; j <= i; j++, c++) {
-                tt[(size_t)c] = t[(size_t)i * pitch + j];
-                dd[(size_t)c] = d[(size_t)i * pitch + j];
-            }
-    }
-    return sat_db_upload_packed(ctx, n_entries, orders, off.data(), tt.data(), dd.data(), db_ordinal);
-}
-
-int sat_db_size(const sat_ctx *ctx) { return ctx ? ctx->n_entries : 0; }
-
-int sat_queries_set(sat_ctx *ctx, int n_queries, const int32_t *n1s, const uint8_t *qtabs,
-                    const float *qdmats, int pitch, const uint8_t *qssetypes, uint32_t first_query_ordinal)
-{
-    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
-    if (n_queries < 1 || !n1s || !qtabs || !qdmats || !qssetypes || pitch < 1)
-        return sat_fail(SAT_EINVAL, "bad query batch (n_queries=%d pitch=%d)", n_queries, pitch);
-    std::vector<sat_ctx::QueryInfo> infos((size_t)n_queries);
-    size_t blob_bytes = 0;
-    for (int qi = 0; qi < n_queries; qi++) {
-        const int n1 = n1s[qi];
-        if (n1 < 1 || n1 > SAT_MAXDIM || n1 > pitch)
-            return sat_fail(SAT_EINVAL, "query %d: order %d outside 1..min(%d, pitch %d)", qi, n1, SAT_MAXDIM, pitch);
-        auto &q = infos[(size_t)qi];
-        q.n1 = n1;
-        q.n1p = n1 <= 16 ? 16 : (n1 <= 32 ? 32 : (n1 <= 64 ? 64 : 112));
-        q.ordinal = first_query_ordinal + (uint32_t)qi;
-        q.blob_off = blob_bytes;
-        q.ssemap_off = 0;
-        const size_t groups = (size_t)q.n1p / 4 * q.n1p;
-        // grouped cells (16 + 4 bytes per group and column), SSE types, then the dense pair cells of the full score
-        blob_bytes += ((groups * 20 + (size_t)q.n1p + 15) & ~(size_t)15) + (size_t)q.n1p * q.n1p * 8;
-    }
-    // grouped, transposed query: group kw, column i holds dmat1[i][4kw..4kw+3] and the four code
-    // bytes tab1[i][4kw..4kw+3]; diagonal, padding and non-finite distances get the sentinel
-    // so they never score (the reference excludes k == i, K.cu:524, and NaN never passes <= 4)
-    std::vector<uint8_t> blob(blob_bytes, 0);
-    for (int qi = 0; qi < n_queries; qi++) {
-        const auto &q = infos[(size_t)qi];
-        const int n1 = q.n1, n1p = q.n1p, groups = n1p / 4;
-        const uint8_t *qtab = qtabs + (size_t)qi * pitch * pitch;
-        const float *qdmat = qdmats + (size_t)qi * pitch * pitch;
-        const uint8_t *types = qssetypes + (size_t)qi * pitch;
-        float4 *qdist = reinterpret_cast<float4 *>(blob.data() + q.blob_off);
-        uint32_t *qcode = reinterpret_cast<uint32_t *>(blob.data() + q.blob_off + (size_t)groups * n1p * 16);
-        uint8_t *qtypes = blob.data() + q.blob_off + (size_t)groups * n1p * 20;
-        // dense [i][k] cells {distance, code byte}: the same values as the grouped arrays, for the pair-by-pair
-        // full score of an initial map
-        uint32_t *qpair = reinterpret_cast<uint32_t *>(blob.data() + q.blob_off + (((size_t)groups * n1p * 20 + (size_t)n1p + 15) & ~(size_t)15));
-        for (int i = 0; i < n1p; i++)
-            for (int k = 0; k < n1p; k++) {
-                float d = SAT_K_QSENT;
-                uint32_t code = 0;
-                if (k < n1 && i < n1 && k != i) {
-                    const float v = qdmat[(size_t)i * pitch + k];
-                    if (std::isfinite(v)) d = v;                  // (range and nibbles are checked below)
-                    code = qtab[(size_t)i * pitch + k];
-                }
-                memcpy(&qpair[((size_t)i * n1p + k) * 2], &d, sizeof d);
-                qpair[((size_t)i * n1p + k) * 2 + 1] = code;
-            }
-        for (int i = 0; i < n1; i++) {
-            if (types[i] > 3)
-                return sat_fail(SAT_EINVAL, "query %d: SSE %d has type code %u (0..3 expected)", qi, i, types[i]);
-            qtypes[i] = types[i];
-        }
-        for (int kw = 0; kw < groups; kw++)
-            for (int i = 0; i < n1p; i++) {
-                float d[4];
-                uint32_t codes = 0;
-                for (int sidx = 0; sidx < 4; sidx++) {
-                    const int k = 4 * kw + sidx;
-                    d[sidx] = SAT_K_QSENT;
-                    if (k < n1 && i < n1 && k != i) {
-                        const float v = qdmat[(size_t)i * pitch + k];
-                        const uint32_t code = qtab[(size_t)i * pitch + k];
-                        if (code & 0x88)
-                            return sat_fail(SAT_EINVAL, "query %d: tableau code 0x%02x at (%d,%d) has a nibble above 7", qi, code, i, k);
-                        if (std::isfinite(v)) {
-                            if (std::fabs(v) >= 1.0e29f)
-                                return sat_fail(SAT_EINVAL, "query %d: distance %g at (%d,%d) out of range", qi, v, i, k);
-                            d[sidx] = v;
-                        }
-                        codes |= code << (8 * sidx);
-                    }
-                }
-                qdist[(size_t)kw * n1p + i] = float4{ d[0], d[1], d[2], d[3] };
-                qcode[(size_t)kw * n1p + i] = codes;
-            }
-    }
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    ctx->d_qblob.reset();
-    ctx->d_qdesc.reset();
-    int rc;
-    if ((rc = ctx->d_qblob.grow(blob_bytes)) != SAT_OK || (rc = ctx->d_qdesc.grow((size_t)n_queries)) != SAT_OK) return rc;
-    HIP_TRY(hipMemcpy(ctx->d_qblob.get(), blob.data(), blob_bytes, hipMemcpyHostToDevice));
-    ctx->queries.swap(infos);
-    ctx->desc_dirty = true;
-    ctx->searched_nq = 0;                     // the result buffers no longer belong to the current batch
-    ctx->fits.clear();
-    return SAT_OK;
-}
-
-int sat_query_set(sat_ctx *ctx, int n1, const uint8_t *qtab, const float *qdmat,
-                  int pitch, const uint8_t *qssetypes, uint32_t query_ordinal)
-{
-    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
-    if (n1 < 1 || n1 > SAT_MAXDIM || !qtab || !qdmat || !qssetypes || pitch < n1)
-        return sat_fail(SAT_EINVAL, "bad query (n1=%d pitch=%d)", n1, pitch);
-    // a batch of one; the type vector is only read up to n1, so its stride does not matter
-    const int32_t n1s[1] = { n1 };
-    return sat_queries_set(ctx, 1, n1s, qtab, qdmat, pitch, qssetypes, query_ordinal);
 }
 
 int sat_query_count(const sat_ctx *ctx) { return ctx ? (int)ctx->queries.size() : 0; }
@@ -1667,42 +871,6 @@ int sat_query_order(const sat_ctx *ctx) { return (ctx && !ctx->queries.empty()) 
 unsigned long long sat_stat_d2h_bytes(const sat_ctx *ctx) { return ctx ? ctx->d2h_bytes : 0ull; }
 
 const char *sat_last_launch_info(const sat_ctx *ctx) { return ctx ? ctx->last_launch_info.c_str() : ""; }
-
-void sat_debug_lds_layout(int m2w, int n1, int n1p, int n2, int chains, int threads, int q_in_lds, int compact,
-                          uint32_t out[11])
-{
-    // m2w: low byte = words of a db-side set; bits 8-9 = 1 + cell layout (SAT_CELLS_*), 0 = the layout launches of
-    // such entries get (satk::cell_layout)
-    const int cells = (m2w >> 8) ? ((m2w >> 8) & 3) - 1 : satk::cell_layout(n2);
-    m2w &= 0xFF;
-    const satk::LdsLayout L = satk::lds_layout(m2w, cells, n2, satk::map_words((n1 + 3) >> 2), n1p, chains, threads,
-                                               q_in_lds != 0, compact != 0);
-    const uint32_t v[11] = { L.code, L.qdist, L.qcode, L.smap, L.tmask, L.qtypes, L.leader, L.red, L.red_stride, L.items, L.total };
-    for (int i = 0; i < 11; i++) out[i] = v[i];
-}
-
-// satabsearch_debug.h: every instantiation pick_sa_kernel can choose, named as sat_last_launch_info names it, one per
-// line in the order of the walk (family, class, set width and layout, QLDS, OPT, WPL).  Host only: the walk takes the
-// addresses of the kernels' host stubs, which also tell two instantiations apart.
-const char *sat_debug_sa_instances(void)
-{
-    static const std::string list = [] {
-        const int layouts[4][2] = { { 1, SAT_CELLS_FULL8 }, { 2, SAT_CELLS_FULL5 }, { 2, SAT_CELLS_TRI5 }, { 4, SAT_CELLS_TRI5 } };
-        std::set<const void *> seen;
-        std::string out;
-        for (int mode = kPlain; mode <= kPairMatch; mode++)
-            for (int n1p : kClassN1P)
-                for (const auto &l : layouts)
-                    for (int qlds = 0; qlds < 2; qlds++)
-                        for (int opt = -1; opt <= 11; opt++)
-                            for (int wpl = 0; wpl <= 4; wpl++) {
-                                const SaKernel k = pick_sa_kernel(mode, n1p, l[0], l[1], qlds != 0, opt, wpl);
-                                if (seen.insert(k.fn).second) out += sa_kernel_name(k) + "\n";
-                            }
-        return out;
-    }();
-    return list.c_str();
-}
 
 int sat_sync(sat_ctx *ctx)
 {

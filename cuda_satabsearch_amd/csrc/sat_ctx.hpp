@@ -1,30 +1,16 @@
-// sat_ctx.hpp - private definition of the C ABI's context (shared by sat_capi.hip and
-// sat_topk.hip; not part of the public interface).
+// sat_ctx.hpp - private definition of the C ABI's context (shared by the library's translation units except
+// sat_launch.hip; not part of the public interface).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <map>
 #include <string>
-#include <tuple>
-#include <unordered_set>
 #include <utility>
 #include <vector>
 
 #include "satabsearch.h"
 #include "sat_sa_kernel.hpp"
-
-// sets sat_last_error() text and returns `code`
-int sat_fail(int code, const char *fmt, ...);
-
-// a failed HIP call: sat_fail with its text, SAT_ENOMEM or SAT_EDEVICE
-#define HIP_TRY(expr)                                                                       \
-    do {                                                                                    \
-        hipError_t err__ = (expr);                                                          \
-        if (err__ != hipSuccess)                                                            \
-            return sat_fail(err__ == hipErrorOutOfMemory ? SAT_ENOMEM : SAT_EDEVICE,        \
-                            "%s failed: %s", #expr, hipGetErrorString(err__));              \
-    } while (0)
+#include "sat_launch.hpp"               // sat_fail, HIP_TRY; the launch code's part of the context
 
 // A device array of T that owns its allocation: the pointer and its capacity in elements live and die together.
 // Freed on destruction or reset(), on whatever device is current then (the owners make theirs current first).
@@ -84,7 +70,10 @@ template <typename T> class DevBuf {
     size_t cap_ = 0;
 };
 
+// db entries are launched in classes of similar order so that every launch sizes its
+// LDS for the largest member of the class only
 constexpr int kNumBuckets = 7;
+constexpr int kBucketMax[kNumBuckets] = { 16, 32, 48, 64, 80, 96, 111 };
 
 struct sat_ctx {
     int device = 0;
@@ -122,12 +111,12 @@ struct sat_ctx {
     DevBuf<float> d_ptab;
     DevBuf<int32_t> d_prow;
 
-    // launch-heuristic overrides (SAT_EXP_* in satabsearch.h), read ONCE when the context is created
-    struct Tuning { int compact = -1, qlds = -1, lpc = -1, general = 0, streams = -1, upload_threads = 0, upload_timing = 0, upload_pieces = 0, epw = 0, lpc_waves = 0, chains = 0, refine_split = 0; size_t lds_pad = 0; } tune;
-    // kernel instantiations whose dynamic-LDS limit has been raised on this device
-    std::unordered_set<const void *> lds_attr_done;
-    // entries per workgroup chosen for (instantiation, threads per entry, LDS bytes per entry): asked once
-    std::map<std::tuple<const void *, int, size_t>, int> epw_choice;
+    // overrides (SAT_EXP_* in satabsearch_debug.h), read ONCE when the context is created: these of the search plan,
+    // the upload and the pair split, the launch heuristics' in `sa`
+    struct Tuning { int streams = -1, upload_threads = 0, upload_timing = 0, upload_pieces = 0, refine_split = 0; } tune;
+    // what sat_launch.hip keeps per context: its overrides, the instantiations whose dynamic-LDS limit has been raised
+    // on this device, the entries per workgroup chosen so far
+    SaLaunchState sa;
     // side streams: the order buckets of one search run concurrently (each launch has a tail of
     // half-empty CUs; the next bucket's workgroups fill it), forked from / joined to `stream`
     hipStream_t side_stream[kNumBuckets] = { nullptr };
@@ -190,10 +179,31 @@ struct sat_ctx {
     // bytes copied device -> host by this context's result calls (sat_stat_d2h_bytes)
     unsigned long long d2h_bytes = 0;
     // kernel instantiations and launch geometry of the last search (sat_last_launch_info; one launch_info() of
-    // sat_capi.hip per launch, from the SaKernel that was launched)
+    // sat_launch.hip per launch, from the SaKernel that was launched)
     std::string last_launch_info;
 };
 
+// ---- sat_db.hip.  (Re)build the device query descriptors - pointers into the query blob and into the result buffers,
+// grouped by size class - where the batch, the result buffers or `lsoln` changed; load the file's code object.
+int refresh_descriptors(sat_ctx *ctx, bool lsoln, hipStream_t stream);
+int sat_db_load_code(sat_ctx *ctx);
+
+// ---- sat_capi.hip, for the overlapped upload of sat_db.hip.  The entries a set of launches covers: indices into the
+// resident shard grouped by order bucket.  A search covers the whole shard (the context's lists); the overlapped upload
+// (sat_db_upload_search) searches the shard piece by piece, each piece with lists of its own.
+struct ListView {
+    const int32_t *d_list;       // device array the `begin` offsets index
+    const int *begin;            // [kNumBuckets + 1]
+    const int *n2max;            // [kNumBuckets] largest order per bucket, 0 = empty
+    int n;                       // entries covered = begin[kNumBuckets] - begin[0]
+};
+// The preconditions of queuing a search, checked in this order: a context, a database (need_db), a query batch,
+// maxstart >= 1.
+int check_ready(const sat_ctx *ctx, bool need_db, int maxstart);
+// Queue a search of `piece` (null: the whole shard) on `stream`.  mx: one pass of the match mode (sat_search_matches)
+// instead of a plain search; lsoln is 0 then.
+int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t stream, const ListView *piece = nullptr,
+                  const SatMatchArgs *mx = nullptr);
 
 // The two halves of sat_search_matches (sat_capi.hip), for sat_multi_search_matches: queue both passes on the
 // context's stream, then wait and copy query q's row of entry e to row q * total + offset + e of the caller's arrays

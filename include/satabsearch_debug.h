@@ -4,14 +4,14 @@
  * keyed by query / db ordinal / restart, not by the launch shape); they are read ONCE by sat_ctx_create, never on
  * the search path.  Nothing here is needed to use the library.
  *
- *   SAT_EXP_LPC = 0|1|2          log2 lanes per restart chain (default: by LDS occupancy, size_workgroup in sat_capi.hip)
+ *   SAT_EXP_LPC = 0|1|2          log2 lanes per restart chain (default: by LDS occupancy, size_workgroup in sat_launch.hip)
  *   SAT_EXP_LPC_WAVES = n        resident waves per CU at which that choice stops adding lanes (default 8; 12 for queries above 64 SSEs)
  *   SAT_EXP_CHAINS = 64|128|192 restart chains per workgroup (default: one per restart, at most 256)
  *   SAT_EXP_COMPACT = 0|1        wave-level work compaction of the SA step (default: exactly when LORDER)
  *   SAT_EXP_QLDS = 0|1           query cells staged in LDS (default: queries of up to 16 SSEs)
  *   SAT_EXP_LDS_PAD = bytes      unused LDS added per db entry (occupancy experiments)
  *   SAT_EXP_EPW = 1..8           db entries per workgroup (default: chosen per launch from the CU's LDS granules)
- *   SAT_EXP_GENERAL = 1          the general kernel instantiation instead of the option-specialised ones (prepare_sa in sat_capi.hip)
+ *   SAT_EXP_GENERAL = 1          the general kernel instantiation instead of the option-specialised ones (prepare_sa in sat_launch.hip)
  *   SAT_EXP_REFINE_SPLIT = n     restarts per work item of a pair search (sat_search_pairs, sat_search_pairs_matches,
  *                                stage 2 of sat_search_refine; default: chosen so that the pairs x items fill the GPU,
  *                                whole rounds of the chains)

@@ -1,7 +1,7 @@
 // Test helper (never loaded by the product): how many workgroups of T threads with S bytes of dynamic LDS are
 // resident on one CU at the same time.  Every workgroup counts itself in, records the peak, waits ~100 us and
 // counts itself out; with many more workgroups than the chip holds the peak is CUs x (resident per CU).
-// The launch sizing (csrc/sat_capi.hip pick_epw) assumes 128 LDS granules of 1280 bytes per CU.
+// The launch sizing (csrc/sat_launch.hip pick_epw) assumes 128 LDS granules of 1280 bytes per CU.
 #include <hip/hip_runtime.h>
 
 __global__ void occupy(int *live, int *peak, unsigned long long ticks)

@@ -1,14 +1,14 @@
 """Every instantiation of the SA kernel against the CPU reference, by name (-m gpu).
 
 The SA kernel is compiled 328 times (sat_debug_sa_instances lists them: 200 plain, 32 match, 64 pair, 32 pair-match);
-pick_sa_kernel (sat_capi.hip) chooses among them at run time.  For every one of them this module holds a RECIPE - an API
+pick_sa_kernel (sat_launch.hip) chooses among them at run time.  For every one of them this module holds a RECIPE - an API
 call, a query batch, a database, LORDER / LSOLN and SAT_EXP_* overrides - that makes the default host path launch exactly
 that kernel, and asserts (a) that sat_last_launch_info() names it for the pass in question and (b) that the results are
 the CPU reference's bit for bit.  The expected name of a recipe is worked out HERE from the recipe (the rules of
 prepare_sa / pick_sa_kernel written down once more, below), never read from the enumeration: a dispatcher that picks
 another kernel than the rules promise fails (a), whatever it computes.
 
-How a recipe steers each template argument (all from sat_capi.hip):
+How a recipe steers each template argument (sat_launch.hip, sat_capi.hip, sat_db.hip):
   family   the API call: search / search_matches / search_pairs / search_pairs_matches.
   N1P      the query order: <= 16, <= 32, <= 64, above (sat_queries_set).
   M2W, CELLS   entries x queries of a class <= 4096 go out as ONE launch laid out for the database's largest entry

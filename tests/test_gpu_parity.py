@@ -761,7 +761,7 @@ def test_full_size_properties():
 
 # ---------------------------------------------------------------- the hardware fact the launch sizing uses
 def test_lds_is_handed_out_in_128_granules_of_1280_bytes():
-    """resident_by_lds, which pick_epw and size_workgroup of cuda_satabsearch_amd/csrc/sat_capi.hip size launches
+    """resident_by_lds, which pick_epw and size_workgroup of cuda_satabsearch_amd/csrc/sat_launch.hip size launches
     with, counts resident entries per CU as 128 / ceil(bytes / 1280): the CU hands
     out its 160 KB of LDS in 1280-byte granules.  Measured here with workgroups that count themselves
     in and out (tests/native/lds_residency.hip): the workgroups resident on a CU drop exactly where a

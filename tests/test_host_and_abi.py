@@ -48,6 +48,35 @@ def test_the_dispatcher_lists_its_328_instantiations():
     assert out.splitlines() == names
 
 
+def test_the_kernel_source_hash_covers_the_kernel_translation_unit_and_nothing_else():
+    """build.kernel_source_hash() stamps profiles/bench_traffic.json: it hashes sat_launch.hip - the only file that
+    instantiates the SA kernels - and the files of csrc/ that one reaches through #include "..." (diag/ apart: only
+    -DSAT_DIAG builds read it).  The context is not among them, so a new buffer or entry point does not touch the hash.
+    Source text only."""
+    import hashlib
+    from cuda_satabsearch_amd import build
+    csrc = os.path.join(ROOT, "cuda_satabsearch_amd", "csrc")
+    closure, todo = set(), ["sat_launch.hip"]
+    while todo:
+        f = todo.pop()
+        if f in closure:
+            continue
+        closure.add(f)
+        for name in re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', open(os.path.join(csrc, f)).read(), re.M):
+            if not name.startswith("diag/") and os.path.exists(os.path.join(csrc, name)):
+                todo.append(name)
+    assert closure == set(build.KERNEL_SOURCES) == {"sat_sa_kernel.hpp", "sat_sa_body.inc", "sat_launch.hpp", "sat_launch.hip"}
+    assert "sat_ctx.hpp" not in closure
+    h = hashlib.sha256()
+    for f in build.KERNEL_SOURCES:
+        h.update(open(os.path.join(csrc, f), "rb").read())
+    assert build.kernel_source_hash() == h.hexdigest()
+    # and no other translation unit of the library instantiates an SA kernel
+    for f in build.DEVICE_SOURCES:
+        text = open(os.path.join(csrc, f)).read()
+        assert (re.search(r"\bsat_sa_(pair_|match_|pair_match_)?kernel\s*<", text) is not None) == (f == "sat_launch.hip"), f
+
+
 def test_a_build_without_the_instance_hook_still_loads(monkeypatch):
     """SAT_DEVICE_LIB loads other builds of the ABI (A/B runs, the diagnostic twin): the hook of satabsearch_debug.h is
     not part of the ABI, so a library from before it must load, and only asking for the list fails."""
