@@ -31,6 +31,7 @@ ABI_SYMBOLS = (
     "sat_score_histogram", "sat_stats_fit", "sat_stats_set",
     "sat_multi_score_histogram", "sat_multi_stats_set", "sat_multi_search_fit",
     "sat_search_pairs_polish", "sat_search_refine_polish", "sat_multi_search_pairs_polish", "sat_multi_search_refine_polish",
+    "sat_polish_all_set", "sat_polish_all_get", "sat_results_base", "sat_multi_polish_all_set",
 )
 
 STAT_BINS = 4096
@@ -142,6 +143,12 @@ def device_lib():
         lib.sat_search_refine_polish.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.sat_multi_search_refine_polish.argtypes = lib.sat_search_refine_polish.argtypes + [C.POINTER(C.c_double)]
+        # (a build of the parent commit loaded through SAT_DEVICE_LIB for an A/B run predates the whole-database polish)
+        if hasattr(lib, "sat_polish_all_set"):
+            lib.sat_polish_all_set.argtypes = [C.c_void_p, C.c_int]
+            lib.sat_polish_all_get.argtypes = [C.c_void_p]
+            lib.sat_results_base.argtypes = [C.c_void_p, C.c_void_p]
+            lib.sat_multi_polish_all_set.argtypes = [C.c_void_p, C.c_int]
         lib.sat_hits_cutoff.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         lib.sat_multi_search_cutoff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                                 C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]

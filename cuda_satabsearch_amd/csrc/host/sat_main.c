@@ -32,7 +32,8 @@
  * sat_gumbel.h; the listing fits on the host, -k / -p on the GPUs from a histogram, so that still only the printed rows
  * leave them), -P T (polish: the rows of -k K are the K best of each query's C best entries after the own-best maps of
  * every candidate's T best restarts were climbed to local optima of the search's neighbourhood on the GPU; a fourth header
- * line "# POLISH ...").
+ * line "# POLISH ..."), -A (with -P T: polish EVERY row of the search - the whole-database mode of the library - and take
+ * the ordinary route of the other options on the polished rows: the listing, -k, -p, -F; "# POLISH tops = T all rows").
  */
 #include <math.h>
 #include <stdarg.h>
@@ -67,11 +68,12 @@ static double now_ms(void)
 #pragma weak sat_multi_search_pairs_matches
 #pragma weak sat_multi_search_fit
 #pragma weak sat_multi_search_refine_polish
+#pragma weak sat_multi_polish_all_set
 
 static void usage(const char *prog)
 {
     fprintf(stderr, "Usage: %s [-c] [-q dbfile] [-r restarts] [-g gpus] [-G gpu,gpu,...] [-s seed] [-k K] [-p P]\n"
-                    "       [-m M] [-M M] [-R restarts [-C C]] [-F censor] [-P T] [-b]\n", prog);
+                    "       [-m M] [-M M] [-R restarts [-C C]] [-F censor] [-P T] [-A] [-b]\n", prog);
     fprintf(stderr, "  -c : run on host CPU not GPU card\n");
     fprintf(stderr, "  -q dbfile : database is read from dbfile, list of query\n"
                     "              ids is read from stdin\n");
@@ -94,6 +96,8 @@ static void usage(const char *prog)
     fprintf(stderr, "  -P T : polish: rank each query's C best entries (-C, default K) after the maps of their T (1..%d)\n"
                     "         best restarts (of -R restarts, default -r) were climbed to local optima; rows as -k, with\n"
                     "         the polished scores and maps (GPU mode, needs -k)\n", SAT_MAX_MATCHES);
+    fprintf(stderr, "  -A : with -P T: all rows - polish every row of the search instead of C candidates; the listing, -k, -p\n"
+                    "       and -F then work on the polished scores and maps (not with -c, -m, -M, -R, -C)\n");
     fprintf(stderr, "  -b : cache the parsed database as dbfile.satbin\n");
     exit(1);
 }
@@ -238,6 +242,7 @@ typedef struct {
     int rowmatch;                     /* -M: matches of each printed row */
     int fit;                          /* -F: statistics fitted to each query's own scores */
     int polish;                       /* -P: maps polished per candidate */
+    int polish_all;                   /* -P T -A: maps polished per row of every search (then polish is 0) */
     double censor;                    /* -F: the right-censored fraction of the rows */
     double pmax;                      /* -p: the largest p-value printed */
     unsigned long long seed;
@@ -360,7 +365,7 @@ static void parse_options(int argc, char *argv[], options *o)
 {
     *o = (options){ .use_gpu = 1, .maxstart = 128, .want_gpus = 1, .seed = SAT_DEFAULT_SEED };
     int c;
-    while ((c = getopt(argc, argv, "cq:r:g:G:s:bk:p:m:M:R:C:F:P:")) != -1) {
+    while ((c = getopt(argc, argv, "cq:r:g:G:s:bk:p:m:M:R:C:F:P:A")) != -1) {
         char *end = NULL;
         long v;
         switch (c) {
@@ -374,6 +379,7 @@ static void parse_options(int argc, char *argv[], options *o)
             break;
         case 's': o->seed = strtoull(optarg, NULL, 0); break;
         case 'b': o->bincache = 1; break;
+        case 'A': o->polish_all = 1; break;
         case 'k': o->topk = atoi(optarg); break;
         case 'p':
             /* the whole argument, a finite number >= 0 */
@@ -430,6 +436,18 @@ static void parse_options(int argc, char *argv[], options *o)
             break;
         default: usage(argv[0]);
         }
+    }
+    if (o->polish_all) {
+        /* all rows: the mode of the library; from here on the run is an ordinary one on polished rows */
+        if (!o->polish) die("ERROR: -A needs -P T\n");
+        if (!o->use_gpu) die("ERROR: -A cannot be combined with -c\n");
+        if (o->nmatch) die("ERROR: -A cannot be combined with -m\n");
+        if (o->rowmatch) die("ERROR: -A cannot be combined with -M\n");
+        if (o->refine) die("ERROR: -A cannot be combined with -R\n");
+        if (o->ncand) die("ERROR: -A cannot be combined with -C\n");
+        if (!sat_multi_polish_all_set) die("ERROR: this library has no sat_multi_polish_all_set\n");
+        o->polish_all = o->polish;
+        o->polish = 0;
     }
     if (o->polish && !o->use_gpu) die("ERROR: -P needs the GPU path\n");
     if (o->polish && o->nmatch) die("ERROR: -P cannot be combined with -m\n");
@@ -896,6 +914,11 @@ static int run_gpu(const options *o, const input *in)
     if (o->polish)
         snprintf(polish_header, sizeof polish_header, "# POLISH tops = %d restarts = %d candidates = %d\n", o->polish,
                  o->refine ? o->refine : o->maxstart, o->ncand);
+    if (o->polish_all) {
+        snprintf(polish_header, sizeof polish_header, "# POLISH tops = %d all rows\n", o->polish_all);
+        if (sat_multi_polish_all_set(multi, o->polish_all) != SAT_OK)
+            die("ERROR: %s\n", sat_last_error());
+    }
     /* -F: every query's fit - from the GPUs with -k / -p, else made here from the listing's scores (the whole
      * database's, both size classes: a query's two blocks carry the same line) */
     sat_fit *fits = o->fit ? checked(calloc((size_t)in->num_queries, sizeof(sat_fit))) : NULL;
@@ -933,6 +956,8 @@ static int run_gpu(const options *o, const input *in)
         if (o->polish)
             fprintf(stderr, "polish: %d candidates per query x %d restarts, %d maps each\n", o->ncand < total ? o->ncand : total,
                     o->refine ? o->refine : o->maxstart, o->polish);
+        else if (o->polish_all)
+            fprintf(stderr, "polish: every row, %d maps each\n", o->polish_all);
         else if (o->refine)
             fprintf(stderr, "refine: stage 2 %f ms, %d candidates per query x %d restarts\n", ms_stage2,
                     o->ncand < total ? o->ncand : total, o->refine);

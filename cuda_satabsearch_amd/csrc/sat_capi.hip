@@ -254,6 +254,7 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
         }
     ctx->searched_nq = ctx->queries.size();
     ctx->searched_lsoln = lsoln != 0;
+    ctx->searched_polished = false;
     ctx->fits.clear();                                   // a fit belongs to the scores it was made from
     ctx->last_launch_info.clear();
     for (size_t i = 0; i < plan.size(); i++) {
@@ -603,7 +604,7 @@ int sat_pairs_collect(sat_ctx *ctx, int npairs, int32_t *scores, int32_t *ssemap
 // (maps) its map pass before the next one reuses the scratch.
 // polish (sat_polish.hip): the selection without the set test, and behind the map pass the polish of the picked maps.
 int sat_pair_matches_launch(sat_ctx *ctx, int lorder, int maxstart, int max_matches, bool maps, const int32_t *query,
-                            const int32_t *entry, int npairs, bool polish)
+                            const int32_t *entry, int npairs, bool polish, bool packed)
 {
     PairMatchPass pm{};
     int rc = match_args(ctx, max_matches, pm.mx);
@@ -676,10 +677,22 @@ int sat_pair_matches_launch(sat_ctx *ctx, int lorder, int maxstart, int max_matc
         }
         if (maps && (rc = launch_pair_pass(ctx, lorder, true, 1, ctx->d_pitems.get(), ch.grp, map_info, &pm)) != SAT_OK)
             return rc;
-        // the polish walks the launch's map items: one per pair, with its descriptor and entry
-        if (polish && (rc = sat_polish_run(ctx, lorder, ctx->d_pitems.get() + ch.grp.moff.front(), ch.n, max_matches, n2_all, npairs,
-                                           pm.mx.counts, pm.mx.scores, pm.mx.restarts, pm.mx.maps)) != SAT_OK)
-            return rc;
+        // the polish walks the launch's map items: one per pair, with its descriptor and entry.  An item group's entries
+        // share an order bucket, and with it the width the polish runs at; neighbouring groups of one width go in one
+        // launch (every launch ends on its slowest maps: fewer launches, fewer tails)
+        if (polish)
+            for (size_t g = 0; g < ch.grp.gcls.size();) {
+                const int width = sat_polish_width(ctx, ch.n, max_matches, ch.grp.gn2[g], packed);
+                int n2max = ch.grp.gn2[g];
+                size_t h = g + 1;
+                for (; h < ch.grp.gcls.size() && sat_polish_width(ctx, ch.n, max_matches, ch.grp.gn2[h], packed) == width; h++)
+                    n2max = std::max(n2max, ch.grp.gn2[h]);
+                const int n = (int)(ch.grp.moff[h] - ch.grp.moff[g]);
+                if (n > 0 && (rc = sat_polish_run(ctx, lorder, ctx->d_pitems.get() + ch.grp.moff[g], n, max_matches, n2max, npairs,
+                                                  pm.mx.counts, pm.mx.scores, pm.mx.restarts, pm.mx.maps, width)) != SAT_OK)
+                    return rc;
+                g = h;
+            }
     }
     char head[128];
     snprintf(head, sizeof head, "record pass (%d restarts, %d per item, %zu launches of up to %d pairs): ", maxstart, split,
@@ -717,6 +730,63 @@ int sat_pair_matches_collect(sat_ctx *ctx, int max_matches, int npairs, int32_t 
                 expand_map(mp.data() + (p * M + m) * SAT_MAXDIM, ctx->queries[(size_t)query[p]].n1, (int32_t)m < counts[p],
                            ssemaps + (p * M + m) * SAT_MAXDIM);
     }
+    return SAT_OK;
+}
+
+// sat_ctx.hpp: the polished form of a plain whole-shard search (the context's polish_all maps per row)
+int sat_polish_all_launch(sat_ctx *ctx, int lorder, int lsoln, int maxstart)
+{
+    int rc = check_ready(ctx, true, maxstart);
+    if (rc != SAT_OK) return rc;
+    const int tops = ctx->polish_all;
+    HIP_TRY(hipSetDevice(ctx->device));
+    // the descriptors carry the rows' destinations: the score rows and, with lsoln, the map blocks
+    if ((rc = refresh_descriptors(ctx, lsoln != 0, ctx->stream)) != SAT_OK) return rc;
+    const size_t N = (size_t)ctx->n_entries, nq = ctx->queries.size(), rows = nq * N;
+    if ((rc = ctx->d_base.grow_after(ctx->stream, ctx->d_scores.capacity())) != SAT_OK ||
+        (rc = ctx->d_polerr.grow_after(ctx->stream, 1)) != SAT_OK)
+        return rc;
+    HIP_TRY(hipMemsetAsync(ctx->d_polerr.get(), 0, sizeof(int32_t), ctx->stream));
+    // a launch: as many rows as sat_pair_matches_launch takes in one launch of its own, at most kPolishAllPairs
+    int n2_all = 0;
+    for (size_t e = 0; e < N; e++) n2_all = std::max(n2_all, ctx->h_orders[e]);
+    const size_t slab_words = (size_t)(1 + satk::set_words(n2_all)) * (size_t)maxstart;
+    const size_t chunk = std::min<size_t>(std::min<size_t>(rows, (size_t)kPolishAllPairs), std::max<size_t>(1, (((size_t)1 << 30) / 4) / slab_words));
+    std::vector<int32_t> query, entry;
+    size_t launches = 0;
+    for (size_t r0 = 0; r0 < rows; r0 += chunk, launches++) {
+        const size_t n = std::min(chunk, rows - r0);
+        query.resize(n);
+        entry.resize(n);
+        for (size_t x = 0; x < n; x++) {
+            query[x] = (int32_t)((r0 + x) / N);
+            entry[x] = (int32_t)((r0 + x) % N);
+        }
+        // (the call waits for the launch before it: its tables and outputs are this launch's alone)
+        if ((rc = sat_pair_matches_launch(ctx, lorder, maxstart, tops, true, query.data(), entry.data(), (int)n, true, true)) != SAT_OK)
+            return rc;
+        const size_t n_score = ctx->h_pitems.size() - n;          // the map items, one per pair, stand behind the score items
+        if ((rc = sat_polish_scatter(ctx, ctx->d_pitems.get() + n_score, (int)n, (int)n, lsoln != 0)) != SAT_OK) return rc;
+    }
+    char head[96];
+    snprintf(head, sizeof head, "polish all (%d tops, %zu launches of up to %zu pairs): ", tops, launches, chunk);
+    ctx->last_launch_info = head + ctx->last_launch_info;
+    ctx->searched_nq = nq;
+    ctx->searched_lsoln = lsoln != 0;
+    ctx->searched_polished = true;
+    ctx->fits.clear();                                   // a fit belongs to the scores it was made from
+    return SAT_OK;
+}
+
+int sat_polish_all_check(sat_ctx *ctx)
+{
+    if (!ctx->searched_polished || ctx->searched_nq != ctx->queries.size()) return SAT_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    int32_t err = 0;
+    HIP_TRY(hipMemcpy(&err, ctx->d_polerr.get(), sizeof err, hipMemcpyDeviceToHost));
+    if (err)
+        return sat_fail(SAT_EDEVICE, "a row's polish did not finish (records and arg-max key disagree, or the move cap was reached)");
     return SAT_OK;
 }
 
@@ -793,6 +863,7 @@ sat_ctx *sat_ctx_create(int device, uint64_t seed)
         ctx->sa.lpc_waves = env_int("SAT_EXP_LPC_WAVES", 0);
         ctx->sa.chains = env_int("SAT_EXP_CHAINS", 0);
         ctx->tune.refine_split = env_int("SAT_EXP_REFINE_SPLIT", 0);
+        ctx->tune.polish_group = env_int("SAT_EXP_POLISH_GROUP", 0);
         const int pad = env_int("SAT_EXP_LDS_PAD", 0);
         ctx->sa.lds_pad = pad > 0 ? (size_t)pad : 0;
         if (ctx->tune.streams != 0) {
@@ -861,7 +932,33 @@ int sat_use_own_stream(sat_ctx *ctx)
 int sat_search_async(sat_ctx *ctx, int lorder, int lsoln, int maxstart)
 {
     if (!ctx) return sat_fail(SAT_EINVAL, "null context");
+    if (ctx->polish_all) return sat_polish_all_launch(ctx, lorder, lsoln, maxstart);
     return launch_search(ctx, lorder, lsoln, maxstart, ctx->stream);
+}
+
+int sat_polish_all_set(sat_ctx *ctx, int tops)
+{
+    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
+    if (tops < 0 || tops > SAT_MAX_MATCHES) return sat_fail(SAT_EINVAL, "tops must be 0..%d (got %d)", SAT_MAX_MATCHES, tops);
+    ctx->polish_all = tops;
+    return SAT_OK;
+}
+
+int sat_polish_all_get(const sat_ctx *ctx) { return ctx ? ctx->polish_all : 0; }
+
+int sat_results_base(sat_ctx *ctx, int32_t *base_scores)
+{
+    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
+    if (!base_scores) return sat_fail(SAT_EINVAL, "base_scores buffer is null");
+    if (ctx->n_entries <= 0) return sat_fail(SAT_ESTATE, "no database uploaded");
+    if (ctx->queries.empty() || ctx->searched_nq != ctx->queries.size() || !ctx->searched_polished || !ctx->d_base.get())
+        return sat_fail(SAT_ESTATE, "the last search was not a polished one (sat_polish_all_set)");
+    const int rc = sat_polish_all_check(ctx);
+    if (rc != SAT_OK) return rc;
+    const size_t n = ctx->queries.size() * (size_t)ctx->n_entries;
+    HIP_TRY(hipMemcpy(base_scores, ctx->d_base.get(), n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    ctx->d2h_bytes += n * sizeof(int32_t);
+    return SAT_OK;
 }
 
 void *sat_device_scores(sat_ctx *ctx) { return ctx ? ctx->d_scores.get() : nullptr; }
@@ -877,7 +974,7 @@ int sat_sync(sat_ctx *ctx)
     if (!ctx) return sat_fail(SAT_EINVAL, "null context");
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return SAT_OK;
+    return sat_polish_all_check(ctx);
 }
 
 int sat_results(sat_ctx *ctx, int lsoln, int32_t *scores, int32_t *ssemaps)
@@ -916,8 +1013,11 @@ int sat_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart,
     if (!ctx) return sat_fail(SAT_EINVAL, "null context");
     if (!scores) return sat_fail(SAT_EINVAL, "scores buffer is null");
     if (lsoln && !ssemaps) return sat_fail(SAT_EINVAL, "lsoln set but ssemaps buffer is null");
-    const int rc = timed(ctx, kernel_ms, [&] { return launch_search(ctx, lorder, lsoln, maxstart, ctx->stream); });
+    int rc = timed(ctx, kernel_ms, [&] {
+        return ctx->polish_all ? sat_polish_all_launch(ctx, lorder, lsoln, maxstart) : launch_search(ctx, lorder, lsoln, maxstart, ctx->stream);
+    });
     if (rc != SAT_OK) return rc;
+    if (ctx->polish_all && (rc = sat_polish_all_check(ctx)) != SAT_OK) return rc;
     return sat_results(ctx, lsoln, scores, ssemaps);
 }
 
@@ -1026,6 +1126,7 @@ int sat_search_timed(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int repe
 {
     if (!ctx) return sat_fail(SAT_EINVAL, "null context");
     if (repeats < 1) return sat_fail(SAT_EINVAL, "repeats must be >= 1");
+    if (ctx->polish_all) return sat_fail(SAT_ESTATE, "sat_search_timed times the plain search: not while sat_polish_all_set is on");
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));

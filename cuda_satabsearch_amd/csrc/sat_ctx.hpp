@@ -113,7 +113,7 @@ struct sat_ctx {
 
     // overrides (SAT_EXP_* in satabsearch_debug.h), read ONCE when the context is created: these of the search plan,
     // the upload and the pair split, the launch heuristics' in `sa`
-    struct Tuning { int streams = -1, upload_threads = 0, upload_timing = 0, upload_pieces = 0, refine_split = 0; } tune;
+    struct Tuning { int streams = -1, upload_threads = 0, upload_timing = 0, upload_pieces = 0, refine_split = 0, polish_group = 0; } tune;
     // what sat_launch.hip keeps per context: its overrides, the instantiations whose dynamic-LDS limit has been raised
     // on this device, the entries per workgroup chosen so far
     SaLaunchState sa;
@@ -125,6 +125,10 @@ struct sat_ctx {
     // what the result buffers hold: set by a search, cleared by an upload or a new query batch
     size_t searched_nq = 0;                  // 0 = no search since the last upload / query change
     bool searched_lsoln = false;
+    bool searched_polished = false;          // the last search was a polished one: d_base holds its rows' base scores
+    // whole-database polish (sat_polish_all_set): 0 = off, else the maps polished per row.  A setting of the context,
+    // like its stream: uploads and query changes leave it alone.
+    int polish_all = 0;
 
     // multi-GPU gather (sat_multi.hip): the result buffers are sized for at least this many rows per
     // query, so that a fixed-size gather may read a shard padded to the largest shard
@@ -155,6 +159,9 @@ struct sat_ctx {
     DevBuf<int32_t> d_polout;
     DevBuf<unsigned long long> d_polkeys;
     DevBuf<int8_t> d_polmaps;
+    // whole-database polish: the rows' scores before the polish, laid out as d_scores; the "did not finish" flag
+    DevBuf<int32_t> d_base;
+    DevBuf<int32_t> d_polerr;
     // refine (sat_search_refine, sat_topk.hip): the final ranking of the nq x C re-scored candidates
     DevBuf<unsigned long long> d_rkeys, d_rsorted;
     DevBuf<int32_t> d_rvals, d_rvals_sorted, d_rfirst, d_rmaps;
@@ -222,7 +229,7 @@ int sat_pairs_collect(sat_ctx *ctx, int npairs, int32_t *scores, int32_t *ssemap
 // the record pass, the selection and (maps) the map pass of every launch of the pair list on the context's stream;
 // then wait and copy the rows of pairs 0 .. npairs - 1 (ssemaps may be NULL).
 int sat_pair_matches_launch(sat_ctx *ctx, int lorder, int maxstart, int max_matches, bool maps, const int32_t *query,
-                            const int32_t *entry, int npairs, bool polish = false);
+                            const int32_t *entry, int npairs, bool polish = false, bool packed = false);
 int sat_pair_matches_collect(sat_ctx *ctx, int max_matches, int npairs, int32_t *counts, int32_t *scores, int32_t *restarts,
                              int32_t *ssemaps, const int32_t *query);
 // stage 1 of sat_search_refine: a plain search without LSOLN queued on the context's stream
@@ -232,11 +239,26 @@ int sat_launch_plain(sat_ctx *ctx, int lorder, int maxstart);
 // selection of pairs pair0 .. pair0 + n - 1 from the record slabs in ctx->d_bmap_slabs (the ranks go to counts / scores
 // / restarts as pair_match_select lays them out); the polish of the n pairs named by the launch's map items, entries of
 // up to n2max SSEs (outputs in ctx->d_polout / d_polkeys / d_polmaps, rows indexed by the pair); wait and copy the rows
-// of pairs 0 .. npairs - 1 (every output but scores may be NULL).
+// of pairs 0 .. npairs - 1 (every output but scores may be NULL).  width: the lanes a map runs on, 16 or 32 (every entry
+// of the items must fit) or 64; sat_polish_width chooses it for an item group (packed: the lane-group kernel wherever the
+// entries fit a group, whatever the size of the launch - the whole-database mode).
 int sat_polish_reserve(sat_ctx *ctx, int npairs);
 int sat_polish_select(sat_ctx *ctx, int pair0, int n, int maxstart, int tops, uint32_t slab_words, int32_t *counts,
                       int32_t *scores, int32_t *restarts);
 int sat_polish_run(sat_ctx *ctx, int lorder, const SatPairItem *d_map_items, int n, int tops, int n2max, int npairs,
-                   const int32_t *counts, const int32_t *scores, const int32_t *restarts, const int8_t *maps);
+                   const int32_t *counts, const int32_t *scores, const int32_t *restarts, const int8_t *maps, int width = 64);
+int sat_polish_width(const sat_ctx *ctx, int launch_pairs, int tops, int n2max, bool packed);
 int sat_polish_collect(sat_ctx *ctx, int npairs, int32_t *scores, int32_t *base_scores, int32_t *restarts, int32_t *moves,
                        int32_t *ssemaps, const int32_t *query);
+
+// Whole-database polish (sat_polish_all_set).  sat_polish_all_launch (sat_capi.hip) is the polished
+// form of launch_search over the whole shard on the context's stream: the pairs (q, e) in row order, cut into launches
+// of at most kPolishAllPairs pairs whose record slabs stay under the 1 GiB budget; each launch builds its own item
+// table, runs 6h's passes and scatters its rows (sat_polish_scatter, sat_polish.hip: the launch's n map items, rows of
+// `npairs` pairs) into d_scores, d_base and, with maps, d_ssemaps.  A launch's scratch beyond the slabs is
+// tops x SAT_MAXDIM map bytes, 16 x (1 + tops) bytes of ranks and rows and its items per pair: at most 0.3 GiB, whatever
+// the database.  sat_polish_all_check waits for the stream and fails with SAT_EDEVICE when a row's polish did not finish.
+constexpr int kPolishAllPairs = 1 << 18;
+int sat_polish_all_launch(sat_ctx *ctx, int lorder, int lsoln, int maxstart);
+int sat_polish_scatter(sat_ctx *ctx, const SatPairItem *d_map_items, int n, int npairs, bool maps);
+int sat_polish_all_check(sat_ctx *ctx);

@@ -406,6 +406,12 @@ int sat_db_upload_search(sat_ctx *ctx, int n_entries, const int32_t *orders,
                          const float *dist_tri, const int64_t *db_ordinal,
                          int lorder, int lsoln, int maxstart)
 {
+    // whole-database polish (sat_polish_all_set): the passes of a polished search follow one another over the whole
+    // shard, so the upload and the search run one after the other
+    if (ctx && ctx->polish_all) {
+        const int rc = upload_impl(ctx, n_entries, orders, cell_off, tab_tri, dist_tri, db_ordinal, nullptr);
+        return rc != SAT_OK ? rc : sat_polish_all_launch(ctx, lorder, lsoln, maxstart);
+    }
     const FirstSearch first = { lorder, lsoln, maxstart };
     return upload_impl(ctx, n_entries, orders, cell_off, tab_tri, dist_tri, db_ordinal, &first);
 }

@@ -599,7 +599,8 @@ static int multi_refine(sat_multi *m, int lorder, int lsoln, int maxstart, int c
     if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
     const auto t0 = std::chrono::steady_clock::now();
     // stage 1 on every shard, each ranking its own best C
-    int rc = each_shard(m, [&](int g) { return sat_search_async(m->ctx[(size_t)g], lorder, 0, maxstart); });
+    // (a plain search whatever sat_polish_all_set says: the mode is for whole-database searches, not for a refine's stage 1)
+    int rc = each_shard(m, [&](int g) { return sat_launch_plain(m->ctx[(size_t)g], lorder, maxstart); });
     if (rc != SAT_OK) return rc;
     const int c = candidates < m->n_entries ? candidates : m->n_entries;
     if (k > c) k = c;
@@ -790,6 +791,16 @@ int sat_multi_score_histogram(sat_multi *m, uint32_t *counts, int32_t *below)
         if (rc != SAT_OK) return rc;
         for (size_t i = 0; i < c.size(); i++) counts[i] += c[i];
         for (size_t q = 0; q < nq; q++) below[q] += b[q];
+    }
+    return SAT_OK;
+}
+
+int sat_multi_polish_all_set(sat_multi *m, int tops)
+{
+    if (!m) return sat_fail(SAT_EINVAL, "null context");
+    for (int g = 0; g < m->ndev; g++) {
+        const int rc = sat_polish_all_set(m->ctx[(size_t)g], tops);
+        if (rc != SAT_OK) return rc;
     }
     return SAT_OK;
 }

@@ -350,6 +350,27 @@ class Searcher:
             self._ctx, int(bool(lorder)), int(bool(lsoln)), int(maxstart), int(candidates), int(refine_maxstart), int(tops),
             int(k), h, m, f, b), k, candidates, refine_maxstart, lsoln)
 
+    def set_polish_all(self, tops):
+        """Whole-database polish (sat_polish_all_set): with tops in 1..8 every plain whole-database search of this
+        searcher - search, search_async, upload_search - gives every row the score (and with lsoln the map) that
+        search_pairs_polish(tops) gives its pair, in the ordinary result buffers: results, topk_hits, hits_cutoff,
+        score_histogram and fit_statistics then work on polished rows.  0 turns it off.  A setting like the stream:
+        it survives upload and set_queries.  search_matches, the pair searches and stage 1 of the refine calls stay
+        plain; search_timed raises while it is on."""
+        self._check(self._lib.sat_polish_all_set(self._ctx, int(tops)))
+
+    def polish_all(self):
+        """The maps polished per row by a whole-database search, 0 = the mode is off (sat_polish_all_get)."""
+        return int(self._lib.sat_polish_all_get(self._ctx))
+
+    def results_base(self):
+        """The rows' scores before the polish of the last polished search (sat_results_base), shaped like results()'
+        scores: bit for bit the plain search's.  Raises unless the last search was a polished one."""
+        nq = getattr(self, "n_queries", 1)
+        base = np.empty((nq, self.n_entries), np.int32)
+        self._check(self._lib.sat_results_base(self._ctx, base.ctypes.data))
+        return base if getattr(self, "_batch", False) else base[0]
+
     def use_stream(self, stream_handle):
         """Queue all further work on the caller's HIP stream (0 / None = default stream),
         e.g. torch.cuda.current_stream().cuda_stream."""
@@ -572,6 +593,11 @@ class MultiSearcher:
         return _search_refine_polish(self, lambda h, m, f, b: self._lib.sat_multi_search_refine_polish(
             self._m, int(bool(lorder)), int(bool(lsoln)), int(maxstart), int(candidates), int(refine_maxstart), int(tops),
             int(k), h, m, f, b, C.byref(ms)), k, candidates, refine_maxstart, lsoln)
+
+    def set_polish_all(self, tops):
+        """Searcher.set_polish_all on every shard (sat_multi_polish_all_set): search, search_topk, search_cutoff and
+        search_fit then work on polished rows, exactly those of one searcher holding the whole database."""
+        self._check(self._lib.sat_multi_polish_all_set(self._m, int(tops)))
 
     def search_topk(self, k, lorder=True, lsoln=False, maxstart=DEFAULT_MAXSTART):
         k = min(int(k), self.n_entries)

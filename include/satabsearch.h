@@ -247,7 +247,8 @@ int sat_search_pairs_matches(sat_ctx *ctx, int lorder, int maxstart, int max_mat
  * pair).  Pairs as sat_search_pairs takes them (any order, repeats, mixed classes); npairs == 0 does nothing; what the
  * other pair searches reject is rejected the same way (SAT_EINVAL / SAT_ESTATE).  Passes per launch of the list (cut as
  * sat_search_pairs_matches cuts it): the pair-match record pass, a selection of the `tops` largest keys (no set test),
- * the pair-match map pass on those restarts, and the polish kernel - one workgroup per pair, one wave per map; a wave
+ * the pair-match map pass on those restarts, and the polish kernel - one workgroup per pair, one wave per map (in launches
+ * of 16 384 maps or more a group of 16 or 32 lanes per map for entries of up to 16 / 32 SSEs, same results); a wave
  * that has not finished within 2 n1 (n1 - 1) + 1 rounds (which cannot happen: scores lie in [-n1 (n1 - 1), n1 (n1 - 1)])
  * makes the call fail with SAT_EDEVICE.  Nothing depends on the launch shape, cell layout, lanes per chain, entries per
  * workgroup, the cut into items or the sharding.  Leaves the buffers behind sat_results / sat_topk* / sat_hits_cutoff
@@ -256,6 +257,37 @@ int sat_search_pairs_matches(sat_ctx *ctx, int lorder, int maxstart, int max_mat
 int sat_search_pairs_polish(sat_ctx *ctx, int lorder, int maxstart, int tops, int npairs, const int32_t *query,
                             const int32_t *entry, int32_t *scores, int32_t *base_scores, int32_t *restarts, int32_t *moves,
                             int32_t *ssemaps, double *kernel_ms);
+
+/*
+ * Whole-database polish.  sat_polish_all_set(ctx, tops) with tops in 1..SAT_MAX_MATCHES turns every plain
+ * whole-database search of the context - sat_search, sat_search_async, sat_db_upload_search, and through them
+ * sat_multi_search, sat_multi_search_topk, sat_multi_search_cutoff and sat_multi_search_fit - into a polished search;
+ * 0 (the default) turns it off again, after which not one bit of any result differs from a context that never had it
+ * on; anything else is SAT_EINVAL.  It is a setting of the context, like its stream: uploads and query changes leave
+ * it alone.  sat_polish_all_get returns it.
+ *   Scores: the score of row (q, e) is exactly the scores[p] that sat_search_pairs_polish(lorder, maxstart, tops)
+ *     returns for the pair (q, e) - same ranks, same tie-breaks, same min(tops, maxstart) -, and with lsoln the row's map
+ *     is that pair's ssemaps row.
+ *   The result buffers and the searched state are as after sat_search with these values: sat_results, sat_topk,
+ *     sat_topk_hits, sat_hits_cutoff, sat_score_histogram, sat_stats_fit / sat_stats_set, sat_device_scores /
+ *     sat_device_ssemaps and the multi-GPU gather work on polished rows.  An installed fit is dropped, as any new
+ *     search drops it.  Without lsoln the maps are computed internally only: sat_results(lsoln = 1) is SAT_ESTATE.
+ *   sat_results_base copies the rows' scores before the polish, [n_queries][n_entries]: rank 0's s, bit for bit what
+ *     the plain search writes, from a device buffer the polished search fills.  SAT_ESTATE unless the last search of
+ *     the context was a polished one.
+ *   Not touched by the mode: sat_search_matches, the pair searches and stage 1 of every refine call stay plain.
+ *     sat_search_timed is SAT_ESTATE while the mode is on (its window is defined for the plain search).
+ *     sat_db_upload_search uploads, then searches, one after the other.
+ *   The passes are sat_search_pairs_polish's over the pairs (q, e) in row order, cut into launches whose record slabs
+ *     stay under 1 GiB and that hold at most 2^18 pairs; the polish runs a map on a group of 16 or 32 lanes for entries
+ *     of up to 16 / 32 SSEs and on a wave above; the rows go from the polish's outputs straight into the result buffers
+ *     on the device.  kernel_ms of sat_search covers all passes; sat_last_launch_info is "polish all (T tops, L launches
+ *     of up to P pairs): " followed by the pair-match string of the last launch.  A row whose polish did not finish (it
+ *     cannot happen, see above) fails sat_search, sat_sync and sat_results_base with SAT_EDEVICE.
+ */
+int sat_polish_all_set(sat_ctx *ctx, int tops);
+int sat_polish_all_get(const sat_ctx *ctx);
+int sat_results_base(sat_ctx *ctx, int32_t *base_scores);
 
 /*
  * Queue all further work of this context on the caller's stream (`hip_stream` is a
@@ -549,12 +581,17 @@ int sat_multi_hits_cutoff(sat_multi *m, double max_pvalue, int max_rows, int32_t
 int sat_multi_score_histogram(sat_multi *m, uint32_t *counts, int32_t *below);
 int sat_multi_stats_set(sat_multi *m, const sat_fit *fits);
 int sat_multi_search_fit(sat_multi *m, int lorder, int lsoln, int maxstart, double censor, sat_fit *fits, double *wall_ms);
+/* sat_polish_all_set with the same setting on every shard's context: sat_multi_search, sat_multi_search_topk,
+ * sat_multi_search_cutoff and sat_multi_search_fit then work on polished rows, exactly those of one context holding
+ * the whole database; the refine calls' stage 1, the match and the pair searches stay plain. */
+int sat_multi_polish_all_set(sat_multi *m, int tops);
 unsigned long long sat_multi_stat_d2h_bytes(const sat_multi *m);
 
 /*
  * Time `repeats` back-to-back searches with HIP events on the launch stream
  * (inputs resident, no copies inside the window).  Returns total milliseconds
  * in *total_ms and the dominant SA kernel's summed device time in *kernel_ms.
+ * SAT_ESTATE while sat_polish_all_set is on.
  */
 int sat_search_timed(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int repeats,
                      double *total_ms, double *kernel_ms);

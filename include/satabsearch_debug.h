@@ -15,6 +15,9 @@
  *   SAT_EXP_REFINE_SPLIT = n     restarts per work item of a pair search (sat_search_pairs, sat_search_pairs_matches,
  *                                stage 2 of sat_search_refine; default: chosen so that the pairs x items fill the GPU,
  *                                whole rounds of the chains)
+ *   SAT_EXP_POLISH_GROUP = 0|16|32|64  lanes a map of the polish runs on (sat_polish.hip; default 0: groups of 16 / 32 lanes for
+ *                                entries of up to 16 / 32 SSEs in the whole-database mode and in large pair launches,
+ *                                else a wave).  A forced width serves the entries it can hold; wider ones fall to the next
  *   SAT_EXP_STREAMS = 0          queue the order buckets of a search one after the other instead of concurrently
  *   SAT_EXP_UPLOAD_THREADS = n   host threads slicing the database copy (default 4)
  *   SAT_EXP_UPLOAD_TIMING = 1    per-phase upload times on stderr
