@@ -32,6 +32,7 @@ ABI_SYMBOLS = (
     "sat_multi_score_histogram", "sat_multi_stats_set", "sat_multi_search_fit",
     "sat_search_pairs_polish", "sat_search_refine_polish", "sat_multi_search_pairs_polish", "sat_multi_search_refine_polish",
     "sat_polish_all_set", "sat_polish_all_get", "sat_results_base", "sat_multi_polish_all_set",
+    "sat_queries_from_db", "sat_multi_queries_from_db", "sat_stat_query_h2d_bytes",
 )
 
 STAT_BINS = 4096
@@ -149,6 +150,14 @@ def device_lib():
             lib.sat_polish_all_get.argtypes = [C.c_void_p]
             lib.sat_results_base.argtypes = [C.c_void_p, C.c_void_p]
             lib.sat_multi_polish_all_set.argtypes = [C.c_void_p, C.c_int]
+        # (as above: a build of the parent commit predates queries taken from the resident database)
+        if hasattr(lib, "sat_queries_from_db"):
+            lib.sat_queries_from_db.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32]
+            lib.sat_multi_queries_from_db.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32]
+            lib.sat_stat_query_h2d_bytes.argtypes = [C.c_void_p]
+            lib.sat_stat_query_h2d_bytes.restype = C.c_uint64
+            lib.sat_debug_query_blob.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]      # include/satabsearch_debug.h
+            lib.sat_debug_query_blob.restype = C.c_longlong
         lib.sat_hits_cutoff.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         lib.sat_multi_search_cutoff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                                 C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]

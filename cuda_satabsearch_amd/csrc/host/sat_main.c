@@ -33,7 +33,11 @@
  * leave them), -P T (polish: the rows of -k K are the K best of each query's C best entries after the own-best maps of
  * every candidate's T best restarts were climbed to local optima of the search's neighbourhood on the GPU; a fourth header
  * line "# POLISH ..."), -A (with -P T: polish EVERY row of the search - the whole-database mode of the library - and take
- * the ordinary route of the other options on the polished rows: the listing, -k, -p, -F; "# POLISH tops = T all rows").
+ * the ordinary route of the other options on the polished rows: the listing, -k, -p, -F; "# POLISH tops = T all rows"),
+ * -Q dbfile (as -q dbfile, same stdout: the queries are entries of the database, which is resident on the GPUs, so each
+ * batch is set from its entry indices and built there - sat_multi_queries_from_db - instead of being expanded on the host
+ * and copied), -a dbfile (all-vs-all: every entry of the database is a query, in file order, set as -Q sets them; stdin
+ * is not read; prints what -q dbfile prints for a stdin that lists every SID in file order).
  */
 #include <math.h>
 #include <stdarg.h>
@@ -69,14 +73,19 @@ static double now_ms(void)
 #pragma weak sat_multi_search_fit
 #pragma weak sat_multi_search_refine_polish
 #pragma weak sat_multi_polish_all_set
+#pragma weak sat_multi_queries_from_db
 
 static void usage(const char *prog)
 {
-    fprintf(stderr, "Usage: %s [-c] [-q dbfile] [-r restarts] [-g gpus] [-G gpu,gpu,...] [-s seed] [-k K] [-p P]\n"
-                    "       [-m M] [-M M] [-R restarts [-C C]] [-F censor] [-P T] [-A] [-b]\n", prog);
+    fprintf(stderr, "Usage: %s [-c] [-q dbfile | -Q dbfile | -a dbfile] [-r restarts] [-g gpus] [-G gpu,gpu,...] [-s seed]\n"
+                    "       [-k K] [-p P] [-m M] [-M M] [-R restarts [-C C]] [-F censor] [-P T] [-A] [-b]\n", prog);
     fprintf(stderr, "  -c : run on host CPU not GPU card\n");
     fprintf(stderr, "  -q dbfile : database is read from dbfile, list of query\n"
                     "              ids is read from stdin\n");
+    fprintf(stderr, "  -Q dbfile : as -q dbfile, same output; the queries are built on the GPU from the resident\n"
+                    "              database instead of on the host (GPU mode)\n");
+    fprintf(stderr, "  -a dbfile : all-vs-all: every entry of dbfile is a query, in file order, built as with -Q;\n"
+                    "              stdin is not read (GPU mode)\n");
     fprintf(stderr, "  -r restarts : number of restarts. Default %d\n", 128);
     fprintf(stderr, "  -g gpus : number of GPUs to shard the database over (0 = all visible). Default 1\n");
     fprintf(stderr, "  -G list : the GPUs to use, e.g. 0,2,3 (a GPU named twice holds two shards)\n");
@@ -246,7 +255,9 @@ typedef struct {
     double censor;                    /* -F: the right-censored fraction of the rows */
     double pmax;                      /* -p: the largest p-value printed */
     unsigned long long seed;
-    const char *qfile;                /* -q: the database; stdin lists the query SIDs */
+    const char *qfile;                /* -q, -Q, -a: the database; stdin lists the query SIDs (not with -a) */
+    const char *from_db;              /* -Q, -a: the database again - the batches are set from entry indices on the GPUs */
+    const char *all;                  /* -a: the database again - every entry is a query */
     int dev_list[64], ndev_list;
     /* what the run prints, derived once the options are checked */
     int ranked;                       /* -k / -p / -R: each query's ranked rows; else the listing in class order */
@@ -365,12 +376,14 @@ static void parse_options(int argc, char *argv[], options *o)
 {
     *o = (options){ .use_gpu = 1, .maxstart = 128, .want_gpus = 1, .seed = SAT_DEFAULT_SEED };
     int c;
-    while ((c = getopt(argc, argv, "cq:r:g:G:s:bk:p:m:M:R:C:F:P:A")) != -1) {
+    while ((c = getopt(argc, argv, "cq:Q:a:r:g:G:s:bk:p:m:M:R:C:F:P:A")) != -1) {
         char *end = NULL;
         long v;
         switch (c) {
         case 'c': o->use_gpu = 0; break;
         case 'q': o->qfile = optarg; break;
+        case 'Q': o->from_db = optarg; break;
+        case 'a': o->all = optarg; break;
         case 'r': o->maxstart = atoi(optarg); break;
         case 'g': o->want_gpus = atoi(optarg); break;
         case 'G':
@@ -437,6 +450,16 @@ static void parse_options(int argc, char *argv[], options *o)
         default: usage(argv[0]);
         }
     }
+    if (o->from_db || o->all) {
+        /* queries from the resident database: from here on the run is a -q run over that file */
+        if (o->from_db && !o->use_gpu) die("ERROR: -Q cannot be combined with -c\n");
+        if (o->all && !o->use_gpu) die("ERROR: -a cannot be combined with -c\n");
+        if (o->from_db && o->qfile) die("ERROR: -Q cannot be combined with -q\n");
+        if (o->all && o->qfile) die("ERROR: -a cannot be combined with -q\n");
+        if (o->all && o->from_db) die("ERROR: -a cannot be combined with -Q\n");
+        if (!sat_multi_queries_from_db) die("ERROR: this library has no sat_multi_queries_from_db\n");
+        o->qfile = o->from_db = o->all ? o->all : o->from_db;
+    }
     if (o->polish_all) {
         /* all rows: the mode of the library; from here on the run is an ordinary one on polished rows */
         if (!o->polish) die("ERROR: -A needs -P T\n");
@@ -484,15 +507,16 @@ static void parse_options(int argc, char *argv[], options *o)
     o->nm = o->nmatch > 0 ? o->nmatch : 1;
 }
 
-/* -q: query SIDs on stdin, one a line (cut to 7 characters), options T T F; else the database name, the options and
- * the query structures on stdin */
+/* -q, -Q: query SIDs on stdin, one a line (cut to 7 characters), options T T F; -a: the same options and nothing read -
+ * the queries are the database's entries, counted when it is loaded; else the database name, the options and the query
+ * structures on stdin */
 static void read_queries(const options *o, input *in)
 {
     if (o->qfile) {
         strncpy(in->dbfile, o->qfile, sizeof in->dbfile - 1);
         in->ltype = in->lorder = 1;
         char buf[SAT_MAX_LINE_LEN];
-        while (!feof(stdin) && fgets(buf, SAT_MAX_LINE_LEN, stdin)) {
+        while (!o->all && !feof(stdin) && fgets(buf, SAT_MAX_LINE_LEN, stdin)) {
             in->sids = checked(realloc(in->sids, (size_t)(in->num_queries + 1) * (SAT_LABELSIZE + 1)));
             char *sid = in->sids + (size_t)in->num_queries++ * (SAT_LABELSIZE + 1);
             memset(sid, 0, SAT_LABELSIZE + 1);
@@ -524,7 +548,8 @@ static void read_queries(const options *o, input *in)
 }
 
 /* The database (-b: its binary image when that is newer than the file), split into the two size classes; then each
- * query's structure: the inline ones in turn, or with -q the database entry of its SID (small class first) */
+ * query's structure: the inline ones in turn, with -q / -Q the database entry of its SID (small class first), with -a
+ * every entry in file order */
 static void load_database(const options *o, input *in)
 {
     FILE *dbfp = fopen(in->dbfile, "r");
@@ -564,10 +589,12 @@ static void load_database(const options *o, input *in)
         die("ERROR: empty database\n");
 
     in->qsrc = o->qfile ? &in->db : &in->queries;
+    if (o->all)
+        in->num_queries = in->db.count;
     in->qindex = checked(malloc(sizeof(int) * (size_t)(in->num_queries + 1)));
     for (int i = 0; i < in->num_queries; i++) {
         in->qindex[i] = i;
-        if (!o->qfile)
+        if (!o->qfile || o->all)
             continue;
         const char *sid = in->sids + (size_t)i * (SAT_LABELSIZE + 1);
         int found = -1;
@@ -655,6 +682,7 @@ typedef struct {
     int batch;                        /* queries a search scores */
     int kk;                           /* -k: rows per query, min(K, entries) */
     int32_t *n1s;                     /* the batch's queries: orders, codes, types and distances at pitch SAT_MAXDIM */
+                                      /* (-Q, -a: the orders alone - the GPUs build the rest from their entries) */
     uint8_t *qtabs, *qtypes;
     float *qdmats;
     slots all;                        /* listing, -m: every entry's slots, row b * entries + e */
@@ -717,6 +745,8 @@ static void alloc_gpu_bufs(const options *o, const input *in, gpu_bufs *B)
         alloc_hits(B, (size_t)B->kk * B->batch, lsoln);  /* only K rows per query (and GPU) ever leave the GPUs */
     }
     B->n1s = checked(malloc(sizeof(int32_t) * (size_t)B->batch));
+    if (o->from_db)
+        return;
     B->qtabs = checked(calloc((size_t)B->batch * SAT_MAXDIM * SAT_MAXDIM, 1));
     B->qdmats = checked(calloc((size_t)B->batch * SAT_MAXDIM * SAT_MAXDIM, sizeof(float)));
     B->qtypes = checked(calloc((size_t)B->batch * SAT_MAXDIM, 1));
@@ -926,8 +956,10 @@ static int run_gpu(const options *o, const input *in)
         const int nqb = in->num_queries - q0 < B.batch ? in->num_queries - q0 : B.batch;
         for (int b = 0; b < nqb; b++) {
             const int qs = in->qindex[q0 + b];
-            uint8_t *tab = B.qtabs + (size_t)b * SAT_MAXDIM * SAT_MAXDIM;
             B.n1s[b] = in->qsrc->order[qs];
+            if (o->from_db)
+                continue;
+            uint8_t *tab = B.qtabs + (size_t)b * SAT_MAXDIM * SAT_MAXDIM;
             sat_set_expand(in->qsrc, qs, SAT_MAXDIM, tab, B.qdmats + (size_t)b * SAT_MAXDIM * SAT_MAXDIM);
             for (int i = 0; i < B.n1s[b]; i++)
                 B.qtypes[(size_t)b * SAT_MAXDIM + i] = tab[i * SAT_MAXDIM + i];
@@ -935,7 +967,9 @@ static int run_gpu(const options *o, const input *in)
         fprintf(stderr, "Executing simulated annealing tableaux match kernel on GPU for %d quer%s (from %s)...\n",
                 nqb, nqb == 1 ? "y" : "ies", sat_set_name(in->qsrc, in->qindex[q0]));
         double ms = 0.0, ms_stage2 = 0.0;
-        int rc = sat_multi_queries_set(multi, nqb, B.n1s, B.qtabs, B.qdmats, SAT_MAXDIM, B.qtypes, (uint32_t)q0);
+        /* -Q, -a: the batch from its entries' indices in the database the GPUs hold */
+        int rc = o->from_db ? sat_multi_queries_from_db(multi, nqb, in->qindex + q0, (uint32_t)q0)
+                            : sat_multi_queries_set(multi, nqb, B.n1s, B.qtabs, B.qdmats, SAT_MAXDIM, B.qtypes, (uint32_t)q0);
         if (rc == SAT_OK)
             rc = search_batch(o, in, multi, &B, fits ? fits + q0 : NULL, &ms, &ms_stage2);
         if (rc < 0) {

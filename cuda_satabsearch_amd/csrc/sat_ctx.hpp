@@ -70,6 +70,24 @@ template <typename T> class DevBuf {
     size_t cap_ = 0;
 };
 
+// A query's size class: its order padded to 16, 32, 64 or 112
+__host__ __device__ inline int query_n1p(int n1) { return n1 <= 16 ? 16 : (n1 <= 32 ? 32 : (n1 <= 64 ? 64 : 112)); }
+
+// One query of padded order n1p in the query blob: qdist | qcode | qtypes | qpair - the grouped cells (16 + 4 bytes per
+// group of four and column), the SSE types, then from the next 16-byte boundary the dense pair cells of the full score.
+// The offsets of the last three and the size of the whole.
+struct QueryBlob { size_t qcode, qtypes, qpair, bytes; };
+__host__ __device__ inline QueryBlob query_blob(int n1p)
+{
+    const size_t n = (size_t)n1p, groups = n / 4 * n;
+    QueryBlob b;
+    b.qcode = groups * 16;
+    b.qtypes = groups * 20;
+    b.qpair = (groups * 20 + n + 15) & ~(size_t)15;
+    b.bytes = b.qpair + n * n * 8;
+    return b;
+}
+
 // db entries are launched in classes of similar order so that every launch sizes its
 // LDS for the largest member of the class only
 constexpr int kNumBuckets = 7;
@@ -99,7 +117,11 @@ struct sat_ctx {
     // inside), set where the descriptors are built
     struct QueryInfo { int n1, n1p; uint32_t ordinal; size_t blob_off; size_t ssemap_off; int cls, desc; };
     std::vector<QueryInfo> queries;
-    DevBuf<uint8_t> d_qblob;                // per query: qdist | qcode | qtypes
+    DevBuf<uint8_t> d_qblob;                // per query: qdist | qcode | qtypes | qpair (query_blob)
+    // queries taken from the resident shard (sat_queries_from_db, sat_qfromdb.hip): the entry of each query as it came
+    // from the host, each query's offset in the blob as the device summed them; only grow
+    DevBuf<int32_t> d_qentry;
+    DevBuf<unsigned long long> d_qoff;
     DevBuf<SatQuery> d_qdesc;               // descriptors grouped by size class
     int class_begin[5] = { 0, 0, 0, 0, 0 };  // classes: n1p = 16, 32, 64, 112
     int class_n1max[4] = { 0, 0, 0, 0 };
@@ -185,6 +207,8 @@ struct sat_ctx {
 
     // bytes copied device -> host by this context's result calls (sat_stat_d2h_bytes)
     unsigned long long d2h_bytes = 0;
+    // bytes copied host -> device by sat_queries_set / sat_queries_from_db (sat_stat_query_h2d_bytes)
+    unsigned long long query_h2d_bytes = 0;
     // kernel instantiations and launch geometry of the last search (sat_last_launch_info; one launch_info() of
     // sat_launch.hip per launch, from the SaKernel that was launched)
     std::string last_launch_info;
@@ -194,6 +218,13 @@ struct sat_ctx {
 // grouped by size class - where the batch, the result buffers or `lsoln` changed; load the file's code object.
 int refresh_descriptors(sat_ctx *ctx, bool lsoln, hipStream_t stream);
 int sat_db_load_code(sat_ctx *ctx);
+
+// ---- sat_qfromdb.hip, for sat_multi_queries_from_db.  sat_queries_from_db on one shard's context, every check made by
+// the caller: query q has order n1s[q] and is entry code[q] >= 0 of this shard, or code[q] = -query_n1p(n1s[q]): a
+// query whose entry another shard holds - it takes its room in the blob and the caller copies its bytes in afterwards.
+int sat_qfromdb_set(sat_ctx *ctx, int n_queries, const int32_t *code, const int32_t *n1s, uint32_t first_query_ordinal);
+// where query q lies in the context's blob, and its size
+void sat_qfromdb_segment(const sat_ctx *ctx, int q, uint8_t **at, size_t *bytes);
 
 // ---- sat_capi.hip, for the overlapped upload of sat_db.hip.  The entries a set of launches covers: indices into the
 // resident shard grouped by order bucket.  A search covers the whole shard (the context's lists); the overlapped upload

@@ -25,21 +25,6 @@ __host__ __device__ inline bool bad_distance(float d)
     return ad >= 1.0e29f && ad <= 3.4028234e38f;      // finite and out of range
 }
 
-// One query of padded order n1p in the query blob: qdist | qcode | qtypes | qpair - the grouped cells (16 + 4 bytes per
-// group of four and column), the SSE types, then from the next 16-byte boundary the dense pair cells of the full score.
-// The offsets of the last three and the size of the whole.
-struct QueryBlob { size_t qcode, qtypes, qpair, bytes; };
-QueryBlob query_blob(int n1p)
-{
-    const size_t n = (size_t)n1p, groups = n / 4 * n;
-    QueryBlob b;
-    b.qcode = groups * 16;
-    b.qtypes = groups * 20;
-    b.qpair = (groups * 20 + n + 15) & ~(size_t)15;
-    b.bytes = b.qpair + n * n * 8;
-    return b;
-}
-
 void free_db(sat_ctx *ctx)
 {
     ctx->d_orders.reset();
@@ -462,7 +447,7 @@ int sat_queries_set(sat_ctx *ctx, int n_queries, const int32_t *n1s, const uint8
             return sat_fail(SAT_EINVAL, "query %d: order %d outside 1..min(%d, pitch %d)", qi, n1, SAT_MAXDIM, pitch);
         auto &q = infos[(size_t)qi];
         q.n1 = n1;
-        q.n1p = n1 <= 16 ? 16 : (n1 <= 32 ? 32 : (n1 <= 64 ? 64 : 112));
+        q.n1p = query_n1p(n1);
         q.ordinal = first_query_ordinal + (uint32_t)qi;
         q.blob_off = blob_bytes;
         q.ssemap_off = 0;
@@ -531,6 +516,7 @@ int sat_queries_set(sat_ctx *ctx, int n_queries, const int32_t *n1s, const uint8
     int rc;
     if ((rc = ctx->d_qblob.grow(blob_bytes)) != SAT_OK || (rc = ctx->d_qdesc.grow((size_t)n_queries)) != SAT_OK) return rc;
     HIP_TRY(hipMemcpy(ctx->d_qblob.get(), blob.data(), blob_bytes, hipMemcpyHostToDevice));
+    ctx->query_h2d_bytes += blob_bytes;
     ctx->queries.swap(infos);
     ctx->desc_dirty = true;
     ctx->searched_nq = 0;                     // the result buffers no longer belong to the current batch

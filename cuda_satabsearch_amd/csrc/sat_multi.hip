@@ -359,6 +359,59 @@ int sat_multi_queries_set(sat_multi *m, int n_queries, const int32_t *n1s, const
     return SAT_OK;
 }
 
+int sat_multi_queries_from_db(sat_multi *m, int n_queries, const int32_t *entry, uint32_t first_query_ordinal)
+{
+    if (!m) return sat_fail(SAT_EINVAL, "null context");
+    if (n_queries < 1 || !entry) return sat_fail(SAT_EINVAL, "bad query batch (n_queries=%d)", n_queries);
+    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
+    // every query goes to the shard that holds its entry, under the entry's index there; the other shards learn its
+    // size class only (sat_qfromdb_set)
+    std::vector<int> owner((size_t)n_queries);
+    std::vector<int32_t> n1s((size_t)n_queries);
+    std::vector<std::vector<int32_t>> code((size_t)m->ndev, std::vector<int32_t>((size_t)n_queries));
+    for (int q = 0; q < n_queries; q++) {
+        if (entry[q] < 0 || entry[q] >= m->n_entries)
+            return sat_fail(SAT_EINVAL, "query %d: entry %d outside 0..%d", q, entry[q], m->n_entries - 1);
+        const int g = (int)(std::upper_bound(m->begin.begin(), m->begin.end(), entry[q]) - m->begin.begin()) - 1;
+        const int32_t local = entry[q] - m->begin[(size_t)g];
+        owner[(size_t)q] = g;
+        n1s[(size_t)q] = m->ctx[(size_t)g]->h_orders[(size_t)local];
+        for (int h = 0; h < m->ndev; h++) code[(size_t)h][(size_t)q] = h == g ? local : -query_n1p(n1s[(size_t)q]);
+    }
+    // each shard expands its own entries (and has waited for its stream when that returns) ...
+    for (int g = 0; g < m->ndev; g++) {
+        const int rc = sat_qfromdb_set(m->ctx[(size_t)g], n_queries, code[(size_t)g].data(), n1s.data(), first_query_ordinal);
+        if (rc != SAT_OK) return rc;
+    }
+    // ... and sends every run of queries it owns to the other shards' blobs (the same offsets on every shard), device to
+    // device: a peer copy between GPUs, a plain copy where the list names one GPU twice
+    for (int q0 = 0; q0 < n_queries;) {
+        const int g = owner[(size_t)q0];
+        int q1 = q0 + 1;
+        while (q1 < n_queries && owner[(size_t)q1] == g) q1++;
+        uint8_t *src, *last, *dst;
+        size_t bytes, last_bytes;
+        sat_qfromdb_segment(m->ctx[(size_t)g], q0, &src, &bytes);
+        sat_qfromdb_segment(m->ctx[(size_t)g], q1 - 1, &last, &last_bytes);
+        bytes = (size_t)(last - src) + last_bytes;
+        HIP_TRY(hipSetDevice(m->devices[(size_t)g]));
+        for (int h = 0; h < m->ndev; h++) {
+            if (h == g) continue;
+            sat_qfromdb_segment(m->ctx[(size_t)h], q0, &dst, &last_bytes);
+            if (m->devices[(size_t)h] == m->devices[(size_t)g])
+                HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, m->ctx[(size_t)g]->stream));
+            else
+                HIP_TRY(hipMemcpyPeerAsync(dst, m->devices[(size_t)h], src, m->devices[(size_t)g], bytes, m->ctx[(size_t)g]->stream));
+        }
+        q0 = q1;
+    }
+    for (int g = 0; g < m->ndev; g++) {
+        HIP_TRY(hipSetDevice(m->devices[(size_t)g]));
+        HIP_TRY(hipStreamSynchronize(m->ctx[(size_t)g]->stream));
+    }
+    return SAT_OK;
+}
+
 int sat_multi_search(sat_multi *m, int lorder, int lsoln, int maxstart, int32_t *scores, int32_t *ssemaps, double *wall_ms)
 {
     if (!m) return sat_fail(SAT_EINVAL, "null context");

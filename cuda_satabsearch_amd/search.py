@@ -280,6 +280,36 @@ class Searcher:
         self.n_queries = nq
         self._batch = True
 
+    def set_queries_from_db(self, entries, first_query_ordinal=0):
+        """Set a batch of queries that are entries of the uploaded database (sat_queries_from_db): query q is entry
+        entries[q] (any order, repeats allowed).  The batch is built on the device from the resident cells - only the
+        indices cross from the host - and is byte for byte the batch set_queries makes of the same structures, so every
+        search returns the same results."""
+        idx = np.ascontiguousarray(entries, dtype=np.int32).ravel()
+        self._check(self._lib.sat_queries_from_db(self._ctx, len(idx), idx.ctypes.data if len(idx) else None,
+                                                  int(first_query_ordinal)))
+        n1s = self._orders[idx]
+        self.n1 = int(n1s[0])
+        self.n1max = int(n1s.max())
+        self.n_queries = len(idx)
+        self._batch = True
+
+    def query_h2d_bytes(self):
+        """Bytes set_query / set_queries (the whole batch) and set_queries_from_db (4 per query) have copied host ->
+        device so far (sat_stat_query_h2d_bytes)."""
+        return int(self._lib.sat_stat_query_h2d_bytes(self._ctx))
+
+    def debug_query_blob(self):
+        """Test hook (satabsearch_debug.h): the current query batch as it lies on the device, uint8[bytes]."""
+        n = self._lib.sat_debug_query_blob(self._ctx, None, 0)
+        if n < 0:
+            self._check(int(n))
+        blob = np.empty(int(n), np.uint8)
+        n = self._lib.sat_debug_query_blob(self._ctx, blob.ctypes.data, blob.size)
+        if n < 0:
+            self._check(int(n))
+        return blob
+
     def set_query_from(self, queries: StructSet, s, query_ordinal=None):
         t, d = queries.dense(s)
         self.set_query(t, d, queries.ssetypes(s), s if query_ordinal is None else query_ordinal)
@@ -537,6 +567,7 @@ class MultiSearcher:
         self._check(self._lib.sat_multi_db_upload_packed(self._m, len(db), db.orders.ctypes.data, db.cell_off.ctypes.data,
                                                          db.tab.ctypes.data, db.dist.ctypes.data))
         self.n_entries = len(db)
+        self._orders = db.orders.copy()
 
     def shards(self):
         begin = np.zeros(self.ndev + 1, np.int32)
@@ -562,6 +593,15 @@ class MultiSearcher:
                                                     pitch, types.ctypes.data, int(first_query_ordinal)))
         self.n_queries = nq
         self.n1max = int(n1s.max())
+
+    def set_queries_from_db(self, entries, first_query_ordinal=0):
+        """Searcher.set_queries_from_db with entries[q] an index into the whole database (sat_multi_queries_from_db):
+        the shard that holds an entry builds its query, the other shards get it by a device-to-device copy."""
+        idx = np.ascontiguousarray(entries, dtype=np.int32).ravel()
+        self._check(self._lib.sat_multi_queries_from_db(self._m, len(idx), idx.ctypes.data if len(idx) else None,
+                                                        int(first_query_ordinal)))
+        self.n_queries = len(idx)
+        self.n1max = int(self._orders[idx].max())
 
     def search(self, lorder=True, lsoln=False, maxstart=DEFAULT_MAXSTART):
         """Returns (scores int32[nq, N], ssemaps int32[nq, N, 111] or None, wall_ms), database order."""

@@ -137,6 +137,27 @@ int sat_queries_set(sat_ctx *ctx, int n_queries, const int32_t *n1s, const uint8
                     const float *qdmats, int pitch, const uint8_t *qssetypes,
                     uint32_t first_query_ordinal);
 
+/*
+ * Set a batch of queries that are ENTRIES OF THE RESIDENT SHARD: query q is entry entry[q] (any order,
+ * repeats allowed), its stream key first_query_ordinal + q.  The database is already on the device as packed triangles,
+ * so nothing but the index list crosses from the host - 4 * n_queries bytes instead of up to 163 KB a query: a kernel
+ * (one workgroup per query) reads the entry's raw uploaded cells and writes the query's part of the batch, byte for
+ * byte what sat_queries_set builds on the host from the entry's dense arrays with the SSE types taken from the tableau
+ * diagonal.  Afterwards the context is exactly as after that sat_queries_set call with the same ordinal - query count,
+ * size classes, stream keys, no searched state, fitted statistics dropped, sat_polish_all_set kept - so every later
+ * call returns bit-identical results.  An uploaded cell is a valid query cell by construction (the upload applies the
+ * same rules), so there is nothing to reject beyond the indices.  Like sat_queries_set it first waits for the work
+ * queued on the context's current stream; the kernel runs on that stream (sat_use_stream is honoured) and has finished
+ * at return.  The batch is a copy: a later upload leaves it as it leaves any other batch.
+ * n_queries < 1, entry == NULL and an index outside 0 .. n_entries - 1 (the message names its position) are SAT_EINVAL
+ * and leave the previous batch intact; no database is SAT_ESTATE; a failed launch is SAT_EDEVICE.
+ */
+int sat_queries_from_db(sat_ctx *ctx, int n_queries, const int32_t *entry, uint32_t first_query_ordinal);
+
+/* Bytes sat_queries_set (the batch's whole blob) and sat_queries_from_db (4 * n_queries) have copied from the host to
+ * the device on this context since it was created. */
+unsigned long long sat_stat_query_h2d_bytes(const sat_ctx *ctx);
+
 /* Queries currently set (1 after sat_query_set). */
 int sat_query_count(const sat_ctx *ctx);
 
@@ -512,6 +533,11 @@ void sat_debug_lds_layout(int m2w, int n1, int n1p, int n2, int chains, int thre
  *                       as a window of the packed arrays; anything else is SAT_EINVAL
  * sat_multi_shards      begin[ndev + 1]: shard g holds entries begin[g] .. begin[g+1]-1
  * sat_multi_queries_set as sat_queries_set, on every GPU
+ * sat_multi_queries_from_db  as sat_queries_from_db with entry[q] an index into the WHOLE database: the shard that
+ *                       holds the entry expands it, and that query's bytes go device to device into every other
+ *                       shard's batch (a peer copy between GPUs, a plain copy where the list names one GPU twice);
+ *                       each shard receives one 4-byte word per query from the host.  Every shard is then exactly as
+ *                       after sat_multi_queries_set with the entries' dense arrays
  * sat_multi_search      as sat_search: scores [nq][n_entries] (and ssemaps) in database order;
  *                       wall_ms = launch on all GPUs .. rows on the host
  * sat_multi_search_topk the best k rows per query, each GPU ranking its own shard (sat_topk_hits) and
@@ -529,6 +555,7 @@ int sat_multi_db_upload_packed(sat_multi *m, int n_entries, const int32_t *order
 int sat_multi_shards(const sat_multi *m, int32_t *begin);
 int sat_multi_queries_set(sat_multi *m, int n_queries, const int32_t *n1s, const uint8_t *qtabs,
                           const float *qdmats, int pitch, const uint8_t *qssetypes, uint32_t first_query_ordinal);
+int sat_multi_queries_from_db(sat_multi *m, int n_queries, const int32_t *entry, uint32_t first_query_ordinal);
 int sat_multi_search(sat_multi *m, int lorder, int lsoln, int maxstart, int32_t *scores, int32_t *ssemaps,
                      double *wall_ms);
 int sat_multi_search_topk(sat_multi *m, int lorder, int lsoln, int maxstart, int k, sat_hit *hits,

@@ -33,6 +33,7 @@
  */
 #ifndef SATABSEARCH_DEBUG_H
 #define SATABSEARCH_DEBUG_H
+#include <stddef.h>
 #include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
@@ -54,6 +55,12 @@ int sat_debug_set_scores(struct sat_ctx *ctx, const int32_t *scores);
  * sat_last_launch_info spells it: "sat_sa_kernel<32, 1, false, 1, 4, 0>", "sat_sa_pair_kernel<...>", ...  Needs no
  * context and no device, and does not depend on the SAT_EXP_* environment.  The string lives as long as the library. */
 const char *sat_debug_sa_instances(void);
+
+/* Every build, a test hook: the current query batch as it lies on the device (per query qdist | qcode | qtypes |
+ * qpair, input order).  Returns its size in bytes, or a negative SAT_E* code (SAT_ESTATE without a query batch); the
+ * bytes are copied to `out` when it is not NULL and `capacity` holds them.  Tests compare the batches of
+ * sat_queries_set and sat_queries_from_db with it. */
+long long sat_debug_query_blob(struct sat_ctx *ctx, void *out, size_t capacity);
 #ifdef __cplusplus
 }
 #endif
