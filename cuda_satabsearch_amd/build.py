@@ -40,8 +40,8 @@ def _stale(target, sources):
 
 # The device library's translation units, sat_launch.hip (every SA kernel instantiation: minutes) first.  The one list
 # of them: the library, its diagnostic twin, the Makefile and scripts/exp/variant_lib.sh all build from it.
-DEVICE_SOURCES = ("sat_launch.hip", "sat_capi.hip", "sat_db.hip", "sat_topk.hip", "sat_multi.hip", "sat_polish.hip",
-                  "sat_qfromdb.hip")
+DEVICE_SOURCES = ("sat_launch.hip", "sat_capi.hip", "sat_pairs.hip", "sat_db.hip", "sat_topk.hip", "sat_multi.hip",
+                  "sat_polish.hip", "sat_qfromdb.hip")
 # sat_launch.hip and what it includes from csrc/ (diag/ apart, which only -DSAT_DIAG builds read)
 KERNEL_SOURCES = ("sat_sa_kernel.hpp", "sat_sa_body.inc", "sat_launch.hpp", "sat_launch.hip")
 HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "-I", INC, "-I", CSRC]

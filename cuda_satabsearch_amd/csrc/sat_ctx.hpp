@@ -1,5 +1,5 @@
 // sat_ctx.hpp - private definition of the C ABI's context (shared by the library's translation units except
-// sat_launch.hip; not part of the public interface).
+// sat_launch.hip; not part of the public interface).  The pair modes' declarations are in sat_pairs.hpp, which includes it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -134,8 +134,10 @@ struct sat_ctx {
     DevBuf<int32_t> d_prow;
 
     // overrides (SAT_EXP_* in satabsearch_debug.h), read ONCE when the context is created: these of the search plan,
-    // the upload and the pair split, the launch heuristics' in `sa`
-    struct Tuning { int streams = -1, upload_threads = 0, upload_timing = 0, upload_pieces = 0, refine_split = 0, polish_group = 0; } tune;
+    // the upload and the pair split, the launch heuristics' in `sa`.  scratch_bytes: what the scratch in d_bmap_slabs may
+    // take before a search is cut into several launches (every cut keeps at least one slab)
+    struct Tuning { int streams = -1, upload_threads = 0, upload_timing = 0, upload_pieces = 0, refine_split = 0, polish_group = 0;
+                    size_t scratch_bytes = (size_t)1 << 30; } tune;
     // what sat_launch.hip keeps per context: its overrides, the instantiations whose dynamic-LDS limit has been raised
     // on this device, the entries per workgroup chosen so far
     SaLaunchState sa;
@@ -250,46 +252,41 @@ int sat_matches_launch(sat_ctx *ctx, int lorder, int maxstart, int max_matches, 
 int sat_matches_collect(sat_ctx *ctx, int max_matches, int32_t *counts, int32_t *scores, int32_t *restarts,
                         int32_t *ssemaps, size_t total, size_t offset);
 
-// Pair mode (sat_capi.hip).  sat_pairs_launch queues both passes of a pair search on the context's stream (pair p:
-// batch query query[p], shard entry entry[p], restarts 0 .. maxstart - 1; maps: also the map pass); the keys land in
-// ctx->d_pkeys, the maps in ctx->d_pmaps.  sat_pairs_collect waits and copies scores (and maps, -1 past the query's
-// order) to the host.
-int sat_pairs_launch(sat_ctx *ctx, int lorder, int maxstart, bool maps, const int32_t *query, const int32_t *entry, int npairs);
-int sat_pairs_collect(sat_ctx *ctx, int npairs, int32_t *scores, int32_t *ssemaps, const int32_t *query);
-// Pair-match mode (sat_capi.hip), the two halves of sat_search_pairs_matches for sat_multi_search_pairs_matches: queue
-// the record pass, the selection and (maps) the map pass of every launch of the pair list on the context's stream;
-// then wait and copy the rows of pairs 0 .. npairs - 1 (ssemaps may be NULL).
-int sat_pair_matches_launch(sat_ctx *ctx, int lorder, int maxstart, int max_matches, bool maps, const int32_t *query,
-                            const int32_t *entry, int npairs, bool polish = false, bool packed = false);
-int sat_pair_matches_collect(sat_ctx *ctx, int max_matches, int npairs, int32_t *counts, int32_t *scores, int32_t *restarts,
-                             int32_t *ssemaps, const int32_t *query);
-// stage 1 of sat_search_refine: a plain search without LSOLN queued on the context's stream
-int sat_launch_plain(sat_ctx *ctx, int lorder, int maxstart);
-// Polish (sat_polish.hip), the hooks of sat_pair_matches_launch(polish = true) - max_matches is then the number of maps
-// per pair, with maps - and the second half of sat_search_pairs_polish: room for the outputs of `npairs` pairs; the
-// selection of pairs pair0 .. pair0 + n - 1 from the record slabs in ctx->d_bmap_slabs (the ranks go to counts / scores
-// / restarts as pair_match_select lays them out); the polish of the n pairs named by the launch's map items, entries of
-// up to n2max SSEs (outputs in ctx->d_polout / d_polkeys / d_polmaps, rows indexed by the pair); wait and copy the rows
-// of pairs 0 .. npairs - 1 (every output but scores may be NULL).  width: the lanes a map runs on, 16 or 32 (every entry
-// of the items must fit) or 64; sat_polish_width chooses it for an item group (packed: the lane-group kernel wherever the
-// entries fit a group, whatever the size of the launch - the whole-database mode).
-int sat_polish_reserve(sat_ctx *ctx, int npairs);
-int sat_polish_select(sat_ctx *ctx, int pair0, int n, int maxstart, int tops, uint32_t slab_words, int32_t *counts,
-                      int32_t *scores, int32_t *restarts);
-int sat_polish_run(sat_ctx *ctx, int lorder, const SatPairItem *d_map_items, int n, int tops, int n2max, int npairs,
-                   const int32_t *counts, const int32_t *scores, const int32_t *restarts, const int8_t *maps, int width = 64);
-int sat_polish_width(const sat_ctx *ctx, int launch_pairs, int tops, int n2max, bool packed);
-int sat_polish_collect(sat_ctx *ctx, int npairs, int32_t *scores, int32_t *base_scores, int32_t *restarts, int32_t *moves,
-                       int32_t *ssemaps, const int32_t *query);
+#ifdef SAT_DIAG
+// ---- sat_capi.hip, diagnostic builds only: satdiag::begin / end (diag/sat_diag.hpp, whose host side that file holds)
+hipError_t sat_diag_begin(hipStream_t stream, unsigned long long *&arg);
+hipError_t sat_diag_end(hipStream_t stream);
+#endif
+// ---- sat_capi.hip, shared with the pair modes (sat_pairs.hip).  prepare_sa (sat_launch.hpp) for queries of class c of
+// the current batch, with the SatKernelArgs fields every launch shares (base_args)
+int prepare_launch(sat_ctx *ctx, int mode, int lorder, int lsoln, int maxstart, int plan_starts, int c, int n2max, long long work,
+                   bool pack, SaLaunch &out);
+// The head of both match searches: a context, max_matches in range, then the SatMatchArgs fields they share (the record
+// pass; maps of SAT_MAXDIM bytes).  The caller adds the row length and the outputs once its buffers stand.  (The
+// descriptor table is taken before the caller's refresh_descriptors: only sat_set_queries reallocates it.)
+int match_args(const sat_ctx *ctx, int max_matches, SatMatchArgs &mx);
 
-// Whole-database polish (sat_polish_all_set).  sat_polish_all_launch (sat_capi.hip) is the polished
-// form of launch_search over the whole shard on the context's stream: the pairs (q, e) in row order, cut into launches
-// of at most kPolishAllPairs pairs whose record slabs stay under the 1 GiB budget; each launch builds its own item
-// table, runs 6h's passes and scatters its rows (sat_polish_scatter, sat_polish.hip: the launch's n map items, rows of
-// `npairs` pairs) into d_scores, d_base and, with maps, d_ssemaps.  A launch's scratch beyond the slabs is
-// tops x SAT_MAXDIM map bytes, 16 x (1 + tops) bytes of ranks and rows and its items per pair: at most 0.3 GiB, whatever
-// the database.  sat_polish_all_check waits for the stream and fails with SAT_EDEVICE when a row's polish did not finish.
-constexpr int kPolishAllPairs = 1 << 18;
-int sat_polish_all_launch(sat_ctx *ctx, int lorder, int lsoln, int maxstart);
-int sat_polish_scatter(sat_ctx *ctx, const SatPairItem *d_map_items, int n, int npairs, bool maps);
-int sat_polish_all_check(sat_ctx *ctx);
+// One map of the device's outputs (int8, SAT_MAXDIM bytes) as the caller's int32 row: the images of the query's n1
+// SSEs, -1 behind them, all -1 for an unused match slot
+inline void expand_map(const int8_t *in, int n1, bool used, int32_t *out)
+{
+    for (int i = 0; i < SAT_MAXDIM; i++) out[i] = (used && i < n1) ? in[i] : -1;
+}
+
+// queue `launch` on the context's stream between its two timing events, wait for it, *kernel_ms (may be null) = the
+// time between the events
+template <typename F> int timed(sat_ctx *ctx, double *kernel_ms, F launch)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    const int rc = launch();
+    if (rc != SAT_OK) return rc;
+    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (kernel_ms) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+        *kernel_ms = ms;
+    }
+    return SAT_OK;
+}

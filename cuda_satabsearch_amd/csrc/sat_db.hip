@@ -11,7 +11,7 @@
 #include <vector>
 
 #include "satabsearch.h"
-#include "sat_ctx.hpp"
+#include "sat_pairs.hpp"
 
 namespace {
 

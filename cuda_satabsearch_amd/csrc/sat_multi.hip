@@ -32,7 +32,7 @@
 #include <utility>
 #include <vector>
 
-#include "sat_ctx.hpp"
+#include "sat_pairs.hpp"
 #include "sat_cutoff.hpp"
 #include "host/sat_gumbel.h"
 #include "host/sat_shard.h"
@@ -208,6 +208,38 @@ int gather_to_device0(sat_multi *m, T *dst, size_t count, ncclDataType_t type, S
     return SAT_OK;
 }
 
+// the shard that holds entry `entry` of the database
+int shard_of(const sat_multi *m, int entry) { return (int)(std::upper_bound(m->begin.begin(), m->begin.end(), entry) - m->begin.begin()) - 1; }
+
+// A sharded pair call behind its own argument checks: the checks every one shares (a database, a query batch, maxstart,
+// the list and its index ranges), every pair filed with the shard that holds its entry, under the entry's index there;
+// launch(shard context, queries, entries, pairs) queued on every GPU, then collect(shard context, pairs, queries, where)
+// for each shard: row i of a shard goes to row where[i] of the caller's arrays, the one its pair came from.
+template <typename Launch, typename Collect>
+int sharded_pairs(sat_multi *m, int maxstart, int npairs, const int32_t *query, const int32_t *entry, double *wall_ms, Launch launch,
+                  Collect collect)
+{
+    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
+    if (m->ctx[0]->queries.empty()) return sat_fail(SAT_ESTATE, "no query set");
+    if (maxstart < 1) return sat_fail(SAT_EINVAL, "maxstart must be >= 1 (got %d)", maxstart);
+    int rc = sat_check_pairs((int)m->ctx[0]->queries.size(), m->n_entries, query, entry, npairs);
+    if (rc != SAT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<std::vector<int32_t>> pq((size_t)m->ndev), pe((size_t)m->ndev), where((size_t)m->ndev);
+    for (int p = 0; p < npairs; p++) {
+        const int g = shard_of(m, entry[p]);
+        pq[(size_t)g].push_back(query[p]);
+        pe[(size_t)g].push_back(entry[p] - m->begin[(size_t)g]);
+        where[(size_t)g].push_back(p);
+    }
+    rc = each_shard(m, [&](int g) { return launch(m->ctx[(size_t)g], pq[(size_t)g].data(), pe[(size_t)g].data(), (int)pq[(size_t)g].size()); });
+    if (rc != SAT_OK) return rc;
+    rc = each_shard(m, [&](int g) { return collect(m->ctx[(size_t)g], (int)pq[(size_t)g].size(), pq[(size_t)g].data(), where[(size_t)g].data()); });
+    if (rc != SAT_OK) return rc;
+    if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return SAT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -372,7 +404,7 @@ int sat_multi_queries_from_db(sat_multi *m, int n_queries, const int32_t *entry,
     for (int q = 0; q < n_queries; q++) {
         if (entry[q] < 0 || entry[q] >= m->n_entries)
             return sat_fail(SAT_EINVAL, "query %d: entry %d outside 0..%d", q, entry[q], m->n_entries - 1);
-        const int g = (int)(std::upper_bound(m->begin.begin(), m->begin.end(), entry[q]) - m->begin.begin()) - 1;
+        const int g = shard_of(m, entry[q]);
         const int32_t local = entry[q] - m->begin[(size_t)g];
         owner[(size_t)q] = g;
         n1s[(size_t)q] = m->ctx[(size_t)g]->h_orders[(size_t)local];
@@ -545,47 +577,13 @@ int sat_multi_search_pairs_matches(sat_multi *m, int lorder, int maxstart, int m
     if (npairs > 0 && (!counts || !scores || !restarts)) return sat_fail(SAT_EINVAL, "counts / scores / restarts buffer is null");
     if (max_matches < 1 || max_matches > SAT_MAX_MATCHES)
         return sat_fail(SAT_EINVAL, "max_matches must be 1..%d (got %d)", SAT_MAX_MATCHES, max_matches);
-    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
-    if (m->ctx[0]->queries.empty()) return sat_fail(SAT_ESTATE, "no query set");
-    if (maxstart < 1) return sat_fail(SAT_EINVAL, "maxstart must be >= 1 (got %d)", maxstart);
-    if (npairs < 0 || (npairs > 0 && (!query || !entry))) return sat_fail(SAT_EINVAL, "bad pair list");
-    const int nq = (int)m->ctx[0]->queries.size();
-    const auto t0 = std::chrono::steady_clock::now();
-    // every pair goes to the shard that holds its entry, under the entry's index there
-    std::vector<std::vector<int32_t>> pq((size_t)m->ndev), pe((size_t)m->ndev), where((size_t)m->ndev);
-    for (int p = 0; p < npairs; p++) {
-        if (query[p] < 0 || query[p] >= nq) return sat_fail(SAT_EINVAL, "pair %d: query %d out of range", p, query[p]);
-        if (entry[p] < 0 || entry[p] >= m->n_entries) return sat_fail(SAT_EINVAL, "pair %d: entry %d out of range", p, entry[p]);
-        const int g = (int)(std::upper_bound(m->begin.begin(), m->begin.end(), entry[p]) - m->begin.begin()) - 1;
-        pq[(size_t)g].push_back(query[p]);
-        pe[(size_t)g].push_back(entry[p] - m->begin[(size_t)g]);
-        where[(size_t)g].push_back(p);
-    }
-    // queued on every GPU, then each shard's rows scattered back into the caller's order
-    int rc = each_shard(m, [&](int g) {
-        return sat_pair_matches_launch(m->ctx[(size_t)g], lorder, maxstart, max_matches, ssemaps != nullptr, pq[(size_t)g].data(),
-                                       pe[(size_t)g].data(), (int)pq[(size_t)g].size());
-    });
-    if (rc != SAT_OK) return rc;
-    const size_t M = (size_t)max_matches;
-    rc = each_shard(m, [&](int g) {
-        const size_t np = pq[(size_t)g].size();
-        std::vector<int32_t> c(np), sc(np * M), rs(np * M), mp(ssemaps ? np * M * SAT_MAXDIM : 0);
-        const int r = sat_pair_matches_collect(m->ctx[(size_t)g], max_matches, (int)np, c.data(), sc.data(), rs.data(),
-                                               ssemaps ? mp.data() : nullptr, pq[(size_t)g].data());
-        if (r != SAT_OK) return r;
-        for (size_t i = 0; i < np; i++) {
-            const size_t p = (size_t)where[(size_t)g][i];
-            counts[p] = c[i];
-            memcpy(scores + p * M, sc.data() + i * M, M * sizeof(int32_t));
-            memcpy(restarts + p * M, rs.data() + i * M, M * sizeof(int32_t));
-            if (ssemaps) memcpy(ssemaps + p * M * SAT_MAXDIM, mp.data() + i * M * SAT_MAXDIM, M * SAT_MAXDIM * sizeof(int32_t));
-        }
-        return SAT_OK;
-    });
-    if (rc != SAT_OK) return rc;
-    if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return SAT_OK;
+    return sharded_pairs(m, maxstart, npairs, query, entry, wall_ms,
+        [&](sat_ctx *c, const int32_t *q, const int32_t *e, int np) {
+            return sat_pair_matches_launch(c, lorder, maxstart, max_matches, ssemaps != nullptr, q, e, np);
+        },
+        [&](sat_ctx *c, int np, const int32_t *q, const int32_t *where) {
+            return sat_pair_matches_collect(c, max_matches, np, counts, scores, restarts, ssemaps, q, where);
+        });
 }
 
 int sat_multi_search_pairs_polish(sat_multi *m, int lorder, int maxstart, int tops, int npairs, const int32_t *query,
@@ -595,46 +593,13 @@ int sat_multi_search_pairs_polish(sat_multi *m, int lorder, int maxstart, int to
     if (!m) return sat_fail(SAT_EINVAL, "null context");
     if (npairs > 0 && !scores) return sat_fail(SAT_EINVAL, "scores buffer is null");
     if (tops < 1 || tops > SAT_MAX_MATCHES) return sat_fail(SAT_EINVAL, "tops must be 1..%d (got %d)", SAT_MAX_MATCHES, tops);
-    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
-    if (m->ctx[0]->queries.empty()) return sat_fail(SAT_ESTATE, "no query set");
-    if (maxstart < 1) return sat_fail(SAT_EINVAL, "maxstart must be >= 1 (got %d)", maxstart);
-    if (npairs < 0 || (npairs > 0 && (!query || !entry))) return sat_fail(SAT_EINVAL, "bad pair list");
-    const int nq = (int)m->ctx[0]->queries.size();
-    const auto t0 = std::chrono::steady_clock::now();
-    // routed and put back as sat_multi_search_pairs_matches does
-    std::vector<std::vector<int32_t>> pq((size_t)m->ndev), pe((size_t)m->ndev), where((size_t)m->ndev);
-    for (int p = 0; p < npairs; p++) {
-        if (query[p] < 0 || query[p] >= nq) return sat_fail(SAT_EINVAL, "pair %d: query %d out of range", p, query[p]);
-        if (entry[p] < 0 || entry[p] >= m->n_entries) return sat_fail(SAT_EINVAL, "pair %d: entry %d out of range", p, entry[p]);
-        const int g = (int)(std::upper_bound(m->begin.begin(), m->begin.end(), entry[p]) - m->begin.begin()) - 1;
-        pq[(size_t)g].push_back(query[p]);
-        pe[(size_t)g].push_back(entry[p] - m->begin[(size_t)g]);
-        where[(size_t)g].push_back(p);
-    }
-    int rc = each_shard(m, [&](int g) {
-        return sat_pair_matches_launch(m->ctx[(size_t)g], lorder, maxstart, tops, true, pq[(size_t)g].data(), pe[(size_t)g].data(),
-                                       (int)pq[(size_t)g].size(), true);
-    });
-    if (rc != SAT_OK) return rc;
-    rc = each_shard(m, [&](int g) {
-        const size_t np = pq[(size_t)g].size();
-        std::vector<int32_t> out(4 * np), mp(ssemaps ? np * SAT_MAXDIM : 0);
-        const int r = sat_polish_collect(m->ctx[(size_t)g], (int)np, out.data(), out.data() + np, out.data() + 2 * np,
-                                         out.data() + 3 * np, ssemaps ? mp.data() : nullptr, pq[(size_t)g].data());
-        if (r != SAT_OK) return r;
-        for (size_t i = 0; i < np; i++) {
-            const size_t p = (size_t)where[(size_t)g][i];
-            scores[p] = out[i];
-            if (base_scores) base_scores[p] = out[np + i];
-            if (restarts) restarts[p] = out[2 * np + i];
-            if (moves) moves[p] = out[3 * np + i];
-            if (ssemaps) memcpy(ssemaps + p * SAT_MAXDIM, mp.data() + i * SAT_MAXDIM, SAT_MAXDIM * sizeof(int32_t));
-        }
-        return SAT_OK;
-    });
-    if (rc != SAT_OK) return rc;
-    if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return SAT_OK;
+    return sharded_pairs(m, maxstart, npairs, query, entry, wall_ms,
+        [&](sat_ctx *c, const int32_t *q, const int32_t *e, int np) {
+            return sat_pair_matches_launch(c, lorder, maxstart, tops, true, q, e, np, PairMode::Polish);
+        },
+        [&](sat_ctx *c, int np, const int32_t *q, const int32_t *where) {
+            return sat_polish_collect(c, np, scores, base_scores, restarts, moves, ssemaps, q, where);
+        });
 }
 
 }  // extern "C"
@@ -653,7 +618,7 @@ static int multi_refine(sat_multi *m, int lorder, int lsoln, int maxstart, int c
     const auto t0 = std::chrono::steady_clock::now();
     // stage 1 on every shard, each ranking its own best C
     // (a plain search whatever sat_polish_all_set says: the mode is for whole-database searches, not for a refine's stage 1)
-    int rc = each_shard(m, [&](int g) { return sat_launch_plain(m->ctx[(size_t)g], lorder, maxstart); });
+    int rc = each_shard(m, [&](int g) { return launch_search(m->ctx[(size_t)g], lorder, 0, maxstart, m->ctx[(size_t)g]->stream); });
     if (rc != SAT_OK) return rc;
     const int c = candidates < m->n_entries ? candidates : m->n_entries;
     if (k > c) k = c;
@@ -687,7 +652,7 @@ static int multi_refine(sat_multi *m, int lorder, int lsoln, int maxstart, int c
     rc = each_shard(m, [&](int g) {
         if (tops)
             return sat_pair_matches_launch(m->ctx[(size_t)g], lorder, refine_maxstart, tops, true, pq[(size_t)g].data(),
-                                           pe[(size_t)g].data(), (int)pq[(size_t)g].size(), true);
+                                           pe[(size_t)g].data(), (int)pq[(size_t)g].size(), PairMode::Polish);
         return sat_pairs_launch(m->ctx[(size_t)g], lorder, refine_maxstart, maps, pq[(size_t)g].data(), pe[(size_t)g].data(),
                                 (int)pq[(size_t)g].size());
     });

@@ -2,69 +2,18 @@
 // include/satabsearch.h).
 //
 // The pair-match mode's record pass files the own best s_r of every restart of a pair; its map pass re-runs chosen
-// restarts for their own-best maps.  Between the two, pair_polish_select takes the T largest keys (s_r, ~r) of a pair -
-// pair_match_select without the set test -, and behind them pair_polish climbs from each of the T maps to a local
-// optimum of the search's neighbourhood by best improvement and reports the best of the T results.  Both kernels and
-// their launch code live here; sat_capi.hip only calls them from sat_pair_matches_launch.
+// restarts for their own-best maps.  Between the two, pair_polish_select (sat_pairs.hip, beside pair_match_select, which
+// it is without the set test) takes the T largest keys (s_r, ~r) of a pair, and behind them pair_polish climbs from each
+// of the T maps to a local optimum of the search's neighbourhood by best improvement and reports the best of the T
+// results.  The polish kernels and their launch code live here; sat_pair_matches_launch calls them.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 #include <vector>
 
-#include "sat_ctx.hpp"
+#include "sat_pairs.hpp"
 
 namespace {
-
-// ---------------------------------------------------------------- selection
-// One workgroup per pair of a launch, over the pair's record slab (restart-major: the R own bests first; the set words
-// behind them are not read).  Round t takes the largest key below the one taken before - keys are distinct, their low
-// word is the restart - so rank t holds the t-th restart by descending (s_r, -r).  Same outputs as pair_match_select:
-// counts[pair] = min(T, R), or -1 when rank 0 is not the arg-max key the record pass folded into keys[pair]; scores /
-// restarts [pair][T], 0 / -1 past the count.
-__global__ void __launch_bounds__(256) pair_polish_select(int pair0, int R, int T, const uint32_t *slabs, uint32_t slab_words,
-                                                          const unsigned long long *keys, int32_t *counts, int32_t *scores,
-                                                          int32_t *restarts)
-{
-    __shared__ unsigned long long red[4];
-    const int p = pair0 + (int)blockIdx.x;
-    const uint32_t *rec = slabs + (size_t)blockIdx.x * slab_words;
-    const int t = (int)threadIdx.x, wave = t >> 6;
-    unsigned long long prev = ~0ull, first = 0ull;
-    int m = 0;
-    for (int round = 0; round < T; round++) {
-        __syncthreads();                               // `red` is free again
-        unsigned long long k = 0ull;
-        for (int r = t; r < R; r += 256) {
-            const int s = (int)rec[r];
-            const unsigned long long rk = (((unsigned long long)(uint32_t)(s + 0x40000000)) << 32) | (0xFFFFFFFFu - (uint32_t)r);
-            k = (rk < prev && rk > k) ? rk : k;
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const unsigned long long other = __shfl_xor(k, off, 64);
-            k = other > k ? other : k;
-        }
-        if ((t & 63) == 0) red[wave] = k;
-        __syncthreads();
-        unsigned long long cur = red[0];
-        for (int w = 1; w < 4; w++) cur = red[w] > cur ? red[w] : cur;
-        if (cur == 0ull) break;                        // (the same for every thread: fewer than T restarts)
-        if (round == 0) first = cur;
-        if (t == 0) {
-            scores[(size_t)p * T + m] = (int32_t)(uint32_t)(cur >> 32) - 0x40000000;
-            restarts[(size_t)p * T + m] = (int32_t)(0xFFFFFFFFu - (uint32_t)(cur & 0xFFFFFFFFu));
-        }
-        prev = cur;
-        m++;
-    }
-    if (t == 0) {
-        counts[p] = first == keys[p] ? m : -1;
-        for (int x = m; x < T; x++) {
-            scores[(size_t)p * T + x] = 0;
-            restarts[(size_t)p * T + x] = -1;
-        }
-    }
-}
 
 // ---------------------------------------------------------------- polish
 struct PolishArgs {
@@ -83,7 +32,7 @@ struct PolishArgs {
     int32_t npairs;               // row length of `out`
     int32_t nitems;               // pair_polish_group: items of the launch (a workgroup holds several)
     int32_t *out;                 // [4][npairs]: score, base score, restart, moves (-1: error)
-    unsigned long long *okeys;    // [pairs] (score + 2^30) << 32, the high word of a pair key (the refine ranking's)
+    unsigned long long *okeys;    // [pairs] pair_key(score, ~0): the high word of a pair key, low word 0 (the refine ranking's)
     int8_t *omaps;                // [pairs][SAT_MAXDIM] the winner's polished map, -1 = unmatched
 };
 
@@ -280,7 +229,7 @@ __global__ void __launch_bounds__(64 * SAT_MAX_MATCHES) pair_polish(const Polish
             a.out[(size_t)a.npairs + p] = ok ? a.scores[(size_t)p * T] : 0;
             a.out[2 * (size_t)a.npairs + p] = ok ? a.restarts[(size_t)p * T + win] : -1;
             a.out[3 * (size_t)a.npairs + p] = ok ? resL[T + win] : -1;
-            a.okeys[p] = ((unsigned long long)(uint32_t)(s + 0x40000000)) << 32;
+            a.okeys[p] = pair_key(s, 0xFFFFFFFFu);
         }
         const int8_t *wm = mapsL + (size_t)(ok ? win : 0) * kListStride;
         for (int i = lane; i < SAT_MAXDIM; i += 64) a.omaps[(size_t)p * SAT_MAXDIM + i] = (ok && i < n1) ? wm[i] : (int8_t)-1;
@@ -500,7 +449,7 @@ __global__ void __launch_bounds__(256) pair_polish_group(const PolishArgs a)
             a.out[(size_t)a.npairs + p] = ok ? a.scores[(size_t)p * T] : 0;
             a.out[2 * (size_t)a.npairs + p] = ok ? a.restarts[(size_t)p * T + win] : -1;
             a.out[3 * (size_t)a.npairs + p] = ok ? resL[NG + g + win] : -1;
-            a.okeys[p] = ((unsigned long long)(uint32_t)(s + 0x40000000)) << 32;
+            a.okeys[p] = pair_key(s, 0xFFFFFFFFu);
         }
         const int8_t *wm = reinterpret_cast<const int8_t *>(groupL + (size_t)(ok ? win : 0) * kGroupBytes + (size_t)kListStride * 12u);
         for (int i = gl; i < SAT_MAXDIM; i += G) a.omaps[(size_t)p * SAT_MAXDIM + i] = (ok && i < n1) ? wm[i] : (int8_t)-1;
@@ -532,7 +481,7 @@ __global__ void __launch_bounds__(256) polish_scatter(const SatPairItem *items, 
 
 }  // namespace
 
-// ---------------------------------------------------------------- launch code (sat_ctx.hpp)
+// ---------------------------------------------------------------- launch code (sat_pairs.hpp)
 
 int sat_polish_reserve(sat_ctx *ctx, int npairs)
 {
@@ -541,16 +490,6 @@ int sat_polish_reserve(sat_ctx *ctx, int npairs)
         (rc = ctx->d_polkeys.grow_after(ctx->stream, (size_t)npairs)) != SAT_OK ||
         (rc = ctx->d_polmaps.grow_after(ctx->stream, (size_t)npairs * SAT_MAXDIM)) != SAT_OK)
         return rc;
-    return SAT_OK;
-}
-
-int sat_polish_select(sat_ctx *ctx, int pair0, int n, int maxstart, int tops, uint32_t slab_words, int32_t *counts,
-                      int32_t *scores, int32_t *restarts)
-{
-    hipLaunchKernelGGL(pair_polish_select, dim3((unsigned)n), dim3(256), 0, ctx->stream, pair0, maxstart, tops,
-                       (const uint32_t *)ctx->d_bmap_slabs.get(), slab_words, (const unsigned long long *)ctx->d_pkeys.get(),
-                       counts, scores, restarts);
-    HIP_TRY(hipGetLastError());
     return SAT_OK;
 }
 
@@ -614,7 +553,7 @@ int sat_polish_scatter(sat_ctx *ctx, const SatPairItem *d_map_items, int n, int 
 
 // wait for the polish and copy its rows: 16 * npairs bytes, + SAT_MAXDIM * npairs with maps
 int sat_polish_collect(sat_ctx *ctx, int npairs, int32_t *scores, int32_t *base_scores, int32_t *restarts, int32_t *moves,
-                       int32_t *ssemaps, const int32_t *query)
+                       int32_t *ssemaps, const int32_t *query, const int32_t *where)
 {
     HIP_TRY(hipSetDevice(ctx->device));
     if (npairs == 0) return SAT_OK;
@@ -626,20 +565,12 @@ int sat_polish_collect(sat_ctx *ctx, int npairs, int32_t *scores, int32_t *base_
     for (size_t p = 0; p < P; p++)
         if (out[3 * P + p] < 0)
             return sat_fail(SAT_EDEVICE, "pair %zu: the polish did not finish (records and arg-max key disagree, or the move cap was reached)", p);
-    memcpy(scores, out.data(), P * sizeof(int32_t));
-    if (base_scores) memcpy(base_scores, out.data() + P, P * sizeof(int32_t));
-    if (restarts) memcpy(restarts, out.data() + 2 * P, P * sizeof(int32_t));
-    if (moves) memcpy(moves, out.data() + 3 * P, P * sizeof(int32_t));
-    if (ssemaps) {
-        std::vector<int8_t> mp(P * SAT_MAXDIM);
-        HIP_TRY(hipMemcpy(mp.data(), ctx->d_polmaps.get(), mp.size(), hipMemcpyDeviceToHost));
-        ctx->d2h_bytes += mp.size();
-        for (size_t p = 0; p < P; p++) {
-            const int n1 = ctx->queries[(size_t)query[p]].n1;
-            for (int i = 0; i < SAT_MAXDIM; i++) ssemaps[p * SAT_MAXDIM + i] = i < n1 ? mp[p * SAT_MAXDIM + i] : -1;
-        }
+    int32_t *const dst[4] = { scores, base_scores, restarts, moves };
+    for (size_t k = 0; k < 4; k++) {
+        if (dst[k] && !where) memcpy(dst[k], out.data() + k * P, P * sizeof(int32_t));
+        for (size_t p = 0; dst[k] && where && p < P; p++) dst[k][where[p]] = out[k * P + p];
     }
-    return SAT_OK;
+    return ssemaps ? sat_collect_maps(ctx, ctx->d_polmaps.get(), P, 1, query, nullptr, where, ssemaps) : SAT_OK;
 }
 
 extern "C" int sat_search_pairs_polish(sat_ctx *ctx, int lorder, int maxstart, int tops, int npairs, const int32_t *query,
@@ -648,16 +579,9 @@ extern "C" int sat_search_pairs_polish(sat_ctx *ctx, int lorder, int maxstart, i
 {
     if (!ctx) return sat_fail(SAT_EINVAL, "null context");
     if (npairs > 0 && !scores) return sat_fail(SAT_EINVAL, "scores buffer is null");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    const int rc = sat_pair_matches_launch(ctx, lorder, maxstart, tops, true, query, entry, npairs, true);
+    const int rc = timed(ctx, kernel_ms, [&] {
+        return sat_pair_matches_launch(ctx, lorder, maxstart, tops, true, query, entry, npairs, PairMode::Polish);
+    });
     if (rc != SAT_OK) return rc;
-    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (kernel_ms) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-        *kernel_ms = ms;
-    }
     return sat_polish_collect(ctx, npairs, scores, base_scores, restarts, moves, ssemaps, query);
 }

@@ -22,14 +22,15 @@
 #include <cmath>
 #include <vector>
 
-#include "sat_ctx.hpp"
+#include "sat_pairs.hpp"
 #include "sat_cutoff.hpp"
 #include "host/sat_gumbel.h"
 
 namespace {
 
 // key = biased score in the high word, inverted entry index in the low word: a descending
-// sort lists higher scores first and, among equal scores, lower entry indices first
+// sort lists higher scores first and, among equal scores, lower entry indices first (pair_key, spelled out here: through
+// the helper this kernel compiles to other instructions, and its code stays what it was)
 __global__ void pack_keys(const int32_t *scores, long long total, int n, unsigned long long *keys)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -78,8 +79,7 @@ __global__ void finish_hits(const unsigned long long *sorted, int n, int k, int 
     if (t >= nq * k) return;
     const int q = t / k, r = t - q * k;
     const unsigned long long key = sorted[(size_t)q * n + r];
-    const int32_t entry = (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFu));
-    const int32_t score = (int32_t)(uint32_t)(key >> 32) - 0x40000000;
+    const int32_t entry = key_index(key), score = key_score(key);
     const int n1 = queries[q].n1, n2 = orders[entry];
     hits[t] = hit_row(entry, score, n1, n2, ztab, ptab, queries[q].fit);
     if (maps) {
@@ -180,7 +180,7 @@ __global__ void pack_refined(const unsigned long long *pkeys, const sat_hit *can
 {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= npairs) return;
-    keys[p] = (pkeys[p] & 0xFFFFFFFF00000000ull) | (0xFFFFFFFFu - (uint32_t)cand[p].entry);
+    keys[p] = pair_key(key_score(pkeys[p]), (uint32_t)cand[p].entry);
     vals[p] = p;
 }
 
@@ -195,8 +195,7 @@ __global__ void finish_refined(const unsigned long long *sorted, const int32_t *
     const int q = t / k, r = t - q * k;
     const unsigned long long key = sorted[(size_t)q * c + r];
     const int p = vals[(size_t)q * c + r];
-    const int32_t entry = (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFu));
-    const int32_t score = (int32_t)(uint32_t)(key >> 32) - 0x40000000;
+    const int32_t entry = key_index(key), score = key_score(key);
     const int n1 = queries[q].n1;
     hits[t] = hit_row(entry, score, n1, orders[entry], ztab, ptab, queries[q].fit);
     first[t] = cand[p].score;
@@ -280,7 +279,7 @@ __global__ void __launch_bounds__(kCutoffBlock) cutoff_compact(const int32_t *sc
     __syncthreads();
     if (hit) {
         const int slot = seg[q] + wave_base[kCutoffWaves] + wave_base[wave] + (int)__popcll(mask & ((1ull << lane) - 1ull));
-        keys[slot] = ((unsigned long long)(uint32_t)(score + 0x40000000) << 32) | (0xFFFFFFFFu - (uint32_t)e);
+        keys[slot] = pair_key(score, (uint32_t)e);
     }
 }
 
@@ -299,8 +298,7 @@ __global__ void cutoff_finish(const unsigned long long *sorted, const int32_t *s
     }
     const int q = lo, r = t - out_off[q];
     const unsigned long long key = sorted[seg[q] + r];
-    const int32_t entry = (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFu));
-    const int32_t score = (int32_t)(uint32_t)(key >> 32) - 0x40000000;
+    const int32_t entry = key_index(key), score = key_score(key);
     const int n1 = queries[q].n1;
     hits[t] = hit_row(entry, score, n1, orders[entry], ztab, ptab, queries[q].fit);
     if (maps) {
@@ -511,7 +509,7 @@ static int refine(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int candida
     if (k > candidates) return sat_fail(SAT_EINVAL, "k (%d) exceeds the candidates per query (%d)", k, candidates);
     HIP_TRY(hipSetDevice(ctx->device));
     // stage 1: the plain search at maxstart, without LSOLN
-    int rc = sat_launch_plain(ctx, lorder, maxstart);
+    int rc = launch_search(ctx, lorder, 0, maxstart, ctx->stream);
     if (rc != SAT_OK) return rc;
     const std::string stage1_info = ctx->last_launch_info;
     const int n = ctx->n_entries, nq = (int)ctx->queries.size();
@@ -528,7 +526,7 @@ static int refine(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int candida
     for (int p = 0; p < npairs; p++) query[(size_t)p] = p / c;
     // stage 2: the candidates at refine_maxstart (and their maps)
     const bool maps = lsoln && ssemaps;
-    rc = tops ? sat_pair_matches_launch(ctx, lorder, refine_maxstart, tops, true, query.data(), entry.data(), npairs, true)
+    rc = tops ? sat_pair_matches_launch(ctx, lorder, refine_maxstart, tops, true, query.data(), entry.data(), npairs, PairMode::Polish)
               : sat_pairs_launch(ctx, lorder, refine_maxstart, maps, query.data(), entry.data(), npairs);
     if (rc != SAT_OK) return rc;
     const unsigned long long *pkeys = tops ? ctx->d_polkeys.get() : ctx->d_pkeys.get();

@@ -30,6 +30,35 @@ def sa_kernel_instances():
     return lib.sat_debug_sa_instances().decode().splitlines()
 
 
+def _pack_queries(queries):
+    """a list of (qtab[n1, n1+], qdmat, qssetypes) triples as sat_queries_set takes a batch: (nq, pitch, n1s int32[nq],
+    tabs uint8[nq, pitch, pitch], dmats float32[nq, pitch, pitch], types uint8[nq, pitch])"""
+    nq = len(queries)
+    pitch = max(int(np.asarray(q[0]).shape[0]) for q in queries)
+    n1s = np.empty(nq, np.int32)
+    tabs = np.zeros((nq, pitch, pitch), np.uint8)
+    dmats = np.zeros((nq, pitch, pitch), np.float32)
+    types = np.zeros((nq, pitch), np.uint8)
+    for k, (t, d, ty) in enumerate(queries):
+        t = np.asarray(t, np.uint8)
+        d = np.asarray(d, np.float32)
+        n1 = t.shape[0]
+        n1s[k] = n1
+        tabs[k, :n1, :n1] = t[:, :n1]
+        dmats[k, :n1, :n1] = d[:, :n1]
+        types[k, :n1] = np.asarray(ty, np.uint8)[:n1] if ty is not None else np.diagonal(t)[:n1]
+    return nq, pitch, n1s, tabs, dmats, types
+
+
+def _pair_lists(queries, entries):
+    """a pair list as the pair searches take it: two int32 arrays of one length"""
+    q = np.ascontiguousarray(queries, dtype=np.int32).ravel()
+    e = np.ascontiguousarray(entries, dtype=np.int32).ravel()
+    if q.shape != e.shape:
+        raise ValueError("queries and entries differ in length")
+    return q, e
+
+
 def _search_matches(obj, fn, handle, max_matches, lorder, maxstart, maps):
     nq, n, m = obj.n_queries, obj.n_entries, max(int(max_matches), 1)
     counts = np.zeros((nq, n), np.int32)
@@ -44,10 +73,7 @@ def _search_matches(obj, fn, handle, max_matches, lorder, maxstart, maps):
 
 def _search_pairs_matches(obj, fn, handle, queries, entries, max_matches, lorder, maxstart, maps):
     """shared by Searcher / MultiSearcher.search_pairs_matches"""
-    q = np.ascontiguousarray(queries, dtype=np.int32).ravel()
-    e = np.ascontiguousarray(entries, dtype=np.int32).ravel()
-    if q.shape != e.shape:
-        raise ValueError("queries and entries differ in length")
+    q, e = _pair_lists(queries, entries)
     p, m = len(q), max(int(max_matches), 1)
     counts = np.zeros(p, np.int32)
     scores = np.zeros((p, m), np.int32)
@@ -62,10 +88,7 @@ def _search_pairs_matches(obj, fn, handle, queries, entries, max_matches, lorder
 
 def _search_pairs_polish(obj, fn, handle, queries, entries, tops, lorder, maxstart):
     """shared by Searcher / MultiSearcher.search_pairs_polish"""
-    q = np.ascontiguousarray(queries, dtype=np.int32).ravel()
-    e = np.ascontiguousarray(entries, dtype=np.int32).ravel()
-    if q.shape != e.shape:
-        raise ValueError("queries and entries differ in length")
+    q, e = _pair_lists(queries, entries)
     p = len(q)
     scores, base, restarts, moves = (np.zeros(p, np.int32) for _ in range(4))
     ssemaps = np.full((p, MAXDIM), -1, np.int32)
@@ -259,20 +282,7 @@ class Searcher:
         (qtab[n1, n1+], qdmat, qssetypes) triples.  search() then returns scores[nq, N]
         (and ssemaps[nq, N, 111]); query q draws from the streams of ordinal
         first_query_ordinal + q."""
-        nq = len(queries)
-        pitch = max(int(np.asarray(q[0]).shape[0]) for q in queries)
-        n1s = np.empty(nq, np.int32)
-        tabs = np.zeros((nq, pitch, pitch), np.uint8)
-        dmats = np.zeros((nq, pitch, pitch), np.float32)
-        types = np.zeros((nq, pitch), np.uint8)
-        for k, (t, d, ty) in enumerate(queries):
-            t = np.asarray(t, np.uint8)
-            d = np.asarray(d, np.float32)
-            n1 = t.shape[0]
-            n1s[k] = n1
-            tabs[k, :n1, :n1] = t[:, :n1]
-            dmats[k, :n1, :n1] = d[:, :n1]
-            types[k, :n1] = np.asarray(ty, np.uint8)[:n1] if ty is not None else np.diagonal(t)[:n1]
+        nq, pitch, n1s, tabs, dmats, types = _pack_queries(queries)
         self._check(self._lib.sat_queries_set(self._ctx, nq, n1s.ctypes.data, tabs.ctypes.data, dmats.ctypes.data,
                                               pitch, types.ctypes.data, int(first_query_ordinal)))
         self.n1 = int(n1s[0])
@@ -339,10 +349,7 @@ class Searcher:
         """Scores of chosen (query, entry) pairs only (sat_search_pairs): queries[p] indexes the current batch,
         entries[p] the resident shard.  Returns (scores int32[P], maps int32[P, 111] or None): exactly what
         search() gives for those rows at the same maxstart."""
-        q = np.ascontiguousarray(queries, dtype=np.int32).ravel()
-        e = np.ascontiguousarray(entries, dtype=np.int32).ravel()
-        if q.shape != e.shape:
-            raise ValueError("queries and entries differ in length")
+        q, e = _pair_lists(queries, entries)
         scores = np.zeros(len(q), np.int32)
         maps = np.full((len(q), MAXDIM), -1, np.int32) if lsoln else None
         ms = C.c_double(0.0)
@@ -575,20 +582,7 @@ class MultiSearcher:
         return begin
 
     def set_queries(self, queries, first_query_ordinal=0):
-        nq = len(queries)
-        pitch = max(int(np.asarray(q[0]).shape[0]) for q in queries)
-        n1s = np.empty(nq, np.int32)
-        tabs = np.zeros((nq, pitch, pitch), np.uint8)
-        dmats = np.zeros((nq, pitch, pitch), np.float32)
-        types = np.zeros((nq, pitch), np.uint8)
-        for k, (t, d, ty) in enumerate(queries):
-            t = np.asarray(t, np.uint8)
-            d = np.asarray(d, np.float32)
-            n1 = t.shape[0]
-            n1s[k] = n1
-            tabs[k, :n1, :n1] = t[:, :n1]
-            dmats[k, :n1, :n1] = d[:, :n1]
-            types[k, :n1] = np.asarray(ty, np.uint8)[:n1] if ty is not None else np.diagonal(t)[:n1]
+        nq, pitch, n1s, tabs, dmats, types = _pack_queries(queries)
         self._check(self._lib.sat_multi_queries_set(self._m, nq, n1s.ctypes.data, tabs.ctypes.data, dmats.ctypes.data,
                                                     pitch, types.ctypes.data, int(first_query_ordinal)))
         self.n_queries = nq

@@ -18,6 +18,9 @@
  *   SAT_EXP_POLISH_GROUP = 0|16|32|64  lanes a map of the polish runs on (sat_polish.hip; default 0: groups of 16 / 32 lanes for
  *                                entries of up to 16 / 32 SSEs in the whole-database mode and in large pair launches,
  *                                else a wave).  A forced width serves the entries it can hold; wider ones fall to the next
+ *   SAT_EXP_SCRATCH_KB = n       scratch a search may take before it is cut into several launches, in KiB (default 0: 1 GiB; the
+ *                                LSOLN best-map slabs of a plain or match search, the record slabs of a pair-match / polish
+ *                                list, the map pass of the pair modes at most 256 MiB of it).  Every cut keeps one slab at least
  *   SAT_EXP_STREAMS = 0          queue the order buckets of a search one after the other instead of concurrently
  *   SAT_EXP_UPLOAD_THREADS = n   host threads slicing the database copy (default 4)
  *   SAT_EXP_UPLOAD_TIMING = 1    per-phase upload times on stderr

@@ -8,7 +8,7 @@ the CPU reference's bit for bit.  The expected name of a recipe is worked out HE
 prepare_sa / pick_sa_kernel written down once more, below), never read from the enumeration: a dispatcher that picks
 another kernel than the rules promise fails (a), whatever it computes.
 
-How a recipe steers each template argument (sat_launch.hip, sat_capi.hip, sat_db.hip):
+How a recipe steers each template argument (sat_launch.hip, sat_capi.hip, sat_pairs.hip, sat_db.hip):
   family   the API call: search / search_matches / search_pairs / search_pairs_matches.
   N1P      the query order: <= 16, <= 32, <= 64, above (sat_queries_set).
   M2W, CELLS   entries x queries of a class <= 4096 go out as ONE launch laid out for the database's largest entry

@@ -1,8 +1,8 @@
 """The whole-database polish on the GPU (-m gpu): sat_polish_all_set turns a plain search into a polished one.  Scores,
 base scores and maps of every row against the CPU reference (tests/polish_lib.py) bit for bit on the edge database and on
 the edges of the lane-group polish kernel, under every forced group width; agreement with sat_search_pairs_polish; the
-result calls downstream of the polished buffers; the life of the mode; shards; forced execution modes; and the command
-line's -P T -A against the library."""
+result calls downstream of the polished buffers; the life of the mode; shards; forced execution modes; the command
+line's -P T -A against the library; and every search cut into several launches by a 16 KB scratch budget."""
 import os
 import subprocess
 import sys
@@ -12,6 +12,7 @@ import pytest
 
 import cuda_satabsearch_amd as sat
 import edge_cases as ec
+import matches_lib
 import polish_all_lib as pal
 
 pytestmark = pytest.mark.gpu
@@ -334,3 +335,67 @@ def test_cli_all_rows_are_the_librarys(golden_dir, name, args):
         want += format_rows(small.names, len(query[2]), hits[b], maps[b] if lsoln else None, lsoln)
     assert p.stdout.decode() == "".join(want)
     assert p.stdout.count(b"# POLISH") == len(queries)
+
+
+# ---------------------------------------------------------------- 9. the cut paths
+CUT_KB = 16
+
+
+@pytest.fixture(scope="module")
+def cut_pairs(group):
+    """all 60 (query, entry) pairs of the group database, shuffled"""
+    db, queries = group[0], group[1]
+    q, e = np.divmod(np.random.default_rng(9).permutation(len(queries) * len(db)).astype(np.int32), np.int32(len(db)))
+    return q, e
+
+
+@pytest.mark.parametrize("lorder", [True, False], ids=["LORDER_T", "LORDER_F"])
+def test_a_16_kb_scratch_budget_cuts_every_search_and_changes_no_result(monkeypatch, group, cut_pairs, lorder):
+    """SAT_EXP_SCRATCH_KB = 16 leaves 16384 / 4 = 4096 words of scratch: every search of the group database (12 entries of
+    up to 65 SSEs, queries of 1, 16, 17, 33 and 111 SSEs, 64 restarts) is cut into several launches, and every row still
+    equals the CPU reference.
+
+    * Record slabs of a pair-match / polish list.  The list's largest entry has 65 SSEs, satk::set_words(65) = 4, so a
+      pair's slab is (1 + 4) x 64 restarts = 320 words and 4096 / 320 = 12 pairs fit: the 60 rows of the polished
+      search are 5 launches of 12 (each the one launch of its own pair-match plan: both in the launch string), the 60 shuffled
+      pairs of search_pairs_matches 5 launches of 12 with SatPairItem::slab counted from each launch's first pair.
+    * Map pass of the pair modes: min(16 KB, 256 MB) = 4096 words.  A best-map slab is ceil(n1max / 4) words x 64 chains
+      (1, 3 or 8 restarts per item size the workgroup for 64): 256 words for the class of the 1- and 16-SSE queries,
+      320 for 17 SSEs, 576 for 33, 1792 for 111 - at most 16, 12, 7 and 2 items per launch.  The 111-SSE query meets the
+      5 entries of up to 16 SSEs in one item group: launches of 2, 2 and 1 items, in search_pairs and in the polished
+      search's launch of that query.
+    * LSOLN slabs of the plain search.  Four query classes, each one launch of the 12 entries, on four lanes of
+      4096 / 4 = 1024 words: 1024 / 256 = 4 workgroups = 2 entries x 2 queries, 1024 / 320 = 3 entries, 1024 / 576 = 1
+      entry, and below one slab of 1792 words the floor of 1 entry: 6 + 4 + 12 + 12 launches."""
+    db, queries, ref, _ = group
+    q, e = cut_pairs
+    n, nq, npairs = len(db), len(queries), len(q)
+    assert n == 12 and nq == 5 and npairs == 60
+    monkeypatch.setenv("SAT_EXP_SCRATCH_KB", str(CUT_KB))              # read when the context is created
+    with sat.Searcher(0) as s:
+        s.upload(db)
+        s.set_queries(queries, pal.GROUP_FIRST)
+        s.set_polish_all(8)
+        scores, maps, _ = s.search(lorder, True, 64)
+        base, info_all = s.results_base(), s.last_launch_info()
+        s.set_polish_all(0)
+        counts, mscores, mrestarts, mmaps, _ = s.search_pairs_matches(q, e, 3, lorder, 64)
+        info_matches = s.last_launch_info()
+        pscores, pmaps = s.search_pairs(q, e, lorder, True, 64)
+        plain, plain_maps, _ = s.search(lorder, True, 64)
+    # 1. the polished search
+    assert_same((scores, base, maps), ref.all_rows(lorder, 64, 8), "polished search: ")
+    assert info_all.startswith("polish all (8 tops, 5 launches of up to 12 pairs): record pass (64 restarts, "), info_all
+    assert ", 1 launches of up to 12 pairs): " in info_all, info_all      # each of the 5 is one launch of its own plan
+    # 2. search_pairs_matches; 3. search_pairs; 4. the plain search: slot 0 of the selection is the best restart
+    assert "5 launches of up to 12 pairs): " in info_matches, info_matches
+    for p in range(npairs):
+        n1 = len(queries[q[p]][2])
+        c, sc, rs, mp = matches_lib.select_matches(*ref.restarts(int(q[p]), int(e[p]), lorder, 64), 3)
+        what = "pair %d (query %d, entry %d)" % (p, q[p], e[p])
+        got = (int(counts[p]), list(mscores[p]), list(mrestarts[p]))
+        assert got == (c, list(sc), list(rs)), "%s: gpu %s reference %s" % (what, got, (c, list(sc), list(rs)))
+        assert np.array_equal(mmaps[p, :, :n1], mp[:, :n1]) and (mmaps[p, :, n1:] == -1).all(), what + ": match maps"
+        assert pscores[p] == sc[0] and plain[q[p], e[p]] == sc[0], what + ": best score"
+        for name, got_map in (("search_pairs", pmaps[p]), ("search", plain_maps[q[p], e[p]])):
+            assert np.array_equal(got_map[:n1], mp[0, :n1]) and (got_map[n1:] == -1).all(), "%s: map of %s" % (what, name)

@@ -77,6 +77,22 @@ def test_the_kernel_source_hash_covers_the_kernel_translation_unit_and_nothing_e
         assert (re.search(r"\bsat_sa_(pair_|match_|pair_match_)?kernel\s*<", text) is not None) == (f == "sat_launch.hip"), f
 
 
+def test_the_pair_modes_are_a_translation_unit_of_the_device_library(monkeypatch):
+    """sat_pairs.hip is in build.DEVICE_SOURCES, and build_device() compiles it for gfx950 to an object of its own that
+    the library links (the commands are recorded, not run); sat_capi.hip, which held the pair modes, holds no kernel."""
+    from cuda_satabsearch_amd import build
+    assert "sat_pairs.hip" in build.DEVICE_SOURCES
+    cmds = []
+    monkeypatch.setattr(build, "_run", cmds.append)
+    build.build_device(force=True)
+    compiles = [c for c in cmds if "-c" in c and c[-1] == os.path.join(build.CSRC, "sat_pairs.hip")]
+    assert len(compiles) == 1 and "--offload-arch=gfx950" in compiles[0]
+    obj = compiles[0][compiles[0].index("-o") + 1]
+    links = [c for c in cmds if "-shared" in c and c[c.index("-o") + 1] == build.DEVICE_LIB[0]]
+    assert len(links) == 1 and "-Wl," + obj in links[0]
+    assert "__global__" not in open(os.path.join(build.CSRC, "sat_capi.hip")).read()
+
+
 def test_a_build_without_the_instance_hook_still_loads(monkeypatch):
     """SAT_DEVICE_LIB loads other builds of the ABI (A/B runs, the diagnostic twin): the hook of satabsearch_debug.h is
     not part of the ABI, so a library from before it must load, and only asking for the list fails."""
