@@ -6,7 +6,8 @@
 #   make test       CPU test suite;  make test-gpu on a machine with an MI355X
 # The sources, flags and dependencies of all three are cuda_satabsearch_amd/build.py's alone (DEVICE_SOURCES: one object
 # per translation unit of the device library, re-made only when it or a header it includes changed: sat_launch.hip,
-# sat_capi.hip, sat_pairs.hip, sat_db.hip, sat_topk.hip, sat_multi.hip, sat_polish.hip, sat_qfromdb.hip).
+# sat_capi.hip, sat_pairs.hip, sat_db.hip, sat_topk.hip, sat_multi.hip, sat_polish.hip, sat_qfromdb.hip,
+# sat_cluster.hip).
 PKG      = cuda_satabsearch_amd
 
 all:

@@ -33,6 +33,8 @@ ABI_SYMBOLS = (
     "sat_search_pairs_polish", "sat_search_refine_polish", "sat_multi_search_pairs_polish", "sat_multi_search_refine_polish",
     "sat_polish_all_set", "sat_polish_all_get", "sat_results_base", "sat_multi_polish_all_set",
     "sat_queries_from_db", "sat_multi_queries_from_db", "sat_stat_query_h2d_bytes",
+    "sat_cluster_begin", "sat_cluster_add", "sat_cluster_labels", "sat_cluster_end",
+    "sat_multi_search_only", "sat_multi_cluster_begin", "sat_multi_cluster_add", "sat_multi_cluster_labels",
 )
 
 STAT_BINS = 4096
@@ -158,6 +160,16 @@ def device_lib():
             lib.sat_stat_query_h2d_bytes.restype = C.c_uint64
             lib.sat_debug_query_blob.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]      # include/satabsearch_debug.h
             lib.sat_debug_query_blob.restype = C.c_longlong
+        # (as above: a build of the parent commit predates the clustering)
+        if hasattr(lib, "sat_cluster_begin"):
+            lib.sat_cluster_begin.argtypes = [C.c_void_p, C.c_int]
+            lib.sat_cluster_add.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
+            lib.sat_cluster_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.sat_cluster_end.argtypes = [C.c_void_p]
+            lib.sat_multi_search_only.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
+            lib.sat_multi_cluster_begin.argtypes = [C.c_void_p]
+            lib.sat_multi_cluster_add.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
+            lib.sat_multi_cluster_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.sat_hits_cutoff.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         lib.sat_multi_search_cutoff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                                 C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
@@ -225,6 +237,8 @@ def host_lib():
         lib.sat_entry_cost.argtypes = [C.c_int]
         lib.sat_entry_cost.restype = C.c_double
         lib.sat_shard_cuts.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        lib.sat_cluster_join.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        lib.sat_cluster_reps.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _host = lib
     return _host
 

@@ -37,7 +37,9 @@
  * -Q dbfile (as -q dbfile, same stdout: the queries are entries of the database, which is resident on the GPUs, so each
  * batch is set from its entry indices and built there - sat_multi_queries_from_db - instead of being expanded on the host
  * and copied), -a dbfile (all-vs-all: every entry of the database is a query, in file order, set as -Q sets them; stdin
- * is not read; prints what -q dbfile prints for a stdin that lists every SID in file order).
+ * is not read; prints what -q dbfile prints for a stdin that lists every SID in file order), -L P (with -a dbfile: cluster
+ * the database - single linkage over the rows whose p-value is <= P, the graph kept on the GPUs, sat_cluster.h - and print
+ * one line per structure, "name representative cluster_size degree", under a "# CLUSTER ..." header instead of any rows).
  */
 #include <math.h>
 #include <stdarg.h>
@@ -50,6 +52,7 @@
 #include <unistd.h>
 
 #include "satabsearch.h"
+#include "sat_cluster.h"
 #include "sat_gumbel.h"
 #include "sat_host_search.h"
 #include "sat_parse.h"
@@ -74,11 +77,16 @@ static double now_ms(void)
 #pragma weak sat_multi_search_refine_polish
 #pragma weak sat_multi_polish_all_set
 #pragma weak sat_multi_queries_from_db
+#pragma weak sat_multi_search_only
+#pragma weak sat_multi_cluster_begin
+#pragma weak sat_multi_cluster_add
+#pragma weak sat_multi_cluster_labels
+#pragma weak sat_cluster_reps
 
 static void usage(const char *prog)
 {
     fprintf(stderr, "Usage: %s [-c] [-q dbfile | -Q dbfile | -a dbfile] [-r restarts] [-g gpus] [-G gpu,gpu,...] [-s seed]\n"
-                    "       [-k K] [-p P] [-m M] [-M M] [-R restarts [-C C]] [-F censor] [-P T] [-A] [-b]\n", prog);
+                    "       [-k K] [-p P] [-m M] [-M M] [-R restarts [-C C]] [-F censor] [-P T] [-A] [-L P] [-b]\n", prog);
     fprintf(stderr, "  -c : run on host CPU not GPU card\n");
     fprintf(stderr, "  -q dbfile : database is read from dbfile, list of query\n"
                     "              ids is read from stdin\n");
@@ -107,6 +115,9 @@ static void usage(const char *prog)
                     "         the polished scores and maps (GPU mode, needs -k)\n", SAT_MAX_MATCHES);
     fprintf(stderr, "  -A : with -P T: all rows - polish every row of the search instead of C candidates; the listing, -k, -p\n"
                     "       and -F then work on the polished scores and maps (not with -c, -m, -M, -R, -C)\n");
+    fprintf(stderr, "  -L P : with -a dbfile: cluster the database on the GPU - single linkage over the rows whose p-value\n"
+                    "         is <= P (0..1); prints one line per structure: name representative cluster_size degree\n"
+                    "         (not with -c, -k, -p, -m, -M, -R, -C)\n");
     fprintf(stderr, "  -b : cache the parsed database as dbfile.satbin\n");
     exit(1);
 }
@@ -254,6 +265,8 @@ typedef struct {
     int polish_all;                   /* -P T -A: maps polished per row of every search (then polish is 0) */
     double censor;                    /* -F: the right-censored fraction of the rows */
     double pmax;                      /* -p: the largest p-value printed */
+    int cluster;                      /* -L: cluster the database instead of printing rows */
+    double lmax;                      /* -L: the largest p-value of an edge */
     unsigned long long seed;
     const char *qfile;                /* -q, -Q, -a: the database; stdin lists the query SIDs (not with -a) */
     const char *from_db;              /* -Q, -a: the database again - the batches are set from entry indices on the GPUs */
@@ -376,7 +389,7 @@ static void parse_options(int argc, char *argv[], options *o)
 {
     *o = (options){ .use_gpu = 1, .maxstart = 128, .want_gpus = 1, .seed = SAT_DEFAULT_SEED };
     int c;
-    while ((c = getopt(argc, argv, "cq:Q:a:r:g:G:s:bk:p:m:M:R:C:F:P:A")) != -1) {
+    while ((c = getopt(argc, argv, "cq:Q:a:r:g:G:s:bk:p:m:M:R:C:F:P:AL:")) != -1) {
         char *end = NULL;
         long v;
         switch (c) {
@@ -402,6 +415,15 @@ static void parse_options(int argc, char *argv[], options *o)
                 usage(argv[0]);
             }
             o->cutoff = 1;
+            break;
+        case 'L':
+            /* the whole argument, a finite number in [0, 1] */
+            o->lmax = strtod(optarg, &end);
+            if (end == optarg || *end != '\0' || !isfinite(o->lmax) || o->lmax < 0.0 || o->lmax > 1.0) {
+                fprintf(stderr, "ERROR: -L needs a p-value in [0, 1] (got '%s')\n", optarg);
+                usage(argv[0]);
+            }
+            o->cluster = 1;
             break;
         case 'F':
             /* the whole argument, a number in [0, 0.5] */
@@ -449,6 +471,21 @@ static void parse_options(int argc, char *argv[], options *o)
             break;
         default: usage(argv[0]);
         }
+    }
+    if (o->cluster) {
+        /* clustering: an all-vs-all run whose rows stay on the GPUs */
+        if (!o->use_gpu) die("ERROR: -L cannot be combined with -c\n");
+        if (!o->all) die("ERROR: -L needs -a dbfile\n");
+        if (o->topk) die("ERROR: -L cannot be combined with -k\n");
+        if (o->cutoff) die("ERROR: -L cannot be combined with -p\n");
+        if (o->nmatch) die("ERROR: -L cannot be combined with -m\n");
+        if (o->rowmatch) die("ERROR: -L cannot be combined with -M\n");
+        if (o->refine) die("ERROR: -L cannot be combined with -R\n");
+        if (o->ncand) die("ERROR: -L cannot be combined with -C\n");
+        if (!sat_multi_search_only || !sat_multi_cluster_begin || !sat_multi_cluster_add || !sat_multi_cluster_labels ||
+            !sat_cluster_reps)
+            die("ERROR: this library has no sat_multi_cluster_add\n");
+        if (o->fit && !sat_multi_search_fit) die("ERROR: this library has no sat_multi_search_fit\n");
     }
     if (o->from_db || o->all) {
         /* queries from the resident database: from here on the run is a -q run over that file */
@@ -716,7 +753,7 @@ static void alloc_hits(gpu_bufs *B, size_t rows, int lsoln)
 static void alloc_gpu_bufs(const options *o, const input *in, gpu_bufs *B)
 {
     const int total = in->db.count, nm = o->nm, lsoln = in->lsoln;
-    const int entry_slots = !o->ranked || o->nmatch;     /* every entry's slots come to the host */
+    const int entry_slots = (!o->ranked && !o->cluster) || o->nmatch;     /* every entry's slots come to the host */
     *B = (gpu_bufs){ .batch = 256, .kk = o->topk < total ? o->topk : total };
     /* Queries go to the GPUs in batches: one set of launches scores a whole batch (grid = entries x queries), which
      * is what fills the machine when the database is small and the query list long (-q).  The batch size is bounded
@@ -735,7 +772,7 @@ static void alloc_gpu_bufs(const options *o, const input *in, gpu_bufs *B)
         alloc_slots(&B->all, rows, nm, o->nmatch, lsoln);
     if (o->nmatch)
         B->restarts = checked(malloc(sizeof(int32_t) * rows * nm));
-    if (!o->ranked && in->cls_count[1] > 0)
+    if (!o->ranked && !o->cluster && in->cls_count[1] > 0)
         alloc_slots(&B->large, (size_t)in->cls_count[1] * in->num_queries, nm, o->nmatch, lsoln);
     if (o->csr) {
         B->hits_cap = o->cutoff ? 1024 : B->kk * B->batch;
@@ -830,6 +867,12 @@ static int search_batch(const options *o, const input *in, sat_multi *multi, gpu
                         double *ms_stage2)
 {
     const int lorder = in->lorder, lsoln = in->lsoln, maxstart = o->maxstart;
+    if (o->cluster) {
+        /* -L: the rows stay on the GPUs (no gather, no LSOLN: no map is printed); with -F the fit is installed there */
+        if (o->fit)
+            return sat_multi_search_fit(multi, lorder, 0, maxstart, o->censor, fits, ms);
+        return sat_multi_search_only(multi, lorder, 0, maxstart, ms);
+    }
     if (o->fit && o->ranked) {
         /* search, histogram and fit on the GPUs (fits: the batch's), then the rows by the fitted p-values: those under
          * -p's cutoff, or with -k alone (every p-value is <= 1) the K best */
@@ -934,6 +977,44 @@ static void print_batch(const options *o, const input *in, gpu_bufs *B, const sa
     }
 }
 
+/* -L: the table of the clustering the GPUs hold - labels, degrees and the edge count cross to the host (8 bytes a
+ * structure and shard), the representatives and sizes are sat_cluster_reps' */
+static int print_clusters(const options *o, const input *in, sat_multi *multi, const sat_fit *fits)
+{
+    const int n = in->db.count;
+    int32_t *label = checked(malloc(sizeof(int32_t) * (size_t)n * 4)), *degree = label + n, *rep = degree + n, *size = rep + n;
+    unsigned long long edges = 0;
+    if (sat_multi_cluster_labels(multi, label, degree, &edges) != SAT_OK) {
+        fprintf(stderr, "clustering failed: %s\n", sat_last_error());
+        free(label);
+        return 1;
+    }
+    const int clusters = sat_cluster_reps(n, label, degree, rep, size);
+    if (clusters < 0)
+        die("ERROR: the GPUs returned labels that are no clustering\n");
+    int singletons = 0, fitted = 0;
+    for (int v = 0; v < n; v++)
+        singletons += size[v] == 1;
+    char line[SAT_MAX_LINE_LEN + 256];
+    int len = snprintf(line, sizeof line, "# CLUSTER dbfile = %s entries = %d pvalue <= %g restarts = %d clusters = %d singletons = %d "
+                       "edges = %llu\n", in->dbfile, n, o->lmax, o->maxstart, clusters, singletons, edges);
+    out_bytes(line, (size_t)len);
+    out_bytes(polish_header, strlen(polish_header));
+    if (fits) {
+        for (int v = 0; v < n; v++)
+            fitted += fits[v].fitted != 0;
+        len = snprintf(line, sizeof line, "# GUMBEL censor = %g fitted = %d of %d\n", o->censor, fitted, n);
+        out_bytes(line, (size_t)len);
+    }
+    for (int v = 0; v < n; v++) {
+        len = snprintf(line, sizeof line, "%-8s %-8s %d %d\n", sat_set_name(&in->db, v), sat_set_name(&in->db, rep[v]), size[v],
+                       degree[v]);
+        out_bytes(line, (size_t)len);
+    }
+    free(label);
+    return 0;
+}
+
 static int run_gpu(const options *o, const input *in)
 {
     sat_multi *multi = open_multi(o, in);
@@ -952,6 +1033,8 @@ static int run_gpu(const options *o, const input *in)
     /* -F: every query's fit - from the GPUs with -k / -p, else made here from the listing's scores (the whole
      * database's, both size classes: a query's two blocks carry the same line) */
     sat_fit *fits = o->fit ? checked(calloc((size_t)in->num_queries, sizeof(sat_fit))) : NULL;
+    if (o->cluster && sat_multi_cluster_begin(multi) != SAT_OK)
+        die("ERROR: %s\n", sat_last_error());
     for (int q0 = 0; q0 < in->num_queries; q0 += B.batch) {
         const int nqb = in->num_queries - q0 < B.batch ? in->num_queries - q0 : B.batch;
         for (int b = 0; b < nqb; b++) {
@@ -972,6 +1055,9 @@ static int run_gpu(const options *o, const input *in)
                             : sat_multi_queries_set(multi, nqb, B.n1s, B.qtabs, B.qdmats, SAT_MAXDIM, B.qtypes, (uint32_t)q0);
         if (rc == SAT_OK)
             rc = search_batch(o, in, multi, &B, fits ? fits + q0 : NULL, &ms, &ms_stage2);
+        /* -L: the batch's edges into the graph on the GPUs; query b is structure qindex[q0 + b] of the database */
+        if (rc == SAT_OK && o->cluster)
+            rc = sat_multi_cluster_add(multi, o->lmax, in->qindex + q0);
         if (rc < 0) {
             fprintf(stderr, "kernel launch failed: %s\n", sat_last_error());
             status = 1;
@@ -997,6 +1083,8 @@ static int run_gpu(const options *o, const input *in)
                     o->ncand < total ? o->ncand : total, o->refine);
         fprintf(stderr, "%f million iterations/sec\n",
                 ((double)total * nqb * ((double)o->maxstart * SAT_MAXITER) / (ms / 1000)) / 1.0e6);
+        if (o->cluster)
+            continue;
         if (o->fit && !o->ranked)
             for (int b = 0; b < nqb; b++)
                 fits[q0 + b] = fit_scores(B.all.scores + (size_t)b * total, total, B.n1s[b], in->db.order, o->censor);
@@ -1004,7 +1092,9 @@ static int run_gpu(const options *o, const input *in)
     }
     /* the listing's deferred block: every query's large-class rows, after all small-class blocks, with the reference
      * GPU path's two blanks before the p-value */
-    if (!status && !o->ranked && in->cls_count[1] > 0)
+    if (!status && o->cluster)
+        status = print_clusters(o, in, multi, fits);
+    if (!status && !o->ranked && !o->cluster && in->cls_count[1] > 0)
         for (int qi = 0; qi < in->num_queries; qi++) {
             print_header(in, qi, fits ? &fits[qi] : NULL);
             for (int d = 0; d < in->cls_count[1]; d++)

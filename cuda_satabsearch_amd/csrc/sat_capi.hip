@@ -350,12 +350,12 @@ sat_ctx *sat_ctx_create(int device, uint64_t seed)
         }
         const int rc_tab = build_metropolis_table(ctx);
         if (rc_tab != SAT_OK) return rc_tab;
-        // load the code objects of the upload, the SA kernels and the pair modes now (an empty launch of a small kernel, or
+        // load the code objects of the upload, the SA kernels, the pair modes and the clustering now (an empty launch of a small kernel, or
         // a question about one): the ~5 ms the first launch of a process pays for them belong to context creation, not
         // to the first upload or search
         int rc_load;
         if ((rc_load = sat_db_load_code(ctx)) != SAT_OK || (rc_load = sa_load_code()) != SAT_OK ||
-            (rc_load = sat_pairs_load_code(ctx)) != SAT_OK)
+            (rc_load = sat_pairs_load_code(ctx)) != SAT_OK || (rc_load = sat_cluster_load_code(ctx)) != SAT_OK)
             return rc_load;
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         return build_gumbel_tables(ctx);

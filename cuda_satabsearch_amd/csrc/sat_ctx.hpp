@@ -107,6 +107,7 @@ struct sat_ctx {
     DevBuf<uint8_t> d_tab;
     DevBuf<float> d_dist;
     DevBuf<uint32_t> d_ordinal;
+    uint32_t max_ordinal = 0;               // the largest of them (sat_cluster_begin sizes its nodes by it)
     DevBuf<int32_t> d_lists;                // entry indices grouped by bucket
     int bucket_begin[kNumBuckets + 1] = { 0 };
     int bucket_n2max[kNumBuckets] = { 0 };
@@ -207,6 +208,13 @@ struct sat_ctx {
     DevBuf<double> d_fit_tabs;
     DevBuf<uint32_t> d_hist;
 
+    // single-linkage clustering (sat_cluster_*, sat_cluster.hip): the accumulator over cluster_nodes nodes (0 = none) -
+    // the union-find's parent [nodes]; labels [nodes] (written by sat_cluster_labels) then degrees [nodes] in one array;
+    // the 64-bit edge counter; the batch's node of each query.  An upload drops it (free_db).
+    int cluster_nodes = 0;
+    DevBuf<int32_t> d_cl_parent, d_cl_out, d_cl_qnode;
+    DevBuf<unsigned long long> d_cl_edges;
+
     // bytes copied device -> host by this context's result calls (sat_stat_d2h_bytes)
     unsigned long long d2h_bytes = 0;
     // bytes copied host -> device by sat_queries_set / sat_queries_from_db (sat_stat_query_h2d_bytes)
@@ -220,6 +228,10 @@ struct sat_ctx {
 // grouped by size class - where the batch, the result buffers or `lsoln` changed; load the file's code object.
 int refresh_descriptors(sat_ctx *ctx, bool lsoln, hipStream_t stream);
 int sat_db_load_code(sat_ctx *ctx);
+
+// ---- sat_cluster.hip.  Load that file's code object (an empty launch of a small kernel); drop the accumulator.
+int sat_cluster_load_code(sat_ctx *ctx);
+void sat_cluster_drop(sat_ctx *ctx);
 
 // ---- sat_qfromdb.hip, for sat_multi_queries_from_db.  sat_queries_from_db on one shard's context, every check made by
 // the caller: query q has order n1s[q] and is entry code[q] >= 0 of this shard, or code[q] = -query_n1p(n1s[q]): a

@@ -2,6 +2,7 @@
 // the query batch (grouped and transposed into one blob), and the descriptors that point into both.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -32,6 +33,8 @@ void free_db(sat_ctx *ctx)
     ctx->d_tab.reset();
     ctx->d_dist.reset();
     ctx->d_ordinal.reset();
+    ctx->max_ordinal = 0;
+    sat_cluster_drop(ctx);                    // its nodes were this database's
     ctx->d_lists.reset();
     ctx->d_scores.reset();
     ctx->d_ssemaps.reset();
@@ -252,6 +255,7 @@ static int upload_impl(sat_ctx *ctx, int n_entries, const int32_t *orders,
 
     std::vector<uint32_t> ord(n_entries);
     for (int e = 0; e < n_entries; e++) ord[e] = db_ordinal ? (uint32_t)db_ordinal[e] : (uint32_t)e;
+    const uint32_t max_ordinal = *std::max_element(ord.begin(), ord.end());
 
     lap("host lists");
     DevBuf<int32_t> d_bad;
@@ -276,6 +280,7 @@ static int upload_impl(sat_ctx *ctx, int n_entries, const int32_t *orders,
         HIP_TRY(hipMemcpy(d_bad.get(), &none, sizeof none, hipMemcpyHostToDevice));
         lap("header copies");
         ctx->n_entries = n_entries;
+        ctx->max_ordinal = max_ordinal;
 
         // The two big arrays go up in slices from a few host threads (each slice a synchronous copy out
         // of the caller's pageable memory: the runtime stages it through its pinned buffers, and several

@@ -1,0 +1,61 @@
+// sat_hitrow.hpp - the row of one (query, entry) score and the qualifying predicate of the p-value cutoff: device code
+// shared by sat_topk.hip (best-k, sat_hits_cutoff) and sat_cluster.hip (sat_cluster_add), so that both read the same
+// double from the same table index.  Not part of the public interface.
+//
+// Everything here stays in an unnamed namespace, as it was in sat_topk.hip: HitQuery is a parameter type of that file's
+// kernels, so their symbols - and with them the file's device code - are what they were.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "satabsearch.h"
+#include "host/sat_gumbel.h"
+
+namespace {
+
+struct HitQuery {
+    int32_t n1;
+    int32_t fitted;            // 1: the query's rows take their statistics from `fit`
+    const int8_t *ssemaps;     // this query's [N][n1] maps, or null
+    const double *fit;         // fitted: z[SAT_STAT_BINS] then p[SAT_STAT_BINS] of the query (sat_stats_set), else null
+};
+
+// the row of (entry, score) for a query of n1 SSEs against an entry of n2.  fit = null: the built-in statistics, z and p
+// of norm2 truncated to an int; else the query's fitted tables at the row's histogram bin (a negative score: bin 0)
+__device__ __forceinline__ sat_hit hit_row(int32_t entry, int32_t score, int n1, int n2, const double *ztab, const double *ptab,
+                                           const double *fit)
+{
+    const double norm2 = 2.0 * score / ((double)(n1 + n2));            // sat_norm2
+    sat_hit h;
+    h.entry = entry;
+    h.score = score;
+    h.norm2 = norm2;
+    if (fit) {
+        const int bin = score < 0 ? 0 : sat_stat_bin_of(score, n1 + n2);
+        h.zscore = fit[bin];
+        h.pvalue = fit[SAT_STAT_BINS + bin];
+        return h;
+    }
+    int x = (int)norm2;                                                // the reference's double -> int
+    x = x < -128 ? -128 : (x > 127 ? 127 : x);                         // |norm2| <= 110 for every legal score
+    h.zscore = ztab[x + 128];
+    h.pvalue = ptab[x + 128];
+    return h;
+}
+
+// ---- p-value cutoff.  Blocks of 1024 rows, `bpq` blocks per query, so that a block holds rows of one query only.  A row
+// qualifies iff the p-value hit_row gives it is <= max_p: the same double, from the same table index.
+constexpr int kCutoffBlock = 1024, kCutoffWaves = kCutoffBlock / 64;
+
+__device__ __forceinline__ bool cutoff_row(const int32_t *scores, int n, int bpq, const int32_t *orders, const HitQuery *queries,
+                                           const double *ztab, const double *ptab, double max_p, int &q, int &e, int32_t &score)
+{
+    q = (int)(blockIdx.x / (unsigned)bpq);
+    e = (int)(blockIdx.x - (unsigned)q * bpq) * kCutoffBlock + (int)threadIdx.x;
+    if (e >= n) return false;
+    score = scores[(size_t)q * n + e];
+    return hit_row(e, score, queries[q].n1, orders[e], ztab, ptab, queries[q].fit).pvalue <= max_p;
+}
+
+}  // namespace

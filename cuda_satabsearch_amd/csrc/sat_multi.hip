@@ -36,6 +36,7 @@
 #include "sat_cutoff.hpp"
 #include "host/sat_gumbel.h"
 #include "host/sat_shard.h"
+#include "host/sat_cluster.h"
 
 namespace {
 
@@ -856,6 +857,68 @@ int sat_multi_search_fit(sat_multi *m, int lorder, int lsoln, int maxstart, doub
     if ((rc = sat_multi_stats_set(m, fit.data())) != SAT_OK) return bail(m, rc);
     if (fits) std::copy(fit.begin(), fit.end(), fits);
     if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return SAT_OK;
+}
+
+int sat_multi_search_only(sat_multi *m, int lorder, int lsoln, int maxstart, double *wall_ms)
+{
+    if (!m) return sat_fail(SAT_EINVAL, "null context");
+    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = each_shard(m, [&](int g) { return sat_search_async(m->ctx[(size_t)g], lorder, lsoln, maxstart); });
+    if (rc != SAT_OK) return rc;
+    // no gather: each shard's scores stay where they are (sat_sync also reports a polished row that did not finish)
+    rc = each_shard(m, [&](int g) { return sat_sync(m->ctx[(size_t)g]); });
+    if (rc != SAT_OK) return rc;
+    if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return SAT_OK;
+}
+
+int sat_multi_cluster_begin(sat_multi *m)
+{
+    if (!m) return sat_fail(SAT_EINVAL, "null context");
+    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
+    // every shard's nodes are the whole database's: its edges end at its own entries' ordinals, but start anywhere
+    for (int g = 0; g < m->ndev; g++) {
+        const int rc = sat_cluster_begin(m->ctx[(size_t)g], m->n_entries);
+        if (rc != SAT_OK) return rc;
+    }
+    return SAT_OK;
+}
+
+int sat_multi_cluster_add(sat_multi *m, double max_pvalue, const int32_t *query_node)
+{
+    if (!m) return sat_fail(SAT_EINVAL, "null context");
+    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
+    // the argument checks of sat_cluster_add, made for all shards before the first one adds anything
+    if (!query_node) return sat_fail(SAT_EINVAL, "query_node is null");
+    if (!std::isfinite(max_pvalue) || max_pvalue < 0.0) return sat_fail(SAT_EINVAL, "max_pvalue must be finite and >= 0");
+    const size_t nq = m->ctx[0]->queries.size();
+    for (size_t q = 0; q < nq; q++)
+        if (query_node[q] < 0 || query_node[q] >= m->n_entries)
+            return sat_fail(SAT_EINVAL, "query %zu: node %d outside 0..%d", q, query_node[q], m->n_entries - 1);
+    return each_shard(m, [&](int g) { return sat_cluster_add(m->ctx[(size_t)g], max_pvalue, query_node); });
+}
+
+int sat_multi_cluster_labels(sat_multi *m, int32_t *label, int32_t *degree, unsigned long long *edges)
+{
+    if (!m) return sat_fail(SAT_EINVAL, "null context");
+    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
+    if (!label) return sat_fail(SAT_EINVAL, "label buffer is null");
+    const size_t n = (size_t)m->n_entries, ndev = (size_t)m->ndev;
+    if (ndev == 1) return sat_cluster_labels(m->ctx[0], label, degree, edges);
+    std::vector<int32_t> labels(ndev * n), deg(degree ? n : 0);
+    if (degree) std::fill(degree, degree + n, 0);
+    if (edges) *edges = 0ull;
+    for (size_t g = 0; g < ndev; g++) {
+        unsigned long long e = 0ull;
+        const int rc = sat_cluster_labels(m->ctx[g], labels.data() + g * n, degree ? deg.data() : nullptr, edges ? &e : nullptr);
+        if (rc != SAT_OK) return rc;
+        for (size_t v = 0; degree && v < n; v++) degree[v] += deg[v];          // integer sums: any order
+        if (edges) *edges += e;
+    }
+    if (sat_cluster_join((int)n, (int)ndev, labels.data(), label) != 0)
+        return sat_fail(SAT_EDEVICE, "a shard returned a label outside 0..%d", m->n_entries - 1);
     return SAT_OK;
 }
 

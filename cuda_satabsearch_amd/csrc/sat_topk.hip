@@ -24,6 +24,7 @@
 
 #include "sat_pairs.hpp"
 #include "sat_cutoff.hpp"
+#include "sat_hitrow.hpp"               // HitQuery, hit_row, cutoff_row: shared with sat_cluster.hip
 #include "host/sat_gumbel.h"
 
 namespace {
@@ -38,36 +39,6 @@ __global__ void pack_keys(const int32_t *scores, long long total, int n, unsigne
         const uint32_t e = (uint32_t)(i % n);
         keys[i] = ((unsigned long long)(uint32_t)(scores[i] + 0x40000000) << 32) | (0xFFFFFFFFu - e);
     }
-}
-
-struct HitQuery {
-    int32_t n1;
-    int32_t fitted;            // 1: the query's rows take their statistics from `fit`
-    const int8_t *ssemaps;     // this query's [N][n1] maps, or null
-    const double *fit;         // fitted: z[SAT_STAT_BINS] then p[SAT_STAT_BINS] of the query (sat_stats_set), else null
-};
-
-// the row of (entry, score) for a query of n1 SSEs against an entry of n2.  fit = null: the built-in statistics, z and p
-// of norm2 truncated to an int; else the query's fitted tables at the row's histogram bin (a negative score: bin 0)
-__device__ __forceinline__ sat_hit hit_row(int32_t entry, int32_t score, int n1, int n2, const double *ztab, const double *ptab,
-                                           const double *fit)
-{
-    const double norm2 = 2.0 * score / ((double)(n1 + n2));            // sat_norm2
-    sat_hit h;
-    h.entry = entry;
-    h.score = score;
-    h.norm2 = norm2;
-    if (fit) {
-        const int bin = score < 0 ? 0 : sat_stat_bin_of(score, n1 + n2);
-        h.zscore = fit[bin];
-        h.pvalue = fit[SAT_STAT_BINS + bin];
-        return h;
-    }
-    int x = (int)norm2;                                                // the reference's double -> int
-    x = x < -128 ? -128 : (x > 127 ? 127 : x);                         // |norm2| <= 110 for every legal score
-    h.zscore = ztab[x + 128];
-    h.pvalue = ptab[x + 128];
-    return h;
 }
 
 // one thread per (query, rank): decode the key, look the statistics up, gather the map
@@ -219,19 +190,7 @@ int check_searched(sat_ctx *ctx)
 // one query only: each wave counts its qualifying rows with a ballot, the block sums its 16 waves' counts in LDS and
 // counts (or claims) them with ONE atomic.  (Every query's counter sits in a few cache lines: at P = 1 one atomic per
 // wave took 170 us of the q200 shape's flag pass)  A row qualifies iff the p-value hit_row gives it is
-// <= max_p: the same double, from the same table index.
-
-constexpr int kCutoffBlock = 1024, kCutoffWaves = kCutoffBlock / 64;
-
-__device__ __forceinline__ bool cutoff_row(const int32_t *scores, int n, int bpq, const int32_t *orders, const HitQuery *queries,
-                                           const double *ztab, const double *ptab, double max_p, int &q, int &e, int32_t &score)
-{
-    q = (int)(blockIdx.x / (unsigned)bpq);
-    e = (int)(blockIdx.x - (unsigned)q * bpq) * kCutoffBlock + (int)threadIdx.x;
-    if (e >= n) return false;
-    score = scores[(size_t)q * n + e];
-    return hit_row(e, score, queries[q].n1, orders[e], ztab, ptab, queries[q].fit).pvalue <= max_p;
-}
+// <= max_p: the same double, from the same table index (cutoff_row, sat_hitrow.hpp).
 
 // counts[q] += qualifying rows of query q
 __global__ void __launch_bounds__(kCutoffBlock) cutoff_count(const int32_t *scores, int n, int bpq, const int32_t *orders,
@@ -361,6 +320,18 @@ int cutoff_chunk(int n)
 }
 
 }  // namespace
+
+// sat_cutoff.hpp, for sat_cluster.hip: the searched-state check, the chunking and the HitQuery rows of the cutoff pass
+int sat_check_searched(sat_ctx *ctx) { return check_searched(ctx); }
+int sat_cutoff_chunk(int n) { return cutoff_chunk(n); }
+int sat_hitq_upload(sat_ctx *ctx)
+{
+    std::vector<HitQuery> hq_host;
+    const int rc = upload_hit_queries(ctx, 0, (int)ctx->queries.size(), false, hq_host);
+    if (rc != SAT_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));             // hq_host dies at return
+    return SAT_OK;
+}
 
 // The histogram of every query of the last search into ctx->d_hist (counts [nq][SAT_STAT_BINS], then below [nq]) and
 // from there to the host.  The query lists go in cutoff_chunk's chunks: fewer blocks per query here, so a chunk that

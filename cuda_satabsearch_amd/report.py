@@ -51,3 +51,33 @@ def result_lines(names, orders, scores, n1, ssemaps=None, wide_pvalue_gap=False)
                 if j >= 0:
                     out.append("%3d %3d" % (i + 1, j + 1))
     return out
+
+
+def cluster_join(label_sets):
+    """Join several labellings of the same nodes (int32[nsets, n], e.g. one per shard) into the canonical one:
+    out[v] = the smallest node of v's component (sat_cluster_join of csrc/host/sat_cluster.h)."""
+    import numpy as np
+    sets = np.ascontiguousarray(label_sets, dtype=np.int32)
+    if sets.ndim == 1:
+        sets = sets[None, :]
+    out = np.empty(sets.shape[1], np.int32)
+    if _native.host_lib().sat_cluster_join(sets.shape[1], sets.shape[0], sets.ctypes.data, out.ctypes.data) != 0:
+        raise ValueError("labels must lie in 0 .. n - 1 (and n, nsets >= 1)")
+    return out
+
+
+def cluster_table(labels, degrees):
+    """(reps int32[n], sizes int32[n]) of the canonical labelling Searcher.cluster_labels returns: reps[v] = the member
+    of v's cluster with the largest degree, ties to the smallest index; sizes[v] = the members of v's cluster
+    (sat_cluster_reps of csrc/host/sat_cluster.h, which the command line's -L prints from).  The cluster count is
+    len(set(labels))."""
+    import numpy as np
+    lab = np.ascontiguousarray(labels, dtype=np.int32).ravel()
+    deg = np.ascontiguousarray(degrees, dtype=np.int32).ravel()
+    if lab.shape != deg.shape:
+        raise ValueError("labels and degrees differ in length")
+    reps = np.empty(len(lab), np.int32)
+    sizes = np.empty(len(lab), np.int32)
+    if _native.host_lib().sat_cluster_reps(len(lab), lab.ctypes.data, deg.ctypes.data, reps.ctypes.data, sizes.ctypes.data) < 0:
+        raise ValueError("labels are not canonical: labels[v] must be the smallest node of v's cluster")
+    return reps, sizes

@@ -180,6 +180,23 @@ def _hits_cutoff(obj, nq, lsoln, first, again):
     return rows, (np.split(maps[:n], cuts) if lsoln else None)
 
 
+def _cluster_add(obj, fn, handle, max_pvalue, query_nodes):
+    """shared by Searcher / MultiSearcher.cluster_add"""
+    nodes = np.ascontiguousarray(query_nodes, dtype=np.int32).ravel()
+    if len(nodes) != getattr(obj, "n_queries", 1):
+        raise ValueError("one node per query of the batch is needed")
+    obj._check(fn(handle, float(max_pvalue), nodes.ctypes.data))
+
+
+def _cluster_labels(obj, fn, handle, n_nodes):
+    """shared by Searcher / MultiSearcher.cluster_labels: (labels int32[n], degrees int32[n], edges)"""
+    labels = np.zeros(n_nodes, np.int32)
+    degrees = np.zeros(n_nodes, np.int32)
+    edges = C.c_ulonglong(0)
+    obj._check(fn(handle, labels.ctypes.data, degrees.ctypes.data, C.byref(edges)))
+    return labels, degrees, int(edges.value)
+
+
 class Searcher:
     """One HIP device, one resident database shard, one current query."""
 
@@ -488,6 +505,34 @@ class Searcher:
         rec = _fit_records(fits, getattr(self, "n_queries", 1))
         self._check(self._lib.sat_stats_set(self._ctx, rec.ctypes.data))
 
+    # ---- clustering (sat_cluster_*) ------------------------------------------
+    def cluster_begin(self, n_nodes=None):
+        """Start (or restart, emptied) the single-linkage accumulator over n_nodes nodes - the structures of the whole
+        database in file order; default: the uploaded entries, right when this searcher holds the whole database with
+        the default ordinals."""
+        n = self.n_entries if n_nodes is None else int(n_nodes)
+        self._check(self._lib.sat_cluster_begin(self._ctx, n))
+        self._cluster_nodes = n
+
+    def cluster_add(self, max_pvalue, query_nodes):
+        """Add the rows of the last search whose p-value - as hits_cutoff tests it: an installed fit and polished rows
+        are followed - is <= max_pvalue as edges between query_nodes[q] and the entry's ordinal in the whole database
+        (sat_cluster_add); a structure against itself is no edge.  Nothing is copied back."""
+        _cluster_add(self, self._lib.sat_cluster_add, self._ctx, max_pvalue, query_nodes)
+
+    def cluster_labels(self):
+        """(labels int32[n_nodes]: the smallest node of each node's connected component; degrees int32[n_nodes]: edges
+        at each node, repeats counted; edges: their total) of what has been added so far (sat_cluster_labels); more
+        cluster_add calls may follow.  report.cluster_table turns them into representatives and sizes."""
+        if not getattr(self, "_cluster_nodes", 0):
+            self._check(self._lib.sat_cluster_labels(self._ctx, None, None, None))      # the library's state error
+        return _cluster_labels(self, self._lib.sat_cluster_labels, self._ctx, self._cluster_nodes)
+
+    def cluster_end(self):
+        """Free the accumulator (sat_cluster_end)."""
+        self._check(self._lib.sat_cluster_end(self._ctx))
+        self._cluster_nodes = 0
+
     def debug_set_scores(self, scores):
         """Test hook (satabsearch_debug.h): overwrite the last search's device scores with int32[nq, N]."""
         sc = np.ascontiguousarray(scores, dtype=np.int32)
@@ -680,6 +725,26 @@ class MultiSearcher:
         self._check(self._lib.sat_multi_search_fit(self._m, int(bool(lorder)), int(bool(lsoln)), int(maxstart), float(censor),
                                                    fits.ctypes.data, C.byref(ms)))
         return fits, ms.value
+
+    def search_only(self, lorder=True, lsoln=False, maxstart=DEFAULT_MAXSTART):
+        """Search every shard and wait; nothing is gathered or copied (sat_multi_search_only).  hits_cutoff,
+        score_histogram and cluster_add then work on it.  Returns wall_ms."""
+        ms = C.c_double(0.0)
+        self._check(self._lib.sat_multi_search_only(self._m, int(bool(lorder)), int(bool(lsoln)), int(maxstart), C.byref(ms)))
+        return ms.value
+
+    def cluster_begin(self):
+        """Searcher.cluster_begin on every shard, over the whole database's nodes (sat_multi_cluster_begin)."""
+        self._check(self._lib.sat_multi_cluster_begin(self._m))
+
+    def cluster_add(self, max_pvalue, query_nodes):
+        """Searcher.cluster_add on every shard: each adds the edges that end at its own entries."""
+        _cluster_add(self, self._lib.sat_multi_cluster_add, self._m, max_pvalue, query_nodes)
+
+    def cluster_labels(self):
+        """Searcher.cluster_labels of the whole database: the shards' labels joined, degrees and edges summed
+        (sat_multi_cluster_labels) - exactly what one searcher holding the whole database returns."""
+        return _cluster_labels(self, self._lib.sat_multi_cluster_labels, self._m, self.n_entries)
 
     def set_statistics(self, fits):
         """Searcher.set_statistics on every shard (sat_multi_stats_set)."""

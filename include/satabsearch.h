@@ -487,6 +487,43 @@ int sat_stats_fit(sat_ctx *ctx, double censor, sat_fit *fits);
  */
 int sat_stats_set(sat_ctx *ctx, const sat_fit *fits);
 
+/*
+ * ---- Single-linkage clustering of the database at a p-value, kept on the device.
+ * Nodes are the structures of the WHOLE database in file order, 0 .. n_nodes - 1.  After a search, row (q, e) QUALIFIES
+ * iff the p-value sat_hits_cutoff tests for it - the same double from the same table index, so a fit installed by
+ * sat_stats_fit / sat_stats_set and the polished rows of sat_polish_all_set are followed - is <= max_pvalue.  A qualifying
+ * row is an undirected EDGE between query_node[q] and the ordinal of entry e in the whole database (db_ordinal of the
+ * upload); a row whose two ends are one node (a structure against itself) is no edge and is counted nowhere.
+ *   label[v]   the smallest node of v's connected component: single linkage at the cutoff
+ *   degree[v]  the edges with v at either end; repeats count each time (a pair that qualifies in both directions gives 2
+ *              to each end)
+ *   edges      the edges added, 64 bits
+ * All three are integers and functions of the multiset of edges: nothing depends on the launch shape, the cut into
+ * batches, the order of the sat_cluster_add calls or the sharding.
+ *
+ * sat_cluster_begin   start (or restart, emptied) the context's accumulator over n_nodes nodes.  Needs a resident database
+ *                     (else SAT_ESTATE); n_nodes < 1 or a resident entry whose ordinal is >= n_nodes is SAT_EINVAL and
+ *                     leaves an earlier accumulator as it was.
+ * sat_cluster_add     add the qualifying rows of the last search (SAT_ESTATE before one, as sat_hits_cutoff, and without
+ *                     an accumulator); query_node[q] is the node of query q of the batch.  query_node == NULL, a node
+ *                     outside 0 .. n_nodes - 1 (the message names its position), a max_pvalue that is not finite or is
+ *                     negative: SAT_EINVAL, nothing added.  Copies 4 * n_queries bytes (and the queries' table
+ *                     pointers, as sat_hits_cutoff) to the device and NOTHING back: sat_stat_d2h_bytes does not move.  One
+ *                     pass over the n_queries x n_entries scores on the context's current stream, behind the search; the
+ *                     call does not wait for it.  Never searches, leaves the result buffers and an installed fit alone,
+ *                     and may be called again: another batch, another cutoff.
+ * sat_cluster_labels  wait, flatten the forest into labels (the accumulator stays as it is: more sat_cluster_add calls
+ *                     may follow) and copy label[n_nodes], degree[n_nodes] and *edges: exactly 8 * n_nodes + 8 bytes.
+ *                     degree and edges may be NULL: 4 * n_nodes, respectively 8, bytes fewer.  label == NULL is SAT_EINVAL.
+ * sat_cluster_end     free the accumulator.
+ * A database upload drops the accumulator (sat_cluster_add / sat_cluster_labels are then SAT_ESTATE until the next
+ * sat_cluster_begin); query changes and searches keep it.
+ */
+int sat_cluster_begin(sat_ctx *ctx, int n_nodes);
+int sat_cluster_add(sat_ctx *ctx, double max_pvalue, const int32_t *query_node);
+int sat_cluster_labels(sat_ctx *ctx, int32_t *label, int32_t *degree, unsigned long long *edges);
+int sat_cluster_end(sat_ctx *ctx);
+
 /* Bytes this context's result calls (sat_results, sat_search, sat_topk, sat_topk_hits, sat_hits_cutoff, the pair searches) have copied
  * from the device to the host since it was created (diagnostics: the best-k path moves O(k) rows). */
 unsigned long long sat_stat_d2h_bytes(const sat_ctx *ctx);
@@ -612,6 +649,19 @@ int sat_multi_search_fit(sat_multi *m, int lorder, int lsoln, int maxstart, doub
  * sat_multi_search_cutoff and sat_multi_search_fit then work on polished rows, exactly those of one context holding
  * the whole database; the refine calls' stage 1, the match and the pair searches stay plain. */
 int sat_multi_polish_all_set(sat_multi *m, int tops);
+/* sat_multi_search_only searches every shard and waits - no gather, no copy: sat_multi_search_fit without the fit.
+ * Afterwards sat_multi_hits_cutoff, sat_multi_score_histogram and sat_multi_cluster_add work on it.  wall_ms as
+ * sat_multi_search.
+ * The clustering over every shard, exactly what one context holding the whole database returns: every shard keeps an
+ * accumulator over the WHOLE database's nodes (sat_multi_cluster_begin: n_nodes = the database size; SAT_ESTATE without
+ * a database), into which sat_multi_cluster_add adds the edges that end at its own entries (query_node[q] a node of the
+ * whole database; rejections as sat_cluster_add, checked before any shard adds).  sat_multi_cluster_labels brings every
+ * shard's labels and degrees to the host (ndev * (8 * n_nodes + 8) bytes), joins the labels (sat_cluster_join of
+ * csrc/host/sat_cluster.h) and sums degrees and edges; degree and edges may be NULL. */
+int sat_multi_search_only(sat_multi *m, int lorder, int lsoln, int maxstart, double *wall_ms);
+int sat_multi_cluster_begin(sat_multi *m);
+int sat_multi_cluster_add(sat_multi *m, double max_pvalue, const int32_t *query_node);
+int sat_multi_cluster_labels(sat_multi *m, int32_t *label, int32_t *degree, unsigned long long *edges);
 unsigned long long sat_multi_stat_d2h_bytes(const sat_multi *m);
 
 /*
