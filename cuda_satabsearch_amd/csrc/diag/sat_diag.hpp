@@ -29,11 +29,13 @@
 #ifdef SAT_DIAG_DUP
 #if SAT_DIAG_DUP == 1
 // every db-cell gather a second time (volatile, result dropped): the LDS counters grow by exactly this site's share
-#define SAT_DIAG_DUP_CELLS(row, l0, l1, l2, l3) do { if constexpr (CELLS == SAT_CELLS_FULL8) {                                            \
+// (the 8-byte cells: quad_terms hands over the cells' byte offsets inside the row)
+#define SAT_DIAG_DUP_CELLS(row, o0, o1, o2, o3) do {                                                                     \
         typedef const volatile __attribute__((address_space(3))) unsigned long long *lds_vu64;                          \
-        const unsigned long long dup0 = *(lds_vu64)&(row).cells[l0], dup1 = *(lds_vu64)&(row).cells[l1],                  \
-                                 dup2 = *(lds_vu64)&(row).cells[l2], dup3 = *(lds_vu64)&(row).cells[l3];                  \
-        asm volatile("" : : "v"(dup0), "v"(dup1), "v"(dup2), "v"(dup3)); } } while (0)
+        const unsigned char *const dupb = reinterpret_cast<const unsigned char *>((row).cells);                         \
+        const unsigned long long dup0 = *(lds_vu64)(dupb + (o0)), dup1 = *(lds_vu64)(dupb + (o1)),                        \
+                                 dup2 = *(lds_vu64)(dupb + (o2)), dup3 = *(lds_vu64)(dupb + (o3));                        \
+        asm volatile("" : : "v"(dup0), "v"(dup1), "v"(dup2), "v"(dup3)); } while (0)
 #elif SAT_DIAG_DUP == 2
 #define SAT_DIAG_DUP_MAPWORD(p) (void)*(const volatile __attribute__((address_space(3))) uint32_t *)(p)
 #elif SAT_DIAG_DUP == 3
@@ -83,7 +85,7 @@ __device__ __forceinline__ void perturb(uint32_t (&d)[4])
 // i < k from the map bytes, nothing shared with the step's delta), and the byte restored.
 #define SAT_DIAG_SELFCHECK_STEP do {                                                                                     \
         const uint8_t keep_ = smap_b[map_byte_addr(ssei)];                                                               \
-        smap_b[map_byte_addr(ssei)] = (uint8_t)newj;                                                                     \
+        smap_b[map_byte_addr(ssei)] = newbyte;                                                                           \
         int chk_ = score_rows();                                                                                         \
         if (lpc >= 2) chk_ += __shfl_xor(chk_, 1, 64);                                                                   \
         if (lpc == 4) chk_ += __shfl_xor(chk_, 2, 64);                                                                   \

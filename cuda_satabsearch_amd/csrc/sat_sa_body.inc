@@ -55,6 +55,10 @@
     // ---- carve LDS: satk::lds_layout, the function the host sizes the workgroup with.  The cell layout
     // goes by the launch's size class, not by this entry's order (n2max > 32 <=> M2W > 1).
     constexpr bool SPLIT = CELLS != SAT_CELLS_FULL8;
+    // chain-map bytes as cell byte offsets with an "unmatched" flag (sat_sa_kernel.hpp: map_bytes_scaled); quad_terms
+    // goes by the cell layout alone, and the 8-byte cells are launched with one-word sets only
+    constexpr bool MAPOFF = map_bytes_scaled(M2W, CELLS);
+    static_assert(MAPOFF == (CELLS == SAT_CELLS_FULL8), "8-byte cells go with one-word db sets");
     const LdsLayout lay = lds_layout(M2W, CELLS, n2, cmp_words, N1P, T, nthreads, QLDS, opt_compact);
     uint2 *Dc = reinterpret_cast<uint2 *>(lds_slot);                          // !SPLIT: 8-byte cells
     float *distL = reinterpret_cast<float *>(lds_slot);                       // SPLIT: distances ...
@@ -235,9 +239,11 @@
     auto score_rows = [&]() -> int {
         int total = 0;
         for (int i = 0; i < n1 - 1; i++) {
-            // an unmatched SSE has no row in LDS: its lane walks row 0 and drops the sum
-            const int j = smap_b[map_byte_addr(i)];
-            const bool jreal = j != NULLJ;
+            // an unmatched SSE has no row in LDS: its lane walks row 0 and drops the sum (scaled bytes: the flag
+            // byte 0x04 decodes to row 0 by the shift alone)
+            const uint32_t jb = smap_b[map_byte_addr(i)];
+            const int j = MAPOFF ? (int)(jb >> 3) : (int)jb;
+            const bool jreal = MAPOFF ? (jb & SAT_MAP_UNMATCHED) == 0u : j != NULLJ;
             const DbRow<CELLS> drow = db_row(jreal ? j : 0);
             int rowsum = 0;
             auto row_group = [&](int kw) {
@@ -283,7 +289,7 @@
     const int tail2_lpi = (n1w + 1) >> 1;
     const int tail2_recip = (65536 + tail2_lpi - 1) / tail2_lpi;
     const int tail2_rows = 2 * tail2_lpi <= cmp_words ? (64 * tail2_recip) >> 16 : 0;
-    const uint32_t nullword = (uint32_t)NULLJ * 0x01010101u;     // a map word of unmatched SSEs
+    const uint32_t nullword = map_encode<MAPOFF>(NULLJ, NULLJ) * 0x01010101u;     // a map word of unmatched SSEs
     SAT_PHASE(7);                         // staging (and, in the restart loop, its own overhead)
     SAT_DIAG_PERTURB_INIT;
     // match mode: the output row of (query, entry), this slot's record slab, the restarts this chain runs (the
@@ -358,7 +364,7 @@
                             if (jj < 0) {
                                 stopped = true;              // K.cu:633-638: give up, no more draws used
                             } else {
-                                smap_b[map_byte_addr(i)] = (uint8_t)jj;
+                                smap_b[map_byte_addr(i)] = (uint8_t)(MAPOFF ? jj << 3 : jj);
                                 bits_set<M1W>(mapped, i);
                                 bits_set<M2W>(occ, jj);
                                 j = jj + 1;
@@ -402,6 +408,7 @@
             // SSE has the c-th occupied db SSE as its image: with a one-word db set the two bit sets are popped
             // in step and the map bytes are never read (with more words the byte read is cheaper than the pop)
             constexpr bool POP_IMAGES = M2W == 1;
+            static_assert(POP_IMAGES || !MAPOFF, "the walk's map-byte reads take plain indices");
             Bits<M1W> ri = mapped;
             Bits<M2W> rj = occ;
             // pops the lowest set bit: its position (0 when the set is empty) and whether there was one
@@ -603,9 +610,12 @@
                 int p;
                 bool none;
                 highest_mapped_upto(mapped, ssei, p, none);
-                const int A = smap_b[map_byte_addr(p)];
+                // (scaled bytes: with no mapped SSE at or below ssei the byte of SSE 0 is read, p is 0 and may equal
+                // ssei: the plain byte was the null SSE by itself there, the scaled one is the flag and shifts to 0, so
+                // `none` says "unmatched"; A is then not used: `empty`)
+                const int A = MAPOFF ? smap_b[map_byte_addr(p)] >> 3 : smap_b[map_byte_addr(p)];
                 SAT_DIAG_DUP_MAPBYTE(&smap_b[map_byte_addr(p)]);
-                oldj = p == ssei ? A : NULLJ;
+                oldj = (p == ssei && !(MAPOFF && none)) ? A : NULLJ;
                 const uint32_t above = 0xFFFFFFFEu << (A & 31);          // bits A+1 .. 31
                 const uint32_t y = occ.w[0] & above;                     // occupied above A
                 const uint32_t gap = (y - 1u) & ~y & above;              // free run up to the next occupied bit
@@ -658,7 +668,7 @@
                 cand.w[2 % M2W] = (uint32_t)c_hi;
                 cand.w[3 % M2W] = (uint32_t)(c_hi >> 32);
             } else {
-                oldj = smap_b[map_byte_addr(ssei)];
+                oldj = map_decode<MAPOFF>(smap_b[map_byte_addr(ssei)], NULLJ);
                 int startj = 0, endj = n2;
                 if (opt_lorder) {
                     Bits<M1W> upto = bits_below<M1W>(ssei + 1), lowpart, highpart;
@@ -669,8 +679,8 @@
                     }
                     const int p = bits_highest<M1W>(lowpart);
                     const int q = bits_lowest<M1W>(highpart);
-                    const int pimg = smap_b[map_byte_addr(p < 0 ? 0 : p)];
-                    const int qimg = smap_b[map_byte_addr(q < 0 ? 0 : q)];
+                    const int pimg = map_decode<MAPOFF>(smap_b[map_byte_addr(p < 0 ? 0 : p)], NULLJ);
+                    const int qimg = map_decode<MAPOFF>(smap_b[map_byte_addr(q < 0 ? 0 : q)], NULLJ);
                     startj = p < 0 ? n2 : pimg;                      // no mapped predecessor: empty window
                     endj = (ssei == n1 - 1) ? n2 : (q < 0 ? -1 : qimg);   // K.cu:1064-1077
                 }
@@ -734,6 +744,7 @@
             }
             const bool nreal = cnt != 0;
             const int newj = nreal ? sel : NULLJ;
+            const uint8_t newbyte = (uint8_t)(MAPOFF ? (nreal ? (uint32_t)sel << 3 : SAT_MAP_UNMATCHED) : (uint32_t)newj);   // its map byte
 
             SAT_PHASE(0);                 // draw + proposal
             // score change (deltasd, K.cu:502-535)
@@ -878,7 +889,7 @@
             if (lsoln && newscore > best) {
                 if (beats_leader(newscore, restart)) {
                     for (int w = 0; w < n1w; w++) bmap[w * T + tid] = smap[w * TP + tid];
-                    bmap_b[bmap_byte_addr(ssei)] = (uint8_t)newj;
+                    bmap_b[bmap_byte_addr(ssei)] = newbyte;
                 }
             }
             best = max(best, newscore);
@@ -891,7 +902,7 @@
                     if (nreal) bits_set<M2W>(rset, newj);
                     if (replay && part == 0) {
                         for (int w = 0; w < n1w; w++) bmap[w * T + tid] = smap[w * TP + tid];
-                        bmap_b[bmap_byte_addr(ssei)] = (uint8_t)newj;
+                        bmap_b[bmap_byte_addr(ssei)] = newbyte;
                     }
                 }
             }
@@ -911,7 +922,7 @@
             else
                 p = *(gptr_f32)((gptr_c)ptabG + (((uint32_t)rowoff + nd) << 2));
             const bool accept = p > u;
-            if (accept) smap_b[map_byte_addr(ssei)] = (uint8_t)newj;
+            if (accept) smap_b[map_byte_addr(ssei)] = newbyte;
             score = accept ? newscore : score;
             {
                 // an accepted move toggles the old image's bit (set) and the new image's bit (clear) of `occ`, and
@@ -963,7 +974,7 @@
             if (any && part == 0) {
                 int8_t *out = mx.maps + (mrow * mx.max_matches + tid) * (size_t)mx.map_pitch;
                 for (int i = 0; i < n1; i++) {
-                    const int j = bmap_b[bmap_byte_addr(i)];
+                    const int j = map_decode<MAPOFF>(bmap_b[bmap_byte_addr(i)], NULLJ);
                     out[i] = (int8_t)(j == NULLJ ? -1 : j);
                 }
             }
@@ -1000,7 +1011,7 @@
         ((((unsigned long long)(uint32_t)(best + 0x40000000)) << 32) | (0xFFFFFFFFu - best_restart)) == win) {
         int8_t *out = PAIRS ? px.maps + (size_t)pit.pair * SAT_K_MAXDIM : Q.ssemaps + (size_t)e * n1;
         for (int i = 0; i < n1; i++) {
-            int j = bmap_b[bmap_byte_addr(i)];
+            const int j = map_decode<MAPOFF>(bmap_b[bmap_byte_addr(i)], NULLJ);
             out[i] = (int8_t)(j == NULLJ ? -1 : j);
         }
     }

@@ -19,7 +19,9 @@
 //        pair scores 0 without any branch or predicate in the hot loop (the reference
 //        tests l >= 0, old_j >= 0, k != sse_i per pair, K.cu:521-531).  The null SSE is never the
 //        ROW of an evaluation: a null image contributes 0, the compacted rounds never list it, and the two
-//        loops that may meet one (full score, static loops) walk row 0 and drop the sum.
+//        loops that may meet one (full score, static loops) walk row 0 and drop the sum.  (Launches with 8-byte
+//        cells keep the column but no longer read it: their map bytes carry "unmatched" as a flag that switches
+//        the pair off in the selector, see map_bytes_scaled below.)
 //   Q    query, grouped by 4 consecutive query SSEs k (one "word" of the map) and
 //        TRANSPOSED: qdist[kw*N1P + i] = float4 of dmat1[i][4kw..4kw+3],
 //        qcode[kw*N1P + i] = the four code bytes tab1[i][4kw..4kw+3] packed in a dword.
@@ -32,7 +34,8 @@
 //        walks the matched pairs (i, k) of each chain and fetches one such cell per pair.
 //   qmask (LDS, launches with one-word db sets) per query SSE the db SSEs of its type,
 //        tmask[qtypes[i]]: one read on the path of every SA step instead of two dependent ones.
-//   smap (LDS) per-chain SSE map, one byte per query SSE, stored word-interleaved
+//   smap (LDS) per-chain SSE map, one byte per query SSE (the image's index, or with 8-byte cells its cell's
+//        byte offset in a row, l << 3, and 0x04 for "unmatched": map_bytes_scaled), stored word-interleaved
 //        smap[w*(T+1) + chain]: word w of every chain is contiguous, so a loop over a
 //        uniform word reads it conflict free; the odd row stride T+1 spreads the words of
 //        ONE chain over different banks for the compacted loop, where the lanes serving
@@ -116,7 +119,7 @@
 #define SAT_DIAG_FS_ROWS_ONLY 0
 #endif
 #ifndef SAT_DIAG_DUP_CELLS
-#define SAT_DIAG_DUP_CELLS(row, l0, l1, l2, l3)
+#define SAT_DIAG_DUP_CELLS(row, o0, o1, o2, o3)
 #endif
 #ifndef SAT_DIAG_DUP_MAPWORD
 #define SAT_DIAG_DUP_MAPWORD(p)
@@ -433,29 +436,80 @@ template <int CELLS> __device__ __forceinline__ uint2 db_cell(const DbRow<CELLS>
     else { const int c = tri_index(row.j, l); return uint2{ __float_as_uint(row.dist[c]), row.code[c] }; }
 }
 
+// Chain-map bytes of the FULL8 launches (entries of up to 32 SSEs, one-word db sets) hold the BYTE OFFSET of the
+// image's cell inside a row of the cell matrix, l << 3 for the images l = 0..31, and 0x04 for "unmatched": the address
+// of a pair's cell is then row base + one byte of the map word, a single v_add_u32_sdwa per pair where the plain
+// index took a byte extract and a shift-add, the row pitch (8 (n2 + 1) bytes) needs no power of two, and the
+// unmatched flag sits where the selector of quad_terms has its "scores 0" bit.  An unmatched byte addresses cell 0 of
+// the row (a real cell, in the bank of the sentinel column of a 32-SSE entry) and the flag drops the term.  Only the
+// kernel sees the encoding: its outputs, the items of the compaction tables and every other layout keep plain indices
+// with the null SSE n2 for "unmatched".
+#define SAT_MAP_UNMATCHED 0x04u
+__host__ __device__ constexpr bool map_bytes_scaled(int m2w, int cells) { return cells == SAT_CELLS_FULL8 && m2w == 1; }
+template <bool SCALED> __device__ __forceinline__ uint32_t map_encode(int j, int nullj)
+{
+    if constexpr (SCALED) return j == nullj ? SAT_MAP_UNMATCHED : (uint32_t)j << 3;
+    else return (uint32_t)j;
+}
+template <bool SCALED> __device__ __forceinline__ int map_decode(uint32_t b, int nullj)
+{
+    if constexpr (SCALED) return (b & SAT_MAP_UNMATCHED) ? nullj : (int)(b >> 3);
+    else return (int)b;
+}
+
 template <int CELLS>
 __device__ __forceinline__ int quad_terms(const float4 qd, const uint32_t qc, const DbRow<CELLS> row,
                                           const uint32_t word, const uint32_t force, const int acc)
 {
-    const uint32_t l0 = word & 0xFFu, l1 = (word >> 8) & 0xFFu, l2 = (word >> 16) & 0xFFu, l3 = word >> 24;
-    SAT_DIAG_DUP_CELLS(row, l0, l1, l2, l3);
-    const uint2 d0 = db_cell<CELLS>(row, (int)l0), d1 = db_cell<CELLS>(row, (int)l1), d2 = db_cell<CELLS>(row, (int)l2),
-                d3 = db_cell<CELLS>(row, (int)l3);
+    uint2 d0, d1, d2, d3;
+    if constexpr (CELLS == SAT_CELLS_FULL8) {
+        // scaled map bytes (map_bytes_scaled): cell address = row base + byte s of the word without its flag bits.  The
+        // masked word is formed once and kept opaque, so that each byte extract stays next to its add and the two
+        // become one v_add_u32_sdwa (left to itself the compiler masks every byte on its own again)
+        uint32_t offs = word & 0xF8F8F8F8u;
+        asm("" : "+v"(offs));
+        const uint32_t o0 = offs & 0xFFu, o1 = (offs >> 8) & 0xFFu, o2 = (offs >> 16) & 0xFFu, o3 = offs >> 24;
+        SAT_DIAG_DUP_CELLS(row, o0, o1, o2, o3);
+        const unsigned char *const base = reinterpret_cast<const unsigned char *>(row.cells);
+        d0 = *reinterpret_cast<const uint2 *>(base + o0);
+        d1 = *reinterpret_cast<const uint2 *>(base + o1);
+        d2 = *reinterpret_cast<const uint2 *>(base + o2);
+        d3 = *reinterpret_cast<const uint2 *>(base + o3);
+    } else {
+        const uint32_t l0 = word & 0xFFu, l1 = (word >> 8) & 0xFFu, l2 = (word >> 16) & 0xFFu, l3 = word >> 24;
+        d0 = db_cell<CELLS>(row, (int)l0);
+        d1 = db_cell<CELLS>(row, (int)l1);
+        d2 = db_cell<CELLS>(row, (int)l2);
+        d3 = db_cell<CELLS>(row, (int)l3);
+    }
     // sign bit of t = "distances differ by more than 4 A"
     const float t0 = 4.0f - fabsf(qd.x - __uint_as_float(d0.x));
     const float t1 = 4.0f - fabsf(qd.y - __uint_as_float(d1.x));
     const float t2 = 4.0f - fabsf(qd.z - __uint_as_float(d2.x));
     const float t3 = 4.0f - fabsf(qd.w - __uint_as_float(d3.x));
     // v_perm_b32(S0, S1, sel): selector 0-3 = byte of S1, 4-7 = byte of S0, 0x0C = zero
-    const uint32_t far = __builtin_amdgcn_perm(__float_as_uint(t1), __float_as_uint(t0), 0x0C0C0703u) |
-                         __builtin_amdgcn_perm(__float_as_uint(t3), __float_as_uint(t2), 0x07030C0Cu);
     const uint32_t x = __builtin_amdgcn_perm(d1.y, d0.y, 0x0C0C0400u) ^
                        __builtin_amdgcn_perm(d3.y, d2.y, 0x04000C0Cu) ^ qc;
     const uint32_t z = (x + 0x77777777u) & 0x88888888u;             // bit 3: low nibbles differ, bit 7: high
-    // ((z >> 3) | (z >> 6)) & 0x03030303 and the merge of the distance bits as two v_bitop3_b32 (full
-    // rate; the and-or / or3 forms the compiler picks for the plain expression issue at half rate)
-    uint32_t sel = __builtin_amdgcn_bitop3_b32(z >> 3, z >> 6, 0x03030303u, 0xA8);        // (a | b) & c
-    sel = __builtin_amdgcn_bitop3_b32(far >> 5, 0x04040404u, sel, 0xEA);                   // (a & b) | c
+    uint32_t sel;
+    if constexpr (CELLS == SAT_CELLS_FULL8) {
+        // selectors 0x09 / 0x0B give 0xFF or 0x00 by the SIGN of S1 / S0: the "too far" bytes come out clean, without
+        // the shift that moved bit 7 to bit 2.  z >> 3 and z >> 6 hold bits 0, 1, 4 and 5 of a byte and a map byte
+        // bits 2 (unmatched) and 3-7 (offset), so ONE or-or joins the code bits with the unmatched flag, and the
+        // and-or that merged the distance bit now also strips everything above bit 2: an unmatched SSE costs no
+        // instruction of its own.
+        const uint32_t far = __builtin_amdgcn_perm(__float_as_uint(t1), __float_as_uint(t0), 0x0C0C0B09u) |
+                             __builtin_amdgcn_perm(__float_as_uint(t3), __float_as_uint(t2), 0x0B090C0Cu);
+        sel = __builtin_amdgcn_bitop3_b32(z >> 3, z >> 6, word, 0xFE);                        // a | b | c
+        sel = __builtin_amdgcn_bitop3_b32(sel, far, 0x07070707u, 0xA8);                       // (a | b) & c
+    } else {
+        const uint32_t far = __builtin_amdgcn_perm(__float_as_uint(t1), __float_as_uint(t0), 0x0C0C0703u) |
+                             __builtin_amdgcn_perm(__float_as_uint(t3), __float_as_uint(t2), 0x07030C0Cu);
+        // ((z >> 3) | (z >> 6)) & 0x03030303 and the merge of the distance bits as two v_bitop3_b32 (full
+        // rate; the and-or / or3 forms the compiler picks for the plain expression issue at half rate)
+        sel = __builtin_amdgcn_bitop3_b32(z >> 3, z >> 6, 0x03030303u, 0xA8);        // (a | b) & c
+        sel = __builtin_amdgcn_bitop3_b32(far >> 5, 0x04040404u, sel, 0xEA);          // (a & b) | c
+    }
     sel |= force;
     const uint32_t terms = __builtin_amdgcn_perm(0u, 0xFE010102u, sel);   // {2, 1, 1, -2 | 0, 0, 0, 0}
     return __builtin_amdgcn_sdot4((int)terms, 0x01010101, acc, false);
