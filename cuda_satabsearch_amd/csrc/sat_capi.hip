@@ -339,6 +339,8 @@ sat_ctx *sat_ctx_create(int device, uint64_t seed)
         ctx->tune.polish_group = env_int("SAT_EXP_POLISH_GROUP", 0);
         const int scratch_kb = env_int("SAT_EXP_SCRATCH_KB", 0);
         if (scratch_kb > 0) ctx->tune.scratch_bytes = (size_t)scratch_kb << 10;
+        const int select_keys = env_int("SAT_EXP_SELECT_KEYS", 0);
+        if (select_keys > 0) ctx->tune.select_keys = select_keys;
         const int pad = env_int("SAT_EXP_LDS_PAD", 0);
         ctx->sa.lds_pad = pad > 0 ? (size_t)pad : 0;
         if (ctx->tune.streams != 0) {

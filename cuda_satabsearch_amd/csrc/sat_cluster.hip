@@ -182,7 +182,7 @@ int sat_cluster_add(sat_ctx *ctx, double max_pvalue, const int32_t *query_node)
         if (query_node[q] < 0 || query_node[q] >= nodes)
             return sat_fail(SAT_EINVAL, "query %d: node %d outside 0..%d", q, query_node[q], nodes - 1);
     if (ctx->max_ordinal >= (uint32_t)nodes) return sat_fail(SAT_ESTATE, "the accumulator does not cover the resident database");
-    const int per_chunk = sat_cutoff_chunk(n);
+    const int per_chunk = sat_cutoff_chunk(ctx, n);
     const int bpq = (n + kCutoffBlock - 1) / kCutoffBlock;
     HIP_TRY(hipSetDevice(ctx->device));
     if ((rc = ctx->d_cl_qnode.grow_after(ctx->stream, (size_t)nq)) != SAT_OK) return rc;

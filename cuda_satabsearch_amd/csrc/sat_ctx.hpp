@@ -136,9 +136,11 @@ struct sat_ctx {
 
     // overrides (SAT_EXP_* in satabsearch_debug.h), read ONCE when the context is created: these of the search plan,
     // the upload and the pair split, the launch heuristics' in `sa`.  scratch_bytes: what the scratch in d_bmap_slabs may
-    // take before a search is cut into several launches (every cut keeps at least one slab)
+    // take before a search is cut into several launches (every cut keeps at least one slab).  select_keys: the (query,
+    // entry) keys a chunk of a selection pass may hold (select_all_hits, cutoff_chunk in sat_topk.hip)
     struct Tuning { int streams = -1, upload_threads = 0, upload_timing = 0, upload_pieces = 0, refine_split = 0, polish_group = 0;
-                    size_t scratch_bytes = (size_t)1 << 30; } tune;
+                    size_t scratch_bytes = (size_t)1 << 30;
+                    long long select_keys = 0x7FFFFFFFll; } tune;
     // what sat_launch.hip keeps per context: its overrides, the instantiations whose dynamic-LDS limit has been raised
     // on this device, the entries per workgroup chosen so far
     SaLaunchState sa;

@@ -20,7 +20,7 @@ int sat_cutoff_rows(sat_ctx *ctx, double max_pvalue, int max_rows, const int32_t
 // sat_hits_cutoff's state check: SAT_ESTATE unless a search has run since the last upload / query change.
 int sat_check_searched(sat_ctx *ctx);
 // queries per launch of a kernel shaped like the cutoff kernels (blocks of 1024 rows, whole blocks per query)
-int sat_cutoff_chunk(int n);
+int sat_cutoff_chunk(const sat_ctx *ctx, int n);
 // The HitQuery rows (sat_hitrow.hpp) of every query of the searched state into ctx->d_hitq, without maps, as
 // sat_cutoff_count leaves them: an installed fit is followed.  Waits for the context's stream.
 int sat_hitq_upload(sat_ctx *ctx);

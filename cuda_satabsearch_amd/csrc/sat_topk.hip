@@ -132,11 +132,11 @@ int select_hits(sat_ctx *ctx, int q0, int nq, int k, bool want_maps, size_t out_
 }
 
 // every query of the last search ranked: its best k rows at row q * k of ctx->d_hits (and ctx->d_hit_maps).  One
-// segmented sort handles up to 2^31 - 1 keys: long query lists over large databases go in chunks.
+// segmented sort handles up to 2^31 - 1 keys (ctx->tune.select_keys): long query lists over large databases go in chunks.
 int select_all_hits(sat_ctx *ctx, int k, bool want_maps)
 {
     const int nq = (int)ctx->queries.size(), n = ctx->n_entries;
-    const int per_chunk = (int)(0x7FFFFFFFll / n) < 1 ? 1 : (int)(0x7FFFFFFFll / n);
+    const int per_chunk = (int)(ctx->tune.select_keys / n) < 1 ? 1 : (int)(ctx->tune.select_keys / n);
     for (int q0 = 0; q0 < nq; q0 += per_chunk) {
         const int nqc = nq - q0 < per_chunk ? nq - q0 : per_chunk;
         const int rc = select_hits(ctx, q0, nqc, k, want_maps, (size_t)q0 * k, (size_t)nq * k);
@@ -310,12 +310,13 @@ __global__ void __launch_bounds__(kHistBlock) score_histogram(const int32_t *sco
     }
 }
 
-// queries per chunk: under 2^31 keys per sort (as sat_topk_hits) and under 2^31 threads per launch
-int cutoff_chunk(int n)
+// queries per chunk: under 2^31 keys per sort (as sat_topk_hits) and under 2^31 threads per launch - or under
+// ctx->tune.select_keys of either
+int cutoff_chunk(const sat_ctx *ctx, int n)
 {
-    const long long bpq = (n + kCutoffBlock - 1) / kCutoffBlock;
-    long long per = 0x7FFFFFFFll / n;
-    if (0x7FFFFFFFll / (bpq * kCutoffBlock) < per) per = 0x7FFFFFFFll / (bpq * kCutoffBlock);
+    const long long bpq = (n + kCutoffBlock - 1) / kCutoffBlock, keys = ctx->tune.select_keys;
+    long long per = keys / n;
+    if (keys / (bpq * kCutoffBlock) < per) per = keys / (bpq * kCutoffBlock);
     return per < 1 ? 1 : (int)per;
 }
 
@@ -323,7 +324,7 @@ int cutoff_chunk(int n)
 
 // sat_cutoff.hpp, for sat_cluster.hip: the searched-state check, the chunking and the HitQuery rows of the cutoff pass
 int sat_check_searched(sat_ctx *ctx) { return check_searched(ctx); }
-int sat_cutoff_chunk(int n) { return cutoff_chunk(n); }
+int sat_cutoff_chunk(const sat_ctx *ctx, int n) { return cutoff_chunk(ctx, n); }
 int sat_hitq_upload(sat_ctx *ctx)
 {
     std::vector<HitQuery> hq_host;
@@ -343,7 +344,7 @@ extern "C" int sat_score_histogram(sat_ctx *ctx, uint32_t *counts, int32_t *belo
     if (!counts || !below) return sat_fail(SAT_EINVAL, "histogram buffer is null");
     const int n = ctx->n_entries, nq = (int)ctx->queries.size();
     if (n > 0x7FFFFFFF - kHistRows) return sat_fail(SAT_EINVAL, "too many entries for the histogram pass");
-    const int per_chunk = cutoff_chunk(n);
+    const int per_chunk = cutoff_chunk(ctx, n);
     const int bpq = (n + kHistRows - 1) / kHistRows;
     const size_t words = (size_t)nq * (SAT_STAT_BINS + 1);
     HIP_TRY(hipSetDevice(ctx->device));
@@ -585,7 +586,7 @@ int sat_cutoff_count(sat_ctx *ctx, double max_pvalue, bool maps, int32_t *counts
     if (rc != SAT_OK) return rc;
     if (maps && !ctx->searched_lsoln) return sat_fail(SAT_ESTATE, "the last search ran without lsoln");
     const int n = ctx->n_entries, nq = (int)ctx->queries.size();
-    const int per_chunk = cutoff_chunk(n), pc = per_chunk < nq ? per_chunk : nq;
+    const int per_chunk = cutoff_chunk(ctx, n), pc = per_chunk < nq ? per_chunk : nq;
     const int bpq = (n + kCutoffBlock - 1) / kCutoffBlock;
     HIP_TRY(hipSetDevice(ctx->device));
     if ((rc = ctx->d_seg.grow((size_t)nq + 3 * (size_t)pc + 2)) != SAT_OK) return rc;
@@ -610,7 +611,7 @@ int sat_cutoff_count(sat_ctx *ctx, double max_pvalue, bool maps, int32_t *counts
 int sat_cutoff_rows(sat_ctx *ctx, double max_pvalue, int max_rows, const int32_t *counts, sat_hit *hits, int32_t *ssemaps)
 {
     const int n = ctx->n_entries, nq = (int)ctx->queries.size();
-    const int per_chunk = cutoff_chunk(n);
+    const int per_chunk = cutoff_chunk(ctx, n);
     const int bpq = (n + kCutoffBlock - 1) / kCutoffBlock;
     const bool maps = ssemaps != nullptr;
     size_t rows_total = 0, keys_max = 0;

@@ -21,7 +21,11 @@
  *   SAT_EXP_SCRATCH_KB = n       scratch a search may take before it is cut into several launches, in KiB (default 0: 1 GiB; the
  *                                LSOLN best-map slabs of a plain or match search, the record slabs of a pair-match / polish
  *                                list, the map pass of the pair modes at most 256 MiB of it).  Every cut keeps one slab at least
- *   SAT_EXP_STREAMS = 0          queue the order buckets of a search one after the other instead of concurrently
+ *   SAT_EXP_SELECT_KEYS = n      the most (query, entry) keys a chunk of a selection pass may hold (default 0: 2^31 - 1): best-k
+ *                                (sat_topk_hits, stage 1 of the refine calls) cuts its query list into chunks of n / entries
+ *                                queries, the p-value cutoff, the score histogram and sat_cluster_add into chunks of
+ *                                n / (entries rounded up to whole blocks of 1024).  A chunk always holds one query at least
+ *   SAT_EXP_STREAMS = 0           queue the order buckets of a search one after the other instead of concurrently
  *   SAT_EXP_UPLOAD_THREADS = n   host threads slicing the database copy (default 4)
  *   SAT_EXP_UPLOAD_TIMING = 1    per-phase upload times on stderr
  *   SAT_EXP_UPLOAD_PIECES = n    pieces of the overlapped upload + search (default by size, at most 8)

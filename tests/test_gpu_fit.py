@@ -4,7 +4,6 @@ fit, three shards on one GPU, and the command line's -F with -k / -p / -M - all 
 
 2 500 entries are no multiple of a histogram block's or a cutoff block's rows, and the queries of 8, 19 and 101 SSEs
 lie in three size classes."""
-import ctypes as C
 import os
 import re
 import subprocess
@@ -14,7 +13,8 @@ import pytest
 
 import cuda_satabsearch_amd as sat
 from cuda_satabsearch_amd import _native
-from cuda_satabsearch_amd.search import _FIT_DTYPE, _HIT_DTYPE
+from cuda_satabsearch_amd.search import _HIT_DTYPE
+from select_lib import expected_rows, fit_table, host_fits, host_histogram
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,60 +23,6 @@ BINS, PER_UNIT, MAXDIM = 4096, 256, 111
 GUMBEL_A, GUMBEL_B = 0.3780327676087335, 0.3582596175507505
 N1S = (8, 19, 101)
 R = 8
-
-
-def host():
-    return _native.host_lib()
-
-
-def host_histogram(scores, n1s, orders):
-    counts = np.zeros((len(n1s), BINS), np.uint32)
-    below = np.zeros(len(n1s), np.int32)
-    orders = np.ascontiguousarray(orders, np.int32)
-    for q, n1 in enumerate(n1s):
-        row = np.ascontiguousarray(scores[q], np.int32)
-        b = C.c_int32(0)
-        host().sat_stat_histogram(row.ctypes.data, len(row), int(n1), orders.ctypes.data, counts[q].ctypes.data, C.byref(b))
-        below[q] = b.value
-    return counts, below
-
-
-def host_fits(counts, below, censor):
-    fits = np.zeros(len(counts), _FIT_DTYPE)
-    for q in range(len(counts)):
-        f = _native.Fit()
-        assert host().sat_gumbel_fit_binned(counts[q].ctypes.data, float(censor), C.byref(f)) == 0
-        fits[q] = (f.a, f.b, f.rows, f.censored, below[q], f.fitted)
-    return fits
-
-
-def fit_table(a, b):
-    z, p = np.empty(BINS), np.empty(BINS)
-    host().sat_gumbel_fit_table(float(a), float(b), z.ctypes.data, p.ctypes.data)
-    return z, p
-
-
-def expected_rows(scores, n1s, orders, fits):
-    """every query's rows in sat_topk_hits order with the statistics the host gives them: the fitted table at the
-    row's bin for a query with a fit, else the built-in int-truncated ones"""
-    out = []
-    for q, n1 in enumerate(n1s):
-        order = np.argsort(-scores[q].astype(np.int64), kind="stable")
-        rows = np.zeros(len(order), _HIT_DTYPE)
-        rows["entry"], rows["score"] = order, scores[q][order]
-        tot = n1 + orders[order].astype(np.int64)
-        rows["norm2"] = 2.0 * rows["score"] / tot.astype(np.float64)
-        if fits is not None and fits[q]["fitted"]:
-            z, p = fit_table(fits[q]["a"], fits[q]["b"])
-            s = rows["score"].astype(np.int64)
-            k = np.where(s < 0, 0, np.minimum((512 * np.maximum(s, 0)) // tot, BINS - 1))
-            rows["zscore"], rows["pvalue"] = z[k], p[k]
-        else:
-            for i, n2 in enumerate(rows["norm2"]):
-                rows["zscore"][i] = host().sat_z_gumbel_trunc(float(n2))
-                rows["pvalue"][i] = host().sat_pv_gumbel(float(rows["zscore"][i]))
-        out.append(rows)
-    return out
 
 
 @pytest.fixture(scope="module")
