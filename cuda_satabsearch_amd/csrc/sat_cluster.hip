@@ -5,7 +5,8 @@
 // predicate of sat_hits_cutoff - and the two differ.  cluster_add walks the rows as cutoff_count does and keeps the graph
 // as a lock-free union-find (parent) plus a degree per node and one edge counter; cluster_labels turns the forest into
 // label[v] = the smallest node of v's component.  Everything is integers and the labels are a property of the edge SET,
-// so nothing depends on the launch shape, the batches, the order of the calls or the sharding.
+// so nothing depends on the launch shape, the batches, the order of the calls or the sharding.  The host side takes the
+// searched-state check, the chunk walk, the queries' HitQuery rows and the counted copies from sat_cutoff.hpp.
 //
 // The union-find links by index - the larger root goes under the smaller - and keeps, at every moment:
 //   (1) parent[v] <= v;                     (3) parent[v] is a node of v's tree, so of v's component of the edges so far;
@@ -19,9 +20,6 @@
 // which acts on the word itself, and on failure the walk goes on from the value the CAS returned - no loop re-reads a
 // word until it changes.  Termination: find descends strictly, and every retry of unite replaces hi by a smaller node.
 #include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <vector>
 
 #include "sat_ctx.hpp"
 #include "sat_cutoff.hpp"
@@ -68,7 +66,7 @@ __device__ __forceinline__ void unite(int32_t *parent, int32_t a, int32_t b)
 }
 
 // One thread per row, the grid of cutoff_count: a qualifying row that is no self row adds 1 to the degree of its entry's
-// node and joins the two ends; the block's edges go through ballot + LDS into ONE 64-bit atomic on the edge counter (one
+// node and joins the two ends; the block's edges go through block_count into ONE 64-bit atomic on the edge counter (one
 // word for the whole grid: one atomic per wave is DESIGN 6d's 170 us) and ONE atomic on the degree of the query's node -
 // a block holds rows of one query only, so its edge count is what that node's degree gains.
 __global__ void __launch_bounds__(kCutoffBlock) cluster_add(const int32_t *scores, int n, int bpq, const int32_t *orders,
@@ -87,18 +85,10 @@ __global__ void __launch_bounds__(kCutoffBlock) cluster_add(const int32_t *score
             unite(parent, a, b);
         }
     }
-    __shared__ int32_t wave_count[kCutoffWaves];
-    const unsigned long long mask = __ballot(edge);
-    if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = (int32_t)__popcll(mask);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int32_t c = 0;
-        for (int w = 0; w < kCutoffWaves; w++) c += wave_count[w];
-        if (c) {
-            atomicAdd(edges, (unsigned long long)c);
-            atomicAdd(degree + query_node[q], c);
-        }
-    }
+    block_count(edge, [&](int32_t c) {
+        atomicAdd(edges, (unsigned long long)c);
+        atomicAdd(degree + query_node[q], c);
+    });
 }
 
 // parent[v] = v, degree[v] = 0 for v < nodes; the edge counter 0
@@ -121,7 +111,7 @@ __global__ void cluster_labels(int nodes, const int32_t *parent, int32_t *label)
 
 int check_accumulator(const sat_ctx *ctx)
 {
-    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
+    SAT_TRY(sat_check_context(ctx));
     if (ctx->cluster_nodes <= 0)
         return sat_fail(SAT_ESTATE, "no cluster accumulator (sat_cluster_begin has not been called since the last database upload)");
     return SAT_OK;
@@ -150,18 +140,17 @@ extern "C" {
 
 int sat_cluster_begin(sat_ctx *ctx, int n_nodes)
 {
-    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
-    if (ctx->n_entries <= 0) return sat_fail(SAT_ESTATE, "no database uploaded");
+    SAT_TRY(sat_check_context(ctx));
+    SAT_TRY(sat_check_uploaded(ctx->n_entries > 0));
     if (n_nodes < 1) return sat_fail(SAT_EINVAL, "n_nodes must be >= 1 (got %d)", n_nodes);
     if (ctx->max_ordinal >= (uint32_t)n_nodes)
         return sat_fail(SAT_EINVAL, "n_nodes = %d, but a resident entry has ordinal %u in the whole database", n_nodes, ctx->max_ordinal);
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));             // an earlier accumulator may still be in use there
     ctx->cluster_nodes = 0;
-    int rc;
-    if ((rc = ctx->d_cl_parent.grow((size_t)n_nodes)) != SAT_OK || (rc = ctx->d_cl_out.grow(2 * (size_t)n_nodes)) != SAT_OK ||
-        (rc = ctx->d_cl_edges.grow(1)) != SAT_OK)
-        return rc;
+    SAT_TRY(ctx->d_cl_parent.grow((size_t)n_nodes));
+    SAT_TRY(ctx->d_cl_out.grow(2 * (size_t)n_nodes));
+    SAT_TRY(ctx->d_cl_edges.grow(1));
     // d_cl_out: labels [n_nodes] (written by sat_cluster_labels), then degrees [n_nodes]
     hipLaunchKernelGGL(cluster_init, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, ctx->stream, n_nodes, ctx->d_cl_parent.get(),
                        ctx->d_cl_out.get() + n_nodes, ctx->d_cl_edges.get());
@@ -172,57 +161,50 @@ int sat_cluster_begin(sat_ctx *ctx, int n_nodes)
 
 int sat_cluster_add(sat_ctx *ctx, double max_pvalue, const int32_t *query_node)
 {
-    int rc = check_accumulator(ctx);
-    if (rc != SAT_OK) return rc;
-    if ((rc = sat_check_searched(ctx)) != SAT_OK) return rc;
+    SAT_TRY(check_accumulator(ctx));
+    SAT_TRY(sat_check_searched(ctx));
     if (!query_node) return sat_fail(SAT_EINVAL, "query_node is null");
-    if (!std::isfinite(max_pvalue) || max_pvalue < 0.0) return sat_fail(SAT_EINVAL, "max_pvalue must be finite and >= 0");
+    SAT_TRY(sat_check_pvalue(max_pvalue));
     const int n = ctx->n_entries, nq = (int)ctx->queries.size(), nodes = ctx->cluster_nodes;
     for (int q = 0; q < nq; q++)
         if (query_node[q] < 0 || query_node[q] >= nodes)
             return sat_fail(SAT_EINVAL, "query %d: node %d outside 0..%d", q, query_node[q], nodes - 1);
     if (ctx->max_ordinal >= (uint32_t)nodes) return sat_fail(SAT_ESTATE, "the accumulator does not cover the resident database");
-    const int per_chunk = sat_cutoff_chunk(ctx, n);
-    const int bpq = (n + kCutoffBlock - 1) / kCutoffBlock;
     HIP_TRY(hipSetDevice(ctx->device));
-    if ((rc = ctx->d_cl_qnode.grow_after(ctx->stream, (size_t)nq)) != SAT_OK) return rc;
+    SAT_TRY(ctx->d_cl_qnode.grow_after(ctx->stream, (size_t)nq));
     // the caller's array may go at return: a synchronous copy, ordered behind the stream by sat_hitq_upload's wait
-    if ((rc = sat_hitq_upload(ctx)) != SAT_OK) return rc;
+    SAT_TRY(sat_hitq_upload(ctx, false));
     HIP_TRY(hipMemcpy(ctx->d_cl_qnode.get(), query_node, (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice));
-    const HitQuery *hq = reinterpret_cast<const HitQuery *>(ctx->d_hitq.get());
-    for (int q0 = 0; q0 < nq; q0 += per_chunk) {
-        const int nqc = nq - q0 < per_chunk ? nq - q0 : per_chunk;
-        hipLaunchKernelGGL(cluster_add, dim3((unsigned)nqc * (unsigned)bpq), dim3(kCutoffBlock), 0, ctx->stream,
-                           ctx->d_scores.get() + (size_t)q0 * n, n, bpq, ctx->d_orders.get(), hq + q0, ctx->d_gumbel_z.get(),
-                           ctx->d_gumbel_p.get(), max_pvalue, ctx->d_cl_qnode.get() + q0, ctx->d_ordinal.get(),
-                           ctx->d_cl_parent.get(), ctx->d_cl_out.get() + nodes, ctx->d_cl_edges.get());
+    const HitQuery *hq = hit_queries(ctx);
+    return sat_row_chunks(ctx, kCutoffBlock, [&](int q0, int, int bpq, dim3 grid) -> int {
+        hipLaunchKernelGGL(cluster_add, grid, dim3(kCutoffBlock), 0, ctx->stream, ctx->d_scores.get() + (size_t)q0 * n, n, bpq,
+                           ctx->d_orders.get(), hq + q0, ctx->d_gumbel_z.get(), ctx->d_gumbel_p.get(), max_pvalue,
+                           ctx->d_cl_qnode.get() + q0, ctx->d_ordinal.get(), ctx->d_cl_parent.get(), ctx->d_cl_out.get() + nodes,
+                           ctx->d_cl_edges.get());
         HIP_TRY(hipGetLastError());
-    }
-    return SAT_OK;
+        return SAT_OK;
+    });
 }
 
 int sat_cluster_labels(sat_ctx *ctx, int32_t *label, int32_t *degree, unsigned long long *edges)
 {
-    int rc = check_accumulator(ctx);
-    if (rc != SAT_OK) return rc;
+    SAT_TRY(check_accumulator(ctx));
     if (!label) return sat_fail(SAT_EINVAL, "label buffer is null");
     const int nodes = ctx->cluster_nodes;
     HIP_TRY(hipSetDevice(ctx->device));
     hipLaunchKernelGGL(cluster_labels, dim3((unsigned)((nodes + 255) / 256)), dim3(256), 0, ctx->stream, nodes, ctx->d_cl_parent.get(),
                        ctx->d_cl_out.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(label, ctx->d_cl_out.get(), (size_t)nodes * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (degree)
-        HIP_TRY(hipMemcpyAsync(degree, ctx->d_cl_out.get() + nodes, (size_t)nodes * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (edges) HIP_TRY(hipMemcpyAsync(edges, ctx->d_cl_edges.get(), sizeof *edges, hipMemcpyDeviceToHost, ctx->stream));
+    SAT_TRY(sat_fetch(ctx, label, ctx->d_cl_out.get(), (size_t)nodes, true));
+    if (degree) SAT_TRY(sat_fetch(ctx, degree, ctx->d_cl_out.get() + nodes, (size_t)nodes, true));
+    if (edges) SAT_TRY(sat_fetch(ctx, edges, ctx->d_cl_edges.get(), 1, true));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    ctx->d2h_bytes += (size_t)nodes * sizeof(int32_t) * (degree ? 2 : 1) + (edges ? sizeof *edges : 0);
     return SAT_OK;
 }
 
 int sat_cluster_end(sat_ctx *ctx)
 {
-    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
+    SAT_TRY(sat_check_context(ctx));
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     sat_cluster_drop(ctx);

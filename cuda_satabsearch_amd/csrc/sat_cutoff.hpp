@@ -1,26 +1,111 @@
-// sat_cutoff.hpp - the two halves of sat_hits_cutoff (sat_topk.hip), shared with sat_multi.hip; not part of the
-// public interface.
+// sat_cutoff.hpp - what the selection layer shares across sat_topk.hip, sat_cluster.hip and sat_multi.hip: the argument
+// checks of its entry points (each text once), the walk over the chunks of a query list, the counted device-to-host
+// copy, the fit of every query from a histogram, the searched-state functions sat_cluster_add uses too, and the two
+// halves of sat_hits_cutoff.  Not part of the public interface.
 #pragma once
 
+#include <algorithm>
+#include <cmath>
 #include <stdint.h>
+#include <vector>
 
-#include "satabsearch.h"
+#include "sat_pairs.hpp"                // the context, sat_fail - and sat_check_pairs, the pair lists' check of this kind
+#include "host/sat_gumbel.h"
 
+// a failed call of the library's own: its code goes up, the message stays what the call set
+#define SAT_TRY(expr) do { const int rc__ = (expr); if (rc__ != SAT_OK) return rc__; } while (0)
+
+// ---- Argument checks: SAT_OK, or the code and the text every entry point that takes the argument gives.  The entry
+// points call them in the order their checks have always fired.
+inline int sat_check_context(const void *ctx) { return ctx ? SAT_OK : sat_fail(SAT_EINVAL, "null context"); }
+inline int sat_check_uploaded(bool uploaded) { return uploaded ? SAT_OK : sat_fail(SAT_ESTATE, "no database uploaded"); }
+inline int sat_check_pvalue(double p) { return std::isfinite(p) && p >= 0.0 ? SAT_OK : sat_fail(SAT_EINVAL, "max_pvalue must be finite and >= 0"); }
+// (fit_rc: what sat_gumbel_fit_binned said to that censor - it refuses the same range)
+inline int sat_check_censor(double c, int fit_rc = 0) { return c >= 0.0 && c <= 0.5 && !fit_rc ? SAT_OK : sat_fail(SAT_EINVAL, "censor must lie in [0, 0.5]"); }
+inline int sat_check_tops(int tops)
+{
+    return tops >= 1 && tops <= SAT_MAX_MATCHES ? SAT_OK : sat_fail(SAT_EINVAL, "tops must be 1..%d (got %d)", SAT_MAX_MATCHES, tops);
+}
+// a best-k call's output buffers (`buffers`: none is null) and its k; the arguments of a refine call, on one context or sharded
+inline int sat_check_topk(bool buffers, int k) { return buffers && k >= 1 ? SAT_OK : sat_fail(SAT_EINVAL, "bad top-k arguments"); }
+inline int sat_check_refine(const void *ctx, const sat_hit *hits, int k, int candidates, int refine_maxstart)
+{
+    SAT_TRY(sat_check_context(ctx));
+    SAT_TRY(sat_check_topk(hits != nullptr, k));
+    if (candidates < 1) return sat_fail(SAT_EINVAL, "candidates must be >= 1 (got %d)", candidates);
+    if (refine_maxstart < 1) return sat_fail(SAT_EINVAL, "refine_maxstart must be >= 1 (got %d)", refine_maxstart);
+    if (k > candidates) return sat_fail(SAT_EINVAL, "k (%d) exceeds the candidates per query (%d)", k, candidates);
+    return SAT_OK;
+}
+
+// the rows a query returns of the c that qualify: all of them when max_rows <= 0
+inline int32_t sat_row_cap(int32_t c, int max_rows) { return max_rows > 0 && c > max_rows ? max_rows : c; }
+
+// ---- The searched state (sat_topk.hip).  SAT_ESTATE unless a search has run since the last upload / query change.
+int sat_check_searched(sat_ctx *ctx);
+// queries per launch of a kernel shaped like the cutoff kernels (blocks of 1024 rows, whole blocks per query): under 2^31
+// keys per sort and under 2^31 threads per launch - or under ctx->tune.select_keys of either
+int sat_cutoff_chunk(const sat_ctx *ctx, int n);
+// The HitQuery rows (sat_hitrow.hpp: hit_queries) of every query of the searched state into ctx->d_hitq - maps: with
+// their solution maps of the last search; an installed fit is followed - and the wait for the context's stream: the
+// rows' host copy dies there, and what the caller copies synchronously next is ordered behind the stream.
+int sat_hitq_upload(sat_ctx *ctx, bool maps);
+
+// ---- A query list in chunks of at most per_chunk queries: step(q0, nqc) for each in turn; the first error ends it.
+template <typename F> int sat_query_chunks(int nq, int per_chunk, F step)
+{
+    for (int q0 = 0; q0 < nq; q0 += per_chunk) SAT_TRY(step(q0, std::min(nq - q0, per_chunk)));
+    return SAT_OK;
+}
+// The searched state's queries for a pass of one thread per row, in blocks of block_rows rows of one query each:
+// sat_cutoff_chunk's chunks, step(q0, nqc, bpq, grid) with bpq blocks per query and the chunk's grid of nqc * bpq blocks.
+template <typename F> int sat_row_chunks(const sat_ctx *ctx, int block_rows, F step)
+{
+    const int n = ctx->n_entries, bpq = (n + block_rows - 1) / block_rows;
+    return sat_query_chunks((int)ctx->queries.size(), sat_cutoff_chunk(ctx, n),
+                            [&](int q0, int nqc) { return step(q0, nqc, bpq, dim3((unsigned)nqc * (unsigned)bpq)); });
+}
+
+// ---- Results to the host: `count` elements, and exactly their bytes added to what sat_stat_d2h_bytes reports.
+// Synchronous, or (queued) on the context's stream, where the caller waits.  src_pitch: the leading T of `count` records
+// of that many bytes each.
+template <typename T> int sat_fetch(sat_ctx *ctx, T *dst, const T *src, size_t count, bool queued = false)
+{
+    if (queued) HIP_TRY(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+    else HIP_TRY(hipMemcpy(dst, src, count * sizeof(T), hipMemcpyDeviceToHost));
+    ctx->d2h_bytes += count * sizeof(T);
+    return SAT_OK;
+}
+template <typename T> int sat_fetch_strided(sat_ctx *ctx, T *dst, const void *src, size_t src_pitch, size_t count)
+{
+    HIP_TRY(hipMemcpy2D(dst, sizeof(T), src, src_pitch, sizeof(T), count, hipMemcpyDeviceToHost));
+    ctx->d2h_bytes += count * sizeof(T);
+    return SAT_OK;
+}
+
+// ---- sat_stats_fit and sat_multi_search_fit behind their checks and searches: histogram(counts, below) of the nq
+// queries, each query fitted with the top `censor` of its rows censored, install(fit), and the fits to `fits` (may be null)
+template <typename Hist, typename Install> int sat_fit_queries(size_t nq, double censor, sat_fit *fits, Hist histogram, Install install)
+{
+    std::vector<uint32_t> counts(nq * SAT_STAT_BINS);
+    std::vector<int32_t> below(nq);
+    SAT_TRY(histogram(counts.data(), below.data()));
+    std::vector<sat_fit> fit(nq);
+    for (size_t q = 0; q < nq; q++) {
+        SAT_TRY(sat_check_censor(censor, sat_gumbel_fit_binned(counts.data() + q * SAT_STAT_BINS, censor, &fit[q])));
+        fit[q].below = below[q];
+    }
+    SAT_TRY(install(fit.data()));
+    if (fits) std::copy(fit.begin(), fit.end(), fits);
+    return SAT_OK;
+}
+
+// ---- The two halves of sat_hits_cutoff (sat_topk.hip); sat_multi_hits_cutoff sums its shards' counts in between.
 // After the checks sat_hits_cutoff makes on a context (a search has run; maps only after a search with LSOLN):
 // the flag / count pass over every query of the last search.  counts[q] (host, n_queries entries) = rows of query q
 // whose p-value is <= max_pvalue, uncapped.  Copies exactly 4 * n_queries bytes to the host.
 int sat_cutoff_count(sat_ctx *ctx, double max_pvalue, bool maps, int32_t *counts);
-
 // Right after sat_cutoff_count with the same max_pvalue and its counts: compaction, sort and finish, then the rows
 // to the host in CSR order - query q's first min(max_rows, counts[q]) rows (all when max_rows <= 0) at the sum of
 // the rows of the queries before it; maps (may be NULL) at the same row index times SAT_MAXDIM.
 int sat_cutoff_rows(sat_ctx *ctx, double max_pvalue, int max_rows, const int32_t *counts, sat_hit *hits, int32_t *ssemaps);
-
-// ---- for sat_cluster.hip (sat_cluster_add walks the same rows through the same predicate, cutoff_row of sat_hitrow.hpp).
-// sat_hits_cutoff's state check: SAT_ESTATE unless a search has run since the last upload / query change.
-int sat_check_searched(sat_ctx *ctx);
-// queries per launch of a kernel shaped like the cutoff kernels (blocks of 1024 rows, whole blocks per query)
-int sat_cutoff_chunk(const sat_ctx *ctx, int n);
-// The HitQuery rows (sat_hitrow.hpp) of every query of the searched state into ctx->d_hitq, without maps, as
-// sat_cutoff_count leaves them: an installed fit is followed.  Waits for the context's stream.
-int sat_hitq_upload(sat_ctx *ctx);

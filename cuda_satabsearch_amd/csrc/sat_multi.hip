@@ -13,6 +13,11 @@
 // for it).  Shards are padded to the largest one: a fixed-size gather, the rows are put in order on
 // the host after the one device-to-host copy.  SAT_MULTI_GATHER=peer selects hipMemcpyPeerAsync
 // into device 0 instead (also what is used when librccl cannot be loaded).
+//
+// The selection calls (best-k, refine, cutoff, histogram and fit, clustering) do not gather: every shard selects its own
+// rows and the host merges them (merge_shards, merge_rows) or sums them.  Their argument checks are those of the
+// single-context calls, from sat_cutoff.hpp; what every sharded call repeats - the set's own two checks, the wall clock,
+// the search on every shard, stage 1 of best-k and refine - is written once below.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>          // types and prototypes only: the entry points are resolved with dlsym
 
@@ -21,7 +26,6 @@
 #include <algorithm>
 #include <chrono>
 #include <climits>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -150,6 +154,22 @@ template <typename F> int each_shard(sat_multi *m, F step)
     return SAT_OK;
 }
 
+// a set that holds a database: what most entry points ask first (those that check arguments in between call the halves)
+int check_uploaded(const sat_multi *m) { return sat_check_uploaded(!m->begin.empty()); }
+int check_multi(const sat_multi *m) { return m ? check_uploaded(m) : sat_check_context(m); }
+
+// the wall clock of a call, from where this is made; stop(ms), on the success paths only: the milliseconds (ms may be null)
+struct Stopwatch {
+    const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    void stop(double *ms) const { if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+
+// a whole-database search queued on every shard (polished where sat_multi_polish_all_set says so)
+int search_shards(sat_multi *m, int lorder, int lsoln, int maxstart)
+{
+    return each_shard(m, [&](int g) { return sat_search_async(m->ctx[(size_t)g], lorder, lsoln, maxstart); });
+}
+
 // The k-way merge of one query's per-shard runs, each ranked by score (descending): shard g's run is rows[g][lo] ..
 // rows[g][hi - 1] with {lo, hi} = run(g).  take(g, row) receives the first `count` rows of the merged order.  Equal
 // scores: the lower shard first - shards are contiguous, so that is database order.
@@ -165,6 +185,57 @@ void merge_shards(const std::vector<std::vector<sat_hit>> &rows, size_t count, R
             if (head[g] < end[g] && (bg == ndev || rows[g][head[g]].score > rows[bg][head[bg]].score)) bg = g;
         take((int)bg, head[bg]++);
     }
+}
+
+// The shards' ranked rows merged into the caller's, query after query: the first count(q) rows of the merge of query q's
+// runs run(q, g), every entry indexed in the whole database, and (ssemaps not null) each row's map of maps[g] along.
+template <typename Count, typename Run>
+void merge_rows(const sat_multi *m, int nq, const std::vector<std::vector<sat_hit>> &rows, const std::vector<std::vector<int32_t>> &maps,
+                Count count, Run run, sat_hit *hits, int32_t *ssemaps)
+{
+    size_t out = 0;
+    for (int q = 0; q < nq; q++)
+        merge_shards(rows, count(q), [&](int g) { return run(q, g); }, [&](int g, size_t row) {
+            hits[out] = rows[(size_t)g][row];
+            hits[out].entry += m->begin[(size_t)g];
+            if (ssemaps) memcpy(ssemaps + out * SAT_MAXDIM, maps[(size_t)g].data() + row * SAT_MAXDIM, sizeof(int32_t) * SAT_MAXDIM);
+            out++;
+        });
+}
+
+// Stage 1 of the sharded best-k and refine calls: search(g) queued on every shard, then each shard's best c rows of every
+// query (maps: and their maps) into cand[g] (cmaps[g]): c rows per query leave each GPU, the host merges ndev x c
+// candidates.  got[g]: the rows per query shard g gave - query q's run there is run(q, g).
+struct ShardRows {
+    std::vector<std::vector<sat_hit>> cand;
+    std::vector<std::vector<int32_t>> cmaps;
+    std::vector<size_t> got;
+    std::pair<size_t, size_t> run(int q, int g) const { return { (size_t)q * got[(size_t)g], (size_t)(q + 1) * got[(size_t)g] }; }
+};
+template <typename Search> int stage1(sat_multi *m, Search search, int c, bool maps, ShardRows &s)
+{
+    SAT_TRY(each_shard(m, search));
+    const size_t rows = m->ctx[0]->queries.size() * (size_t)c;
+    s.cand.resize((size_t)m->ndev);
+    s.cmaps.resize((size_t)m->ndev);
+    s.got.assign((size_t)m->ndev, 0);
+    return each_shard(m, [&](int g) {
+        s.cand[(size_t)g].resize(rows);
+        if (maps) s.cmaps[(size_t)g].resize(rows * SAT_MAXDIM);
+        const int r = sat_topk_hits(m->ctx[(size_t)g], c, s.cand[(size_t)g].data(), maps ? s.cmaps[(size_t)g].data() : nullptr);
+        s.got[(size_t)g] = r < 0 ? 0 : (size_t)r;
+        return r < 0 ? r : SAT_OK;
+    });
+}
+
+// hit_row (sat_hitrow.hpp) without a fit, on the host, bit for bit: the same division, the truncation to an int and the
+// clamp to the table's -128 .. 127 explained there, z and p from the functions that filled the device's table
+sat_hit host_hit_row(int32_t entry, int32_t score, int n1, int n2)
+{
+    const double norm2 = sat_norm2(score, n1, n2);
+    const int x = std::max(-128, std::min(127, (int)norm2));
+    const double z = sat_z_gumbel_trunc((double)x);
+    return { entry, score, norm2, z, sat_pv_gumbel(z) };
 }
 
 // bring `count` elements of every device's `src(g)` into block g of `dst` on device 0
@@ -220,12 +291,12 @@ template <typename Launch, typename Collect>
 int sharded_pairs(sat_multi *m, int maxstart, int npairs, const int32_t *query, const int32_t *entry, double *wall_ms, Launch launch,
                   Collect collect)
 {
-    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
+    SAT_TRY(check_uploaded(m));
     if (m->ctx[0]->queries.empty()) return sat_fail(SAT_ESTATE, "no query set");
     if (maxstart < 1) return sat_fail(SAT_EINVAL, "maxstart must be >= 1 (got %d)", maxstart);
     int rc = sat_check_pairs((int)m->ctx[0]->queries.size(), m->n_entries, query, entry, npairs);
     if (rc != SAT_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
+    const Stopwatch clock;
     std::vector<std::vector<int32_t>> pq((size_t)m->ndev), pe((size_t)m->ndev), where((size_t)m->ndev);
     for (int p = 0; p < npairs; p++) {
         const int g = shard_of(m, entry[p]);
@@ -237,7 +308,7 @@ int sharded_pairs(sat_multi *m, int maxstart, int npairs, const int32_t *query, 
     if (rc != SAT_OK) return rc;
     rc = each_shard(m, [&](int g) { return collect(m->ctx[(size_t)g], (int)pq[(size_t)g].size(), pq[(size_t)g].data(), where[(size_t)g].data()); });
     if (rc != SAT_OK) return rc;
-    if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    clock.stop(wall_ms);
     return SAT_OK;
 }
 
@@ -325,7 +396,7 @@ const char *sat_multi_gather_kind(const sat_multi *m)
 int sat_multi_db_upload_packed(sat_multi *m, int n_entries, const int32_t *orders, const int64_t *cell_off,
                                const uint8_t *tab_tri, const float *dist_tri)
 {
-    if (!m) return sat_fail(SAT_EINVAL, "null context");
+    SAT_TRY(sat_check_context(m));
     if (n_entries < m->ndev) return sat_fail(SAT_EINVAL, "%d entries cannot be cut into %d shards", n_entries, m->ndev);
     if (!orders || !cell_off || !tab_tri || !dist_tri) return sat_fail(SAT_EINVAL, "null array");
     // a shard is uploaded as a WINDOW of the packed arrays (from its first entry's first cell): the entries must lie
@@ -376,7 +447,7 @@ int sat_multi_db_upload_packed(sat_multi *m, int n_entries, const int32_t *order
 int sat_multi_shards(const sat_multi *m, int32_t *begin)
 {
     if (!m || !begin) return sat_fail(SAT_EINVAL, "null argument");
-    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
+    SAT_TRY(check_uploaded(m));
     for (int g = 0; g <= m->ndev; g++) begin[g] = m->begin[(size_t)g];
     return SAT_OK;
 }
@@ -384,7 +455,7 @@ int sat_multi_shards(const sat_multi *m, int32_t *begin)
 int sat_multi_queries_set(sat_multi *m, int n_queries, const int32_t *n1s, const uint8_t *qtabs, const float *qdmats,
                           int pitch, const uint8_t *qssetypes, uint32_t first_query_ordinal)
 {
-    if (!m) return sat_fail(SAT_EINVAL, "null context");
+    SAT_TRY(sat_check_context(m));
     for (int g = 0; g < m->ndev; g++) {
         int rc = sat_queries_set(m->ctx[(size_t)g], n_queries, n1s, qtabs, qdmats, pitch, qssetypes, first_query_ordinal);
         if (rc != SAT_OK) return rc;
@@ -394,9 +465,9 @@ int sat_multi_queries_set(sat_multi *m, int n_queries, const int32_t *n1s, const
 
 int sat_multi_queries_from_db(sat_multi *m, int n_queries, const int32_t *entry, uint32_t first_query_ordinal)
 {
-    if (!m) return sat_fail(SAT_EINVAL, "null context");
+    SAT_TRY(sat_check_context(m));
     if (n_queries < 1 || !entry) return sat_fail(SAT_EINVAL, "bad query batch (n_queries=%d)", n_queries);
-    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
+    SAT_TRY(check_uploaded(m));
     // every query goes to the shard that holds its entry, under the entry's index there; the other shards learn its
     // size class only (sat_qfromdb_set)
     std::vector<int> owner((size_t)n_queries);
@@ -447,19 +518,19 @@ int sat_multi_queries_from_db(sat_multi *m, int n_queries, const int32_t *entry,
 
 int sat_multi_search(sat_multi *m, int lorder, int lsoln, int maxstart, int32_t *scores, int32_t *ssemaps, double *wall_ms)
 {
-    if (!m) return sat_fail(SAT_EINVAL, "null context");
+    SAT_TRY(sat_check_context(m));
     if (!scores) return sat_fail(SAT_EINVAL, "scores buffer is null");
     if (lsoln && !ssemaps) return sat_fail(SAT_EINVAL, "lsoln set but ssemaps buffer is null");
-    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
-    const auto t0 = std::chrono::steady_clock::now();
+    SAT_TRY(check_uploaded(m));
+    const Stopwatch clock;
     // (an error below waits for the searches already queued on the other GPUs before it is returned)
-    int rc = each_shard(m, [&](int g) { return sat_search_async(m->ctx[(size_t)g], lorder, lsoln, maxstart); });
+    int rc = search_shards(m, lorder, lsoln, maxstart);
     if (rc != SAT_OK) return rc;
     sat_ctx *root = m->ctx[0];
     const size_t nq = root->queries.size(), N = (size_t)m->n_entries, pad = (size_t)m->pad_rows;
     if (m->ndev == 1 && !m->force_gather) {
         rc = sat_results(root, lsoln, scores, ssemaps);
-        if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        clock.stop(wall_ms);
         return rc;
     }
     // ---- one gather of the (padded) per-shard rows to device 0, one copy to the host
@@ -511,62 +582,39 @@ int sat_multi_search(sat_multi *m, int lorder, int lsoln, int maxstart, int32_t 
             }
         }
     }
-    if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    clock.stop(wall_ms);
     return SAT_OK;
 }
 
 int sat_multi_search_topk(sat_multi *m, int lorder, int lsoln, int maxstart, int k, sat_hit *hits, int32_t *ssemaps, double *wall_ms)
 {
-    if (!m) return sat_fail(SAT_EINVAL, "null context");
-    if (!hits || k < 1) return sat_fail(SAT_EINVAL, "bad top-k arguments");
-    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
-    const auto t0 = std::chrono::steady_clock::now();
-    int rc = each_shard(m, [&](int g) { return sat_search_async(m->ctx[(size_t)g], lorder, lsoln, maxstart); });
-    if (rc != SAT_OK) return rc;
+    SAT_TRY(sat_check_context(m));
+    SAT_TRY(sat_check_topk(hits != nullptr, k));
+    SAT_TRY(check_uploaded(m));
+    const Stopwatch clock;
     if (k > m->n_entries) k = m->n_entries;
-    const int nq = (int)m->ctx[0]->queries.size();
-    // every GPU ranks its own shard (k rows per query leave each GPU), the host merges ndev x k candidates
-    std::vector<std::vector<sat_hit>> cand((size_t)m->ndev);
-    std::vector<std::vector<int32_t>> cmaps((size_t)m->ndev);
-    std::vector<size_t> got((size_t)m->ndev, 0);
-    rc = each_shard(m, [&](int g) {
-        cand[(size_t)g].resize((size_t)nq * k);
-        if (ssemaps) cmaps[(size_t)g].resize((size_t)nq * k * SAT_MAXDIM);
-        const int r = sat_topk_hits(m->ctx[(size_t)g], k, cand[(size_t)g].data(), ssemaps ? cmaps[(size_t)g].data() : nullptr);
-        got[(size_t)g] = r < 0 ? 0 : (size_t)r;
-        return r < 0 ? r : SAT_OK;
-    });
-    if (rc != SAT_OK) return rc;
-    size_t out = 0;
-    for (size_t q = 0; q < (size_t)nq; q++)
-        merge_shards(cand, (size_t)k, [&](int g) { return std::make_pair(q * got[(size_t)g], (q + 1) * got[(size_t)g]); },
-                     [&](int g, size_t row) {
-                         hits[out] = cand[(size_t)g][row];
-                         hits[out].entry += m->begin[(size_t)g];
-                         if (ssemaps)
-                             memcpy(ssemaps + out * SAT_MAXDIM, cmaps[(size_t)g].data() + row * SAT_MAXDIM, sizeof(int32_t) * SAT_MAXDIM);
-                         out++;
-                     });
-    if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ShardRows s;
+    SAT_TRY(stage1(m, [&](int g) { return sat_search_async(m->ctx[(size_t)g], lorder, lsoln, maxstart); }, k, ssemaps != nullptr, s));
+    merge_rows(m, (int)m->ctx[0]->queries.size(), s.cand, s.cmaps, [&](int) { return (size_t)k; },
+               [&](int q, int g) { return s.run(q, g); }, hits, ssemaps);
+    clock.stop(wall_ms);
     return k;
 }
 
 int sat_multi_search_matches(sat_multi *m, int lorder, int maxstart, int max_matches, int32_t *counts,
                              int32_t *scores, int32_t *restarts, int32_t *ssemaps, double *wall_ms)
 {
-    if (!m) return sat_fail(SAT_EINVAL, "null context");
+    SAT_TRY(sat_check_context(m));
     if (!counts || !scores || !restarts) return sat_fail(SAT_EINVAL, "counts / scores / restarts buffer is null");
-    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
-    const auto t0 = std::chrono::steady_clock::now();
+    SAT_TRY(check_uploaded(m));
+    const Stopwatch clock;
     // both passes queued on every GPU, then each shard's rows copied to its place in database order
-    int rc = each_shard(m, [&](int g) { return sat_matches_launch(m->ctx[(size_t)g], lorder, maxstart, max_matches, ssemaps != nullptr); });
-    if (rc != SAT_OK) return rc;
-    rc = each_shard(m, [&](int g) {
+    SAT_TRY(each_shard(m, [&](int g) { return sat_matches_launch(m->ctx[(size_t)g], lorder, maxstart, max_matches, ssemaps != nullptr); }));
+    SAT_TRY(each_shard(m, [&](int g) {
         return sat_matches_collect(m->ctx[(size_t)g], max_matches, counts, scores, restarts, ssemaps, (size_t)m->n_entries,
                                    (size_t)m->begin[(size_t)g]);
-    });
-    if (rc != SAT_OK) return rc;
-    if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }));
+    clock.stop(wall_ms);
     return SAT_OK;
 }
 
@@ -574,7 +622,7 @@ int sat_multi_search_pairs_matches(sat_multi *m, int lorder, int maxstart, int m
                                    const int32_t *entry, int32_t *counts, int32_t *scores, int32_t *restarts, int32_t *ssemaps,
                                    double *wall_ms)
 {
-    if (!m) return sat_fail(SAT_EINVAL, "null context");
+    SAT_TRY(sat_check_context(m));
     if (npairs > 0 && (!counts || !scores || !restarts)) return sat_fail(SAT_EINVAL, "counts / scores / restarts buffer is null");
     if (max_matches < 1 || max_matches > SAT_MAX_MATCHES)
         return sat_fail(SAT_EINVAL, "max_matches must be 1..%d (got %d)", SAT_MAX_MATCHES, max_matches);
@@ -591,9 +639,9 @@ int sat_multi_search_pairs_polish(sat_multi *m, int lorder, int maxstart, int to
                                   const int32_t *entry, int32_t *scores, int32_t *base_scores, int32_t *restarts, int32_t *moves,
                                   int32_t *ssemaps, double *wall_ms)
 {
-    if (!m) return sat_fail(SAT_EINVAL, "null context");
+    SAT_TRY(sat_check_context(m));
     if (npairs > 0 && !scores) return sat_fail(SAT_EINVAL, "scores buffer is null");
-    if (tops < 1 || tops > SAT_MAX_MATCHES) return sat_fail(SAT_EINVAL, "tops must be 1..%d (got %d)", SAT_MAX_MATCHES, tops);
+    SAT_TRY(sat_check_tops(tops));
     return sharded_pairs(m, maxstart, npairs, query, entry, wall_ms,
         [&](sat_ctx *c, const int32_t *q, const int32_t *e, int np) {
             return sat_pair_matches_launch(c, lorder, maxstart, tops, true, q, e, np, PairMode::Polish);
@@ -610,58 +658,44 @@ static int multi_refine(sat_multi *m, int lorder, int lsoln, int maxstart, int c
                         sat_hit *hits, int32_t *ssemaps, int32_t *first_scores, int32_t *base_scores, double *wall_ms,
                         double *stage2_ms)
 {
-    if (!m) return sat_fail(SAT_EINVAL, "null context");
-    if (!hits || k < 1) return sat_fail(SAT_EINVAL, "bad top-k arguments");
-    if (candidates < 1) return sat_fail(SAT_EINVAL, "candidates must be >= 1 (got %d)", candidates);
-    if (refine_maxstart < 1) return sat_fail(SAT_EINVAL, "refine_maxstart must be >= 1 (got %d)", refine_maxstart);
-    if (k > candidates) return sat_fail(SAT_EINVAL, "k (%d) exceeds the candidates per query (%d)", k, candidates);
-    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
-    const auto t0 = std::chrono::steady_clock::now();
+    SAT_TRY(sat_check_refine(m, hits, k, candidates, refine_maxstart));
+    SAT_TRY(check_uploaded(m));
+    const Stopwatch clock;
     // stage 1 on every shard, each ranking its own best C
     // (a plain search whatever sat_polish_all_set says: the mode is for whole-database searches, not for a refine's stage 1)
-    int rc = each_shard(m, [&](int g) { return launch_search(m->ctx[(size_t)g], lorder, 0, maxstart, m->ctx[(size_t)g]->stream); });
-    if (rc != SAT_OK) return rc;
     const int c = candidates < m->n_entries ? candidates : m->n_entries;
     if (k > c) k = c;
     const int nq = (int)m->ctx[0]->queries.size();
-    std::vector<std::vector<sat_hit>> cand((size_t)m->ndev);
-    std::vector<size_t> got((size_t)m->ndev, 0);
-    rc = each_shard(m, [&](int g) {
-        cand[(size_t)g].resize((size_t)nq * c);
-        const int r = sat_topk_hits(m->ctx[(size_t)g], c, cand[(size_t)g].data(), nullptr);
-        got[(size_t)g] = r < 0 ? 0 : (size_t)r;
-        return r < 0 ? r : SAT_OK;
-    });
-    if (rc != SAT_OK) return rc;
+    ShardRows s;
+    SAT_TRY(stage1(m, [&](int g) { return launch_search(m->ctx[(size_t)g], lorder, 0, maxstart, m->ctx[(size_t)g]->stream); }, c, false, s));
     // the global best C of every query, filed by shard as pairs
     struct Cand { int g, local, first, second, base; };
     std::vector<std::vector<Cand>> per_q((size_t)nq);
     std::vector<std::vector<int32_t>> pq((size_t)m->ndev), pe((size_t)m->ndev);
     std::vector<std::vector<std::pair<int, int>>> slot((size_t)m->ndev);     // (query, index in per_q) of each pair
     for (int q = 0; q < nq; q++)
-        merge_shards(cand, (size_t)c, [&](int g) { return std::make_pair((size_t)q * got[(size_t)g], (size_t)(q + 1) * got[(size_t)g]); },
+        merge_shards(s.cand, (size_t)c, [&](int g) { return s.run(q, g); },
                      [&](int g, size_t row) {
-                         const sat_hit &h = cand[(size_t)g][row];
+                         const sat_hit &h = s.cand[(size_t)g][row];
                          pq[(size_t)g].push_back(q);
                          pe[(size_t)g].push_back(h.entry);
                          slot[(size_t)g].push_back({ q, (int)per_q[(size_t)q].size() });
                          per_q[(size_t)q].push_back({ g, h.entry, h.score, 0, 0 });
                      });
     // stage 2: every shard re-scores its candidates (queued on all, then collected)
-    const auto t2 = std::chrono::steady_clock::now();
+    const Stopwatch clock2;
     const bool maps = lsoln && ssemaps;
-    rc = each_shard(m, [&](int g) {
+    SAT_TRY(each_shard(m, [&](int g) {
         if (tops)
             return sat_pair_matches_launch(m->ctx[(size_t)g], lorder, refine_maxstart, tops, true, pq[(size_t)g].data(),
                                            pe[(size_t)g].data(), (int)pq[(size_t)g].size(), PairMode::Polish);
         return sat_pairs_launch(m->ctx[(size_t)g], lorder, refine_maxstart, maps, pq[(size_t)g].data(), pe[(size_t)g].data(),
                                 (int)pq[(size_t)g].size());
-    });
-    if (rc != SAT_OK) return rc;
+    }));
     std::vector<std::vector<int32_t>> cmaps((size_t)nq);
     if (maps)
         for (int q = 0; q < nq; q++) cmaps[(size_t)q].resize(per_q[(size_t)q].size() * SAT_MAXDIM);
-    rc = each_shard(m, [&](int g) {
+    SAT_TRY(each_shard(m, [&](int g) {
         const size_t np = pq[(size_t)g].size();
         std::vector<int32_t> sc(np), bs(tops ? np : 0), mp(maps ? np * SAT_MAXDIM : 0);
         const int r = tops ? sat_polish_collect(m->ctx[(size_t)g], (int)np, sc.data(), bs.data(), nullptr, nullptr,
@@ -675,9 +709,8 @@ static int multi_refine(sat_multi *m, int lorder, int lsoln, int maxstart, int c
             if (maps) memcpy(cmaps[(size_t)sl.first].data() + (size_t)sl.second * SAT_MAXDIM, mp.data() + p * SAT_MAXDIM, sizeof(int32_t) * SAT_MAXDIM);
         }
         return SAT_OK;
-    });
-    if (rc != SAT_OK) return rc;
-    if (stage2_ms) *stage2_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count();
+    }));
+    clock2.stop(stage2_ms);
     // the final rows: stage-2 score descending, ties in database order; statistics as the device table holds them
     for (int q = 0; q < nq; q++) {
         auto &v = per_q[(size_t)q];
@@ -691,23 +724,14 @@ static int multi_refine(sat_multi *m, int lorder, int lsoln, int maxstart, int c
         const int n1 = m->ctx[0]->queries[(size_t)q].n1;
         for (int r = 0; r < k; r++) {
             const Cand &x = v[(size_t)order[(size_t)r]];
-            const int n2 = m->ctx[(size_t)x.g]->h_orders[(size_t)x.local];
-            sat_hit h;
-            h.entry = gidx(x);
-            h.score = x.second;
-            h.norm2 = sat_norm2(x.second, n1, n2);
-            int t = (int)h.norm2;
-            t = t < -128 ? -128 : (t > 127 ? 127 : t);
-            h.zscore = sat_z_gumbel_trunc((double)t);
-            h.pvalue = sat_pv_gumbel(h.zscore);
-            hits[(size_t)q * k + r] = h;
+            hits[(size_t)q * k + r] = host_hit_row(gidx(x), x.second, n1, m->ctx[(size_t)x.g]->h_orders[(size_t)x.local]);
             if (first_scores) first_scores[(size_t)q * k + r] = x.first;
             if (base_scores) base_scores[(size_t)q * k + r] = x.base;
             if (maps) memcpy(ssemaps + ((size_t)q * k + r) * SAT_MAXDIM, cmaps[(size_t)q].data() + (size_t)order[(size_t)r] * SAT_MAXDIM,
                              sizeof(int32_t) * SAT_MAXDIM);
         }
     }
-    if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    clock.stop(wall_ms);
     return k;
 }
 
@@ -724,7 +748,7 @@ int sat_multi_search_refine_polish(sat_multi *m, int lorder, int lsoln, int maxs
                                    int k, sat_hit *hits, int32_t *ssemaps, int32_t *first_scores, int32_t *base_scores,
                                    double *wall_ms)
 {
-    if (tops < 1 || tops > SAT_MAX_MATCHES) return sat_fail(SAT_EINVAL, "tops must be 1..%d (got %d)", SAT_MAX_MATCHES, tops);
+    SAT_TRY(sat_check_tops(tops));
     return multi_refine(m, lorder, lsoln, maxstart, candidates, refine_maxstart, tops, k, hits, ssemaps, first_scores, base_scores,
                         wall_ms, nullptr);
 }
@@ -732,23 +756,18 @@ int sat_multi_search_refine_polish(sat_multi *m, int lorder, int lsoln, int maxs
 int sat_multi_hits_cutoff(sat_multi *m, double max_pvalue, int max_rows, int32_t *counts, int capacity, sat_hit *hits,
                           int32_t *ssemaps)
 {
-    if (!m) return sat_fail(SAT_EINVAL, "null context");
-    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
+    SAT_TRY(check_multi(m));
     if (!counts) return sat_fail(SAT_EINVAL, "counts buffer is null");
-    if (!std::isfinite(max_pvalue) || max_pvalue < 0.0) return sat_fail(SAT_EINVAL, "max_pvalue must be finite and >= 0");
+    SAT_TRY(sat_check_pvalue(max_pvalue));
     const int nq = (int)m->ctx[0]->queries.size();
-    auto cap = [&](int32_t c) { return max_rows > 0 && c > max_rows ? max_rows : c; };
     // every shard counts its qualifying rows; a query's rows are the sum, cut to max_rows
     std::vector<std::vector<int32_t>> raw((size_t)m->ndev, std::vector<int32_t>((size_t)nq));
-    for (int g = 0; g < m->ndev; g++) {
-        const int rc = sat_cutoff_count(m->ctx[(size_t)g], max_pvalue, ssemaps != nullptr, raw[(size_t)g].data());
-        if (rc != SAT_OK) return rc;
-    }
+    for (int g = 0; g < m->ndev; g++) SAT_TRY(sat_cutoff_count(m->ctx[(size_t)g], max_pvalue, ssemaps != nullptr, raw[(size_t)g].data()));
     size_t total = 0;
     for (int q = 0; q < nq; q++) {
         long long c = 0;
         for (int g = 0; g < m->ndev; g++) c += raw[(size_t)g][(size_t)q];
-        counts[q] = cap(c > INT_MAX ? INT_MAX : (int32_t)c);
+        counts[q] = sat_row_cap(c > INT_MAX ? INT_MAX : (int32_t)c, max_rows);
         total += (size_t)counts[q];
     }
     if (total > (size_t)INT_MAX) return sat_fail(SAT_EINVAL, "%zu rows qualify: more than one call can return", total);
@@ -758,46 +777,34 @@ int sat_multi_hits_cutoff(sat_multi *m, double max_pvalue, int max_rows, int32_t
     std::vector<std::vector<int32_t>> rmaps((size_t)m->ndev);
     std::vector<std::vector<size_t>> off((size_t)m->ndev, std::vector<size_t>((size_t)nq + 1, 0));
     for (int g = 0; g < m->ndev; g++) {
-        for (int q = 0; q < nq; q++) off[(size_t)g][(size_t)q + 1] = off[(size_t)g][(size_t)q] + (size_t)cap(raw[(size_t)g][(size_t)q]);
+        for (int q = 0; q < nq; q++) off[(size_t)g][(size_t)q + 1] = off[(size_t)g][(size_t)q] + (size_t)sat_row_cap(raw[(size_t)g][(size_t)q], max_rows);
         rows[(size_t)g].resize(off[(size_t)g][(size_t)nq]);
         if (ssemaps) rmaps[(size_t)g].resize(off[(size_t)g][(size_t)nq] * SAT_MAXDIM);
-        const int rc = sat_cutoff_rows(m->ctx[(size_t)g], max_pvalue, max_rows, raw[(size_t)g].data(), rows[(size_t)g].data(),
-                                       ssemaps ? rmaps[(size_t)g].data() : nullptr);
-        if (rc != SAT_OK) return rc;
+        SAT_TRY(sat_cutoff_rows(m->ctx[(size_t)g], max_pvalue, max_rows, raw[(size_t)g].data(), rows[(size_t)g].data(),
+                                ssemaps ? rmaps[(size_t)g].data() : nullptr));
     }
-    size_t out = 0;
-    for (int q = 0; q < nq; q++)
-        merge_shards(rows, (size_t)counts[q], [&](int g) { return std::make_pair(off[(size_t)g][(size_t)q], off[(size_t)g][(size_t)q + 1]); },
-                     [&](int g, size_t row) {
-                         hits[out] = rows[(size_t)g][row];
-                         hits[out].entry += m->begin[(size_t)g];
-                         if (ssemaps)
-                             memcpy(ssemaps + out * SAT_MAXDIM, rmaps[(size_t)g].data() + row * SAT_MAXDIM, sizeof(int32_t) * SAT_MAXDIM);
-                         out++;
-                     });
+    merge_rows(m, nq, rows, rmaps, [&](int q) { return (size_t)counts[q]; },
+               [&](int q, int g) { return std::make_pair(off[(size_t)g][(size_t)q], off[(size_t)g][(size_t)q + 1]); }, hits, ssemaps);
     return (int)total;
 }
 
 int sat_multi_search_cutoff(sat_multi *m, int lorder, int lsoln, int maxstart, double max_pvalue, int max_rows, int32_t *counts,
                             int capacity, sat_hit *hits, int32_t *ssemaps, double *wall_ms)
 {
-    if (!m) return sat_fail(SAT_EINVAL, "null context");
-    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
+    SAT_TRY(check_multi(m));
     if (!counts) return sat_fail(SAT_EINVAL, "counts buffer is null");
-    if (!std::isfinite(max_pvalue) || max_pvalue < 0.0) return sat_fail(SAT_EINVAL, "max_pvalue must be finite and >= 0");
-    const auto t0 = std::chrono::steady_clock::now();
-    const int rc = each_shard(m, [&](int g) { return sat_search_async(m->ctx[(size_t)g], lorder, lsoln, maxstart); });
-    if (rc != SAT_OK) return rc;
+    SAT_TRY(sat_check_pvalue(max_pvalue));
+    const Stopwatch clock;
+    SAT_TRY(search_shards(m, lorder, lsoln, maxstart));
     const int r = sat_multi_hits_cutoff(m, max_pvalue, max_rows, counts, capacity, hits, ssemaps);
     if (r < 0) return bail(m, r);
-    if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    clock.stop(wall_ms);
     return r;
 }
 
 int sat_multi_score_histogram(sat_multi *m, uint32_t *counts, int32_t *below)
 {
-    if (!m) return sat_fail(SAT_EINVAL, "null context");
-    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
+    SAT_TRY(check_multi(m));
     if (!counts || !below) return sat_fail(SAT_EINVAL, "histogram buffer is null");
     const size_t nq = m->ctx[0]->queries.size();
     // integer counts add up across the shards, in any order
@@ -806,8 +813,7 @@ int sat_multi_score_histogram(sat_multi *m, uint32_t *counts, int32_t *below)
     std::fill(counts, counts + nq * SAT_STAT_BINS, 0u);
     std::fill(below, below + nq, 0);
     for (int g = 0; g < m->ndev; g++) {
-        const int rc = sat_score_histogram(m->ctx[(size_t)g], c.data(), b.data());
-        if (rc != SAT_OK) return rc;
+        SAT_TRY(sat_score_histogram(m->ctx[(size_t)g], c.data(), b.data()));
         for (size_t i = 0; i < c.size(); i++) counts[i] += c[i];
         for (size_t q = 0; q < nq; q++) below[q] += b[q];
     }
@@ -816,83 +822,58 @@ int sat_multi_score_histogram(sat_multi *m, uint32_t *counts, int32_t *below)
 
 int sat_multi_polish_all_set(sat_multi *m, int tops)
 {
-    if (!m) return sat_fail(SAT_EINVAL, "null context");
-    for (int g = 0; g < m->ndev; g++) {
-        const int rc = sat_polish_all_set(m->ctx[(size_t)g], tops);
-        if (rc != SAT_OK) return rc;
-    }
+    SAT_TRY(sat_check_context(m));
+    for (sat_ctx *c : m->ctx) SAT_TRY(sat_polish_all_set(c, tops));
     return SAT_OK;
 }
 
 int sat_multi_stats_set(sat_multi *m, const sat_fit *fits)
 {
-    if (!m) return sat_fail(SAT_EINVAL, "null context");
-    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
-    for (int g = 0; g < m->ndev; g++) {
-        const int rc = sat_stats_set(m->ctx[(size_t)g], fits);
-        if (rc != SAT_OK) return rc;
-    }
+    SAT_TRY(check_multi(m));
+    for (sat_ctx *c : m->ctx) SAT_TRY(sat_stats_set(c, fits));
     return SAT_OK;
 }
 
 int sat_multi_search_fit(sat_multi *m, int lorder, int lsoln, int maxstart, double censor, sat_fit *fits, double *wall_ms)
 {
-    if (!m) return sat_fail(SAT_EINVAL, "null context");
-    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
-    if (!(censor >= 0.0 && censor <= 0.5)) return sat_fail(SAT_EINVAL, "censor must lie in [0, 0.5]");
-    const auto t0 = std::chrono::steady_clock::now();
-    int rc = each_shard(m, [&](int g) { return sat_search_async(m->ctx[(size_t)g], lorder, lsoln, maxstart); });
-    if (rc != SAT_OK) return rc;
+    SAT_TRY(check_multi(m));
+    SAT_TRY(sat_check_censor(censor));
+    const Stopwatch clock;
+    SAT_TRY(search_shards(m, lorder, lsoln, maxstart));
     // no gather: each shard's scores stay where they are, only the histograms cross to the host
-    const size_t nq = m->ctx[0]->queries.size();
-    std::vector<uint32_t> counts(nq * SAT_STAT_BINS);
-    std::vector<int32_t> below(nq);
-    if ((rc = sat_multi_score_histogram(m, counts.data(), below.data())) != SAT_OK) return bail(m, rc);
-    std::vector<sat_fit> fit(nq);
-    for (size_t q = 0; q < nq; q++) {
-        if (sat_gumbel_fit_binned(counts.data() + q * SAT_STAT_BINS, censor, &fit[q]) != 0)
-            return bail(m, sat_fail(SAT_EINVAL, "censor must lie in [0, 0.5]"));
-        fit[q].below = below[q];
-    }
-    if ((rc = sat_multi_stats_set(m, fit.data())) != SAT_OK) return bail(m, rc);
-    if (fits) std::copy(fit.begin(), fit.end(), fits);
-    if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const int rc = sat_fit_queries(m->ctx[0]->queries.size(), censor, fits,
+                                   [&](uint32_t *counts, int32_t *below) { return sat_multi_score_histogram(m, counts, below); },
+                                   [&](const sat_fit *fit) { return sat_multi_stats_set(m, fit); });
+    if (rc != SAT_OK) return bail(m, rc);
+    clock.stop(wall_ms);
     return SAT_OK;
 }
 
 int sat_multi_search_only(sat_multi *m, int lorder, int lsoln, int maxstart, double *wall_ms)
 {
-    if (!m) return sat_fail(SAT_EINVAL, "null context");
-    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
-    const auto t0 = std::chrono::steady_clock::now();
-    int rc = each_shard(m, [&](int g) { return sat_search_async(m->ctx[(size_t)g], lorder, lsoln, maxstart); });
-    if (rc != SAT_OK) return rc;
+    SAT_TRY(check_multi(m));
+    const Stopwatch clock;
+    SAT_TRY(search_shards(m, lorder, lsoln, maxstart));
     // no gather: each shard's scores stay where they are (sat_sync also reports a polished row that did not finish)
-    rc = each_shard(m, [&](int g) { return sat_sync(m->ctx[(size_t)g]); });
-    if (rc != SAT_OK) return rc;
-    if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    SAT_TRY(each_shard(m, [&](int g) { return sat_sync(m->ctx[(size_t)g]); }));
+    clock.stop(wall_ms);
     return SAT_OK;
 }
 
 int sat_multi_cluster_begin(sat_multi *m)
 {
-    if (!m) return sat_fail(SAT_EINVAL, "null context");
-    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
+    SAT_TRY(check_multi(m));
     // every shard's nodes are the whole database's: its edges end at its own entries' ordinals, but start anywhere
-    for (int g = 0; g < m->ndev; g++) {
-        const int rc = sat_cluster_begin(m->ctx[(size_t)g], m->n_entries);
-        if (rc != SAT_OK) return rc;
-    }
+    for (sat_ctx *c : m->ctx) SAT_TRY(sat_cluster_begin(c, m->n_entries));
     return SAT_OK;
 }
 
 int sat_multi_cluster_add(sat_multi *m, double max_pvalue, const int32_t *query_node)
 {
-    if (!m) return sat_fail(SAT_EINVAL, "null context");
-    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
+    SAT_TRY(check_multi(m));
     // the argument checks of sat_cluster_add, made for all shards before the first one adds anything
     if (!query_node) return sat_fail(SAT_EINVAL, "query_node is null");
-    if (!std::isfinite(max_pvalue) || max_pvalue < 0.0) return sat_fail(SAT_EINVAL, "max_pvalue must be finite and >= 0");
+    SAT_TRY(sat_check_pvalue(max_pvalue));
     const size_t nq = m->ctx[0]->queries.size();
     for (size_t q = 0; q < nq; q++)
         if (query_node[q] < 0 || query_node[q] >= m->n_entries)
@@ -902,8 +883,7 @@ int sat_multi_cluster_add(sat_multi *m, double max_pvalue, const int32_t *query_
 
 int sat_multi_cluster_labels(sat_multi *m, int32_t *label, int32_t *degree, unsigned long long *edges)
 {
-    if (!m) return sat_fail(SAT_EINVAL, "null context");
-    if (m->begin.empty()) return sat_fail(SAT_ESTATE, "no database uploaded");
+    SAT_TRY(check_multi(m));
     if (!label) return sat_fail(SAT_EINVAL, "label buffer is null");
     const size_t n = (size_t)m->n_entries, ndev = (size_t)m->ndev;
     if (ndev == 1) return sat_cluster_labels(m->ctx[0], label, degree, edges);

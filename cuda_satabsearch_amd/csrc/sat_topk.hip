@@ -1,5 +1,9 @@
-// sat_topk.hip - best-k hits of a finished search, selected, ranked and given their statistics
-// on the device, so that only k rows per query leave the GPU.
+// sat_topk.hip - the rows of a finished search, selected, ranked and given their statistics on the device, so that only
+// the rows asked for leave the GPU: best-k (sat_topk, sat_topk_hits), the final ranking of the refine calls, every row
+// under a p-value cutoff (sat_hits_cutoff and its two halves), the score histogram and the fit built on it.  One code
+// object: the file's kernels and the hipCUB / rocPRIM instantiations they rank with.  What it shares with
+// sat_cluster.hip and sat_multi.hip - the argument checks, the chunk walk, the counted copies - is in sat_cutoff.hpp, the
+// device code of a row in sat_hitrow.hpp.
 //
 // Users of the reference sort the full "name score norm2 z p" listing by raw score and keep the
 // head (README_example_usage.txt:100, 256: `sort -k 2,2nr | head`).  Here: one pass packs every
@@ -24,7 +28,7 @@
 
 #include "sat_pairs.hpp"
 #include "sat_cutoff.hpp"
-#include "sat_hitrow.hpp"               // HitQuery, hit_row, cutoff_row: shared with sat_cluster.hip
+#include "sat_hitrow.hpp"               // HitQuery, hit_row, row_map, cutoff_row, block_count: shared with sat_cluster.hip
 #include "host/sat_gumbel.h"
 
 namespace {
@@ -53,20 +57,14 @@ __global__ void finish_hits(const unsigned long long *sorted, int n, int k, int 
     const int32_t entry = key_index(key), score = key_score(key);
     const int n1 = queries[q].n1, n2 = orders[entry];
     hits[t] = hit_row(entry, score, n1, n2, ztab, ptab, queries[q].fit);
-    if (maps) {
-        int32_t *out = maps + (size_t)t * SAT_MAXDIM;
-        const int8_t *src = queries[q].ssemaps ? queries[q].ssemaps + (size_t)entry * n1 : nullptr;
-        for (int i = 0; i < SAT_MAXDIM; i++) out[i] = (src && i < n1) ? (int32_t)src[i] : -1;
-    }
+    if (maps) row_map(queries[q].ssemaps ? queries[q].ssemaps + (size_t)entry * n1 : nullptr, n1, maps + (size_t)t * SAT_MAXDIM);
 }
 
 // The HitQuery rows of queries [q0, q0 + nq) into ctx->d_hitq (maps: their solution maps of the last search; the fitted
-// tables of the queries that have a fit), queued
-// on the context's stream from `hq`, which the caller keeps until the stream has passed the copy.
+// tables of the queries that have a fit), queued on the context's stream from `hq`, which the caller keeps until then.
 int upload_hit_queries(sat_ctx *ctx, int q0, int nq, bool maps, std::vector<HitQuery> &hq)
 {
-    const int rc = ctx->d_hitq.grow((size_t)nq * sizeof(HitQuery));
-    if (rc != SAT_OK) return rc;
+    SAT_TRY(ctx->d_hitq.grow((size_t)nq * sizeof(HitQuery)));
     hq.resize((size_t)nq);
     for (int q = 0; q < nq; q++) {
         const auto &info = ctx->queries[(size_t)(q0 + q)];
@@ -80,15 +78,38 @@ int upload_hit_queries(sat_ctx *ctx, int q0, int nq, bool maps, std::vector<HitQ
     return SAT_OK;
 }
 
-const HitQuery *hit_queries(const sat_ctx *ctx) { return reinterpret_cast<const HitQuery *>(ctx->d_hitq.get()); }
-
-// n keys sorted descending from `in` to `out` on `stream`: one segment, or nseg segments seg[s] .. seg[s + 1] - 1 (a
-// device array).  temp = null: only sets temp_bytes to the space the sort needs (hipcub's two-phase call).
-hipError_t sort_keys_desc(void *temp, size_t &temp_bytes, const unsigned long long *in, unsigned long long *out, int n, int nseg,
-                          int *seg, hipStream_t stream)
+// What a ranking of queries [q0, q0 + nq) reads from the host: the segment offsets q * stride, q = 0 .. nq, into
+// ctx->d_seg (nq * stride < 2^31: the callers cut the batch) and the HitQuery rows, queued like those from `host`.
+struct RankInput { std::vector<int> seg; std::vector<HitQuery> hq; };
+int upload_rank_input(sat_ctx *ctx, int q0, int nq, int stride, bool maps, RankInput &host)
 {
-    if (nseg == 1) return hipcub::DeviceRadixSort::SortKeysDescending(temp, temp_bytes, in, out, n, 0, 64, stream);
-    return hipcub::DeviceSegmentedRadixSort::SortKeysDescending(temp, temp_bytes, in, out, n, nseg, seg, seg + 1, 0, 64, stream);
+    SAT_TRY(ctx->d_seg.grow((size_t)nq + 1));
+    host.seg.resize((size_t)nq + 1);
+    for (int q = 0; q <= nq; q++) host.seg[(size_t)q] = q * stride;
+    HIP_TRY(hipMemcpyAsync(ctx->d_seg.get(), host.seg.data(), host.seg.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    return upload_hit_queries(ctx, q0, nq, maps, host.hq);
+}
+
+// hipCUB's two-phase call: run(null, bytes) only sets bytes to the space the call needs, ctx->d_sort_temp grows to it
+// (behind the stream: the call before may still work in it), run(space, bytes) does the work.
+template <typename F> int cub_run(sat_ctx *ctx, F run)
+{
+    size_t temp_bytes = 0;
+    HIP_TRY(run(nullptr, temp_bytes));
+    SAT_TRY(ctx->d_sort_temp.grow_after(ctx->stream, temp_bytes ? temp_bytes : 1));
+    HIP_TRY(run(ctx->d_sort_temp.get(), temp_bytes));
+    return SAT_OK;
+}
+
+// n keys sorted descending from ctx->d_keys to ctx->d_sorted: one segment, or nseg segments seg[s] .. seg[s + 1] - 1 (device)
+int sort_keys_desc(sat_ctx *ctx, int n, int nseg, int *seg)
+{
+    const unsigned long long *in = ctx->d_keys.get();
+    unsigned long long *out = ctx->d_sorted.get();
+    return cub_run(ctx, [&](void *temp, size_t &temp_bytes) {
+        if (nseg == 1) return hipcub::DeviceRadixSort::SortKeysDescending(temp, temp_bytes, in, out, n, 0, 64, ctx->stream);
+        return hipcub::DeviceSegmentedRadixSort::SortKeysDescending(temp, temp_bytes, in, out, n, nseg, seg, seg + 1, 0, 64, ctx->stream);
+    });
 }
 
 // rank queries [q0, q0 + nq) of the last search; rows land at row `out_row` of ctx->d_hits (and
@@ -98,30 +119,20 @@ int select_hits(sat_ctx *ctx, int q0, int nq, int k, bool want_maps, size_t out_
     const int n = ctx->n_entries;
     const size_t total = (size_t)nq * n;
     HIP_TRY(hipSetDevice(ctx->device));
-    int rc;
-    if ((rc = ctx->d_keys.grow(total)) != SAT_OK) return rc;
-    if ((rc = ctx->d_sorted.grow(total)) != SAT_OK) return rc;
+    SAT_TRY(ctx->d_keys.grow(total));
+    SAT_TRY(ctx->d_sorted.grow(total));
     if (out_row == 0) {                                   // first chunk: size the row buffers for the whole batch
-        if ((rc = ctx->d_hits.grow(rows_total)) != SAT_OK) return rc;
-        if (want_maps && (rc = ctx->d_hit_maps.grow(rows_total * SAT_MAXDIM)) != SAT_OK) return rc;
+        SAT_TRY(ctx->d_hits.grow(rows_total));
+        if (want_maps) SAT_TRY(ctx->d_hit_maps.grow(rows_total * SAT_MAXDIM));
     }
-    if ((rc = ctx->d_seg.grow((size_t)nq + 1)) != SAT_OK) return rc;
-
-    std::vector<int> seg((size_t)nq + 1);
-    std::vector<HitQuery> hq;
-    for (int q = 0; q <= nq; q++) seg[(size_t)q] = q * n;            // nq * n < 2^31: the callers cut the batch
-    HIP_TRY(hipMemcpyAsync(ctx->d_seg.get(), seg.data(), seg.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = upload_hit_queries(ctx, q0, nq, want_maps, hq)) != SAT_OK) return rc;
+    RankInput host;
+    SAT_TRY(upload_rank_input(ctx, q0, nq, n, want_maps, host));
 
     const int32_t *scores = ctx->d_scores.get() + (size_t)q0 * n;
     hipLaunchKernelGGL(pack_keys, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, scores, (long long)total, n,
                        ctx->d_keys.get());
     HIP_TRY(hipGetLastError());
-    size_t temp_bytes = 0;
-    HIP_TRY(sort_keys_desc(nullptr, temp_bytes, ctx->d_keys.get(), ctx->d_sorted.get(), (int)total, nq, ctx->d_seg.get(), ctx->stream));
-    if ((rc = ctx->d_sort_temp.grow(temp_bytes ? temp_bytes : 1)) != SAT_OK) return rc;
-    HIP_TRY(sort_keys_desc(ctx->d_sort_temp.get(), temp_bytes, ctx->d_keys.get(), ctx->d_sorted.get(), (int)total, nq, ctx->d_seg.get(),
-                           ctx->stream));
+    SAT_TRY(sort_keys_desc(ctx, (int)total, nq, ctx->d_seg.get()));
     hipLaunchKernelGGL(finish_hits, dim3((unsigned)((nq * k + 127) / 128)), dim3(128), 0, ctx->stream, ctx->d_sorted.get(), n, k, nq,
                        ctx->d_orders.get(), hit_queries(ctx), ctx->d_gumbel_z.get(), ctx->d_gumbel_p.get(), ctx->d_hits.get() + out_row,
                        want_maps ? ctx->d_hit_maps.get() + out_row * SAT_MAXDIM : nullptr);
@@ -137,12 +148,7 @@ int select_all_hits(sat_ctx *ctx, int k, bool want_maps)
 {
     const int nq = (int)ctx->queries.size(), n = ctx->n_entries;
     const int per_chunk = (int)(ctx->tune.select_keys / n) < 1 ? 1 : (int)(ctx->tune.select_keys / n);
-    for (int q0 = 0; q0 < nq; q0 += per_chunk) {
-        const int nqc = nq - q0 < per_chunk ? nq - q0 : per_chunk;
-        const int rc = select_hits(ctx, q0, nqc, k, want_maps, (size_t)q0 * k, (size_t)nq * k);
-        if (rc != SAT_OK) return rc;
-    }
-    return SAT_OK;
+    return sat_query_chunks(nq, per_chunk, [&](int q0, int nqc) { return select_hits(ctx, q0, nqc, k, want_maps, (size_t)q0 * k, (size_t)nq * k); });
 }
 
 // refine: pair p = q * C + c is candidate c of query q (stage-1 row p of ctx->d_hits); its final key is the
@@ -171,19 +177,11 @@ __global__ void finish_refined(const unsigned long long *sorted, const int32_t *
     hits[t] = hit_row(entry, score, n1, orders[entry], ztab, ptab, queries[q].fit);
     first[t] = cand[p].score;
     if (base) base[t] = pbase[p];                        // polish: the pair's score before it
-    if (maps) {
+    if (maps) {                                          // (not row_map: without its null test this loop compiles to other code)
         int32_t *out = maps + (size_t)t * SAT_MAXDIM;
         const int8_t *src = pmaps + (size_t)p * SAT_MAXDIM;
         for (int i = 0; i < SAT_MAXDIM; i++) out[i] = i < n1 ? (int32_t)src[i] : -1;
     }
-}
-
-int check_searched(sat_ctx *ctx)
-{
-    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
-    if (ctx->n_entries <= 0 || ctx->queries.empty() || !ctx->d_scores.get() || ctx->searched_nq != ctx->queries.size())
-        return sat_fail(SAT_ESTATE, "no search has run since the last database upload / query change");
-    return SAT_OK;
 }
 
 // ---- p-value cutoff (sat_hits_cutoff).  Blocks of 1024 rows, `bpq` blocks per query, so that a block holds rows of
@@ -200,15 +198,7 @@ __global__ void __launch_bounds__(kCutoffBlock) cutoff_count(const int32_t *scor
     int q, e;
     int32_t score = 0;
     const bool hit = cutoff_row(scores, n, bpq, orders, queries, ztab, ptab, max_p, q, e, score);
-    __shared__ int32_t wave_count[kCutoffWaves];
-    const unsigned long long mask = __ballot(hit);
-    if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = (int32_t)__popcll(mask);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int32_t c = 0;
-        for (int w = 0; w < kCutoffWaves; w++) c += wave_count[w];
-        if (c) atomicAdd(counts + q, c);
-    }
+    block_count(hit, [&](int32_t c) { atomicAdd(counts + q, c); });
 }
 
 // the qualifying rows' keys (pack_keys' layout) into their query's segment seg[q] .. seg[q + 1], in any order: each
@@ -260,11 +250,7 @@ __global__ void cutoff_finish(const unsigned long long *sorted, const int32_t *s
     const int32_t entry = key_index(key), score = key_score(key);
     const int n1 = queries[q].n1;
     hits[t] = hit_row(entry, score, n1, orders[entry], ztab, ptab, queries[q].fit);
-    if (maps) {
-        int32_t *out = maps + (size_t)t * SAT_MAXDIM;
-        const int8_t *src = queries[q].ssemaps ? queries[q].ssemaps + (size_t)entry * n1 : nullptr;
-        for (int i = 0; i < SAT_MAXDIM; i++) out[i] = (src && i < n1) ? (int32_t)src[i] : -1;
-    }
+    if (maps) row_map(queries[q].ssemaps ? queries[q].ssemaps + (size_t)entry * n1 : nullptr, n1, maps + (size_t)t * SAT_MAXDIM);
 }
 
 
@@ -310,9 +296,18 @@ __global__ void __launch_bounds__(kHistBlock) score_histogram(const int32_t *sco
     }
 }
 
-// queries per chunk: under 2^31 keys per sort (as sat_topk_hits) and under 2^31 threads per launch - or under
-// ctx->tune.select_keys of either
-int cutoff_chunk(const sat_ctx *ctx, int n)
+}  // namespace
+
+// ---- sat_cutoff.hpp: the searched state, for this file and for sat_cluster_add, which walks the same rows
+int sat_check_searched(sat_ctx *ctx)
+{
+    SAT_TRY(sat_check_context(ctx));
+    if (ctx->n_entries <= 0 || ctx->queries.empty() || !ctx->d_scores.get() || ctx->searched_nq != ctx->queries.size())
+        return sat_fail(SAT_ESTATE, "no search has run since the last database upload / query change");
+    return SAT_OK;
+}
+
+int sat_cutoff_chunk(const sat_ctx *ctx, int n)
 {
     const long long bpq = (n + kCutoffBlock - 1) / kCutoffBlock, keys = ctx->tune.select_keys;
     long long per = keys / n;
@@ -320,60 +315,46 @@ int cutoff_chunk(const sat_ctx *ctx, int n)
     return per < 1 ? 1 : (int)per;
 }
 
-}  // namespace
-
-// sat_cutoff.hpp, for sat_cluster.hip: the searched-state check, the chunking and the HitQuery rows of the cutoff pass
-int sat_check_searched(sat_ctx *ctx) { return check_searched(ctx); }
-int sat_cutoff_chunk(const sat_ctx *ctx, int n) { return cutoff_chunk(ctx, n); }
-int sat_hitq_upload(sat_ctx *ctx)
+int sat_hitq_upload(sat_ctx *ctx, bool maps)
 {
     std::vector<HitQuery> hq_host;
-    const int rc = upload_hit_queries(ctx, 0, (int)ctx->queries.size(), false, hq_host);
-    if (rc != SAT_OK) return rc;
+    SAT_TRY(upload_hit_queries(ctx, 0, (int)ctx->queries.size(), maps, hq_host));
     HIP_TRY(hipStreamSynchronize(ctx->stream));             // hq_host dies at return
     return SAT_OK;
 }
 
 // The histogram of every query of the last search into ctx->d_hist (counts [nq][SAT_STAT_BINS], then below [nq]) and
-// from there to the host.  The query lists go in cutoff_chunk's chunks: fewer blocks per query here, so a chunk that
+// from there to the host.  The query lists go in sat_cutoff_chunk's chunks: fewer blocks per query here, so a chunk that
 // fits the cutoff kernels' grid fits this one.
 extern "C" int sat_score_histogram(sat_ctx *ctx, uint32_t *counts, int32_t *below)
 {
-    int rc = check_searched(ctx);
-    if (rc != SAT_OK) return rc;
+    SAT_TRY(sat_check_searched(ctx));
     if (!counts || !below) return sat_fail(SAT_EINVAL, "histogram buffer is null");
     const int n = ctx->n_entries, nq = (int)ctx->queries.size();
     if (n > 0x7FFFFFFF - kHistRows) return sat_fail(SAT_EINVAL, "too many entries for the histogram pass");
-    const int per_chunk = cutoff_chunk(ctx, n);
-    const int bpq = (n + kHistRows - 1) / kHistRows;
     const size_t words = (size_t)nq * (SAT_STAT_BINS + 1);
     HIP_TRY(hipSetDevice(ctx->device));
-    if ((rc = ctx->d_hist.grow(words)) != SAT_OK) return rc;
-    std::vector<HitQuery> hq_host;
-    if ((rc = upload_hit_queries(ctx, 0, nq, false, hq_host)) != SAT_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));             // hq_host dies at return
+    SAT_TRY(ctx->d_hist.grow(words));
+    SAT_TRY(sat_hitq_upload(ctx, false));
     const HitQuery *hq = hit_queries(ctx);
     uint32_t *d_counts = ctx->d_hist.get();
     int32_t *d_below = reinterpret_cast<int32_t *>(d_counts + (size_t)nq * SAT_STAT_BINS);
     HIP_TRY(hipMemsetAsync(d_counts, 0, words * sizeof(uint32_t), ctx->stream));
-    for (int q0 = 0; q0 < nq; q0 += per_chunk) {
-        const int nqc = nq - q0 < per_chunk ? nq - q0 : per_chunk;
-        hipLaunchKernelGGL(score_histogram, dim3((unsigned)nqc * (unsigned)bpq), dim3(kHistBlock), 0, ctx->stream,
-                           ctx->d_scores.get() + (size_t)q0 * n, n, bpq, ctx->d_orders.get(), hq + q0,
-                           d_counts + (size_t)q0 * SAT_STAT_BINS, d_below + q0);
+    SAT_TRY(sat_row_chunks(ctx, kHistRows, [&](int q0, int, int bpq, dim3 grid) -> int {
+        hipLaunchKernelGGL(score_histogram, grid, dim3(kHistBlock), 0, ctx->stream, ctx->d_scores.get() + (size_t)q0 * n, n, bpq,
+                           ctx->d_orders.get(), hq + q0, d_counts + (size_t)q0 * SAT_STAT_BINS, d_below + q0);
         HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipMemcpyAsync(counts, d_counts, (size_t)nq * SAT_STAT_BINS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(below, d_below, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        return SAT_OK;
+    }));
+    SAT_TRY(sat_fetch(ctx, counts, d_counts, (size_t)nq * SAT_STAT_BINS, true));
+    SAT_TRY(sat_fetch(ctx, below, d_below, (size_t)nq, true));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    ctx->d2h_bytes += words * sizeof(uint32_t);
     return SAT_OK;
 }
 
 extern "C" int sat_stats_set(sat_ctx *ctx, const sat_fit *fits)
 {
-    int rc = check_searched(ctx);
-    if (rc != SAT_OK) return rc;
+    SAT_TRY(sat_check_searched(ctx));
     ctx->fits.clear();
     if (!fits) return SAT_OK;
     const size_t nq = ctx->queries.size();
@@ -387,7 +368,7 @@ extern "C" int sat_stats_set(sat_ctx *ctx, const sat_fit *fits)
     if (any) {
         HIP_TRY(hipSetDevice(ctx->device));
         // (rows selected earlier may still be read through the old tables on the stream)
-        if ((rc = ctx->d_fit_tabs.grow_after(ctx->stream, nq * 2 * SAT_STAT_BINS)) != SAT_OK) return rc;
+        SAT_TRY(ctx->d_fit_tabs.grow_after(ctx->stream, nq * 2 * SAT_STAT_BINS));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         std::vector<double> tab(2 * SAT_STAT_BINS);
         for (size_t q = 0; q < nq; q++) {
@@ -403,28 +384,15 @@ extern "C" int sat_stats_set(sat_ctx *ctx, const sat_fit *fits)
 
 extern "C" int sat_stats_fit(sat_ctx *ctx, double censor, sat_fit *fits)
 {
-    int rc = check_searched(ctx);
-    if (rc != SAT_OK) return rc;
-    if (!(censor >= 0.0 && censor <= 0.5)) return sat_fail(SAT_EINVAL, "censor must lie in [0, 0.5]");
-    const size_t nq = ctx->queries.size();
-    std::vector<uint32_t> counts(nq * SAT_STAT_BINS);
-    std::vector<int32_t> below(nq);
-    if ((rc = sat_score_histogram(ctx, counts.data(), below.data())) != SAT_OK) return rc;
-    std::vector<sat_fit> fit(nq);
-    for (size_t q = 0; q < nq; q++) {
-        if (sat_gumbel_fit_binned(counts.data() + q * SAT_STAT_BINS, censor, &fit[q]) != 0)
-            return sat_fail(SAT_EINVAL, "censor must lie in [0, 0.5]");
-        fit[q].below = below[q];
-    }
-    if ((rc = sat_stats_set(ctx, fit.data())) != SAT_OK) return rc;
-    if (fits) std::copy(fit.begin(), fit.end(), fits);
-    return SAT_OK;
+    SAT_TRY(sat_check_searched(ctx));
+    SAT_TRY(sat_check_censor(censor));
+    return sat_fit_queries(ctx->queries.size(), censor, fits, [&](uint32_t *counts, int32_t *below) { return sat_score_histogram(ctx, counts, below); },
+                           [&](const sat_fit *fit) { return sat_stats_set(ctx, fit); });
 }
 
 extern "C" int sat_debug_set_scores(sat_ctx *ctx, const int32_t *scores)
 {
-    int rc = check_searched(ctx);
-    if (rc != SAT_OK) return rc;
+    SAT_TRY(sat_check_searched(ctx));
     if (!scores) return sat_fail(SAT_EINVAL, "scores buffer is null");
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -435,15 +403,13 @@ extern "C" int sat_debug_set_scores(sat_ctx *ctx, const int32_t *scores)
 
 extern "C" int sat_topk(sat_ctx *ctx, int query, int k, int32_t *entry_index, int32_t *scores_out)
 {
-    int rc = check_searched(ctx);
-    if (rc != SAT_OK) return rc;
-    if (!entry_index || !scores_out || k < 1) return sat_fail(SAT_EINVAL, "bad top-k arguments");
+    SAT_TRY(sat_check_searched(ctx));
+    SAT_TRY(sat_check_topk(entry_index && scores_out, k));
     if (query < 0 || query >= (int)ctx->queries.size()) return sat_fail(SAT_EINVAL, "query %d out of range", query);
     if (k > ctx->n_entries) k = ctx->n_entries;
-    if ((rc = select_hits(ctx, query, 1, k, false, 0, (size_t)k)) != SAT_OK) return rc;
+    SAT_TRY(select_hits(ctx, query, 1, k, false, 0, (size_t)k));
     std::vector<sat_hit> rows((size_t)k);
-    HIP_TRY(hipMemcpy(rows.data(), ctx->d_hits.get(), rows.size() * sizeof(sat_hit), hipMemcpyDeviceToHost));
-    ctx->d2h_bytes += rows.size() * sizeof(sat_hit);
+    SAT_TRY(sat_fetch(ctx, rows.data(), ctx->d_hits.get(), rows.size()));
     for (int i = 0; i < k; i++) {
         entry_index[i] = rows[(size_t)i].entry;
         scores_out[i] = rows[(size_t)i].score;
@@ -453,19 +419,14 @@ extern "C" int sat_topk(sat_ctx *ctx, int query, int k, int32_t *entry_index, in
 
 extern "C" int sat_topk_hits(sat_ctx *ctx, int k, sat_hit *hits, int32_t *ssemaps)
 {
-    int rc = check_searched(ctx);
-    if (rc != SAT_OK) return rc;
-    if (!hits || k < 1) return sat_fail(SAT_EINVAL, "bad top-k arguments");
+    SAT_TRY(sat_check_searched(ctx));
+    SAT_TRY(sat_check_topk(hits != nullptr, k));
     if (ssemaps && !ctx->searched_lsoln) return sat_fail(SAT_ESTATE, "the last search ran without lsoln");
     if (k > ctx->n_entries) k = ctx->n_entries;
-    const int nq = (int)ctx->queries.size();
-    if ((rc = select_all_hits(ctx, k, ssemaps != nullptr)) != SAT_OK) return rc;
-    HIP_TRY(hipMemcpy(hits, ctx->d_hits.get(), (size_t)nq * k * sizeof(sat_hit), hipMemcpyDeviceToHost));
-    ctx->d2h_bytes += (size_t)nq * k * sizeof(sat_hit);
-    if (ssemaps) {
-        HIP_TRY(hipMemcpy(ssemaps, ctx->d_hit_maps.get(), (size_t)nq * k * SAT_MAXDIM * sizeof(int32_t), hipMemcpyDeviceToHost));
-        ctx->d2h_bytes += (size_t)nq * k * SAT_MAXDIM * sizeof(int32_t);
-    }
+    const size_t rows = ctx->queries.size() * (size_t)k;
+    SAT_TRY(select_all_hits(ctx, k, ssemaps != nullptr));
+    SAT_TRY(sat_fetch(ctx, hits, ctx->d_hits.get(), rows));
+    if (ssemaps) SAT_TRY(sat_fetch(ctx, ssemaps, ctx->d_hit_maps.get(), rows * SAT_MAXDIM));
     return k;
 }
 
@@ -474,15 +435,10 @@ extern "C" int sat_topk_hits(sat_ctx *ctx, int k, sat_hit *hits, int32_t *ssemap
 static int refine(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int candidates, int refine_maxstart, int tops,
                   int k, sat_hit *hits, int32_t *ssemaps, int32_t *first_scores, int32_t *base_scores)
 {
-    if (!ctx) return sat_fail(SAT_EINVAL, "null context");
-    if (!hits || k < 1) return sat_fail(SAT_EINVAL, "bad top-k arguments");
-    if (candidates < 1) return sat_fail(SAT_EINVAL, "candidates must be >= 1 (got %d)", candidates);
-    if (refine_maxstart < 1) return sat_fail(SAT_EINVAL, "refine_maxstart must be >= 1 (got %d)", refine_maxstart);
-    if (k > candidates) return sat_fail(SAT_EINVAL, "k (%d) exceeds the candidates per query (%d)", k, candidates);
+    SAT_TRY(sat_check_refine(ctx, hits, k, candidates, refine_maxstart));
     HIP_TRY(hipSetDevice(ctx->device));
     // stage 1: the plain search at maxstart, without LSOLN
-    int rc = launch_search(ctx, lorder, 0, maxstart, ctx->stream);
-    if (rc != SAT_OK) return rc;
+    SAT_TRY(launch_search(ctx, lorder, 0, maxstart, ctx->stream));
     const std::string stage1_info = ctx->last_launch_info;
     const int n = ctx->n_entries, nq = (int)ctx->queries.size();
     const int c = candidates < n ? candidates : n;
@@ -490,75 +446,54 @@ static int refine(sat_ctx *ctx, int lorder, int lsoln, int maxstart, int candida
     if ((long long)nq * c > 0x7FFFFFFFll) return sat_fail(SAT_EINVAL, "queries x candidates exceed 2^31 - 1");
     const int npairs = nq * c;
     // the best c entries of every query, ranked on the device (rows stay there); only their indices come back
-    if ((rc = select_all_hits(ctx, c, false)) != SAT_OK) return rc;
+    SAT_TRY(select_all_hits(ctx, c, false));
     std::vector<int32_t> query((size_t)npairs), entry((size_t)npairs);
-    HIP_TRY(hipMemcpy2D(entry.data(), sizeof(int32_t), ctx->d_hits.get(), sizeof(sat_hit), sizeof(int32_t), (size_t)npairs,
-                        hipMemcpyDeviceToHost));
-    ctx->d2h_bytes += (size_t)npairs * sizeof(int32_t);
+    SAT_TRY(sat_fetch_strided(ctx, entry.data(), ctx->d_hits.get(), sizeof(sat_hit), (size_t)npairs));     // sat_hit begins with its entry
     for (int p = 0; p < npairs; p++) query[(size_t)p] = p / c;
     // stage 2: the candidates at refine_maxstart (and their maps)
     const bool maps = lsoln && ssemaps;
-    rc = tops ? sat_pair_matches_launch(ctx, lorder, refine_maxstart, tops, true, query.data(), entry.data(), npairs, PairMode::Polish)
-              : sat_pairs_launch(ctx, lorder, refine_maxstart, maps, query.data(), entry.data(), npairs);
-    if (rc != SAT_OK) return rc;
+    SAT_TRY(tops ? sat_pair_matches_launch(ctx, lorder, refine_maxstart, tops, true, query.data(), entry.data(), npairs, PairMode::Polish)
+                 : sat_pairs_launch(ctx, lorder, refine_maxstart, maps, query.data(), entry.data(), npairs));
     const unsigned long long *pkeys = tops ? ctx->d_polkeys.get() : ctx->d_pkeys.get();
     const int8_t *pmaps = tops ? ctx->d_polmaps.get() : ctx->d_pmaps.get();
     const std::string stage2_info = ctx->last_launch_info;
     // the final ranking: segments of c keys, one per query
-    if ((rc = ctx->d_rkeys.grow((size_t)npairs)) != SAT_OK) return rc;
-    if ((rc = ctx->d_rsorted.grow((size_t)npairs)) != SAT_OK) return rc;
-    if ((rc = ctx->d_rvals.grow((size_t)npairs)) != SAT_OK) return rc;
-    if ((rc = ctx->d_rvals_sorted.grow((size_t)npairs)) != SAT_OK) return rc;
-    if ((rc = ctx->d_rhits.grow((size_t)nq * k)) != SAT_OK) return rc;
-    if ((rc = ctx->d_rfirst.grow(2 * (size_t)nq * k)) != SAT_OK) return rc;      // stage-1 scores, then (polish) base scores
-    if (maps && (rc = ctx->d_rmaps.grow((size_t)nq * k * SAT_MAXDIM)) != SAT_OK) return rc;
-    if ((rc = ctx->d_seg.grow((size_t)nq + 1)) != SAT_OK) return rc;
-    std::vector<int> seg((size_t)nq + 1);
-    std::vector<HitQuery> hq;
-    for (int q = 0; q <= nq; q++) seg[(size_t)q] = q * c;
-    HIP_TRY(hipMemcpyAsync(ctx->d_seg.get(), seg.data(), seg.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = upload_hit_queries(ctx, 0, nq, false, hq)) != SAT_OK) return rc;
+    const size_t rows = (size_t)nq * k;
+    SAT_TRY(ctx->d_rkeys.grow((size_t)npairs));
+    SAT_TRY(ctx->d_rsorted.grow((size_t)npairs));
+    SAT_TRY(ctx->d_rvals.grow((size_t)npairs));
+    SAT_TRY(ctx->d_rvals_sorted.grow((size_t)npairs));
+    SAT_TRY(ctx->d_rhits.grow(rows));
+    SAT_TRY(ctx->d_rfirst.grow(2 * rows));                               // stage-1 scores, then (polish) base scores
+    if (maps) SAT_TRY(ctx->d_rmaps.grow(rows * SAT_MAXDIM));
+    RankInput host;
+    SAT_TRY(upload_rank_input(ctx, 0, nq, c, false, host));
     hipLaunchKernelGGL(pack_refined, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, ctx->stream, pkeys, ctx->d_hits.get(),
                        npairs, ctx->d_rkeys.get(), ctx->d_rvals.get());
     HIP_TRY(hipGetLastError());
-    size_t temp_bytes = 0;
-    HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortPairsDescending(nullptr, temp_bytes, ctx->d_rkeys.get(), ctx->d_rsorted.get(),
-                                                                 ctx->d_rvals.get(), ctx->d_rvals_sorted.get(), npairs, nq,
-                                                                 ctx->d_seg.get(), ctx->d_seg.get() + 1, 0, 64, ctx->stream));
-    if ((rc = ctx->d_sort_temp.grow(temp_bytes ? temp_bytes : 1)) != SAT_OK) return rc;
-    HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortPairsDescending(ctx->d_sort_temp.get(), temp_bytes, ctx->d_rkeys.get(),
-                                                                 ctx->d_rsorted.get(), ctx->d_rvals.get(), ctx->d_rvals_sorted.get(),
-                                                                 npairs, nq, ctx->d_seg.get(), ctx->d_seg.get() + 1, 0, 64, ctx->stream));
+    SAT_TRY(cub_run(ctx, [&](void *temp, size_t &temp_bytes) {
+        return hipcub::DeviceSegmentedRadixSort::SortPairsDescending(temp, temp_bytes, ctx->d_rkeys.get(), ctx->d_rsorted.get(),
+                                                                     ctx->d_rvals.get(), ctx->d_rvals_sorted.get(), npairs, nq,
+                                                                     ctx->d_seg.get(), ctx->d_seg.get() + 1, 0, 64, ctx->stream);
+    }));
     hipLaunchKernelGGL(finish_refined, dim3((unsigned)((nq * k + 127) / 128)), dim3(128), 0, ctx->stream, ctx->d_rsorted.get(),
                        ctx->d_rvals_sorted.get(), c, k, nq, ctx->d_orders.get(), hit_queries(ctx), ctx->d_gumbel_z.get(),
                        ctx->d_gumbel_p.get(), ctx->d_hits.get(), pmaps, ctx->d_rhits.get(), ctx->d_rfirst.get(),
                        maps ? ctx->d_rmaps.get() : nullptr, tops ? (const int32_t *)ctx->d_polout.get() + npairs : nullptr,
-                       tops ? ctx->d_rfirst.get() + (size_t)nq * k : nullptr);
+                       tops ? ctx->d_rfirst.get() + rows : nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    const size_t rows = (size_t)nq * k;
     if (tops) {
         // a pair whose polish did not finish carries moves = -1 (sat_polish.hip): one flag row, npairs ints
         std::vector<int32_t> mv((size_t)npairs);
-        HIP_TRY(hipMemcpy(mv.data(), ctx->d_polout.get() + 3 * (size_t)npairs, mv.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-        ctx->d2h_bytes += mv.size() * sizeof(int32_t);
+        SAT_TRY(sat_fetch(ctx, mv.data(), ctx->d_polout.get() + 3 * (size_t)npairs, mv.size()));
         for (int p = 0; p < npairs; p++)
             if (mv[(size_t)p] < 0) return sat_fail(SAT_EDEVICE, "pair %d: the polish did not finish", p);
-        if (base_scores) {
-            HIP_TRY(hipMemcpy(base_scores, ctx->d_rfirst.get() + rows, rows * sizeof(int32_t), hipMemcpyDeviceToHost));
-            ctx->d2h_bytes += rows * sizeof(int32_t);
-        }
+        if (base_scores) SAT_TRY(sat_fetch(ctx, base_scores, ctx->d_rfirst.get() + rows, rows));
     }
-    HIP_TRY(hipMemcpy(hits, ctx->d_rhits.get(), rows * sizeof(sat_hit), hipMemcpyDeviceToHost));
-    ctx->d2h_bytes += rows * sizeof(sat_hit);
-    if (first_scores) {
-        HIP_TRY(hipMemcpy(first_scores, ctx->d_rfirst.get(), rows * sizeof(int32_t), hipMemcpyDeviceToHost));
-        ctx->d2h_bytes += rows * sizeof(int32_t);
-    }
-    if (maps) {
-        HIP_TRY(hipMemcpy(ssemaps, ctx->d_rmaps.get(), rows * SAT_MAXDIM * sizeof(int32_t), hipMemcpyDeviceToHost));
-        ctx->d2h_bytes += rows * SAT_MAXDIM * sizeof(int32_t);
-    }
+    SAT_TRY(sat_fetch(ctx, hits, ctx->d_rhits.get(), rows));
+    if (first_scores) SAT_TRY(sat_fetch(ctx, first_scores, ctx->d_rfirst.get(), rows));
+    if (maps) SAT_TRY(sat_fetch(ctx, ssemaps, ctx->d_rmaps.get(), rows * SAT_MAXDIM));
     ctx->last_launch_info = "stage 1: " + stage1_info + " || stage 2: " + stage2_info;
     return k;
 }
@@ -573,7 +508,7 @@ extern "C" int sat_search_refine_polish(sat_ctx *ctx, int lorder, int lsoln, int
                                         int tops, int k, sat_hit *hits, int32_t *ssemaps, int32_t *first_scores,
                                         int32_t *base_scores)
 {
-    if (tops < 1 || tops > SAT_MAX_MATCHES) return sat_fail(SAT_EINVAL, "tops must be 1..%d (got %d)", SAT_MAX_MATCHES, tops);
+    SAT_TRY(sat_check_tops(tops));
     return refine(ctx, lorder, lsoln, maxstart, candidates, refine_maxstart, tops, k, hits, ssemaps, first_scores, base_scores);
 }
 
@@ -582,118 +517,95 @@ extern "C" int sat_search_refine_polish(sat_ctx *ctx, int lorder, int lsoln, int
 
 int sat_cutoff_count(sat_ctx *ctx, double max_pvalue, bool maps, int32_t *counts)
 {
-    int rc = check_searched(ctx);
-    if (rc != SAT_OK) return rc;
+    SAT_TRY(sat_check_searched(ctx));
     if (maps && !ctx->searched_lsoln) return sat_fail(SAT_ESTATE, "the last search ran without lsoln");
-    const int n = ctx->n_entries, nq = (int)ctx->queries.size();
-    const int per_chunk = cutoff_chunk(ctx, n), pc = per_chunk < nq ? per_chunk : nq;
-    const int bpq = (n + kCutoffBlock - 1) / kCutoffBlock;
+    const int n = ctx->n_entries, nq = (int)ctx->queries.size(), pc = std::min(sat_cutoff_chunk(ctx, n), nq);
     HIP_TRY(hipSetDevice(ctx->device));
-    if ((rc = ctx->d_seg.grow((size_t)nq + 3 * (size_t)pc + 2)) != SAT_OK) return rc;
-    std::vector<HitQuery> hq_host;
-    if ((rc = upload_hit_queries(ctx, 0, nq, maps, hq_host)) != SAT_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));             // hq_host dies at return
+    SAT_TRY(ctx->d_seg.grow((size_t)nq + 3 * (size_t)pc + 2));
+    SAT_TRY(sat_hitq_upload(ctx, maps));
     const HitQuery *hq = hit_queries(ctx);
     HIP_TRY(hipMemsetAsync(ctx->d_seg.get(), 0, (size_t)nq * sizeof(int32_t), ctx->stream));
-    for (int q0 = 0; q0 < nq; q0 += per_chunk) {
-        const int nqc = nq - q0 < per_chunk ? nq - q0 : per_chunk;
-        hipLaunchKernelGGL(cutoff_count, dim3((unsigned)nqc * (unsigned)bpq), dim3(kCutoffBlock), 0, ctx->stream,
-                           ctx->d_scores.get() + (size_t)q0 * n, n, bpq, ctx->d_orders.get(), hq + q0, ctx->d_gumbel_z.get(),
-                           ctx->d_gumbel_p.get(), max_pvalue, ctx->d_seg.get() + q0);
+    SAT_TRY(sat_row_chunks(ctx, kCutoffBlock, [&](int q0, int, int bpq, dim3 grid) -> int {
+        hipLaunchKernelGGL(cutoff_count, grid, dim3(kCutoffBlock), 0, ctx->stream, ctx->d_scores.get() + (size_t)q0 * n, n, bpq,
+                           ctx->d_orders.get(), hq + q0, ctx->d_gumbel_z.get(), ctx->d_gumbel_p.get(), max_pvalue, ctx->d_seg.get() + q0);
         HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipMemcpyAsync(counts, ctx->d_seg.get(), (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        return SAT_OK;
+    }));
+    SAT_TRY(sat_fetch(ctx, counts, ctx->d_seg.get(), (size_t)nq, true));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    ctx->d2h_bytes += (size_t)nq * sizeof(int32_t);
     return SAT_OK;
 }
 
 int sat_cutoff_rows(sat_ctx *ctx, double max_pvalue, int max_rows, const int32_t *counts, sat_hit *hits, int32_t *ssemaps)
 {
     const int n = ctx->n_entries, nq = (int)ctx->queries.size();
-    const int per_chunk = cutoff_chunk(ctx, n);
-    const int bpq = (n + kCutoffBlock - 1) / kCutoffBlock;
     const bool maps = ssemaps != nullptr;
+    // the row buffers hold every query's rows, the key buffers the keys of the largest chunk
     size_t rows_total = 0, keys_max = 0;
-    for (int q0 = 0; q0 < nq; q0 += per_chunk) {
-        const int nqc = nq - q0 < per_chunk ? nq - q0 : per_chunk;
-        size_t keys = 0;
-        for (int q = q0; q < q0 + nqc; q++) {
-            keys += (size_t)counts[q];
-            rows_total += (size_t)(max_rows > 0 && counts[q] > max_rows ? max_rows : counts[q]);
-        }
-        if (keys > keys_max) keys_max = keys;
-    }
+    for (int q = 0; q < nq; q++) rows_total += (size_t)sat_row_cap(counts[q], max_rows);
     if (rows_total == 0) return SAT_OK;
+    (void)sat_row_chunks(ctx, kCutoffBlock, [&](int q0, int nqc, int, dim3) {
+        size_t keys = 0;
+        for (int q = q0; q < q0 + nqc; q++) keys += (size_t)counts[q];
+        if (keys > keys_max) keys_max = keys;
+        return SAT_OK;
+    });
     HIP_TRY(hipSetDevice(ctx->device));
-    int rc;
-    if ((rc = ctx->d_keys.grow(keys_max)) != SAT_OK) return rc;
-    if ((rc = ctx->d_sorted.grow(keys_max)) != SAT_OK) return rc;
-    if ((rc = ctx->d_hits.grow(rows_total)) != SAT_OK) return rc;
-    if (maps && (rc = ctx->d_hit_maps.grow(rows_total * SAT_MAXDIM)) != SAT_OK) return rc;
+    SAT_TRY(ctx->d_keys.grow(keys_max));
+    SAT_TRY(ctx->d_sorted.grow(keys_max));
+    SAT_TRY(ctx->d_hits.grow(rows_total));
+    if (maps) SAT_TRY(ctx->d_hit_maps.grow(rows_total * SAT_MAXDIM));
     const HitQuery *hq = hit_queries(ctx);                                    // as sat_cutoff_count left them
     size_t out_row = 0;
     std::vector<int32_t> out_off;
-    for (int q0 = 0; q0 < nq; q0 += per_chunk) {
-        const int nqc = nq - q0 < per_chunk ? nq - q0 : per_chunk;
+    SAT_TRY(sat_row_chunks(ctx, kCutoffBlock, [&](int q0, int nqc, int bpq, dim3 grid) -> int {
         int32_t *seg = ctx->d_seg.get() + nq, *d_out = seg + nqc + 1, *cursor = d_out + nqc + 1;
         // the chunk's output offsets (each query cut to max_rows); its segment offsets: a scan of its counts
         out_off.assign((size_t)nqc + 1, 0);
         int keys = 0;
         for (int q = 0; q < nqc; q++) {
-            const int c = counts[q0 + q];
-            keys += c;
-            out_off[(size_t)q + 1] = out_off[(size_t)q] + (max_rows > 0 && c > max_rows ? max_rows : c);
+            keys += counts[q0 + q];
+            out_off[(size_t)q + 1] = out_off[(size_t)q] + sat_row_cap(counts[q0 + q], max_rows);
         }
         const int rows = out_off[(size_t)nqc];
-        if (rows == 0) continue;
+        if (rows == 0) return SAT_OK;
         HIP_TRY(hipMemcpyAsync(d_out, out_off.data(), out_off.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(hipMemsetAsync(seg, 0, sizeof(int32_t), ctx->stream));
         HIP_TRY(hipMemsetAsync(cursor, 0, (size_t)nqc * sizeof(int32_t), ctx->stream));
-        size_t scan_bytes = 0, sort_bytes = 0;
-        HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, ctx->d_seg.get() + q0, seg + 1, nqc, ctx->stream));
-        HIP_TRY(sort_keys_desc(nullptr, sort_bytes, ctx->d_keys.get(), ctx->d_sorted.get(), keys, nqc, seg, ctx->stream));
-        const size_t temp_bytes = scan_bytes > sort_bytes ? scan_bytes : sort_bytes;
-        if ((rc = ctx->d_sort_temp.grow(temp_bytes ? temp_bytes : 1)) != SAT_OK) return rc;
-        HIP_TRY(hipcub::DeviceScan::InclusiveSum(ctx->d_sort_temp.get(), scan_bytes, ctx->d_seg.get() + q0, seg + 1, nqc, ctx->stream));
-        hipLaunchKernelGGL(cutoff_compact, dim3((unsigned)nqc * (unsigned)bpq), dim3(kCutoffBlock), 0, ctx->stream,
-                           ctx->d_scores.get() + (size_t)q0 * n, n, bpq, ctx->d_orders.get(), hq + q0, ctx->d_gumbel_z.get(),
-                           ctx->d_gumbel_p.get(), max_pvalue, seg, cursor, ctx->d_keys.get());
+        SAT_TRY(cub_run(ctx, [&](void *temp, size_t &temp_bytes) {
+            return hipcub::DeviceScan::InclusiveSum(temp, temp_bytes, ctx->d_seg.get() + q0, seg + 1, nqc, ctx->stream);
+        }));
+        hipLaunchKernelGGL(cutoff_compact, grid, dim3(kCutoffBlock), 0, ctx->stream, ctx->d_scores.get() + (size_t)q0 * n, n, bpq,
+                           ctx->d_orders.get(), hq + q0, ctx->d_gumbel_z.get(), ctx->d_gumbel_p.get(), max_pvalue, seg, cursor,
+                           ctx->d_keys.get());
         HIP_TRY(hipGetLastError());
-        HIP_TRY(sort_keys_desc(ctx->d_sort_temp.get(), sort_bytes, ctx->d_keys.get(), ctx->d_sorted.get(), keys, nqc, seg, ctx->stream));
+        SAT_TRY(sort_keys_desc(ctx, keys, nqc, seg));
         hipLaunchKernelGGL(cutoff_finish, dim3((unsigned)((rows + 127) / 128)), dim3(128), 0, ctx->stream, ctx->d_sorted.get(), seg, d_out,
                            nqc, rows, ctx->d_orders.get(), hq + q0, ctx->d_gumbel_z.get(), ctx->d_gumbel_p.get(),
                            ctx->d_hits.get() + out_row, maps ? ctx->d_hit_maps.get() + out_row * SAT_MAXDIM : nullptr);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(ctx->stream));                     // out_off is reused by the next chunk
         out_row += (size_t)rows;
-    }
-    HIP_TRY(hipMemcpy(hits, ctx->d_hits.get(), rows_total * sizeof(sat_hit), hipMemcpyDeviceToHost));
-    ctx->d2h_bytes += rows_total * sizeof(sat_hit);
-    if (maps) {
-        HIP_TRY(hipMemcpy(ssemaps, ctx->d_hit_maps.get(), rows_total * SAT_MAXDIM * sizeof(int32_t), hipMemcpyDeviceToHost));
-        ctx->d2h_bytes += rows_total * SAT_MAXDIM * sizeof(int32_t);
-    }
+        return SAT_OK;
+    }));
+    SAT_TRY(sat_fetch(ctx, hits, ctx->d_hits.get(), rows_total));
+    if (maps) SAT_TRY(sat_fetch(ctx, ssemaps, ctx->d_hit_maps.get(), rows_total * SAT_MAXDIM));
     return SAT_OK;
 }
 
 extern "C" int sat_hits_cutoff(sat_ctx *ctx, double max_pvalue, int max_rows, int32_t *counts, int capacity, sat_hit *hits,
                                int32_t *ssemaps)
 {
-    int rc = check_searched(ctx);
-    if (rc != SAT_OK) return rc;
+    SAT_TRY(sat_check_searched(ctx));
     if (!counts) return sat_fail(SAT_EINVAL, "counts buffer is null");
-    if (!std::isfinite(max_pvalue) || max_pvalue < 0.0) return sat_fail(SAT_EINVAL, "max_pvalue must be finite and >= 0");
+    SAT_TRY(sat_check_pvalue(max_pvalue));
     const int nq = (int)ctx->queries.size();
     std::vector<int32_t> raw((size_t)nq);
-    if ((rc = sat_cutoff_count(ctx, max_pvalue, ssemaps != nullptr, raw.data())) != SAT_OK) return rc;
+    SAT_TRY(sat_cutoff_count(ctx, max_pvalue, ssemaps != nullptr, raw.data()));
     size_t total = 0;
-    for (int q = 0; q < nq; q++) {
-        counts[q] = max_rows > 0 && raw[(size_t)q] > max_rows ? max_rows : raw[(size_t)q];
-        total += (size_t)counts[q];
-    }
+    for (int q = 0; q < nq; q++) total += (size_t)(counts[q] = sat_row_cap(raw[(size_t)q], max_rows));
     if (total > (size_t)INT_MAX) return sat_fail(SAT_EINVAL, "%zu rows qualify: more than one call can return", total);
     if (!hits || (long long)total > (long long)capacity) return (int)total;
-    if ((rc = sat_cutoff_rows(ctx, max_pvalue, max_rows, raw.data(), hits, ssemaps)) != SAT_OK) return rc;
+    SAT_TRY(sat_cutoff_rows(ctx, max_pvalue, max_rows, raw.data(), hits, ssemaps));
     return (int)total;
 }
