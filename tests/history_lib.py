@@ -1,0 +1,833 @@
+"""Call sequences on ONE context (tests/test_gpu_history.py, tests/test_history_cpu.py): worlds, operations with their
+CPU references, a model of the documented context state, and seeded schedules.
+
+* A WORLD is (database, query batch, first ordinal), synthetic with fixed seeds: six databases (largest entry <= 16,
+  <= 32, 33..48 and 111 SSEs; 150 entries for the shards; 1100 entries, which with four queries leave the single-launch
+  plan) and the batches of COMBOS.  A database's restart counts are 1, 3 and its RMAX (100, 64, 32, 16, 16, 8).  The
+  planted queries come from a few source structures whose leading blocks stand in every database (IMPLANTS), so that
+  every world has hits, related entries and an entry with two matches: tests/test_history_cpu.py checks that no
+  reference is vacuous.
+* An OPERATION is a kind and parameters.  run() calls the library, expect() computes the same tuple of arrays from CPU
+  code only: oracle_lib.search (whole rows), matches_lib / polish_lib (restarts, the greedy rule, the polish) and
+  select_lib (the selection passes, the fit, the clustering).  No GPU context is ever a reference.  References are cached
+  per (world, parameters), so a schedule that comes back to a world costs nothing more.
+* The MODEL restates include/satabsearch.h: what is resident, whether and how the batch was searched, the installed fit,
+  the accumulator, the polish-all setting.  It says which calls must succeed and which score matrix they read.
+* schedule(seed) is a greedy cover: walks of WALK_STEPS steps, each on a fresh context, that between them run every
+  ordered pair (kind A directly followed by kind B) the model allows.  Test infrastructure only."""
+import collections
+
+import numpy as np
+
+import cuda_satabsearch_amd as sat
+import matches_lib
+import oracle_lib
+import polish_all_lib as pal
+import polish_lib
+import select_lib
+
+MAXDIM = 111
+WALK_STEPS = 40
+SEED, WALKS, MULTI_WALKS = 1, 24, 12     # schedule(SEED) has WALKS walks, schedule(SEED, True) MULTI_WALKS (test_history_cpu.py)
+
+# ---------------------------------------------------------------- worlds
+RMAX = {"d16": 100, "d32": 64, "d48": 32, "d111": 16, "d150": 16, "d1100": 8}
+# the batches a database is searched with (a batch made from a database stays with it)
+COMBOS = {"d16": ("q1", "q5", "db"), "d32": ("q1", "q5", "q2", "q4", "db"), "d48": ("q2", "q5", "db"),
+          "d111": ("q5",), "d150": ("q2", "q4"), "d1100": ("q4",)}
+FIRST = {"q1": 0, "q5": 5, "q2": 2, "q4": 1, "db": 3}
+BIG = ("d1100",)       # 4400 rows: whole-row references only (no polished search, no search_matches), to keep the CPU side short
+LARGEST, SMALLEST = ("d111", "q5"), ("d16", "q1")        # they differ in entries, queries, largest n1 and largest n2
+
+_cache = {}
+
+
+def _memo(key, make):
+    if key not in _cache:
+        _cache[key] = make()
+    return _cache[key]
+
+
+DB_SEEDS = {"d16": 300}        # chosen so that each of its worlds shows a polish whose winner is not the best restart
+SOURCE_ORDERS = (32, 32, 65, 111, 16)
+# (database: {entry: (order, source)}): the leading block of a source structure stands at these entries, so that the
+# planted queries of every batch have a real hit in every database they are searched with
+IMPLANTS = {"d16": {1: (16, 4), 3: (12, 4)},
+            "d32": {0: (32, 0), 15: (24, 0), 20: (32, 1), 33: (17, 2), 5: (1, 3), 11: (2, 3), 8: (16, 4)},
+            "d48": {5: (32, 0), 3: (20, 0), 2: (48, 2), 9: (33, 3), 7: (32, 1), 13: (6, 3), 11: (16, 4)},
+            "d111": {1: (111, 3), 2: (65, 2), 4: (97, 3)},
+            "d150": {7: (48, 2), 0: (32, 0), 20: (32, 1), 30: (16, 4)},
+            "d1100": {3: (32, 0), 20: (32, 1), 900: (8, 2), 40: (16, 4)}}
+
+
+def motif():
+    """the 8-SSE query: source structure 4 holds it twice"""
+    return _memo("motif", lambda: sat.synth.make_query(8, seed=49))
+
+
+def source():
+    """the structures the planted queries come from; the last one (16 SSEs) is the 8-SSE motif twice in one chain, so
+    that an entry with two non-overlapping matches of it exists"""
+    def make():
+        src = sat.synth.make_db(len(SOURCE_ORDERS), orders=np.array(SOURCE_ORDERS, np.int32), seed=0x50C, sort=False)
+        t, d = src.dense(4)
+        t8, d8, _ = motif()
+        for at in (0, 8):
+            t[at:at + 8, at:at + 8], d[at:at + 8, at:at + 8] = t8, d8
+        ii, jj = np.tril_indices(16)
+        o = int(src.cell_off[4])
+        src.tab[o:o + ii.size], src.dist[o:o + ii.size] = t[ii, jj], d[ii, jj]
+        return src
+    return _memo("source", make)
+
+
+def _orders(name):
+    if name == "d16":
+        o = np.array([7, 16, 1, 12, 9], np.int32)
+    elif name == "d111":
+        o = np.array([60, 111, 65, 72, 97, 61, 88, 111, 64, 100, 66, 80], np.int32)
+    else:
+        n, lo, hi = {"d32": (40, 3, 32), "d48": (18, 6, 48), "d150": (150, 6, 48), "d1100": (1100, 8, 32)}[name]
+        o = np.random.default_rng(len(name) * 1000 + n).integers(lo, hi + 1, n).astype(np.int32)
+    for k, (order, _) in IMPLANTS[name].items():
+        o[k] = order
+    return o
+
+
+def db(name):
+    """the database `name`, unsorted"""
+    def make():
+        o = _orders(name)
+        d = sat.synth.make_db(len(o), orders=o, seed=DB_SEEDS.get(name, 0xD0 + len(o)), sort=False)
+        for k, (order, s) in IMPLANTS[name].items():
+            t, dm = source().dense(s)
+            ii, jj = np.tril_indices(order)
+            at = int(d.cell_off[k])
+            d.tab[at:at + ii.size], d.dist[at:at + ii.size] = t[ii, jj], dm[ii, jj]
+        return d
+    return _memo(("db", name), make)
+
+
+def db_indices(name):
+    """the entries set_queries_from_db takes from database `name`: any order, one repeat"""
+    n = len(db(name))
+    idx = list(IMPLANTS[name])[:4] + [(3 * i + 1) % n for i in range(2)]       # related entries and unrelated ones
+    return np.array(idx + idx[:1], np.int32)
+
+
+def batch(key):
+    """(queries [(tab, dmat, types)], first ordinal) of batch `key`: "q1" one query of 8 SSEs (set_query), "q5" five of
+    3, 16, 17, 40 and 111 SSEs (every class; planted and foreign), "q2" 24 and 32 SSEs, "q4" four of 20..32 SSEs,
+    ("db", name) entries of that database."""
+    def make():
+        src, sy = source(), sat.synth
+        if key == "q1":
+            qs = [motif()]
+        elif key == "q5":
+            qs = [sy.make_query(3, seed=51), sy.planted_query(src, 4, keep=1.0, seed=52), sy.make_query(17, seed=53),
+                  sy.planted_query(src, 2, keep=40 / 65.0, seed=54), sy.planted_query(src, 3, keep=1.0, jitter=0.5, seed=55)]
+        elif key == "q2":
+            qs = [sy.planted_query(src, 1, keep=0.75, seed=56), sy.planted_query(src, 0, keep=1.0, seed=57)]
+        elif key == "q4":
+            qs = [sy.make_query(20, seed=58), sy.planted_query(src, 0, keep=1.0, seed=59), sy.make_query(28, seed=60),
+                  sy.planted_query(src, 1, keep=0.75, seed=61)]
+        else:
+            d = db(key[1])
+            qs = [d.dense(int(i)) + (d.ssetypes(int(i)),) for i in db_indices(key[1])]
+        return qs, FIRST[key if isinstance(key, str) else "db"]
+    return _memo(("batch", key), make)
+
+
+def n1s_of(bkey):
+    return [len(q[2]) for q in batch(bkey)[0]]
+
+
+# ---------------------------------------------------------------- the CPU reference of a world
+Searched = collections.namedtuple("Searched", "lorder r lsoln tops")          # tops > 0: a polished search
+
+
+class WorldRef:
+    """Everything the library may return for (database, batch), from CPU code.  Whole-row scores come from
+    oracle_lib.search, restarts from the chain oracle (shared by every restart count: restart r is one stream)."""
+
+    def __init__(self, dbname, bkey):
+        self.db = db(dbname)
+        self.queries, self.first = batch(bkey)
+        self.n, self.nq = len(self.db), len(self.queries)
+        self.n1s = [len(q[2]) for q in self.queries]
+        self.n1max = max(self.n1s)
+        self.rmax = RMAX[dbname]
+        self.pal = pal.Reference(self.db, self.queries, self.first)
+        self.memo = {}
+
+    def restarts(self, q, e, lorder, r):
+        self.pal.restarts(q, e, lorder, max(r, self.rmax))                       # one run serves every count
+        return self.pal.restarts(q, e, lorder, r)
+
+    def pair(self, q, e):
+        if (q, e) not in self.pal.pairs:
+            self.pal.pairs[(q, e)] = polish_lib.Pair.of(self.db, e, self.queries[q])
+        return self.pal.pairs[(q, e)]
+
+    def plain(self, lorder, r):
+        """(scores [nq, n], maps [nq, n, 111]) of the plain search"""
+        def make():
+            out = [oracle_lib.search(self.db, *self.queries[q], lorder, True, r, query_ordinal=self.first + q)[:2]
+                   for q in range(self.nq)]
+            return np.stack([o[0] for o in out]), np.stack([o[1] for o in out])
+        return _memo2(self.memo, ("plain", lorder, r), make)
+
+    def polished(self, lorder, r, tops):
+        """(scores, base, maps) of the polished search"""
+        def make():
+            for q in range(self.nq):
+                for e in range(self.n):
+                    self.restarts(q, e, lorder, r)
+            return self.pal.all_rows(lorder, r, tops)
+        return _memo2(self.memo, ("polished", lorder, r, tops), make)
+
+    def matrix(self, sd):
+        """(scores, maps or None): what the result calls read after the search `sd`"""
+        if sd.tops:
+            sc, _, mp = self.polished(sd.lorder, sd.r, sd.tops)
+        else:
+            sc, mp = self.plain(sd.lorder, sd.r)
+        return sc, (mp if sd.lsoln else None)
+
+    def fits(self, sd, fit):
+        """the sat_fit records of the model's fit descriptor: None, ("fit", censor) or ("set", name)"""
+        if fit is None:
+            return None
+        if fit[0] == "fit":
+            return self.select(sd, None).fit(fit[1])
+        rec = np.zeros(self.nq, select_lib._FIT_DTYPE)
+        for q in range(self.nq):
+            if q == 0 or q < self.nq - 1:                                        # the last of several keeps the built-ins
+                rec[q]["a"], rec[q]["b"], rec[q]["fitted"] = 2.0 + 0.5 * q, 0.75, 1
+        return rec
+
+    def select(self, sd, fit):
+        def make():
+            sc, mp = self.matrix(sd)
+            return select_lib.Reference(sc, self.n1s, self.db.orders, self.fits(sd, fit), mp)
+        return _memo2(self.memo, ("select", sd, fit), make)
+
+    def pcut(self, sd, fit, frac, nodes=None):
+        """a cutoff from the reference's own p-values: the one `frac` of the way up its distinct values (with `nodes`,
+        the queries' nodes: those of the rows that are edges, not a structure against itself)"""
+        ref = self.select(sd, fit)
+        rows = [ref.rows(q) for q in range(self.nq)]
+        if nodes is not None:
+            rows = [r[r["entry"] != nodes[q]] for q, r in enumerate(rows)]
+        pv = np.unique(np.concatenate([r["pvalue"] for r in rows]))
+        return float(pv[int(frac * (len(pv) - 1))])
+
+    def pairs(self, count):
+        """a list of `count` (query, entry) pairs: any order, repeats"""
+        rng = np.random.default_rng(count * 7919 + self.n * 31 + self.nq)
+        return rng.integers(0, self.nq, count).astype(np.int32), rng.integers(0, self.n, count).astype(np.int32)
+
+    def match_rows(self, q, e, lorder, r, m):
+        """(counts [P], scores [P, M], restarts [P, M], maps [P, M, n1max]) of the pairs, by the greedy rule"""
+        counts = np.zeros(len(q), np.int32)
+        scores, rs = np.zeros((len(q), m), np.int32), np.zeros((len(q), m), np.int32)
+        maps = np.full((len(q), m, self.n1max), -1, np.int32)
+        for p, (qi, ei) in enumerate(zip(q.tolist(), e.tolist())):
+            c, sc, rr, mp = matches_lib.select_matches(*self.restarts(qi, ei, lorder, r), m)
+            counts[p], scores[p], rs[p] = c, sc, rr
+            maps[p, :, :self.n1s[qi]] = mp[:, :self.n1s[qi]]
+        return counts, scores, rs, maps
+
+    def polish_rows(self, q, e, lorder, r, tops):
+        """(scores, base, restarts, moves [P], maps [P, n1max]) of the pairs"""
+        out = [np.zeros(len(q), np.int32) for _ in range(4)] + [np.full((len(q), self.n1max), -1, np.int32)]
+        for p, (qi, ei) in enumerate(zip(q.tolist(), e.tolist())):
+            got = _memo2(self.memo, ("polish", qi, ei, lorder, r, tops), lambda: polish_lib.polish_ranked(
+                self.pair(qi, ei), *self.restarts(qi, ei, lorder, r), lorder, tops))
+            for k in range(4):
+                out[k][p] = got[k]
+            out[4][p, :self.n1s[qi]] = np.asarray(got[4])[:self.n1s[qi]]
+        return tuple(out)
+
+    def refine(self, lorder, r, cand, big_r, k, lsoln, tops=0):
+        """the ranking rule of the refine calls restated: each query's best C rows of the plain search at r in best-k
+        order, their stage-2 scores (the plain search at R, or its polish), the best K by (score descending, entry
+        ascending) with the built-in statistics of the stage-2 score.  (hits [nq, K], maps [nq, K, 111], stage-1 scores,
+        scores before the polish)"""
+        c = min(cand, self.n)
+        kk = min(k, c)
+        stage1 = self.plain(lorder, r)[0]
+        hits = np.zeros((self.nq, kk), select_lib._HIT_DTYPE)
+        maps = np.full((self.nq, kk, MAXDIM), -1, np.int32)
+        first, base = np.zeros((self.nq, kk), np.int32), np.zeros((self.nq, kk), np.int32)
+        for q in range(self.nq):
+            cands = np.argsort(-stage1[q].astype(np.int64), kind="stable")[:c]
+            if tops:
+                qq = np.full(len(cands), q, np.int32)
+                s2, b2, _, _, m2 = self.polish_rows(qq, cands.astype(np.int32), lorder, big_r, tops)
+            else:
+                sc, mp = self.plain(lorder, big_r)
+                s2, b2, m2 = sc[q, cands], sc[q, cands], mp[q, cands]
+            order = sorted(range(len(cands)), key=lambda i: (-int(s2[i]), int(cands[i])))[:kk]
+            for row, i in enumerate(order):
+                e = int(cands[i])
+                norm2 = 2.0 * int(s2[i]) / float(self.n1s[q] + int(self.db.orders[e]))
+                hits[q, row] = (e, s2[i], norm2) + select_lib.builtin_stats(norm2)
+                maps[q, row, :self.n1s[q]] = m2[i][:self.n1s[q]]
+                first[q, row], base[q, row] = stage1[q, e], b2[i]
+        return hits, (maps if lsoln else None), first, base
+
+
+def _memo2(memo, key, make):
+    if key not in memo:
+        memo[key] = make()
+    return memo[key]
+
+
+def world_ref(dbname, bkey):
+    return _memo(("ref", dbname, bkey), lambda: WorldRef(dbname, bkey))
+
+
+# ---------------------------------------------------------------- operations
+Op = collections.namedtuple("Op", "kind args")
+
+
+def op(kind, **args):
+    return Op(kind, tuple(sorted(args.items())))
+
+
+MOVES = ("upload", "upload_dense", "set_queries", "set_query", "set_queries_from_db", "set_polish_all", "polish_all_off",
+         "cluster_begin", "cluster_add", "cluster_end")                          # no data comes back
+SEARCHES = ("search", "search_async_results", "upload_search", "search_matches", "search_refine", "search_refine_polish")
+PAIR_SEARCHES = ("search_pairs", "search_pairs_matches", "search_pairs_polish")
+RESULTS = ("results", "results_base", "topk_hits", "hits_cutoff", "score_histogram", "fit_statistics", "set_statistics")
+KINDS = MOVES + SEARCHES + PAIR_SEARCHES + RESULTS + ("cluster_labels",)
+DATA_KINDS = tuple(k for k in KINDS if k not in MOVES)
+# what sat_multi has (search_topk and search_fit stand for topk_hits and fit_statistics: they search again, the same way)
+MULTI_KINDS = ("upload", "set_queries", "set_queries_from_db", "set_polish_all", "polish_all_off", "cluster_begin", "cluster_add",
+               "search", "search_matches", "search_refine", "search_refine_polish", "search_pairs_matches", "search_pairs_polish",
+               "topk_hits", "hits_cutoff", "score_histogram", "fit_statistics", "set_statistics", "cluster_labels")
+# the counts a kind has of its own, smallest and largest
+COUNTS = {"pairs": (1, 7, 30), "m": (1, 3, 8), "tops": (1, 3, 8), "k": (1, 3, 10), "cand": (4, 12)}
+
+
+class Model:
+    """The documented state of a context (include/satabsearch.h), restated."""
+
+    def __init__(self, multi=False):
+        self.multi = multi
+        self.db = self.batch = None          # names of the resident database and the current batch
+        self.searched = None                 # Searched of the search the result buffers hold, None: not for this batch
+        self.fit = None                      # the installed fit: None, ("fit", censor), ("set", name)
+        self.cluster = None                  # the accumulator: [nodes, [(world, Searched, fit, frac, query nodes)]]
+        self.tops = 0                        # sat_polish_all_set
+
+    def legal(self, kind):
+        """must the call succeed now?"""
+        if self.multi and kind not in MULTI_KINDS:
+            return False
+        if kind in ("upload", "upload_dense", "set_queries", "set_query", "set_polish_all", "polish_all_off"):
+            return True
+        if kind in ("set_queries_from_db", "cluster_begin"):
+            return self.db is not None
+        if kind == "upload_search":
+            return self.batch is not None
+        if kind in SEARCHES or kind in PAIR_SEARCHES:
+            return self.db is not None and self.batch is not None
+        if kind in ("cluster_labels", "cluster_end"):
+            return self.cluster is not None
+        if kind == "cluster_add":
+            return self.cluster is not None and self.searched is not None
+        if kind == "results_base":
+            return self.searched is not None and self.searched.tops > 0
+        return self.searched is not None                                          # the other result calls
+
+    def flags(self):
+        sd = self.searched
+        return (self.db is not None, self.batch is not None, sd is not None, bool(sd and sd.lsoln), bool(sd and sd.tops),
+                self.fit is not None, self.cluster is not None, self.tops > 0)
+
+    def world(self):
+        return world_ref(self.db, self.batch)
+
+    def apply(self, o):
+        a, kind = dict(o.args), o.kind
+        if kind in ("upload", "upload_dense", "upload_search"):
+            self.db, self.searched, self.fit, self.cluster = a["db"], None, None, None
+        if kind in ("set_queries", "set_query", "set_queries_from_db"):
+            self.batch, self.searched, self.fit = a["batch"], None, None
+        if kind in ("set_polish_all", "polish_all_off"):
+            self.tops = a["tops"] if kind == "set_polish_all" else 0
+        if kind in ("search", "search_async_results", "upload_search"):
+            self.searched, self.fit = Searched(a["lorder"], a["r"], a["lsoln"], self.tops), None
+        if kind in ("search_matches", "search_refine", "search_refine_polish"):      # match 0 / stage 1: a plain search
+            self.searched, self.fit = Searched(a["lorder"], a["r"], False, 0), None
+        if kind == "topk_hits" and self.multi:
+            self.fit = None                                                       # search_topk searches again
+        if kind == "fit_statistics":
+            self.fit = ("fit", a["censor"])
+        if kind == "set_statistics":
+            self.fit = None if a["fit"] == "none" else ("set", a["fit"])
+        if kind == "cluster_begin":
+            self.cluster = [len(db(self.db)), []]
+        if kind == "cluster_add":
+            self.cluster[1].append((self.db, self.batch, self.searched, self.fit, a["frac"], self.query_nodes()))
+        if kind == "cluster_end":
+            self.cluster = None
+
+    def query_nodes(self):
+        """query q's node: its entry for a batch made of the database, any node otherwise"""
+        nodes = self.cluster[0] if self.cluster else len(db(self.db))
+        if not isinstance(self.batch, str):
+            return tuple(int(i) for i in db_indices(self.batch[1]))
+        return tuple((7 * q + 2) % nodes for q in range(len(n1s_of(self.batch))))
+
+
+# ---- expect: the tuple of arrays an operation must return, from the state BEFORE it
+def _flat_rows(rows, maps, counts):
+    out = [np.asarray(counts, np.int32), np.concatenate(rows)]
+    if maps is not None:
+        out.append(np.concatenate(maps).reshape(-1, MAXDIM))
+    return tuple(out)
+
+
+def _expect(o, m):
+    a, kind = dict(o.args), o.kind
+    w = world_ref(a["db"], m.batch) if kind == "upload_search" else m.world() if kind != "cluster_labels" else None
+    sd = m.searched
+    if kind in ("search", "search_async_results", "upload_search"):
+        sc, mp = w.matrix(Searched(a["lorder"], a["r"], a["lsoln"], m.tops))
+        return (sc,) if mp is None else (sc, mp)
+    if kind == "results":
+        sc, mp = w.matrix(sd)
+        return (sc,) if not a["lsoln"] else (sc, mp)
+    if kind == "results_base":
+        return (w.polished(sd.lorder, sd.r, sd.tops)[1],)
+    if kind in ("search_matches", "search_pairs_matches"):
+        if kind == "search_matches":
+            q, e = np.divmod(np.arange(w.nq * w.n, dtype=np.int32), np.int32(w.n))
+        else:
+            q, e = w.pairs(a["pairs"])
+        c, sc, rs, mp = w.match_rows(q, e, a["lorder"], a["r"], a["m"])
+        return (c, sc, rs, mp) if a["maps"] else (c, sc, rs)
+    if kind == "search_pairs":
+        q, e = w.pairs(a["pairs"])
+        sc, mp = w.plain(a["lorder"], a["r"])
+        return (sc[q, e], mp[q, e]) if a["lsoln"] else (sc[q, e],)
+    if kind == "search_pairs_polish":
+        return w.polish_rows(*w.pairs(a["pairs"]), a["lorder"], a["r"], a["tops"])
+    if kind in ("search_refine", "search_refine_polish"):
+        hits, mp, first, base = w.refine(a["lorder"], a["r"], a["cand"], a["big_r"], a["k"], a["lsoln"], a.get("tops", 0))
+        out = (hits, first) + ((base,) if kind == "search_refine_polish" else ())
+        return out + ((mp,) if a["lsoln"] else ())
+    if kind == "topk_hits":
+        rows, mp = w.select(sd, None if m.multi else m.fit).topk(a["k"])      # search_topk searches again: the fit is gone
+        return (rows, mp) if a["maps"] else (rows,)
+    if kind == "hits_cutoff":
+        rows, mp, counts = w.select(sd, m.fit).cutoff(w.pcut(sd, m.fit, a["frac"]), a["k"])
+        return _flat_rows(rows, mp if a["maps"] else None, counts)
+    if kind == "score_histogram":
+        return w.select(sd, None).histogram()
+    if kind == "fit_statistics":                                                  # the fit, then the rows it gives
+        fit = ("fit", a["censor"])
+        rows, _, counts = w.select(sd, fit).cutoff(w.pcut(sd, fit, 0.5), None)
+        return (w.fits(sd, fit),) + _flat_rows(rows, None, counts)
+    if kind == "set_statistics":
+        return (w.select(sd, None if a["fit"] == "none" else ("set", a["fit"])).topk(3)[0],)
+    if kind == "cluster_labels":
+        nodes, adds = m.cluster
+        ea, eb = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]
+        for dbname, bkey, asd, afit, frac, qnodes in adds:
+            aw = world_ref(dbname, bkey)
+            ref = aw.select(asd, afit)
+            cut = aw.pcut(asd, afit, frac, qnodes)
+            for q in range(aw.nq):
+                ents = ref.rows(q)["entry"][ref.rows(q)["pvalue"] <= cut].astype(np.int64)
+                ea.append(np.full(len(ents), qnodes[q], np.int64))
+                eb.append(ents)
+        ea, eb = np.concatenate(ea), np.concatenate(eb)
+        keep = ea != eb
+        ea, eb = ea[keep], eb[keep]
+        deg = (np.bincount(ea, minlength=nodes) + np.bincount(eb, minlength=nodes)).astype(np.int32)
+        return select_lib.components(nodes, ea, eb), deg, np.array([len(ea)], np.int64)
+    raise ValueError(kind)
+
+
+def _state_key(o, m):
+    cl = None if o.kind != "cluster_labels" else (m.cluster[0], tuple(m.cluster[1]))
+    return (o, m.db, m.batch, m.searched, m.fit, m.tops, cl)
+
+
+def expect(o, m):
+    """the arrays operation `o` must return on a context in state `m` (cached)"""
+    return _memo(("expect", _state_key(o, m)), lambda: _expect(o, m))
+
+
+# ---- run: the same tuple from the library
+def _upload_dense(s, d):
+    pitch = int(d.orders.max())
+    tabs, dmats = np.zeros((len(d), pitch, pitch), np.uint8), np.zeros((len(d), pitch, pitch), np.float32)
+    for e in range(len(d)):
+        tabs[e], dmats[e] = d.dense(e, pitch)
+    s.upload_dense(d.orders, tabs, dmats, pitch)
+
+
+def _rows_of(s, m, got, maps):
+    rows, mp = got if maps else (got, None)
+    return _flat_rows(rows, mp, [len(r) for r in rows])
+
+
+def run(s, o, m):
+    """run operation `o` on searcher `s` (a Searcher, or a MultiSearcher when m.multi) whose state is `m`"""
+    a, kind = dict(o.args), o.kind
+    sd = m.searched
+    if kind in ("upload", "upload_dense"):
+        return s.upload(db(a["db"])) if kind == "upload" else _upload_dense(s, db(a["db"]))
+    if kind == "set_query":
+        return s.set_query(*batch(a["batch"])[0][0], FIRST["q1"])
+    if kind == "set_queries":
+        return s.set_queries(*batch(a["batch"]))
+    if kind == "set_queries_from_db":
+        return s.set_queries_from_db(db_indices(a["batch"][1]), FIRST["db"])
+    if kind in ("set_polish_all", "polish_all_off"):
+        return s.set_polish_all(a.get("tops", 0))
+    if kind == "cluster_begin":
+        return s.cluster_begin()
+    if kind == "cluster_end":
+        return s.cluster_end()
+    if kind == "cluster_add":
+        return s.cluster_add(m.world().pcut(sd, m.fit, a["frac"], m.query_nodes()), m.query_nodes())
+    if kind == "cluster_labels":
+        labels, deg, edges = s.cluster_labels()
+        return labels, deg, np.array([edges], np.int64)
+    w = world_ref(a["db"], m.batch) if kind == "upload_search" else m.world()
+    shape = (w.nq, w.n)
+    if kind in ("search", "search_async_results", "upload_search", "results"):
+        if kind == "search":
+            sc, mp = s.search(a["lorder"], a["lsoln"], a["r"])[:2]
+        else:
+            if kind == "search_async_results":
+                s.search_async(a["lorder"], a["lsoln"], a["r"])
+            elif kind == "upload_search":
+                s.upload_search(db(a["db"]), a["lorder"], a["lsoln"], a["r"])
+            sc, mp = s.results(a["lsoln"])
+        return (sc.reshape(shape),) if mp is None else (sc.reshape(shape), mp.reshape(shape + (MAXDIM,)))
+    if kind == "results_base":
+        return (s.results_base().reshape(shape),)
+    if kind == "search_matches":
+        c, sc, rs, mp = s.search_matches(a["m"], a["lorder"], a["r"], a["maps"])[:4]
+        flat = (c.ravel(), sc.reshape(-1, a["m"]), rs.reshape(-1, a["m"]))
+        return flat + ((mp.reshape(-1, a["m"], w.n1max),) if a["maps"] else ())
+    if kind == "search_pairs":
+        sc, mp = s.search_pairs(*w.pairs(a["pairs"]), a["lorder"], a["lsoln"], a["r"])
+        return (sc, mp) if a["lsoln"] else (sc,)
+    if kind == "search_pairs_matches":
+        got = s.search_pairs_matches(*w.pairs(a["pairs"]), a["m"], a["lorder"], a["r"], a["maps"])
+        return got[:4] if a["maps"] else got[:3]
+    if kind == "search_pairs_polish":
+        return s.search_pairs_polish(*w.pairs(a["pairs"]), a["tops"], a["lorder"], a["r"])[:5]
+    if kind == "search_refine":
+        hits, mp, first = s.search_refine(a["k"], a["cand"], a["big_r"], a["lorder"], a["lsoln"], a["r"])
+        return (hits, first) + ((mp,) if a["lsoln"] else ())
+    if kind == "search_refine_polish":
+        hits, mp, first, base = s.search_refine_polish(a["k"], a["cand"], a["big_r"], a["tops"], a["lorder"], a["lsoln"], a["r"])
+        return (hits, first, base) + ((mp,) if a["lsoln"] else ())
+    if kind == "topk_hits":
+        if m.multi:
+            rows, mp = s.search_topk(a["k"], sd.lorder, sd.lsoln, sd.r)[:2]
+            return (rows, mp) if a["maps"] else (rows,)
+        got = s.topk_hits(a["k"], a["maps"])
+        return got if a["maps"] else (got,)
+    if kind == "hits_cutoff":
+        return _rows_of(s, m, s.hits_cutoff(w.pcut(sd, m.fit, a["frac"]), a["k"], a["maps"]), a["maps"])
+    if kind == "score_histogram":
+        return s.score_histogram()
+    if kind == "fit_statistics":
+        fit = ("fit", a["censor"])
+        fits = s.search_fit(a["censor"], sd.lorder, sd.lsoln, sd.r)[0] if m.multi else s.fit_statistics(a["censor"])
+        return (fits,) + _rows_of(s, m, s.hits_cutoff(w.pcut(sd, fit, 0.5)), False)
+    if kind == "set_statistics":
+        s.set_statistics(None if a["fit"] == "none" else w.fits(sd, ("set", a["fit"])))
+        if m.multi:
+            return (np.stack([r[:3] for r in s.hits_cutoff(1.0, 3)]),)
+        return (s.topk_hits(3),)
+    raise ValueError(kind)
+
+
+def same(got, want):
+    """the first difference between two tuples of arrays as text, or None: exact, byte for byte"""
+    if len(got) != len(want):
+        return "%d arrays, the reference has %d" % (len(got), len(want))
+    for i, (g, w) in enumerate(zip(got, want)):
+        g, w = np.asarray(g), np.asarray(w)
+        if g.shape != w.shape or g.dtype != w.dtype:
+            return "array %d is %s %s, the reference %s %s" % (i, g.dtype, g.shape, w.dtype, w.shape)
+        if g.tobytes() != w.tobytes():
+            flat_g, flat_w = g.reshape(-1), w.reshape(-1)
+            bad = [k for k in range(len(flat_g)) if flat_g[k].tobytes() != flat_w[k].tobytes()]
+            return "array %d differs at %d of %d places, first flat index %d: got %s, the reference %s" % (
+                i, len(bad), len(flat_g), bad[0], flat_g[bad[0]], flat_w[bad[0]])
+    return None
+
+
+# ---------------------------------------------------------------- drawing an operation's parameters
+def _pick(rng, values, avoid=None):
+    values = [v for v in values if v != avoid] or list(values)
+    return values[int(rng.integers(len(values)))]
+
+
+def draw(kind, m, rng, size=None, last=None):
+    """operation of `kind` with parameters legal in state `m`; size "lo" / "hi" asks for the smallest / largest counts,
+    `last` ({name: count}, updated) for counts that differ from the ones used before"""
+    def count(name):
+        c = COUNTS[name]
+        v = c[0] if size == "lo" else c[-1] if size == "hi" else _pick(rng, c, (last or {}).get(name))
+        if last is not None:
+            last[name] = v
+        return v
+
+    def restarts():
+        return RMAX[m.db] if size == "hi" else 1 if size == "lo" else _pick(rng, (1, 3, RMAX[m.db]))
+
+    flag = lambda: bool(rng.integers(2))
+    if kind in ("upload", "upload_dense", "upload_search"):
+        fits = [d for d in COMBOS if m.batch is None or (m.batch in COMBOS[d] if isinstance(m.batch, str) else m.batch[1] == d)]
+        if kind == "upload_dense":
+            fits = [d for d in fits if d not in ("d150", "d1100")]
+        if m.tops:
+            fits = [d for d in fits if d not in BIG]
+        name = _pick(rng, fits, m.db)
+        if kind != "upload_search":
+            return op(kind, db=name)
+        return op(kind, db=name, lorder=flag(), lsoln=flag(), r=_pick(rng, (1, 3, RMAX[name])))
+    if kind == "set_query":
+        return op(kind, batch="q1") if m.db is None or "q1" in COMBOS[m.db] else None
+    if kind == "set_queries":
+        fits = [b for b in ("q5", "q2", "q4") if m.db is None or b in COMBOS[m.db]]
+        return op(kind, batch=_pick(rng, fits, m.batch))
+    if kind == "set_queries_from_db":
+        return op(kind, batch=("db", m.db)) if "db" in COMBOS[m.db] else None
+    if kind in ("set_polish_all", "search_matches") and m.db in BIG:
+        return None
+    if kind == "set_polish_all":
+        return op(kind, tops=count("tops"))
+    if kind in ("polish_all_off", "cluster_begin", "cluster_end", "cluster_labels", "score_histogram", "results_base"):
+        return op(kind)
+    if kind == "cluster_add":
+        return op(kind, frac=_pick(rng, (0.1, 0.4)))
+    if kind in ("search", "search_async_results"):
+        return op(kind, lorder=flag(), lsoln=flag(), r=restarts())
+    if kind == "search_matches":
+        return op(kind, lorder=flag(), r=restarts(), m=count("m"), maps=flag())
+    if kind == "search_pairs":
+        return op(kind, lorder=flag(), r=restarts(), pairs=count("pairs"), lsoln=flag())
+    if kind == "search_pairs_matches":
+        return op(kind, lorder=flag(), r=restarts(), pairs=count("pairs"), m=count("m"), maps=flag())
+    if kind == "search_pairs_polish":
+        return op(kind, lorder=flag(), r=restarts(), pairs=count("pairs"), tops=count("tops"))
+    if kind in ("search_refine", "search_refine_polish"):
+        more = {"tops": count("tops")} if kind == "search_refine_polish" else {}
+        return op(kind, lorder=flag(), r=_pick(rng, (1, 3)), big_r=RMAX[m.db], cand=count("cand"), k=min(count("k"), 4),
+                  lsoln=flag(), **more)
+    if kind == "results":
+        return op(kind, lsoln=m.searched.lsoln and flag())
+    if kind == "topk_hits":
+        return op(kind, k=count("k"), maps=m.searched.lsoln and flag())
+    if kind == "hits_cutoff":
+        return op(kind, frac=_pick(rng, (0.15, 0.6)), k=count("k") if size else _pick(rng, (None, 2)), maps=m.searched.lsoln and flag())
+    if kind == "fit_statistics":
+        return op(kind, censor=_pick(rng, (0.0, 0.1)))
+    if kind == "set_statistics":
+        return op(kind, fit=_pick(rng, ("ab", "none")))
+    raise ValueError(kind)
+
+
+# ---------------------------------------------------------------- which pairs of kinds the model allows
+def _successors(m, kinds):
+    """(kind, state after a representative operation of it) for every kind legal in `m`: legality depends on the flags
+    only, and of an operation's parameters only lsoln moves a flag"""
+    for kind in kinds:
+        if m.legal(kind):
+            for lsoln in ((False, True) if kind in ("search", "search_async_results", "upload_search") else (False,)):
+                nxt = _clone(m)
+                nxt.apply(_representative(kind, lsoln))
+                yield kind, nxt
+
+
+def allowed_pairs(multi=False):
+    """every (A, B): B is legal in some reachable state right after A, found by walking the model over its flags"""
+    def make():
+        kinds = MULTI_KINDS if multi else KINDS
+        start = Model(multi)
+        seen, todo, pairs = {start.flags()}, [start], set()
+        while todo:
+            for kind, nxt in _successors(todo.pop(), kinds):
+                pairs.update((kind, b) for b in kinds if nxt.legal(b))
+                if nxt.flags() not in seen:
+                    seen.add(nxt.flags())
+                    todo.append(nxt)
+        return frozenset(pairs)
+    return _memo(("allowed", multi), make)
+
+
+def _route(m, last, todo, kinds):
+    """the first kind of a shortest run of operations from state `m` that ends in a pair of `todo`, or None"""
+    seen, level = {(last, m.flags())}, [(None, last, m)]
+    while level:
+        nxt_level = []
+        for first, prev, state in level:
+            for kind, nxt in _successors(state, kinds):
+                if (prev, kind) in todo:
+                    return first or kind
+                if (kind, nxt.flags()) not in seen:
+                    seen.add((kind, nxt.flags()))
+                    nxt_level.append((first or kind, kind, nxt))
+        level = nxt_level
+    return None
+
+
+def _clone(m):
+    c = Model(m.multi)
+    c.db, c.batch, c.searched, c.fit, c.tops = m.db, m.batch, m.searched, m.fit, m.tops
+    c.cluster = None if m.cluster is None else [m.cluster[0], list(m.cluster[1])]
+    return c
+
+
+def _representative(kind, lsoln):
+    return op(kind, db="d16", batch="q1", lorder=True, lsoln=lsoln, r=1, tops=3, censor=0.0, fit="ab", frac=0.1)
+
+
+# ---------------------------------------------------------------- schedules
+def schedule(seed, multi=False):
+    """walks (lists of operations, each for a fresh context) that between them follow every allowed pair of kinds"""
+    def make():
+        rng = np.random.default_rng(seed)
+        kinds = MULTI_KINDS if multi else KINDS
+        todo = set(allowed_pairs(multi))
+        walks = []
+        while todo:
+            before = len(todo)
+            m, walk, last, counts = Model(multi), [], None, {}
+            while len(walk) < WALK_STEPS:
+                cands = [k for k in kinds if m.legal(k)]
+                # a pair not yet followed - of those the kind with the most unfollowed pairs behind it; else toward one
+                fresh = [k for k in cands if (last, k) in todo]
+                weight = [sum(1 for p in todo if p[0] == k) for k in fresh]
+                best = [k for k, x in zip(fresh, weight) if x == max(weight)]
+                toward = [] if fresh else [_route(m, last, todo, kinds)]
+                o = None
+                for kind in rng.permutation(best).tolist() + rng.permutation(fresh).tolist() + toward + rng.permutation(cands).tolist():
+                    o = draw(kind, m, rng, None, counts) if kind else None
+                    if o is not None:
+                        break
+                todo.discard((last, o.kind))
+                walk.append(o)
+                m.apply(o)
+                last = o.kind
+            walks.append(walk)
+            if len(todo) == before:
+                raise AssertionError("the cover does not advance: %s" % sorted(todo)[:5])
+        return walks + [_nodes_walk(multi)]
+    return _memo(("schedule", seed, multi), make)
+
+
+def _set_batch(dbname, b):
+    if b == "q1":
+        return op("set_query", batch=b)
+    return op("set_queries_from_db", batch=("db", dbname)) if b == "db" else op("set_queries", batch=b)
+
+
+def _nodes_walk(multi):
+    """the accumulator over 40, 5, 18, 5 and 12 nodes on one context, each filled from two query batches: the greedy
+    walks begin too few accumulators to move the node count up and down twice"""
+    ops = []
+    for dbname, first, second in (("d32", "q5", "db"), ("d16", "db", "q5"), ("d48", "q2", "db"), ("d16", "q1", "db"),
+                                  ("d111", "q5", "q5")):
+        if multi:
+            first, second = ("q5" if b == "q1" else b for b in (first, second))
+        ops += [op("upload", db=dbname), _set_batch(dbname, first), op("search", lorder=True, lsoln=False, r=3), op("cluster_begin"),
+                op("cluster_add", frac=0.4), _set_batch(dbname, second), op("search", lorder=False, lsoln=False, r=RMAX[dbname]),
+                op("cluster_add", frac=0.1), op("cluster_labels")]
+    return ops
+
+
+def grow_shrink_grow(kind, multi=False):
+    """scenario 1: `kind` at its largest world and counts, another family at the smallest world, `kind` at its smallest
+    world and counts, then at the largest again - with whatever the model needs in front of each"""
+    rng = np.random.default_rng(len(kind))
+    other = "search_matches" if "polish" in kind or kind == "results_base" else "search_pairs_polish"
+    ops, m = [], Model(multi)
+
+    def add(o):
+        ops.append(o)
+        m.apply(o)
+
+    def goto(world, size, target):
+        dbname, b = world
+        if multi and b == "q1":
+            b = "q2" if dbname != "d16" else "db"
+        if target == "results_base":
+            add(op("set_polish_all", tops=COUNTS["tops"][0 if size == "lo" else -1]))
+        elif m.tops:
+            add(op("polish_all_off"))
+        if target != "upload_search":
+            add(op("upload", db=dbname))
+        add(_set_batch(dbname, b))
+        if target in RESULTS or target == "cluster_labels":
+            add(op("search", lorder=True, lsoln=True, r=RMAX[dbname] if size == "hi" else 3))
+        if target == "cluster_labels":
+            add(op("cluster_begin"))
+            add(op("cluster_add", frac=0.4))
+
+    largest = None
+    for world, size, what in ((LARGEST, "hi", kind), (SMALLEST, "lo", other), (SMALLEST, "lo", kind), (LARGEST, "hi", kind)):
+        goto(world, size, what)
+        if what == "upload_search":
+            add(op(what, db=world[0], lorder=True, lsoln=size == "hi", r=RMAX[world[0]] if size == "hi" else 1))
+        else:
+            add(largest if size == "hi" and largest else draw(what, m, rng, size))
+        largest = largest or ops[-1]
+    return ops
+
+
+def shard_sequence():
+    """150 -> 12 -> 40 -> 5 -> 150 entries under one two-query batch: sat_multi's padded rows and the per-shard floors go
+    up and down while the gathers' buffers only grow"""
+    return [op("upload", db="d150"), op("set_queries", batch="q2"), op("search", lorder=True, lsoln=True, r=16),
+            op("topk_hits", k=10, maps=True), op("search_matches", lorder=True, r=3, m=3, maps=True),
+            op("upload", db="d111"), op("search", lorder=False, lsoln=True, r=3), op("topk_hits", k=3, maps=True),
+            op("search_pairs_polish", lorder=True, r=16, pairs=7, tops=3),
+            op("upload", db="d32"), op("search_matches", lorder=False, r=64, m=8, maps=True),
+            op("search", lorder=True, lsoln=True, r=64), op("hits_cutoff", frac=0.6, k=None, maps=True), op("score_histogram"),
+            op("upload", db="d16"), op("search", lorder=True, lsoln=True, r=100), op("fit_statistics", censor=0.0),
+            op("upload", db="d150"), op("search", lorder=True, lsoln=True, r=1), op("topk_hits", k=3, maps=True),
+            op("search_refine", lorder=True, r=1, big_r=16, cand=12, k=3, lsoln=True)]
+
+
+def dimensions(o, m):
+    """the sizes operation `o` works at in state `m` (after it): for the rise-and-fall conditions"""
+    a, out = dict(o.args), {}
+    if m.db is not None:
+        d = db(m.db)
+        out["entries"], out["n2"] = len(d), int(d.orders.max())
+    if m.batch is not None:
+        n1s = n1s_of(m.batch)
+        out["queries"], out["n1"] = len(n1s), max(n1s)
+    for name in ("pairs", "m", "tops", "k"):
+        if name in a and a[name] is not None:
+            out[name] = a[name]
+    if o.kind == "cluster_begin":
+        out["nodes"] = m.cluster[0]
+    return out
+
+
+def rises_and_falls(walk, multi=False):
+    """{dimension: (rises, falls)} along one walk"""
+    m, last, out = Model(multi), {}, collections.defaultdict(lambda: [0, 0])
+    for o in walk:
+        m.apply(o)
+        for name, v in dimensions(o, m).items():
+            if name in last and v != last[name]:
+                out[name][0 if v > last[name] else 1] += 1
+            last[name] = v
+    return {k: tuple(v) for k, v in out.items()}

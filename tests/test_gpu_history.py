@@ -1,0 +1,145 @@
+"""What a context carries from one call to the next (-m gpu): sequences of calls of every family on ONE Searcher (or
+MultiSearcher), each result compared byte for byte with its CPU reference (tests/history_lib.py: oracle_lib, matches_lib,
+polish_lib, select_lib - never another GPU context).  1. every data-returning kind at its largest world, another family at
+the smallest, the kind at its smallest, then at the largest again; 2. seeded walks that between them follow every ordered
+pair of kinds the model of the documented state allows, with entries, queries, n1, n2, pairs, M, T, k and nodes going up
+and down on one context; 3. at every step of every walk every result call the model says is not available returns its
+documented error and changes nothing; 4. walks under a 16 KB scratch budget and a small selection-key budget, which make
+the launch cuts depend on what the buffers were sized for before; 5. the same on 2 and 3 shards on device 0, with shard
+sizes that move the padded rows up and down."""
+import numpy as np
+import pytest
+
+import cuda_satabsearch_amd as sat
+import history_lib as hl
+
+pytestmark = pytest.mark.gpu
+
+
+def text(o):
+    return "%s(%s)" % (o.kind, ", ".join("%s=%s" % kv for kv in o.args))
+
+
+def follow(s, ops, multi=False, after_step=None):
+    """run `ops` on `s`, comparing every data-returning step with its reference; returns the number compared"""
+    m, compared = hl.Model(multi), 0
+    for step, o in enumerate(ops):
+        assert m.legal(o.kind), "step %d: the model does not allow %s" % (step, text(o))
+        got = hl.run(s, o, m)
+        if o.kind in hl.DATA_KINDS:
+            diff = hl.same(got, hl.expect(o, m))
+            assert diff is None, "step %d, %s on (%s, %s) after %s: %s" % (
+                step, text(o), dict(o.args).get("db", m.db), m.batch, [text(x) for x in ops[max(0, step - 4):step]], diff)
+            compared += 1
+        m.apply(o)
+        if after_step:
+            after_step(s, m)
+    return compared
+
+
+def data_steps(ops):
+    return sum(1 for o in ops if o.kind in hl.DATA_KINDS)
+
+
+def shards(count):
+    return sat.MultiSearcher(count, devices=[0] * count)
+
+
+# ---------------------------------------------------------------- 1. grow, shrink, grow
+@pytest.mark.parametrize("kind", hl.DATA_KINDS)
+def test_grow_shrink_grow(kind):
+    ops = hl.grow_shrink_grow(kind)
+    assert [o.kind for o in ops].count(kind) >= 3
+    with sat.Searcher(0) as s:
+        assert follow(s, ops) == data_steps(ops)
+
+
+# ---------------------------------------------------------------- 2. scheduled walks
+@pytest.mark.parametrize("walk", range(hl.WALKS))
+def test_walk(walk):
+    walks = hl.schedule(hl.SEED)
+    assert len(walks) == hl.WALKS
+    with sat.Searcher(0) as s:
+        assert follow(s, walks[walk]) == data_steps(walks[walk])
+
+
+# ---------------------------------------------------------------- 3. refusals
+def refused(call, code):
+    with pytest.raises(sat.SatError, match=r"^\[%d\]" % code):
+        call()
+
+
+def refusals(s, m):
+    """every result call the model says is not available: SAT_ESTATE (-5); where it is available, a bad argument:
+    SAT_EINVAL (-1).  Neither may change what the next legal call returns - the walk goes on comparing."""
+    sd = m.searched
+    nq = len(hl.n1s_of(m.batch)) if m.batch is not None else 1
+    nodes = np.zeros(nq, np.int32)
+    if sd is None:
+        for call in (s.results, lambda: s.topk_hits(1), lambda: s.hits_cutoff(0.5), s.score_histogram):
+            refused(call, -5)
+    else:
+        refused(lambda: s.hits_cutoff(-1.0), -1)
+    if sd is None or not sd.lsoln:
+        for call in (lambda: s.results(True), lambda: s.topk_hits(1, True), lambda: s.hits_cutoff(0.5, None, True)):
+            refused(call, -5)
+    if sd is None or not sd.tops:
+        refused(s.results_base, -5)
+    if sd is None or m.cluster is None:
+        refused(lambda: s.cluster_add(0.5, nodes), -5)
+    else:
+        refused(lambda: s.cluster_add(0.5, nodes + m.cluster[0]), -1)
+    if m.cluster is None:
+        refused(s.cluster_labels, -5)
+    refused(lambda: s.set_polish_all(9), -1)
+
+
+@pytest.mark.parametrize("walk", range(hl.WALKS))
+def test_refusals_at_every_step(walk):
+    """every walk once more with the refusals behind every step: which call is refused depends on what the context has
+    held before - sat_results_base after a plain search that follows a polished one, maps after a search without LSOLN
+    that follows one with (tests/test_history_cpu.py: the walks contain both)"""
+    ops = hl.schedule(hl.SEED)[walk]
+    with sat.Searcher(0) as s:
+        refusals(s, hl.Model())
+        assert follow(s, ops, after_step=refusals) == data_steps(ops)
+
+
+# ---------------------------------------------------------------- 4. budgets that make sizing history-sensitive
+@pytest.mark.parametrize("name,value,walk", [("SAT_EXP_SCRATCH_KB", "16", 1), ("SAT_EXP_SELECT_KEYS", "100", 2),
+                                             ("SAT_EXP_SCRATCH_KB", "16", 13), ("SAT_EXP_SELECT_KEYS", "100", 14)])
+def test_walk_under_a_small_budget(monkeypatch, name, value, walk):
+    """16 KB of scratch cuts every LSOLN, match and polish pass into launches whose size depends on the slab buffer's
+    capacity; 100 selection keys cut the query list of the selection passes into chunks of 100 / entries queries"""
+    ops = hl.schedule(hl.SEED)[walk]
+    monkeypatch.setenv(name, value)                                     # read when the context is created
+    with sat.Searcher(0) as s:
+        assert follow(s, ops) == data_steps(ops)
+
+
+# ---------------------------------------------------------------- 5. shards
+MULTI_DATA_KINDS = [k for k in hl.DATA_KINDS if k in hl.MULTI_KINDS]
+
+
+@pytest.mark.parametrize("count", [2, 3])
+@pytest.mark.parametrize("kind", MULTI_DATA_KINDS)
+def test_shards_grow_shrink_grow(kind, count):
+    ops = hl.grow_shrink_grow(kind, multi=True)
+    with shards(count) as s:
+        assert follow(s, ops, multi=True) == data_steps(ops)
+
+
+@pytest.mark.parametrize("count,walk", [(2, 0), (3, 1), (2, hl.MULTI_WALKS - 1), (3, hl.MULTI_WALKS - 1)])
+def test_shards_walk(count, walk):
+    walks = hl.schedule(hl.SEED, multi=True)
+    assert len(walks) == hl.MULTI_WALKS
+    with shards(count) as s:
+        assert follow(s, walks[walk], multi=True) == data_steps(walks[walk])
+
+
+@pytest.mark.parametrize("count", [2, 3])
+def test_shards_padded_rows_rise_and_fall(count):
+    """150 -> 12 -> 40 -> 5 -> 150 entries: the gathers read a padded shard out of buffers an earlier, larger search sized"""
+    ops = hl.shard_sequence()
+    with shards(count) as s:
+        assert follow(s, ops, multi=True) == data_steps(ops)
