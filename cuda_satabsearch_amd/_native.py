@@ -35,8 +35,11 @@ ABI_SYMBOLS = (
     "sat_queries_from_db", "sat_multi_queries_from_db", "sat_stat_query_h2d_bytes",
     "sat_cluster_begin", "sat_cluster_add", "sat_cluster_labels", "sat_cluster_end",
     "sat_multi_search_only", "sat_multi_cluster_begin", "sat_multi_cluster_add", "sat_multi_cluster_labels",
+    "sat_cluster_begin_levels", "sat_cluster_add_levels", "sat_cluster_labels_levels",
+    "sat_multi_cluster_begin_levels", "sat_multi_cluster_add_levels", "sat_multi_cluster_labels_levels",
 )
 
+MAX_CLUSTER_LEVELS = 8
 STAT_BINS = 4096
 STAT_BINS_PER_UNIT = 256
 
@@ -170,6 +173,14 @@ def device_lib():
             lib.sat_multi_cluster_begin.argtypes = [C.c_void_p]
             lib.sat_multi_cluster_add.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
             lib.sat_multi_cluster_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        # (as above: a build of the parent commit predates the leveled clustering)
+        if hasattr(lib, "sat_cluster_begin_levels"):
+            lib.sat_cluster_begin_levels.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+            lib.sat_cluster_add_levels.argtypes = [C.c_void_p, C.c_void_p]
+            lib.sat_cluster_labels_levels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.sat_multi_cluster_begin_levels.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+            lib.sat_multi_cluster_add_levels.argtypes = [C.c_void_p, C.c_void_p]
+            lib.sat_multi_cluster_labels_levels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.sat_hits_cutoff.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         lib.sat_multi_search_cutoff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                                 C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
@@ -239,6 +250,7 @@ def host_lib():
         lib.sat_shard_cuts.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         lib.sat_cluster_join.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         lib.sat_cluster_reps.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.sat_cluster_nested.argtypes = [C.c_int, C.c_int, C.c_void_p]
         _host = lib
     return _host
 

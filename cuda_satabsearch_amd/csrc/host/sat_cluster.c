@@ -36,6 +36,26 @@ int sat_cluster_join(int n, int nsets, const int32_t *labels, int32_t *out)
     return 0;
 }
 
+int sat_cluster_nested(int n, int n_levels, const int32_t *labels)
+{
+    if (n < 1 || n_levels < 1 || !labels)
+        return -1;
+    for (int j = 0; j < n_levels; j++) {
+        const int32_t *label = labels + (size_t)j * (size_t)n;
+        for (int32_t v = 0; v < n; v++)
+            if (label[v] < 0 || label[v] > v || label[label[v]] != label[v])
+                return -1;
+    }
+    /* level j refines level j + 1 iff every node and its label of level j are in one cluster of level j + 1 */
+    for (int j = 0; j + 1 < n_levels; j++) {
+        const int32_t *fine = labels + (size_t)j * (size_t)n, *coarse = fine + n;
+        for (int32_t v = 0; v < n; v++)
+            if (coarse[v] != coarse[fine[v]])
+                return j + 1;
+    }
+    return 0;
+}
+
 int sat_cluster_reps(int n, const int32_t *label, const int32_t *degree, int32_t *rep, int32_t *size)
 {
     if (n < 1 || !label || !rep || !size)

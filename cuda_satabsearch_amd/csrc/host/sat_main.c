@@ -39,7 +39,9 @@
  * and copied), -a dbfile (all-vs-all: every entry of the database is a query, in file order, set as -Q sets them; stdin
  * is not read; prints what -q dbfile prints for a stdin that lists every SID in file order), -L P (with -a dbfile: cluster
  * the database - single linkage over the rows whose p-value is <= P, the graph kept on the GPUs, sat_cluster.h - and print
- * one line per structure, "name representative cluster_size degree", under a "# CLUSTER ..." header instead of any rows).
+ * one line per structure, "name representative cluster_size degree", under a "# CLUSTER ..." header instead of any rows),
+ * -H P1,..,PL (-L at 1..8 ascending cutoffs from ONE all-vs-all run: a "# LEVEL j ..." line per cutoff and, per structure,
+ * -L Pj's three columns for every j side by side; the clusterings are nested).
  */
 #include <math.h>
 #include <stdarg.h>
@@ -82,11 +84,15 @@ static double now_ms(void)
 #pragma weak sat_multi_cluster_add
 #pragma weak sat_multi_cluster_labels
 #pragma weak sat_cluster_reps
+#pragma weak sat_multi_cluster_begin_levels
+#pragma weak sat_multi_cluster_add_levels
+#pragma weak sat_multi_cluster_labels_levels
+#pragma weak sat_cluster_nested
 
 static void usage(const char *prog)
 {
     fprintf(stderr, "Usage: %s [-c] [-q dbfile | -Q dbfile | -a dbfile] [-r restarts] [-g gpus] [-G gpu,gpu,...] [-s seed]\n"
-                    "       [-k K] [-p P] [-m M] [-M M] [-R restarts [-C C]] [-F censor] [-P T] [-A] [-L P] [-b]\n", prog);
+                    "       [-k K] [-p P] [-m M] [-M M] [-R restarts [-C C]] [-F censor] [-P T] [-A] [-L P] [-b] [-H P1,P2,...]\n", prog);
     fprintf(stderr, "  -c : run on host CPU not GPU card\n");
     fprintf(stderr, "  -q dbfile : database is read from dbfile, list of query\n"
                     "              ids is read from stdin\n");
@@ -118,6 +124,11 @@ static void usage(const char *prog)
     fprintf(stderr, "  -L P : with -a dbfile: cluster the database on the GPU - single linkage over the rows whose p-value\n"
                     "         is <= P (0..1); prints one line per structure: name representative cluster_size degree\n"
                     "         (not with -c, -k, -p, -m, -M, -R, -C)\n");
+    fprintf(stderr, "  -H P1,P2,... : with -a dbfile: cluster the database at 1..%d ascending p-values (each 0..1) in ONE run - the\n"
+                    "         clusterings of -L P1, -L P2, ... from one all-vs-all search, nested; prints a line per cutoff\n"
+                    "         (# LEVEL j pvalue <= Pj clusters singletons edges) and one line per structure:\n"
+                    "         name, then representative cluster_size degree for every level\n"
+                    "         (not with -c, -L, -k, -p, -m, -M, -R, -C)\n", SAT_MAX_CLUSTER_LEVELS);
     fprintf(stderr, "  -b : cache the parsed database as dbfile.satbin\n");
     exit(1);
 }
@@ -267,6 +278,8 @@ typedef struct {
     double pmax;                      /* -p: the largest p-value printed */
     int cluster;                      /* -L: cluster the database instead of printing rows */
     double lmax;                      /* -L: the largest p-value of an edge */
+    int nlevels;                      /* -H: the cutoffs' count (then cluster is set too: the run is -L's but for its adds and its table) */
+    double levels[SAT_MAX_CLUSTER_LEVELS];  /* -H: the largest p-value of an edge of each level, ascending */
     unsigned long long seed;
     const char *qfile;                /* -q, -Q, -a: the database; stdin lists the query SIDs (not with -a) */
     const char *from_db;              /* -Q, -a: the database again - the batches are set from entry indices on the GPUs */
@@ -384,12 +397,31 @@ static void print_header(const input *in, int qi, const sat_fit *f)
     out_bytes(line, (size_t)n);
 }
 
+/* -H's list into o->levels / o->nlevels; 0: not 1 .. SAT_MAX_CLUSTER_LEVELS numbers in [0, 1], strictly ascending, the
+ * whole argument */
+static int parse_levels(const char *arg, options *o)
+{
+    o->nlevels = 0;
+    for (const char *at = arg;; ) {
+        char *end = NULL;
+        const double p = strtod(at, &end);
+        if (end == at || (*end != ',' && *end != '\0') || !isfinite(p) || p < 0.0 || p > 1.0)
+            return 0;
+        if (o->nlevels == SAT_MAX_CLUSTER_LEVELS || (o->nlevels > 0 && !(p > o->levels[o->nlevels - 1])))
+            return 0;
+        o->levels[o->nlevels++] = p;
+        if (*end == '\0')
+            return 1;
+        at = end + 1;
+    }
+}
+
 /* The options, then the refusals in a fixed order (the tests pin it), all before the banner and any device call */
 static void parse_options(int argc, char *argv[], options *o)
 {
     *o = (options){ .use_gpu = 1, .maxstart = 128, .want_gpus = 1, .seed = SAT_DEFAULT_SEED };
     int c;
-    while ((c = getopt(argc, argv, "cq:Q:a:r:g:G:s:bk:p:m:M:R:C:F:P:AL:")) != -1) {
+    while ((c = getopt(argc, argv, "cq:Q:a:r:g:G:s:bk:p:m:M:R:C:F:P:AL:H:")) != -1) {
         char *end = NULL;
         long v;
         switch (c) {
@@ -424,6 +456,13 @@ static void parse_options(int argc, char *argv[], options *o)
                 usage(argv[0]);
             }
             o->cluster = 1;
+            break;
+        case 'H':
+            /* the whole argument: 1 .. SAT_MAX_CLUSTER_LEVELS numbers, each as -L's, with commas between, strictly ascending */
+            if (!parse_levels(optarg, o)) {
+                fprintf(stderr, "ERROR: -H needs 1..%d ascending p-values in [0, 1] (got '%s')\n", SAT_MAX_CLUSTER_LEVELS, optarg);
+                usage(argv[0]);
+            }
             break;
         case 'F':
             /* the whole argument, a number in [0, 0.5] */
@@ -472,7 +511,23 @@ static void parse_options(int argc, char *argv[], options *o)
         default: usage(argv[0]);
         }
     }
-    if (o->cluster) {
+    if (o->nlevels) {
+        /* clustering at several cutoffs: -L's run with another add call and another table */
+        if (!o->use_gpu) die("ERROR: -H cannot be combined with -c\n");
+        if (!o->all) die("ERROR: -H needs -a dbfile\n");
+        if (o->cluster) die("ERROR: -H cannot be combined with -L\n");
+        if (o->topk) die("ERROR: -H cannot be combined with -k\n");
+        if (o->cutoff) die("ERROR: -H cannot be combined with -p\n");
+        if (o->nmatch) die("ERROR: -H cannot be combined with -m\n");
+        if (o->rowmatch) die("ERROR: -H cannot be combined with -M\n");
+        if (o->refine) die("ERROR: -H cannot be combined with -R\n");
+        if (o->ncand) die("ERROR: -H cannot be combined with -C\n");
+        if (!sat_multi_search_only || !sat_multi_cluster_begin_levels || !sat_multi_cluster_add_levels ||
+            !sat_multi_cluster_labels_levels || !sat_cluster_reps || !sat_cluster_nested)
+            die("ERROR: this library has no sat_multi_cluster_add_levels\n");
+        if (o->fit && !sat_multi_search_fit) die("ERROR: this library has no sat_multi_search_fit\n");
+        o->cluster = 1;
+    } else if (o->cluster) {
         /* clustering: an all-vs-all run whose rows stay on the GPUs */
         if (!o->use_gpu) die("ERROR: -L cannot be combined with -c\n");
         if (!o->all) die("ERROR: -L needs -a dbfile\n");
@@ -1015,6 +1070,61 @@ static int print_clusters(const options *o, const input *in, sat_multi *multi, c
     return 0;
 }
 
+/* -H: the tables of the L clusterings the GPUs hold, side by side - per level what print_clusters prints for it: 8 bytes
+ * a structure, level and shard cross to the host; the levels must be nested (sat_cluster_nested) */
+static int print_cluster_levels(const options *o, const input *in, sat_multi *multi, const sat_fit *fits)
+{
+    const int n = in->db.count, nl = o->nlevels;
+    const size_t cells = (size_t)n * (size_t)nl;
+    int32_t *label = checked(malloc(sizeof(int32_t) * cells * 4)), *degree = label + cells, *rep = degree + cells, *size = rep + cells;
+    unsigned long long edges[SAT_MAX_CLUSTER_LEVELS] = { 0 };
+    if (sat_multi_cluster_labels_levels(multi, label, degree, edges) != SAT_OK) {
+        fprintf(stderr, "clustering failed: %s\n", sat_last_error());
+        free(label);
+        return 1;
+    }
+    const int broken = sat_cluster_nested(n, nl, label);
+    if (broken < 0)
+        die("ERROR: the GPUs returned labels that are no clustering\n");
+    if (broken > 0)
+        die("ERROR: the clusters of level %d do not lie inside those of level %d\n", broken, broken + 1);
+    char line[SAT_MAX_LINE_LEN + 256];
+    int len = snprintf(line, sizeof line, "# CLUSTER dbfile = %s entries = %d levels = %d restarts = %d\n", in->dbfile, n, nl, o->maxstart);
+    out_bytes(line, (size_t)len);
+    for (int j = 0; j < nl; j++) {
+        const size_t at = (size_t)j * (size_t)n;
+        const int clusters = sat_cluster_reps(n, label + at, degree + at, rep + at, size + at);
+        if (clusters < 0)
+            die("ERROR: the GPUs returned labels that are no clustering\n");
+        int singletons = 0;
+        for (int v = 0; v < n; v++)
+            singletons += size[at + v] == 1;
+        len = snprintf(line, sizeof line, "# LEVEL %d pvalue <= %g clusters = %d singletons = %d edges = %llu\n", j + 1, o->levels[j], clusters,
+                       singletons, edges[j]);
+        out_bytes(line, (size_t)len);
+    }
+    out_bytes(polish_header, strlen(polish_header));
+    if (fits) {
+        int fitted = 0;
+        for (int v = 0; v < n; v++)
+            fitted += fits[v].fitted != 0;
+        len = snprintf(line, sizeof line, "# GUMBEL censor = %g fitted = %d of %d\n", o->censor, fitted, n);
+        out_bytes(line, (size_t)len);
+    }
+    for (int v = 0; v < n; v++) {
+        len = snprintf(line, sizeof line, "%-8s", sat_set_name(&in->db, v));
+        out_bytes(line, (size_t)len);
+        for (int j = 0; j < nl; j++) {
+            const size_t at = (size_t)j * (size_t)n + (size_t)v;
+            len = snprintf(line, sizeof line, " %-8s %d %d", sat_set_name(&in->db, rep[at]), size[at], degree[at]);
+            out_bytes(line, (size_t)len);
+        }
+        out_bytes("\n", 1);
+    }
+    free(label);
+    return 0;
+}
+
 static int run_gpu(const options *o, const input *in)
 {
     sat_multi *multi = open_multi(o, in);
@@ -1033,7 +1143,7 @@ static int run_gpu(const options *o, const input *in)
     /* -F: every query's fit - from the GPUs with -k / -p, else made here from the listing's scores (the whole
      * database's, both size classes: a query's two blocks carry the same line) */
     sat_fit *fits = o->fit ? checked(calloc((size_t)in->num_queries, sizeof(sat_fit))) : NULL;
-    if (o->cluster && sat_multi_cluster_begin(multi) != SAT_OK)
+    if (o->cluster && (o->nlevels ? sat_multi_cluster_begin_levels(multi, o->nlevels, o->levels) : sat_multi_cluster_begin(multi)) != SAT_OK)
         die("ERROR: %s\n", sat_last_error());
     for (int q0 = 0; q0 < in->num_queries; q0 += B.batch) {
         const int nqb = in->num_queries - q0 < B.batch ? in->num_queries - q0 : B.batch;
@@ -1055,9 +1165,9 @@ static int run_gpu(const options *o, const input *in)
                             : sat_multi_queries_set(multi, nqb, B.n1s, B.qtabs, B.qdmats, SAT_MAXDIM, B.qtypes, (uint32_t)q0);
         if (rc == SAT_OK)
             rc = search_batch(o, in, multi, &B, fits ? fits + q0 : NULL, &ms, &ms_stage2);
-        /* -L: the batch's edges into the graph on the GPUs; query b is structure qindex[q0 + b] of the database */
+        /* -L, -H: the batch's edges into the graph(s) on the GPUs; query b is structure qindex[q0 + b] of the database */
         if (rc == SAT_OK && o->cluster)
-            rc = sat_multi_cluster_add(multi, o->lmax, in->qindex + q0);
+            rc = o->nlevels ? sat_multi_cluster_add_levels(multi, in->qindex + q0) : sat_multi_cluster_add(multi, o->lmax, in->qindex + q0);
         if (rc < 0) {
             fprintf(stderr, "kernel launch failed: %s\n", sat_last_error());
             status = 1;
@@ -1093,7 +1203,7 @@ static int run_gpu(const options *o, const input *in)
     /* the listing's deferred block: every query's large-class rows, after all small-class blocks, with the reference
      * GPU path's two blanks before the p-value */
     if (!status && o->cluster)
-        status = print_clusters(o, in, multi, fits);
+        status = o->nlevels ? print_cluster_levels(o, in, multi, fits) : print_clusters(o, in, multi, fits);
     if (!status && !o->ranked && !o->cluster && in->cls_count[1] > 0)
         for (int qi = 0; qi < in->num_queries; qi++) {
             print_header(in, qi, fits ? &fits[qi] : NULL);

@@ -213,7 +213,13 @@ struct sat_ctx {
     // single-linkage clustering (sat_cluster_*, sat_cluster.hip): the accumulator over cluster_nodes nodes (0 = none) -
     // the union-find's parent [nodes]; labels [nodes] (written by sat_cluster_labels) then degrees [nodes] in one array;
     // the 64-bit edge counter; the batch's node of each query.  An upload drops it (free_db).
+    // Leveled (sat_cluster_begin_levels; cluster_levels = L > 0, cutoffs cluster_cut[0 .. L - 1] ascending):
+    // one forest per level in d_cl_parent [L][nodes]; d_cl_out holds labels [L][nodes], degrees [L][nodes] (both written
+    // by sat_cluster_labels_levels) and then the degrees counted AT each level [L][nodes]; d_cl_edges the edges at each
+    // level [L], then their running sums [L].
     int cluster_nodes = 0;
+    int cluster_levels = 0;
+    double cluster_cut[SAT_MAX_CLUSTER_LEVELS] = { 0 };
     DevBuf<int32_t> d_cl_parent, d_cl_out, d_cl_qnode;
     DevBuf<unsigned long long> d_cl_edges;
 

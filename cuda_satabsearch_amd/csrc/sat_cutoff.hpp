@@ -20,6 +20,20 @@
 inline int sat_check_context(const void *ctx) { return ctx ? SAT_OK : sat_fail(SAT_EINVAL, "null context"); }
 inline int sat_check_uploaded(bool uploaded) { return uploaded ? SAT_OK : sat_fail(SAT_ESTATE, "no database uploaded"); }
 inline int sat_check_pvalue(double p) { return std::isfinite(p) && p >= 0.0 ? SAT_OK : sat_fail(SAT_EINVAL, "max_pvalue must be finite and >= 0"); }
+// the cutoffs of a leveled cluster accumulator: 1 .. SAT_MAX_CLUSTER_LEVELS of them, each finite and in [0, 1], strictly ascending
+inline int sat_check_levels(int n_levels, const double *max_pvalue)
+{
+    if (n_levels < 1 || n_levels > SAT_MAX_CLUSTER_LEVELS)
+        return sat_fail(SAT_EINVAL, "n_levels must be 1..%d (got %d)", SAT_MAX_CLUSTER_LEVELS, n_levels);
+    if (!max_pvalue) return sat_fail(SAT_EINVAL, "max_pvalue list is null");
+    for (int j = 0; j < n_levels; j++) {
+        if (!(std::isfinite(max_pvalue[j]) && max_pvalue[j] >= 0.0 && max_pvalue[j] <= 1.0))
+            return sat_fail(SAT_EINVAL, "level %d: max_pvalue must be finite and lie in [0, 1]", j);
+        if (j > 0 && !(max_pvalue[j] > max_pvalue[j - 1]))
+            return sat_fail(SAT_EINVAL, "level %d: max_pvalue must be above level %d's (%g after %g)", j, j - 1, max_pvalue[j], max_pvalue[j - 1]);
+    }
+    return SAT_OK;
+}
 // (fit_rc: what sat_gumbel_fit_binned said to that censor - it refuses the same range)
 inline int sat_check_censor(double c, int fit_rc = 0) { return c >= 0.0 && c <= 0.5 && !fit_rc ? SAT_OK : sat_fail(SAT_EINVAL, "censor must lie in [0, 0.5]"); }
 inline int sat_check_tops(int tops)

@@ -902,6 +902,55 @@ int sat_multi_cluster_labels(sat_multi *m, int32_t *label, int32_t *degree, unsi
     return SAT_OK;
 }
 
+int sat_multi_cluster_begin_levels(sat_multi *m, int n_levels, const double *max_pvalue)
+{
+    SAT_TRY(check_multi(m));
+    // every shard makes the same checks on the same arguments: the first one's refusal is every one's, before any began
+    for (sat_ctx *c : m->ctx) SAT_TRY(sat_cluster_begin_levels(c, m->n_entries, n_levels, max_pvalue));
+    return SAT_OK;
+}
+
+int sat_multi_cluster_add_levels(sat_multi *m, const int32_t *query_node)
+{
+    SAT_TRY(check_multi(m));
+    // the argument checks of sat_cluster_add_levels, made for all shards before the first one adds anything
+    if (!query_node) return sat_fail(SAT_EINVAL, "query_node is null");
+    const size_t nq = m->ctx[0]->queries.size();
+    for (size_t q = 0; q < nq; q++)
+        if (query_node[q] < 0 || query_node[q] >= m->n_entries)
+            return sat_fail(SAT_EINVAL, "query %zu: node %d outside 0..%d", q, query_node[q], m->n_entries - 1);
+    return each_shard(m, [&](int g) { return sat_cluster_add_levels(m->ctx[(size_t)g], query_node); });
+}
+
+int sat_multi_cluster_labels_levels(sat_multi *m, int32_t *label, int32_t *degree, unsigned long long *edges)
+{
+    SAT_TRY(check_multi(m));
+    if (!label) return sat_fail(SAT_EINVAL, "label buffer is null");
+    const size_t n = (size_t)m->n_entries, ndev = (size_t)m->ndev, levels = (size_t)m->ctx[0]->cluster_levels;
+    // one shard, or no leveled accumulator (the shard's call says which state error that is)
+    if (ndev == 1 || levels == 0) return sat_cluster_labels_levels(m->ctx[0], label, degree, edges);
+    // the shards' labels as [level][shard][node], so that a level's sets lie together for the join
+    std::vector<int32_t> labels(levels * ndev * n), shard(levels * n), deg(degree ? levels * n : 0);
+    std::vector<unsigned long long> e(levels);
+    if (degree) std::fill(degree, degree + levels * n, 0);
+    if (edges) std::fill(edges, edges + levels, 0ull);
+    for (size_t g = 0; g < ndev; g++) {
+        const int rc = sat_cluster_labels_levels(m->ctx[g], shard.data(), degree ? deg.data() : nullptr, edges ? e.data() : nullptr);
+        if (rc != SAT_OK) return rc;
+        for (size_t j = 0; j < levels; j++) {
+            std::copy(shard.begin() + j * n, shard.begin() + (j + 1) * n, labels.begin() + (j * ndev + g) * n);
+            if (edges) edges[j] += e[j];
+        }
+        for (size_t i = 0; degree && i < levels * n; i++) degree[i] += deg[i];  // integer sums: any order
+    }
+    for (size_t j = 0; j < levels; j++)
+        if (sat_cluster_join((int)n, (int)ndev, labels.data() + j * ndev * n, label + j * n) != 0)
+            return sat_fail(SAT_EDEVICE, "a shard returned a label outside 0..%d", m->n_entries - 1);
+    const int broken = sat_cluster_nested((int)n, (int)levels, label);
+    if (broken != 0) return sat_fail(SAT_EDEVICE, "the joined labels of level %d do not lie inside level %d's", broken - 1, broken);
+    return SAT_OK;
+}
+
 unsigned long long sat_multi_stat_d2h_bytes(const sat_multi *m)
 {
     if (!m) return 0ull;

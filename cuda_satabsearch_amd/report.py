@@ -81,3 +81,25 @@ def cluster_table(labels, degrees):
     if _native.host_lib().sat_cluster_reps(len(lab), lab.ctypes.data, deg.ctypes.data, reps.ctypes.data, sizes.ctypes.data) < 0:
         raise ValueError("labels are not canonical: labels[v] must be the smallest node of v's cluster")
     return reps, sizes
+
+
+def cluster_levels_table(labels, degrees):
+    """(reps int32[L, n], sizes int32[L, n]) of the labellings Searcher.cluster_labels_levels returns (int32[L, n] each,
+    tightest level first): cluster_table per level (sat_cluster_reps, which the command line's -H prints from).  Raises
+    ValueError when a level is not canonical or a level's clusters do not lie inside the next level's
+    (sat_cluster_nested of csrc/host/sat_cluster.h)."""
+    import numpy as np
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    deg = np.ascontiguousarray(degrees, dtype=np.int32)
+    if lab.ndim != 2 or lab.shape != deg.shape:
+        raise ValueError("labels and degrees must both be [levels, n]")
+    host = _native.host_lib()
+    broken = host.sat_cluster_nested(lab.shape[1], lab.shape[0], lab.ctypes.data)
+    if broken < 0:
+        raise ValueError("labels are not canonical: labels[j][v] must be the smallest node of v's cluster at level j")
+    if broken > 0:
+        raise ValueError("the levels are not nested: a cluster of level %d lies in no one cluster of level %d" % (broken, broken + 1))
+    reps, sizes = np.empty_like(lab), np.empty_like(lab)
+    for j in range(lab.shape[0]):
+        host.sat_cluster_reps(lab.shape[1], lab[j].ctypes.data, deg[j].ctypes.data, reps[j].ctypes.data, sizes[j].ctypes.data)
+    return reps, sizes

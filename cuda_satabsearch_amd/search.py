@@ -197,6 +197,31 @@ def _cluster_labels(obj, fn, handle, n_nodes):
     return labels, degrees, int(edges.value)
 
 
+def _cluster_levels(pvalues):
+    """the cutoffs of cluster_begin_levels as the library takes them: (count, float64 array)"""
+    cuts = np.ascontiguousarray(pvalues, dtype=np.float64).ravel()
+    return len(cuts), cuts
+
+
+def _cluster_add_levels(obj, fn, handle, query_nodes):
+    """shared by Searcher / MultiSearcher.cluster_add_levels"""
+    nodes = np.ascontiguousarray(query_nodes, dtype=np.int32).ravel()
+    if len(nodes) != getattr(obj, "n_queries", 1):
+        raise ValueError("one node per query of the batch is needed")
+    obj._check(fn(handle, nodes.ctypes.data))
+
+
+def _cluster_labels_levels(obj, fn, handle, n_levels, n_nodes):
+    """shared by Searcher / MultiSearcher.cluster_labels_levels: (labels int32[L, n], degrees int32[L, n], edges uint64[L])"""
+    if not n_levels:
+        obj._check(fn(handle, None, None, None))            # the library's state error
+    labels = np.zeros((n_levels, n_nodes), np.int32)
+    degrees = np.zeros((n_levels, n_nodes), np.int32)
+    edges = np.zeros(n_levels, np.uint64)
+    obj._check(fn(handle, labels.ctypes.data, degrees.ctypes.data, edges.ctypes.data))
+    return labels, degrees, edges
+
+
 class Searcher:
     """One HIP device, one resident database shard, one current query."""
 
@@ -512,7 +537,7 @@ class Searcher:
         the default ordinals."""
         n = self.n_entries if n_nodes is None else int(n_nodes)
         self._check(self._lib.sat_cluster_begin(self._ctx, n))
-        self._cluster_nodes = n
+        self._cluster_nodes, self._cluster_levels = n, 0
 
     def cluster_add(self, max_pvalue, query_nodes):
         """Add the rows of the last search whose p-value - as hits_cutoff tests it: an installed fit and polished rows
@@ -529,9 +554,32 @@ class Searcher:
         return _cluster_labels(self, self._lib.sat_cluster_labels, self._ctx, self._cluster_nodes)
 
     def cluster_end(self):
-        """Free the accumulator (sat_cluster_end)."""
+        """Free the accumulator, plain or leveled (sat_cluster_end)."""
         self._check(self._lib.sat_cluster_end(self._ctx))
         self._cluster_nodes = 0
+        self._cluster_levels = 0
+
+    # ---- the same at several cutoffs in one pass (sat_cluster_*_levels) -------
+    def cluster_begin_levels(self, pvalues, n_nodes=None):
+        """Start the LEVELED accumulator: cluster_begin for the 1..8 strictly ascending cutoffs `pvalues` (each in
+        [0, 1]) at once, replacing whatever accumulator there was.  A searcher holds one accumulator, plain or leveled;
+        the calls of the other kind raise."""
+        n = self.n_entries if n_nodes is None else int(n_nodes)
+        count, cuts = _cluster_levels(pvalues)
+        self._check(self._lib.sat_cluster_begin_levels(self._ctx, n, count, cuts.ctypes.data))
+        self._cluster_nodes, self._cluster_levels = n, count
+
+    def cluster_add_levels(self, query_nodes):
+        """cluster_add at every level's cutoff in one pass over the rows of the last search (sat_cluster_add_levels):
+        a row is an edge of every level whose cutoff its p-value does not exceed.  Nothing is copied back."""
+        _cluster_add_levels(self, self._lib.sat_cluster_add_levels, self._ctx, query_nodes)
+
+    def cluster_labels_levels(self):
+        """(labels int32[L, n_nodes], degrees int32[L, n_nodes], edges uint64[L]), tightest level first: per level what
+        cluster_labels returns for the same adds at that level's cutoff (sat_cluster_labels_levels).  The levels are
+        nested: labels[j + 1][labels[j]] == labels[j + 1].  report.cluster_levels_table turns them into tables."""
+        return _cluster_labels_levels(self, self._lib.sat_cluster_labels_levels, self._ctx, getattr(self, "_cluster_levels", 0),
+                                      getattr(self, "_cluster_nodes", 0))
 
     def debug_set_scores(self, scores):
         """Test hook (satabsearch_debug.h): overwrite the last search's device scores with int32[nq, N]."""
@@ -736,6 +784,7 @@ class MultiSearcher:
     def cluster_begin(self):
         """Searcher.cluster_begin on every shard, over the whole database's nodes (sat_multi_cluster_begin)."""
         self._check(self._lib.sat_multi_cluster_begin(self._m))
+        self._cluster_levels = 0
 
     def cluster_add(self, max_pvalue, query_nodes):
         """Searcher.cluster_add on every shard: each adds the edges that end at its own entries."""
@@ -745,6 +794,22 @@ class MultiSearcher:
         """Searcher.cluster_labels of the whole database: the shards' labels joined, degrees and edges summed
         (sat_multi_cluster_labels) - exactly what one searcher holding the whole database returns."""
         return _cluster_labels(self, self._lib.sat_multi_cluster_labels, self._m, self.n_entries)
+
+    def cluster_begin_levels(self, pvalues):
+        """Searcher.cluster_begin_levels on every shard, over the whole database's nodes (sat_multi_cluster_begin_levels)."""
+        count, cuts = _cluster_levels(pvalues)
+        self._check(self._lib.sat_multi_cluster_begin_levels(self._m, count, cuts.ctypes.data))
+        self._cluster_levels = count
+
+    def cluster_add_levels(self, query_nodes):
+        """Searcher.cluster_add_levels on every shard: each adds the edges that end at its own entries."""
+        _cluster_add_levels(self, self._lib.sat_multi_cluster_add_levels, self._m, query_nodes)
+
+    def cluster_labels_levels(self):
+        """Searcher.cluster_labels_levels of the whole database: per level the shards' labels joined, degrees and edges
+        summed (sat_multi_cluster_labels_levels) - exactly what one searcher holding the whole database returns."""
+        return _cluster_labels_levels(self, self._lib.sat_multi_cluster_labels_levels, self._m, getattr(self, "_cluster_levels", 0),
+                                      self.n_entries)
 
     def set_statistics(self, fits):
         """Searcher.set_statistics on every shard (sat_multi_stats_set)."""

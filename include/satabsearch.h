@@ -30,6 +30,7 @@ extern "C" {
 #define SAT_MAXITER       100    /* saparams.h:33 (MAXITER): SA steps per restart           */
 #define SAT_DEFAULT_SEED  1234   /* H.cu:263, :871                                           */
 #define SAT_MAX_MATCHES   8      /* largest max_matches of sat_search_matches                */
+#define SAT_MAX_CLUSTER_LEVELS 8 /* most p-value cutoffs of one leveled cluster accumulator  */
 
 #define SAT_OK          0
 #define SAT_EINVAL     -1   /* bad argument (order out of range, bad type code, ...)        */
@@ -524,6 +525,31 @@ int sat_cluster_add(sat_ctx *ctx, double max_pvalue, const int32_t *query_node);
 int sat_cluster_labels(sat_ctx *ctx, int32_t *label, int32_t *degree, unsigned long long *edges);
 int sat_cluster_end(sat_ctx *ctx);
 
+/*
+ * ---- The same clustering at several p-values in one pass: L = n_levels cutoffs max_pvalue[0] < ... <
+ * max_pvalue[L - 1], 1 <= L <= SAT_MAX_CLUSTER_LEVELS, each finite and in [0, 1].  Nodes, rows and the double tested are
+ * those above; row (q, e) is an edge of level j iff that double is <= max_pvalue[j] (a NaN qualifies nowhere) and its two
+ * ends differ, so the edges of level j are among those of level j + 1.  Per level j, label[j][v], degree[j][v] and
+ * edges[j] are exactly what the calls above return for the same add calls at max_pvalue[j] - integers, functions of the
+ * multiset of edges - and the levels are NESTED: label[j + 1][v] == label[j + 1][label[j][v]].
+ * A context holds ONE accumulator, plain (above) or leveled; the add and labels calls of the other kind are SAT_ESTATE,
+ * with a message that names the kind that is active.  sat_cluster_end and a database upload drop either kind.
+ *
+ * The begin call      the checks of sat_cluster_begin, then the levels': n_levels outside 1 .. SAT_MAX_CLUSTER_LEVELS, a
+ *                     null list, a cutoff that is not finite, lies outside [0, 1] or is not above the one before it
+ *                     (the message names its position): SAT_EINVAL, and an earlier accumulator of either kind stays as it
+ *                     was.  An accepted call replaces whatever accumulator there was.
+ * The add call        sat_cluster_add for every level at once: its checks, copies, stream order and one pass over the
+ *                     rows; each row's p-value is fetched once.  Nothing comes back: sat_stat_d2h_bytes does not move.
+ * The labels call     wait, flatten every level's forest and copy label[L][n_nodes], degree[L][n_nodes] and edges[L],
+ *                     tightest level first: exactly L * (8 * n_nodes + 8) bytes; degree and edges may be NULL (fewer
+ *                     bytes).  The nesting is checked on the host (SAT_EDEVICE if it fails).  The forests stay usable
+ *                     for more add calls.
+ */
+int sat_cluster_begin_levels(sat_ctx *ctx, int n_nodes, int n_levels, const double *max_pvalue);
+int sat_cluster_add_levels(sat_ctx *ctx, const int32_t *query_node);
+int sat_cluster_labels_levels(sat_ctx *ctx, int32_t *label, int32_t *degree, unsigned long long *edges);
+
 /* Bytes this context's result calls (sat_results, sat_search, sat_topk, sat_topk_hits, sat_hits_cutoff, the pair searches) have copied
  * from the device to the host since it was created (diagnostics: the best-k path moves O(k) rows). */
 unsigned long long sat_stat_d2h_bytes(const sat_ctx *ctx);
@@ -662,6 +688,13 @@ int sat_multi_search_only(sat_multi *m, int lorder, int lsoln, int maxstart, dou
 int sat_multi_cluster_begin(sat_multi *m);
 int sat_multi_cluster_add(sat_multi *m, double max_pvalue, const int32_t *query_node);
 int sat_multi_cluster_labels(sat_multi *m, int32_t *label, int32_t *degree, unsigned long long *edges);
+/* The leveled accumulator over every shard (the calls of DESIGN.md 6p on each shard's context, n_nodes = the database
+ * size): every shard keeps L forests over the whole database's nodes; the labels call brings every shard's arrays to
+ * the host (ndev * L * (8 * n_nodes + 8) bytes), joins each level's labels with sat_cluster_join, sums degrees and edges
+ * per level and checks the nesting.  Arguments, layouts and rejections as on one context. */
+int sat_multi_cluster_begin_levels(sat_multi *m, int n_levels, const double *max_pvalue);
+int sat_multi_cluster_add_levels(sat_multi *m, const int32_t *query_node);
+int sat_multi_cluster_labels_levels(sat_multi *m, int32_t *label, int32_t *degree, unsigned long long *edges);
 unsigned long long sat_multi_stat_d2h_bytes(const sat_multi *m);
 
 /*
