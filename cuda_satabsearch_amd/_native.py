@@ -37,9 +37,13 @@ ABI_SYMBOLS = (
     "sat_multi_search_only", "sat_multi_cluster_begin", "sat_multi_cluster_add", "sat_multi_cluster_labels",
     "sat_cluster_begin_levels", "sat_cluster_add_levels", "sat_cluster_labels_levels",
     "sat_multi_cluster_begin_levels", "sat_multi_cluster_add_levels", "sat_multi_cluster_labels_levels",
+    "sat_eval_classes", "sat_eval_rows", "sat_eval_tables", "sat_multi_eval_classes", "sat_multi_eval_rows",
 )
 
 MAX_CLUSTER_LEVELS = 8
+# rows of one query a block of eval_histogram (csrc/sat_eval.hip: kEvalRows) counts, and the bins a side its LDS holds
+EVAL_BLOCK_ROWS = 4096
+EVAL_WINDOW_BINS = 2048
 STAT_BINS = 4096
 STAT_BINS_PER_UNIT = 256
 
@@ -58,6 +62,12 @@ class Fit(C.Structure):
     """struct sat_fit of include/satabsearch.h"""
     _fields_ = [("a", C.c_double), ("b", C.c_double), ("rows", C.c_int32), ("censored", C.c_int32),
                 ("below", C.c_int32), ("fitted", C.c_int32)]
+
+
+class Eval(C.Structure):
+    """struct sat_eval of include/satabsearch.h (sat_eval_row of csrc/host/sat_eval.h)"""
+    _fields_ = [("u2", C.c_uint64), ("t2", C.c_uint64), ("positives", C.c_int32), ("negatives", C.c_int32),
+                ("n_used", C.c_int32), ("query_class", C.c_int32)]
 
 
 class StructSetC(C.Structure):
@@ -181,6 +191,13 @@ def device_lib():
             lib.sat_multi_cluster_begin_levels.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
             lib.sat_multi_cluster_add_levels.argtypes = [C.c_void_p, C.c_void_p]
             lib.sat_multi_cluster_labels_levels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        # (as above: a build of the parent commit predates the evaluation against a classification)
+        if hasattr(lib, "sat_eval_rows"):
+            lib.sat_eval_classes.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+            lib.sat_eval_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+            lib.sat_eval_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.sat_multi_eval_classes.argtypes = [C.c_void_p, C.c_void_p]
+            lib.sat_multi_eval_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         lib.sat_hits_cutoff.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         lib.sat_multi_search_cutoff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                                 C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
@@ -251,6 +268,7 @@ def host_lib():
         lib.sat_cluster_join.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         lib.sat_cluster_reps.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.sat_cluster_nested.argtypes = [C.c_int, C.c_int, C.c_void_p]
+        lib.sat_eval_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Eval)]
         _host = lib
     return _host
 

@@ -41,7 +41,11 @@
  * the database - single linkage over the rows whose p-value is <= P, the graph kept on the GPUs, sat_cluster.h - and print
  * one line per structure, "name representative cluster_size degree", under a "# CLUSTER ..." header instead of any rows),
  * -H P1,..,PL (-L at 1..8 ascending cutoffs from ONE all-vs-all run: a "# LEVEL j ..." line per cutoff and, per structure,
- * -L Pj's three columns for every j side by side; the clusterings are nested).
+ * -L Pj's three columns for every j side by side; the clusterings are nested), -E classfile [-N n] (with -a dbfile or
+ * -Q dbfile: score the search against a classification - per query the AUC and the ROC-n, default n = 50, of its ranking
+ * of the classified structures, from two score histograms made and reduced on the GPUs, sat_eval.h: 32 bytes a query come
+ * back, and one line per query is printed, "name class positives negatives u2 t2 n_used auc rocn", under "# EVAL ..." and
+ * "# MEAN ..." instead of any rows).
  */
 #include <math.h>
 #include <stdarg.h>
@@ -88,11 +92,14 @@ static double now_ms(void)
 #pragma weak sat_multi_cluster_add_levels
 #pragma weak sat_multi_cluster_labels_levels
 #pragma weak sat_cluster_nested
+#pragma weak sat_multi_eval_classes
+#pragma weak sat_multi_eval_rows
 
 static void usage(const char *prog)
 {
     fprintf(stderr, "Usage: %s [-c] [-q dbfile | -Q dbfile | -a dbfile] [-r restarts] [-g gpus] [-G gpu,gpu,...] [-s seed]\n"
-                    "       [-k K] [-p P] [-m M] [-M M] [-R restarts [-C C]] [-F censor] [-P T] [-A] [-L P] [-b] [-H P1,P2,...]\n", prog);
+                    "       [-k K] [-p P] [-m M] [-M M] [-R restarts [-C C]] [-F censor] [-P T] [-A] [-L P] [-b] [-H P1,P2,...]\n"
+                    "       [-E classfile [-N n]]\n", prog);
     fprintf(stderr, "  -c : run on host CPU not GPU card\n");
     fprintf(stderr, "  -q dbfile : database is read from dbfile, list of query\n"
                     "              ids is read from stdin\n");
@@ -129,6 +136,12 @@ static void usage(const char *prog)
                     "         (# LEVEL j pvalue <= Pj clusters singletons edges) and one line per structure:\n"
                     "         name, then representative cluster_size degree for every level\n"
                     "         (not with -c, -L, -k, -p, -m, -M, -R, -C)\n", SAT_MAX_CLUSTER_LEVELS);
+    fprintf(stderr, "  -E classfile : with -a dbfile or -Q dbfile: score the search against a classification on the GPU - classfile\n"
+                    "         lists 'name class' per line (# comments; unlisted structures are unclassified); prints one line\n"
+                    "         per query: name class positives negatives u2 t2 n_used auc rocn, where auc = u2 / (2 positives\n"
+                    "         negatives) and rocn = t2 / (2 positives n_used) rank the classified structures other than the\n"
+                    "         query itself by raw score, ties counted half (not with -c, -k, -p, -m, -M, -R, -C, -F, -L, -H)\n");
+    fprintf(stderr, "  -N n : with -E: the negatives ROC-n counts up to (n >= 1). Default 50\n");
     fprintf(stderr, "  -b : cache the parsed database as dbfile.satbin\n");
     exit(1);
 }
@@ -280,6 +293,8 @@ typedef struct {
     double lmax;                      /* -L: the largest p-value of an edge */
     int nlevels;                      /* -H: the cutoffs' count (then cluster is set too: the run is -L's but for its adds and its table) */
     double levels[SAT_MAX_CLUSTER_LEVELS];  /* -H: the largest p-value of an edge of each level, ascending */
+    const char *classfile;            /* -E: score the search against this classification instead of printing rows */
+    int rocn;                         /* -N: the negatives ROC-n counts up to (0: not given) */
     unsigned long long seed;
     const char *qfile;                /* -q, -Q, -a: the database; stdin lists the query SIDs (not with -a) */
     const char *from_db;              /* -Q, -a: the database again - the batches are set from entry indices on the GPUs */
@@ -421,7 +436,7 @@ static void parse_options(int argc, char *argv[], options *o)
 {
     *o = (options){ .use_gpu = 1, .maxstart = 128, .want_gpus = 1, .seed = SAT_DEFAULT_SEED };
     int c;
-    while ((c = getopt(argc, argv, "cq:Q:a:r:g:G:s:bk:p:m:M:R:C:F:P:AL:H:")) != -1) {
+    while ((c = getopt(argc, argv, "cq:Q:a:r:g:G:s:bk:p:m:M:R:C:F:P:AL:H:E:N:")) != -1) {
         char *end = NULL;
         long v;
         switch (c) {
@@ -497,6 +512,16 @@ static void parse_options(int argc, char *argv[], options *o)
             }
             o->polish = (int)v;
             break;
+        case 'E': o->classfile = optarg; break;
+        case 'N':
+            /* positive, digits only */
+            v = strtol(optarg, &end, 10);
+            if (end == optarg || *end != '\0' || v < 1 || v > 0x7FFFFFFFL) {
+                fprintf(stderr, "ERROR: -N needs an integer >= 1 (got '%s')\n", optarg);
+                usage(argv[0]);
+            }
+            o->rocn = (int)v;
+            break;
         case 'R':
         case 'C':
             /* positive, digits only */
@@ -510,6 +535,25 @@ static void parse_options(int argc, char *argv[], options *o)
             break;
         default: usage(argv[0]);
         }
+    }
+    if (o->rocn && !o->classfile) die("ERROR: -N needs -E classfile\n");
+    if (o->classfile) {
+        /* evaluation: a run over queries of the database whose rows stay on the GPUs */
+        if (!o->use_gpu) die("ERROR: -E cannot be combined with -c\n");
+        if (!o->all && !o->from_db) die("ERROR: -E needs -a dbfile or -Q dbfile\n");
+        if (o->topk) die("ERROR: -E cannot be combined with -k\n");
+        if (o->cutoff) die("ERROR: -E cannot be combined with -p\n");
+        if (o->nmatch) die("ERROR: -E cannot be combined with -m\n");
+        if (o->rowmatch) die("ERROR: -E cannot be combined with -M\n");
+        if (o->refine) die("ERROR: -E cannot be combined with -R\n");
+        if (o->ncand) die("ERROR: -E cannot be combined with -C\n");
+        if (o->fit) die("ERROR: -E cannot be combined with -F\n");
+        if (o->cluster) die("ERROR: -E cannot be combined with -L\n");
+        if (o->nlevels) die("ERROR: -E cannot be combined with -H\n");
+        if (o->polish && !o->polish_all) die("ERROR: -E takes -P T only with -A\n");
+        if (!sat_multi_search_only || !sat_multi_eval_classes || !sat_multi_eval_rows)
+            die("ERROR: this library has no sat_multi_eval_rows\n");
+        if (!o->rocn) o->rocn = 50;
     }
     if (o->nlevels) {
         /* clustering at several cutoffs: -L's run with another add call and another table */
@@ -808,7 +852,7 @@ static void alloc_hits(gpu_bufs *B, size_t rows, int lsoln)
 static void alloc_gpu_bufs(const options *o, const input *in, gpu_bufs *B)
 {
     const int total = in->db.count, nm = o->nm, lsoln = in->lsoln;
-    const int entry_slots = (!o->ranked && !o->cluster) || o->nmatch;     /* every entry's slots come to the host */
+    const int entry_slots = (!o->ranked && !o->cluster && !o->classfile) || o->nmatch;     /* every entry's slots come to the host */
     *B = (gpu_bufs){ .batch = 256, .kk = o->topk < total ? o->topk : total };
     /* Queries go to the GPUs in batches: one set of launches scores a whole batch (grid = entries x queries), which
      * is what fills the machine when the database is small and the query list long (-q).  The batch size is bounded
@@ -827,7 +871,7 @@ static void alloc_gpu_bufs(const options *o, const input *in, gpu_bufs *B)
         alloc_slots(&B->all, rows, nm, o->nmatch, lsoln);
     if (o->nmatch)
         B->restarts = checked(malloc(sizeof(int32_t) * rows * nm));
-    if (!o->ranked && !o->cluster && in->cls_count[1] > 0)
+    if (!o->ranked && !o->cluster && !o->classfile && in->cls_count[1] > 0)
         alloc_slots(&B->large, (size_t)in->cls_count[1] * in->num_queries, nm, o->nmatch, lsoln);
     if (o->csr) {
         B->hits_cap = o->cutoff ? 1024 : B->kk * B->batch;
@@ -922,8 +966,8 @@ static int search_batch(const options *o, const input *in, sat_multi *multi, gpu
                         double *ms_stage2)
 {
     const int lorder = in->lorder, lsoln = in->lsoln, maxstart = o->maxstart;
-    if (o->cluster) {
-        /* -L: the rows stay on the GPUs (no gather, no LSOLN: no map is printed); with -F the fit is installed there */
+    if (o->cluster || o->classfile) {
+        /* -L, -E: the rows stay on the GPUs (no gather, no LSOLN: no map is printed); with -F the fit is installed there */
         if (o->fit)
             return sat_multi_search_fit(multi, lorder, 0, maxstart, o->censor, fits, ms);
         return sat_multi_search_only(multi, lorder, 0, maxstart, ms);
@@ -1125,8 +1169,64 @@ static int print_cluster_levels(const options *o, const input *in, sat_multi *mu
     return 0;
 }
 
+/* -E: the table of the evaluation - the queries' rows as the GPUs reduced them (32 bytes a query crossed to the host);
+ * the two ratios are taken here, and their means over the queries where both are defined */
+static void print_eval(const options *o, const input *in, const sat_classes *cl, const sat_eval *ev)
+{
+    /* (the class file's name and the class tokens are of any length: they go out as they are, not through `line`) */
+    char line[SAT_MAX_LINE_LEN + 256];
+    int len = snprintf(line, sizeof line, "# EVAL dbfile = %s classes = ", in->dbfile);
+    out_bytes(line, (size_t)len);
+    out_bytes(o->classfile, strlen(o->classfile));
+    len = snprintf(line, sizeof line, " entries = %d classified = %d distinct = %d restarts = %d rocn = %d\n", in->db.count, cl->classified,
+                   cl->distinct, o->maxstart, o->rocn);
+    out_bytes(line, (size_t)len);
+    out_bytes(polish_header, strlen(polish_header));
+    int defined = 0;
+    double auc_sum = 0.0, rocn_sum = 0.0;
+    for (int qi = 0; qi < in->num_queries; qi++)
+        if (ev[qi].positives > 0 && ev[qi].negatives > 0) {
+            auc_sum += (double)ev[qi].u2 / (2.0 * (double)ev[qi].positives * (double)ev[qi].negatives);
+            rocn_sum += (double)ev[qi].t2 / (2.0 * (double)ev[qi].positives * (double)ev[qi].n_used);
+            defined++;
+        }
+    if (defined)
+        len = snprintf(line, sizeof line, "# MEAN queries = %d auc = %.6f rocn = %.6f\n", defined, auc_sum / defined, rocn_sum / defined);
+    else
+        len = snprintf(line, sizeof line, "# MEAN queries = 0 auc = NA rocn = NA\n");
+    out_bytes(line, (size_t)len);
+    for (int qi = 0; qi < in->num_queries; qi++) {
+        const sat_eval *e = &ev[qi];
+        const char *token = e->query_class >= 0 && e->query_class < cl->distinct ? cl->token[e->query_class] : "-";
+        len = snprintf(line, sizeof line, "%-8s ", sat_set_name(&in->db, in->qindex[qi]));
+        out_bytes(line, (size_t)len);
+        out_bytes(token, strlen(token));
+        len = snprintf(line, sizeof line, " %d %d %llu %llu %d", e->positives, e->negatives, (unsigned long long)e->u2,
+                       (unsigned long long)e->t2, e->n_used);
+        out_bytes(line, (size_t)len);
+        if (e->positives > 0 && e->negatives > 0)
+            len = snprintf(line, sizeof line, " %.6f %.6f\n", (double)e->u2 / (2.0 * (double)e->positives * (double)e->negatives),
+                           (double)e->t2 / (2.0 * (double)e->positives * (double)e->n_used));
+        else
+            len = snprintf(line, sizeof line, " NA NA\n");
+        out_bytes(line, (size_t)len);
+    }
+}
+
 static int run_gpu(const options *o, const input *in)
 {
+    /* -E: the classification, read before any GPU is touched: a bad file ends the run here */
+    sat_classes classes;
+    memset(&classes, 0, sizeof classes);
+    if (o->classfile) {
+        char err[SAT_MAX_LINE_LEN + 256];
+        if (sat_read_classes(o->classfile, &in->db, &classes, err, sizeof err) != 0)
+            die("ERROR: %s\n", err);
+        if (classes.unknown)
+            fprintf(stderr, "WARNING: %d names of %s are not in the database\n", classes.unknown, o->classfile);
+        fprintf(stderr, "Read %d classes of %d of %d structures from %s\n", classes.distinct, classes.classified, in->db.count, o->classfile);
+    }
+    sat_eval *evals = o->classfile ? checked(calloc((size_t)in->num_queries + 1, sizeof(sat_eval))) : NULL;
     sat_multi *multi = open_multi(o, in);
     gpu_bufs B;
     alloc_gpu_bufs(o, in, &B);
@@ -1144,6 +1244,8 @@ static int run_gpu(const options *o, const input *in)
      * database's, both size classes: a query's two blocks carry the same line) */
     sat_fit *fits = o->fit ? checked(calloc((size_t)in->num_queries, sizeof(sat_fit))) : NULL;
     if (o->cluster && (o->nlevels ? sat_multi_cluster_begin_levels(multi, o->nlevels, o->levels) : sat_multi_cluster_begin(multi)) != SAT_OK)
+        die("ERROR: %s\n", sat_last_error());
+    if (o->classfile && sat_multi_eval_classes(multi, classes.node_class) != SAT_OK)
         die("ERROR: %s\n", sat_last_error());
     for (int q0 = 0; q0 < in->num_queries; q0 += B.batch) {
         const int nqb = in->num_queries - q0 < B.batch ? in->num_queries - q0 : B.batch;
@@ -1168,6 +1270,9 @@ static int run_gpu(const options *o, const input *in)
         /* -L, -H: the batch's edges into the graph(s) on the GPUs; query b is structure qindex[q0 + b] of the database */
         if (rc == SAT_OK && o->cluster)
             rc = o->nlevels ? sat_multi_cluster_add_levels(multi, in->qindex + q0) : sat_multi_cluster_add(multi, o->lmax, in->qindex + q0);
+        /* -E: the batch's rows scored where they are; query b is structure qindex[q0 + b] of the database */
+        if (rc == SAT_OK && o->classfile)
+            rc = sat_multi_eval_rows(multi, in->qindex + q0, o->rocn, evals + q0);
         if (rc < 0) {
             fprintf(stderr, "kernel launch failed: %s\n", sat_last_error());
             status = 1;
@@ -1193,7 +1298,7 @@ static int run_gpu(const options *o, const input *in)
                     o->ncand < total ? o->ncand : total, o->refine);
         fprintf(stderr, "%f million iterations/sec\n",
                 ((double)total * nqb * ((double)o->maxstart * SAT_MAXITER) / (ms / 1000)) / 1.0e6);
-        if (o->cluster)
+        if (o->cluster || o->classfile)
             continue;
         if (o->fit && !o->ranked)
             for (int b = 0; b < nqb; b++)
@@ -1204,7 +1309,9 @@ static int run_gpu(const options *o, const input *in)
      * GPU path's two blanks before the p-value */
     if (!status && o->cluster)
         status = o->nlevels ? print_cluster_levels(o, in, multi, fits) : print_clusters(o, in, multi, fits);
-    if (!status && !o->ranked && !o->cluster && in->cls_count[1] > 0)
+    if (!status && o->classfile)
+        print_eval(o, in, &classes, evals);
+    if (!status && !o->ranked && !o->cluster && !o->classfile && in->cls_count[1] > 0)
         for (int qi = 0; qi < in->num_queries; qi++) {
             print_header(in, qi, fits ? &fits[qi] : NULL);
             for (int d = 0; d < in->cls_count[1]; d++)
@@ -1215,6 +1322,8 @@ static int run_gpu(const options *o, const input *in)
     sat_multi_destroy(multi);
     free_gpu_bufs(&B);
     free(fits);
+    free(evals);
+    sat_classes_free(&classes);
     return status;
 }
 

@@ -22,6 +22,7 @@
 #include <pthread.h>
 #include <stdlib.h>
 #include <string.h>
+#include <strings.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -654,4 +655,138 @@ int sat_set_load_binary(const char *path, sat_struct_set *set)
     sat_set_free(set);
     *set = tmp;
     return 0;
+}
+
+/* ---- the class file of -E (sat_read_classes) */
+
+typedef struct { const char *name; int index; } class_name_ref;
+
+static int class_name_cmp(const void *a, const void *b)
+{
+    const class_name_ref *x = (const class_name_ref *)a, *y = (const class_name_ref *)b;
+    const int c = strcasecmp(x->name, y->name);
+    return c ? c : (x->index > y->index) - (x->index < y->index);
+}
+
+static uint32_t class_token_hash(const char *s)
+{
+    uint32_t h = 2166136261u;                                  /* FNV-1a */
+    for (; *s; s++) h = (h ^ (unsigned char)*s) * 16777619u;
+    return h;
+}
+
+/* the id of `token` in c->token, appended when new; slots: an open-addressed table of ids + 1, *nslots a power of two
+ * kept at least twice the tokens; -1: out of memory */
+static int class_token_id(sat_classes *c, const char *token, int **slots, size_t *nslots)
+{
+    if ((size_t)(c->distinct + 1) * 2 > *nslots) {
+        const size_t n = *nslots ? *nslots * 2 : 64;
+        int *grown = (int *)calloc(n, sizeof(int));
+        if (!grown) return -1;
+        for (int t = 0; t < c->distinct; t++) {
+            size_t at = class_token_hash(c->token[t]) & (n - 1);
+            while (grown[at]) at = (at + 1) & (n - 1);
+            grown[at] = t + 1;
+        }
+        free(*slots);
+        *slots = grown;
+        *nslots = n;
+    }
+    size_t at = class_token_hash(token) & (*nslots - 1);
+    for (; (*slots)[at]; at = (at + 1) & (*nslots - 1))
+        if (!strcmp(c->token[(*slots)[at] - 1], token)) return (*slots)[at] - 1;
+    char **tokens = (char **)realloc(c->token, sizeof(char *) * (size_t)(c->distinct + 1));
+    if (!tokens) return -1;
+    c->token = tokens;
+    const size_t len = strlen(token) + 1;
+    if (!(c->token[c->distinct] = (char *)malloc(len))) return -1;
+    memcpy(c->token[c->distinct], token, len);
+    (*slots)[at] = c->distinct + 1;
+    return c->distinct++;
+}
+
+void sat_classes_free(sat_classes *c)
+{
+    for (int t = 0; t < c->distinct; t++) free(c->token[t]);
+    free(c->token);
+    free(c->node_class);
+    memset(c, 0, sizeof *c);
+}
+
+int sat_read_classes(const char *path, const sat_struct_set *db, sat_classes *out, char *err, size_t err_len)
+{
+    memset(out, 0, sizeof *out);
+    if (err_len) err[0] = '\0';
+    FILE *fp = fopen(path, "r");
+    if (!fp) {
+        snprintf(err, err_len, "cannot open class file %s", path);
+        return -1;
+    }
+    const int n = db->count;
+    class_name_ref *names = (class_name_ref *)malloc(sizeof(class_name_ref) * (size_t)(n + 1));
+    int *line_of = (int *)calloc((size_t)n + 1, sizeof(int));              /* the line that classified an entry, 0 = none */
+    out->node_class = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n + 1));
+    out->entries = n;
+    char *line = NULL;
+    size_t cap = 0, nslots = 0;
+    int *slots = NULL, rc = 0, lineno = 0;
+    if (!names || !line_of || !out->node_class) {
+        snprintf(err, err_len, "out of memory");
+        rc = -1;
+    }
+    for (int v = 0; rc == 0 && v < n; v++) {
+        names[v].name = sat_set_name(db, v);
+        names[v].index = v;
+        out->node_class[v] = -1;
+    }
+    if (rc == 0) qsort(names, (size_t)n, sizeof *names, class_name_cmp);
+    while (rc == 0 && getline(&line, &cap, fp) >= 0) {
+        lineno++;
+        char *name = line + strspn(line, " \t\r\n\f\v");
+        if (*name == '\0' || *name == '#') continue;
+        char *end = name + strcspn(name, " \t\r\n\f\v");
+        char *cls = end + strspn(end, " \t\r\n\f\v");
+        if (*cls == '\0') {
+            snprintf(err, err_len, "%s line %d: no class after the name '%.64s'", path, lineno, name);
+            rc = -1;
+            break;
+        }
+        *end = '\0';
+        cls[strcspn(cls, " \t\r\n\f\v")] = '\0';
+        /* the entries of that name (case as -q looks SIDs up): the first of them in the sorted index, then its run */
+        int lo = 0, hi = n;
+        while (lo < hi) {
+            const int mid = lo + (hi - lo) / 2;
+            if (strcasecmp(names[mid].name, name) < 0) lo = mid + 1;
+            else hi = mid;
+        }
+        if (lo == n || strcasecmp(names[lo].name, name) != 0) {
+            out->unknown++;
+            continue;
+        }
+        if (line_of[names[lo].index]) {
+            snprintf(err, err_len, "%s line %d: the name '%.64s' is listed twice (first on line %d)", path, lineno, name,
+                     line_of[names[lo].index]);
+            rc = -1;
+            break;
+        }
+        const int id = class_token_id(out, cls, &slots, &nslots);
+        if (id < 0) {
+            snprintf(err, err_len, "out of memory");
+            rc = -1;
+            break;
+        }
+        for (; lo < n && strcasecmp(names[lo].name, name) == 0; lo++) {
+            line_of[names[lo].index] = lineno;
+            out->node_class[names[lo].index] = id;
+            out->classified++;
+        }
+    }
+    free(line);
+    free(slots);
+    free(names);
+    free(line_of);
+    fclose(fp);
+    if (rc != 0) sat_classes_free(out);
+    return rc;
 }

@@ -111,6 +111,27 @@ static inline const char *sat_set_name(const sat_struct_set *set, int s)
     return set->name + (size_t)s * (SAT_LABELSIZE + 1);
 }
 
+/*
+ * The class file of -E: a classification of the structures of a database.  Lines are "name class" with any white space
+ * between and around the two fields (whatever follows the class on the line is not read); the class is any token, e.g.
+ * a SCOP sccs cut to the wanted level; blank lines and lines whose first character is '#' are skipped; lines may be of
+ * any length, the last one need not end in a newline.  Class tokens become dense ids 0, 1, .. in order of first
+ * appearance.  A name is looked up in the database without regard to case, as -q looks a SID up, and classifies every
+ * entry of that name; a name that no entry has is counted in `unknown`; entries that no line names stay unclassified.
+ * Returns 0, or -1 with a message in err (the file cannot be opened, a line without a class, a name of the database
+ * listed twice - the message names the line -, no memory) and *out emptied.
+ */
+typedef struct sat_classes {
+    int32_t *node_class;   /* [entries] the class id of structure v of the database, -1 = unclassified */
+    char   **token;        /* [distinct] the class token of each id                                    */
+    int      entries;      /* the database's structures                                                */
+    int      distinct;     /* class ids in use                                                         */
+    int      classified;   /* structures with a class                                                  */
+    int      unknown;      /* lines whose name is not in the database                                  */
+} sat_classes;
+int sat_read_classes(const char *path, const sat_struct_set *db, sat_classes *out, char *err, size_t err_len);
+void sat_classes_free(sat_classes *c);
+
 #ifdef __cplusplus
 }
 #endif

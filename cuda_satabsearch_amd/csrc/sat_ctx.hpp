@@ -223,6 +223,17 @@ struct sat_ctx {
     DevBuf<int32_t> d_cl_parent, d_cl_out, d_cl_qnode;
     DevBuf<unsigned long long> d_cl_edges;
 
+    // evaluation against a classification (sat_eval_*, sat_eval.hip): the class of each of eval_nodes
+    // nodes (0 = none installed) on the host, of each resident entry on the device; scratch that only grows - every
+    // query's table [2][bins] of the call at hand, the queries' rows for the kernels, the results.  An upload drops the
+    // classes (free_db).
+    int eval_nodes = 0;
+    std::vector<int32_t> eval_class;
+    DevBuf<int32_t> d_entry_class;
+    DevBuf<uint32_t> d_eval_tab;
+    DevBuf<unsigned char> d_eval_q;
+    DevBuf<sat_eval> d_eval_rows;
+
     // bytes copied device -> host by this context's result calls (sat_stat_d2h_bytes)
     unsigned long long d2h_bytes = 0;
     // bytes copied host -> device by sat_queries_set / sat_queries_from_db (sat_stat_query_h2d_bytes)
@@ -240,6 +251,10 @@ int sat_db_load_code(sat_ctx *ctx);
 // ---- sat_cluster.hip.  Load that file's code object (an empty launch of a small kernel); drop the accumulator.
 int sat_cluster_load_code(sat_ctx *ctx);
 void sat_cluster_drop(sat_ctx *ctx);
+
+// ---- sat_eval.hip.  Load that file's code object (an empty launch of a small kernel); drop the installed classes.
+int sat_eval_load_code(sat_ctx *ctx);
+void sat_eval_drop(sat_ctx *ctx);
 
 // ---- sat_qfromdb.hip, for sat_multi_queries_from_db.  sat_queries_from_db on one shard's context, every check made by
 // the caller: query q has order n1s[q] and is entry code[q] >= 0 of this shard, or code[q] = -query_n1p(n1s[q]): a

@@ -52,6 +52,33 @@ inline int sat_check_refine(const void *ctx, const sat_hit *hits, int k, int can
     return SAT_OK;
 }
 
+// The evaluation against a classification (sat_eval_*, sat_eval.hip; sat_multi_eval_* make the same checks for every
+// shard before the first one works): the node count against the resident ordinals, installed classes, a call's rocn
+// and buffers (`buffers`: none is null), the node of every query - the message names the first bad one's position
+inline int sat_check_nodes(int n_nodes, uint32_t max_ordinal)
+{
+    if (n_nodes < 1) return sat_fail(SAT_EINVAL, "n_nodes must be >= 1 (got %d)", n_nodes);
+    if (max_ordinal >= (uint32_t)n_nodes)
+        return sat_fail(SAT_EINVAL, "n_nodes = %d, but a resident entry has ordinal %u in the whole database", n_nodes, max_ordinal);
+    return SAT_OK;
+}
+inline int sat_check_eval_classes(bool installed)
+{
+    return installed ? SAT_OK : sat_fail(SAT_ESTATE, "no classes installed (sat_eval_classes has not been called since the last database upload)");
+}
+inline int sat_check_eval_args(int rocn, bool buffers)
+{
+    if (rocn < 1) return sat_fail(SAT_EINVAL, "rocn must be >= 1 (got %d)", rocn);
+    return buffers ? SAT_OK : sat_fail(SAT_EINVAL, "null array");
+}
+inline int sat_check_query_nodes(int nq, const int32_t *query_node, int nodes)
+{
+    for (int q = 0; q < nq; q++)
+        if (query_node[q] < 0 || query_node[q] >= nodes)
+            return sat_fail(SAT_EINVAL, "query %d: node %d outside 0..%d", q, query_node[q], nodes - 1);
+    return SAT_OK;
+}
+
 // the rows a query returns of the c that qualify: all of them when max_rows <= 0
 inline int32_t sat_row_cap(int32_t c, int max_rows) { return max_rows > 0 && c > max_rows ? max_rows : c; }
 

@@ -41,6 +41,7 @@
 #include "host/sat_gumbel.h"
 #include "host/sat_shard.h"
 #include "host/sat_cluster.h"
+#include "host/sat_eval.h"
 
 namespace {
 
@@ -948,6 +949,44 @@ int sat_multi_cluster_labels_levels(sat_multi *m, int32_t *label, int32_t *degre
             return sat_fail(SAT_EDEVICE, "a shard returned a label outside 0..%d", m->n_entries - 1);
     const int broken = sat_cluster_nested((int)n, (int)levels, label);
     if (broken != 0) return sat_fail(SAT_EDEVICE, "the joined labels of level %d do not lie inside level %d's", broken - 1, broken);
+    return SAT_OK;
+}
+
+int sat_multi_eval_classes(sat_multi *m, const int32_t *node_class)
+{
+    SAT_TRY(check_multi(m));
+    // every shard's nodes are the whole database's; the same checks on the same arguments: the first refusal is every one's
+    for (sat_ctx *c : m->ctx) SAT_TRY(sat_eval_classes(c, m->n_entries, node_class));
+    return SAT_OK;
+}
+
+int sat_multi_eval_rows(sat_multi *m, const int32_t *query_node, int rocn, sat_eval *rows)
+{
+    SAT_TRY(check_multi(m));
+    if (m->ndev == 1) return sat_eval_rows(m->ctx[0], query_node, rocn, rows);      // no table crosses
+    // the checks of sat_eval_rows, made for all shards before the first one works
+    for (sat_ctx *c : m->ctx) {
+        SAT_TRY(sat_check_searched(c));
+        SAT_TRY(sat_check_eval_classes(c->eval_nodes > 0));
+    }
+    SAT_TRY(sat_check_eval_args(rocn, query_node && rows));
+    const int nq = (int)m->ctx[0]->queries.size();
+    SAT_TRY(sat_check_query_nodes(nq, query_node, m->ctx[0]->eval_nodes));
+    // each shard's tables of its own entries, packed in query order; integer counts add up, in any order
+    std::vector<size_t> off((size_t)nq + 1, 0);
+    for (int q = 0; q < nq; q++) off[(size_t)q + 1] = off[(size_t)q] + 2 * (size_t)sat_eval_bins(m->ctx[0]->queries[(size_t)q].n1);
+    std::vector<uint32_t> sum(off[(size_t)nq], 0u), part(off[(size_t)nq]);
+    for (int g = 0; g < m->ndev; g++) {
+        SAT_TRY(sat_eval_tables(m->ctx[(size_t)g], query_node, part.data(), nullptr));
+        for (size_t i = 0; i < sum.size(); i++) sum[i] += part[i];
+    }
+    for (int q = 0; q < nq; q++) {
+        const int32_t bins = sat_eval_bins(m->ctx[0]->queries[(size_t)q].n1), cls = m->ctx[0]->eval_class[(size_t)query_node[q]];
+        sat_eval_row row = { 0, 0, 0, 0, 0, cls < 0 ? -1 : cls };
+        if (cls >= 0 && sat_eval_reduce(sum.data() + off[(size_t)q], sum.data() + off[(size_t)q] + bins, bins, rocn, &row) != 0)
+            return sat_fail(SAT_EDEVICE, "query %d: the shards' tables do not add up to a table", q);
+        memcpy(rows + q, &row, sizeof row);
+    }
     return SAT_OK;
 }
 

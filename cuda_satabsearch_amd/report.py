@@ -103,3 +103,50 @@ def cluster_levels_table(labels, degrees):
     for j in range(lab.shape[0]):
         host.sat_cluster_reps(lab.shape[1], lab[j].ctypes.data, deg[j].ctypes.data, reps[j].ctypes.data, sizes[j].ctypes.data)
     return reps, sizes
+
+
+def eval_reduce(pos, neg, rocn=50):
+    """(u2, t2, positives, negatives, n_used) of one query's two score histograms (equal length, bin 0 the lowest
+    score): the sums behind its AUC = u2 / (2 positives negatives) and ROC-n = t2 / (2 positives n_used), by the one
+    reducing function of csrc/host/sat_eval.h that the device uses too (sat_eval_reduce)."""
+    import ctypes as C
+    import numpy as np
+    p = np.ascontiguousarray(pos, dtype=np.uint32).ravel()
+    g = np.ascontiguousarray(neg, dtype=np.uint32).ravel()
+    if p.shape != g.shape:
+        raise ValueError("pos and neg differ in length")
+    row = _native.Eval()
+    if _native.host_lib().sat_eval_reduce(p.ctypes.data, g.ctypes.data, len(p), int(rocn), C.byref(row)) != 0:
+        raise ValueError("a table needs bins >= 1, rocn >= 1 and fewer than 2^31 rows a side")
+    return int(row.u2), int(row.t2), int(row.positives), int(row.negatives), int(row.n_used)
+
+
+def eval_ratios(row):
+    """(auc, rocn) of a row of Searcher.eval_rows, None for both where the query has no positive or no negative"""
+    if row["positives"] <= 0 or row["negatives"] <= 0:
+        return None, None
+    return (int(row["u2"]) / (2.0 * float(row["positives"]) * float(row["negatives"])),
+            int(row["t2"]) / (2.0 * float(row["positives"]) * float(row["n_used"])))
+
+
+def eval_table(names, class_tokens, rows, dbfile, classfile, entries, classified, restarts, rocn, polish_all=0):
+    """The lines the command line's -E prints: names[q] the query's name, class_tokens[id] the token of a class id,
+    rows the records of Searcher.eval_rows for all queries in order."""
+    out = ["# EVAL dbfile = %s classes = %s entries = %d classified = %d distinct = %d restarts = %d rocn = %d"
+           % (dbfile, classfile, entries, classified, len(class_tokens), restarts, rocn)]
+    if polish_all:
+        out.append("# POLISH tops = %d all rows" % polish_all)
+    ratios = [eval_ratios(r) for r in rows]
+    both = [r for r in ratios if r[0] is not None]
+    auc_sum = rocn_sum = 0.0
+    for a, r in both:                                    # summed in query order, as the command line does
+        auc_sum += a
+        rocn_sum += r
+    out.append("# MEAN queries = %d auc = %.6f rocn = %.6f" % (len(both), auc_sum / len(both), rocn_sum / len(both)) if both
+               else "# MEAN queries = 0 auc = NA rocn = NA")
+    for name, row, (a, r) in zip(names, rows, ratios):
+        cls = int(row["query_class"])
+        out.append("%-8s %s %d %d %d %d %d %s %s" % (name, class_tokens[cls] if cls >= 0 else "-", row["positives"], row["negatives"],
+                                                    int(row["u2"]), int(row["t2"]), row["n_used"],
+                                                    "NA" if a is None else "%.6f" % a, "NA" if r is None else "%.6f" % r))
+    return out

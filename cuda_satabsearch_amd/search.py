@@ -109,6 +109,9 @@ _FIT_DTYPE = np.dtype([("a", np.float64), ("b", np.float64), ("rows", np.int32),
                        ("below", np.int32), ("fitted", np.int32)], align=True)
 assert _FIT_DTYPE.itemsize == C.sizeof(_native.Fit)
 STAT_BINS = _native.STAT_BINS
+_EVAL_DTYPE = np.dtype([("u2", np.uint64), ("t2", np.uint64), ("positives", np.int32), ("negatives", np.int32),
+                        ("n_used", np.int32), ("query_class", np.int32)], align=True)
+assert _EVAL_DTYPE.itemsize == C.sizeof(_native.Eval) == 32
 
 
 def _score_histogram(obj, fn, handle, nq):
@@ -222,6 +225,22 @@ def _cluster_labels_levels(obj, fn, handle, n_levels, n_nodes):
     return labels, degrees, edges
 
 
+def _eval_nodes(obj, query_nodes):
+    """the queries' nodes as the evaluation calls take them"""
+    nodes = np.ascontiguousarray(query_nodes, dtype=np.int32).ravel()
+    if len(nodes) != getattr(obj, "n_queries", 1):
+        raise ValueError("one node per query of the batch is needed")
+    return nodes
+
+
+def _eval_rows(obj, fn, handle, query_nodes, rocn):
+    """shared by Searcher / MultiSearcher.eval_rows"""
+    nodes = _eval_nodes(obj, query_nodes)
+    rows = np.zeros(len(nodes), _EVAL_DTYPE)
+    obj._check(fn(handle, nodes.ctypes.data, int(rocn), rows.ctypes.data))
+    return rows
+
+
 class Searcher:
     """One HIP device, one resident database shard, one current query."""
 
@@ -316,6 +335,7 @@ class Searcher:
                                             qssetypes.ctypes.data, int(query_ordinal)))
         self.n1 = n1
         self.n1max = n1
+        self._n1s = np.array([n1], np.int32)
         self.n_queries = 1
         self._batch = False
 
@@ -329,6 +349,7 @@ class Searcher:
                                               pitch, types.ctypes.data, int(first_query_ordinal)))
         self.n1 = int(n1s[0])
         self.n1max = int(n1s.max())
+        self._n1s = np.array(n1s, np.int32)
         self.n_queries = nq
         self._batch = True
 
@@ -343,6 +364,7 @@ class Searcher:
         n1s = self._orders[idx]
         self.n1 = int(n1s[0])
         self.n1max = int(n1s.max())
+        self._n1s = np.array(n1s, np.int32)
         self.n_queries = len(idx)
         self._batch = True
 
@@ -581,6 +603,33 @@ class Searcher:
         return _cluster_labels_levels(self, self._lib.sat_cluster_labels_levels, self._ctx, getattr(self, "_cluster_levels", 0),
                                       getattr(self, "_cluster_nodes", 0))
 
+    # ---- evaluation against a classification (sat_eval_*) -----------------------
+    def set_eval_classes(self, node_class):
+        """Install the classes of the nodes - the structures of the whole database in file order; int32, < 0 =
+        unclassified - or remove them (None).  An upload drops them (sat_eval_classes)."""
+        if node_class is None:
+            self._check(self._lib.sat_eval_classes(self._ctx, 0, None))
+            return
+        cls = np.ascontiguousarray(node_class, dtype=np.int32).ravel()
+        self._check(self._lib.sat_eval_classes(self._ctx, len(cls), cls.ctypes.data))
+
+    def eval_rows(self, query_nodes, rocn=50):
+        """Score the last search against the installed classes (sat_eval_rows): one record per query with the fields
+        u2, t2, positives, negatives, n_used, query_class; report.eval_ratios turns one into (AUC, ROC-n).  The tables
+        are made and reduced on the device: 32 bytes a query come back."""
+        return _eval_rows(self, self._lib.sat_eval_rows, self._ctx, query_nodes, rocn)
+
+    def eval_tables(self, query_nodes):
+        """The raw tables eval_rows reduces (sat_eval_tables), for shards and tests: a list with one uint32[2, bins]
+        array per query - positives, then negatives, by score; bins = 2 n1 (n1 - 1) + 1, bin = score + n1 (n1 - 1).
+        Integer counts: the tables of the shards of a database add up to the whole database's."""
+        nodes = _eval_nodes(self, query_nodes)
+        bins = 2 * self._n1s.astype(np.int64) * (self._n1s - 1) + 1
+        cuts = np.concatenate([[0], np.cumsum(2 * bins)])
+        counts = np.zeros(int(cuts[-1]), np.uint32)
+        self._check(self._lib.sat_eval_tables(self._ctx, nodes.ctypes.data, counts.ctypes.data, None))
+        return [counts[cuts[q]:cuts[q + 1]].reshape(2, int(bins[q])) for q in range(len(nodes))]
+
     def debug_set_scores(self, scores):
         """Test hook (satabsearch_debug.h): overwrite the last search's device scores with int32[nq, N]."""
         sc = np.ascontiguousarray(scores, dtype=np.int32)
@@ -810,6 +859,21 @@ class MultiSearcher:
         summed (sat_multi_cluster_labels_levels) - exactly what one searcher holding the whole database returns."""
         return _cluster_labels_levels(self, self._lib.sat_multi_cluster_labels_levels, self._m, getattr(self, "_cluster_levels", 0),
                                       self.n_entries)
+
+    def set_eval_classes(self, node_class):
+        """Searcher.set_eval_classes on every shard, over the whole database's nodes (sat_multi_eval_classes)."""
+        if node_class is None:
+            self._check(self._lib.sat_multi_eval_classes(self._m, None))
+            return
+        cls = np.ascontiguousarray(node_class, dtype=np.int32).ravel()
+        if len(cls) != self.n_entries:
+            raise ValueError("one class per structure of the database is needed")
+        self._check(self._lib.sat_multi_eval_classes(self._m, cls.ctypes.data))
+
+    def eval_rows(self, query_nodes, rocn=50):
+        """Searcher.eval_rows of the whole database: each shard makes the tables of its own entries, the host sums and
+        reduces them (sat_multi_eval_rows) - exactly what one searcher holding the whole database returns."""
+        return _eval_rows(self, self._lib.sat_multi_eval_rows, self._m, query_nodes, rocn)
 
     def set_statistics(self, fits):
         """Searcher.set_statistics on every shard (sat_multi_stats_set)."""

@@ -695,6 +695,43 @@ int sat_multi_cluster_labels(sat_multi *m, int32_t *label, int32_t *degree, unsi
 int sat_multi_cluster_begin_levels(sat_multi *m, int n_levels, const double *max_pvalue);
 int sat_multi_cluster_add_levels(sat_multi *m, const int32_t *query_node);
 int sat_multi_cluster_labels_levels(sat_multi *m, int32_t *label, int32_t *degree, unsigned long long *edges);
+/*
+ * A search scored against a classification of the database, on the GPUs (the definitions and the one
+ * reducing function are in csrc/host/sat_eval.h).  Nodes are the structures of the whole database in file order, as for
+ * the clustering; node_class[v] >= 0 is node v's class, < 0 means unclassified.
+ *
+ * sat_eval_classes   installs the classes of n_nodes nodes: the class of every resident entry is kept on the device.
+ *                    NULL removes them; a database upload drops them.  SAT_ESTATE without a database; SAT_EINVAL, and
+ *                    nothing changes, for n_nodes < 1 or a resident entry whose ordinal is >= n_nodes.
+ * sat_eval_rows      scores the LAST search (it never searches: SAT_ESTATE before one, and without installed classes):
+ *                    query q is node query_node[q], of class c = node_class[query_node[q]].  Its counted rows are the
+ *                    resident entries that are classified and are not the query's own node; a counted row is a positive
+ *                    when its class is c, else a negative; rows are ranked by the raw score (polished where the search
+ *                    was; an installed fit does not matter).  rows[q] is the struct below: with Pabove(s) the positives
+ *                    above score s,
+ *                        u2 = sum over s of neg[s] * (2 * Pabove(s) + pos[s]),   AUC   = u2 / (2 * positives * negatives)
+ *                        t2 = the same sum over the first n_used = min(rocn, negatives) negatives from the top, a tie
+ *                             group sharing what is left evenly,                 ROC-n = t2 / (2 * positives * n_used)
+ *                    (both undefined when positives or negatives is 0).  A query whose own class is < 0 gets an all-zero
+ *                    row with query_class = -1.  The tables are built and reduced on the device: 24 bytes a query go up
+ *                    and exactly 32 come back.  The result buffers, an installed fit and a cluster accumulator are left
+ *                    alone; a second call gives the same rows.  SAT_EINVAL, and nothing changes: rocn < 1, a null
+ *                    pointer, a node outside 0 .. n_nodes - 1 (the message names its position).
+ * sat_eval_tables    the raw tables instead of their reduction, for shards and tests: query q of order n1 has
+ *                    bins = 2 * n1 * (n1 - 1) + 1 scores -n1 (n1 - 1) .. n1 (n1 - 1) (a score outside is clamped in);
+ *                    its table is pos[bins] then neg[bins], bin = score + n1 (n1 - 1), and starts at counts[offset[q]].
+ *                    offset = NULL packs the tables one after the other in query order (the sum of 2 * bins words).
+ *                    Checks as sat_eval_rows.  Integer counts: the tables of the shards of a database add up.
+ * sat_multi_eval_*   the same over every shard, exactly what one context holding the whole database returns, bit for
+ *                    bit: n_nodes is the database size; each shard makes the tables of its own entries, the host sums
+ *                    them and reduces (ndev * the tables' bytes cross to it); with one shard no table crosses.
+ */
+typedef struct sat_eval { uint64_t u2, t2; int32_t positives, negatives, n_used, query_class; } sat_eval; /* 32 bytes */
+int sat_eval_classes(sat_ctx *ctx, int n_nodes, const int32_t *node_class);
+int sat_eval_rows(sat_ctx *ctx, const int32_t *query_node, int rocn, sat_eval *rows);
+int sat_eval_tables(sat_ctx *ctx, const int32_t *query_node, uint32_t *counts, const int64_t *offset);
+int sat_multi_eval_classes(sat_multi *m, const int32_t *node_class);
+int sat_multi_eval_rows(sat_multi *m, const int32_t *query_node, int rocn, sat_eval *rows);
 unsigned long long sat_multi_stat_d2h_bytes(const sat_multi *m);
 
 /*

@@ -11,5 +11,6 @@ name=$1; shift
 srcs=$(cd $repo && python -c "from cuda_satabsearch_amd import build; print(' '.join(build.CSRC + '/' + f for f in build.DEVICE_SOURCES))")
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -fPIC -shared "$@" \
   -I $repo/include -I $repo/cuda_satabsearch_amd/csrc -o $repo/cuda_satabsearch_amd/libsat_$name.so $srcs \
-  -Wl,$repo/cuda_satabsearch_amd/sat_gumbel.o -Wl,$repo/cuda_satabsearch_amd/sat_shard.o -Wl,$repo/cuda_satabsearch_amd/sat_cluster.o -lm -ldl
+  -Wl,$repo/cuda_satabsearch_amd/sat_gumbel.o -Wl,$repo/cuda_satabsearch_amd/sat_shard.o -Wl,$repo/cuda_satabsearch_amd/sat_cluster.o \
+  -Wl,$repo/cuda_satabsearch_amd/sat_eval.o -lm -ldl
 echo "built cuda_satabsearch_amd/libsat_$name.so"
