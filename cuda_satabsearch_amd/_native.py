@@ -38,9 +38,13 @@ ABI_SYMBOLS = (
     "sat_cluster_begin_levels", "sat_cluster_add_levels", "sat_cluster_labels_levels",
     "sat_multi_cluster_begin_levels", "sat_multi_cluster_add_levels", "sat_multi_cluster_labels_levels",
     "sat_eval_classes", "sat_eval_rows", "sat_eval_tables", "sat_multi_eval_classes", "sat_multi_eval_rows",
+    "sat_cover_begin", "sat_cover_add", "sat_cover_solve", "sat_cover_end",
+    "sat_multi_cover_begin", "sat_multi_cover_add", "sat_multi_cover_solve",
 )
 
 MAX_CLUSTER_LEVELS = 8
+# rounds of the cover's solve queued between two looks at its `done` flag (SAT_COVER_ROUND_BATCH of include/satabsearch.h)
+COVER_ROUND_BATCH = 64
 # rows of one query a block of eval_histogram (csrc/sat_eval.hip: kEvalRows) counts, and the bins a side its LDS holds
 EVAL_BLOCK_ROWS = 4096
 EVAL_WINDOW_BINS = 2048
@@ -198,6 +202,15 @@ def device_lib():
             lib.sat_eval_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             lib.sat_multi_eval_classes.argtypes = [C.c_void_p, C.c_void_p]
             lib.sat_multi_eval_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        # (as above: a build of the parent commit predates the cover)
+        if hasattr(lib, "sat_cover_begin"):
+            lib.sat_cover_begin.argtypes = [C.c_void_p, C.c_int]
+            lib.sat_cover_add.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
+            lib.sat_cover_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.sat_cover_end.argtypes = [C.c_void_p]
+            lib.sat_multi_cover_begin.argtypes = [C.c_void_p]
+            lib.sat_multi_cover_add.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
+            lib.sat_multi_cover_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.sat_hits_cutoff.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         lib.sat_multi_search_cutoff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                                 C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
@@ -269,6 +282,8 @@ def host_lib():
         lib.sat_cluster_reps.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.sat_cluster_nested.argtypes = [C.c_int, C.c_int, C.c_void_p]
         lib.sat_eval_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Eval)]
+        lib.sat_cover_sizes.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+        lib.sat_cover_greedy.argtypes = [C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _host = lib
     return _host
 

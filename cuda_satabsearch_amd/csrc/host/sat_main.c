@@ -45,7 +45,10 @@
  * -Q dbfile: score the search against a classification - per query the AUC and the ROC-n, default n = 50, of its ranking
  * of the classified structures, from two score histograms made and reduced on the GPUs, sat_eval.h: 32 bytes a query come
  * back, and one line per query is printed, "name class positives negatives u2 t2 n_used auc rocn", under "# EVAL ..." and
- * "# MEAN ..." instead of any rows).
+ * "# MEAN ..." instead of any rows), -D P (with -a dbfile: cluster the database around representatives - a greedy cover of
+ * the graph of the rows whose p-value is <= P, kept as a bit matrix and solved on the GPUs, sat_cover.h: every structure is
+ * a direct hit of its representative - and print -L's four columns, the degree counting distinct neighbours, under a
+ * "# COVER ..." header).
  */
 #include <math.h>
 #include <stdarg.h>
@@ -59,6 +62,7 @@
 
 #include "satabsearch.h"
 #include "sat_cluster.h"
+#include "sat_cover.h"
 #include "sat_gumbel.h"
 #include "sat_host_search.h"
 #include "sat_parse.h"
@@ -92,6 +96,10 @@ static double now_ms(void)
 #pragma weak sat_multi_cluster_add_levels
 #pragma weak sat_multi_cluster_labels_levels
 #pragma weak sat_cluster_nested
+#pragma weak sat_multi_cover_begin
+#pragma weak sat_multi_cover_add
+#pragma weak sat_multi_cover_solve
+#pragma weak sat_cover_sizes
 #pragma weak sat_multi_eval_classes
 #pragma weak sat_multi_eval_rows
 
@@ -99,7 +107,7 @@ static void usage(const char *prog)
 {
     fprintf(stderr, "Usage: %s [-c] [-q dbfile | -Q dbfile | -a dbfile] [-r restarts] [-g gpus] [-G gpu,gpu,...] [-s seed]\n"
                     "       [-k K] [-p P] [-m M] [-M M] [-R restarts [-C C]] [-F censor] [-P T] [-A] [-L P] [-b] [-H P1,P2,...]\n"
-                    "       [-E classfile [-N n]]\n", prog);
+                    "       [-E classfile [-N n]] [-D P]\n", prog);
     fprintf(stderr, "  -c : run on host CPU not GPU card\n");
     fprintf(stderr, "  -q dbfile : database is read from dbfile, list of query\n"
                     "              ids is read from stdin\n");
@@ -142,6 +150,11 @@ static void usage(const char *prog)
                     "         negatives) and rocn = t2 / (2 positives n_used) rank the classified structures other than the\n"
                     "         query itself by raw score, ties counted half (not with -c, -k, -p, -m, -M, -R, -C, -F, -L, -H)\n");
     fprintf(stderr, "  -N n : with -E: the negatives ROC-n counts up to (n >= 1). Default 50\n");
+    fprintf(stderr, "  -D P : with -a dbfile: cluster the database around representatives on the GPU - a greedy cover of the graph\n"
+                    "         of the rows whose p-value is <= P (0..1): every structure is a direct hit of its representative\n"
+                    "         and no two representatives are hits of each other; prints one line per structure:\n"
+                    "         name representative cluster_size degree, the degree counting distinct neighbours\n"
+                    "         (not with -c, -k, -p, -m, -M, -R, -C, -L, -H, -E)\n");
     fprintf(stderr, "  -b : cache the parsed database as dbfile.satbin\n");
     exit(1);
 }
@@ -293,6 +306,8 @@ typedef struct {
     double lmax;                      /* -L: the largest p-value of an edge */
     int nlevels;                      /* -H: the cutoffs' count (then cluster is set too: the run is -L's but for its adds and its table) */
     double levels[SAT_MAX_CLUSTER_LEVELS];  /* -H: the largest p-value of an edge of each level, ascending */
+    int cover;                        /* -D: cluster around representatives (then cluster is set too: the run is -L's but for its adds and its table) */
+    double dmax;                      /* -D: the largest p-value of an edge */
     const char *classfile;            /* -E: score the search against this classification instead of printing rows */
     int rocn;                         /* -N: the negatives ROC-n counts up to (0: not given) */
     unsigned long long seed;
@@ -436,7 +451,7 @@ static void parse_options(int argc, char *argv[], options *o)
 {
     *o = (options){ .use_gpu = 1, .maxstart = 128, .want_gpus = 1, .seed = SAT_DEFAULT_SEED };
     int c;
-    while ((c = getopt(argc, argv, "cq:Q:a:r:g:G:s:bk:p:m:M:R:C:F:P:AL:H:E:N:")) != -1) {
+    while ((c = getopt(argc, argv, "cq:Q:a:r:g:G:s:bk:p:m:M:R:C:F:P:AL:H:E:N:D:")) != -1) {
         char *end = NULL;
         long v;
         switch (c) {
@@ -471,6 +486,15 @@ static void parse_options(int argc, char *argv[], options *o)
                 usage(argv[0]);
             }
             o->cluster = 1;
+            break;
+        case 'D':
+            /* the whole argument, a finite number in [0, 1] */
+            o->dmax = strtod(optarg, &end);
+            if (end == optarg || *end != '\0' || !isfinite(o->dmax) || o->dmax < 0.0 || o->dmax > 1.0) {
+                fprintf(stderr, "ERROR: -D needs a p-value in [0, 1] (got '%s')\n", optarg);
+                usage(argv[0]);
+            }
+            o->cover = 1;
             break;
         case 'H':
             /* the whole argument: 1 .. SAT_MAX_CLUSTER_LEVELS numbers, each as -L's, with commas between, strictly ascending */
@@ -537,6 +561,24 @@ static void parse_options(int argc, char *argv[], options *o)
         }
     }
     if (o->rocn && !o->classfile) die("ERROR: -N needs -E classfile\n");
+    if (o->cover) {
+        /* clustering around representatives: -L's run with another accumulator and another table */
+        if (!o->use_gpu) die("ERROR: -D cannot be combined with -c\n");
+        if (!o->all) die("ERROR: -D needs -a dbfile\n");
+        if (o->topk) die("ERROR: -D cannot be combined with -k\n");
+        if (o->cutoff) die("ERROR: -D cannot be combined with -p\n");
+        if (o->nmatch) die("ERROR: -D cannot be combined with -m\n");
+        if (o->rowmatch) die("ERROR: -D cannot be combined with -M\n");
+        if (o->refine) die("ERROR: -D cannot be combined with -R\n");
+        if (o->ncand) die("ERROR: -D cannot be combined with -C\n");
+        if (o->cluster) die("ERROR: -D cannot be combined with -L\n");
+        if (o->nlevels) die("ERROR: -D cannot be combined with -H\n");
+        if (o->classfile) die("ERROR: -D cannot be combined with -E\n");
+        if (!sat_multi_search_only || !sat_multi_cover_begin || !sat_multi_cover_add || !sat_multi_cover_solve || !sat_cover_sizes)
+            die("ERROR: this library has no sat_multi_cover_add\n");
+        if (o->fit && !sat_multi_search_fit) die("ERROR: this library has no sat_multi_search_fit\n");
+        o->cluster = 1;                              /* (-L's own checks below ask nothing these have not) */
+    }
     if (o->classfile) {
         /* evaluation: a run over queries of the database whose rows stay on the GPUs */
         if (!o->use_gpu) die("ERROR: -E cannot be combined with -c\n");
@@ -967,7 +1009,7 @@ static int search_batch(const options *o, const input *in, sat_multi *multi, gpu
 {
     const int lorder = in->lorder, lsoln = in->lsoln, maxstart = o->maxstart;
     if (o->cluster || o->classfile) {
-        /* -L, -E: the rows stay on the GPUs (no gather, no LSOLN: no map is printed); with -F the fit is installed there */
+        /* -L, -H, -D, -E: the rows stay on the GPUs (no gather, no LSOLN: no map is printed); with -F the fit is installed there */
         if (o->fit)
             return sat_multi_search_fit(multi, lorder, 0, maxstart, o->censor, fits, ms);
         return sat_multi_search_only(multi, lorder, 0, maxstart, ms);
@@ -1114,6 +1156,45 @@ static int print_clusters(const options *o, const input *in, sat_multi *multi, c
     return 0;
 }
 
+/* -D: the table of the cover the GPUs solved - representatives and degrees (8 bytes a structure), the edge and round
+ * counts; the sizes are sat_cover_sizes'.  The library has checked the cover's two invariants before it returned */
+static int print_cover(const options *o, const input *in, sat_multi *multi, const sat_fit *fits)
+{
+    const int n = in->db.count;
+    int32_t *rep = checked(malloc(sizeof(int32_t) * (size_t)n * 3)), *degree = rep + n, *size = degree + n;
+    unsigned long long edges = 0;
+    int rounds = 0;
+    if (sat_multi_cover_solve(multi, rep, degree, &edges, &rounds) != SAT_OK) {
+        fprintf(stderr, "clustering failed: %s\n", sat_last_error());
+        free(rep);
+        return 1;
+    }
+    const int clusters = sat_cover_sizes(n, rep, size);
+    if (clusters < 0)
+        die("ERROR: the GPUs returned representatives that are no cover\n");
+    int singletons = 0, fitted = 0;
+    for (int v = 0; v < n; v++)
+        singletons += size[v] == 1;
+    char line[SAT_MAX_LINE_LEN + 256];
+    int len = snprintf(line, sizeof line, "# COVER dbfile = %s entries = %d pvalue <= %g restarts = %d clusters = %d singletons = %d "
+                       "edges = %llu rounds = %d\n", in->dbfile, n, o->dmax, o->maxstart, clusters, singletons, edges, rounds);
+    out_bytes(line, (size_t)len);
+    out_bytes(polish_header, strlen(polish_header));
+    if (fits) {
+        for (int v = 0; v < n; v++)
+            fitted += fits[v].fitted != 0;
+        len = snprintf(line, sizeof line, "# GUMBEL censor = %g fitted = %d of %d\n", o->censor, fitted, n);
+        out_bytes(line, (size_t)len);
+    }
+    for (int v = 0; v < n; v++) {
+        len = snprintf(line, sizeof line, "%-8s %-8s %d %d\n", sat_set_name(&in->db, v), sat_set_name(&in->db, rep[v]), size[v],
+                       degree[v]);
+        out_bytes(line, (size_t)len);
+    }
+    free(rep);
+    return 0;
+}
+
 /* -H: the tables of the L clusterings the GPUs hold, side by side - per level what print_clusters prints for it: 8 bytes
  * a structure, level and shard cross to the host; the levels must be nested (sat_cluster_nested) */
 static int print_cluster_levels(const options *o, const input *in, sat_multi *multi, const sat_fit *fits)
@@ -1243,7 +1324,8 @@ static int run_gpu(const options *o, const input *in)
     /* -F: every query's fit - from the GPUs with -k / -p, else made here from the listing's scores (the whole
      * database's, both size classes: a query's two blocks carry the same line) */
     sat_fit *fits = o->fit ? checked(calloc((size_t)in->num_queries, sizeof(sat_fit))) : NULL;
-    if (o->cluster && (o->nlevels ? sat_multi_cluster_begin_levels(multi, o->nlevels, o->levels) : sat_multi_cluster_begin(multi)) != SAT_OK)
+    if (o->cluster && (o->cover ? sat_multi_cover_begin(multi) : o->nlevels ? sat_multi_cluster_begin_levels(multi, o->nlevels, o->levels)
+                                                               : sat_multi_cluster_begin(multi)) != SAT_OK)
         die("ERROR: %s\n", sat_last_error());
     if (o->classfile && sat_multi_eval_classes(multi, classes.node_class) != SAT_OK)
         die("ERROR: %s\n", sat_last_error());
@@ -1267,9 +1349,10 @@ static int run_gpu(const options *o, const input *in)
                             : sat_multi_queries_set(multi, nqb, B.n1s, B.qtabs, B.qdmats, SAT_MAXDIM, B.qtypes, (uint32_t)q0);
         if (rc == SAT_OK)
             rc = search_batch(o, in, multi, &B, fits ? fits + q0 : NULL, &ms, &ms_stage2);
-        /* -L, -H: the batch's edges into the graph(s) on the GPUs; query b is structure qindex[q0 + b] of the database */
+        /* -L, -H, -D: the batch's edges into the graph(s) on the GPUs; query b is structure qindex[q0 + b] of the database */
         if (rc == SAT_OK && o->cluster)
-            rc = o->nlevels ? sat_multi_cluster_add_levels(multi, in->qindex + q0) : sat_multi_cluster_add(multi, o->lmax, in->qindex + q0);
+            rc = o->cover ? sat_multi_cover_add(multi, o->dmax, in->qindex + q0)
+                 : o->nlevels ? sat_multi_cluster_add_levels(multi, in->qindex + q0) : sat_multi_cluster_add(multi, o->lmax, in->qindex + q0);
         /* -E: the batch's rows scored where they are; query b is structure qindex[q0 + b] of the database */
         if (rc == SAT_OK && o->classfile)
             rc = sat_multi_eval_rows(multi, in->qindex + q0, o->rocn, evals + q0);
@@ -1308,7 +1391,7 @@ static int run_gpu(const options *o, const input *in)
     /* the listing's deferred block: every query's large-class rows, after all small-class blocks, with the reference
      * GPU path's two blanks before the p-value */
     if (!status && o->cluster)
-        status = o->nlevels ? print_cluster_levels(o, in, multi, fits) : print_clusters(o, in, multi, fits);
+        status = o->cover ? print_cover(o, in, multi, fits) : o->nlevels ? print_cluster_levels(o, in, multi, fits) : print_clusters(o, in, multi, fits);
     if (!status && o->classfile)
         print_eval(o, in, &classes, evals);
     if (!status && !o->ranked && !o->cluster && !o->classfile && in->cls_count[1] > 0)

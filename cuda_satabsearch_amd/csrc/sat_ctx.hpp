@@ -223,6 +223,16 @@ struct sat_ctx {
     DevBuf<int32_t> d_cl_parent, d_cl_out, d_cl_qnode;
     DevBuf<unsigned long long> d_cl_edges;
 
+    // clustering around representatives (sat_cover_*, sat_cover.hip): the accumulator over cover_nodes nodes
+    // (0 = none) - the adjacency bit matrix, [nodes] rows of sat_cover_stride(nodes) words (host/sat_cover.h); the
+    // `unassigned` mask and then the representatives' mask, a row's words each; rep [nodes] then degree [nodes] in one
+    // array; the solve's state words (the round's key, done, rounds, the degrees' sum, the broken invariants); the batch's
+    // node of each query.  It shares no word with the single-linkage accumulator above: a context may hold both.  An
+    // upload drops it (free_db).
+    int cover_nodes = 0;
+    DevBuf<unsigned long long> d_cv_adj, d_cv_mask, d_cv_state;
+    DevBuf<int32_t> d_cv_out, d_cv_qnode;
+
     // evaluation against a classification (sat_eval_*, sat_eval.hip): the class of each of eval_nodes
     // nodes (0 = none installed) on the host, of each resident entry on the device; scratch that only grows - every
     // query's table [2][bins] of the call at hand, the queries' rows for the kernels, the results.  An upload drops the
@@ -251,6 +261,14 @@ int sat_db_load_code(sat_ctx *ctx);
 // ---- sat_cluster.hip.  Load that file's code object (an empty launch of a small kernel); drop the accumulator.
 int sat_cluster_load_code(sat_ctx *ctx);
 void sat_cluster_drop(sat_ctx *ctx);
+
+// ---- sat_cover.hip.  Load that file's code object (an empty launch of a small kernel); drop the accumulator; and for
+// sat_multi_cover_solve: rows row0 .. row0 + rows - 1 of the context's adjacency matrix to the host (counted in its
+// d2h bytes), and such rows ORed into the context's own.
+int sat_cover_load_code(sat_ctx *ctx);
+void sat_cover_drop(sat_ctx *ctx);
+int sat_cover_rows_fetch(sat_ctx *ctx, int row0, int rows, unsigned long long *host);
+int sat_cover_rows_or(sat_ctx *ctx, int row0, int rows, const unsigned long long *host);
 
 // ---- sat_eval.hip.  Load that file's code object (an empty launch of a small kernel); drop the installed classes.
 int sat_eval_load_code(sat_ctx *ctx);

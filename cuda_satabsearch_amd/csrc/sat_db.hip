@@ -35,6 +35,7 @@ void free_db(sat_ctx *ctx)
     ctx->d_ordinal.reset();
     ctx->max_ordinal = 0;
     sat_cluster_drop(ctx);                    // its nodes were this database's
+    sat_cover_drop(ctx);                      // and the cover accumulator's
     sat_eval_drop(ctx);                       // and so were the classes'
     ctx->d_lists.reset();
     ctx->d_scores.reset();

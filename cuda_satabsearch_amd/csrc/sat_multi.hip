@@ -41,6 +41,7 @@
 #include "host/sat_gumbel.h"
 #include "host/sat_shard.h"
 #include "host/sat_cluster.h"
+#include "host/sat_cover.h"
 #include "host/sat_eval.h"
 
 namespace {
@@ -950,6 +951,43 @@ int sat_multi_cluster_labels_levels(sat_multi *m, int32_t *label, int32_t *degre
     const int broken = sat_cluster_nested((int)n, (int)levels, label);
     if (broken != 0) return sat_fail(SAT_EDEVICE, "the joined labels of level %d do not lie inside level %d's", broken - 1, broken);
     return SAT_OK;
+}
+
+int sat_multi_cover_begin(sat_multi *m)
+{
+    SAT_TRY(check_multi(m));
+    // every shard's nodes are the whole database's: its rows end at its own entries' ordinals, but start anywhere
+    for (sat_ctx *c : m->ctx) SAT_TRY(sat_cover_begin(c, m->n_entries));
+    return SAT_OK;
+}
+
+int sat_multi_cover_add(sat_multi *m, double max_pvalue, const int32_t *query_node)
+{
+    SAT_TRY(check_multi(m));
+    // the argument checks of sat_cover_add, made for all shards before the first one adds anything
+    if (!query_node) return sat_fail(SAT_EINVAL, "query_node is null");
+    SAT_TRY(sat_check_pvalue(max_pvalue));
+    SAT_TRY(sat_check_query_nodes((int)m->ctx[0]->queries.size(), query_node, m->n_entries));
+    return each_shard(m, [&](int g) { return sat_cover_add(m->ctx[(size_t)g], max_pvalue, query_node); });
+}
+
+int sat_multi_cover_solve(sat_multi *m, int32_t *rep, int32_t *degree, unsigned long long *edges, int *rounds)
+{
+    SAT_TRY(check_multi(m));
+    if (!rep) return sat_fail(SAT_EINVAL, "rep buffer is null");
+    // The other shards' matrices ORed into shard 0's, through the host, a slab of rows at a time (32 MB at most, or one
+    // row).  An OR adds edges of the whole graph only and is idempotent: shard 0 may be added to and solved again
+    const int n = m->n_entries;
+    const size_t stride = sat_cover_stride(n);
+    const int slab = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)32 << 20) / (stride * sizeof(unsigned long long))));
+    std::vector<unsigned long long> rows(m->ndev > 1 ? (size_t)slab * stride : 0);
+    for (int g = 1; g < m->ndev; g++)
+        for (int row0 = 0; row0 < n; row0 += slab) {
+            const int count = std::min(slab, n - row0);
+            SAT_TRY(sat_cover_rows_fetch(m->ctx[(size_t)g], row0, count, rows.data()));
+            SAT_TRY(sat_cover_rows_or(m->ctx[0], row0, count, rows.data()));
+        }
+    return sat_cover_solve(m->ctx[0], rep, degree, edges, rounds);
 }
 
 int sat_multi_eval_classes(sat_multi *m, const int32_t *node_class)

@@ -105,6 +105,36 @@ def cluster_levels_table(labels, degrees):
     return reps, sizes
 
 
+def cover_greedy(n, a, b):
+    """(rep int32[n], degrees int32[n], rounds) of the greedy cover of the graph on n nodes with the edges (a[i], b[i]):
+    the specification of csrc/host/sat_cover.h in plain C (sat_cover_greedy), for rows that never saw a GPU - what
+    Searcher.cover_solve returns for the same edges.  Self pairs are no edges; repeats and both directions are one."""
+    import numpy as np
+    ea = np.ascontiguousarray(a, dtype=np.int32).ravel()
+    eb = np.ascontiguousarray(b, dtype=np.int32).ravel()
+    if ea.shape != eb.shape:
+        raise ValueError("a and b differ in length")
+    n = int(n)
+    rep = np.empty(max(n, 0), np.int32)
+    deg = np.empty(max(n, 0), np.int32)
+    rounds = _native.host_lib().sat_cover_greedy(n, len(ea), ea.ctypes.data, eb.ctypes.data, rep.ctypes.data, deg.ctypes.data)
+    if rounds < 0:
+        raise ValueError("n must be >= 1 and every node must lie in 0 .. n - 1")
+    return rep, deg, rounds
+
+
+def cover_sizes(rep):
+    """(sizes int32[n], clusters) of a cover table: sizes[v] = the members of v's cluster (sat_cover_sizes of
+    csrc/host/sat_cover.h, which the command line's -D prints from)."""
+    import numpy as np
+    r = np.ascontiguousarray(rep, dtype=np.int32).ravel()
+    sizes = np.empty(len(r), np.int32)
+    clusters = _native.host_lib().sat_cover_sizes(len(r), r.ctypes.data, sizes.ctypes.data)
+    if clusters < 0:
+        raise ValueError("rep is no cover table: rep[rep[v]] must be rep[v], in 0 .. n - 1")
+    return sizes, clusters
+
+
 def eval_reduce(pos, neg, rocn=50):
     """(u2, t2, positives, negatives, n_used) of one query's two score histograms (equal length, bin 0 the lowest
     score): the sums behind its AUC = u2 / (2 positives negatives) and ROC-n = t2 / (2 positives n_used), by the one

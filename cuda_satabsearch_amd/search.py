@@ -225,6 +225,16 @@ def _cluster_labels_levels(obj, fn, handle, n_levels, n_nodes):
     return labels, degrees, edges
 
 
+def _cover_solve(obj, fn, handle, n_nodes):
+    """shared by Searcher / MultiSearcher.cover_solve: (rep int32[n], degrees int32[n], edges, rounds)"""
+    rep = np.zeros(n_nodes, np.int32)
+    degrees = np.zeros(n_nodes, np.int32)
+    edges = C.c_ulonglong(0)
+    rounds = C.c_int(0)
+    obj._check(fn(handle, rep.ctypes.data, degrees.ctypes.data, C.byref(edges), C.byref(rounds)))
+    return rep, degrees, int(edges.value), int(rounds.value)
+
+
 def _eval_nodes(obj, query_nodes):
     """the queries' nodes as the evaluation calls take them"""
     nodes = np.ascontiguousarray(query_nodes, dtype=np.int32).ravel()
@@ -603,6 +613,33 @@ class Searcher:
         return _cluster_labels_levels(self, self._lib.sat_cluster_labels_levels, self._ctx, getattr(self, "_cluster_levels", 0),
                                       getattr(self, "_cluster_nodes", 0))
 
+    # ---- clustering around representatives (sat_cover_*) ----------------------
+    def cover_begin(self, n_nodes=None):
+        """Start (or restart, emptied) the cover accumulator over n_nodes nodes (default as cluster_begin): the graph
+        itself as a bit matrix on the device, n_nodes^2 / 8 bytes.  It lives beside a cluster accumulator."""
+        n = self.n_entries if n_nodes is None else int(n_nodes)
+        self._check(self._lib.sat_cover_begin(self._ctx, n))
+        self._cover_nodes = n
+
+    def cover_add(self, max_pvalue, query_nodes):
+        """cluster_add's rows as UNDIRECTED edges of the graph (sat_cover_add): a pair seen twice or in both directions
+        is one edge.  Nothing is copied back."""
+        _cluster_add(self, self._lib.sat_cover_add, self._ctx, max_pvalue, query_nodes)
+
+    def cover_solve(self):
+        """(rep int32[n_nodes], degrees int32[n_nodes]: distinct neighbours, edges: distinct pairs, rounds: the clusters
+        of two or more members) of the greedy cover of what has been added so far (sat_cover_solve): every node is its
+        representative or adjacent to it, no two representatives are adjacent.  More cover_add calls may follow.
+        report.cover_sizes turns rep into cluster sizes."""
+        if not getattr(self, "_cover_nodes", 0):
+            self._check(self._lib.sat_cover_solve(self._ctx, None, None, None, None))     # the library's state error
+        return _cover_solve(self, self._lib.sat_cover_solve, self._ctx, self._cover_nodes)
+
+    def cover_end(self):
+        """Free the cover accumulator (sat_cover_end)."""
+        self._check(self._lib.sat_cover_end(self._ctx))
+        self._cover_nodes = 0
+
     # ---- evaluation against a classification (sat_eval_*) -----------------------
     def set_eval_classes(self, node_class):
         """Install the classes of the nodes - the structures of the whole database in file order; int32, < 0 =
@@ -843,6 +880,19 @@ class MultiSearcher:
         """Searcher.cluster_labels of the whole database: the shards' labels joined, degrees and edges summed
         (sat_multi_cluster_labels) - exactly what one searcher holding the whole database returns."""
         return _cluster_labels(self, self._lib.sat_multi_cluster_labels, self._m, self.n_entries)
+
+    def cover_begin(self):
+        """Searcher.cover_begin on every shard, over the whole database's nodes (sat_multi_cover_begin)."""
+        self._check(self._lib.sat_multi_cover_begin(self._m))
+
+    def cover_add(self, max_pvalue, query_nodes):
+        """Searcher.cover_add on every shard: each adds the rows of its own entries to its own matrix."""
+        _cluster_add(self, self._lib.sat_multi_cover_add, self._m, max_pvalue, query_nodes)
+
+    def cover_solve(self):
+        """Searcher.cover_solve of the whole database: the shards' matrices ORed onto the first shard's device and solved
+        there (sat_multi_cover_solve) - exactly what one searcher holding the whole database returns."""
+        return _cover_solve(self, self._lib.sat_multi_cover_solve, self._m, self.n_entries)
 
     def cluster_begin_levels(self, pvalues):
         """Searcher.cluster_begin_levels on every shard, over the whole database's nodes (sat_multi_cluster_begin_levels)."""

@@ -550,6 +550,42 @@ int sat_cluster_begin_levels(sat_ctx *ctx, int n_nodes, int n_levels, const doub
 int sat_cluster_add_levels(sat_ctx *ctx, const int32_t *query_node);
 int sat_cluster_labels_levels(sat_ctx *ctx, int32_t *label, int32_t *degree, unsigned long long *edges);
 
+/*
+ * ---- Clustering the database around representatives: a greedy cover of the graph itself, kept on the device (DESIGN.md
+ * 6r; the specification, the matrix layout and a plain-C restatement are in csrc/host/sat_cover.h).
+ * Nodes, rows and the double tested are those of the single-linkage calls above.  A qualifying row whose two ends differ
+ * is the UNDIRECTED edge {query_node[q], ordinal of e}: seen in both directions, or twice, it is ONE edge - unlike above,
+ * where rows are counted.  The context keeps the adjacency as a bit matrix: n_nodes rows of ceil(n_nodes / 64) 64-bit
+ * words, n_nodes^2 / 8 bytes (15 000 nodes: 28 MB).
+ *   degree[v]  the DISTINCT neighbours of v
+ *   edges      the distinct unordered pairs: the degrees' sum halved, 64 bits
+ *   rep[v]     v's representative under the greedy cover: with every node unassigned, the unassigned node with the largest
+ *              gain = 1 + its unassigned neighbours (ties: the smallest index) takes them as its cluster, and they leave;
+ *              when the largest gain is 1 every node left is its own representative
+ *   rounds     the clusters of two or more members
+ * So every node is its representative or a neighbour of it, and no two representatives are neighbours; the solve checks
+ * both on the device before it returns (SAT_EDEVICE if either is broken).  Everything is a function of the edge SET:
+ * nothing depends on the launch shape, the batches, the order or repetition of the add calls, or the sharding.
+ *
+ * sat_cover_begin   start (or restart, emptied) the accumulator over n_nodes nodes; checks as sat_cluster_begin.  A matrix
+ *                   that does not fit is SAT_ENOMEM, with the bytes it needs in the message.  It is an accumulator of its
+ *                   own: the single-linkage one, plain or leveled, may live beside it on the context and neither sees the
+ *                   other.
+ * sat_cover_add     add the qualifying rows of the last search; arguments, checks, copies to the device and stream order
+ *                   as sat_cluster_add.  NOTHING comes back: sat_stat_d2h_bytes does not move.
+ * sat_cover_solve   wait, run the rounds and copy rep[n_nodes] (required: NULL is SAT_EINVAL), degree[n_nodes], *edges and
+ *                   *rounds (each may be NULL).  The matrix is only read: more adds and another solve may follow.  The
+ *                   rounds are queued SAT_COVER_ROUND_BATCH at a time and the host reads one 8-byte flag per batch, so
+ *                   the call copies exactly 4 * n_nodes (+ 4 * n_nodes with degree) + 24 + 8 * (rounds /
+ *                   SAT_COVER_ROUND_BATCH + 1) bytes, whether edges and rounds are asked for or not.
+ * sat_cover_end     free the accumulator.  A database upload drops it too; query changes and searches keep it.
+ */
+#define SAT_COVER_ROUND_BATCH 64
+int sat_cover_begin(sat_ctx *ctx, int n_nodes);
+int sat_cover_add(sat_ctx *ctx, double max_pvalue, const int32_t *query_node);
+int sat_cover_solve(sat_ctx *ctx, int32_t *rep, int32_t *degree, unsigned long long *edges, int *rounds);
+int sat_cover_end(sat_ctx *ctx);
+
 /* Bytes this context's result calls (sat_results, sat_search, sat_topk, sat_topk_hits, sat_hits_cutoff, the pair searches) have copied
  * from the device to the host since it was created (diagnostics: the best-k path moves O(k) rows). */
 unsigned long long sat_stat_d2h_bytes(const sat_ctx *ctx);
@@ -695,6 +731,15 @@ int sat_multi_cluster_labels(sat_multi *m, int32_t *label, int32_t *degree, unsi
 int sat_multi_cluster_begin_levels(sat_multi *m, int n_levels, const double *max_pvalue);
 int sat_multi_cluster_add_levels(sat_multi *m, const int32_t *query_node);
 int sat_multi_cluster_labels_levels(sat_multi *m, int32_t *label, int32_t *degree, unsigned long long *edges);
+/* The cover over every shard, exactly what one context holding the whole database returns: every shard keeps a matrix
+ * over the WHOLE database's nodes, into which sat_multi_cover_add adds the rows of its own entries (checks as
+ * sat_multi_cluster_add, made before any shard adds).  sat_multi_cover_solve ORs the matrices of the shards 1 .. ndev - 1
+ * into shard 0's, through the host - n_nodes * ceil(n_nodes / 64) * 8 bytes down and up again per extra shard, once per
+ * solve - and solves there; an OR is idempotent, so shard 0's matrix stays a part of the whole graph and more adds and
+ * solves may follow.  With one shard no matrix crosses. */
+int sat_multi_cover_begin(sat_multi *m);
+int sat_multi_cover_add(sat_multi *m, double max_pvalue, const int32_t *query_node);
+int sat_multi_cover_solve(sat_multi *m, int32_t *rep, int32_t *degree, unsigned long long *edges, int *rounds);
 /*
  * A search scored against a classification of the database, on the GPUs (the definitions and the one
  * reducing function are in csrc/host/sat_eval.h).  Nodes are the structures of the whole database in file order, as for
