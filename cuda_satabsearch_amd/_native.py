@@ -33,6 +33,7 @@ ABI_SYMBOLS = (
     "sat_search_pairs_polish", "sat_search_refine_polish", "sat_multi_search_pairs_polish", "sat_multi_search_refine_polish",
     "sat_polish_all_set", "sat_polish_all_get", "sat_results_base", "sat_multi_polish_all_set",
     "sat_queries_from_db", "sat_multi_queries_from_db", "sat_stat_query_h2d_bytes",
+    "sat_queries_from_db_sses", "sat_multi_queries_from_db_sses",
     "sat_cluster_begin", "sat_cluster_add", "sat_cluster_labels", "sat_cluster_end",
     "sat_multi_search_only", "sat_multi_cluster_begin", "sat_multi_cluster_add", "sat_multi_cluster_labels",
     "sat_cluster_begin_levels", "sat_cluster_add_levels", "sat_cluster_labels_levels",
@@ -177,6 +178,12 @@ def device_lib():
             lib.sat_stat_query_h2d_bytes.restype = C.c_uint64
             lib.sat_debug_query_blob.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]      # include/satabsearch_debug.h
             lib.sat_debug_query_blob.restype = C.c_longlong
+        # (as above: a build of the parent commit predates the motif queries)
+        if hasattr(lib, "sat_queries_from_db_sses"):
+            lib.sat_queries_from_db_sses.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+            lib.sat_multi_queries_from_db_sses.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+            lib.sat_debug_multi_ctx.argtypes = [C.c_void_p, C.c_int]                          # include/satabsearch_debug.h
+            lib.sat_debug_multi_ctx.restype = C.c_void_p
         # (as above: a build of the parent commit predates the clustering)
         if hasattr(lib, "sat_cluster_begin"):
             lib.sat_cluster_begin.argtypes = [C.c_void_p, C.c_int]

@@ -49,6 +49,11 @@
  * the graph of the rows whose p-value is <= P, kept as a bit matrix and solved on the GPUs, sat_cover.h: every structure is
  * a direct hit of its representative - and print -L's four columns, the degree counting distinct neighbours, under a
  * "# COVER ..." header).
+ * Motif queries: with -q dbfile and -Q dbfile a stdin line may be SID@list, the list (sat_parse_sse_list: 2,1,8,5,3 or
+ * 1-3,9 - 1-based, as pytableaucreate.py -s takes it, but kept in the order given) naming the SSEs of that entry the
+ * query is made of.  The block gets a header line "# QUERY SSES = 2,1,8,5,3" after "# DBFILE" and is otherwise printed
+ * as for a stand-alone query structure of the list's length; -Q builds such a batch on the GPUs
+ * (sat_multi_queries_from_db_sses), -q cuts the sub-arrays on the host.
  */
 #include <math.h>
 #include <stdarg.h>
@@ -87,6 +92,7 @@ static double now_ms(void)
 #pragma weak sat_multi_search_refine_polish
 #pragma weak sat_multi_polish_all_set
 #pragma weak sat_multi_queries_from_db
+#pragma weak sat_multi_queries_from_db_sses
 #pragma weak sat_multi_search_only
 #pragma weak sat_multi_cluster_begin
 #pragma weak sat_multi_cluster_add
@@ -113,6 +119,9 @@ static void usage(const char *prog)
                     "              ids is read from stdin\n");
     fprintf(stderr, "  -Q dbfile : as -q dbfile, same output; the queries are built on the GPU from the resident\n"
                     "              database instead of on the host (GPU mode)\n");
+    fprintf(stderr, "  SID@list : (-q, -Q) a stdin line may name a motif: the listed SSEs of the entry, 1-based, commas and\n"
+                    "              ranges, in the order given, e.g. d1ubia_@2,1,8,5,3 or d1ubia_@1-3,5 (header line # QUERY SSES);\n"
+                    "              such a line holds at most %d characters, and may end in CR LF\n", SAT_MAX_LINE_LEN - 2);
     fprintf(stderr, "  -a dbfile : all-vs-all: every entry of dbfile is a query, in file order, built as with -Q;\n"
                     "              stdin is not read (GPU mode)\n");
     fprintf(stderr, "  -r restarts : number of restarts. Default %d\n", 128);
@@ -329,8 +338,29 @@ typedef struct {
     int num_queries;
     const sat_struct_set *qsrc;       /* where the queries' structures are: queries, or db with -q */
     int *qindex;                      /* query i is structure qindex[i] of qsrc */
+    /* motif queries (SID@list with -q / -Q): query i is the listed SSEs of that structure, in the list's order */
+    int motifs;                       /* how many of the queries are motifs; 0: qsub, sse_begin and sse are NULL */
+    char **qlist;                     /* [num_queries] with -q / -Q: the list's text as read, NULL for a whole structure */
+    int *qsub;                        /* the motif's own structure - the sub-arrays - in `queries`, -1 for a whole one */
+    int32_t *sse_begin;               /* [num_queries + 1] CSR into sse; an empty range is a whole structure */
+    uint8_t *sse;                     /* the lists, 0-based */
     int *cls_index[2], cls_count[2];  /* db entries of the small (order <= 96) and the large class, file order */
 } input;
+
+/* Where query qi's structure is: its set and (*s) its index there - a motif's sub-structure, else the entry itself */
+static const sat_struct_set *query_set(const input *in, int qi, int *s)
+{
+    const int motif = in->motifs && in->qsub[qi] >= 0;
+    *s = motif ? in->qsub[qi] : in->qindex[qi];
+    return motif ? &in->queries : in->qsrc;
+}
+
+static int query_order(const input *in, int qi)
+{
+    int s;
+    const sat_struct_set *set = query_set(in, qi, &s);
+    return set->order[s];
+}
 
 /* Per-entry results on the host: slot m of row r at r * nm + m (nm = M of -m, else 1).  counts: each row's matches
  * (-m), or NULL: one.  maps: SAT_MAXDIM ints a slot with LSOLN, else NULL. */
@@ -412,6 +442,15 @@ static void print_header(const input *in, int qi, const sat_fit *f)
     out_bytes(line, (size_t)n);
     n = snprintf(line, sizeof line, "# DBFILE = %-80s\n", in->dbfile);
     out_bytes(line, (size_t)n);
+    if (in->motifs && in->qsub[qi] >= 0) {
+        /* the list as numbers, 1-based, ranges expanded, in the order given */
+        out_bytes("# QUERY SSES = ", 15);
+        for (int32_t k = in->sse_begin[qi]; k < in->sse_begin[qi + 1]; k++) {
+            n = snprintf(line, sizeof line, k > in->sse_begin[qi] ? ",%d" : "%d", in->sse[k] + 1);
+            out_bytes(line, (size_t)n);
+        }
+        out_bytes("\n", 1);
+    }
     out_bytes(polish_header, strlen(polish_header));
     begin_query_stats(f);
     if (!f)
@@ -698,6 +737,21 @@ static void read_queries(const options *o, input *in)
             in->sids = checked(realloc(in->sids, (size_t)(in->num_queries + 1) * (SAT_LABELSIZE + 1)));
             char *sid = in->sids + (size_t)in->num_queries++ * (SAT_LABELSIZE + 1);
             memset(sid, 0, SAT_LABELSIZE + 1);
+            /* SID@list: the SID is what stands before the first '@', the list the rest of the line */
+            char *list = strchr(buf, '@');
+            in->qlist = checked(realloc(in->qlist, sizeof(char *) * (size_t)in->num_queries));
+            in->qlist[in->num_queries - 1] = NULL;
+            if (list) {
+                /* a list is never cut in two: a line that fills the buffer would go on as the next query */
+                if (strlen(buf) == SAT_MAX_LINE_LEN - 1 && buf[SAT_MAX_LINE_LEN - 2] != '\n')
+                    die("ERROR: query line with a list is longer than %d characters\n", SAT_MAX_LINE_LEN - 2);
+                *list++ = '\0';
+                list[strcspn(list, "\n")] = '\0';
+                if (*list && list[strlen(list) - 1] == '\r')         /* a CRLF line: as a 7-character SID's is cut off */
+                    list[strlen(list) - 1] = '\0';
+                in->qlist[in->num_queries - 1] = checked(strdup(list));
+                in->motifs++;
+            }
             strncpy(sid, buf, SAT_LABELSIZE);
             sid[SAT_LABELSIZE - 1] = '\0';
             size_t len = strlen(sid);
@@ -723,6 +777,43 @@ static void read_queries(const options *o, input *in)
         fprintf(stderr, "WARNING: LTYPE is always set to T\n");
         in->ltype = 1;
     }
+}
+
+/* Motif queries, once every query's entry is known: each list checked against its entry's order (a bad one ends the run
+ * here, before any search), and the motif's own structure - packed cell (i, k) is the entry's cell (max, min) of (l[i],
+ * l[k]) - appended to in->queries under the entry's name: what -q and -c search and what every mode prints from */
+static void cut_motifs(input *in)
+{
+    uint8_t list[SAT_MAXDIM], *tab = checked(malloc(SAT_MAXDIM * (SAT_MAXDIM + 1) / 2));
+    float *dist = checked(malloc(sizeof(float) * SAT_MAXDIM * (SAT_MAXDIM + 1) / 2));
+    in->qsub = checked(malloc(sizeof(int) * (size_t)in->num_queries));
+    in->sse_begin = checked(calloc((size_t)in->num_queries + 1, sizeof(int32_t)));
+    in->sse = checked(malloc((size_t)in->motifs * SAT_MAXDIM));
+    for (int q = 0; q < in->num_queries; q++) {
+        const int e = in->qindex[q];
+        in->qsub[q] = -1;
+        in->sse_begin[q + 1] = in->sse_begin[q];
+        if (!in->qlist[q])
+            continue;
+        char err[128];
+        const int m = sat_parse_sse_list(in->qlist[q], in->db.order[e], list, err, sizeof err);
+        if (m < 0)
+            die("ERROR: query %s@%s: %s\n", in->sids + (size_t)q * (SAT_LABELSIZE + 1), in->qlist[q], err);
+        const int64_t base = in->db.cell_off[e];
+        for (int i = 0; i < m; i++)
+            for (int k = 0; k <= i; k++) {
+                const int hi = list[i] > list[k] ? list[i] : list[k], lo = list[i] > list[k] ? list[k] : list[i];
+                tab[i * (i + 1) / 2 + k] = in->db.tab[base + hi * (hi + 1) / 2 + lo];
+                dist[i * (i + 1) / 2 + k] = in->db.dist[base + hi * (hi + 1) / 2 + lo];
+            }
+        in->qsub[q] = sat_set_append(&in->queries, sat_set_name(&in->db, e), m, tab, dist);
+        if (in->qsub[q] < 0)
+            die("ERROR: no memory for query %s@%s\n", in->sids + (size_t)q * (SAT_LABELSIZE + 1), in->qlist[q]);
+        memcpy(in->sse + in->sse_begin[q], list, (size_t)m);
+        in->sse_begin[q + 1] += m;
+    }
+    free(tab);
+    free(dist);
 }
 
 /* The database (-b: its binary image when that is newer than the file), split into the two size classes; then each
@@ -786,12 +877,20 @@ static void load_database(const options *o, input *in)
             die("ERROR: query %s not found\n", sid);
         in->qindex[i] = found;
     }
+    if (in->motifs)
+        cut_motifs(in);
 }
 
 static void free_input(input *in)
 {
     free(in->qindex);
     free(in->sids);
+    for (int i = 0; in->qlist && i < in->num_queries; i++)
+        free(in->qlist[i]);
+    free(in->qlist);
+    free(in->qsub);
+    free(in->sse_begin);
+    free(in->sse);
     free(in->cls_index[0]);
     free(in->cls_index[1]);
     sat_set_free(&in->queries);
@@ -824,13 +923,14 @@ static int run_host(const options *o, const input *in)
     const int passes = in->cls_count[1] > 0 ? 2 : 1;
     for (int k = 0; k < passes; k++)
         for (int qi = 0; qi < in->num_queries; qi++) {
-            const int qs = in->qindex[qi];
+            int qs;
+            const sat_struct_set *qset = query_set(in, qi, &qs);
             if (!o->fit)
                 print_header(in, qi, NULL);
             fprintf(stderr, "Executing simulated annealing tableaux match kernel on host for query %s...\n",
-                    sat_set_name(in->qsrc, qs));
+                    sat_set_name(qset, qs));
             double t1 = now_ms();
-            if (sat_host_search(&in->db, in->cls_index[k], in->cls_count[k], in->qsrc, qs, in->lorder, in->lsoln,
+            if (sat_host_search(&in->db, in->cls_index[k], in->cls_count[k], qset, qs, in->lorder, in->lsoln,
                                 o->maxstart, &stream, one.scores, one.maps) != 0)
                 die("malloc failed in host search\n");
             double ms = now_ms() - t1;
@@ -841,11 +941,11 @@ static int run_host(const options *o, const input *in)
                 /* the block's own rows: the one stream runs class after class, so a block is fitted when it is printed */
                 for (int d = 0; d < in->cls_count[k]; d++)
                     fit_orders[d] = in->db.order[in->cls_index[k][d]];
-                sat_fit f = fit_scores(one.scores, in->cls_count[k], in->qsrc->order[qs], fit_orders, o->censor);
+                sat_fit f = fit_scores(one.scores, in->cls_count[k], qset->order[qs], fit_orders, o->censor);
                 print_header(in, qi, &f);
             }
             for (int d = 0; d < in->cls_count[k]; d++)
-                print_entry(in, in->cls_index[k][d], in->qsrc->order[qs], NULL, NULL, &one, (size_t)d, 0);
+                print_entry(in, in->cls_index[k][d], qset->order[qs], NULL, NULL, &one, (size_t)d, 0);
         }
     free(one.scores);
     free(one.maps);
@@ -873,6 +973,7 @@ typedef struct {
     slots rowm;                       /* -M: the slots of the batch's ranked rows, row r of hits */
     int32_t *rowm_restarts, *pair_q, *pair_e;   /* -M: each slot's restart; the rows as (query, entry) pairs */
     size_t rowm_cap;                  /* -M: rows they hold */
+    int32_t *sse_begin;               /* -Q with motif queries: the batch's list offsets, batch + 1 of them */
 } gpu_bufs;
 
 static void alloc_slots(slots *s, size_t rows, int nm, int with_counts, int lsoln)
@@ -923,6 +1024,8 @@ static void alloc_gpu_bufs(const options *o, const input *in, gpu_bufs *B)
         alloc_hits(B, (size_t)B->kk * B->batch, lsoln);  /* only K rows per query (and GPU) ever leave the GPUs */
     }
     B->n1s = checked(malloc(sizeof(int32_t) * (size_t)B->batch));
+    if (o->from_db && in->motifs)
+        B->sse_begin = checked(malloc(sizeof(int32_t) * ((size_t)B->batch + 1)));
     if (o->from_db)
         return;
     B->qtabs = checked(calloc((size_t)B->batch * SAT_MAXDIM * SAT_MAXDIM, 1));
@@ -956,6 +1059,7 @@ static void alloc_rowm(gpu_bufs *B, size_t rows, int nm, int lsoln)
 static void free_gpu_bufs(gpu_bufs *B)
 {
     free(B->n1s);
+    free(B->sse_begin);
     free(B->qtabs);
     free(B->qtypes);
     free(B->qdmats);
@@ -1307,6 +1411,8 @@ static int run_gpu(const options *o, const input *in)
             fprintf(stderr, "WARNING: %d names of %s are not in the database\n", classes.unknown, o->classfile);
         fprintf(stderr, "Read %d classes of %d of %d structures from %s\n", classes.distinct, classes.classified, in->db.count, o->classfile);
     }
+    if (o->from_db && in->motifs && !sat_multi_queries_from_db_sses)
+        die("ERROR: this library has no sat_multi_queries_from_db_sses\n");
     sat_eval *evals = o->classfile ? checked(calloc((size_t)in->num_queries + 1, sizeof(sat_eval))) : NULL;
     sat_multi *multi = open_multi(o, in);
     gpu_bufs B;
@@ -1332,20 +1438,27 @@ static int run_gpu(const options *o, const input *in)
     for (int q0 = 0; q0 < in->num_queries; q0 += B.batch) {
         const int nqb = in->num_queries - q0 < B.batch ? in->num_queries - q0 : B.batch;
         for (int b = 0; b < nqb; b++) {
-            const int qs = in->qindex[q0 + b];
-            B.n1s[b] = in->qsrc->order[qs];
+            int qs;
+            const sat_struct_set *qset = query_set(in, q0 + b, &qs);
+            B.n1s[b] = qset->order[qs];
             if (o->from_db)
                 continue;
             uint8_t *tab = B.qtabs + (size_t)b * SAT_MAXDIM * SAT_MAXDIM;
-            sat_set_expand(in->qsrc, qs, SAT_MAXDIM, tab, B.qdmats + (size_t)b * SAT_MAXDIM * SAT_MAXDIM);
+            sat_set_expand(qset, qs, SAT_MAXDIM, tab, B.qdmats + (size_t)b * SAT_MAXDIM * SAT_MAXDIM);
             for (int i = 0; i < B.n1s[b]; i++)
                 B.qtypes[(size_t)b * SAT_MAXDIM + i] = tab[i * SAT_MAXDIM + i];
         }
         fprintf(stderr, "Executing simulated annealing tableaux match kernel on GPU for %d quer%s (from %s)...\n",
                 nqb, nqb == 1 ? "y" : "ies", sat_set_name(in->qsrc, in->qindex[q0]));
         double ms = 0.0, ms_stage2 = 0.0;
-        /* -Q, -a: the batch from its entries' indices in the database the GPUs hold */
-        int rc = o->from_db ? sat_multi_queries_from_db(multi, nqb, in->qindex + q0, (uint32_t)q0)
+        /* -Q, -a: the batch from its entries' indices in the database the GPUs hold; where the run has a motif, with
+         * the batch's lists, their offsets counted from the batch's first */
+        if (o->from_db && in->motifs)
+            for (int b = 0; b <= nqb; b++)
+                B.sse_begin[b] = in->sse_begin[q0 + b] - in->sse_begin[q0];
+        int rc = o->from_db && in->motifs ? sat_multi_queries_from_db_sses(multi, nqb, in->qindex + q0, B.sse_begin,
+                                                                           in->sse + in->sse_begin[q0], (uint32_t)q0)
+                 : o->from_db ? sat_multi_queries_from_db(multi, nqb, in->qindex + q0, (uint32_t)q0)
                             : sat_multi_queries_set(multi, nqb, B.n1s, B.qtabs, B.qdmats, SAT_MAXDIM, B.qtypes, (uint32_t)q0);
         if (rc == SAT_OK)
             rc = search_batch(o, in, multi, &B, fits ? fits + q0 : NULL, &ms, &ms_stage2);
@@ -1398,7 +1511,7 @@ static int run_gpu(const options *o, const input *in)
         for (int qi = 0; qi < in->num_queries; qi++) {
             print_header(in, qi, fits ? &fits[qi] : NULL);
             for (int d = 0; d < in->cls_count[1]; d++)
-                print_entry(in, in->cls_index[1][d], in->qsrc->order[in->qindex[qi]], NULL, NULL, &B.large,
+                print_entry(in, in->cls_index[1][d], query_order(in, qi), NULL, NULL, &B.large,
                             (size_t)qi * in->cls_count[1] + d, 1);
         }
     fprintf(stderr, "copied %llu bytes of results from the GPU(s)\n", sat_multi_stat_d2h_bytes(multi));

@@ -790,3 +790,71 @@ int sat_read_classes(const char *path, const sat_struct_set *db, sat_classes *ou
     if (rc != 0) sat_classes_free(out);
     return rc;
 }
+
+/* ---- the SSE list of a motif query (sat_parse.h) */
+
+/* a run of decimal digits at *at as a number (capped well above any order), *at moved past it; -1: no digit there */
+static int sse_number(const char **at)
+{
+    const char *p = *at;
+    int v = 0;
+    if (*p < '0' || *p > '9')
+        return -1;
+    for (; *p >= '0' && *p <= '9'; p++)
+        if (v < 1000000)
+            v = v * 10 + (*p - '0');
+    *at = p;
+    return v;
+}
+
+int sat_parse_sse_list(const char *text, int order, uint8_t *out, char *err, size_t err_len)
+{
+    unsigned char seen[SAT_MAXDIM + 1] = { 0 };
+    int m = 0;
+    if (order < 1 || order > SAT_MAXDIM) {
+        snprintf(err, err_len, "order %d outside 1..%d", order, SAT_MAXDIM);
+        return -1;
+    }
+    for (const char *at = text;; at++) {
+        const int a = sse_number(&at);
+        int b = a;
+        if (a < 0) {
+            /* where a number has to start: nothing, a comma, a sign - an item without its number; else text */
+            if (*at == '\0' || *at == ',' || *at == '-')
+                snprintf(err, err_len, "empty item");
+            else
+                snprintf(err, err_len, "trailing text '%.16s'", at);
+            return -1;
+        }
+        if (*at == '-') {
+            at++;
+            b = sse_number(&at);
+            if (b < 0) {
+                snprintf(err, err_len, "range %d- without its end", a);
+                return -1;
+            }
+            if (b < a) {
+                snprintf(err, err_len, "range %d-%d descends", a, b);
+                return -1;
+            }
+        }
+        for (int v = a; v <= b; v++) {
+            if (v < 1 || v > order) {
+                snprintf(err, err_len, "SSE %d out of range 1..%d", v, order);
+                return -1;
+            }
+            if (seen[v]) {
+                snprintf(err, err_len, "SSE %d twice", v);
+                return -1;
+            }
+            seen[v] = 1;
+            out[m++] = (uint8_t)(v - 1);
+        }
+        if (*at == '\0')
+            return m;
+        if (*at != ',') {
+            snprintf(err, err_len, "trailing text '%.16s'", at);
+            return -1;
+        }
+    }
+}

@@ -132,6 +132,16 @@ typedef struct sat_classes {
 int sat_read_classes(const char *path, const sat_struct_set *db, sat_classes *out, char *err, size_t err_len);
 void sat_classes_free(sat_classes *c);
 
+/*
+ * The SSE list of a motif query, "SID@list" on the stdin of -q / -Q (the syntax of pytableaucreate.py -s): items
+ * separated by commas, an item a number N or a range A-B with A <= B, decimal digits only, 1-BASED, every number within
+ * 1..order and listed once, the whole text consumed.  The order of the list is kept: out[i], 0-BASED as the library
+ * takes it (sat_queries_from_db_sses), is the entry's SSE that query SSE i is; out holds `order` bytes.  Returns the
+ * list's length m, 1 <= m <= order, or -1 with what is wrong in err: "SSE 9 out of range 1..8", "SSE 3 twice", "empty
+ * item", "range 5-2 descends", "trailing text 'x'".
+ */
+int sat_parse_sse_list(const char *text, int order, uint8_t *out, char *err, size_t err_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -120,7 +120,8 @@ struct sat_ctx {
     std::vector<QueryInfo> queries;
     DevBuf<uint8_t> d_qblob;                // per query: qdist | qcode | qtypes | qpair (query_blob)
     // queries taken from the resident shard (sat_queries_from_db, sat_qfromdb.hip): the entry of each query as it came
-    // from the host, each query's offset in the blob as the device summed them; only grow
+    // from the host (with sat_queries_from_db_sses followed by the lists' offsets and the list bytes), each query's
+    // offset in the blob as the device summed them; only grow
     DevBuf<int32_t> d_qentry;
     DevBuf<unsigned long long> d_qoff;
     DevBuf<SatQuery> d_qdesc;               // descriptors grouped by size class
@@ -277,7 +278,14 @@ void sat_eval_drop(sat_ctx *ctx);
 // ---- sat_qfromdb.hip, for sat_multi_queries_from_db.  sat_queries_from_db on one shard's context, every check made by
 // the caller: query q has order n1s[q] and is entry code[q] >= 0 of this shard, or code[q] = -query_n1p(n1s[q]): a
 // query whose entry another shard holds - it takes its room in the blob and the caller copies its bytes in afterwards.
-int sat_qfromdb_set(sat_ctx *ctx, int n_queries, const int32_t *code, const int32_t *n1s, uint32_t first_query_ordinal);
+// sse_begin, sse: null, or the lists of sat_queries_from_db_sses (n1s[q] is then the list's length where query q has
+// one); only the lists of the shard's own queries are read, so the caller may leave the other ranges empty.
+int sat_qfromdb_set(sat_ctx *ctx, int n_queries, const int32_t *code, const int32_t *n1s, const int32_t *sse_begin,
+                    const uint8_t *sse, uint32_t first_query_ordinal);
+// the checks of sat_queries_from_db_sses' lists, SAT_EINVAL with the message set: the offsets of the batch; the list of
+// m SSEs of query q, which is entry `entry` of that order
+int sat_qfromdb_check_offsets(int n_queries, const int32_t *sse_begin, const uint8_t *sse);
+int sat_qfromdb_check_list(int q, int entry, int order, const uint8_t *list, int m);
 // where query q lies in the context's blob, and its size
 void sat_qfromdb_segment(const sat_ctx *ctx, int q, uint8_t **at, size_t *bytes);
 

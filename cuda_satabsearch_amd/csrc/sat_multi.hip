@@ -36,6 +36,7 @@
 #include <utility>
 #include <vector>
 
+#include "satabsearch_debug.h"
 #include "sat_pairs.hpp"
 #include "sat_cutoff.hpp"
 #include "host/sat_gumbel.h"
@@ -465,16 +466,19 @@ int sat_multi_queries_set(sat_multi *m, int n_queries, const int32_t *n1s, const
     return SAT_OK;
 }
 
-int sat_multi_queries_from_db(sat_multi *m, int n_queries, const int32_t *entry, uint32_t first_query_ordinal)
+// sat_multi_queries_from_db (sse_begin null) and sat_multi_queries_from_db_sses: the lists are checked against the order
+// of each query's entry on the shard that holds it, and every shard is sent the lists of its own queries alone - the
+// others' ranges are empty there, their room in the blob follows from the code
+static int multi_queries_from_db(sat_multi *m, int n_queries, const int32_t *entry, const int32_t *sse_begin, const uint8_t *sse,
+                                 uint32_t first_query_ordinal)
 {
-    SAT_TRY(sat_check_context(m));
-    if (n_queries < 1 || !entry) return sat_fail(SAT_EINVAL, "bad query batch (n_queries=%d)", n_queries);
-    SAT_TRY(check_uploaded(m));
     // every query goes to the shard that holds its entry, under the entry's index there; the other shards learn its
     // size class only (sat_qfromdb_set)
     std::vector<int> owner((size_t)n_queries);
     std::vector<int32_t> n1s((size_t)n_queries);
     std::vector<std::vector<int32_t>> code((size_t)m->ndev, std::vector<int32_t>((size_t)n_queries));
+    std::vector<std::vector<int32_t>> begin((size_t)(sse_begin ? m->ndev : 0), std::vector<int32_t>((size_t)n_queries + 1, 0));
+    std::vector<std::vector<uint8_t>> lists((size_t)(sse_begin ? m->ndev : 0));
     for (int q = 0; q < n_queries; q++) {
         if (entry[q] < 0 || entry[q] >= m->n_entries)
             return sat_fail(SAT_EINVAL, "query %d: entry %d outside 0..%d", q, entry[q], m->n_entries - 1);
@@ -482,11 +486,20 @@ int sat_multi_queries_from_db(sat_multi *m, int n_queries, const int32_t *entry,
         const int32_t local = entry[q] - m->begin[(size_t)g];
         owner[(size_t)q] = g;
         n1s[(size_t)q] = m->ctx[(size_t)g]->h_orders[(size_t)local];
+        if (sse_begin) {
+            const int len = sse_begin[q + 1] - sse_begin[q];
+            SAT_TRY(sat_qfromdb_check_list(q, entry[q], n1s[(size_t)q], sse + sse_begin[q], len));
+            if (len > 0) n1s[(size_t)q] = len;
+            lists[(size_t)g].insert(lists[(size_t)g].end(), sse + sse_begin[q], sse + sse_begin[q + 1]);
+            for (int h = 0; h < m->ndev; h++) begin[(size_t)h][(size_t)q + 1] = (int32_t)lists[(size_t)h].size();
+        }
         for (int h = 0; h < m->ndev; h++) code[(size_t)h][(size_t)q] = h == g ? local : -query_n1p(n1s[(size_t)q]);
     }
     // each shard expands its own entries (and has waited for its stream when that returns) ...
     for (int g = 0; g < m->ndev; g++) {
-        const int rc = sat_qfromdb_set(m->ctx[(size_t)g], n_queries, code[(size_t)g].data(), n1s.data(), first_query_ordinal);
+        const int rc = sat_qfromdb_set(m->ctx[(size_t)g], n_queries, code[(size_t)g].data(), n1s.data(),
+                                       sse_begin ? begin[(size_t)g].data() : nullptr, sse_begin ? lists[(size_t)g].data() : nullptr,
+                                       first_query_ordinal);
         if (rc != SAT_OK) return rc;
     }
     // ... and sends every run of queries it owns to the other shards' blobs (the same offsets on every shard), device to
@@ -516,6 +529,26 @@ int sat_multi_queries_from_db(sat_multi *m, int n_queries, const int32_t *entry,
         HIP_TRY(hipStreamSynchronize(m->ctx[(size_t)g]->stream));
     }
     return SAT_OK;
+}
+
+sat_ctx *sat_debug_multi_ctx(sat_multi *m, int shard) { return m && shard >= 0 && shard < m->ndev ? m->ctx[(size_t)shard] : nullptr; }
+
+int sat_multi_queries_from_db(sat_multi *m, int n_queries, const int32_t *entry, uint32_t first_query_ordinal)
+{
+    SAT_TRY(sat_check_context(m));
+    if (n_queries < 1 || !entry) return sat_fail(SAT_EINVAL, "bad query batch (n_queries=%d)", n_queries);
+    SAT_TRY(check_uploaded(m));
+    return multi_queries_from_db(m, n_queries, entry, nullptr, nullptr, first_query_ordinal);
+}
+
+int sat_multi_queries_from_db_sses(sat_multi *m, int n_queries, const int32_t *entry, const int32_t *sse_begin, const uint8_t *sse,
+                                   uint32_t first_query_ordinal)
+{
+    SAT_TRY(sat_check_context(m));
+    if (n_queries < 1 || !entry) return sat_fail(SAT_EINVAL, "bad query batch (n_queries=%d)", n_queries);
+    SAT_TRY(sat_qfromdb_check_offsets(n_queries, sse_begin, sse));
+    SAT_TRY(check_uploaded(m));
+    return multi_queries_from_db(m, n_queries, entry, sse_begin, sse, first_query_ordinal);
 }
 
 int sat_multi_search(sat_multi *m, int lorder, int lsoln, int maxstart, int32_t *scores, int32_t *ssemaps, double *wall_ms)

@@ -50,6 +50,22 @@ def _pack_queries(queries):
     return nq, pitch, n1s, tabs, dmats, types
 
 
+def _pack_sse_lists(sses, nq):
+    """the motif lists of set_queries_from_db as sat_queries_from_db_sses takes them: (sse_begin int32[nq + 1], sse
+    uint8[total], never of size 0); an item that is None or empty - the whole entry - is an empty range"""
+    if len(sses) != nq:
+        raise ValueError("sses needs one item per query")
+    lists = [np.zeros(0, np.int64) if l is None else np.asarray(l, dtype=np.int64).ravel() for l in sses]
+    if any(((l < 0) | (l > 255)).any() for l in lists):
+        raise ValueError("an SSE index outside 0..255")
+    begin = np.zeros(nq + 1, np.int32)
+    begin[1:] = np.cumsum([len(l) for l in lists])
+    sse = np.zeros(max(int(begin[-1]), 1), np.uint8)
+    if begin[-1]:
+        sse[:begin[-1]] = np.concatenate(lists)
+    return begin, sse
+
+
 def _pair_lists(queries, entries):
     """a pair list as the pair searches take it: two int32 arrays of one length"""
     q = np.ascontiguousarray(queries, dtype=np.int32).ravel()
@@ -363,15 +379,24 @@ class Searcher:
         self.n_queries = nq
         self._batch = True
 
-    def set_queries_from_db(self, entries, first_query_ordinal=0):
+    def set_queries_from_db(self, entries, first_query_ordinal=0, sses=None):
         """Set a batch of queries that are entries of the uploaded database (sat_queries_from_db): query q is entry
         entries[q] (any order, repeats allowed).  The batch is built on the device from the resident cells - only the
         indices cross from the host - and is byte for byte the batch set_queries makes of the same structures, so every
-        search returns the same results."""
+        search returns the same results.
+        sses: motif queries (sat_queries_from_db_sses) - one item per query, None or empty for the whole entry, else the
+        0-based indices of the entry's SSEs the query is made of, in the order given (query SSE i is entry SSE
+        sses[q][i]); the query's order is the list's length."""
         idx = np.ascontiguousarray(entries, dtype=np.int32).ravel()
-        self._check(self._lib.sat_queries_from_db(self._ctx, len(idx), idx.ctypes.data if len(idx) else None,
-                                                  int(first_query_ordinal)))
-        n1s = self._orders[idx]
+        if sses is None:
+            self._check(self._lib.sat_queries_from_db(self._ctx, len(idx), idx.ctypes.data if len(idx) else None,
+                                                      int(first_query_ordinal)))
+            n1s = self._orders[idx]
+        else:
+            begin, sse = _pack_sse_lists(sses, len(idx))
+            self._check(self._lib.sat_queries_from_db_sses(self._ctx, len(idx), idx.ctypes.data if len(idx) else None,
+                                                           begin.ctypes.data, sse.ctypes.data, int(first_query_ordinal)))
+            n1s = np.where(np.diff(begin) > 0, np.diff(begin), self._orders[idx])
         self.n1 = int(n1s[0])
         self.n1max = int(n1s.max())
         self._n1s = np.array(n1s, np.int32)
@@ -379,8 +404,8 @@ class Searcher:
         self._batch = True
 
     def query_h2d_bytes(self):
-        """Bytes set_query / set_queries (the whole batch) and set_queries_from_db (4 per query) have copied host ->
-        device so far (sat_stat_query_h2d_bytes)."""
+        """Bytes set_query / set_queries (the whole batch) and set_queries_from_db (4 per query; with sses 8 per query,
+        4 and the lists) have copied host -> device so far (sat_stat_query_h2d_bytes)."""
         return int(self._lib.sat_stat_query_h2d_bytes(self._ctx))
 
     def debug_query_blob(self):
@@ -767,14 +792,34 @@ class MultiSearcher:
         self.n_queries = nq
         self.n1max = int(n1s.max())
 
-    def set_queries_from_db(self, entries, first_query_ordinal=0):
-        """Searcher.set_queries_from_db with entries[q] an index into the whole database (sat_multi_queries_from_db):
-        the shard that holds an entry builds its query, the other shards get it by a device-to-device copy."""
+    def set_queries_from_db(self, entries, first_query_ordinal=0, sses=None):
+        """Searcher.set_queries_from_db with entries[q] an index into the whole database (sat_multi_queries_from_db,
+        with sses sat_multi_queries_from_db_sses): the shard that holds an entry builds its query, the other shards get
+        it by a device-to-device copy."""
         idx = np.ascontiguousarray(entries, dtype=np.int32).ravel()
-        self._check(self._lib.sat_multi_queries_from_db(self._m, len(idx), idx.ctypes.data if len(idx) else None,
-                                                        int(first_query_ordinal)))
+        if sses is None:
+            self._check(self._lib.sat_multi_queries_from_db(self._m, len(idx), idx.ctypes.data if len(idx) else None,
+                                                            int(first_query_ordinal)))
+            n1s = self._orders[idx]
+        else:
+            begin, sse = _pack_sse_lists(sses, len(idx))
+            self._check(self._lib.sat_multi_queries_from_db_sses(self._m, len(idx), idx.ctypes.data if len(idx) else None,
+                                                                 begin.ctypes.data, sse.ctypes.data, int(first_query_ordinal)))
+            n1s = np.where(np.diff(begin) > 0, np.diff(begin), self._orders[idx])
         self.n_queries = len(idx)
-        self.n1max = int(self._orders[idx].max())
+        self.n1max = int(n1s.max())
+
+    def debug_shard_queries(self, shard):
+        """Test hook (satabsearch_debug.h): shard `shard`'s query batch as it lies on its device, uint8[bytes], and the
+        bytes its context has been sent for query batches so far."""
+        ctx = self._lib.sat_debug_multi_ctx(self._m, int(shard))
+        if not ctx:
+            raise SatError("no shard %d" % shard)
+        n = self._lib.sat_debug_query_blob(ctx, None, 0)
+        self._check(int(min(n, 0)))
+        blob = np.empty(int(n), np.uint8)
+        self._check(int(min(self._lib.sat_debug_query_blob(ctx, blob.ctypes.data, blob.size), 0)))
+        return blob, int(self._lib.sat_stat_query_h2d_bytes(ctx))
 
     def search(self, lorder=True, lsoln=False, maxstart=DEFAULT_MAXSTART):
         """Returns (scores int32[nq, N], ssemaps int32[nq, N, 111] or None, wall_ms), database order."""

@@ -155,8 +155,31 @@ int sat_queries_set(sat_ctx *ctx, int n_queries, const int32_t *n1s, const uint8
  */
 int sat_queries_from_db(sat_ctx *ctx, int n_queries, const int32_t *entry, uint32_t first_query_ordinal);
 
-/* Bytes sat_queries_set (the batch's whole blob) and sat_queries_from_db (4 * n_queries) have copied from the host to
- * the device on this context since it was created. */
+/*
+ * MOTIF QUERIES: as sat_queries_from_db, but query q is a chosen list of entry[q]'s SSEs.  sse_begin
+ * [n_queries + 1] is CSR into sse with sse_begin[0] == 0: query q's list l is sse[sse_begin[q] .. sse_begin[q + 1]), m
+ * distinct 0-BASED SSE indices of the entry (order n), 1 <= m <= n, in ANY order; an empty range means the whole entry.
+ * Query SSE i is entry SSE l[i]: an ascending list is a substructure, any other order a permuted one - under LORDER = T
+ * the search then looks for that permuted topology.  (The reference's query builder, pytableaucreate.py -s, sorts its
+ * list; the order is kept as given here.)  The query is exactly the structure of order m with
+ *     tab[i][k]  = the entry's tab[max(l[i], l[k])][min(l[i], l[k])],
+ *     dist[i][k] = the same cell of the entry's distances,
+ *     SSE type i = the entry's tableau diagonal at l[i],
+ * and its size class follows m, not n: five SSEs of a 101-SSE entry are a 16-wide query.  The kernel of
+ * sat_queries_from_db gathers the list's packed sub-triangle from the entry's raw uploaded cells and expands that, so
+ * afterwards the context is exactly as after sat_queries_set with these dense arrays and the same ordinal, and every
+ * later call, in every mode, returns bit-identical results.
+ * The call copies exactly 8 * n_queries + 4 + sse_begin[n_queries] bytes to the device - the indices, the offsets, the
+ * list bytes, counted in sat_stat_query_h2d_bytes - and nothing comes back.
+ * SAT_EINVAL, the previous batch intact: what sat_queries_from_db refuses; sse_begin or sse NULL; sse_begin[0] != 0 or
+ * offsets that descend; a list longer than its entry's order; an index >= the order; an index twice in one list (the
+ * message names the query's position and the offending SSE).  No database is SAT_ESTATE, a failed launch SAT_EDEVICE.
+ */
+int sat_queries_from_db_sses(sat_ctx *ctx, int n_queries, const int32_t *entry, const int32_t *sse_begin, const uint8_t *sse,
+                             uint32_t first_query_ordinal);
+
+/* Bytes sat_queries_set (the batch's whole blob), sat_queries_from_db (4 * n_queries) and sat_queries_from_db_sses
+ * (8 * n_queries + 4 + the lists) have copied from the host to the device on this context since it was created. */
 unsigned long long sat_stat_query_h2d_bytes(const sat_ctx *ctx);
 
 /* Queries currently set (1 after sat_query_set). */
@@ -637,6 +660,11 @@ void sat_debug_lds_layout(int m2w, int n1, int n1p, int n2, int chains, int thre
  *                       shard's batch (a peer copy between GPUs, a plain copy where the list names one GPU twice);
  *                       each shard receives one 4-byte word per query from the host.  Every shard is then exactly as
  *                       after sat_multi_queries_set with the entries' dense arrays
+ * sat_multi_queries_from_db_sses  as sat_queries_from_db_sses in the same way: the shard that holds the entry gathers and
+ *                       expands the motif, the other shards keep room for a query of the list's length and take its
+ *                       bytes device to device; each shard receives 8 * n_queries + 4 bytes and the lists of its OWN
+ *                       queries from the host.  Every shard is then exactly as after sat_multi_queries_set with the
+ *                       motifs' dense arrays
  * sat_multi_search      as sat_search: scores [nq][n_entries] (and ssemaps) in database order;
  *                       wall_ms = launch on all GPUs .. rows on the host
  * sat_multi_search_topk the best k rows per query, each GPU ranking its own shard (sat_topk_hits) and
@@ -655,6 +683,8 @@ int sat_multi_shards(const sat_multi *m, int32_t *begin);
 int sat_multi_queries_set(sat_multi *m, int n_queries, const int32_t *n1s, const uint8_t *qtabs,
                           const float *qdmats, int pitch, const uint8_t *qssetypes, uint32_t first_query_ordinal);
 int sat_multi_queries_from_db(sat_multi *m, int n_queries, const int32_t *entry, uint32_t first_query_ordinal);
+int sat_multi_queries_from_db_sses(sat_multi *m, int n_queries, const int32_t *entry, const int32_t *sse_begin, const uint8_t *sse,
+                                   uint32_t first_query_ordinal);
 int sat_multi_search(sat_multi *m, int lorder, int lsoln, int maxstart, int32_t *scores, int32_t *ssemaps,
                      double *wall_ms);
 int sat_multi_search_topk(sat_multi *m, int lorder, int lsoln, int maxstart, int k, sat_hit *hits,

@@ -68,6 +68,13 @@ const char *sat_debug_sa_instances(void);
  * bytes are copied to `out` when it is not NULL and `capacity` holds them.  Tests compare the batches of
  * sat_queries_set and sat_queries_from_db with it. */
 long long sat_debug_query_blob(struct sat_ctx *ctx, void *out, size_t capacity);
+
+/* Every build, a test hook: the context of shard `shard` of a sat_multi (NULL outside 0 .. ndev - 1), for
+ * sat_debug_query_blob and sat_stat_query_h2d_bytes - what each shard of sat_multi_queries_from_db(_sses) holds and was
+ * sent.  The context stays the sat_multi's: read it with those two calls only, never set queries on it, search with it
+ * or destroy it. */
+struct sat_multi;
+struct sat_ctx *sat_debug_multi_ctx(struct sat_multi *m, int shard);
 #ifdef __cplusplus
 }
 #endif
