@@ -41,6 +41,7 @@ ABI_SYMBOLS = (
     "sat_eval_classes", "sat_eval_rows", "sat_eval_tables", "sat_multi_eval_classes", "sat_multi_eval_rows",
     "sat_cover_begin", "sat_cover_add", "sat_cover_solve", "sat_cover_end",
     "sat_multi_cover_begin", "sat_multi_cover_add", "sat_multi_cover_solve",
+    "sat_profile_rows", "sat_multi_profile_rows",
 )
 
 MAX_CLUSTER_LEVELS = 8
@@ -218,6 +219,10 @@ def device_lib():
             lib.sat_multi_cover_begin.argtypes = [C.c_void_p]
             lib.sat_multi_cover_add.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
             lib.sat_multi_cover_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        # (as above: a build of the parent commit predates the profile)
+        if hasattr(lib, "sat_profile_rows"):
+            lib.sat_profile_rows.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.sat_multi_profile_rows.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.sat_hits_cutoff.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         lib.sat_multi_search_cutoff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                                 C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
@@ -291,6 +296,7 @@ def host_lib():
         lib.sat_eval_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Eval)]
         lib.sat_cover_sizes.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
         lib.sat_cover_greedy.argtypes = [C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.sat_profile_core.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
         _host = lib
     return _host
 

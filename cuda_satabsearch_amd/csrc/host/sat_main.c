@@ -48,7 +48,13 @@
  * "# MEAN ..." instead of any rows), -D P (with -a dbfile: cluster the database around representatives - a greedy cover of
  * the graph of the rows whose p-value is <= P, kept as a bit matrix and solved on the GPUs, sat_cover.h: every structure is
  * a direct hit of its representative - and print -L's four columns, the degree counting distinct neighbours, under a
- * "# COVER ..." header).
+ * "# COVER ..." header), -W P [-f F] (profile each query's SSEs over its hits: every batch is searched with LSOLN on,
+ * its rows and maps stay on the GPUs, and sat_multi_profile_rows counts there, per query, the rows whose p-value is <= P
+ * - the query's own entry apart - and for every pair of the query's SSEs those whose map matches both; 4 + 4 n1 n1 bytes a
+ * query come back.  Under a "# PROFILE ..." header each query gets "# QUERY name sses = n1 hits = H", its conserved core
+ * "# CORE sses = c joint >= J name@list" - sat_profile.h: SSEs every two of which are matched together in at least F,
+ * default 0.5, of the hits; the text after J is a SID@list line for -q / -Q - and n1 lines "i type matched joint_i1 ..
+ * joint_in1" instead of any rows).
  * Motif queries: with -q dbfile and -Q dbfile a stdin line may be SID@list, the list (sat_parse_sse_list: 2,1,8,5,3 or
  * 1-3,9 - 1-based, as pytableaucreate.py -s takes it, but kept in the order given) naming the SSEs of that entry the
  * query is made of.  The block gets a header line "# QUERY SSES = 2,1,8,5,3" after "# DBFILE" and is otherwise printed
@@ -71,6 +77,7 @@
 #include "sat_gumbel.h"
 #include "sat_host_search.h"
 #include "sat_parse.h"
+#include "sat_profile.h"
 
 
 static double now_ms(void)
@@ -108,12 +115,15 @@ static double now_ms(void)
 #pragma weak sat_cover_sizes
 #pragma weak sat_multi_eval_classes
 #pragma weak sat_multi_eval_rows
+#pragma weak sat_multi_profile_rows
+#pragma weak sat_profile_core
 
 static void usage(const char *prog)
 {
     fprintf(stderr, "Usage: %s [-c] [-q dbfile | -Q dbfile | -a dbfile] [-r restarts] [-g gpus] [-G gpu,gpu,...] [-s seed]\n"
                     "       [-k K] [-p P] [-m M] [-M M] [-R restarts [-C C]] [-F censor] [-P T] [-A] [-L P] [-b] [-H P1,P2,...]\n"
-                    "       [-E classfile [-N n]] [-D P]\n", prog);
+                    "       [-E classfile [-N n]] [-D P]\n"
+                    "       [-W P [-f F]]\n", prog);
     fprintf(stderr, "  -c : run on host CPU not GPU card\n");
     fprintf(stderr, "  -q dbfile : database is read from dbfile, list of query\n"
                     "              ids is read from stdin\n");
@@ -164,6 +174,13 @@ static void usage(const char *prog)
                     "         and no two representatives are hits of each other; prints one line per structure:\n"
                     "         name representative cluster_size degree, the degree counting distinct neighbours\n"
                     "         (not with -c, -k, -p, -m, -M, -R, -C, -L, -H, -E)\n");
+    fprintf(stderr, "  -W P : which SSEs: profile each query's SSEs over its hits on the GPU - the rows whose p-value is <= P\n"
+                    "         (0..1), the query's own entry apart; prints per query its hits, its conserved core as a SID@list\n"
+                    "         line (# CORE) and one line per SSE: i type matched joint_i1 .. joint_in1, the hits that match SSE i\n"
+                    "         and those that match SSE i and SSE k together; no rows, no maps\n"
+                    "         (not with -c, -k, -p, -m, -M, -R, -C, -L, -H, -D, -E, -N)\n");
+    fprintf(stderr, "  -f F : with -W: every two SSEs of the core are matched together in at least F (0 < F <= 1) of the hits.\n"
+                    "         Default 0.5\n");
     fprintf(stderr, "  -b : cache the parsed database as dbfile.satbin\n");
     exit(1);
 }
@@ -319,6 +336,10 @@ typedef struct {
     double dmax;                      /* -D: the largest p-value of an edge */
     const char *classfile;            /* -E: score the search against this classification instead of printing rows */
     int rocn;                         /* -N: the negatives ROC-n counts up to (0: not given) */
+    int profile;                      /* -W: profile each query's SSEs over its hits instead of printing rows */
+    double wmax;                      /* -W: the largest p-value of a hit */
+    int core_given;                   /* -f was given */
+    double core;                      /* -f: the fraction of the hits every pair of the core is matched together in */
     unsigned long long seed;
     const char *qfile;                /* -q, -Q, -a: the database; stdin lists the query SIDs (not with -a) */
     const char *from_db;              /* -Q, -a: the database again - the batches are set from entry indices on the GPUs */
@@ -490,7 +511,7 @@ static void parse_options(int argc, char *argv[], options *o)
 {
     *o = (options){ .use_gpu = 1, .maxstart = 128, .want_gpus = 1, .seed = SAT_DEFAULT_SEED };
     int c;
-    while ((c = getopt(argc, argv, "cq:Q:a:r:g:G:s:bk:p:m:M:R:C:F:P:AL:H:E:N:D:")) != -1) {
+    while ((c = getopt(argc, argv, "cq:Q:a:r:g:G:s:bk:p:m:M:R:C:F:P:AL:H:E:N:D:W:f:")) != -1) {
         char *end = NULL;
         long v;
         switch (c) {
@@ -534,6 +555,24 @@ static void parse_options(int argc, char *argv[], options *o)
                 usage(argv[0]);
             }
             o->cover = 1;
+            break;
+        case 'W':
+            /* the whole argument, a finite number in [0, 1] */
+            o->wmax = strtod(optarg, &end);
+            if (end == optarg || *end != '\0' || !isfinite(o->wmax) || o->wmax < 0.0 || o->wmax > 1.0) {
+                fprintf(stderr, "ERROR: -W needs a p-value in [0, 1] (got '%s')\n", optarg);
+                usage(argv[0]);
+            }
+            o->profile = 1;
+            break;
+        case 'f':
+            /* the whole argument, a number in (0, 1] */
+            o->core = strtod(optarg, &end);
+            if (end == optarg || *end != '\0' || !(o->core > 0.0 && o->core <= 1.0)) {
+                fprintf(stderr, "ERROR: -f needs a fraction in (0, 1] (got '%s')\n", optarg);
+                usage(argv[0]);
+            }
+            o->core_given = 1;
             break;
         case 'H':
             /* the whole argument: 1 .. SAT_MAX_CLUSTER_LEVELS numbers, each as -L's, with commas between, strictly ascending */
@@ -598,6 +637,27 @@ static void parse_options(int argc, char *argv[], options *o)
             break;
         default: usage(argv[0]);
         }
+    }
+    if (o->core_given && !o->profile) die("ERROR: -f needs -W P\n");
+    if (o->profile) {
+        /* profile: a run whose rows and maps stay on the GPUs; -q, -Q, -a and the stdin queries all feed it */
+        if (!o->use_gpu) die("ERROR: -W cannot be combined with -c\n");
+        if (o->topk) die("ERROR: -W cannot be combined with -k\n");
+        if (o->cutoff) die("ERROR: -W cannot be combined with -p\n");
+        if (o->nmatch) die("ERROR: -W cannot be combined with -m\n");
+        if (o->rowmatch) die("ERROR: -W cannot be combined with -M\n");
+        if (o->refine) die("ERROR: -W cannot be combined with -R\n");
+        if (o->ncand) die("ERROR: -W cannot be combined with -C\n");
+        if (o->nlevels) die("ERROR: -W cannot be combined with -H\n");
+        if (o->cover) die("ERROR: -W cannot be combined with -D\n");
+        if (o->cluster) die("ERROR: -W cannot be combined with -L\n");
+        if (o->classfile) die("ERROR: -W cannot be combined with -E\n");
+        if (o->rocn) die("ERROR: -W cannot be combined with -N\n");
+        if (o->polish && !o->polish_all) die("ERROR: -W takes -P T only with -A\n");
+        if (!sat_multi_search_only || !sat_multi_profile_rows || !sat_profile_core)
+            die("ERROR: this library has no sat_multi_profile_rows\n");
+        if (o->fit && !sat_multi_search_fit) die("ERROR: this library has no sat_multi_search_fit\n");
+        if (!o->core_given) o->core = 0.5;
     }
     if (o->rocn && !o->classfile) die("ERROR: -N needs -E classfile\n");
     if (o->cover) {
@@ -955,6 +1015,9 @@ static int run_host(const options *o, const input *in)
 
 /* ---- GPU mode */
 
+/* -W: the solution maps a batch may hold on the GPUs (batch x entries x the largest query's SSEs bytes) */
+#define PROFILE_MAP_BYTES ((size_t)4 << 30)
+
 /* The host side of the GPU path, sized once for the mode */
 typedef struct {
     int batch;                        /* queries a search scores */
@@ -974,6 +1037,9 @@ typedef struct {
     int32_t *rowm_restarts, *pair_q, *pair_e;   /* -M: each slot's restart; the rows as (query, entry) pairs */
     size_t rowm_cap;                  /* -M: rows they hold */
     int32_t *sse_begin;               /* -Q with motif queries: the batch's list offsets, batch + 1 of them */
+    int32_t *qnode;                   /* -W: the batch's queries as database entries, -1 for a query that is none */
+    uint32_t *phits, *pjoint;         /* -W: every query's hits; the matrices, query qi's at poff[qi] */
+    size_t *poff;                     /* -W: num_queries + 1 of them */
 } gpu_bufs;
 
 static void alloc_slots(slots *s, size_t rows, int nm, int with_counts, int lsoln)
@@ -995,7 +1061,7 @@ static void alloc_hits(gpu_bufs *B, size_t rows, int lsoln)
 static void alloc_gpu_bufs(const options *o, const input *in, gpu_bufs *B)
 {
     const int total = in->db.count, nm = o->nm, lsoln = in->lsoln;
-    const int entry_slots = (!o->ranked && !o->cluster && !o->classfile) || o->nmatch;     /* every entry's slots come to the host */
+    const int entry_slots = (!o->ranked && !o->cluster && !o->classfile && !o->profile) || o->nmatch;     /* every entry's slots come to the host */
     *B = (gpu_bufs){ .batch = 256, .kk = o->topk < total ? o->topk : total };
     /* Queries go to the GPUs in batches: one set of launches scores a whole batch (grid = entries x queries), which
      * is what fills the machine when the database is small and the query list long (-q).  The batch size is bounded
@@ -1007,14 +1073,31 @@ static void alloc_gpu_bufs(const options *o, const input *in, gpu_bufs *B)
         const size_t budget = (size_t)1 << 30;
         if ((size_t)B->batch * per_query > budget) B->batch = (int)(budget / per_query);
     }
+    if (o->profile) {
+        /* the batch's maps stay on the GPUs, a byte per entry and query SSE: at most PROFILE_MAP_BYTES of them, sized by
+         * the run's largest query.  The counters are a query's own: nothing depends on the cut.  And every query's
+         * result until the table is printed: 4 + 4 n1 n1 bytes */
+        size_t n1max = 1;
+        B->poff = checked(calloc((size_t)in->num_queries + 1, sizeof(size_t)));
+        for (int qi = 0; qi < in->num_queries; qi++) {
+            const size_t n1 = (size_t)query_order(in, qi);
+            n1max = n1 > n1max ? n1 : n1max;
+            B->poff[qi + 1] = B->poff[qi] + n1 * n1;
+        }
+        if ((size_t)B->batch * (size_t)total * n1max > PROFILE_MAP_BYTES) B->batch = (int)(PROFILE_MAP_BYTES / ((size_t)total * n1max));
+        B->phits = checked(malloc(sizeof(uint32_t) * ((size_t)in->num_queries + 1)));
+        B->pjoint = checked(malloc(sizeof(uint32_t) * (B->poff[in->num_queries] + 1)));
+    }
     if (B->batch < 1) B->batch = 1;
     if (B->batch > in->num_queries) B->batch = in->num_queries;
+    if (o->profile)
+        B->qnode = checked(malloc(sizeof(int32_t) * (size_t)B->batch));
     const size_t rows = (size_t)total * B->batch;
     if (entry_slots)
         alloc_slots(&B->all, rows, nm, o->nmatch, lsoln);
     if (o->nmatch)
         B->restarts = checked(malloc(sizeof(int32_t) * rows * nm));
-    if (!o->ranked && !o->cluster && !o->classfile && in->cls_count[1] > 0)
+    if (!o->ranked && !o->cluster && !o->classfile && !o->profile && in->cls_count[1] > 0)
         alloc_slots(&B->large, (size_t)in->cls_count[1] * in->num_queries, nm, o->nmatch, lsoln);
     if (o->csr) {
         B->hits_cap = o->cutoff ? 1024 : B->kk * B->batch;
@@ -1060,6 +1143,10 @@ static void free_gpu_bufs(gpu_bufs *B)
 {
     free(B->n1s);
     free(B->sse_begin);
+    free(B->qnode);
+    free(B->phits);
+    free(B->pjoint);
+    free(B->poff);
     free(B->qtabs);
     free(B->qtypes);
     free(B->qdmats);
@@ -1112,11 +1199,12 @@ static int search_batch(const options *o, const input *in, sat_multi *multi, gpu
                         double *ms_stage2)
 {
     const int lorder = in->lorder, lsoln = in->lsoln, maxstart = o->maxstart;
-    if (o->cluster || o->classfile) {
-        /* -L, -H, -D, -E: the rows stay on the GPUs (no gather, no LSOLN: no map is printed); with -F the fit is installed there */
+    if (o->cluster || o->classfile || o->profile) {
+        /* -L, -H, -D, -E: the rows stay on the GPUs (no gather, no LSOLN: no map is printed); with -F the fit is installed
+         * there.  -W: the same with LSOLN on, whatever the input says - the maps are what it counts, where they are */
         if (o->fit)
-            return sat_multi_search_fit(multi, lorder, 0, maxstart, o->censor, fits, ms);
-        return sat_multi_search_only(multi, lorder, 0, maxstart, ms);
+            return sat_multi_search_fit(multi, lorder, o->profile, maxstart, o->censor, fits, ms);
+        return sat_multi_search_only(multi, lorder, o->profile, maxstart, ms);
     }
     if (o->fit && o->ranked) {
         /* search, histogram and fit on the GPUs (fits: the batch's), then the rows by the fitted p-values: those under
@@ -1398,6 +1486,70 @@ static void print_eval(const options *o, const input *in, const sat_classes *cl,
     }
 }
 
+/* -W: the table of the profiles - every query's hits and matrix as the GPUs counted them (4 + 4 n1 n1 bytes a query
+ * crossed to the host); the core is sat_profile_core's.  A motif's core is written in its source entry's numbering */
+static void print_profiles(const options *o, const input *in, const gpu_bufs *B, const sat_fit *fits)
+{
+    static const char *tname[4] = { "e", "xa", "xi", "xg" };
+    char line[SAT_MAX_LINE_LEN + 256];
+    int len = snprintf(line, sizeof line, "# PROFILE dbfile = %s pvalue <= %g fraction >= %g restarts = %d queries = %d\n", in->dbfile,
+                       o->wmax, o->core, o->maxstart, in->num_queries);
+    out_bytes(line, (size_t)len);
+    out_bytes(polish_header, strlen(polish_header));
+    if (fits) {
+        int fitted = 0;
+        for (int qi = 0; qi < in->num_queries; qi++)
+            fitted += fits[qi].fitted != 0;
+        len = snprintf(line, sizeof line, "# GUMBEL censor = %g fitted = %d of %d\n", o->censor, fitted, in->num_queries);
+        out_bytes(line, (size_t)len);
+    }
+    uint8_t in_core[SAT_MAXDIM];
+    for (int qi = 0; qi < in->num_queries; qi++) {
+        int qs;
+        const sat_struct_set *qset = query_set(in, qi, &qs);
+        const int n1 = qset->order[qs], motif = in->motifs && in->qsub[qi] >= 0;
+        const char *name = sat_set_name(in->qsrc, in->qindex[qi]);
+        const uint32_t *joint = B->pjoint + B->poff[qi];
+        len = snprintf(line, sizeof line, "# QUERY %s sses = %d hits = %u\n", name, n1, B->phits[qi]);
+        out_bytes(line, (size_t)len);
+        if (motif) {
+            out_bytes("# QUERY SSES = ", 15);
+            for (int32_t k = in->sse_begin[qi]; k < in->sse_begin[qi + 1]; k++) {
+                len = snprintf(line, sizeof line, k > in->sse_begin[qi] ? ",%d" : "%d", in->sse[k] + 1);
+                out_bytes(line, (size_t)len);
+            }
+            out_bytes("\n", 1);
+        }
+        uint32_t joint_min = 0;
+        const int core = sat_profile_core(n1, B->phits[qi], joint, o->core, in_core, &joint_min);
+        if (core < 0)
+            die("ERROR: no core for query %s\n", name);
+        if (core == 0) {
+            out_bytes("# CORE none\n", 12);
+        } else {
+            len = snprintf(line, sizeof line, "# CORE sses = %d joint >= %u %s@", core, joint_min, name);
+            out_bytes(line, (size_t)len);
+            for (int i = 0, first = 1; i < n1; i++)
+                if (in_core[i]) {
+                    len = snprintf(line, sizeof line, first ? "%d" : ",%d", motif ? in->sse[in->sse_begin[qi] + i] + 1 : i + 1);
+                    out_bytes(line, (size_t)len);
+                    first = 0;
+                }
+            out_bytes("\n", 1);
+        }
+        const uint8_t *tab = qset->tab + qset->cell_off[qs];
+        for (int i = 0; i < n1; i++) {
+            len = snprintf(line, sizeof line, "%d %s %u", i + 1, tname[tab[(size_t)i * (i + 1) / 2 + i] & 3], joint[(size_t)i * n1 + i]);
+            out_bytes(line, (size_t)len);
+            for (int k = 0; k < n1; k++) {
+                len = snprintf(line, sizeof line, " %u", joint[(size_t)i * n1 + k]);
+                out_bytes(line, (size_t)len);
+            }
+            out_bytes("\n", 1);
+        }
+    }
+}
+
 static int run_gpu(const options *o, const input *in)
 {
     /* -E: the classification, read before any GPU is touched: a bad file ends the run here */
@@ -1469,6 +1621,13 @@ static int run_gpu(const options *o, const input *in)
         /* -E: the batch's rows scored where they are; query b is structure qindex[q0 + b] of the database */
         if (rc == SAT_OK && o->classfile)
             rc = sat_multi_eval_rows(multi, in->qindex + q0, o->rocn, evals + q0);
+        /* -W: the batch's rows and maps counted where they are; query b is structure qindex[q0 + b] of the database when
+         * it was taken from there (a motif: its source entry), else no structure of it */
+        if (rc == SAT_OK && o->profile) {
+            for (int b = 0; b < nqb; b++)
+                B.qnode[b] = o->qfile ? in->qindex[q0 + b] : -1;
+            rc = sat_multi_profile_rows(multi, o->wmax, B.qnode, B.phits + q0, B.pjoint + B.poff[q0], NULL);
+        }
         if (rc < 0) {
             fprintf(stderr, "kernel launch failed: %s\n", sat_last_error());
             status = 1;
@@ -1494,7 +1653,7 @@ static int run_gpu(const options *o, const input *in)
                     o->ncand < total ? o->ncand : total, o->refine);
         fprintf(stderr, "%f million iterations/sec\n",
                 ((double)total * nqb * ((double)o->maxstart * SAT_MAXITER) / (ms / 1000)) / 1.0e6);
-        if (o->cluster || o->classfile)
+        if (o->cluster || o->classfile || o->profile)
             continue;
         if (o->fit && !o->ranked)
             for (int b = 0; b < nqb; b++)
@@ -1507,7 +1666,9 @@ static int run_gpu(const options *o, const input *in)
         status = o->cover ? print_cover(o, in, multi, fits) : o->nlevels ? print_cluster_levels(o, in, multi, fits) : print_clusters(o, in, multi, fits);
     if (!status && o->classfile)
         print_eval(o, in, &classes, evals);
-    if (!status && !o->ranked && !o->cluster && !o->classfile && in->cls_count[1] > 0)
+    if (!status && o->profile)
+        print_profiles(o, in, &B, fits);
+    if (!status && !o->ranked && !o->cluster && !o->classfile && !o->profile && in->cls_count[1] > 0)
         for (int qi = 0; qi < in->num_queries; qi++) {
             print_header(in, qi, fits ? &fits[qi] : NULL);
             for (int d = 0; d < in->cls_count[1]; d++)

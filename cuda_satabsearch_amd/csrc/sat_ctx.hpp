@@ -245,6 +245,11 @@ struct sat_ctx {
     DevBuf<unsigned char> d_eval_q;
     DevBuf<sat_eval> d_eval_rows;
 
+    // a query's SSEs profiled over its hits (sat_profile_rows, sat_profile.hip): scratch that only grows -
+    // hits [nq] then every query's [n1][n1] matrix, packed in query order; the queries' rows for the kernels
+    DevBuf<uint32_t> d_profile;
+    DevBuf<unsigned char> d_profile_q;
+
     // bytes copied device -> host by this context's result calls (sat_stat_d2h_bytes)
     unsigned long long d2h_bytes = 0;
     // bytes copied host -> device by sat_queries_set / sat_queries_from_db (sat_stat_query_h2d_bytes)
@@ -274,6 +279,9 @@ int sat_cover_rows_or(sat_ctx *ctx, int row0, int rows, const unsigned long long
 // ---- sat_eval.hip.  Load that file's code object (an empty launch of a small kernel); drop the installed classes.
 int sat_eval_load_code(sat_ctx *ctx);
 void sat_eval_drop(sat_ctx *ctx);
+
+// ---- sat_profile.hip.  Load that file's code object (an empty launch of a small kernel).
+int sat_profile_load_code(sat_ctx *ctx);
 
 // ---- sat_qfromdb.hip, for sat_multi_queries_from_db.  sat_queries_from_db on one shard's context, every check made by
 // the caller: query q has order n1s[q] and is entry code[q] >= 0 of this shard, or code[q] = -query_n1p(n1s[q]): a

@@ -19,6 +19,8 @@
 // points call them in the order their checks have always fired.
 inline int sat_check_context(const void *ctx) { return ctx ? SAT_OK : sat_fail(SAT_EINVAL, "null context"); }
 inline int sat_check_uploaded(bool uploaded) { return uploaded ? SAT_OK : sat_fail(SAT_ESTATE, "no database uploaded"); }
+// a call that reads the solution maps of the last search (searched_lsoln: it kept them)
+inline int sat_check_lsoln(bool searched_lsoln) { return searched_lsoln ? SAT_OK : sat_fail(SAT_ESTATE, "the last search ran without lsoln"); }
 inline int sat_check_pvalue(double p) { return std::isfinite(p) && p >= 0.0 ? SAT_OK : sat_fail(SAT_EINVAL, "max_pvalue must be finite and >= 0"); }
 // the cutoffs of a leveled cluster accumulator: 1 .. SAT_MAX_CLUSTER_LEVELS of them, each finite and in [0, 1], strictly ascending
 inline int sat_check_levels(int n_levels, const double *max_pvalue)
@@ -150,3 +152,7 @@ int sat_cutoff_count(sat_ctx *ctx, double max_pvalue, bool maps, int32_t *counts
 // to the host in CSR order - query q's first min(max_rows, counts[q]) rows (all when max_rows <= 0) at the sum of
 // the rows of the queries before it; maps (may be NULL) at the same row index times SAT_MAXDIM.
 int sat_cutoff_rows(sat_ctx *ctx, double max_pvalue, int max_rows, const int32_t *counts, sat_hit *hits, int32_t *ssemaps);
+
+// ---- The checks of sat_profile_rows (sat_profile.hip) behind the context's, in its order and nothing else: a search
+// has run, with lsoln; the two arrays; the p-value.  sat_multi_profile_rows makes them for every shard before the first works.
+int sat_profile_check(sat_ctx *ctx, double max_pvalue, const uint32_t *hits, const uint32_t *joint);

@@ -1061,6 +1061,33 @@ int sat_multi_eval_rows(sat_multi *m, const int32_t *query_node, int rocn, sat_e
     return SAT_OK;
 }
 
+int sat_multi_profile_rows(sat_multi *m, double max_pvalue, const int32_t *query_node, uint32_t *hits, uint32_t *joint, const int64_t *offset)
+{
+    SAT_TRY(check_multi(m));
+    if (m->ndev == 1) return sat_profile_rows(m->ctx[0], max_pvalue, query_node, hits, joint, offset);     // nothing is added
+    // the checks of sat_profile_rows, made for all shards before the first one works
+    for (sat_ctx *c : m->ctx) SAT_TRY(sat_profile_check(c, max_pvalue, hits, joint));
+    // each shard's counts of its own entries, packed in query order; integer counts add up, in any order
+    const size_t nq = m->ctx[0]->queries.size();
+    std::vector<size_t> off(nq + 1, 0);
+    for (size_t q = 0; q < nq; q++) off[q + 1] = off[q] + (size_t)m->ctx[0]->queries[q].n1 * (size_t)m->ctx[0]->queries[q].n1;
+    std::vector<uint32_t> part_hits(nq), part(off[nq]);
+    std::fill(hits, hits + nq, 0u);
+    for (size_t q = 0; q < nq; q++) {
+        uint32_t *out = joint + (offset ? (size_t)offset[q] : off[q]);
+        std::fill(out, out + (off[q + 1] - off[q]), 0u);
+    }
+    for (int g = 0; g < m->ndev; g++) {
+        SAT_TRY(sat_profile_rows(m->ctx[(size_t)g], max_pvalue, query_node, part_hits.data(), part.data(), nullptr));
+        for (size_t q = 0; q < nq; q++) {
+            hits[q] += part_hits[q];
+            uint32_t *out = joint + (offset ? (size_t)offset[q] : off[q]);
+            for (size_t i = off[q]; i < off[q + 1]; i++) out[i - off[q]] += part[i];
+        }
+    }
+    return SAT_OK;
+}
+
 unsigned long long sat_multi_stat_d2h_bytes(const sat_multi *m)
 {
     if (!m) return 0ull;

@@ -421,7 +421,7 @@ extern "C" int sat_topk_hits(sat_ctx *ctx, int k, sat_hit *hits, int32_t *ssemap
 {
     SAT_TRY(sat_check_searched(ctx));
     SAT_TRY(sat_check_topk(hits != nullptr, k));
-    if (ssemaps && !ctx->searched_lsoln) return sat_fail(SAT_ESTATE, "the last search ran without lsoln");
+    if (ssemaps) SAT_TRY(sat_check_lsoln(ctx->searched_lsoln));
     if (k > ctx->n_entries) k = ctx->n_entries;
     const size_t rows = ctx->queries.size() * (size_t)k;
     SAT_TRY(select_all_hits(ctx, k, ssemaps != nullptr));
@@ -518,7 +518,7 @@ extern "C" int sat_search_refine_polish(sat_ctx *ctx, int lorder, int lsoln, int
 int sat_cutoff_count(sat_ctx *ctx, double max_pvalue, bool maps, int32_t *counts)
 {
     SAT_TRY(sat_check_searched(ctx));
-    if (maps && !ctx->searched_lsoln) return sat_fail(SAT_ESTATE, "the last search ran without lsoln");
+    if (maps) SAT_TRY(sat_check_lsoln(ctx->searched_lsoln));
     const int n = ctx->n_entries, nq = (int)ctx->queries.size(), pc = std::min(sat_cutoff_chunk(ctx, n), nq);
     HIP_TRY(hipSetDevice(ctx->device));
     SAT_TRY(ctx->d_seg.grow((size_t)nq + 3 * (size_t)pc + 2));

@@ -180,3 +180,53 @@ def eval_table(names, class_tokens, rows, dbfile, classfile, entries, classified
                                                     int(row["u2"]), int(row["t2"]), row["n_used"],
                                                     "NA" if a is None else "%.6f" % a, "NA" if r is None else "%.6f" % r))
     return out
+
+
+def profile_core(joint, hits, fraction=0.5):
+    """(in_core bool[n1], joint_min) of one query's profile - its uint32[n1, n1] matrix and its hits from
+    Searcher.profile_rows: the SSEs every two of which are matched together in at least `fraction` of the hits
+    (sat_profile_core of csrc/host/sat_profile.h, which the command line's -W prints from); joint_min is the smallest
+    joint count among them, 0 for an empty core."""
+    import ctypes as C
+    import numpy as np
+    j = np.ascontiguousarray(joint, dtype=np.uint32)
+    if j.ndim != 2 or j.shape[0] != j.shape[1] or j.shape[0] < 1:
+        raise ValueError("joint must be a square matrix of at least one SSE")
+    core = np.zeros(j.shape[0], np.uint8)
+    least = C.c_uint32(0)
+    if _native.host_lib().sat_profile_core(j.shape[0], int(hits), j.ctypes.data, float(fraction), core.ctypes.data, C.addressof(least)) < 0:
+        raise ValueError("fraction must lie in (0, 1]")
+    return core.astype(bool), int(least.value)
+
+
+_SSE_TYPE_NAMES = ("e", "xa", "xi", "xg")
+
+
+def profile_table(names, types, hits, joints, dbfile, pvalue, fraction, restarts, sses=None, polish_all=0, gumbel=None):
+    """The lines the command line's -W prints: names[q] the query's name, types[q] its SSEs' type codes (the tableau's
+    diagonal: 0 e, 1 xa, 2 xi, 3 xg, or their spellings), hits and joints what Searcher.profile_rows returned for all
+    queries in order.  sses[q], where the query is a motif, is its 0-based list in the source entry's numbering (else
+    None): the core is then written in that numbering, so that the text after "joint >= J " is a SID@list line.
+    gumbel: (censor, fitted) under -F."""
+    out = ["# PROFILE dbfile = %s pvalue <= %s fraction >= %s restarts = %d queries = %d" % (dbfile, _g(pvalue), _g(fraction), restarts, len(names))]
+    if polish_all:
+        out.append("# POLISH tops = %d all rows" % polish_all)
+    if gumbel is not None:
+        out.append("# GUMBEL censor = %s fitted = %d of %d" % (_g(gumbel[0]), gumbel[1], len(names)))
+    for q, name in enumerate(names):
+        joint, n1 = joints[q], len(joints[q])
+        lst = None if sses is None else sses[q]
+        out.append("# QUERY %s sses = %d hits = %d" % (name, n1, int(hits[q])))
+        if lst is not None:
+            out.append("# QUERY SSES = " + ",".join(str(int(l) + 1) for l in lst))
+        core, least = profile_core(joint, hits[q], fraction)
+        if not core.any():
+            out.append("# CORE none")
+        else:
+            members = [(int(lst[i]) if lst is not None else i) + 1 for i in range(n1) if core[i]]
+            out.append("# CORE sses = %d joint >= %d %s@%s" % (len(members), least, name, ",".join(map(str, members))))
+        for i in range(n1):
+            t = types[q][i]
+            out.append("%d %s %d %s" % (i + 1, t if isinstance(t, str) else _SSE_TYPE_NAMES[int(t) & 3], int(joint[i][i]),
+                                        " ".join(str(int(x)) for x in joint[i])))
+    return out

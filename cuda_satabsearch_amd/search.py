@@ -259,6 +259,28 @@ def _eval_nodes(obj, query_nodes):
     return nodes
 
 
+def _profile_rows_raw(obj, fn, handle, max_pvalue, query_node, hits, joint, offset):
+    """shared by Searcher / MultiSearcher.profile_rows_raw"""
+    node = None if query_node is None else np.ascontiguousarray(query_node, dtype=np.int32).ravel()
+    if node is not None and len(node) != getattr(obj, "n_queries", 1):
+        raise ValueError("one node per query of the batch is needed")
+    off = None if offset is None else np.ascontiguousarray(offset, dtype=np.int64).ravel()
+    if off is not None and len(off) != getattr(obj, "n_queries", 1):
+        raise ValueError("one offset per query of the batch is needed")
+    ptr = lambda a: None if a is None else a.ctypes.data
+    obj._check(fn(handle, float(max_pvalue), ptr(node), ptr(hits), ptr(joint), ptr(off)))
+
+
+def _profile_rows(obj, fn, handle, max_pvalue, query_node):
+    """shared by Searcher / MultiSearcher.profile_rows"""
+    n1s = obj._n1s.astype(np.int64)
+    cuts = np.concatenate([[0], np.cumsum(n1s * n1s)])
+    hits = np.zeros(len(n1s), np.uint32)
+    joint = np.zeros(max(int(cuts[-1]), 1), np.uint32)
+    _profile_rows_raw(obj, fn, handle, max_pvalue, query_node, hits, joint, None)
+    return hits, [joint[cuts[q]:cuts[q + 1]].reshape(int(n1s[q]), int(n1s[q])) for q in range(len(n1s))]
+
+
 def _eval_rows(obj, fn, handle, query_nodes, rocn):
     """shared by Searcher / MultiSearcher.eval_rows"""
     nodes = _eval_nodes(obj, query_nodes)
@@ -692,6 +714,20 @@ class Searcher:
         self._check(self._lib.sat_eval_tables(self._ctx, nodes.ctypes.data, counts.ctypes.data, None))
         return [counts[cuts[q]:cuts[q + 1]].reshape(2, int(bins[q])) for q in range(len(nodes))]
 
+    # ---- a query's SSEs profiled over its hits (sat_profile_rows) ----------------
+    def profile_rows(self, max_pvalue, query_node=None):
+        """Profile the last search, which must have run with lsoln (sat_profile_rows): (hits uint32[nq], a list with one
+        uint32[n1, n1] array per query).  A row counts when its p-value is <= max_pvalue and its entry is not the query's
+        own node (query_node[q], an index into the whole database; < 0 or None: the query is no entry); joint[i][k] is
+        the counted rows whose map matches SSE i and SSE k, the diagonal those that match SSE i at all.  Counted on the
+        device: 4 + 4 n1^2 bytes a query come back.  report.profile_core turns a matrix into the conserved core."""
+        return _profile_rows(self, self._lib.sat_profile_rows, self._ctx, max_pvalue, query_node)
+
+    def profile_rows_raw(self, max_pvalue, query_node, hits, joint, offset=None):
+        """sat_profile_rows into the caller's uint32 arrays: query q's matrix at joint[offset[q]], packed in query order
+        without offsets.  None passes a null pointer."""
+        _profile_rows_raw(self, self._lib.sat_profile_rows, self._ctx, max_pvalue, query_node, hits, joint, offset)
+
     def debug_set_scores(self, scores):
         """Test hook (satabsearch_debug.h): overwrite the last search's device scores with int32[nq, N]."""
         sc = np.ascontiguousarray(scores, dtype=np.int32)
@@ -790,6 +826,7 @@ class MultiSearcher:
         self._check(self._lib.sat_multi_queries_set(self._m, nq, n1s.ctypes.data, tabs.ctypes.data, dmats.ctypes.data,
                                                     pitch, types.ctypes.data, int(first_query_ordinal)))
         self.n_queries = nq
+        self._n1s = np.array(n1s, np.int32)
         self.n1max = int(n1s.max())
 
     def set_queries_from_db(self, entries, first_query_ordinal=0, sses=None):
@@ -807,6 +844,7 @@ class MultiSearcher:
                                                                  begin.ctypes.data, sse.ctypes.data, int(first_query_ordinal)))
             n1s = np.where(np.diff(begin) > 0, np.diff(begin), self._orders[idx])
         self.n_queries = len(idx)
+        self._n1s = np.array(n1s, np.int32)
         self.n1max = int(n1s.max())
 
     def debug_shard_queries(self, shard):
@@ -969,6 +1007,15 @@ class MultiSearcher:
         """Searcher.eval_rows of the whole database: each shard makes the tables of its own entries, the host sums and
         reduces them (sat_multi_eval_rows) - exactly what one searcher holding the whole database returns."""
         return _eval_rows(self, self._lib.sat_multi_eval_rows, self._m, query_nodes, rocn)
+
+    def profile_rows(self, max_pvalue, query_node=None):
+        """Searcher.profile_rows of the whole database: each shard profiles its own entries and the host adds the
+        matrices (sat_multi_profile_rows) - exactly what one searcher holding the whole database returns."""
+        return _profile_rows(self, self._lib.sat_multi_profile_rows, self._m, max_pvalue, query_node)
+
+    def profile_rows_raw(self, max_pvalue, query_node, hits, joint, offset=None):
+        """Searcher.profile_rows_raw over every shard."""
+        _profile_rows_raw(self, self._lib.sat_multi_profile_rows, self._m, max_pvalue, query_node, hits, joint, offset)
 
     def set_statistics(self, fits):
         """Searcher.set_statistics on every shard (sat_multi_stats_set)."""

@@ -807,6 +807,31 @@ int sat_eval_rows(sat_ctx *ctx, const int32_t *query_node, int rocn, sat_eval *r
 int sat_eval_tables(sat_ctx *ctx, const int32_t *query_node, uint32_t *counts, const int64_t *offset);
 int sat_multi_eval_classes(sat_multi *m, const int32_t *node_class);
 int sat_multi_eval_rows(sat_multi *m, const int32_t *query_node, int rocn, sat_eval *rows);
+/*
+ * A query's SSEs profiled over its hits, on the GPUs (the core of a profile is csrc/host/sat_profile.h's).
+ *
+ * sat_profile_rows   profiles the LAST search (it never searches: SAT_ESTATE before one, and after one without lsoln -
+ *                    the maps are what it reads).  A row (q, e) counts iff its p-value - the double sat_hits_cutoff
+ *                    compares: an installed fit and a whole-database polish are followed - is <= max_pvalue and, where
+ *                    query_node is not NULL and query_node[q] >= 0, the entry's ordinal in the whole database is not
+ *                    query_node[q]: a structure is no hit of itself.  (No range check: a node no ordinal equals excludes
+ *                    nothing.)  hits[q] is the number of counted rows; query q of order n1 has the n1 x n1 matrix, row-
+ *                    major, full and symmetric, joint[offset[q] + i * n1 + k] = the counted rows whose map matches SSE i
+ *                    and SSE k, the diagonal the rows that match SSE i at all.  offset = NULL packs the matrices one after
+ *                    the other in query order (the sum of n1 * n1 words); words between the matrices are not written.
+ *                    The counting is done on the device, in integers: exactly 4 * n_queries + 4 * sum(n1 * n1) bytes
+ *                    come back, no row and no map.  The result buffers, an installed fit, the polish setting, a cluster
+ *                    or cover accumulator and installed classes are left alone; a second call gives the same numbers.
+ *                    SAT_EINVAL, and nothing changes: hits or joint NULL, max_pvalue negative or not finite.
+ * sat_multi_profile_rows   the same over every shard, exactly what one context holding the whole database returns, bit
+ *                    for bit: every check is made for every shard before the first one works; each shard profiles its
+ *                    own entries and the host adds the matrices (ndev * the bytes above cross to it); with one shard
+ *                    nothing is added.
+ */
+int sat_profile_rows(sat_ctx *ctx, double max_pvalue, const int32_t *query_node, uint32_t *hits, uint32_t *joint,
+                     const int64_t *offset);
+int sat_multi_profile_rows(sat_multi *m, double max_pvalue, const int32_t *query_node, uint32_t *hits, uint32_t *joint,
+                           const int64_t *offset);
 unsigned long long sat_multi_stat_d2h_bytes(const sat_multi *m);
 
 /*
