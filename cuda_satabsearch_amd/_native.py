@@ -42,6 +42,9 @@ ABI_SYMBOLS = (
     "sat_cover_begin", "sat_cover_add", "sat_cover_solve", "sat_cover_end",
     "sat_multi_cover_begin", "sat_multi_cover_add", "sat_multi_cover_solve",
     "sat_profile_rows", "sat_multi_profile_rows",
+    "sat_baseline_keep", "sat_baseline_drop", "sat_baseline_results", "sat_reorder_hits", "sat_search_reordered",
+    "sat_multi_baseline_keep", "sat_multi_baseline_drop", "sat_multi_baseline_results", "sat_multi_reorder_hits",
+    "sat_multi_search_reordered",
 )
 
 MAX_CLUSTER_LEVELS = 8
@@ -62,6 +65,12 @@ class Hit(C.Structure):
     """struct sat_hit of include/satabsearch.h"""
     _fields_ = [("entry", C.c_int32), ("score", C.c_int32), ("norm2", C.c_double), ("zscore", C.c_double),
                 ("pvalue", C.c_double)]
+
+
+class ReorderHit(C.Structure):
+    """struct sat_reorder_hit of include/satabsearch.h, 64 bytes"""
+    _fields_ = [("hit", Hit), ("base_pvalue", C.c_double), ("base_score", C.c_int32), ("kind", C.c_int32),
+                ("matched", C.c_int32), ("descents", C.c_int32), ("cut", C.c_int32), ("pad", C.c_int32)]
 
 
 class Fit(C.Structure):
@@ -223,6 +232,18 @@ def device_lib():
         if hasattr(lib, "sat_profile_rows"):
             lib.sat_profile_rows.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             lib.sat_multi_profile_rows.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        # (as above: a build of the parent commit predates the reordered hits)
+        if hasattr(lib, "sat_reorder_hits"):
+            for name in ("sat_baseline_keep", "sat_baseline_drop", "sat_multi_baseline_keep", "sat_multi_baseline_drop"):
+                getattr(lib, name).argtypes = [C.c_void_p]
+            lib.sat_baseline_results.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.sat_multi_baseline_results.argtypes = lib.sat_baseline_results.argtypes
+            lib.sat_reorder_hits.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                             C.c_void_p]
+            lib.sat_multi_reorder_hits.argtypes = lib.sat_reorder_hits.argtypes
+            lib.sat_search_reordered.argtypes = [C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_double)]
+            lib.sat_multi_search_reordered.argtypes = lib.sat_search_reordered.argtypes
+            lib.sat_debug_baseline_shape.argtypes = [C.c_void_p, C.c_int, C.c_int]        # include/satabsearch_debug.h
         lib.sat_hits_cutoff.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         lib.sat_multi_search_cutoff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                                 C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
@@ -297,6 +318,8 @@ def host_lib():
         lib.sat_cover_sizes.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
         lib.sat_cover_greedy.argtypes = [C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.sat_profile_core.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+        lib.sat_map_kind.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.sat_map_kind.restype = C.c_int32
         _host = lib
     return _host
 

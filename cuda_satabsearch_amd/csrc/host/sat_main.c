@@ -54,7 +54,12 @@
  * query come back.  Under a "# PROFILE ..." header each query gets "# QUERY name sses = n1 hits = H", its conserved core
  * "# CORE sses = c joint >= J name@list" - sat_profile.h: SSEs every two of which are matched together in at least F,
  * default 0.5, of the hits; the text after J is a SID@list line for -q / -Q - and n1 lines "i type matched joint_i1 ..
- * joint_in1" instead of any rows).
+ * joint_in1" instead of any rows), -X B [-x kinds] with -p P (hits out of sequence order: every batch is searched twice on
+ * the GPUs, in order without maps and - kept on the device as the baseline - out of order with maps, whatever the input's
+ * LORDER and LSOLN say; sat_multi_reorder_hits then selects, of -p P's rows of the second search, those whose ordered
+ * p-value is >= B and whose map is of one of the kinds - s sequential, c circular, n not sequential otherwise; default
+ * cn, sat_reorder.h - and each block, under one more header line "# REORDER ordered pvalue >= B kinds = cn", lists only
+ * those rows, with six more columns: ordered_raw ordered_pvalue kind(seq|circ|perm) matched descents cut).
  * Motif queries: with -q dbfile and -Q dbfile a stdin line may be SID@list, the list (sat_parse_sse_list: 2,1,8,5,3 or
  * 1-3,9 - 1-based, as pytableaucreate.py -s takes it, but kept in the order given) naming the SSEs of that entry the
  * query is made of.  The block gets a header line "# QUERY SSES = 2,1,8,5,3" after "# DBFILE" and is otherwise printed
@@ -117,13 +122,16 @@ static double now_ms(void)
 #pragma weak sat_multi_eval_rows
 #pragma weak sat_multi_profile_rows
 #pragma weak sat_profile_core
+#pragma weak sat_multi_baseline_keep
+#pragma weak sat_multi_reorder_hits
 
 static void usage(const char *prog)
 {
     fprintf(stderr, "Usage: %s [-c] [-q dbfile | -Q dbfile | -a dbfile] [-r restarts] [-g gpus] [-G gpu,gpu,...] [-s seed]\n"
                     "       [-k K] [-p P] [-m M] [-M M] [-R restarts [-C C]] [-F censor] [-P T] [-A] [-L P] [-b] [-H P1,P2,...]\n"
                     "       [-E classfile [-N n]] [-D P]\n"
-                    "       [-W P [-f F]]\n", prog);
+                    "       [-W P [-f F]]\n"
+                    "       [-X B [-x kinds]]\n", prog);
     fprintf(stderr, "  -c : run on host CPU not GPU card\n");
     fprintf(stderr, "  -q dbfile : database is read from dbfile, list of query\n"
                     "              ids is read from stdin\n");
@@ -181,6 +189,13 @@ static void usage(const char *prog)
                     "         (not with -c, -k, -p, -m, -M, -R, -C, -L, -H, -D, -E, -N)\n");
     fprintf(stderr, "  -f F : with -W: every two SSEs of the core are matched together in at least F (0 < F <= 1) of the hits.\n"
                     "         Default 0.5\n");
+    fprintf(stderr, "  -X B : with -p P: only the hits that need a match out of sequence order - every query is searched in order\n"
+                    "         and out of order (whatever LORDER and LSOLN say), and of -p's rows of the second search those are\n"
+                    "         printed whose ordered p-value is >= B (0..1) and whose map is of one of -x's kinds; six more columns\n"
+                    "         a row: ordered_raw ordered_pvalue kind(seq|circ|perm) matched descents cut; use -F with it\n"
+                    "         (not with -c, -m, -M, -R, -C, -L, -H, -D, -E, -N, -W)\n");
+    fprintf(stderr, "  -x kinds : with -X: the kinds of map printed, letters of s (sequential), c (circular permutation),\n"
+                    "         n (not sequential otherwise). Default cn\n");
     fprintf(stderr, "  -b : cache the parsed database as dbfile.satbin\n");
     exit(1);
 }
@@ -338,6 +353,9 @@ typedef struct {
     int rocn;                         /* -N: the negatives ROC-n counts up to (0: not given) */
     int profile;                      /* -W: profile each query's SSEs over its hits instead of printing rows */
     double wmax;                      /* -W: the largest p-value of a hit */
+    int reorder;                      /* -X: only the rows that are hits out of sequence order alone */
+    double bmin;                      /* -X: the smallest ordered p-value of such a row */
+    int kinds;                        /* -x: SAT_KIND_* bits of the maps printed (0: not given) */
     int core_given;                   /* -f was given */
     double core;                      /* -f: the fraction of the hits every pair of the core is matched together in */
     unsigned long long seed;
@@ -506,12 +524,36 @@ static int parse_levels(const char *arg, options *o)
     }
 }
 
+/* -x's letters as SAT_KIND_* bits; 0: empty, or another character */
+static int parse_kinds(const char *arg)
+{
+    int kinds = 0;
+    for (const char *c = arg; *c; c++) {
+        if (*c == 's') kinds |= SAT_KIND_SEQUENTIAL;
+        else if (*c == 'c') kinds |= SAT_KIND_CIRCULAR;
+        else if (*c == 'n') kinds |= SAT_KIND_PERMUTED;
+        else return 0;
+    }
+    return kinds;
+}
+
+/* the bits as -x's letters, in the order s, c, n */
+static const char *kinds_text(int kinds, char text[4])
+{
+    int n = 0;
+    if (kinds & SAT_KIND_SEQUENTIAL) text[n++] = 's';
+    if (kinds & SAT_KIND_CIRCULAR) text[n++] = 'c';
+    if (kinds & SAT_KIND_PERMUTED) text[n++] = 'n';
+    text[n] = '\0';
+    return text;
+}
+
 /* The options, then the refusals in a fixed order (the tests pin it), all before the banner and any device call */
 static void parse_options(int argc, char *argv[], options *o)
 {
     *o = (options){ .use_gpu = 1, .maxstart = 128, .want_gpus = 1, .seed = SAT_DEFAULT_SEED };
     int c;
-    while ((c = getopt(argc, argv, "cq:Q:a:r:g:G:s:bk:p:m:M:R:C:F:P:AL:H:E:N:D:W:f:")) != -1) {
+    while ((c = getopt(argc, argv, "cq:Q:a:r:g:G:s:bk:p:m:M:R:C:F:P:AL:H:E:N:D:W:f:X:x:")) != -1) {
         char *end = NULL;
         long v;
         switch (c) {
@@ -564,6 +606,23 @@ static void parse_options(int argc, char *argv[], options *o)
                 usage(argv[0]);
             }
             o->profile = 1;
+            break;
+        case 'X':
+            /* the whole argument, a finite number in [0, 1] */
+            o->bmin = strtod(optarg, &end);
+            if (end == optarg || *end != '\0' || !isfinite(o->bmin) || o->bmin < 0.0 || o->bmin > 1.0) {
+                fprintf(stderr, "ERROR: -X needs a p-value in [0, 1] (got '%s')\n", optarg);
+                usage(argv[0]);
+            }
+            o->reorder = 1;
+            break;
+        case 'x':
+            /* the whole argument, one or more of the letters s, c, n */
+            o->kinds = parse_kinds(optarg);
+            if (!o->kinds) {
+                fprintf(stderr, "ERROR: -x needs letters of s, c, n (got '%s')\n", optarg);
+                usage(argv[0]);
+            }
             break;
         case 'f':
             /* the whole argument, a number in (0, 1] */
@@ -637,6 +696,26 @@ static void parse_options(int argc, char *argv[], options *o)
             break;
         default: usage(argv[0]);
         }
+    }
+    if (o->kinds && !o->reorder) die("ERROR: -x needs -X B\n");
+    if (o->reorder) {
+        /* hits out of sequence order: -p's run, searched twice, with another selection */
+        if (!o->use_gpu) die("ERROR: -X cannot be combined with -c\n");
+        if (o->nmatch) die("ERROR: -X cannot be combined with -m\n");
+        if (o->rowmatch) die("ERROR: -X cannot be combined with -M\n");
+        if (o->refine) die("ERROR: -X cannot be combined with -R\n");
+        if (o->ncand) die("ERROR: -X cannot be combined with -C\n");
+        if (o->cluster) die("ERROR: -X cannot be combined with -L\n");
+        if (o->nlevels) die("ERROR: -X cannot be combined with -H\n");
+        if (o->cover) die("ERROR: -X cannot be combined with -D\n");
+        if (o->classfile) die("ERROR: -X cannot be combined with -E\n");
+        if (o->rocn) die("ERROR: -X cannot be combined with -N\n");
+        if (o->profile) die("ERROR: -X cannot be combined with -W\n");
+        if (!o->cutoff) die("ERROR: -X needs -p P\n");
+        if (o->polish && !o->polish_all) die("ERROR: -X takes -P T only with -A\n");
+        if (!sat_multi_search_only || !sat_multi_search_fit || !sat_multi_baseline_keep || !sat_multi_reorder_hits)
+            die("ERROR: this library has no sat_multi_reorder_hits\n");
+        if (!o->kinds) o->kinds = SAT_KIND_CIRCULAR | SAT_KIND_PERMUTED;
     }
     if (o->core_given && !o->profile) die("ERROR: -f needs -W P\n");
     if (o->profile) {
@@ -1033,6 +1112,9 @@ typedef struct {
     int32_t *hit_maps;
     int32_t *pcounts;                 /* -p: rows of each query of the batch */
     int hits_cap;                     /* -p: rows hits holds */
+    int reorder;                      /* -X: the rows come as rhits, hits holds their sat_hit part */
+    sat_reorder_hit *rhits;           /* -X: hits_cap of them */
+    sat_fit *base_fits;               /* -X with -F: the batch's fits of the ordered search */
     slots rowm;                       /* -M: the slots of the batch's ranked rows, row r of hits */
     int32_t *rowm_restarts, *pair_q, *pair_e;   /* -M: each slot's restart; the rows as (query, entry) pairs */
     size_t rowm_cap;                  /* -M: rows they hold */
@@ -1055,6 +1137,10 @@ static void alloc_hits(gpu_bufs *B, size_t rows, int lsoln)
     free(B->hits);
     free(B->hit_maps);
     B->hits = checked(malloc(sizeof(sat_hit) * rows));
+    if (B->reorder) {
+        free(B->rhits);
+        B->rhits = checked(malloc(sizeof(sat_reorder_hit) * rows));
+    }
     B->hit_maps = lsoln ? checked(malloc(sizeof(int32_t) * SAT_MAXDIM * rows)) : NULL;
 }
 
@@ -1062,7 +1148,7 @@ static void alloc_gpu_bufs(const options *o, const input *in, gpu_bufs *B)
 {
     const int total = in->db.count, nm = o->nm, lsoln = in->lsoln;
     const int entry_slots = (!o->ranked && !o->cluster && !o->classfile && !o->profile) || o->nmatch;     /* every entry's slots come to the host */
-    *B = (gpu_bufs){ .batch = 256, .kk = o->topk < total ? o->topk : total };
+    *B = (gpu_bufs){ .batch = 256, .kk = o->topk < total ? o->topk : total, .reorder = o->reorder };
     /* Queries go to the GPUs in batches: one set of launches scores a whole batch (grid = entries x queries), which
      * is what fills the machine when the database is small and the query list long (-q).  The batch size is bounded
      * by the host slots of every entry: score and map, with -m also count and restarts (the device holds the same
@@ -1107,6 +1193,8 @@ static void alloc_gpu_bufs(const options *o, const input *in, gpu_bufs *B)
         alloc_hits(B, (size_t)B->kk * B->batch, lsoln);  /* only K rows per query (and GPU) ever leave the GPUs */
     }
     B->n1s = checked(malloc(sizeof(int32_t) * (size_t)B->batch));
+    if (o->reorder && o->fit)
+        B->base_fits = checked(calloc((size_t)B->batch, sizeof(sat_fit)));
     if (o->from_db && in->motifs)
         B->sse_begin = checked(malloc(sizeof(int32_t) * ((size_t)B->batch + 1)));
     if (o->from_db)
@@ -1154,6 +1242,8 @@ static void free_gpu_bufs(gpu_bufs *B)
     free(B->restarts);
     free_slots(&B->large);
     free(B->hits);
+    free(B->rhits);
+    free(B->base_fits);
     free(B->hit_maps);
     free(B->pcounts);
     free_slots(&B->rowm);
@@ -1205,6 +1295,31 @@ static int search_batch(const options *o, const input *in, sat_multi *multi, gpu
         if (o->fit)
             return sat_multi_search_fit(multi, lorder, o->profile, maxstart, o->censor, fits, ms);
         return sat_multi_search_only(multi, lorder, o->profile, maxstart, ms);
+    }
+    if (o->reorder) {
+        /* -X: the ordered search without maps, fitted (-F) and kept on the GPUs as the baseline; the unordered search with
+         * maps, fitted to its own scores; then of -p's rows those the baseline does not call a hit and whose map is of one
+         * of the kinds.  A short buffer is grown and the rows selected again. */
+        double ms2 = 0.0;
+        int rc = o->fit ? sat_multi_search_fit(multi, 1, 0, maxstart, o->censor, B->base_fits, ms)
+                        : sat_multi_search_only(multi, 1, 0, maxstart, ms);
+        if (rc == SAT_OK)
+            rc = sat_multi_baseline_keep(multi);
+        if (rc == SAT_OK)
+            rc = o->fit ? sat_multi_search_fit(multi, 0, 1, maxstart, o->censor, fits, &ms2)
+                        : sat_multi_search_only(multi, 0, 1, maxstart, &ms2);
+        *ms += ms2;
+        if (rc != SAT_OK)
+            return rc;
+        rc = sat_multi_reorder_hits(multi, o->pmax, o->bmin, o->kinds, o->topk, B->pcounts, B->hits_cap, B->rhits, B->hit_maps);
+        if (rc > B->hits_cap) {
+            B->hits_cap = rc;
+            alloc_hits(B, (size_t)rc, 1);
+            rc = sat_multi_reorder_hits(multi, o->pmax, o->bmin, o->kinds, o->topk, B->pcounts, B->hits_cap, B->rhits, B->hit_maps);
+        }
+        for (int r = 0; r < rc; r++)
+            B->hits[r] = B->rhits[r].hit;
+        return rc;
     }
     if (o->fit && o->ranked) {
         /* search, histogram and fit on the GPUs (fits: the batch's), then the rows by the fitted p-values: those under
@@ -1287,6 +1402,35 @@ static void print_batch(const options *o, const input *in, gpu_bufs *B, const sa
     for (int b = 0; b < nqb; b++) {
         const size_t row0 = (size_t)b * in->db.count;
         print_header(in, q0 + b, fits ? &fits[q0 + b] : NULL);
+        if (o->reorder) {
+            /* -X: one more header line (two with -F: the ordered search's fit), then the rows with their six columns,
+             * each followed by the unordered map's lines.  Few rows: printf formats them. */
+            char line[256], kt[4];
+            const int n1 = B->n1s[b];
+            int n = snprintf(line, sizeof line, "# REORDER ordered pvalue >= %g kinds = %s\n", o->bmin, kinds_text(o->kinds, kt));
+            out_bytes(line, (size_t)n);
+            if (B->base_fits) {
+                const sat_fit *f = &B->base_fits[b];
+                n = f->fitted ? snprintf(line, sizeof line, "# GUMBEL ordered a = %.17g b = %.17g rows = %d censored = %d below = %d\n",
+                                         f->a, f->b, f->rows, f->censored, f->below)
+                              : snprintf(line, sizeof line, "# GUMBEL ordered not fitted\n");
+                out_bytes(line, (size_t)n);
+            }
+            for (size_t r = first; r < first + (size_t)B->pcounts[b]; r++) {
+                const sat_reorder_hit *h = &B->rhits[r];
+                const char *kind = h->kind == SAT_KIND_SEQUENTIAL ? "seq" : h->kind == SAT_KIND_CIRCULAR ? "circ" : "perm";
+                n = snprintf(line, sizeof line, "%-8s %d %g %g %g %d %g %s %d %d %d\n", sat_set_name(&in->db, h->hit.entry), h->hit.score,
+                             h->hit.norm2, h->hit.zscore, h->hit.pvalue, h->base_score, h->base_pvalue, kind, h->matched, h->descents,
+                             h->cut);
+                out_bytes(line, (size_t)n);
+                const int32_t *map = B->hit_maps + r * SAT_MAXDIM;
+                for (int k = 0; k < n1; k++)
+                    if (map[k] >= 0)
+                        out_map_line(k + 1, map[k] + 1);
+            }
+            first += (size_t)B->pcounts[b];
+            continue;
+        }
         if (o->ranked) {
             const size_t nrows = (size_t)(o->csr ? B->pcounts[b] : rc);
             for (size_t r = first; r < first + nrows; r++)
@@ -1696,6 +1840,11 @@ int main(int argc, char *argv[])
     sat_set_init(&in.db);
     read_queries(&o, &in);
     load_database(&o, &in);
+    if (o.reorder) {
+        /* -X runs both searches itself; its rows are the unordered search's, with their maps */
+        in.lorder = 0;
+        in.lsoln = 1;
+    }
     fprintf(stderr, "maxstart = %d\n", o.maxstart);
     const int status = o.use_gpu ? run_gpu(&o, &in) : run_host(&o, &in);
     free_input(&in);

@@ -250,6 +250,17 @@ struct sat_ctx {
     DevBuf<uint32_t> d_profile;
     DevBuf<unsigned char> d_profile_q;
 
+    // the baseline of sat_reorder_hits (sat_baseline_keep, sat_reorder.hip): every row's score and p-value
+    // of the search that was the last one when it was kept, laid out as d_scores - 12 bytes a row.  baseline_nq x
+    // baseline_n rows, 0 = none kept: it belongs to (resident database, query batch), so an upload and a query change
+    // drop it; searches, fits, the polish setting and the accumulators leave it alone.  The buffers only grow.
+    size_t baseline_nq = 0;
+    int baseline_n = 0;
+    DevBuf<int32_t> d_bl_score;
+    DevBuf<double> d_bl_pvalue;
+    // the selection's rows (sat_reorder_hit) before they leave; scratch that only grows
+    DevBuf<sat_reorder_hit> d_reorder_rows;
+
     // bytes copied device -> host by this context's result calls (sat_stat_d2h_bytes)
     unsigned long long d2h_bytes = 0;
     // bytes copied host -> device by sat_queries_set / sat_queries_from_db (sat_stat_query_h2d_bytes)
@@ -282,6 +293,9 @@ void sat_eval_drop(sat_ctx *ctx);
 
 // ---- sat_profile.hip.  Load that file's code object (an empty launch of a small kernel).
 int sat_profile_load_code(sat_ctx *ctx);
+
+// ---- sat_reorder.hip.  Load that file's code object (an empty launch of a small kernel).
+int sat_reorder_load_code(sat_ctx *ctx);
 
 // ---- sat_qfromdb.hip, for sat_multi_queries_from_db.  sat_queries_from_db on one shard's context, every check made by
 // the caller: query q has order n1s[q] and is entry code[q] >= 0 of this shard, or code[q] = -query_n1p(n1s[q]): a

@@ -156,3 +156,13 @@ int sat_cutoff_rows(sat_ctx *ctx, double max_pvalue, int max_rows, const int32_t
 // ---- The checks of sat_profile_rows (sat_profile.hip) behind the context's, in its order and nothing else: a search
 // has run, with lsoln; the two arrays; the p-value.  sat_multi_profile_rows makes them for every shard before the first works.
 int sat_profile_check(sat_ctx *ctx, double max_pvalue, const uint32_t *hits, const uint32_t *joint);
+
+// ---- sat_reorder_hits (sat_reorder.hip) in three parts, for sat_multi_reorder_hits, which makes the checks for every
+// shard before the first works and sums the shards' counts between the halves.  The checks behind the context's, in
+// their order: a search has run, with lsoln; a baseline, of the searched shape; counts; the two p-values; kinds.  Then
+// the halves, as sat_cutoff_count / sat_cutoff_rows above with the wider predicate and rows: counts[q] uncapped,
+// 4 * n_queries bytes; the rows (64 bytes each) and maps (may be NULL) in CSR order.
+int sat_reorder_check(sat_ctx *ctx, double max_pvalue, double min_base_pvalue, int kinds, const int32_t *counts);
+int sat_reorder_count(sat_ctx *ctx, double max_pvalue, double min_base_pvalue, int kinds, int32_t *counts);
+int sat_reorder_rows(sat_ctx *ctx, double max_pvalue, double min_base_pvalue, int kinds, int max_rows, const int32_t *counts,
+                     sat_reorder_hit *rows, int32_t *ssemaps);

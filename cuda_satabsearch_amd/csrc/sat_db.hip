@@ -45,6 +45,7 @@ void free_db(sat_ctx *ctx)
     ctx->min_rows = 0;
     ctx->searched_nq = 0;
     ctx->fits.clear();
+    ctx->baseline_nq = 0;                     // the kept baseline was of this database's rows
     ctx->h_orders.clear();
 }
 
@@ -528,6 +529,7 @@ int sat_queries_set(sat_ctx *ctx, int n_queries, const int32_t *n1s, const uint8
     ctx->desc_dirty = true;
     ctx->searched_nq = 0;                     // the result buffers no longer belong to the current batch
     ctx->fits.clear();
+    ctx->baseline_nq = 0;                     // nor does a kept baseline
     return SAT_OK;
 }
 

@@ -1088,6 +1088,109 @@ int sat_multi_profile_rows(sat_multi *m, double max_pvalue, const int32_t *query
     return SAT_OK;
 }
 
+int sat_multi_baseline_keep(sat_multi *m)
+{
+    SAT_TRY(check_multi(m));
+    for (sat_ctx *c : m->ctx) SAT_TRY(sat_check_searched(c));
+    return each_shard(m, [&](int g) { return sat_baseline_keep(m->ctx[(size_t)g]); });
+}
+
+int sat_multi_baseline_drop(sat_multi *m)
+{
+    SAT_TRY(sat_check_context(m));
+    for (sat_ctx *c : m->ctx) SAT_TRY(sat_baseline_drop(c));
+    return SAT_OK;
+}
+
+int sat_multi_baseline_results(sat_multi *m, int32_t *scores, double *pvalues)
+{
+    SAT_TRY(check_multi(m));
+    for (sat_ctx *c : m->ctx)
+        if (!c->baseline_nq) return sat_baseline_results(c, scores, pvalues);          // its SAT_ESTATE and text
+    // each shard's [nq][its entries] rows into the columns of its entries
+    const size_t nq = m->ctx[0]->baseline_nq, total = (size_t)m->n_entries;
+    std::vector<int32_t> s;
+    std::vector<double> p;
+    for (int g = 0; g < m->ndev; g++) {
+        const size_t ng = (size_t)(m->begin[(size_t)g + 1] - m->begin[(size_t)g]), at = (size_t)m->begin[(size_t)g];
+        if (scores) s.resize(nq * ng);
+        if (pvalues) p.resize(nq * ng);
+        SAT_TRY(sat_baseline_results(m->ctx[(size_t)g], scores ? s.data() : nullptr, pvalues ? p.data() : nullptr));
+        for (size_t q = 0; q < nq; q++) {
+            if (scores) std::copy(s.begin() + q * ng, s.begin() + (q + 1) * ng, scores + q * total + at);
+            if (pvalues) std::copy(p.begin() + q * ng, p.begin() + (q + 1) * ng, pvalues + q * total + at);
+        }
+    }
+    return SAT_OK;
+}
+
+int sat_multi_reorder_hits(sat_multi *m, double max_pvalue, double min_base_pvalue, int kinds, int max_rows, int32_t *counts,
+                           int capacity, sat_reorder_hit *rows, int32_t *ssemaps)
+{
+    SAT_TRY(check_multi(m));
+    // the checks of sat_reorder_hits, made for all shards before the first one works
+    for (sat_ctx *c : m->ctx) SAT_TRY(sat_reorder_check(c, max_pvalue, min_base_pvalue, kinds, counts));
+    const int nq = (int)m->ctx[0]->queries.size();
+    // every shard counts its qualifying rows; a query's rows are the sum, cut to max_rows
+    std::vector<std::vector<int32_t>> raw((size_t)m->ndev, std::vector<int32_t>((size_t)nq));
+    for (int g = 0; g < m->ndev; g++) SAT_TRY(sat_reorder_count(m->ctx[(size_t)g], max_pvalue, min_base_pvalue, kinds, raw[(size_t)g].data()));
+    size_t total = 0;
+    for (int q = 0; q < nq; q++) {
+        long long c = 0;
+        for (int g = 0; g < m->ndev; g++) c += raw[(size_t)g][(size_t)q];
+        counts[q] = sat_row_cap(c > INT_MAX ? INT_MAX : (int32_t)c, max_rows);
+        total += (size_t)counts[q];
+    }
+    if (total > (size_t)INT_MAX) return sat_fail(SAT_EINVAL, "%zu rows qualify: more than one call can return", total);
+    if (!rows || (long long)total > (long long)capacity) return (int)total;
+    // each shard's rows (max_rows per query at most), merged per query: score descending, ties in database order - the
+    // lower shard first, as merge_shards has it for sat_multi_hits_cutoff
+    std::vector<std::vector<sat_reorder_hit>> part((size_t)m->ndev);
+    std::vector<std::vector<int32_t>> pmaps((size_t)m->ndev);
+    std::vector<std::vector<size_t>> off((size_t)m->ndev, std::vector<size_t>((size_t)nq + 1, 0));
+    for (int g = 0; g < m->ndev; g++) {
+        for (int q = 0; q < nq; q++) off[(size_t)g][(size_t)q + 1] = off[(size_t)g][(size_t)q] + (size_t)sat_row_cap(raw[(size_t)g][(size_t)q], max_rows);
+        part[(size_t)g].resize(off[(size_t)g][(size_t)nq]);
+        if (ssemaps) pmaps[(size_t)g].resize(off[(size_t)g][(size_t)nq] * SAT_MAXDIM);
+        SAT_TRY(sat_reorder_rows(m->ctx[(size_t)g], max_pvalue, min_base_pvalue, kinds, max_rows, raw[(size_t)g].data(), part[(size_t)g].data(),
+                                 ssemaps ? pmaps[(size_t)g].data() : nullptr));
+    }
+    size_t out = 0;
+    std::vector<size_t> head((size_t)m->ndev);
+    for (int q = 0; q < nq; q++) {
+        for (int g = 0; g < m->ndev; g++) head[(size_t)g] = off[(size_t)g][(size_t)q];
+        for (int32_t r = 0; r < counts[q]; r++) {
+            int bg = -1;
+            for (int g = 0; g < m->ndev; g++)
+                if (head[(size_t)g] < off[(size_t)g][(size_t)q + 1] &&
+                    (bg < 0 || part[(size_t)g][head[(size_t)g]].hit.score > part[(size_t)bg][head[(size_t)bg]].hit.score))
+                    bg = g;
+            const size_t row = head[(size_t)bg]++;
+            rows[out] = part[(size_t)bg][row];
+            rows[out].hit.entry += m->begin[(size_t)bg];
+            if (ssemaps) memcpy(ssemaps + out * SAT_MAXDIM, pmaps[(size_t)bg].data() + row * SAT_MAXDIM, sizeof(int32_t) * SAT_MAXDIM);
+            out++;
+        }
+    }
+    return (int)total;
+}
+
+int sat_multi_search_reordered(sat_multi *m, int maxstart, double censor, double *wall_ms)
+{
+    SAT_TRY(check_multi(m));
+    const bool fit = censor >= 0.0;
+    if (fit) SAT_TRY(sat_check_censor(censor));
+    const Stopwatch clock;
+    for (int pass = 0; pass < 2; pass++) {
+        const int lorder = pass == 0, lsoln = pass == 1;            // the ordered search is the baseline
+        SAT_TRY(fit ? sat_multi_search_fit(m, lorder, lsoln, maxstart, censor, nullptr, nullptr)
+                    : sat_multi_search_only(m, lorder, lsoln, maxstart, nullptr));
+        if (pass == 0) SAT_TRY(sat_multi_baseline_keep(m));
+    }
+    clock.stop(wall_ms);
+    return SAT_OK;
+}
+
 unsigned long long sat_multi_stat_d2h_bytes(const sat_multi *m)
 {
     if (!m) return 0ull;

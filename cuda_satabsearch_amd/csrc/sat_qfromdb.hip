@@ -194,6 +194,7 @@ int sat_qfromdb_set(sat_ctx *ctx, int n_queries, const int32_t *code, const int3
     ctx->desc_dirty = true;
     ctx->searched_nq = 0;
     ctx->fits.clear();
+    ctx->baseline_nq = 0;
     ctx->d_qblob.reset();
     ctx->d_qdesc.reset();
     int rc;

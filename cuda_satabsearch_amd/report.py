@@ -230,3 +230,45 @@ def profile_table(names, types, hits, joints, dbfile, pvalue, fraction, restarts
             out.append("%d %s %d %s" % (i + 1, t if isinstance(t, str) else _SSE_TYPE_NAMES[int(t) & 3], int(joint[i][i]),
                                         " ".join(str(int(x)) for x in joint[i])))
     return out
+
+
+KIND_NAMES = {1: "seq", 2: "circ", 4: "perm"}
+_KIND_LETTERS = ((1, "s"), (2, "c"), (4, "n"))
+
+
+def map_kind(ssemap):
+    """(kind, matched, descents, cut) of one solution map - the images of the query's SSEs, -1 where unmatched: kind 1
+    sequential (no descent among the images in query order), 2 circular (one descent and the last image below the
+    first: a rotation; cut = the 1-based query SSE at which the second run starts), 4 permuted (sat_map_kind of
+    csrc/host/sat_reorder.h, the definition the device's selection uses)."""
+    import ctypes as C
+    import numpy as np
+    m = np.ascontiguousarray(ssemap, dtype=np.int32).ravel()
+    out = (C.c_int32 * 3)()
+    base = C.addressof(out)
+    kind = _native.host_lib().sat_map_kind(m.ctypes.data if len(m) else None, len(m), base, base + 4, base + 8)
+    if kind < 0:
+        raise ValueError("bad map")
+    return int(kind), int(out[0]), int(out[1]), int(out[2])
+
+
+def reorder_table(names, rows, maps, n1, min_base_pvalue, kinds, base_fit=None):
+    """The lines the command line's -X prints for one query behind its usual header lines: rows and maps what
+    Searcher.reorder_hits(..., lsoln=True) returned for it, names the database's, n1 the query's order; base_fit: under
+    -F the ordered search's fit record (a, b, rows, censored, below, fitted)."""
+    out = ["# REORDER ordered pvalue >= %s kinds = %s" % (_g(min_base_pvalue), "".join(c for bit, c in _KIND_LETTERS if kinds & bit))]
+    if base_fit is not None:
+        f = base_fit
+        out.append("# GUMBEL ordered a = %.17g b = %.17g rows = %d censored = %d below = %d" % (f["a"], f["b"], f["rows"], f["censored"], f["below"])
+                   if f["fitted"] else "# GUMBEL ordered not fitted")
+    for r, row in enumerate(rows):
+        h = row["hit"]
+        out.append("%-8s %d %s %s %s %d %s %s %d %d %d" % (names[int(h["entry"])], int(h["score"]), _g(h["norm2"]), _g(h["zscore"]),
+                                                         _g(h["pvalue"]), int(row["base_score"]), _g(row["base_pvalue"]),
+                                                         KIND_NAMES[int(row["kind"])], int(row["matched"]), int(row["descents"]),
+                                                         int(row["cut"])))
+        for i in range(n1):
+            j = int(maps[r][i])
+            if j >= 0:
+                out.append("%3d %3d" % (i + 1, j + 1))
+    return out

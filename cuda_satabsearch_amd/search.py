@@ -121,6 +121,11 @@ assert _HIT_DTYPE.itemsize == C.sizeof(_native.Hit)
 
 
 # struct sat_fit (include/satabsearch.h) as a numpy record: fit_statistics, set_statistics, search_fit
+_REORDER_DTYPE = np.dtype([("hit", _HIT_DTYPE), ("base_pvalue", np.float64), ("base_score", np.int32), ("kind", np.int32),
+                           ("matched", np.int32), ("descents", np.int32), ("cut", np.int32), ("pad", np.int32)], align=True)
+assert _REORDER_DTYPE.itemsize == C.sizeof(_native.ReorderHit) == 64
+KIND_SEQUENTIAL, KIND_CIRCULAR, KIND_PERMUTED, KIND_ALL = 1, 2, 4, 7
+
 _FIT_DTYPE = np.dtype([("a", np.float64), ("b", np.float64), ("rows", np.int32), ("censored", np.int32),
                        ("below", np.int32), ("fitted", np.int32)], align=True)
 assert _FIT_DTYPE.itemsize == C.sizeof(_native.Fit)
@@ -178,14 +183,15 @@ def _search_refine_polish(obj, call, k, candidates, refine_maxstart, lsoln):
     return hits, maps, first, base[0].reshape(first.shape)
 
 
-def _hits_cutoff(obj, nq, lsoln, first, again):
+def _hits_cutoff(obj, nq, lsoln, first, again, dtype=_HIT_DTYPE):
     """shared by Searcher.hits_cutoff / MultiSearcher.search_cutoff: `first(counts, capacity, hits, maps)` runs the C
     entry point once; when the rows did not fit, `again` (same arguments) selects them again into a buffer of the
-    returned size.  Returns (list of nq hit arrays, list of nq int32[rows, 111] map arrays or None)."""
+    returned size.  Returns (list of nq hit arrays, list of nq int32[rows, 111] map arrays or None).  (dtype: the rows
+    of reorder_hits, which has the same contract.)"""
     counts = np.zeros(nq, np.int32)
     cap = max(int(getattr(obj, "_cutoff_cap", 0)), 256)
     for call in (first, again):
-        hits = np.zeros(cap, _HIT_DTYPE)
+        hits = np.zeros(cap, dtype)
         maps = np.full((cap, MAXDIM), -1, np.int32) if lsoln else None
         n = call(counts.ctypes.data, cap, hits.ctypes.data, maps.ctypes.data if lsoln else None)
         if n < 0:
@@ -197,6 +203,21 @@ def _hits_cutoff(obj, nq, lsoln, first, again):
     cuts = np.cumsum(counts)[:-1]
     rows = np.split(hits[:n], cuts)
     return rows, (np.split(maps[:n], cuts) if lsoln else None)
+
+
+def _baseline_results(obj, fn, handle, nq):
+    """shared by Searcher / MultiSearcher.baseline_results"""
+    scores = np.empty((nq, obj.n_entries), np.int32)
+    pvalues = np.empty((nq, obj.n_entries), np.float64)
+    obj._check(fn(handle, scores.ctypes.data, pvalues.ctypes.data))
+    return scores, pvalues
+
+
+def _reorder_hits(obj, fn, handle, nq, max_pvalue, min_base_pvalue, kinds, k, lsoln):
+    """shared by Searcher / MultiSearcher.reorder_hits"""
+    call = lambda c, cap, h, m: fn(handle, float(max_pvalue), float(min_base_pvalue), int(kinds), int(k or 0), c, cap, h, m)
+    rows, maps = _hits_cutoff(obj, nq, lsoln, call, call, _REORDER_DTYPE)
+    return (rows, maps) if lsoln else rows
 
 
 def _cluster_add(obj, fn, handle, max_pvalue, query_nodes):
@@ -585,6 +606,37 @@ class Searcher:
         rows, maps = _hits_cutoff(self, nq, lsoln, call, call)
         return (rows, maps) if lsoln else rows
 
+    # ---- hits out of sequence order (sat_baseline_*, sat_reorder_hits) ----------
+    def baseline_keep(self):
+        """Keep the rows of the last search - score and p-value, an installed fit followed - on the device as the
+        baseline of reorder_hits (sat_baseline_keep): 12 bytes a row, nothing crosses to the host, no wait.  An upload
+        and every query-setting call drop it; searches and fits leave it alone."""
+        self._check(self._lib.sat_baseline_keep(self._ctx))
+
+    def baseline_drop(self):
+        self._check(self._lib.sat_baseline_drop(self._ctx))
+
+    def baseline_results(self):
+        """The kept baseline: (scores int32[nq, n_entries], pvalues float64[nq, n_entries])."""
+        return _baseline_results(self, self._lib.sat_baseline_results, self._ctx, getattr(self, "n_queries", 1))
+
+    def reorder_hits(self, max_pvalue, min_base_pvalue=0.0, kinds=KIND_CIRCULAR | KIND_PERMUTED, k=None, lsoln=False):
+        """The rows of the last search (one with lsoln) that hits_cutoff(max_pvalue) returns, whose kept baseline p-value
+        is >= min_base_pvalue and whose map's order is one of `kinds` (an OR of KIND_SEQUENTIAL, KIND_CIRCULAR,
+        KIND_PERMUTED), selected on the device (sat_reorder_hits): a list of nq structured arrays with fields hit (a
+        hits_cutoff row), base_pvalue, base_score, kind, matched, descents, cut; in hits_cutoff's order, cut to the first
+        k; with lsoln also the list of int32[rows, 111] maps."""
+        return _reorder_hits(self, self._lib.sat_reorder_hits, self._ctx, getattr(self, "n_queries", 1), max_pvalue,
+                             min_base_pvalue, kinds, k, lsoln)
+
+    def search_reordered(self, maxstart=DEFAULT_MAXSTART, censor=None):
+        """The ordered search, kept as the baseline, then the unordered search with maps (sat_search_reordered); censor
+        not None: each fitted to its own scores (fit_statistics).  reorder_hits - and every other selection call - then
+        works on the unordered search.  Returns the two searches' kernel_ms."""
+        ms = C.c_double(0.0)
+        self._check(self._lib.sat_search_reordered(self._ctx, int(maxstart), -1.0 if censor is None else float(censor), C.byref(ms)))
+        return ms.value
+
     def score_histogram(self):
         """The histogram of the last search's norm2 scores, made on the device (sat_score_histogram):
         (counts uint32[nq, 4096], below int32[nq]) - bin floor(norm2 * 256), the last bin the overflow; rows with a
@@ -928,6 +980,29 @@ class MultiSearcher:
         call = lambda c, cap, h, m: self._lib.sat_multi_hits_cutoff(self._m, float(max_pvalue), int(k or 0), c, cap, h, m)
         rows, maps = _hits_cutoff(self, self.n_queries, lsoln, call, call)
         return (rows, maps) if lsoln else rows
+
+    def baseline_keep(self):
+        """Searcher.baseline_keep on every shard (sat_multi_baseline_keep)."""
+        self._check(self._lib.sat_multi_baseline_keep(self._m))
+
+    def baseline_drop(self):
+        self._check(self._lib.sat_multi_baseline_drop(self._m))
+
+    def baseline_results(self):
+        """Searcher.baseline_results over the whole database (sat_multi_baseline_results)."""
+        return _baseline_results(self, self._lib.sat_multi_baseline_results, self._m, self.n_queries)
+
+    def reorder_hits(self, max_pvalue, min_base_pvalue=0.0, kinds=KIND_CIRCULAR | KIND_PERMUTED, k=None, lsoln=False):
+        """Searcher.reorder_hits over every shard, entries indexed in the whole database: exactly what one context
+        holding the whole database returns (sat_multi_reorder_hits)."""
+        return _reorder_hits(self, self._lib.sat_multi_reorder_hits, self._m, self.n_queries, max_pvalue, min_base_pvalue,
+                             kinds, k, lsoln)
+
+    def search_reordered(self, maxstart=DEFAULT_MAXSTART, censor=None):
+        """Searcher.search_reordered on every shard (sat_multi_search_reordered).  Returns wall_ms."""
+        ms = C.c_double(0.0)
+        self._check(self._lib.sat_multi_search_reordered(self._m, int(maxstart), -1.0 if censor is None else float(censor), C.byref(ms)))
+        return ms.value
 
     def score_histogram(self):
         """Searcher.score_histogram summed over every shard's last search (sat_multi_score_histogram)."""

@@ -835,6 +835,70 @@ int sat_multi_profile_rows(sat_multi *m, double max_pvalue, const int32_t *query
 unsigned long long sat_multi_stat_d2h_bytes(const sat_multi *m);
 
 /*
+ * Hits that match only out of sequence order, on the GPUs (the order of a map is csrc/host/sat_reorder.h's).
+ * Two searches of the same (database, query batch) are compared on the device: the first is KEPT as the baseline, the
+ * second is the searched state every selection call works on; sat_reorder_hits reports the rows of the second that the
+ * first does not call a hit and whose map has one of the asked-for orders.
+ *
+ * sat_baseline_keep   keeps the rows of the LAST search as the context's baseline: per row (q, e) its int32 score and
+ *                    its p-value - the double sat_hits_cutoff compares at that moment, an installed fit and a whole-
+ *                    database polish followed.  A small kernel on the context's stream; the call does not wait and
+ *                    nothing crosses to the host (sat_stat_d2h_bytes does not move).  Costs 12 bytes a row of device
+ *                    memory, kept until dropped.  SAT_ESTATE before a search.  The baseline belongs to (resident
+ *                    database, query batch): a database upload and every query-setting call drop it; searches, fits,
+ *                    sat_polish_all_set and the cluster, cover and eval state keep it.
+ * sat_baseline_drop   forgets it (the memory stays with the context).
+ * sat_baseline_results   the kept rows, [n_queries][n_entries] each; either array may be NULL.  Copies exactly 4 and /
+ *                    or 8 bytes a row.  SAT_ESTATE without a baseline.
+ * sat_reorder_hits   never searches.  Row (q, e) of the last search qualifies iff (1) sat_hits_cutoff's predicate passes
+ *                    it at max_pvalue - the same double from the same table index -, (2) its kept base_pvalue is >=
+ *                    min_base_pvalue (0: no condition) and (3) `kinds`, an OR of SAT_KIND_SEQUENTIAL (1),
+ *                    SAT_KIND_CIRCULAR (2), SAT_KIND_PERMUTED (4), has the bit of its map's kind.  Output, order (score
+ *                    descending, ties in database order), CSR layout, the cut to max_rows, the capacity contract (rows
+ *                    NULL or T > capacity: only counts is written, T returned) and the return value are
+ *                    sat_hits_cutoff's; rows[].hit is byte-equal to the sat_hit that call gives the row.  ssemaps (may
+ *                    be NULL): the rows' maps, SAT_MAXDIM each.  Copies 4 * n_queries + 64 * T bytes (+ 444 * T with
+ *                    ssemaps).  Integers and a fixed order throughout: the launch shape, the chunks of the query list
+ *                    and the sharding cannot show in a byte.
+ *                    SAT_ESTATE: no search has run; the last search ran without lsoln; no baseline; the baseline's shape
+ *                    is not the current n_queries x n_entries.  SAT_EINVAL, nothing changed: counts NULL; a p-value
+ *                    negative or not finite; kinds outside 1..7.
+ * sat_search_reordered   the two searches in one call: the ordered search (lorder = 1, lsoln = 0), sat_stats_fit(censor)
+ *                    when censor >= 0, sat_baseline_keep, the unordered search (lorder = 0, lsoln = 1), sat_stats_fit
+ *                    again - each search fitted to its own scores.  Afterwards the searched state is the unordered
+ *                    search's.  *kernel_ms (may be NULL): both searches' time on the stream.
+ * sat_multi_*        the same over every shard; sat_multi_reorder_hits merges as sat_multi_hits_cutoff does (per query
+ *                    by score, then by entry index in the whole database) and returns exactly what one context holding
+ *                    the whole database returns; every check is made for every shard before the first one works.
+ */
+#define SAT_KIND_SEQUENTIAL 1   /* (as csrc/host/sat_reorder.h defines them) */
+#define SAT_KIND_CIRCULAR   2
+#define SAT_KIND_PERMUTED   4
+#define SAT_KIND_ALL        7
+typedef struct sat_reorder_hit {
+    sat_hit hit;            /* the row sat_hits_cutoff gives                                             */
+    double  base_pvalue;    /* the baseline's p-value of the row                                         */
+    int32_t base_score;     /* and its raw score                                                         */
+    int32_t kind;           /* SAT_KIND_* of the map                                                     */
+    int32_t matched;        /* query SSEs the map matches                                                */
+    int32_t descents;       /* places where the images step down                                         */
+    int32_t cut;            /* circular: the 1-based query SSE at which the second run starts; else 0    */
+    int32_t pad;            /* 0                                                                         */
+} sat_reorder_hit;          /* 64 bytes */
+int sat_baseline_keep(sat_ctx *ctx);
+int sat_baseline_drop(sat_ctx *ctx);
+int sat_baseline_results(sat_ctx *ctx, int32_t *scores, double *pvalues);
+int sat_reorder_hits(sat_ctx *ctx, double max_pvalue, double min_base_pvalue, int kinds, int max_rows, int32_t *counts,
+                     int capacity, sat_reorder_hit *rows, int32_t *ssemaps);
+int sat_search_reordered(sat_ctx *ctx, int maxstart, double censor, double *kernel_ms);
+int sat_multi_baseline_keep(sat_multi *m);
+int sat_multi_baseline_drop(sat_multi *m);
+int sat_multi_baseline_results(sat_multi *m, int32_t *scores, double *pvalues);
+int sat_multi_reorder_hits(sat_multi *m, double max_pvalue, double min_base_pvalue, int kinds, int max_rows, int32_t *counts,
+                           int capacity, sat_reorder_hit *rows, int32_t *ssemaps);
+int sat_multi_search_reordered(sat_multi *m, int maxstart, double censor, double *wall_ms);
+
+/*
  * Time `repeats` back-to-back searches with HIP events on the launch stream
  * (inputs resident, no copies inside the window).  Returns total milliseconds
  * in *total_ms and the dominant SA kernel's summed device time in *kernel_ms.

@@ -75,6 +75,12 @@ long long sat_debug_query_blob(struct sat_ctx *ctx, void *out, size_t capacity);
  * or destroy it. */
 struct sat_multi;
 struct sat_ctx *sat_debug_multi_ctx(struct sat_multi *m, int shard);
+
+/* Every build, a test hook: declare the kept baseline (sat_baseline_keep) to be of n_queries x n_entries rows, whatever
+ * it holds.  An upload and every query change drop the baseline, so no sequence of public calls leaves one of another
+ * shape than the searched state's; tests reach sat_reorder_hits' refusal of such a baseline with this.  The buffers are
+ * not touched: put the true shape back before the baseline is read.  SAT_ESTATE without a baseline. */
+int sat_debug_baseline_shape(struct sat_ctx *ctx, int n_queries, int n_entries);
 #ifdef __cplusplus
 }
 #endif
