@@ -328,6 +328,9 @@ static void die(const char *fmt, ...)
     exit(1);
 }
 
+#define SAT_STR_(x) #x
+#define SAT_STR(x) SAT_STR_(x)             /* a numeric macro as text, for the messages */
+
 static void *checked(void *p)
 {
     if (!p)
@@ -335,39 +338,81 @@ static void *checked(void *p)
     return p;
 }
 
+/* A header or table line (never a row of a listing: those are assembled, above).  A text that does not fit ends the run */
+__attribute__((format(printf, 1, 2)))
+static void out_fmt(const char *fmt, ...)
+{
+    char line[SAT_MAX_LINE_LEN + 256];
+    va_list ap;
+    va_start(ap, fmt);
+    const int n = vsnprintf(line, sizeof line, fmt, ap);
+    va_end(ap);
+    if (n < 0 || (size_t)n >= sizeof line)
+        die("ERROR: an output line of %d characters does not fit its buffer\n", n);
+    out_bytes(line, (size_t)n);
+}
+
+/* What the user wrote: the letters given and their parsed values.  Only the getopt loop of parse_options writes it */
 typedef struct {
-    int use_gpu, maxstart, want_gpus, bincache, topk, nmatch, refine, ncand, cutoff;
+    uint64_t seen;                    /* the letters given, letter_bit() of each (-k 0 is no -k: it prints the listing) */
+    int maxstart, want_gpus, topk, nmatch, refine, ncand;
     int rowmatch;                     /* -M: matches of each printed row */
-    int fit;                          /* -F: statistics fitted to each query's own scores */
-    int polish;                       /* -P: maps polished per candidate */
-    int polish_all;                   /* -P T -A: maps polished per row of every search (then polish is 0) */
+    int tops;                         /* -P: the restarts whose maps are polished */
     double censor;                    /* -F: the right-censored fraction of the rows */
     double pmax;                      /* -p: the largest p-value printed */
-    int cluster;                      /* -L: cluster the database instead of printing rows */
     double lmax;                      /* -L: the largest p-value of an edge */
-    int nlevels;                      /* -H: the cutoffs' count (then cluster is set too: the run is -L's but for its adds and its table) */
+    int nlevels;                      /* -H: the cutoffs' count */
     double levels[SAT_MAX_CLUSTER_LEVELS];  /* -H: the largest p-value of an edge of each level, ascending */
-    int cover;                        /* -D: cluster around representatives (then cluster is set too: the run is -L's but for its adds and its table) */
     double dmax;                      /* -D: the largest p-value of an edge */
-    const char *classfile;            /* -E: score the search against this classification instead of printing rows */
-    int rocn;                         /* -N: the negatives ROC-n counts up to (0: not given) */
-    int profile;                      /* -W: profile each query's SSEs over its hits instead of printing rows */
+    const char *classfile;            /* -E: the classification the search is scored against */
+    int rocn;                         /* -N: the negatives ROC-n counts up to */
     double wmax;                      /* -W: the largest p-value of a hit */
-    int reorder;                      /* -X: only the rows that are hits out of sequence order alone */
-    double bmin;                      /* -X: the smallest ordered p-value of such a row */
-    int kinds;                        /* -x: SAT_KIND_* bits of the maps printed (0: not given) */
-    int core_given;                   /* -f was given */
+    double bmin;                      /* -X: the smallest ordered p-value of a row */
+    int kinds;                        /* -x: SAT_KIND_* bits of the maps printed */
     double core;                      /* -f: the fraction of the hits every pair of the core is matched together in */
     unsigned long long seed;
-    const char *qfile;                /* -q, -Q, -a: the database; stdin lists the query SIDs (not with -a) */
-    const char *from_db;              /* -Q, -a: the database again - the batches are set from entry indices on the GPUs */
-    const char *all;                  /* -a: the database again - every entry is a query */
+    const char *qfile, *from_db, *all;  /* -q, -Q, -a: the database */
     int dev_list[64], ndev_list;
-    /* what the run prints, derived once the options are checked */
-    int ranked;                       /* -k / -p / -R: each query's ranked rows; else the listing in class order */
+} given;
+
+static uint64_t letter_bit(int c)
+{
+    return c >= 'a' && c <= 'z' ? (uint64_t)1 << (c - 'a') : c >= 'A' && c <= 'Z' ? (uint64_t)1 << (26 + c - 'A') : 0;
+}
+
+static int has(const given *g, int letter)
+{
+    return (g->seen & letter_bit(letter)) != 0;
+}
+
+/* What the run does: all of it derived from what was given, in plan_run, once every rule has passed */
+typedef enum { FROM_STDIN, FROM_SIDS, FROM_DB_SIDS, FROM_DB_ALL } query_source;
+typedef enum { OUT_LISTING, OUT_RANKED, OUT_NONE } row_output;
+typedef enum { NO_CONSUMER, CLUSTER, CLUSTER_LEVELS, COVER, EVAL, PROFILE } row_consumer;
+typedef enum { NO_POLISH, POLISH_CANDIDATES, POLISH_ALL } polish_mode;
+typedef struct {
+    const given *g;                   /* the values as given */
+    query_source source;              /* inline structures on stdin; -q: SIDs, built on the host; -Q: SIDs, built on the GPUs
+                                       * from the resident database; -a: every entry, built there */
+    const char *dbfile;               /* -q, -Q, -a: the database; NULL: stdin names it */
+    row_output out;                   /* what leaves the GPUs: the listing in class order; -k / -p / -R: each query's ranked
+                                       * rows; nothing: a consumer reads the rows where they are */
+    row_consumer consumer;            /* -L, -H, -D, -E, -W: which */
+    polish_mode polish;               /* -P T: the maps of each candidate's T best restarts; with -A: of every row's */
+    int tops;                         /* T */
+    int ncand;                        /* -R, -P: candidates per query, C of -C, else K */
     int csr;                          /* -p, and -k with -F: a row count per query (pcounts) instead of K rows each */
     int nm;                           /* slots per entry: M of -m, else 1 */
+    int kinds;                        /* -X: SAT_KIND_* bits of the maps printed, -x's, else c and n */
+    double core;                      /* -W: -f's fraction, else 0.5 */
+    int rocn;                         /* -E: -N's count, else 50 */
 } options;
+
+/* -Q, -a: the batches are set from entry indices on the GPUs */
+static int queries_from_db(const options *o)
+{
+    return o->source == FROM_DB_SIDS || o->source == FROM_DB_ALL;
+}
 
 typedef struct {
     char dbfile[SAT_MAX_LINE_LEN];
@@ -469,45 +514,60 @@ static void begin_query_stats(const sat_fit *f)
     memset(fit_cur->text, 0, sizeof fit_cur->text);
 }
 
+/* A motif query's "# QUERY SSES" line: the list as numbers, 1-based, ranges expanded, in the order given */
+static void out_query_sses(const input *in, int qi)
+{
+    if (!in->motifs || in->qsub[qi] < 0)
+        return;
+    out_bytes("# QUERY SSES = ", 15);
+    for (int32_t k = in->sse_begin[qi]; k < in->sse_begin[qi + 1]; k++)
+        out_fmt(k > in->sse_begin[qi] ? ",%d" : "%d", in->sse[k] + 1);
+    out_bytes("\n", 1);
+}
+
+/* A query's "# GUMBEL" line; which: "", or "ordered " for the fit of -X's ordered search */
+static void out_gumbel(const sat_fit *f, const char *which)
+{
+    if (f->fitted)
+        out_fmt("# GUMBEL %sa = %.17g b = %.17g rows = %d censored = %d below = %d\n", which, f->a, f->b, f->rows, f->censored,
+                f->below);
+    else
+        out_fmt("# GUMBEL %snot fitted\n", which);
+}
+
+/* A table's "# GUMBEL" line: how many of its n queries were fitted; nothing without -F */
+static void out_fitted(const options *o, const sat_fit *fits, int n)
+{
+    int fitted = 0;
+    if (!fits)
+        return;
+    for (int v = 0; v < n; v++)
+        fitted += fits[v].fitted != 0;
+    out_fmt("# GUMBEL censor = %g fitted = %d of %d\n", o->g->censor, fitted, n);
+}
+
 /* The three '#' lines that open a block of query qi; with -F (f: the query's fit) a fourth, and the statistics of the
  * rows that follow are f's */
 static void print_header(const input *in, int qi, const sat_fit *f)
 {
-    char line[SAT_MAX_LINE_LEN + 64];
-    int n = snprintf(line, sizeof line, "# cudaSaTabsearch LTYPE = %c LORDER = %c LSOLN = %c\n",
-                     in->ltype ? 'T' : 'F', in->lorder ? 'T' : 'F', in->lsoln ? 'T' : 'F');
-    out_bytes(line, (size_t)n);
-    n = snprintf(line, sizeof line, "# QUERY ID = %-8s\n", sat_set_name(in->qsrc, in->qindex[qi]));
-    out_bytes(line, (size_t)n);
-    n = snprintf(line, sizeof line, "# DBFILE = %-80s\n", in->dbfile);
-    out_bytes(line, (size_t)n);
-    if (in->motifs && in->qsub[qi] >= 0) {
-        /* the list as numbers, 1-based, ranges expanded, in the order given */
-        out_bytes("# QUERY SSES = ", 15);
-        for (int32_t k = in->sse_begin[qi]; k < in->sse_begin[qi + 1]; k++) {
-            n = snprintf(line, sizeof line, k > in->sse_begin[qi] ? ",%d" : "%d", in->sse[k] + 1);
-            out_bytes(line, (size_t)n);
-        }
-        out_bytes("\n", 1);
-    }
+    out_fmt("# cudaSaTabsearch LTYPE = %c LORDER = %c LSOLN = %c\n", in->ltype ? 'T' : 'F', in->lorder ? 'T' : 'F',
+            in->lsoln ? 'T' : 'F');
+    out_fmt("# QUERY ID = %-8s\n", sat_set_name(in->qsrc, in->qindex[qi]));
+    out_fmt("# DBFILE = %-80s\n", in->dbfile);
+    out_query_sses(in, qi);
     out_bytes(polish_header, strlen(polish_header));
     begin_query_stats(f);
     if (!f)
         return;
-    if (f->fitted) {
-        n = snprintf(line, sizeof line, "# GUMBEL a = %.17g b = %.17g rows = %d censored = %d below = %d\n", f->a, f->b,
-                     f->rows, f->censored, f->below);
-    } else {
-        n = snprintf(line, sizeof line, "# GUMBEL not fitted\n");
+    if (!f->fitted)
         fprintf(stderr, "WARNING: no Gumbel fit for query %s: its rows keep the built-in statistics\n",
                 sat_set_name(in->qsrc, in->qindex[qi]));
-    }
-    out_bytes(line, (size_t)n);
+    out_gumbel(f, "");
 }
 
-/* -H's list into o->levels / o->nlevels; 0: not 1 .. SAT_MAX_CLUSTER_LEVELS numbers in [0, 1], strictly ascending, the
+/* -H's list into g->levels / g->nlevels; 0: not 1 .. SAT_MAX_CLUSTER_LEVELS numbers in [0, 1], strictly ascending, the
  * whole argument */
-static int parse_levels(const char *arg, options *o)
+static int parse_levels(const char *arg, given *o)
 {
     o->nlevels = 0;
     for (const char *at = arg;; ) {
@@ -548,319 +608,229 @@ static const char *kinds_text(int kinds, char text[4])
     return text;
 }
 
-/* The options, then the refusals in a fixed order (the tests pin it), all before the banner and any device call */
-static void parse_options(int argc, char *argv[], options *o)
+/* "ERROR: -L needs WHAT (got 'ARG')", then the usage; without `what` the usage alone */
+__attribute__((noreturn))
+static void bad_arg(const char *prog, int letter, const char *what)
 {
-    *o = (options){ .use_gpu = 1, .maxstart = 128, .want_gpus = 1, .seed = SAT_DEFAULT_SEED };
-    int c;
-    while ((c = getopt(argc, argv, "cq:Q:a:r:g:G:s:bk:p:m:M:R:C:F:P:AL:H:E:N:D:W:f:X:x:")) != -1) {
-        char *end = NULL;
-        long v;
-        switch (c) {
-        case 'c': o->use_gpu = 0; break;
-        case 'q': o->qfile = optarg; break;
-        case 'Q': o->from_db = optarg; break;
-        case 'a': o->all = optarg; break;
-        case 'r': o->maxstart = atoi(optarg); break;
-        case 'g': o->want_gpus = atoi(optarg); break;
-        case 'G':
-            for (char *tok = strtok(optarg, ","); tok && o->ndev_list < 64; tok = strtok(NULL, ","))
-                o->dev_list[o->ndev_list++] = atoi(tok);
-            break;
-        case 's': o->seed = strtoull(optarg, NULL, 0); break;
-        case 'b': o->bincache = 1; break;
-        case 'A': o->polish_all = 1; break;
-        case 'k': o->topk = atoi(optarg); break;
-        case 'p':
-            /* the whole argument, a finite number >= 0 */
-            o->pmax = strtod(optarg, &end);
-            if (end == optarg || *end != '\0' || !isfinite(o->pmax) || o->pmax < 0.0) {
-                fprintf(stderr, "ERROR: -p needs a p-value >= 0 (got '%s')\n", optarg);
-                usage(argv[0]);
-            }
-            o->cutoff = 1;
-            break;
-        case 'L':
-            /* the whole argument, a finite number in [0, 1] */
-            o->lmax = strtod(optarg, &end);
-            if (end == optarg || *end != '\0' || !isfinite(o->lmax) || o->lmax < 0.0 || o->lmax > 1.0) {
-                fprintf(stderr, "ERROR: -L needs a p-value in [0, 1] (got '%s')\n", optarg);
-                usage(argv[0]);
-            }
-            o->cluster = 1;
-            break;
-        case 'D':
-            /* the whole argument, a finite number in [0, 1] */
-            o->dmax = strtod(optarg, &end);
-            if (end == optarg || *end != '\0' || !isfinite(o->dmax) || o->dmax < 0.0 || o->dmax > 1.0) {
-                fprintf(stderr, "ERROR: -D needs a p-value in [0, 1] (got '%s')\n", optarg);
-                usage(argv[0]);
-            }
-            o->cover = 1;
-            break;
-        case 'W':
-            /* the whole argument, a finite number in [0, 1] */
-            o->wmax = strtod(optarg, &end);
-            if (end == optarg || *end != '\0' || !isfinite(o->wmax) || o->wmax < 0.0 || o->wmax > 1.0) {
-                fprintf(stderr, "ERROR: -W needs a p-value in [0, 1] (got '%s')\n", optarg);
-                usage(argv[0]);
-            }
-            o->profile = 1;
-            break;
-        case 'X':
-            /* the whole argument, a finite number in [0, 1] */
-            o->bmin = strtod(optarg, &end);
-            if (end == optarg || *end != '\0' || !isfinite(o->bmin) || o->bmin < 0.0 || o->bmin > 1.0) {
-                fprintf(stderr, "ERROR: -X needs a p-value in [0, 1] (got '%s')\n", optarg);
-                usage(argv[0]);
-            }
-            o->reorder = 1;
-            break;
-        case 'x':
-            /* the whole argument, one or more of the letters s, c, n */
-            o->kinds = parse_kinds(optarg);
-            if (!o->kinds) {
-                fprintf(stderr, "ERROR: -x needs letters of s, c, n (got '%s')\n", optarg);
-                usage(argv[0]);
-            }
-            break;
-        case 'f':
-            /* the whole argument, a number in (0, 1] */
-            o->core = strtod(optarg, &end);
-            if (end == optarg || *end != '\0' || !(o->core > 0.0 && o->core <= 1.0)) {
-                fprintf(stderr, "ERROR: -f needs a fraction in (0, 1] (got '%s')\n", optarg);
-                usage(argv[0]);
-            }
-            o->core_given = 1;
-            break;
-        case 'H':
-            /* the whole argument: 1 .. SAT_MAX_CLUSTER_LEVELS numbers, each as -L's, with commas between, strictly ascending */
-            if (!parse_levels(optarg, o)) {
-                fprintf(stderr, "ERROR: -H needs 1..%d ascending p-values in [0, 1] (got '%s')\n", SAT_MAX_CLUSTER_LEVELS, optarg);
-                usage(argv[0]);
-            }
-            break;
-        case 'F':
-            /* the whole argument, a number in [0, 0.5] */
-            o->censor = strtod(optarg, &end);
-            if (end == optarg || *end != '\0' || !(o->censor >= 0.0 && o->censor <= 0.5)) {
-                fprintf(stderr, "ERROR: -F needs a censored fraction in [0, 0.5] (got '%s')\n", optarg);
-                usage(argv[0]);
-            }
-            o->fit = 1;
-            break;
-        case 'm':
-            /* 1 .. SAT_MAX_MATCHES, digits only: anything else (0, a sign, text) is a usage error */
-            v = strtol(optarg, &end, 10);
-            if (end == optarg || *end != '\0' || v < 1 || v > SAT_MAX_MATCHES) usage(argv[0]);
-            o->nmatch = (int)v;
-            break;
-        case 'M':
-            /* 1 .. SAT_MAX_MATCHES, digits only */
-            v = strtol(optarg, &end, 10);
-            if (end == optarg || *end != '\0' || v < 1 || v > SAT_MAX_MATCHES) {
-                fprintf(stderr, "ERROR: -M needs an integer 1..%d (got '%s')\n", SAT_MAX_MATCHES, optarg);
-                usage(argv[0]);
-            }
-            o->rowmatch = (int)v;
-            break;
-        case 'P':
-            /* 1 .. SAT_MAX_MATCHES, digits only */
-            v = strtol(optarg, &end, 10);
-            if (end == optarg || *end != '\0' || v < 1 || v > SAT_MAX_MATCHES) {
-                fprintf(stderr, "ERROR: -P needs an integer 1..%d (got '%s')\n", SAT_MAX_MATCHES, optarg);
-                usage(argv[0]);
-            }
-            o->polish = (int)v;
-            break;
-        case 'E': o->classfile = optarg; break;
-        case 'N':
-            /* positive, digits only */
-            v = strtol(optarg, &end, 10);
-            if (end == optarg || *end != '\0' || v < 1 || v > 0x7FFFFFFFL) {
-                fprintf(stderr, "ERROR: -N needs an integer >= 1 (got '%s')\n", optarg);
-                usage(argv[0]);
-            }
-            o->rocn = (int)v;
-            break;
-        case 'R':
-        case 'C':
-            /* positive, digits only */
-            v = strtol(optarg, &end, 10);
-            if (end == optarg || *end != '\0' || v < 1 || v > 0x7FFFFFFFL) {
-                fprintf(stderr, "ERROR: -%c needs a positive integer (got '%s')\n", c, optarg);
-                usage(argv[0]);
-            }
-            if (c == 'R') o->refine = (int)v;
-            else o->ncand = (int)v;
-            break;
-        default: usage(argv[0]);
-        }
-    }
-    if (o->kinds && !o->reorder) die("ERROR: -x needs -X B\n");
-    if (o->reorder) {
+    if (what)
+        fprintf(stderr, "ERROR: -%c needs %s (got '%s')\n", letter, what, optarg);
+    usage(prog);
+    exit(1);
+}
+
+/* optarg as a real number: the whole argument, finite, >= lo (open: > lo) and <= hi */
+static double real_arg(const char *prog, int letter, const char *what, double lo, int open, double hi)
+{
+    char *end = NULL;
+    const double v = strtod(optarg, &end);
+    if (end == optarg || *end != '\0' || !isfinite(v) || (open ? !(v > lo) : v < lo) || v > hi)
+        bad_arg(prog, letter, what);
+    return v;
+}
+
+/* optarg as an integer 1 .. max: the whole argument, digits only (0, a sign, text are refused) */
+static int int_arg(const char *prog, int letter, const char *what, long max)
+{
+    char *end = NULL;
+    const long v = strtol(optarg, &end, 10);
+    if (end == optarg || *end != '\0' || v < 1 || v > max)
+        bad_arg(prog, letter, what);
+    return (int)v;
+}
+
+/* "-OWNER cannot be combined with -x" for the first letter of `letters` that was given beside -OWNER */
+static void forbid(const given *g, int owner, const char *letters)
+{
+    for (const char *c = letters; has(g, owner) && *c; c++)
+        if (has(g, *c))
+            die("ERROR: -%c cannot be combined with -%c\n", owner, *c);
+}
+
+/* -R, -P: the candidates per query */
+static int candidates(const given *g)
+{
+    return has(g, 'C') ? g->ncand : g->topk;
+}
+
+/* The refusals, in a fixed order (tests/golden/cli_rules pins which one a command line gets that breaks several).  A mode
+ * is a forbid() line of its own, its "needs" lines and the entry points it calls; nothing here changes what was given,
+ * so where a block stands decides only which of several refusals is reported */
+static void check_rules(const given *g)
+{
+    const int gpu = !has(g, 'c'), fit = has(g, 'F');
+    const int each = has(g, 'P') && !has(g, 'A');            /* -P T without -A: polish per candidate, -k's rows */
+    const int ranked = g->topk > 0 || has(g, 'p');           /* (-R needs -k) */
+    if (has(g, 'x') && !has(g, 'X')) die("ERROR: -x needs -X B\n");
+    if (has(g, 'X')) {
         /* hits out of sequence order: -p's run, searched twice, with another selection */
-        if (!o->use_gpu) die("ERROR: -X cannot be combined with -c\n");
-        if (o->nmatch) die("ERROR: -X cannot be combined with -m\n");
-        if (o->rowmatch) die("ERROR: -X cannot be combined with -M\n");
-        if (o->refine) die("ERROR: -X cannot be combined with -R\n");
-        if (o->ncand) die("ERROR: -X cannot be combined with -C\n");
-        if (o->cluster) die("ERROR: -X cannot be combined with -L\n");
-        if (o->nlevels) die("ERROR: -X cannot be combined with -H\n");
-        if (o->cover) die("ERROR: -X cannot be combined with -D\n");
-        if (o->classfile) die("ERROR: -X cannot be combined with -E\n");
-        if (o->rocn) die("ERROR: -X cannot be combined with -N\n");
-        if (o->profile) die("ERROR: -X cannot be combined with -W\n");
-        if (!o->cutoff) die("ERROR: -X needs -p P\n");
-        if (o->polish && !o->polish_all) die("ERROR: -X takes -P T only with -A\n");
+        forbid(g, 'X', "cmMRCLHDENW");
+        if (!has(g, 'p')) die("ERROR: -X needs -p P\n");
+        if (each) die("ERROR: -X takes -P T only with -A\n");
         if (!sat_multi_search_only || !sat_multi_search_fit || !sat_multi_baseline_keep || !sat_multi_reorder_hits)
             die("ERROR: this library has no sat_multi_reorder_hits\n");
-        if (!o->kinds) o->kinds = SAT_KIND_CIRCULAR | SAT_KIND_PERMUTED;
     }
-    if (o->core_given && !o->profile) die("ERROR: -f needs -W P\n");
-    if (o->profile) {
+    if (has(g, 'f') && !has(g, 'W')) die("ERROR: -f needs -W P\n");
+    if (has(g, 'W')) {
         /* profile: a run whose rows and maps stay on the GPUs; -q, -Q, -a and the stdin queries all feed it */
-        if (!o->use_gpu) die("ERROR: -W cannot be combined with -c\n");
-        if (o->topk) die("ERROR: -W cannot be combined with -k\n");
-        if (o->cutoff) die("ERROR: -W cannot be combined with -p\n");
-        if (o->nmatch) die("ERROR: -W cannot be combined with -m\n");
-        if (o->rowmatch) die("ERROR: -W cannot be combined with -M\n");
-        if (o->refine) die("ERROR: -W cannot be combined with -R\n");
-        if (o->ncand) die("ERROR: -W cannot be combined with -C\n");
-        if (o->nlevels) die("ERROR: -W cannot be combined with -H\n");
-        if (o->cover) die("ERROR: -W cannot be combined with -D\n");
-        if (o->cluster) die("ERROR: -W cannot be combined with -L\n");
-        if (o->classfile) die("ERROR: -W cannot be combined with -E\n");
-        if (o->rocn) die("ERROR: -W cannot be combined with -N\n");
-        if (o->polish && !o->polish_all) die("ERROR: -W takes -P T only with -A\n");
+        forbid(g, 'W', "ckpmMRCHDLEN");
+        if (each) die("ERROR: -W takes -P T only with -A\n");
         if (!sat_multi_search_only || !sat_multi_profile_rows || !sat_profile_core)
             die("ERROR: this library has no sat_multi_profile_rows\n");
-        if (o->fit && !sat_multi_search_fit) die("ERROR: this library has no sat_multi_search_fit\n");
-        if (!o->core_given) o->core = 0.5;
+        if (fit && !sat_multi_search_fit) die("ERROR: this library has no sat_multi_search_fit\n");
     }
-    if (o->rocn && !o->classfile) die("ERROR: -N needs -E classfile\n");
-    if (o->cover) {
+    if (has(g, 'N') && !has(g, 'E')) die("ERROR: -N needs -E classfile\n");
+    if (has(g, 'D')) {
         /* clustering around representatives: -L's run with another accumulator and another table */
-        if (!o->use_gpu) die("ERROR: -D cannot be combined with -c\n");
-        if (!o->all) die("ERROR: -D needs -a dbfile\n");
-        if (o->topk) die("ERROR: -D cannot be combined with -k\n");
-        if (o->cutoff) die("ERROR: -D cannot be combined with -p\n");
-        if (o->nmatch) die("ERROR: -D cannot be combined with -m\n");
-        if (o->rowmatch) die("ERROR: -D cannot be combined with -M\n");
-        if (o->refine) die("ERROR: -D cannot be combined with -R\n");
-        if (o->ncand) die("ERROR: -D cannot be combined with -C\n");
-        if (o->cluster) die("ERROR: -D cannot be combined with -L\n");
-        if (o->nlevels) die("ERROR: -D cannot be combined with -H\n");
-        if (o->classfile) die("ERROR: -D cannot be combined with -E\n");
+        forbid(g, 'D', "c");
+        if (!has(g, 'a')) die("ERROR: -D needs -a dbfile\n");
+        forbid(g, 'D', "kpmMRCLHE");
         if (!sat_multi_search_only || !sat_multi_cover_begin || !sat_multi_cover_add || !sat_multi_cover_solve || !sat_cover_sizes)
             die("ERROR: this library has no sat_multi_cover_add\n");
-        if (o->fit && !sat_multi_search_fit) die("ERROR: this library has no sat_multi_search_fit\n");
-        o->cluster = 1;                              /* (-L's own checks below ask nothing these have not) */
+        if (fit && !sat_multi_search_fit) die("ERROR: this library has no sat_multi_search_fit\n");
     }
-    if (o->classfile) {
+    if (has(g, 'E')) {
         /* evaluation: a run over queries of the database whose rows stay on the GPUs */
-        if (!o->use_gpu) die("ERROR: -E cannot be combined with -c\n");
-        if (!o->all && !o->from_db) die("ERROR: -E needs -a dbfile or -Q dbfile\n");
-        if (o->topk) die("ERROR: -E cannot be combined with -k\n");
-        if (o->cutoff) die("ERROR: -E cannot be combined with -p\n");
-        if (o->nmatch) die("ERROR: -E cannot be combined with -m\n");
-        if (o->rowmatch) die("ERROR: -E cannot be combined with -M\n");
-        if (o->refine) die("ERROR: -E cannot be combined with -R\n");
-        if (o->ncand) die("ERROR: -E cannot be combined with -C\n");
-        if (o->fit) die("ERROR: -E cannot be combined with -F\n");
-        if (o->cluster) die("ERROR: -E cannot be combined with -L\n");
-        if (o->nlevels) die("ERROR: -E cannot be combined with -H\n");
-        if (o->polish && !o->polish_all) die("ERROR: -E takes -P T only with -A\n");
+        forbid(g, 'E', "c");
+        if (!has(g, 'a') && !has(g, 'Q')) die("ERROR: -E needs -a dbfile or -Q dbfile\n");
+        forbid(g, 'E', "kpmMRCFLH");
+        if (each) die("ERROR: -E takes -P T only with -A\n");
         if (!sat_multi_search_only || !sat_multi_eval_classes || !sat_multi_eval_rows)
             die("ERROR: this library has no sat_multi_eval_rows\n");
-        if (!o->rocn) o->rocn = 50;
     }
-    if (o->nlevels) {
+    if (has(g, 'H')) {
         /* clustering at several cutoffs: -L's run with another add call and another table */
-        if (!o->use_gpu) die("ERROR: -H cannot be combined with -c\n");
-        if (!o->all) die("ERROR: -H needs -a dbfile\n");
-        if (o->cluster) die("ERROR: -H cannot be combined with -L\n");
-        if (o->topk) die("ERROR: -H cannot be combined with -k\n");
-        if (o->cutoff) die("ERROR: -H cannot be combined with -p\n");
-        if (o->nmatch) die("ERROR: -H cannot be combined with -m\n");
-        if (o->rowmatch) die("ERROR: -H cannot be combined with -M\n");
-        if (o->refine) die("ERROR: -H cannot be combined with -R\n");
-        if (o->ncand) die("ERROR: -H cannot be combined with -C\n");
+        forbid(g, 'H', "c");
+        if (!has(g, 'a')) die("ERROR: -H needs -a dbfile\n");
+        forbid(g, 'H', "LkpmMRC");
         if (!sat_multi_search_only || !sat_multi_cluster_begin_levels || !sat_multi_cluster_add_levels ||
             !sat_multi_cluster_labels_levels || !sat_cluster_reps || !sat_cluster_nested)
             die("ERROR: this library has no sat_multi_cluster_add_levels\n");
-        if (o->fit && !sat_multi_search_fit) die("ERROR: this library has no sat_multi_search_fit\n");
-        o->cluster = 1;
-    } else if (o->cluster) {
+        if (fit && !sat_multi_search_fit) die("ERROR: this library has no sat_multi_search_fit\n");
+    } else if (has(g, 'L')) {
         /* clustering: an all-vs-all run whose rows stay on the GPUs */
-        if (!o->use_gpu) die("ERROR: -L cannot be combined with -c\n");
-        if (!o->all) die("ERROR: -L needs -a dbfile\n");
-        if (o->topk) die("ERROR: -L cannot be combined with -k\n");
-        if (o->cutoff) die("ERROR: -L cannot be combined with -p\n");
-        if (o->nmatch) die("ERROR: -L cannot be combined with -m\n");
-        if (o->rowmatch) die("ERROR: -L cannot be combined with -M\n");
-        if (o->refine) die("ERROR: -L cannot be combined with -R\n");
-        if (o->ncand) die("ERROR: -L cannot be combined with -C\n");
+        forbid(g, 'L', "c");
+        if (!has(g, 'a')) die("ERROR: -L needs -a dbfile\n");
+        forbid(g, 'L', "kpmMRC");
         if (!sat_multi_search_only || !sat_multi_cluster_begin || !sat_multi_cluster_add || !sat_multi_cluster_labels ||
             !sat_cluster_reps)
             die("ERROR: this library has no sat_multi_cluster_add\n");
-        if (o->fit && !sat_multi_search_fit) die("ERROR: this library has no sat_multi_search_fit\n");
+        if (fit && !sat_multi_search_fit) die("ERROR: this library has no sat_multi_search_fit\n");
     }
-    if (o->from_db || o->all) {
-        /* queries from the resident database: from here on the run is a -q run over that file */
-        if (o->from_db && !o->use_gpu) die("ERROR: -Q cannot be combined with -c\n");
-        if (o->all && !o->use_gpu) die("ERROR: -a cannot be combined with -c\n");
-        if (o->from_db && o->qfile) die("ERROR: -Q cannot be combined with -q\n");
-        if (o->all && o->qfile) die("ERROR: -a cannot be combined with -q\n");
-        if (o->all && o->from_db) die("ERROR: -a cannot be combined with -Q\n");
-        if (!sat_multi_queries_from_db) die("ERROR: this library has no sat_multi_queries_from_db\n");
-        o->qfile = o->from_db = o->all ? o->all : o->from_db;
-    }
-    if (o->polish_all) {
-        /* all rows: the mode of the library; from here on the run is an ordinary one on polished rows */
-        if (!o->polish) die("ERROR: -A needs -P T\n");
-        if (!o->use_gpu) die("ERROR: -A cannot be combined with -c\n");
-        if (o->nmatch) die("ERROR: -A cannot be combined with -m\n");
-        if (o->rowmatch) die("ERROR: -A cannot be combined with -M\n");
-        if (o->refine) die("ERROR: -A cannot be combined with -R\n");
-        if (o->ncand) die("ERROR: -A cannot be combined with -C\n");
+    /* queries from the resident database */
+    forbid(g, 'Q', "c");
+    forbid(g, 'a', "c");
+    forbid(g, 'Q', "q");
+    forbid(g, 'a', "qQ");
+    if ((has(g, 'Q') || has(g, 'a')) && !sat_multi_queries_from_db) die("ERROR: this library has no sat_multi_queries_from_db\n");
+    if (has(g, 'A')) {
+        /* all rows: the mode of the library; the run is an ordinary one on polished rows */
+        if (!has(g, 'P')) die("ERROR: -A needs -P T\n");
+        forbid(g, 'A', "cmMRC");
         if (!sat_multi_polish_all_set) die("ERROR: this library has no sat_multi_polish_all_set\n");
-        o->polish_all = o->polish;
-        o->polish = 0;
     }
-    if (o->polish && !o->use_gpu) die("ERROR: -P needs the GPU path\n");
-    if (o->polish && o->nmatch) die("ERROR: -P cannot be combined with -m\n");
-    if (o->polish && o->rowmatch) die("ERROR: -P cannot be combined with -M\n");
-    if (o->polish && o->cutoff) die("ERROR: -P cannot be combined with -p\n");
-    if (o->polish && o->fit) die("ERROR: -P cannot be combined with -F\n");
-    if (o->polish && o->topk <= 0) die("ERROR: -P needs -k K\n");
-    if (o->polish && !sat_multi_search_refine_polish) die("ERROR: this library has no sat_multi_search_refine_polish\n");
-    if (o->cutoff && !o->use_gpu) die("ERROR: -p needs the GPU path\n");
-    if (o->cutoff && o->nmatch) die("ERROR: -p cannot be combined with -m\n");
-    if (o->cutoff && o->refine) die("ERROR: -p cannot be combined with -R\n");
-    if (o->cutoff && (!sat_multi_search_cutoff || !sat_multi_hits_cutoff))
-        die("ERROR: this library has no sat_multi_search_cutoff\n");
-    if (o->refine && !o->use_gpu) die("ERROR: -R needs the GPU path\n");
-    if (o->refine && o->nmatch) die("ERROR: -R cannot be combined with -m\n");
-    if (o->refine && o->topk <= 0) die("ERROR: -R needs -k K\n");
-    if (o->ncand && !o->refine && !o->polish) die("ERROR: -C needs -R\n");
-    if ((o->refine || o->polish) && !o->ncand) o->ncand = o->topk;
-    if ((o->refine || o->polish) && o->topk > o->ncand) die("ERROR: -k K (%d) exceeds -C C (%d)\n", o->topk, o->ncand);
-    if (o->refine && !sat_multi_search_refine) die("ERROR: this library has no sat_multi_search_refine\n");
-    if (o->nmatch && !o->use_gpu) die("ERROR: -m needs the GPU path\n");
-    if (o->nmatch && !sat_multi_search_matches) die("ERROR: this library has no sat_multi_search_matches\n");
-    o->ranked = o->topk > 0 || o->cutoff;                /* (-R needs -k) */
-    if (o->rowmatch && !o->use_gpu) die("ERROR: -M needs the GPU path\n");
-    if (o->rowmatch && o->nmatch) die("ERROR: -M cannot be combined with -m\n");
-    if (o->rowmatch && !o->ranked) die("ERROR: -M needs -k K, -p P or -R restarts -k K\n");
-    if (o->rowmatch && !sat_multi_search_pairs_matches)
-        die("ERROR: this library has no sat_multi_search_pairs_matches\n");
-    if (o->fit && o->refine) die("ERROR: -F cannot be combined with -R\n");
-    if (o->fit && o->nmatch) die("ERROR: -F cannot be combined with -m\n");
-    if (o->fit && o->ranked && (!sat_multi_search_fit || !sat_multi_hits_cutoff))
-        die("ERROR: this library has no sat_multi_search_fit\n");
-    o->csr = o->cutoff || (o->fit && o->topk > 0);
-    o->nm = o->nmatch > 0 ? o->nmatch : 1;
+    if (each) {
+        if (!gpu) die("ERROR: -P needs the GPU path\n");
+        forbid(g, 'P', "mMpF");
+        if (g->topk <= 0) die("ERROR: -P needs -k K\n");
+        if (!sat_multi_search_refine_polish) die("ERROR: this library has no sat_multi_search_refine_polish\n");
+    }
+    if (has(g, 'p')) {
+        if (!gpu) die("ERROR: -p needs the GPU path\n");
+        forbid(g, 'p', "mR");
+        if (!sat_multi_search_cutoff || !sat_multi_hits_cutoff) die("ERROR: this library has no sat_multi_search_cutoff\n");
+    }
+    if (has(g, 'R')) {
+        if (!gpu) die("ERROR: -R needs the GPU path\n");
+        forbid(g, 'R', "m");
+        if (g->topk <= 0) die("ERROR: -R needs -k K\n");
+    }
+    if (has(g, 'C') && !has(g, 'R') && !each) die("ERROR: -C needs -R\n");
+    if ((has(g, 'R') || each) && g->topk > candidates(g)) die("ERROR: -k K (%d) exceeds -C C (%d)\n", g->topk, candidates(g));
+    if (has(g, 'R') && !sat_multi_search_refine) die("ERROR: this library has no sat_multi_search_refine\n");
+    if (has(g, 'm')) {
+        if (!gpu) die("ERROR: -m needs the GPU path\n");
+        if (!sat_multi_search_matches) die("ERROR: this library has no sat_multi_search_matches\n");
+    }
+    if (has(g, 'M')) {
+        if (!gpu) die("ERROR: -M needs the GPU path\n");
+        forbid(g, 'M', "m");
+        if (!ranked) die("ERROR: -M needs -k K, -p P or -R restarts -k K\n");
+        if (!sat_multi_search_pairs_matches) die("ERROR: this library has no sat_multi_search_pairs_matches\n");
+    }
+    forbid(g, 'F', "Rm");
+    if (fit && ranked && (!sat_multi_search_fit || !sat_multi_hits_cutoff)) die("ERROR: this library has no sat_multi_search_fit\n");
+}
+
+/* The options into *g - only this loop writes it - and the refusals, all before the banner and any device call */
+static void parse_options(int argc, char *argv[], given *g)
+{
+    const char *prog = argv[0];
+    *g = (given){ .maxstart = 128, .want_gpus = 1, .seed = SAT_DEFAULT_SEED };
+    int c;
+    while ((c = getopt(argc, argv, "cq:Q:a:r:g:G:s:bk:p:m:M:R:C:F:P:AL:H:E:N:D:W:f:X:x:")) != -1) {
+        g->seen |= letter_bit(c);
+        switch (c) {
+        case 'c': case 'b': case 'A': break;
+        case 'q': g->qfile = optarg; break;
+        case 'Q': g->from_db = optarg; break;
+        case 'a': g->all = optarg; break;
+        case 'E': g->classfile = optarg; break;
+        case 'r': g->maxstart = atoi(optarg); break;
+        case 'g': g->want_gpus = atoi(optarg); break;
+        case 'G':
+            for (char *tok = strtok(optarg, ","); tok && g->ndev_list < 64; tok = strtok(NULL, ","))
+                g->dev_list[g->ndev_list++] = atoi(tok);
+            break;
+        case 's': g->seed = strtoull(optarg, NULL, 0); break;
+        case 'k':
+            g->topk = atoi(optarg);
+            if (!g->topk) g->seen &= ~letter_bit('k');
+            break;
+        case 'p': g->pmax = real_arg(prog, c, "a p-value >= 0", 0.0, 0, INFINITY); break;
+        case 'L': g->lmax = real_arg(prog, c, "a p-value in [0, 1]", 0.0, 0, 1.0); break;
+        case 'D': g->dmax = real_arg(prog, c, "a p-value in [0, 1]", 0.0, 0, 1.0); break;
+        case 'W': g->wmax = real_arg(prog, c, "a p-value in [0, 1]", 0.0, 0, 1.0); break;
+        case 'X': g->bmin = real_arg(prog, c, "a p-value in [0, 1]", 0.0, 0, 1.0); break;
+        case 'f': g->core = real_arg(prog, c, "a fraction in (0, 1]", 0.0, 1, 1.0); break;
+        case 'F': g->censor = real_arg(prog, c, "a censored fraction in [0, 0.5]", 0.0, 0, 0.5); break;
+        case 'm': g->nmatch = int_arg(prog, c, NULL, SAT_MAX_MATCHES); break;
+        case 'M': g->rowmatch = int_arg(prog, c, "an integer 1.." SAT_STR(SAT_MAX_MATCHES), SAT_MAX_MATCHES); break;
+        case 'P': g->tops = int_arg(prog, c, "an integer 1.." SAT_STR(SAT_MAX_MATCHES), SAT_MAX_MATCHES); break;
+        case 'N': g->rocn = int_arg(prog, c, "an integer >= 1", 0x7FFFFFFFL); break;
+        case 'R': g->refine = int_arg(prog, c, "a positive integer", 0x7FFFFFFFL); break;
+        case 'C': g->ncand = int_arg(prog, c, "a positive integer", 0x7FFFFFFFL); break;
+        case 'x':
+            /* the whole argument, one or more of the letters s, c, n */
+            g->kinds = parse_kinds(optarg);
+            if (!g->kinds)
+                bad_arg(prog, c, "letters of s, c, n");
+            break;
+        case 'H':
+            /* the whole argument: 1 .. SAT_MAX_CLUSTER_LEVELS numbers, each as -L's, with commas between, strictly ascending */
+            if (!parse_levels(optarg, g))
+                bad_arg(prog, c, "1.." SAT_STR(SAT_MAX_CLUSTER_LEVELS) " ascending p-values in [0, 1]");
+            break;
+        default: usage(prog);
+        }
+    }
+    check_rules(g);
+}
+
+/* What the run does, from what was given */
+static void plan_run(const given *g, options *o)
+{
+    *o = (options){ .g = g, .tops = g->tops, .ncand = candidates(g) };
+    o->source = has(g, 'a') ? FROM_DB_ALL : has(g, 'Q') ? FROM_DB_SIDS : has(g, 'q') ? FROM_SIDS : FROM_STDIN;
+    o->dbfile = has(g, 'a') ? g->all : has(g, 'Q') ? g->from_db : g->qfile;
+    o->consumer = has(g, 'L') ? CLUSTER : has(g, 'H') ? CLUSTER_LEVELS : has(g, 'D') ? COVER : has(g, 'E') ? EVAL
+                  : has(g, 'W') ? PROFILE : NO_CONSUMER;
+    o->out = o->consumer != NO_CONSUMER ? OUT_NONE : g->topk > 0 || has(g, 'p') ? OUT_RANKED : OUT_LISTING;
+    o->polish = !has(g, 'P') ? NO_POLISH : has(g, 'A') ? POLISH_ALL : POLISH_CANDIDATES;
+    o->csr = has(g, 'p') || (has(g, 'F') && g->topk > 0);
+    o->nm = g->nmatch > 0 ? g->nmatch : 1;
+    o->kinds = has(g, 'x') ? g->kinds : SAT_KIND_CIRCULAR | SAT_KIND_PERMUTED;
+    o->core = has(g, 'f') ? g->core : 0.5;
+    o->rocn = has(g, 'N') ? g->rocn : 50;
 }
 
 /* -q, -Q: query SIDs on stdin, one a line (cut to 7 characters), options T T F; -a: the same options and nothing read -
@@ -868,11 +838,11 @@ static void parse_options(int argc, char *argv[], options *o)
  * structures on stdin */
 static void read_queries(const options *o, input *in)
 {
-    if (o->qfile) {
-        strncpy(in->dbfile, o->qfile, sizeof in->dbfile - 1);
+    if (o->dbfile) {
+        strncpy(in->dbfile, o->dbfile, sizeof in->dbfile - 1);
         in->ltype = in->lorder = 1;
         char buf[SAT_MAX_LINE_LEN];
-        while (!o->all && !feof(stdin) && fgets(buf, SAT_MAX_LINE_LEN, stdin)) {
+        while (o->source != FROM_DB_ALL && !feof(stdin) && fgets(buf, SAT_MAX_LINE_LEN, stdin)) {
             in->sids = checked(realloc(in->sids, (size_t)(in->num_queries + 1) * (SAT_LABELSIZE + 1)));
             char *sid = in->sids + (size_t)in->num_queries++ * (SAT_LABELSIZE + 1);
             memset(sid, 0, SAT_LABELSIZE + 1);
@@ -915,6 +885,11 @@ static void read_queries(const options *o, input *in)
     if (!in->ltype) {
         fprintf(stderr, "WARNING: LTYPE is always set to T\n");
         in->ltype = 1;
+    }
+    if (has(o->g, 'X')) {
+        /* -X runs both searches itself, whatever the input says; its rows are the unordered search's, with their maps */
+        in->lorder = 0;
+        in->lsoln = 1;
     }
 }
 
@@ -969,7 +944,7 @@ static void load_database(const options *o, input *in)
     int total = -1;
     char binpath[SAT_MAX_LINE_LEN + 16];
     snprintf(binpath, sizeof(binpath), "%s.satbin", in->dbfile);
-    if (o->bincache) {
+    if (has(o->g, 'b')) {
         struct stat sa, sb;
         if (stat(in->dbfile, &sa) == 0 && stat(binpath, &sb) == 0 && sb.st_mtime >= sa.st_mtime &&
             sat_set_load_binary(binpath, &in->db) == 0) {
@@ -979,7 +954,7 @@ static void load_database(const options *o, input *in)
     }
     if (total < 0) {
         total = sat_read_structures_file(in->dbfile, &in->db, "database");     /* mmap reader, same semantics */
-        if (total >= 0 && o->bincache && sat_set_save_binary(&in->db, binpath) != 0)
+        if (total >= 0 && has(o->g, 'b') && sat_set_save_binary(&in->db, binpath) != 0)
             fprintf(stderr, "WARNING: could not write %s\n", binpath);
     }
     if (total < 0)
@@ -996,13 +971,13 @@ static void load_database(const options *o, input *in)
     if (total == 0)
         die("ERROR: empty database\n");
 
-    in->qsrc = o->qfile ? &in->db : &in->queries;
-    if (o->all)
+    in->qsrc = o->dbfile ? &in->db : &in->queries;
+    if (o->source == FROM_DB_ALL)
         in->num_queries = in->db.count;
     in->qindex = checked(malloc(sizeof(int) * (size_t)(in->num_queries + 1)));
     for (int i = 0; i < in->num_queries; i++) {
         in->qindex[i] = i;
-        if (!o->qfile || o->all)
+        if (o->source != FROM_SIDS && o->source != FROM_DB_SIDS)
             continue;
         const char *sid = in->sids + (size_t)i * (SAT_LABELSIZE + 1);
         int found = -1;
@@ -1054,9 +1029,10 @@ static sat_fit fit_scores(const int32_t *scores, int n, int n1, const int32_t *o
 static int run_host(const options *o, const input *in)
 {
     const size_t total = (size_t)in->db.count;
+    const int fit = has(o->g, 'F');
     slots one = { 1, NULL, checked(malloc(sizeof(int32_t) * total)),
                   in->lsoln ? checked(malloc(sizeof(int32_t) * SAT_MAXDIM * total)) : NULL };
-    int32_t *fit_orders = o->fit ? checked(malloc(sizeof(int32_t) * (total + 1))) : NULL;
+    int32_t *fit_orders = fit ? checked(malloc(sizeof(int32_t) * (total + 1))) : NULL;
     sat_host_stream stream;
     sat_host_stream_seed(&stream, 1234);
     const int passes = in->cls_count[1] > 0 ? 2 : 1;
@@ -1064,23 +1040,23 @@ static int run_host(const options *o, const input *in)
         for (int qi = 0; qi < in->num_queries; qi++) {
             int qs;
             const sat_struct_set *qset = query_set(in, qi, &qs);
-            if (!o->fit)
+            if (!fit)
                 print_header(in, qi, NULL);
             fprintf(stderr, "Executing simulated annealing tableaux match kernel on host for query %s...\n",
                     sat_set_name(qset, qs));
             double t1 = now_ms();
             if (sat_host_search(&in->db, in->cls_index[k], in->cls_count[k], qset, qs, in->lorder, in->lsoln,
-                                o->maxstart, &stream, one.scores, one.maps) != 0)
+                                o->g->maxstart, &stream, one.scores, one.maps) != 0)
                 die("malloc failed in host search\n");
             double ms = now_ms() - t1;
             fprintf(stderr, "host execution time %f ms\n", ms);
             fprintf(stderr, "%f million iterations/sec\n",
-                    ((double)in->cls_count[k] * ((double)o->maxstart * SAT_MAXITER) / (ms / 1000)) / 1.0e6);
-            if (o->fit) {
+                    ((double)in->cls_count[k] * ((double)o->g->maxstart * SAT_MAXITER) / (ms / 1000)) / 1.0e6);
+            if (fit) {
                 /* the block's own rows: the one stream runs class after class, so a block is fitted when it is printed */
                 for (int d = 0; d < in->cls_count[k]; d++)
                     fit_orders[d] = in->db.order[in->cls_index[k][d]];
-                sat_fit f = fit_scores(one.scores, in->cls_count[k], qset->order[qs], fit_orders, o->censor);
+                sat_fit f = fit_scores(one.scores, in->cls_count[k], qset->order[qs], fit_orders, o->g->censor);
                 print_header(in, qi, &f);
             }
             for (int d = 0; d < in->cls_count[k]; d++)
@@ -1122,6 +1098,8 @@ typedef struct {
     int32_t *qnode;                   /* -W: the batch's queries as database entries, -1 for a query that is none */
     uint32_t *phits, *pjoint;         /* -W: every query's hits; the matrices, query qi's at poff[qi] */
     size_t *poff;                     /* -W: num_queries + 1 of them */
+    sat_classes classes;              /* -E: the classification */
+    sat_eval *evals;                  /* -E: every query's row as the GPUs reduced it */
 } gpu_bufs;
 
 static void alloc_slots(slots *s, size_t rows, int nm, int with_counts, int lsoln)
@@ -1146,20 +1124,32 @@ static void alloc_hits(gpu_bufs *B, size_t rows, int lsoln)
 
 static void alloc_gpu_bufs(const options *o, const input *in, gpu_bufs *B)
 {
+    const given *g = o->g;
     const int total = in->db.count, nm = o->nm, lsoln = in->lsoln;
-    const int entry_slots = (!o->ranked && !o->cluster && !o->classfile && !o->profile) || o->nmatch;     /* every entry's slots come to the host */
-    *B = (gpu_bufs){ .batch = 256, .kk = o->topk < total ? o->topk : total, .reorder = o->reorder };
+    const int entry_slots = o->out == OUT_LISTING || g->nmatch;          /* every entry's slots come to the host */
+    *B = (gpu_bufs){ .batch = 256, .kk = g->topk < total ? g->topk : total, .reorder = has(g, 'X') };
+    if (o->consumer == EVAL) {
+        /* the classification, read before any GPU is touched: a bad file ends the run here */
+        char err[SAT_MAX_LINE_LEN + 256];
+        if (sat_read_classes(g->classfile, &in->db, &B->classes, err, sizeof err) != 0)
+            die("ERROR: %s\n", err);
+        if (B->classes.unknown)
+            fprintf(stderr, "WARNING: %d names of %s are not in the database\n", B->classes.unknown, g->classfile);
+        fprintf(stderr, "Read %d classes of %d of %d structures from %s\n", B->classes.distinct, B->classes.classified, total,
+                g->classfile);
+        B->evals = checked(calloc((size_t)in->num_queries + 1, sizeof(sat_eval)));
+    }
     /* Queries go to the GPUs in batches: one set of launches scores a whole batch (grid = entries x queries), which
      * is what fills the machine when the database is small and the query list long (-q).  The batch size is bounded
      * by the host slots of every entry: score and map, with -m also count and restarts (the device holds the same
      * slots, maps as bytes). */
     if (entry_slots) {
-        const size_t per_entry = (size_t)nm * (lsoln ? SAT_MAXDIM + 1 : 1) + (o->nmatch ? 1 + (size_t)nm : 0);
+        const size_t per_entry = (size_t)nm * (lsoln ? SAT_MAXDIM + 1 : 1) + (g->nmatch ? 1 + (size_t)nm : 0);
         const size_t per_query = (size_t)total * per_entry * sizeof(int32_t);
         const size_t budget = (size_t)1 << 30;
         if ((size_t)B->batch * per_query > budget) B->batch = (int)(budget / per_query);
     }
-    if (o->profile) {
+    if (o->consumer == PROFILE) {
         /* the batch's maps stay on the GPUs, a byte per entry and query SSE: at most PROFILE_MAP_BYTES of them, sized by
          * the run's largest query.  The counters are a query's own: nothing depends on the cut.  And every query's
          * result until the table is printed: 4 + 4 n1 n1 bytes */
@@ -1176,28 +1166,28 @@ static void alloc_gpu_bufs(const options *o, const input *in, gpu_bufs *B)
     }
     if (B->batch < 1) B->batch = 1;
     if (B->batch > in->num_queries) B->batch = in->num_queries;
-    if (o->profile)
+    if (o->consumer == PROFILE)
         B->qnode = checked(malloc(sizeof(int32_t) * (size_t)B->batch));
     const size_t rows = (size_t)total * B->batch;
     if (entry_slots)
-        alloc_slots(&B->all, rows, nm, o->nmatch, lsoln);
-    if (o->nmatch)
+        alloc_slots(&B->all, rows, nm, g->nmatch, lsoln);
+    if (g->nmatch)
         B->restarts = checked(malloc(sizeof(int32_t) * rows * nm));
-    if (!o->ranked && !o->cluster && !o->classfile && !o->profile && in->cls_count[1] > 0)
-        alloc_slots(&B->large, (size_t)in->cls_count[1] * in->num_queries, nm, o->nmatch, lsoln);
+    if (o->out == OUT_LISTING && in->cls_count[1] > 0)
+        alloc_slots(&B->large, (size_t)in->cls_count[1] * in->num_queries, nm, g->nmatch, lsoln);
     if (o->csr) {
-        B->hits_cap = o->cutoff ? 1024 : B->kk * B->batch;
+        B->hits_cap = has(g, 'p') ? 1024 : B->kk * B->batch;
         B->pcounts = checked(malloc(sizeof(int32_t) * (size_t)B->batch));
         alloc_hits(B, (size_t)B->hits_cap, lsoln);
-    } else if (o->topk > 0) {
+    } else if (g->topk > 0) {
         alloc_hits(B, (size_t)B->kk * B->batch, lsoln);  /* only K rows per query (and GPU) ever leave the GPUs */
     }
     B->n1s = checked(malloc(sizeof(int32_t) * (size_t)B->batch));
-    if (o->reorder && o->fit)
+    if (has(g, 'X') && has(g, 'F'))
         B->base_fits = checked(calloc((size_t)B->batch, sizeof(sat_fit)));
-    if (o->from_db && in->motifs)
+    if (queries_from_db(o) && in->motifs)
         B->sse_begin = checked(malloc(sizeof(int32_t) * ((size_t)B->batch + 1)));
-    if (o->from_db)
+    if (queries_from_db(o))
         return;
     B->qtabs = checked(calloc((size_t)B->batch * SAT_MAXDIM * SAT_MAXDIM, 1));
     B->qdmats = checked(calloc((size_t)B->batch * SAT_MAXDIM * SAT_MAXDIM, sizeof(float)));
@@ -1250,6 +1240,8 @@ static void free_gpu_bufs(gpu_bufs *B)
     free(B->rowm_restarts);
     free(B->pair_q);
     free(B->pair_e);
+    free(B->evals);
+    sat_classes_free(&B->classes);
 }
 
 /* One multi-GPU context holding the database: it is cut into contiguous shards of equal COST (entries of a
@@ -1257,16 +1249,16 @@ static void free_gpu_bufs(gpu_bufs *B)
  * all of them and one gather (RCCL over xGMI) brings the rows to device 0. */
 static sat_multi *open_multi(const options *o, const input *in)
 {
-    const int total = in->db.count, ndev = sat_device_count();
+    const int total = in->db.count, ndev = sat_device_count(), nlist = o->g->ndev_list;
     if (ndev <= 0)
         die("There is no usable HIP device (use -c for the host mode).\n");
     fprintf(stderr, "found %d HIP devices\n", ndev);
-    int ngpu = o->want_gpus > 0 ? o->want_gpus : ndev;
+    int ngpu = o->g->want_gpus > 0 ? o->g->want_gpus : ndev;
     if (ngpu > ndev) ngpu = ndev;
-    if (o->ndev_list > 0) ngpu = o->ndev_list;
+    if (nlist > 0) ngpu = nlist;
     if (ngpu > total) ngpu = total;
     const double t0 = now_ms();
-    sat_multi *multi = sat_multi_create(ngpu, o->ndev_list > 0 ? o->dev_list : NULL, o->seed);
+    sat_multi *multi = sat_multi_create(ngpu, nlist > 0 ? o->g->dev_list : NULL, o->g->seed);
     if (!multi)
         die("sat_multi_create(%d) failed: %s\n", ngpu, sat_last_error());
     if (sat_multi_db_upload_packed(multi, total, in->db.order, in->db.cell_off, in->db.tab, in->db.dist) != SAT_OK)
@@ -1283,89 +1275,95 @@ static sat_multi *open_multi(const options *o, const input *in)
     return multi;
 }
 
+/* -X, and -p / -k with -F: the rows of the search just made whose p-value is <= pmax, selected on the GPUs into the
+ * buffers as they are.  Returns the rows there are */
+static int select_rows(const options *o, sat_multi *multi, gpu_bufs *B, double pmax)
+{
+    const given *g = o->g;
+    if (has(g, 'X'))
+        return sat_multi_reorder_hits(multi, pmax, g->bmin, o->kinds, g->topk, B->pcounts, B->hits_cap, B->rhits, B->hit_maps);
+    return sat_multi_hits_cutoff(multi, pmax, g->topk, B->pcounts, B->hits_cap, B->hits, B->hit_maps);
+}
+
+/* rc rows were selected: where the buffers were short of them, they are grown and the rows selected again */
+static int grow_and_select(const options *o, const input *in, sat_multi *multi, gpu_bufs *B, double pmax, int rc)
+{
+    if (rc <= B->hits_cap)
+        return rc;
+    B->hits_cap = rc;
+    alloc_hits(B, (size_t)rc, in->lsoln);
+    return select_rows(o, multi, B, pmax);
+}
+
 /* The mode's search of the batch set last.  Returns rows per query (-k, -R), the batch's rows (-p), 0 (listing, -m)
  * or a negative SAT_E* code. */
 static int search_batch(const options *o, const input *in, sat_multi *multi, gpu_bufs *B, sat_fit *fits, double *ms,
                         double *ms_stage2)
 {
-    const int lorder = in->lorder, lsoln = in->lsoln, maxstart = o->maxstart;
-    if (o->cluster || o->classfile || o->profile) {
+    const given *g = o->g;
+    const int lorder = in->lorder, lsoln = in->lsoln, maxstart = g->maxstart, fit = has(g, 'F');
+    if (o->out == OUT_NONE) {
         /* -L, -H, -D, -E: the rows stay on the GPUs (no gather, no LSOLN: no map is printed); with -F the fit is installed
          * there.  -W: the same with LSOLN on, whatever the input says - the maps are what it counts, where they are */
-        if (o->fit)
-            return sat_multi_search_fit(multi, lorder, o->profile, maxstart, o->censor, fits, ms);
-        return sat_multi_search_only(multi, lorder, o->profile, maxstart, ms);
+        const int maps = o->consumer == PROFILE;
+        if (fit)
+            return sat_multi_search_fit(multi, lorder, maps, maxstart, g->censor, fits, ms);
+        return sat_multi_search_only(multi, lorder, maps, maxstart, ms);
     }
-    if (o->reorder) {
+    if (has(g, 'X')) {
         /* -X: the ordered search without maps, fitted (-F) and kept on the GPUs as the baseline; the unordered search with
-         * maps, fitted to its own scores; then of -p's rows those the baseline does not call a hit and whose map is of one
-         * of the kinds.  A short buffer is grown and the rows selected again. */
+         * maps, fitted to its own scores; then of -p's rows those the baseline does not call a hit and whose map is of
+         * one of the kinds */
         double ms2 = 0.0;
-        int rc = o->fit ? sat_multi_search_fit(multi, 1, 0, maxstart, o->censor, B->base_fits, ms)
-                        : sat_multi_search_only(multi, 1, 0, maxstart, ms);
+        int rc = fit ? sat_multi_search_fit(multi, 1, 0, maxstart, g->censor, B->base_fits, ms)
+                     : sat_multi_search_only(multi, 1, 0, maxstart, ms);
         if (rc == SAT_OK)
             rc = sat_multi_baseline_keep(multi);
         if (rc == SAT_OK)
-            rc = o->fit ? sat_multi_search_fit(multi, 0, 1, maxstart, o->censor, fits, &ms2)
-                        : sat_multi_search_only(multi, 0, 1, maxstart, &ms2);
+            rc = fit ? sat_multi_search_fit(multi, 0, 1, maxstart, g->censor, fits, &ms2)
+                     : sat_multi_search_only(multi, 0, 1, maxstart, &ms2);
         *ms += ms2;
         if (rc != SAT_OK)
             return rc;
-        rc = sat_multi_reorder_hits(multi, o->pmax, o->bmin, o->kinds, o->topk, B->pcounts, B->hits_cap, B->rhits, B->hit_maps);
-        if (rc > B->hits_cap) {
-            B->hits_cap = rc;
-            alloc_hits(B, (size_t)rc, 1);
-            rc = sat_multi_reorder_hits(multi, o->pmax, o->bmin, o->kinds, o->topk, B->pcounts, B->hits_cap, B->rhits, B->hit_maps);
-        }
+        rc = grow_and_select(o, in, multi, B, g->pmax, select_rows(o, multi, B, g->pmax));
         for (int r = 0; r < rc; r++)
             B->hits[r] = B->rhits[r].hit;
         return rc;
     }
-    if (o->fit && o->ranked) {
+    if (fit && o->out == OUT_RANKED) {
         /* search, histogram and fit on the GPUs (fits: the batch's), then the rows by the fitted p-values: those under
          * -p's cutoff, or with -k alone (every p-value is <= 1) the K best */
-        int rc = sat_multi_search_fit(multi, lorder, lsoln, maxstart, o->censor, fits, ms);
+        const int rc = sat_multi_search_fit(multi, lorder, lsoln, maxstart, g->censor, fits, ms);
         if (rc != SAT_OK)
             return rc;
-        const double pmax = o->cutoff ? o->pmax : 1.0;
-        rc = sat_multi_hits_cutoff(multi, pmax, o->topk, B->pcounts, B->hits_cap, B->hits, B->hit_maps);
-        if (rc > B->hits_cap) {
-            B->hits_cap = rc;
-            alloc_hits(B, (size_t)rc, lsoln);
-            rc = sat_multi_hits_cutoff(multi, pmax, o->topk, B->pcounts, B->hits_cap, B->hits, B->hit_maps);
-        }
-        return rc;
+        const double pmax = has(g, 'p') ? g->pmax : 1.0;
+        return grow_and_select(o, in, multi, B, pmax, select_rows(o, multi, B, pmax));
     }
-    if (o->cutoff) {
-        /* every row of the batch under the cutoff; a short buffer is grown and the rows selected again */
-        int rc = sat_multi_search_cutoff(multi, lorder, lsoln, maxstart, o->pmax, o->topk, B->pcounts, B->hits_cap,
-                                         B->hits, B->hit_maps, ms);
-        if (rc > B->hits_cap) {
-            B->hits_cap = rc;
-            alloc_hits(B, (size_t)rc, lsoln);
-            rc = sat_multi_hits_cutoff(multi, o->pmax, o->topk, B->pcounts, B->hits_cap, B->hits, B->hit_maps);
-        }
-        return rc;
+    if (has(g, 'p')) {
+        /* every row of the batch under the cutoff, selected with the search */
+        const int rc = sat_multi_search_cutoff(multi, lorder, lsoln, maxstart, g->pmax, g->topk, B->pcounts, B->hits_cap, B->hits,
+                                               B->hit_maps, ms);
+        return grow_and_select(o, in, multi, B, g->pmax, rc);
     }
-    if (o->polish)
-        return sat_multi_search_refine_polish(multi, lorder, lsoln, maxstart, o->ncand, o->refine ? o->refine : maxstart, o->polish,
+    if (o->polish == POLISH_CANDIDATES)
+        return sat_multi_search_refine_polish(multi, lorder, lsoln, maxstart, o->ncand, g->refine ? g->refine : maxstart, o->tops,
                                               B->kk, B->hits, B->hit_maps, NULL, NULL, ms);
-    if (o->refine)
-        return sat_multi_search_refine(multi, lorder, lsoln, maxstart, o->ncand, o->refine, B->kk, B->hits,
+    if (g->refine)
+        return sat_multi_search_refine(multi, lorder, lsoln, maxstart, o->ncand, g->refine, B->kk, B->hits,
                                        B->hit_maps, NULL, ms, ms_stage2);
-    if (o->nmatch) {
+    if (g->nmatch) {
         /* match 0 of every entry is the plain search's score and map: the listing's rows come from the match slots;
          * -k ranks the entries as without -m (its own search), the extra rows from the slots */
         int rc = sat_multi_search_matches(multi, lorder, maxstart, o->nm, B->all.counts, B->all.scores, B->restarts,
                                           B->all.maps, ms);
-        if (rc == SAT_OK && o->topk > 0) {
+        if (rc == SAT_OK && g->topk > 0) {
             double ms2 = 0.0;
             rc = sat_multi_search_topk(multi, lorder, lsoln, maxstart, B->kk, B->hits, B->hit_maps, &ms2);
             *ms += ms2;
         }
         return rc;
     }
-    if (o->topk > 0)
+    if (g->topk > 0)
         return sat_multi_search_topk(multi, lorder, lsoln, maxstart, B->kk, B->hits, B->hit_maps, ms);
     return sat_multi_search(multi, lorder, lsoln, maxstart, B->all.scores, B->all.maps, ms);
 }
@@ -1379,14 +1377,14 @@ static int match_ranked_rows(const options *o, const input *in, sat_multi *multi
     size_t rows = 0;
     for (int b = 0; b < nqb; b++)
         rows += (size_t)(o->csr ? B->pcounts[b] : rc);
-    alloc_rowm(B, rows ? rows : 1, o->rowmatch, in->lsoln);
+    alloc_rowm(B, rows ? rows : 1, o->g->rowmatch, in->lsoln);
     size_t r = 0;
     for (int b = 0; b < nqb; b++)
         for (size_t n = (size_t)(o->csr ? B->pcounts[b] : rc); n > 0; n--, r++) {
             B->pair_q[r] = b;
             B->pair_e[r] = B->hits[r].entry;
         }
-    return sat_multi_search_pairs_matches(multi, in->lorder, o->refine ? o->refine : o->maxstart, o->rowmatch, (int)rows,
+    return sat_multi_search_pairs_matches(multi, in->lorder, o->g->refine ? o->g->refine : o->g->maxstart, o->g->rowmatch, (int)rows,
                                           B->pair_q, B->pair_e, B->rowm.counts, B->rowm.scores, B->rowm_restarts,
                                           B->rowm.maps, ms);
 }
@@ -1402,27 +1400,19 @@ static void print_batch(const options *o, const input *in, gpu_bufs *B, const sa
     for (int b = 0; b < nqb; b++) {
         const size_t row0 = (size_t)b * in->db.count;
         print_header(in, q0 + b, fits ? &fits[q0 + b] : NULL);
-        if (o->reorder) {
+        if (has(o->g, 'X')) {
             /* -X: one more header line (two with -F: the ordered search's fit), then the rows with their six columns,
              * each followed by the unordered map's lines.  Few rows: printf formats them. */
-            char line[256], kt[4];
+            char kt[4];
             const int n1 = B->n1s[b];
-            int n = snprintf(line, sizeof line, "# REORDER ordered pvalue >= %g kinds = %s\n", o->bmin, kinds_text(o->kinds, kt));
-            out_bytes(line, (size_t)n);
-            if (B->base_fits) {
-                const sat_fit *f = &B->base_fits[b];
-                n = f->fitted ? snprintf(line, sizeof line, "# GUMBEL ordered a = %.17g b = %.17g rows = %d censored = %d below = %d\n",
-                                         f->a, f->b, f->rows, f->censored, f->below)
-                              : snprintf(line, sizeof line, "# GUMBEL ordered not fitted\n");
-                out_bytes(line, (size_t)n);
-            }
+            out_fmt("# REORDER ordered pvalue >= %g kinds = %s\n", o->g->bmin, kinds_text(o->kinds, kt));
+            if (B->base_fits)
+                out_gumbel(&B->base_fits[b], "ordered ");
             for (size_t r = first; r < first + (size_t)B->pcounts[b]; r++) {
                 const sat_reorder_hit *h = &B->rhits[r];
                 const char *kind = h->kind == SAT_KIND_SEQUENTIAL ? "seq" : h->kind == SAT_KIND_CIRCULAR ? "circ" : "perm";
-                n = snprintf(line, sizeof line, "%-8s %d %g %g %g %d %g %s %d %d %d\n", sat_set_name(&in->db, h->hit.entry), h->hit.score,
-                             h->hit.norm2, h->hit.zscore, h->hit.pvalue, h->base_score, h->base_pvalue, kind, h->matched, h->descents,
-                             h->cut);
-                out_bytes(line, (size_t)n);
+                out_fmt("%-8s %d %g %g %g %d %g %s %d %d %d\n", sat_set_name(&in->db, h->hit.entry), h->hit.score, h->hit.norm2,
+                        h->hit.zscore, h->hit.pvalue, h->base_score, h->base_pvalue, kind, h->matched, h->descents, h->cut);
                 const int32_t *map = B->hit_maps + r * SAT_MAXDIM;
                 for (int k = 0; k < n1; k++)
                     if (map[k] >= 0)
@@ -1431,12 +1421,12 @@ static void print_batch(const options *o, const input *in, gpu_bufs *B, const sa
             first += (size_t)B->pcounts[b];
             continue;
         }
-        if (o->ranked) {
+        if (o->out == OUT_RANKED) {
             const size_t nrows = (size_t)(o->csr ? B->pcounts[b] : rc);
             for (size_t r = first; r < first + nrows; r++)
                 print_entry(in, B->hits[r].entry, B->n1s[b], &B->hits[r],
-                            B->hit_maps ? B->hit_maps + r * SAT_MAXDIM : NULL, o->rowmatch ? &B->rowm : all,
-                            o->rowmatch ? r : row0 + B->hits[r].entry, 0);
+                            B->hit_maps ? B->hit_maps + r * SAT_MAXDIM : NULL, o->g->rowmatch ? &B->rowm : all,
+                            o->g->rowmatch ? r : row0 + B->hits[r].entry, 0);
             first += nrows;
             continue;
         }
@@ -1454,80 +1444,45 @@ static void print_batch(const options *o, const input *in, gpu_bufs *B, const sa
     }
 }
 
-/* -L: the table of the clustering the GPUs hold - labels, degrees and the edge count cross to the host (8 bytes a
- * structure and shard), the representatives and sizes are sat_cluster_reps' */
+static int count_singletons(const int32_t *size, int n)
+{
+    int singletons = 0;
+    for (int v = 0; v < n; v++)
+        singletons += size[v] == 1;
+    return singletons;
+}
+
+/* -L, -D: the table of the clustering the GPUs hold, "name representative size degree" a structure.  -L: labels, degrees
+ * and the edge count cross to the host (8 bytes a structure and shard), the representatives and sizes are
+ * sat_cluster_reps'.  -D: the cover the GPUs solved - representatives and degrees (8 bytes a structure), the edge and
+ * round counts; the sizes are sat_cover_sizes', and the library has checked the cover's two invariants before it returned */
 static int print_clusters(const options *o, const input *in, sat_multi *multi, const sat_fit *fits)
 {
-    const int n = in->db.count;
+    const int n = in->db.count, cover = o->consumer == COVER;
     int32_t *label = checked(malloc(sizeof(int32_t) * (size_t)n * 4)), *degree = label + n, *rep = degree + n, *size = rep + n;
     unsigned long long edges = 0;
-    if (sat_multi_cluster_labels(multi, label, degree, &edges) != SAT_OK) {
+    int rounds = 0;
+    if ((cover ? sat_multi_cover_solve(multi, rep, degree, &edges, &rounds)
+               : sat_multi_cluster_labels(multi, label, degree, &edges)) != SAT_OK) {
         fprintf(stderr, "clustering failed: %s\n", sat_last_error());
         free(label);
         return 1;
     }
-    const int clusters = sat_cluster_reps(n, label, degree, rep, size);
+    const int clusters = cover ? sat_cover_sizes(n, rep, size) : sat_cluster_reps(n, label, degree, rep, size);
     if (clusters < 0)
-        die("ERROR: the GPUs returned labels that are no clustering\n");
-    int singletons = 0, fitted = 0;
-    for (int v = 0; v < n; v++)
-        singletons += size[v] == 1;
-    char line[SAT_MAX_LINE_LEN + 256];
-    int len = snprintf(line, sizeof line, "# CLUSTER dbfile = %s entries = %d pvalue <= %g restarts = %d clusters = %d singletons = %d "
-                       "edges = %llu\n", in->dbfile, n, o->lmax, o->maxstart, clusters, singletons, edges);
-    out_bytes(line, (size_t)len);
+        die(cover ? "ERROR: the GPUs returned representatives that are no cover\n"
+                  : "ERROR: the GPUs returned labels that are no clustering\n");
+    out_fmt("# %s dbfile = %s entries = %d pvalue <= %g restarts = %d clusters = %d singletons = %d edges = %llu",
+            cover ? "COVER" : "CLUSTER", in->dbfile, n, cover ? o->g->dmax : o->g->lmax, o->g->maxstart, clusters,
+            count_singletons(size, n), edges);
+    if (cover)
+        out_fmt(" rounds = %d", rounds);
+    out_bytes("\n", 1);
     out_bytes(polish_header, strlen(polish_header));
-    if (fits) {
-        for (int v = 0; v < n; v++)
-            fitted += fits[v].fitted != 0;
-        len = snprintf(line, sizeof line, "# GUMBEL censor = %g fitted = %d of %d\n", o->censor, fitted, n);
-        out_bytes(line, (size_t)len);
-    }
-    for (int v = 0; v < n; v++) {
-        len = snprintf(line, sizeof line, "%-8s %-8s %d %d\n", sat_set_name(&in->db, v), sat_set_name(&in->db, rep[v]), size[v],
-                       degree[v]);
-        out_bytes(line, (size_t)len);
-    }
+    out_fitted(o, fits, n);
+    for (int v = 0; v < n; v++)
+        out_fmt("%-8s %-8s %d %d\n", sat_set_name(&in->db, v), sat_set_name(&in->db, rep[v]), size[v], degree[v]);
     free(label);
-    return 0;
-}
-
-/* -D: the table of the cover the GPUs solved - representatives and degrees (8 bytes a structure), the edge and round
- * counts; the sizes are sat_cover_sizes'.  The library has checked the cover's two invariants before it returned */
-static int print_cover(const options *o, const input *in, sat_multi *multi, const sat_fit *fits)
-{
-    const int n = in->db.count;
-    int32_t *rep = checked(malloc(sizeof(int32_t) * (size_t)n * 3)), *degree = rep + n, *size = degree + n;
-    unsigned long long edges = 0;
-    int rounds = 0;
-    if (sat_multi_cover_solve(multi, rep, degree, &edges, &rounds) != SAT_OK) {
-        fprintf(stderr, "clustering failed: %s\n", sat_last_error());
-        free(rep);
-        return 1;
-    }
-    const int clusters = sat_cover_sizes(n, rep, size);
-    if (clusters < 0)
-        die("ERROR: the GPUs returned representatives that are no cover\n");
-    int singletons = 0, fitted = 0;
-    for (int v = 0; v < n; v++)
-        singletons += size[v] == 1;
-    char line[SAT_MAX_LINE_LEN + 256];
-    int len = snprintf(line, sizeof line, "# COVER dbfile = %s entries = %d pvalue <= %g restarts = %d clusters = %d singletons = %d "
-                       "edges = %llu rounds = %d\n", in->dbfile, n, o->dmax, o->maxstart, clusters, singletons, edges, rounds);
-    out_bytes(line, (size_t)len);
-    out_bytes(polish_header, strlen(polish_header));
-    if (fits) {
-        for (int v = 0; v < n; v++)
-            fitted += fits[v].fitted != 0;
-        len = snprintf(line, sizeof line, "# GUMBEL censor = %g fitted = %d of %d\n", o->censor, fitted, n);
-        out_bytes(line, (size_t)len);
-    }
-    for (int v = 0; v < n; v++) {
-        len = snprintf(line, sizeof line, "%-8s %-8s %d %d\n", sat_set_name(&in->db, v), sat_set_name(&in->db, rep[v]), size[v],
-                       degree[v]);
-        out_bytes(line, (size_t)len);
-    }
-    free(rep);
     return 0;
 }
 
@@ -1535,7 +1490,7 @@ static int print_cover(const options *o, const input *in, sat_multi *multi, cons
  * a structure, level and shard cross to the host; the levels must be nested (sat_cluster_nested) */
 static int print_cluster_levels(const options *o, const input *in, sat_multi *multi, const sat_fit *fits)
 {
-    const int n = in->db.count, nl = o->nlevels;
+    const int n = in->db.count, nl = o->g->nlevels;
     const size_t cells = (size_t)n * (size_t)nl;
     int32_t *label = checked(malloc(sizeof(int32_t) * cells * 4)), *degree = label + cells, *rep = degree + cells, *size = rep + cells;
     unsigned long long edges[SAT_MAX_CLUSTER_LEVELS] = { 0 };
@@ -1549,36 +1504,22 @@ static int print_cluster_levels(const options *o, const input *in, sat_multi *mu
         die("ERROR: the GPUs returned labels that are no clustering\n");
     if (broken > 0)
         die("ERROR: the clusters of level %d do not lie inside those of level %d\n", broken, broken + 1);
-    char line[SAT_MAX_LINE_LEN + 256];
-    int len = snprintf(line, sizeof line, "# CLUSTER dbfile = %s entries = %d levels = %d restarts = %d\n", in->dbfile, n, nl, o->maxstart);
-    out_bytes(line, (size_t)len);
+    out_fmt("# CLUSTER dbfile = %s entries = %d levels = %d restarts = %d\n", in->dbfile, n, nl, o->g->maxstart);
     for (int j = 0; j < nl; j++) {
         const size_t at = (size_t)j * (size_t)n;
         const int clusters = sat_cluster_reps(n, label + at, degree + at, rep + at, size + at);
         if (clusters < 0)
             die("ERROR: the GPUs returned labels that are no clustering\n");
-        int singletons = 0;
-        for (int v = 0; v < n; v++)
-            singletons += size[at + v] == 1;
-        len = snprintf(line, sizeof line, "# LEVEL %d pvalue <= %g clusters = %d singletons = %d edges = %llu\n", j + 1, o->levels[j], clusters,
-                       singletons, edges[j]);
-        out_bytes(line, (size_t)len);
+        out_fmt("# LEVEL %d pvalue <= %g clusters = %d singletons = %d edges = %llu\n", j + 1, o->g->levels[j], clusters,
+                count_singletons(size + at, n), edges[j]);
     }
     out_bytes(polish_header, strlen(polish_header));
-    if (fits) {
-        int fitted = 0;
-        for (int v = 0; v < n; v++)
-            fitted += fits[v].fitted != 0;
-        len = snprintf(line, sizeof line, "# GUMBEL censor = %g fitted = %d of %d\n", o->censor, fitted, n);
-        out_bytes(line, (size_t)len);
-    }
+    out_fitted(o, fits, n);
     for (int v = 0; v < n; v++) {
-        len = snprintf(line, sizeof line, "%-8s", sat_set_name(&in->db, v));
-        out_bytes(line, (size_t)len);
+        out_fmt("%-8s", sat_set_name(&in->db, v));
         for (int j = 0; j < nl; j++) {
             const size_t at = (size_t)j * (size_t)n + (size_t)v;
-            len = snprintf(line, sizeof line, " %-8s %d %d", sat_set_name(&in->db, rep[at]), size[at], degree[at]);
-            out_bytes(line, (size_t)len);
+            out_fmt(" %-8s %d %d", sat_set_name(&in->db, rep[at]), size[at], degree[at]);
         }
         out_bytes("\n", 1);
     }
@@ -1588,45 +1529,40 @@ static int print_cluster_levels(const options *o, const input *in, sat_multi *mu
 
 /* -E: the table of the evaluation - the queries' rows as the GPUs reduced them (32 bytes a query crossed to the host);
  * the two ratios are taken here, and their means over the queries where both are defined */
-static void print_eval(const options *o, const input *in, const sat_classes *cl, const sat_eval *ev)
+static void print_eval(const options *o, const input *in, const gpu_bufs *B)
 {
-    /* (the class file's name and the class tokens are of any length: they go out as they are, not through `line`) */
-    char line[SAT_MAX_LINE_LEN + 256];
-    int len = snprintf(line, sizeof line, "# EVAL dbfile = %s classes = ", in->dbfile);
-    out_bytes(line, (size_t)len);
-    out_bytes(o->classfile, strlen(o->classfile));
-    len = snprintf(line, sizeof line, " entries = %d classified = %d distinct = %d restarts = %d rocn = %d\n", in->db.count, cl->classified,
-                   cl->distinct, o->maxstart, o->rocn);
-    out_bytes(line, (size_t)len);
+    const sat_classes *cl = &B->classes;
+    /* (the class file's name and the class tokens are of any length: they go out as they are, not through out_fmt) */
+    out_fmt("# EVAL dbfile = %s classes = ", in->dbfile);
+    out_bytes(o->g->classfile, strlen(o->g->classfile));
+    out_fmt(" entries = %d classified = %d distinct = %d restarts = %d rocn = %d\n", in->db.count, cl->classified, cl->distinct,
+            o->g->maxstart, o->rocn);
     out_bytes(polish_header, strlen(polish_header));
     int defined = 0;
     double auc_sum = 0.0, rocn_sum = 0.0;
-    for (int qi = 0; qi < in->num_queries; qi++)
-        if (ev[qi].positives > 0 && ev[qi].negatives > 0) {
-            auc_sum += (double)ev[qi].u2 / (2.0 * (double)ev[qi].positives * (double)ev[qi].negatives);
-            rocn_sum += (double)ev[qi].t2 / (2.0 * (double)ev[qi].positives * (double)ev[qi].n_used);
+    for (int qi = 0; qi < in->num_queries; qi++) {
+        const sat_eval *e = &B->evals[qi];
+        if (e->positives > 0 && e->negatives > 0) {
+            auc_sum += (double)e->u2 / (2.0 * (double)e->positives * (double)e->negatives);
+            rocn_sum += (double)e->t2 / (2.0 * (double)e->positives * (double)e->n_used);
             defined++;
         }
+    }
     if (defined)
-        len = snprintf(line, sizeof line, "# MEAN queries = %d auc = %.6f rocn = %.6f\n", defined, auc_sum / defined, rocn_sum / defined);
+        out_fmt("# MEAN queries = %d auc = %.6f rocn = %.6f\n", defined, auc_sum / defined, rocn_sum / defined);
     else
-        len = snprintf(line, sizeof line, "# MEAN queries = 0 auc = NA rocn = NA\n");
-    out_bytes(line, (size_t)len);
+        out_fmt("# MEAN queries = 0 auc = NA rocn = NA\n");
     for (int qi = 0; qi < in->num_queries; qi++) {
-        const sat_eval *e = &ev[qi];
+        const sat_eval *e = &B->evals[qi];
         const char *token = e->query_class >= 0 && e->query_class < cl->distinct ? cl->token[e->query_class] : "-";
-        len = snprintf(line, sizeof line, "%-8s ", sat_set_name(&in->db, in->qindex[qi]));
-        out_bytes(line, (size_t)len);
+        out_fmt("%-8s ", sat_set_name(&in->db, in->qindex[qi]));
         out_bytes(token, strlen(token));
-        len = snprintf(line, sizeof line, " %d %d %llu %llu %d", e->positives, e->negatives, (unsigned long long)e->u2,
-                       (unsigned long long)e->t2, e->n_used);
-        out_bytes(line, (size_t)len);
+        out_fmt(" %d %d %llu %llu %d", e->positives, e->negatives, (unsigned long long)e->u2, (unsigned long long)e->t2, e->n_used);
         if (e->positives > 0 && e->negatives > 0)
-            len = snprintf(line, sizeof line, " %.6f %.6f\n", (double)e->u2 / (2.0 * (double)e->positives * (double)e->negatives),
-                           (double)e->t2 / (2.0 * (double)e->positives * (double)e->n_used));
+            out_fmt(" %.6f %.6f\n", (double)e->u2 / (2.0 * (double)e->positives * (double)e->negatives),
+                    (double)e->t2 / (2.0 * (double)e->positives * (double)e->n_used));
         else
-            len = snprintf(line, sizeof line, " NA NA\n");
-        out_bytes(line, (size_t)len);
+            out_fmt(" NA NA\n");
     }
 }
 
@@ -1635,18 +1571,10 @@ static void print_eval(const options *o, const input *in, const sat_classes *cl,
 static void print_profiles(const options *o, const input *in, const gpu_bufs *B, const sat_fit *fits)
 {
     static const char *tname[4] = { "e", "xa", "xi", "xg" };
-    char line[SAT_MAX_LINE_LEN + 256];
-    int len = snprintf(line, sizeof line, "# PROFILE dbfile = %s pvalue <= %g fraction >= %g restarts = %d queries = %d\n", in->dbfile,
-                       o->wmax, o->core, o->maxstart, in->num_queries);
-    out_bytes(line, (size_t)len);
+    out_fmt("# PROFILE dbfile = %s pvalue <= %g fraction >= %g restarts = %d queries = %d\n", in->dbfile, o->g->wmax, o->core,
+            o->g->maxstart, in->num_queries);
     out_bytes(polish_header, strlen(polish_header));
-    if (fits) {
-        int fitted = 0;
-        for (int qi = 0; qi < in->num_queries; qi++)
-            fitted += fits[qi].fitted != 0;
-        len = snprintf(line, sizeof line, "# GUMBEL censor = %g fitted = %d of %d\n", o->censor, fitted, in->num_queries);
-        out_bytes(line, (size_t)len);
-    }
+    out_fitted(o, fits, in->num_queries);
     uint8_t in_core[SAT_MAXDIM];
     for (int qi = 0; qi < in->num_queries; qi++) {
         int qs;
@@ -1654,16 +1582,8 @@ static void print_profiles(const options *o, const input *in, const gpu_bufs *B,
         const int n1 = qset->order[qs], motif = in->motifs && in->qsub[qi] >= 0;
         const char *name = sat_set_name(in->qsrc, in->qindex[qi]);
         const uint32_t *joint = B->pjoint + B->poff[qi];
-        len = snprintf(line, sizeof line, "# QUERY %s sses = %d hits = %u\n", name, n1, B->phits[qi]);
-        out_bytes(line, (size_t)len);
-        if (motif) {
-            out_bytes("# QUERY SSES = ", 15);
-            for (int32_t k = in->sse_begin[qi]; k < in->sse_begin[qi + 1]; k++) {
-                len = snprintf(line, sizeof line, k > in->sse_begin[qi] ? ",%d" : "%d", in->sse[k] + 1);
-                out_bytes(line, (size_t)len);
-            }
-            out_bytes("\n", 1);
-        }
+        out_fmt("# QUERY %s sses = %d hits = %u\n", name, n1, B->phits[qi]);
+        out_query_sses(in, qi);
         uint32_t joint_min = 0;
         const int core = sat_profile_core(n1, B->phits[qi], joint, o->core, in_core, &joint_min);
         if (core < 0)
@@ -1671,65 +1591,101 @@ static void print_profiles(const options *o, const input *in, const gpu_bufs *B,
         if (core == 0) {
             out_bytes("# CORE none\n", 12);
         } else {
-            len = snprintf(line, sizeof line, "# CORE sses = %d joint >= %u %s@", core, joint_min, name);
-            out_bytes(line, (size_t)len);
+            out_fmt("# CORE sses = %d joint >= %u %s@", core, joint_min, name);
             for (int i = 0, first = 1; i < n1; i++)
                 if (in_core[i]) {
-                    len = snprintf(line, sizeof line, first ? "%d" : ",%d", motif ? in->sse[in->sse_begin[qi] + i] + 1 : i + 1);
-                    out_bytes(line, (size_t)len);
+                    out_fmt(first ? "%d" : ",%d", motif ? in->sse[in->sse_begin[qi] + i] + 1 : i + 1);
                     first = 0;
                 }
             out_bytes("\n", 1);
         }
         const uint8_t *tab = qset->tab + qset->cell_off[qs];
         for (int i = 0; i < n1; i++) {
-            len = snprintf(line, sizeof line, "%d %s %u", i + 1, tname[tab[(size_t)i * (i + 1) / 2 + i] & 3], joint[(size_t)i * n1 + i]);
-            out_bytes(line, (size_t)len);
-            for (int k = 0; k < n1; k++) {
-                len = snprintf(line, sizeof line, " %u", joint[(size_t)i * n1 + k]);
-                out_bytes(line, (size_t)len);
-            }
+            out_fmt("%d %s %u", i + 1, tname[tab[(size_t)i * (i + 1) / 2 + i] & 3], joint[(size_t)i * n1 + i]);
+            for (int k = 0; k < n1; k++)
+                out_fmt(" %u", joint[(size_t)i * n1 + k]);
             out_bytes("\n", 1);
         }
     }
 }
 
+/* The on-GPU consumer of the run's rows (-L, -H, -D, -E, -W; none: nothing to do), in three steps.  Before the first
+ * batch: its accumulator on the GPUs */
+static int consumer_begin(const options *o, sat_multi *multi, const gpu_bufs *B)
+{
+    switch (o->consumer) {
+    case CLUSTER: return sat_multi_cluster_begin(multi);
+    case CLUSTER_LEVELS: return sat_multi_cluster_begin_levels(multi, o->g->nlevels, o->g->levels);
+    case COVER: return sat_multi_cover_begin(multi);
+    case EVAL: return sat_multi_eval_classes(multi, B->classes.node_class);
+    default: return SAT_OK;
+    }
+}
+
+/* After each batch's search: its rows of queries q0 .. q0 + nqb - 1 taken in where they are.  Query b is structure
+ * qindex[q0 + b] of the database; for -W when it was taken from there (a motif: its source entry), else no structure of it */
+static int consumer_add(const options *o, const input *in, sat_multi *multi, gpu_bufs *B, int q0, int nqb)
+{
+    const int *entries = in->qindex + q0;
+    switch (o->consumer) {
+    case CLUSTER: return sat_multi_cluster_add(multi, o->g->lmax, entries);
+    case CLUSTER_LEVELS: return sat_multi_cluster_add_levels(multi, entries);
+    case COVER: return sat_multi_cover_add(multi, o->g->dmax, entries);
+    case EVAL: return sat_multi_eval_rows(multi, entries, o->rocn, B->evals + q0);
+    case PROFILE:
+        for (int b = 0; b < nqb; b++)
+            B->qnode[b] = o->dbfile ? entries[b] : -1;
+        return sat_multi_profile_rows(multi, o->g->wmax, B->qnode, B->phits + q0, B->pjoint + B->poff[q0], NULL);
+    default: return SAT_OK;
+    }
+}
+
+/* After the last batch: its table.  Returns the run's status */
+static int consumer_print(const options *o, const input *in, sat_multi *multi, const gpu_bufs *B, const sat_fit *fits)
+{
+    switch (o->consumer) {
+    case CLUSTER: case COVER: return print_clusters(o, in, multi, fits);
+    case CLUSTER_LEVELS: return print_cluster_levels(o, in, multi, fits);
+    case EVAL: print_eval(o, in, B); return 0;
+    case PROFILE: print_profiles(o, in, B, fits); return 0;
+    default: return 0;
+    }
+}
+
+/* -Q, -a: the batch q0 .. q0 + nqb - 1 from its entries' indices in the database the GPUs hold; where the run has a motif,
+ * with the batch's lists, their offsets counted from the batch's first.  Else the structures expanded here and copied */
+static int set_queries(const options *o, const input *in, sat_multi *multi, gpu_bufs *B, int q0, int nqb)
+{
+    if (!queries_from_db(o))
+        return sat_multi_queries_set(multi, nqb, B->n1s, B->qtabs, B->qdmats, SAT_MAXDIM, B->qtypes, (uint32_t)q0);
+    if (!in->motifs)
+        return sat_multi_queries_from_db(multi, nqb, in->qindex + q0, (uint32_t)q0);
+    for (int b = 0; b <= nqb; b++)
+        B->sse_begin[b] = in->sse_begin[q0 + b] - in->sse_begin[q0];
+    return sat_multi_queries_from_db_sses(multi, nqb, in->qindex + q0, B->sse_begin, in->sse + in->sse_begin[q0], (uint32_t)q0);
+}
+
 static int run_gpu(const options *o, const input *in)
 {
-    /* -E: the classification, read before any GPU is touched: a bad file ends the run here */
-    sat_classes classes;
-    memset(&classes, 0, sizeof classes);
-    if (o->classfile) {
-        char err[SAT_MAX_LINE_LEN + 256];
-        if (sat_read_classes(o->classfile, &in->db, &classes, err, sizeof err) != 0)
-            die("ERROR: %s\n", err);
-        if (classes.unknown)
-            fprintf(stderr, "WARNING: %d names of %s are not in the database\n", classes.unknown, o->classfile);
-        fprintf(stderr, "Read %d classes of %d of %d structures from %s\n", classes.distinct, classes.classified, in->db.count, o->classfile);
-    }
-    if (o->from_db && in->motifs && !sat_multi_queries_from_db_sses)
-        die("ERROR: this library has no sat_multi_queries_from_db_sses\n");
-    sat_eval *evals = o->classfile ? checked(calloc((size_t)in->num_queries + 1, sizeof(sat_eval))) : NULL;
-    sat_multi *multi = open_multi(o, in);
+    const given *g = o->g;
+    const int total = in->db.count, fit = has(g, 'F'), stage2 = g->refine ? g->refine : g->maxstart;
+    int status = 0;
     gpu_bufs B;
     alloc_gpu_bufs(o, in, &B);
-    const int total = in->db.count;
-    int status = 0;
-    if (o->polish)
-        snprintf(polish_header, sizeof polish_header, "# POLISH tops = %d restarts = %d candidates = %d\n", o->polish,
-                 o->refine ? o->refine : o->maxstart, o->ncand);
-    if (o->polish_all) {
-        snprintf(polish_header, sizeof polish_header, "# POLISH tops = %d all rows\n", o->polish_all);
-        if (sat_multi_polish_all_set(multi, o->polish_all) != SAT_OK)
+    if (queries_from_db(o) && in->motifs && !sat_multi_queries_from_db_sses)
+        die("ERROR: this library has no sat_multi_queries_from_db_sses\n");
+    sat_multi *multi = open_multi(o, in);
+    if (o->polish == POLISH_CANDIDATES)
+        snprintf(polish_header, sizeof polish_header, "# POLISH tops = %d restarts = %d candidates = %d\n", o->tops, stage2, o->ncand);
+    if (o->polish == POLISH_ALL) {
+        snprintf(polish_header, sizeof polish_header, "# POLISH tops = %d all rows\n", o->tops);
+        if (sat_multi_polish_all_set(multi, o->tops) != SAT_OK)
             die("ERROR: %s\n", sat_last_error());
     }
     /* -F: every query's fit - from the GPUs with -k / -p, else made here from the listing's scores (the whole
      * database's, both size classes: a query's two blocks carry the same line) */
-    sat_fit *fits = o->fit ? checked(calloc((size_t)in->num_queries, sizeof(sat_fit))) : NULL;
-    if (o->cluster && (o->cover ? sat_multi_cover_begin(multi) : o->nlevels ? sat_multi_cluster_begin_levels(multi, o->nlevels, o->levels)
-                                                               : sat_multi_cluster_begin(multi)) != SAT_OK)
-        die("ERROR: %s\n", sat_last_error());
-    if (o->classfile && sat_multi_eval_classes(multi, classes.node_class) != SAT_OK)
+    sat_fit *fits = fit ? checked(calloc((size_t)in->num_queries, sizeof(sat_fit))) : NULL;
+    if (consumer_begin(o, multi, &B) != SAT_OK)
         die("ERROR: %s\n", sat_last_error());
     for (int q0 = 0; q0 < in->num_queries; q0 += B.batch) {
         const int nqb = in->num_queries - q0 < B.batch ? in->num_queries - q0 : B.batch;
@@ -1737,7 +1693,7 @@ static int run_gpu(const options *o, const input *in)
             int qs;
             const sat_struct_set *qset = query_set(in, q0 + b, &qs);
             B.n1s[b] = qset->order[qs];
-            if (o->from_db)
+            if (queries_from_db(o))
                 continue;
             uint8_t *tab = B.qtabs + (size_t)b * SAT_MAXDIM * SAT_MAXDIM;
             sat_set_expand(qset, qs, SAT_MAXDIM, tab, B.qdmats + (size_t)b * SAT_MAXDIM * SAT_MAXDIM);
@@ -1747,37 +1703,18 @@ static int run_gpu(const options *o, const input *in)
         fprintf(stderr, "Executing simulated annealing tableaux match kernel on GPU for %d quer%s (from %s)...\n",
                 nqb, nqb == 1 ? "y" : "ies", sat_set_name(in->qsrc, in->qindex[q0]));
         double ms = 0.0, ms_stage2 = 0.0;
-        /* -Q, -a: the batch from its entries' indices in the database the GPUs hold; where the run has a motif, with
-         * the batch's lists, their offsets counted from the batch's first */
-        if (o->from_db && in->motifs)
-            for (int b = 0; b <= nqb; b++)
-                B.sse_begin[b] = in->sse_begin[q0 + b] - in->sse_begin[q0];
-        int rc = o->from_db && in->motifs ? sat_multi_queries_from_db_sses(multi, nqb, in->qindex + q0, B.sse_begin,
-                                                                           in->sse + in->sse_begin[q0], (uint32_t)q0)
-                 : o->from_db ? sat_multi_queries_from_db(multi, nqb, in->qindex + q0, (uint32_t)q0)
-                            : sat_multi_queries_set(multi, nqb, B.n1s, B.qtabs, B.qdmats, SAT_MAXDIM, B.qtypes, (uint32_t)q0);
+        /* the library calls of a batch, in this order: queries set, search, consumer add, then -M */
+        int rc = set_queries(o, in, multi, &B, q0, nqb);
         if (rc == SAT_OK)
             rc = search_batch(o, in, multi, &B, fits ? fits + q0 : NULL, &ms, &ms_stage2);
-        /* -L, -H, -D: the batch's edges into the graph(s) on the GPUs; query b is structure qindex[q0 + b] of the database */
-        if (rc == SAT_OK && o->cluster)
-            rc = o->cover ? sat_multi_cover_add(multi, o->dmax, in->qindex + q0)
-                 : o->nlevels ? sat_multi_cluster_add_levels(multi, in->qindex + q0) : sat_multi_cluster_add(multi, o->lmax, in->qindex + q0);
-        /* -E: the batch's rows scored where they are; query b is structure qindex[q0 + b] of the database */
-        if (rc == SAT_OK && o->classfile)
-            rc = sat_multi_eval_rows(multi, in->qindex + q0, o->rocn, evals + q0);
-        /* -W: the batch's rows and maps counted where they are; query b is structure qindex[q0 + b] of the database when
-         * it was taken from there (a motif: its source entry), else no structure of it */
-        if (rc == SAT_OK && o->profile) {
-            for (int b = 0; b < nqb; b++)
-                B.qnode[b] = o->qfile ? in->qindex[q0 + b] : -1;
-            rc = sat_multi_profile_rows(multi, o->wmax, B.qnode, B.phits + q0, B.pjoint + B.poff[q0], NULL);
-        }
+        if (rc == SAT_OK)
+            rc = consumer_add(o, in, multi, &B, q0, nqb);
         if (rc < 0) {
             fprintf(stderr, "kernel launch failed: %s\n", sat_last_error());
             status = 1;
             break;
         }
-        if (o->rowmatch) {
+        if (g->rowmatch) {
             double ms_rows = 0.0;
             if (match_ranked_rows(o, in, multi, &B, nqb, rc, &ms_rows) != SAT_OK) {
                 fprintf(stderr, "kernel launch failed: %s\n", sat_last_error());
@@ -1787,32 +1724,28 @@ static int run_gpu(const options *o, const input *in)
             fprintf(stderr, "matches of the printed rows: %f ms\n", ms_rows);
         }
         fprintf(stderr, "GPU execution time %f ms\n", ms);
-        if (o->polish)
+        if (o->polish == POLISH_CANDIDATES)
             fprintf(stderr, "polish: %d candidates per query x %d restarts, %d maps each\n", o->ncand < total ? o->ncand : total,
-                    o->refine ? o->refine : o->maxstart, o->polish);
-        else if (o->polish_all)
-            fprintf(stderr, "polish: every row, %d maps each\n", o->polish_all);
-        else if (o->refine)
+                    stage2, o->tops);
+        else if (o->polish == POLISH_ALL)
+            fprintf(stderr, "polish: every row, %d maps each\n", o->tops);
+        else if (g->refine)
             fprintf(stderr, "refine: stage 2 %f ms, %d candidates per query x %d restarts\n", ms_stage2,
-                    o->ncand < total ? o->ncand : total, o->refine);
+                    o->ncand < total ? o->ncand : total, g->refine);
         fprintf(stderr, "%f million iterations/sec\n",
-                ((double)total * nqb * ((double)o->maxstart * SAT_MAXITER) / (ms / 1000)) / 1.0e6);
-        if (o->cluster || o->classfile || o->profile)
+                ((double)total * nqb * ((double)g->maxstart * SAT_MAXITER) / (ms / 1000)) / 1.0e6);
+        if (o->out == OUT_NONE)
             continue;
-        if (o->fit && !o->ranked)
+        if (fit && o->out == OUT_LISTING)
             for (int b = 0; b < nqb; b++)
-                fits[q0 + b] = fit_scores(B.all.scores + (size_t)b * total, total, B.n1s[b], in->db.order, o->censor);
+                fits[q0 + b] = fit_scores(B.all.scores + (size_t)b * total, total, B.n1s[b], in->db.order, g->censor);
         print_batch(o, in, &B, fits, q0, nqb, rc);
     }
+    if (!status)
+        status = consumer_print(o, in, multi, &B, fits);
     /* the listing's deferred block: every query's large-class rows, after all small-class blocks, with the reference
      * GPU path's two blanks before the p-value */
-    if (!status && o->cluster)
-        status = o->cover ? print_cover(o, in, multi, fits) : o->nlevels ? print_cluster_levels(o, in, multi, fits) : print_clusters(o, in, multi, fits);
-    if (!status && o->classfile)
-        print_eval(o, in, &classes, evals);
-    if (!status && o->profile)
-        print_profiles(o, in, &B, fits);
-    if (!status && !o->ranked && !o->cluster && !o->classfile && !o->profile && in->cls_count[1] > 0)
+    if (!status && o->out == OUT_LISTING && in->cls_count[1] > 0)
         for (int qi = 0; qi < in->num_queries; qi++) {
             print_header(in, qi, fits ? &fits[qi] : NULL);
             for (int d = 0; d < in->cls_count[1]; d++)
@@ -1823,15 +1756,15 @@ static int run_gpu(const options *o, const input *in)
     sat_multi_destroy(multi);
     free_gpu_bufs(&B);
     free(fits);
-    free(evals);
-    sat_classes_free(&classes);
     return status;
 }
 
 int main(int argc, char *argv[])
 {
+    given g;
     options o;
-    parse_options(argc, argv, &o);
+    parse_options(argc, argv, &g);
+    plan_run(&g, &o);
     fprintf(stderr, "MAXDIM = %d\n", SAT_MAXDIM);
     atexit(out_flush);                                   /* every exit path, exit(1) included */
     input in;
@@ -1840,13 +1773,8 @@ int main(int argc, char *argv[])
     sat_set_init(&in.db);
     read_queries(&o, &in);
     load_database(&o, &in);
-    if (o.reorder) {
-        /* -X runs both searches itself; its rows are the unordered search's, with their maps */
-        in.lorder = 0;
-        in.lsoln = 1;
-    }
-    fprintf(stderr, "maxstart = %d\n", o.maxstart);
-    const int status = o.use_gpu ? run_gpu(&o, &in) : run_host(&o, &in);
+    fprintf(stderr, "maxstart = %d\n", g.maxstart);
+    const int status = has(&g, 'c') ? run_host(&o, &in) : run_gpu(&o, &in);
     free_input(&in);
     free(norm2_cache);
     free(fit_store);
