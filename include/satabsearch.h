@@ -845,8 +845,10 @@ unsigned long long sat_multi_stat_d2h_bytes(const sat_multi *m);
  *                    database polish followed.  A small kernel on the context's stream; the call does not wait and
  *                    nothing crosses to the host (sat_stat_d2h_bytes does not move).  Costs 12 bytes a row of device
  *                    memory, kept until dropped.  SAT_ESTATE before a search.  The baseline belongs to (resident
- *                    database, query batch): a database upload and every query-setting call drop it; searches, fits,
- *                    sat_polish_all_set and the cluster, cover and eval state keep it.
+ *                    database, query batch): a database upload and every query-setting call (sat_query_set, sat_queries_set,
+ *                    sat_queries_from_db, sat_queries_from_db_sses - also with an unchanged shape) drop it; searches, the
+ *                    pair searches, fits, sat_polish_all_set and the cluster, cover, eval and profile calls keep it.  A
+ *                    second sat_baseline_keep replaces it.
  * sat_baseline_drop   forgets it (the memory stays with the context).
  * sat_baseline_results   the kept rows, [n_queries][n_entries] each; either array may be NULL.  Copies exactly 4 and /
  *                    or 8 bytes a row.  SAT_ESTATE without a baseline.
@@ -866,7 +868,11 @@ unsigned long long sat_multi_stat_d2h_bytes(const sat_multi *m);
  * sat_search_reordered   the two searches in one call: the ordered search (lorder = 1, lsoln = 0), sat_stats_fit(censor)
  *                    when censor >= 0, sat_baseline_keep, the unordered search (lorder = 0, lsoln = 1), sat_stats_fit
  *                    again - each search fitted to its own scores.  Afterwards the searched state is the unordered
- *                    search's.  *kernel_ms (may be NULL): both searches' time on the stream.
+ *                    search's.  Both searches follow sat_polish_all_set as sat_search does: where it is on, the baseline
+ *                    and the searched state hold polished rows, and sat_results_base works.  The baseline is kept behind
+ *                    the first fit and before the second search: its p-values are the ordered search's under the ordered
+ *                    search's own fit.  A censor outside [0, 0.5] is SAT_EINVAL before either search: nothing changes.
+ *                    *kernel_ms (may be NULL): both searches' time on the stream.
  * sat_multi_*        the same over every shard; sat_multi_reorder_hits merges as sat_multi_hits_cutoff does (per query
  *                    by score, then by entry index in the whole database) and returns exactly what one context holding
  *                    the whole database returns; every check is made for every shard before the first one works.

@@ -69,6 +69,27 @@ def expected_rows(scores, n1s, query_nodes, node_class, rocn, ordinals=None):
     return rows
 
 
+def expected_tables(scores, n1s, query_nodes, node_class, ordinals=None):
+    """the packed uint32 tables sat_eval_tables must return: per query pos[bins] then neg[bins], bins = 2 n1 (n1 - 1) + 1,
+    bin = clamped score + n1 (n1 - 1); rows counted as in expected_rows; an unclassified query's table is zero"""
+    scores = np.asarray(scores).reshape(len(query_nodes), -1)
+    node_class = np.asarray(node_class, np.int32)
+    ordinals = np.arange(scores.shape[1]) if ordinals is None else np.asarray(ordinals)
+    entry_class = node_class[ordinals]
+    out = []
+    for q, node in enumerate(query_nodes):
+        m = int(n1s[q]) * (int(n1s[q]) - 1)
+        tab = np.zeros((2, 2 * m + 1), np.uint32)
+        c = int(node_class[node])
+        if c >= 0:
+            counted = (entry_class >= 0) & (ordinals != node)
+            s = clamp(scores[q], n1s[q]) + m
+            for side, keep in enumerate((counted & (entry_class == c), counted & (entry_class != c))):
+                np.add.at(tab[side], s[keep], 1)
+        out.append(tab.ravel())
+    return np.concatenate(out)
+
+
 def same_rows(got, want, what=""):
     assert got.dtype == EVAL_DTYPE or got.dtype.itemsize == 32
     for f in EVAL_DTYPE.names:

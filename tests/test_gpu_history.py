@@ -6,11 +6,15 @@ pair of kinds the model of the documented state allows, with entries, queries, n
 and down on one context; 3. at every step of every walk every result call the model says is not available returns its
 documented error and changes nothing; 4. walks under a 16 KB scratch budget and a small selection-key budget, which make
 the launch cuts depend on what the buffers were sized for before; 5. the same on 2 and 3 shards on device 0, with shard
-sizes that move the padded rows up and down."""
+sizes that move the padded rows up and down.
+The kinds added since (the leveled accumulator, the cover, the evaluation, motif batches, the profile, the baseline and the
+reordered hits) run through the same five: scenario 1 by DATA_KINDS, and the walks of the second schedule (NEW_WALKS: every
+allowed pair with a new kind in it) through 2 to 5."""
 import numpy as np
 import pytest
 
 import cuda_satabsearch_amd as sat
+import cover_lib
 import history_lib as hl
 
 pytestmark = pytest.mark.gpu
@@ -31,10 +35,21 @@ def follow(s, ops, multi=False, after_step=None):
             assert diff is None, "step %d, %s on (%s, %s) after %s: %s" % (
                 step, text(o), dict(o.args).get("db", m.db), m.batch, [text(x) for x in ops[max(0, step - 4):step]], diff)
             compared += 1
+            properties(o, m, got)
         m.apply(o)
         if after_step:
             after_step(s, m)
     return compared
+
+
+def properties(o, m, got):
+    """what the header promises of a result beyond its bytes: the nesting of the levels, the cover's two invariants"""
+    if o.kind == "cluster_labels_levels":
+        labels = got[0]
+        for j in range(len(labels) - 1):
+            assert np.array_equal(labels[j + 1][labels[j]], labels[j + 1]), "levels %d and %d are not nested" % (j, j + 1)
+    if o.kind == "cover_solve":
+        cover_lib.check_invariants(m.cover[0], *hl._added_edges(m.cover[1]), got[0])
 
 
 def data_steps(ops):
@@ -63,6 +78,14 @@ def test_walk(walk):
         assert follow(s, walks[walk]) == data_steps(walks[walk])
 
 
+@pytest.mark.parametrize("walk", range(hl.NEW_WALKS))
+def test_new_walk(walk):
+    walks = hl.schedule(hl.SEED, False, True)
+    assert len(walks) == hl.NEW_WALKS
+    with sat.Searcher(0) as s:
+        assert follow(s, walks[walk]) == data_steps(walks[walk])
+
+
 # ---------------------------------------------------------------- 3. refusals
 def refused(call, code):
     with pytest.raises(sat.SatError, match=r"^\[%d\]" % code):
@@ -85,13 +108,62 @@ def refusals(s, m):
             refused(call, -5)
     if sd is None or not sd.tops:
         refused(s.results_base, -5)
-    if sd is None or m.cluster is None:
+    if sd is None or m.cluster is None or m.leveled():               # (the other accumulator kind: SAT_ESTATE)
         refused(lambda: s.cluster_add(0.5, nodes), -5)
     else:
         refused(lambda: s.cluster_add(0.5, nodes + m.cluster[0]), -1)
-    if m.cluster is None:
+    if m.cluster is None or m.leveled():
         refused(s.cluster_labels, -5)
     refused(lambda: s.set_polish_all(9), -1)
+    # the calls added since: no leveled accumulator (none, or the plain one), no cover, no classes, no lsoln, no baseline
+    if sd is None or not m.leveled():
+        refused(lambda: s.cluster_add_levels(nodes), -5)
+    else:
+        refused(lambda: s.cluster_add_levels(nodes + m.cluster[0]), -1)
+    if not m.leveled():
+        refused(s.cluster_labels_levels, -5)
+    if m.db is not None:                                              # an earlier accumulator of either kind stays as it was
+        refused(lambda: s.cluster_begin_levels([0.5, 0.1]), -1)
+        refused(lambda: s.cluster_begin_levels(np.linspace(0.1, 0.9, hl.MAX_LEVELS + 1)), -1)
+        refused(lambda: s.cover_begin(0), -1)
+        refused(lambda: s.set_eval_classes(hl.classes(m.db)[:-1]), -1)
+    else:
+        for call in (lambda: s.cluster_begin_levels([0.5], 5), lambda: s.cover_begin(5), lambda: s.set_eval_classes(np.zeros(5, np.int32))):
+            refused(call, -5)
+    if sd is None or m.cover is None:
+        refused(lambda: s.cover_add(0.5, nodes), -5)
+    else:
+        refused(lambda: s.cover_add(0.5, nodes + m.cover[0]), -1)
+        refused(lambda: s.cover_add(-0.5, nodes), -1)
+    if m.cover is None:
+        refused(s.cover_solve, -5)
+    if sd is None or not m.classes:
+        refused(lambda: s.eval_rows(nodes), -5)
+        refused(lambda: s.eval_tables(nodes) if m.batch is not None else s.eval_rows(nodes, 1), -5)
+    else:
+        refused(lambda: s.eval_rows(nodes, 0), -1)
+        refused(lambda: s.eval_rows(nodes + len(hl.db(m.db))), -1)
+        refused(lambda: s.eval_tables(nodes - 1), -1)
+    if m.batch is not None:                                           # (the wrapper sizes the matrices by the batch)
+        if sd is None or not sd.lsoln:
+            refused(lambda: s.profile_rows(0.5), -5)
+        else:
+            refused(lambda: s.profile_rows(-0.5), -1)
+            refused(lambda: s.profile_rows(float("nan"), nodes), -1)
+    if sd is None:
+        refused(s.baseline_keep, -5)
+    if m.baseline is None:
+        refused(s.baseline_results, -5)
+    if m.baseline is None or sd is None or not sd.lsoln:
+        refused(lambda: s.reorder_hits(0.5), -5)
+        refused(lambda: s.reorder_hits(0.5, 0.0, 7, None, True), -5)
+    else:
+        refused(lambda: s.reorder_hits(0.5, 0.0, 0), -1)
+        refused(lambda: s.reorder_hits(0.5, 0.0, 8), -1)
+        refused(lambda: s.reorder_hits(-0.5), -1)
+        refused(lambda: s.reorder_hits(0.5, -0.5), -1)
+    if m.db is not None and m.batch is not None:
+        refused(lambda: s.search_reordered(3, 1.5), -1)               # before either search: nothing changes
 
 
 @pytest.mark.parametrize("walk", range(hl.WALKS))
@@ -105,13 +177,26 @@ def test_refusals_at_every_step(walk):
         assert follow(s, ops, after_step=refusals) == data_steps(ops)
 
 
+@pytest.mark.parametrize("walk", range(hl.NEW_WALKS))
+def test_refusals_at_every_step_of_a_new_walk(walk):
+    """the same over the second schedule: which accumulator kind is live, whether a baseline or classes are, depends on
+    what the context has been through"""
+    ops = hl.schedule(hl.SEED, False, True)[walk]
+    with sat.Searcher(0) as s:
+        refusals(s, hl.Model())
+        assert follow(s, ops, after_step=refusals) == data_steps(ops)
+
+
 # ---------------------------------------------------------------- 4. budgets that make sizing history-sensitive
 @pytest.mark.parametrize("name,value,walk", [("SAT_EXP_SCRATCH_KB", "16", 1), ("SAT_EXP_SELECT_KEYS", "100", 2),
-                                             ("SAT_EXP_SCRATCH_KB", "16", 13), ("SAT_EXP_SELECT_KEYS", "100", 14)])
+                                             ("SAT_EXP_SCRATCH_KB", "16", 13), ("SAT_EXP_SELECT_KEYS", "100", 14),
+                                             ("SAT_EXP_SELECT_KEYS", "100", -1), ("SAT_EXP_SELECT_KEYS", "100", -2),
+                                             ("SAT_EXP_SCRATCH_KB", "16", -2)])
 def test_walk_under_a_small_budget(monkeypatch, name, value, walk):
     """16 KB of scratch cuts every LSOLN, match and polish pass into launches whose size depends on the slab buffer's
-    capacity; 100 selection keys cut the query list of the selection passes into chunks of 100 / entries queries"""
-    ops = hl.schedule(hl.SEED)[walk]
+    capacity; 100 selection keys cut the query list of the selection passes into chunks of 100 / entries queries - the
+    new result calls go through the same chunk walk (walk < 0: the hand-made walks of the second schedule)"""
+    ops = hl.schedule(hl.SEED)[walk] if walk >= 0 else hl.schedule(hl.SEED, False, True)[walk]
     monkeypatch.setenv(name, value)                                     # read when the context is created
     with sat.Searcher(0) as s:
         assert follow(s, ops) == data_steps(ops)
@@ -133,6 +218,14 @@ def test_shards_grow_shrink_grow(kind, count):
 def test_shards_walk(count, walk):
     walks = hl.schedule(hl.SEED, multi=True)
     assert len(walks) == hl.MULTI_WALKS
+    with shards(count) as s:
+        assert follow(s, walks[walk], multi=True) == data_steps(walks[walk])
+
+
+@pytest.mark.parametrize("count,walk", [(2, 0), (3, 1), (2, hl.NEW_MULTI_WALKS - 2), (3, hl.NEW_MULTI_WALKS - 1)])
+def test_shards_new_walk(count, walk):
+    walks = hl.schedule(hl.SEED, True, True)
+    assert len(walks) == hl.NEW_MULTI_WALKS
     with shards(count) as s:
         assert follow(s, walks[walk], multi=True) == data_steps(walks[walk])
 

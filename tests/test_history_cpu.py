@@ -26,7 +26,7 @@ def sequences():
 @pytest.mark.parametrize("multi,count", [(False, hl.WALKS), (True, hl.MULTI_WALKS)], ids=["one_context", "shards"])
 def test_schedule_covers_every_allowed_pair(multi, count):
     walks = hl.schedule(hl.SEED, multi)
-    kinds = hl.MULTI_KINDS if multi else hl.KINDS
+    kinds = hl.kinds_of(multi)                                                   # the 27 kinds, or the 19 sat_multi has of them
     assert len(walks) == count and all(hl.WALK_STEPS <= len(w) <= hl.WALK_STEPS + 5 for w in walks)
     followed = set()
     for walk in walks:
@@ -101,18 +101,20 @@ def test_grow_shrink_grow_differs_in_every_dimension():
 
 
 # ---------------------------------------------------------------- the model
-FLAGS = ("db", "batch", "searched", "lsoln", "polished", "fit", "cluster", "tops")
+FLAGS = ("db", "batch", "searched", "lsoln", "polished", "fit", "cluster", "tops", "leveled", "cover", "classes", "baseline")
 SEARCH = dict(lorder=True, r=3)
-# what each call drops from a context that has everything: a polished LSOLN search of the batch, a fit, an accumulator,
-# polish-all on (include/satabsearch.h)
+# what each call drops from a context that has everything: a polished LSOLN search of the batch, a fit, an accumulator
+# (plain, or leveled: "leveled" goes with "cluster"), polish-all on, a cover accumulator, classes, a baseline
+# (include/satabsearch.h)
 DROPS = {
-    hl.op("upload", db="d32"): {"searched", "lsoln", "polished", "fit", "cluster"},
-    hl.op("upload_dense", db="d32"): {"searched", "lsoln", "polished", "fit", "cluster"},
-    hl.op("upload_search", db="d32", lsoln=True, **SEARCH): {"fit", "cluster"},
-    hl.op("upload_search", db="d32", lsoln=False, **SEARCH): {"lsoln", "fit", "cluster"},
-    hl.op("set_queries", batch="q2"): {"searched", "lsoln", "polished", "fit"},
-    hl.op("set_query", batch="q1"): {"searched", "lsoln", "polished", "fit"},
-    hl.op("set_queries_from_db", batch=("db", "d16")): {"searched", "lsoln", "polished", "fit"},
+    hl.op("upload", db="d32"): {"searched", "lsoln", "polished", "fit", "cluster", "cover", "classes", "baseline"},
+    hl.op("upload_dense", db="d32"): {"searched", "lsoln", "polished", "fit", "cluster", "cover", "classes", "baseline"},
+    hl.op("upload_search", db="d32", lsoln=True, **SEARCH): {"fit", "cluster", "cover", "classes", "baseline"},
+    hl.op("upload_search", db="d32", lsoln=False, **SEARCH): {"lsoln", "fit", "cluster", "cover", "classes", "baseline"},
+    hl.op("set_queries", batch="q2"): {"searched", "lsoln", "polished", "fit", "baseline"},
+    hl.op("set_query", batch="q1"): {"searched", "lsoln", "polished", "fit", "baseline"},
+    hl.op("set_queries_from_db", batch=("db", "d16")): {"searched", "lsoln", "polished", "fit", "baseline"},
+    hl.op("set_queries_motif", batch=("motif", "d16")): {"searched", "lsoln", "polished", "fit", "baseline"},
     hl.op("set_polish_all", tops=1): set(),
     hl.op("polish_all_off"): {"tops"},
     hl.op("search", lsoln=True, **SEARCH): {"fit"},
@@ -136,26 +138,62 @@ DROPS = {
     hl.op("cluster_add", frac=0.1): set(),
     hl.op("cluster_labels"): set(),
     hl.op("cluster_end"): {"cluster"},
+    hl.op("cluster_begin_levels", levels=3): set(),
+    hl.op("cluster_add_levels"): set(),
+    hl.op("cluster_labels_levels"): set(),
+    hl.op("cover_begin"): set(),
+    hl.op("cover_add", frac=0.1): set(),
+    hl.op("cover_solve"): set(),
+    hl.op("cover_end"): {"cover"},
+    hl.op("set_eval_classes"): set(),
+    hl.op("eval_classes_off"): {"classes"},
+    hl.op("eval_rows", rocn=3): set(),
+    hl.op("eval_tables"): set(),
+    hl.op("profile_rows", frac=0.5, gaps=True): set(),
+    hl.op("baseline_keep"): set(),
+    hl.op("baseline_drop"): {"baseline"},
+    hl.op("baseline_results"): set(),
+    hl.op("reorder_hits", frac=0.5, base_frac=None, kinds=7, k=None, maps=True): set(),
+    hl.op("search_reordered", r=3, censor=0.0): set(),               # polished (the setting is honoured), LSOLN, fitted
+    hl.op("search_reordered", r=3, censor=None): {"fit"},
 }
+# a begin replaces the accumulator of the other kind: the one flag a call of the table turns ON, and the one a plain begin
+# turns off on a context whose accumulator is leveled
+TURNS_ON = {hl.op("cluster_begin_levels", levels=3): {"leveled"}}
+LEVELED_DROPS = {hl.op("cluster_begin"): {"leveled"}}
 
 
-def full_model(multi=False):
+def full_model(multi=False, leveled=False):
+    """a context with everything; its accumulator is plain or leveled, and "leveled" says which"""
     m = hl.Model(multi)
     for o in (hl.op("upload", db="d16"), hl.op("set_queries", batch="q5"), hl.op("set_polish_all", tops=3),
-              hl.op("search", lsoln=True, **SEARCH), hl.op("fit_statistics", censor=0.0), hl.op("cluster_begin")):
+              hl.op("search", lsoln=True, **SEARCH), hl.op("fit_statistics", censor=0.0),
+              hl.op("cluster_begin_levels", levels=3) if leveled else hl.op("cluster_begin"), hl.op("cover_begin"),
+              hl.op("set_eval_classes"), hl.op("baseline_keep")):
         assert m.legal(o.kind)
         m.apply(o)
-    assert m.flags() == (True,) * len(FLAGS)
+    assert m.flags() == tuple(name != "leveled" or leveled for name in FLAGS)
     return m
 
 
 def test_model_follows_the_table_of_dropped_state():
-    assert {o.kind for o in DROPS} == set(hl.KINDS)
+    assert {o.kind for o in DROPS} == set(hl.ALL_KINDS) and set(hl.KINDS) < set(hl.ALL_KINDS)
     for o, drops in DROPS.items():
-        m = full_model()
-        assert m.legal(o.kind), o
-        m.apply(o)
-        assert {name for name, on in zip(FLAGS, m.flags()) if not on} == drops, o
+        checked = 0
+        for leveled in (False, True):
+            m = full_model(leveled=leveled)
+            if not m.legal(o.kind):                    # the add and labels calls of the other accumulator kind
+                assert o.kind in ("cluster_add", "cluster_labels", "cluster_add_levels", "cluster_labels_levels"), o
+                assert leveled != o.kind.endswith("_levels"), o
+                continue
+            m.apply(o)
+            off = set(drops) | ({"leveled"} if not leveled else set())
+            if leveled:
+                off |= LEVELED_DROPS.get(o, set()) | ({"leveled"} if "cluster" in drops else set())
+            off -= TURNS_ON.get(o, set())
+            assert {name for name, on in zip(FLAGS, m.flags()) if not on} == off, (o, leveled)
+            checked += 1
+        assert checked >= 1, o
     # what is installed afterwards
     m = full_model()
     m.apply(hl.op("search_matches", m=3, maps=True, lorder=False, r=1))
@@ -169,10 +207,39 @@ def test_model_follows_the_table_of_dropped_state():
     m = full_model(True)
     m.apply(hl.op("topk_hits", k=3, maps=False))
     assert m.fit is None and m.searched is not None
-    assert not any(m.legal(k) for k in hl.KINDS if k not in hl.MULTI_KINDS)
-    # nothing but the settings is legal on a new context
-    assert sorted(k for k in hl.KINDS if hl.Model().legal(k)) == ["polish_all_off", "set_polish_all", "set_queries", "set_query",
-                                                                 "upload", "upload_dense"]
+    assert not any(m.legal(k) for k in hl.ALL_KINDS if k not in hl.MULTI_KINDS)
+    assert set(hl.ALL_KINDS) - set(hl.MULTI_KINDS) == {"upload_dense", "set_query", "upload_search", "search_async_results", "search_pairs",
+                                                     "results", "results_base", "cluster_end", "cover_end", "eval_tables"}
+    # nothing but the settings (and the two calls that only forget) is legal on a new context
+    assert sorted(k for k in hl.ALL_KINDS if hl.Model().legal(k)) == ["baseline_drop", "eval_classes_off", "polish_all_off", "set_polish_all",
+                                                                     "set_queries", "set_query", "upload", "upload_dense"]
+    # what is installed afterwards, the new state: the baseline is the rows as they were kept
+    m = full_model()
+    kept = (m.searched, m.fit)
+    assert m.baseline == kept and kept == (hl.Searched(True, 3, True, 3), ("fit", 0.0))
+    for o in (hl.op("search", lorder=False, lsoln=True, r=1), hl.op("fit_statistics", censor=0.1), hl.op("polish_all_off"),
+              hl.op("search_pairs", pairs=7, lsoln=True, **SEARCH), hl.op("cluster_begin"), hl.op("cover_add", frac=0.1),
+              hl.op("eval_rows", rocn=3), hl.op("profile_rows", frac=0.5, gaps=False), hl.op("set_statistics", fit="none")):
+        assert m.legal(o.kind), o
+        m.apply(o)
+        assert m.baseline == kept and m.legal("reorder_hits") and m.legal("baseline_results"), o
+    m.apply(hl.op("search", lorder=False, lsoln=False, r=1))
+    assert m.baseline == kept and not m.legal("reorder_hits") and not m.legal("profile_rows") and m.legal("eval_rows")
+    m.apply(hl.op("set_polish_all", tops=1))
+    m.apply(hl.op("search_reordered", r=3, censor=0.1))
+    assert m.baseline == (hl.Searched(True, 3, False, 1), ("fit", 0.1)) and m.fit == ("fit", 0.1)
+    assert m.searched == hl.Searched(False, 3, True, 1) and m.legal("reorder_hits") and m.legal("results_base")
+    # the accumulators: one of a kind, the cover beside it; an upload drops the three and the classes
+    m = full_model()
+    assert m.legal("cluster_add") and not m.legal("cluster_add_levels") and not m.legal("cluster_labels_levels")
+    m.apply(hl.op("cluster_add", frac=0.1))
+    m.apply(hl.op("cluster_begin_levels", levels=3))
+    assert m.cluster[1] == [] and m.legal("cluster_add_levels") and not m.legal("cluster_add") and not m.legal("cluster_labels")
+    assert m.legal("cover_add") and m.legal("cover_solve")
+    m.apply(hl.op("cluster_end"))
+    assert m.cluster is None and m.cover is not None and not m.legal("cluster_labels_levels")
+    m.apply(hl.op("upload", db="d16"))
+    assert not any(m.legal(k) for k in ("cover_solve", "cover_add", "eval_rows", "baseline_results", "cluster_labels"))
 
 
 # ---------------------------------------------------------------- the worlds and their references
@@ -260,3 +327,191 @@ def test_the_reference_cache_keeps_the_cpu_side_short():
             m.apply(o)
     print("%d references of %d walks in %.1f s" % (steps, hl.WALKS, time.time() - started))
     assert steps == sum(1 for w in hl.schedule(hl.SEED) for o in w if o.kind in hl.DATA_KINDS) and steps > 500
+
+
+# ---------------------------------------------------------------- the second schedule: old and new kinds
+def states(walk, multi=False):
+    """(operation, the model before it) along one walk"""
+    m = hl.Model(multi)
+    for o in walk:
+        assert m.legal(o.kind), o
+        yield o, m
+        m = hl._clone(m)
+        m.apply(o)
+
+
+@pytest.mark.parametrize("multi,count,pairs", [(False, hl.NEW_WALKS, 1198), (True, hl.NEW_MULTI_WALKS, 807)], ids=["one_context", "shards"])
+def test_new_schedule_covers_every_allowed_pair_with_a_new_kind(multi, count, pairs):
+    walks = hl.schedule(hl.SEED, multi, True)
+    kinds = hl.kinds_of(multi, True)
+    assert len(walks) == count and all(len(w) <= hl.WALK_STEPS + 10 for w in walks)
+    followed = set()
+    for walk in walks:
+        names = [o.kind for o, _ in states(walk, multi)]
+        followed |= set(zip(names, names[1:]))
+    allowed = hl.allowed_pairs(multi, True)
+    assert len(allowed) == pairs and allowed <= followed, sorted(allowed - followed)[:10]
+    assert all(a in hl.NEW_KINDS or b in hl.NEW_KINDS for a, b in allowed) and {k for p in allowed for k in p} == set(kinds)
+    # the goal is every pair of the model over all kinds that has a new kind in it - not a subset of it
+    everything = hl.allowed_pairs(multi, False) | allowed
+    assert len(everything) == len(hl.allowed_pairs(multi, False)) + pairs
+    for a, b in (("cluster_begin_levels", "cluster_add"), ("cluster_begin", "cluster_labels_levels"), ("upload", "cover_solve"),
+                 ("upload", "eval_rows"), ("set_queries", "baseline_results"), ("set_queries_motif", "reorder_hits"),
+                 ("search_matches", "profile_rows"), ("baseline_drop", "reorder_hits")):
+        assert (a, b) not in allowed, (a, b)
+    for a, b in (("search_reordered", "reorder_hits"), ("search", "reorder_hits"), ("search_pairs_matches", "eval_rows"),
+                 ("set_queries", "cover_solve"), ("set_queries", "cluster_labels_levels"), ("fit_statistics", "baseline_results"),
+                 ("cluster_begin_levels", "cover_add"), ("polish_all_off", "baseline_keep")):
+        assert (a, b) in allowed, (a, b)
+    hl._cache.pop(("schedule", hl.SEED, multi, True))
+    assert hl.schedule(hl.SEED, multi, True) == walks
+    # the first schedule is what it was: its kinds only
+    assert all(o.kind in hl.kinds_of(multi) for w in hl.schedule(hl.SEED, multi) for o in w)
+
+
+def rows_of(m):
+    return len(hl.n1s_of(m.batch)) * len(hl.db(m.db))
+
+
+@pytest.mark.parametrize("multi", [False, True], ids=["one_context", "shards"])
+def test_new_walks_contain_the_named_sequences(multi):
+    found, up, down = collections.Counter(), set(), set()
+    for walk in hl.schedule(hl.SEED, multi, True):
+        since_reordered = since_keep = None             # the kinds run since search_reordered / since a keep under a polished search
+        added, last_rows, since_pairs = {}, {}, False
+        for o, m in states(walk, multi):
+            k = o.kind
+            if k == "reorder_hits":
+                found["a baseline kept across a search"] += since_reordered is not None and "search" in since_reordered
+                found["a baseline of a polished search, the polish then off"] += since_keep is not None and "polish_all_off" in since_keep
+            if k in hl.QUERY_SETTING or k.startswith("upload") or k in ("baseline_drop", "baseline_keep", "search_reordered"):
+                since_reordered = since_keep = None
+            if k == "search_reordered":
+                since_reordered = []
+            elif since_reordered is not None:
+                since_reordered.append(k)
+            if k == "baseline_keep" and m.searched.tops and m.tops:
+                since_keep = []
+            elif since_keep is not None:
+                since_keep.append(k)
+            found["a leveled begin over a live plain accumulator"] += k == "cluster_begin_levels" and m.cluster is not None and not m.leveled()
+            found["a plain begin over a live leveled accumulator"] += k == "cluster_begin" and m.leveled()
+            if k in ("cover_add", "cluster_add_levels"):
+                other = "cluster_add_levels" if k == "cover_add" else "cover_add"
+                found["a cover add and a leveled add from one search"] += added.get(other) == (m.db, m.batch, m.searched, m.fit)
+                added[k] = (m.db, m.batch, m.searched, m.fit)
+            if k in hl.SEARCHES or k in hl.QUERY_SETTING or k.startswith("upload") or k == "search_reordered":
+                since_pairs, added = False, {}
+            if k in hl.PAIR_SEARCHES:
+                since_pairs = True
+            found["eval_rows after a pair search"] += k == "eval_rows" and since_pairs
+            found["profile_rows after a pair search"] += k == "profile_rows" and since_pairs
+            if k in hl.NEW_DATA and m.batch is not None:
+                after = hl._clone(m)
+                after.apply(o)
+                now = rows_of(after)
+                if k in last_rows and now > last_rows[k]:
+                    up.add(k)
+                if k in last_rows and now < last_rows[k]:
+                    down.add(k)
+                last_rows[k] = now
+    for name in ("a baseline kept across a search", "a baseline of a polished search, the polish then off",
+                 "a leveled begin over a live plain accumulator", "a plain begin over a live leveled accumulator",
+                 "a cover add and a leveled add from one search", "eval_rows after a pair search", "profile_rows after a pair search"):
+        assert found[name] >= 1, (name, found)
+    data = {k for k in hl.NEW_DATA if not multi or k in hl.MULTI_KINDS}
+    assert up == data and down == data, (data - up, data - down)      # each on a larger batch behind a smaller one, and the reverse
+
+
+def new_references(kind, multi=False):
+    """(operation, model before it, its reference) of every `kind` step of the two hand-made walks of the second schedule"""
+    for walk in hl.schedule(hl.SEED, multi, True)[-2:]:
+        for o, m in states(walk, multi):
+            if o.kind == kind:
+                yield o, m, hl.expect(o, m)
+
+
+def test_new_references_are_not_vacuous():
+    """conditions on the CPU references alone, of steps the GPU module runs (the hand-made walks: the permutant world and
+    25 / 200 / 25 rows)"""
+    reorder_lib, select_lib = hl.reorder_lib, hl.select_lib
+    # reorder_hits: one reference with sequential, circular and permuted rows, a query with none, and a min_base_pvalue that
+    # removes some of the rows the same call returns without it, but not all
+    shown = False
+    for o, m, (counts, rows, *_) in new_references("reorder_hits"):
+        a = dict(o.args)
+        if a["base_frac"] is None or a["k"] or a["kinds"] != 7:
+            continue
+        w = m.world()
+        free = sum(len(r) for r in w.reorder(m.searched, m.fit, m.baseline, w.pcut(m.searched, m.fit, a["frac"]), 0.0, 7, None)[0])
+        shown |= (set(rows["kind"].tolist()) == {reorder_lib.SEQ, reorder_lib.CIRC, reorder_lib.PERM} and (counts == 0).any()
+                  and 0 < len(rows) < free and bool((rows["base_pvalue"] > rows["hit"]["pvalue"]).any()))
+    assert shown
+    # eval_rows: positives and negatives, an unclassified query, and a tie group of negatives that straddles the rocn cut
+    shown = False
+    for o, m, (rows,) in new_references("eval_rows"):
+        w, rocn, cl, nodes = m.world(), dict(o.args)["rocn"], hl.classes(m.db), m.query_nodes()
+        straddles = False
+        for q, node in enumerate(nodes):
+            if cl[node] >= 0:
+                counted = (cl >= 0) & (np.arange(w.n) != node) & (cl != cl[node])
+                neg = np.sort(w.matrix(m.searched)[0][q][counted])[::-1]
+                straddles |= len(neg) > rocn and neg[rocn - 1] == neg[rocn]
+        shown |= (straddles and bool(((rows["positives"] > 0) & (rows["negatives"] > 0)).any()) and bool((rows["query_class"] == -1).any())
+                  and bool((rows["t2"] > 0).any()))
+    assert shown
+    # cover_solve: two rounds at least, and representatives that are not the single-linkage labels of the same edges
+    shown = False
+    for o, m, (rep, deg, counts) in new_references("cover_solve"):
+        ea, eb = hl._added_edges(m.cover[1])
+        shown |= counts[1] >= 2 and not np.array_equal(rep, select_lib.components(m.cover[0], ea, eb))
+    assert shown
+    # cluster_labels_levels: two levels with different labels; the cutoffs ascend strictly
+    shown = False
+    for o, m, (labels, deg, edges) in new_references("cluster_labels_levels"):
+        cuts = hl.level_cuts(*m.cluster[2])
+        assert len(cuts) == len(labels) and all(a < b for a, b in zip(cuts, cuts[1:])) and 0.0 < cuts[0] and cuts[-1] < 1.0
+        shown |= len(labels) >= 2 and any(not np.array_equal(labels[j], labels[j + 1]) for j in range(len(labels) - 1)) and edges[0] < edges[-1]
+    assert shown
+    assert {len(hl.level_cuts("d32", n)) for n in (1, 3, hl.MAX_LEVELS)} == {1, 3, hl.MAX_LEVELS}
+    # profile_rows: hits, and a pair of SSEs matched together less often than either alone; packed and with gaps
+    shown, gaps = False, set()
+    for o, m, (hits, packed) in new_references("profile_rows"):
+        w = m.world()
+        offset, words = hl.profile_offsets(w.n1s, dict(o.args)["gaps"])
+        gaps.add(dict(o.args)["gaps"])
+        assert len(packed) == words and (not dict(o.args)["gaps"] or (packed == hl.PROFILE_FILL).sum() >= 5 * w.nq)
+        for q, n1 in enumerate(w.n1s):
+            j = packed[offset[q]:offset[q] + n1 * n1].reshape(n1, n1)
+            shown |= hits[q] > 0 and bool((j < np.diag(j)[:, None]).any())
+    assert shown and gaps == {False, True}
+    # a motif batch whose list is not ascending, one that is the whole entry, and every n1 is the list's length
+    lists = hl.motif_lists("dperm")
+    assert any(l is not None and list(l) != sorted(l) for l in lists) and any(l is None for l in lists)
+    assert [len(q[2]) for q in hl.batch(("motif", "dperm"))[0]] == [
+        len(l) if l is not None else int(hl.db("dperm").orders[e]) for l, e in zip(lists, hl.db_indices("dperm"))]
+    # the classification: implants by their source, unclassified entries, and both in every database
+    for name in hl.NEW_COMBOS:
+        c = hl.classes(name)
+        assert (c == -1).any() and all(c[e] == s[1] for e, s in hl.IMPLANTS[name].items()) and len(set(c.tolist())) >= 4
+    assert len(hl.db("dperm")) == 30 and int(hl.db("dperm").orders.max()) == 32
+    # search_reordered: its baseline differs from its searched state, and a fitted p-value differs from the built-in one
+    for o, m, ref in new_references("search_reordered"):
+        sc, base_sc, base_p, rows = ref[0], ref[2], ref[3], ref[4]
+        assert (sc != base_sc).any()
+    # baseline_results as kept under one fit and read under another: the p-values are those of keep time
+    assert any(m.baseline[1] != m.fit or m.baseline[0] != m.searched for _, m, _ in new_references("baseline_results"))
+
+
+def test_the_reference_cache_keeps_the_new_cpu_side_short():
+    """every reference of every walk of the second schedule, computed once (the figure is printed, not asserted)"""
+    started, steps = time.time(), 0
+    for walk in hl.schedule(hl.SEED, False, True):
+        for o, m in states(walk):
+            if o.kind in hl.DATA_KINDS:
+                got = hl.expect(o, m)
+                assert hl.expect(o, m) is got
+                steps += 1
+    print("%d references of %d walks in %.1f s" % (steps, hl.NEW_WALKS, time.time() - started))
+    assert steps == sum(1 for w in hl.schedule(hl.SEED, False, True) for o in w if o.kind in hl.DATA_KINDS) and steps > 800
+    assert {o.kind for w in hl.schedule(hl.SEED, False, True) for o in w} == set(hl.ALL_KINDS)
