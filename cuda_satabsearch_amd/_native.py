@@ -45,6 +45,8 @@ ABI_SYMBOLS = (
     "sat_baseline_keep", "sat_baseline_drop", "sat_baseline_results", "sat_reorder_hits", "sat_search_reordered",
     "sat_multi_baseline_keep", "sat_multi_baseline_drop", "sat_multi_baseline_results", "sat_multi_reorder_hits",
     "sat_multi_search_reordered",
+    "sat_search_exact", "sat_exact_results", "sat_exact_stats",
+    "sat_multi_search_exact", "sat_multi_exact_results", "sat_multi_exact_stats",
 )
 
 MAX_CLUSTER_LEVELS = 8
@@ -54,6 +56,9 @@ COVER_ROUND_BATCH = 64
 EVAL_BLOCK_ROWS = 4096
 EVAL_WINDOW_BINS = 2048
 STAT_BINS = 4096
+# SAT_EXACT_MAX_QUERY and SAT_EXACT_DEFAULT_NODES of include/satabsearch.h
+EXACT_MAX_QUERY = 16
+EXACT_DEFAULT_NODES = 1 << 18
 STAT_BINS_PER_UNIT = 256
 
 
@@ -83,6 +88,12 @@ class Eval(C.Structure):
     """struct sat_eval of include/satabsearch.h (sat_eval_row of csrc/host/sat_eval.h)"""
     _fields_ = [("u2", C.c_uint64), ("t2", C.c_uint64), ("positives", C.c_int32), ("negatives", C.c_int32),
                 ("n_used", C.c_int32), ("query_class", C.c_int32)]
+
+
+class ExactStat(C.Structure):
+    """struct sat_exact_stat of include/satabsearch.h, 40 bytes"""
+    _fields_ = [("rows", C.c_int64), ("proven", C.c_int64), ("improved", C.c_int64), ("gain", C.c_int64),
+                ("nodes", C.c_uint64)]
 
 
 class StructSetC(C.Structure):
@@ -244,6 +255,14 @@ def device_lib():
             lib.sat_search_reordered.argtypes = [C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_double)]
             lib.sat_multi_search_reordered.argtypes = lib.sat_search_reordered.argtypes
             lib.sat_debug_baseline_shape.argtypes = [C.c_void_p, C.c_int, C.c_int]        # include/satabsearch_debug.h
+        # (as above: a build of the parent commit predates the exact search)
+        if hasattr(lib, "sat_search_exact"):
+            lib.sat_search_exact.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_ulonglong, C.POINTER(C.c_double)]
+            lib.sat_exact_results.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.sat_exact_stats.argtypes = [C.c_void_p, C.c_void_p]
+            lib.sat_multi_search_exact.argtypes = lib.sat_search_exact.argtypes
+            lib.sat_multi_exact_results.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.sat_multi_exact_stats.argtypes = [C.c_void_p, C.c_void_p]
         lib.sat_hits_cutoff.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         lib.sat_multi_search_cutoff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                                 C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
@@ -320,6 +339,8 @@ def host_lib():
         lib.sat_profile_core.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
         lib.sat_map_kind.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.sat_map_kind.restype = C.c_int32
+        lib.sat_exact_host.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_int32, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _host = lib
     return _host
 

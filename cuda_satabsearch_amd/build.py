@@ -3,7 +3,7 @@
     python -m cuda_satabsearch_amd.build [--oracle] [--ref]
 
 * libsatabsearch.so   HIP kernels + C ABI (include/satabsearch.h), hipcc --offload-arch=gfx950
-* libsathost.so       host-only C: ASCII reader, Gumbel statistics, shard cuts, cluster tables, AUC / ROC-n, greedy cover, profile core, map order (csrc/host/)
+* libsathost.so       host-only C: ASCII reader, Gumbel statistics, shard cuts, cluster tables, AUC / ROC-n, greedy cover, profile core, map order, exact-search twin (csrc/host/)
 * bin/satabsearch     the command line (csrc/host/sat_main.c), links both
 
 `--oracle` additionally runs oracle/Makefile (test infrastructure, never linked into
@@ -42,7 +42,7 @@ def _stale(target, sources):
 # of them: the library, its diagnostic twin, the Makefile and scripts/exp/variant_lib.sh all build from it.
 DEVICE_SOURCES = ("sat_launch.hip", "sat_capi.hip", "sat_pairs.hip", "sat_db.hip", "sat_topk.hip", "sat_multi.hip",
                   "sat_polish.hip", "sat_qfromdb.hip", "sat_cluster.hip", "sat_eval.hip", "sat_cover.hip", "sat_profile.hip",
-                  "sat_reorder.hip")
+                  "sat_reorder.hip", "sat_exact.hip")
 # sat_launch.hip and what it includes from csrc/ (diag/ apart, which only -DSAT_DIAG builds read)
 KERNEL_SOURCES = ("sat_sa_kernel.hpp", "sat_sa_body.inc", "sat_launch.hpp", "sat_launch.hip")
 HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "-I", INC, "-I", CSRC]
@@ -88,9 +88,9 @@ def include_closure(src):
 def build_host(force=False):
     out = os.path.join(PKG, "libsathost.so")
     srcs = [os.path.join(HOST, f) for f in ("sat_parse.c", "sat_gumbel.c", "sat_shard.c", "sat_cluster.c", "sat_eval.c", "sat_cover.c",
-                                            "sat_profile.c", "sat_reorder.c")]
+                                            "sat_profile.c", "sat_reorder.c", "sat_exact.c")]
     deps = srcs + [os.path.join(HOST, f) for f in ("sat_parse.h", "sat_gumbel.h", "sat_stats.h", "sat_shard.h", "sat_cluster.h", "sat_eval.h",
-                                                "sat_cover.h", "sat_profile.h", "sat_reorder.h")]
+                                                "sat_cover.h", "sat_profile.h", "sat_reorder.h", "sat_exact.h")]
     if force or _stale(out, deps):
         _run([CC, "-O2", "-fPIC", "-shared", "-Wall", "-Wextra", "-I", HOST, "-o", out] + srcs + ["-lm", "-lpthread"])
     return out

@@ -254,6 +254,7 @@ int launch_search(sat_ctx *ctx, int lorder, int lsoln, int maxstart, hipStream_t
     ctx->searched_nq = ctx->queries.size();
     ctx->searched_lsoln = lsoln != 0;
     ctx->searched_polished = false;
+    ctx->searched_exact = false;
     ctx->fits.clear();                                   // a fit belongs to the scores it was made from
     ctx->last_launch_info.clear();
     for (size_t i = 0; i < plan.size(); i++) {
@@ -359,7 +360,8 @@ sat_ctx *sat_ctx_create(int device, uint64_t seed)
         if ((rc_load = sat_db_load_code(ctx)) != SAT_OK || (rc_load = sa_load_code()) != SAT_OK ||
             (rc_load = sat_pairs_load_code(ctx)) != SAT_OK || (rc_load = sat_cluster_load_code(ctx)) != SAT_OK ||
             (rc_load = sat_eval_load_code(ctx)) != SAT_OK || (rc_load = sat_cover_load_code(ctx)) != SAT_OK ||
-            (rc_load = sat_profile_load_code(ctx)) != SAT_OK || (rc_load = sat_reorder_load_code(ctx)) != SAT_OK)
+            (rc_load = sat_profile_load_code(ctx)) != SAT_OK || (rc_load = sat_reorder_load_code(ctx)) != SAT_OK ||
+            (rc_load = sat_exact_load_code(ctx)) != SAT_OK)
             return rc_load;
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         return build_gumbel_tables(ctx);

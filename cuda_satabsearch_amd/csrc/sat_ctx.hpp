@@ -154,6 +154,7 @@ struct sat_ctx {
     size_t searched_nq = 0;                  // 0 = no search since the last upload / query change
     bool searched_lsoln = false;
     bool searched_polished = false;          // the last search was a polished one: d_base holds its rows' base scores
+    bool searched_exact = false;             // the last search was an exact one (sat_search_exact): d_xbase, d_xflag, d_xnodes hold its rows'
     // whole-database polish (sat_polish_all_set): 0 = off, else the maps polished per row.  A setting of the context,
     // like its stream: uploads and query changes leave it alone.
     int polish_all = 0;
@@ -261,6 +262,13 @@ struct sat_ctx {
     // the selection's rows (sat_reorder_hit) before they leave; scratch that only grows
     DevBuf<sat_reorder_hit> d_reorder_rows;
 
+    // exact search (sat_search_exact, sat_exact.hip): every row's incumbent score, laid out as d_scores; its
+    // "unproven" flag and its node count; the per-query statistics before they leave.  The buffers only grow.
+    DevBuf<int32_t> d_xbase;
+    DevBuf<uint8_t> d_xflag;
+    DevBuf<uint32_t> d_xnodes;
+    DevBuf<sat_exact_stat> d_xstats;
+
     // bytes copied device -> host by this context's result calls (sat_stat_d2h_bytes)
     unsigned long long d2h_bytes = 0;
     // bytes copied host -> device by sat_queries_set / sat_queries_from_db (sat_stat_query_h2d_bytes)
@@ -296,6 +304,14 @@ int sat_profile_load_code(sat_ctx *ctx);
 
 // ---- sat_reorder.hip.  Load that file's code object (an empty launch of a small kernel).
 int sat_reorder_load_code(sat_ctx *ctx);
+
+// ---- sat_exact.hip.  Load that file's code object (an empty launch of a small kernel); and for sat_multi_search_exact:
+// the refusals of sat_search_exact (all SAT_EINVAL, nothing queued or changed), the incumbent search and the proof pass
+// queued on the context's stream, and the check that the last search was an exact one.
+int sat_exact_load_code(sat_ctx *ctx);
+int sat_exact_check(const sat_ctx *ctx, int maxstart, unsigned long long max_nodes);
+int sat_exact_launch(sat_ctx *ctx, int lorder, int maxstart, unsigned long long max_nodes);
+int sat_exact_check_state(const sat_ctx *ctx);
 
 // ---- sat_qfromdb.hip, for sat_multi_queries_from_db.  sat_queries_from_db on one shard's context, every check made by
 // the caller: query q has order n1s[q] and is entry code[q] >= 0 of this shard, or code[q] = -query_n1p(n1s[q]): a

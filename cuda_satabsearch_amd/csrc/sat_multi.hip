@@ -895,6 +895,73 @@ int sat_multi_search_only(sat_multi *m, int lorder, int lsoln, int maxstart, dou
     return SAT_OK;
 }
 
+int sat_multi_search_exact(sat_multi *m, int lorder, int maxstart, unsigned long long max_nodes, double *wall_ms)
+{
+    SAT_TRY(sat_check_context(m));
+    if (m->begin.empty()) return sat_fail(SAT_EINVAL, "exact search: no database uploaded");
+    // the refusals of sat_search_exact, made for all shards before the first one works
+    for (sat_ctx *c : m->ctx) SAT_TRY(sat_exact_check(c, maxstart, max_nodes));
+    const Stopwatch clock;
+    SAT_TRY(each_shard(m, [&](int g) { return sat_exact_launch(m->ctx[(size_t)g], lorder, maxstart, max_nodes); }));
+    // no gather: each shard's rows stay where they are
+    SAT_TRY(each_shard(m, [&](int g) { return sat_sync(m->ctx[(size_t)g]); }));
+    clock.stop(wall_ms);
+    return SAT_OK;
+}
+
+int sat_multi_exact_results(sat_multi *m, int32_t *scores, int32_t *ssemaps, int32_t *base_scores, uint8_t *unproven, uint32_t *nodes)
+{
+    SAT_TRY(sat_check_context(m));
+    for (sat_ctx *c : m->ctx) SAT_TRY(sat_exact_check_state(c));
+    // each shard's [nq][its entries] rows into the columns of its entries
+    const size_t nq = m->ctx[0]->queries.size(), total = (size_t)m->n_entries;
+    std::vector<int32_t> s, mp, b;
+    std::vector<uint8_t> f;
+    std::vector<uint32_t> nd;
+    for (int g = 0; g < m->ndev; g++) {
+        const size_t ng = (size_t)(m->begin[(size_t)g + 1] - m->begin[(size_t)g]), at = (size_t)m->begin[(size_t)g];
+        if (scores || ssemaps) s.resize(nq * ng);
+        if (ssemaps) mp.resize(nq * ng * SAT_MAXDIM);
+        if (base_scores) b.resize(nq * ng);
+        if (unproven) f.resize(nq * ng);
+        if (nodes) nd.resize(nq * ng);
+        if (scores || ssemaps) {
+            if (ssemaps) std::fill(mp.begin(), mp.end(), -1);
+            SAT_TRY(sat_results(m->ctx[(size_t)g], ssemaps ? 1 : 0, s.data(), ssemaps ? mp.data() : nullptr));
+        }
+        SAT_TRY(sat_exact_results(m->ctx[(size_t)g], base_scores ? b.data() : nullptr, unproven ? f.data() : nullptr, nodes ? nd.data() : nullptr));
+        for (size_t q = 0; q < nq; q++) {
+            if (scores) std::copy(s.begin() + q * ng, s.begin() + (q + 1) * ng, scores + q * total + at);
+            if (ssemaps) std::copy(mp.begin() + q * ng * SAT_MAXDIM, mp.begin() + (q + 1) * ng * SAT_MAXDIM, ssemaps + (q * total + at) * SAT_MAXDIM);
+            if (base_scores) std::copy(b.begin() + q * ng, b.begin() + (q + 1) * ng, base_scores + q * total + at);
+            if (unproven) std::copy(f.begin() + q * ng, f.begin() + (q + 1) * ng, unproven + q * total + at);
+            if (nodes) std::copy(nd.begin() + q * ng, nd.begin() + (q + 1) * ng, nodes + q * total + at);
+        }
+    }
+    return SAT_OK;
+}
+
+int sat_multi_exact_stats(sat_multi *m, sat_exact_stat *per_query)
+{
+    SAT_TRY(sat_check_context(m));
+    for (sat_ctx *c : m->ctx) SAT_TRY(sat_exact_check_state(c));
+    if (!per_query) return sat_fail(SAT_EINVAL, "per_query buffer is null");
+    const size_t nq = m->ctx[0]->queries.size();
+    std::vector<sat_exact_stat> part(nq);
+    std::fill(per_query, per_query + nq, sat_exact_stat{ 0, 0, 0, 0, 0 });
+    for (int g = 0; g < m->ndev; g++) {
+        SAT_TRY(sat_exact_stats(m->ctx[(size_t)g], part.data()));
+        for (size_t q = 0; q < nq; q++) {                // integer sums: any order
+            per_query[q].rows += part[q].rows;
+            per_query[q].proven += part[q].proven;
+            per_query[q].improved += part[q].improved;
+            per_query[q].gain += part[q].gain;
+            per_query[q].nodes += part[q].nodes;
+        }
+    }
+    return SAT_OK;
+}
+
 int sat_multi_cluster_begin(sat_multi *m)
 {
     SAT_TRY(check_multi(m));

@@ -545,6 +545,7 @@ int sat_polish_all_launch(sat_ctx *ctx, int lorder, int lsoln, int maxstart)
     ctx->searched_nq = nq;
     ctx->searched_lsoln = lsoln != 0;
     ctx->searched_polished = true;
+    ctx->searched_exact = false;
     ctx->fits.clear();                                   // a fit belongs to the scores it was made from
     return SAT_OK;
 }

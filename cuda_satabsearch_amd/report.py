@@ -272,3 +272,16 @@ def reorder_table(names, rows, maps, n1, min_base_pvalue, kinds, base_fit=None):
             if j >= 0:
                 out.append("%3d %3d" % (i + 1, j + 1))
     return out
+
+
+def exact_table(stats, names=None):
+    """The statistics of an exact search (Searcher.exact_stats) as text lines: per query its rows, the rows proven
+    optimal, the rows the proof pass improved, the mean gain of an improved row and the nodes a row.  names: the queries'
+    names (default: their positions)."""
+    lines = ["# query rows proven improved mean_gain nodes_per_row"]
+    for q, s in enumerate(stats):
+        rows, improved = int(s["rows"]), int(s["improved"])
+        lines.append("%s %d %d %d %.3f %.1f" % (names[q] if names is not None else str(q), rows, int(s["proven"]), improved,
+                                              int(s["gain"]) / improved if improved else 0.0,
+                                              int(s["nodes"]) / rows if rows else 0.0))
+    return lines

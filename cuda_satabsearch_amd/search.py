@@ -126,6 +126,8 @@ _REORDER_DTYPE = np.dtype([("hit", _HIT_DTYPE), ("base_pvalue", np.float64), ("b
 assert _REORDER_DTYPE.itemsize == C.sizeof(_native.ReorderHit) == 64
 KIND_SEQUENTIAL, KIND_CIRCULAR, KIND_PERMUTED, KIND_ALL = 1, 2, 4, 7
 
+_EXACT_STAT_DTYPE = np.dtype([("rows", np.int64), ("proven", np.int64), ("improved", np.int64), ("gain", np.int64),
+                              ("nodes", np.uint64)])
 _FIT_DTYPE = np.dtype([("a", np.float64), ("b", np.float64), ("rows", np.int32), ("censored", np.int32),
                        ("below", np.int32), ("fitted", np.int32)], align=True)
 assert _FIT_DTYPE.itemsize == C.sizeof(_native.Fit)
@@ -528,6 +530,36 @@ class Searcher:
         return _search_refine_polish(self, lambda h, m, f, b: self._lib.sat_search_refine_polish(
             self._ctx, int(bool(lorder)), int(bool(lsoln)), int(maxstart), int(candidates), int(refine_maxstart), int(tops),
             int(k), h, m, f, b), k, candidates, refine_maxstart, lsoln)
+
+    def search_exact(self, lorder=True, maxstart=DEFAULT_MAXSTART, max_nodes=_native.EXACT_DEFAULT_NODES):
+        """Exact search for queries of up to 16 SSEs (sat_search_exact): the search this searcher's settings make gives
+        every row an incumbent, then a branch and bound on the GPU proves every row optimal or replaces it by a strictly
+        better map, within max_nodes nodes a row.  Returns (scores, ssemaps, kernel_ms) shaped like search(lsoln=True);
+        the rows stand in the ordinary buffers, so results, topk_hits, hits_cutoff and the rest work on them.
+        exact_results() has the base scores, the unproven flags and the node counts."""
+        ms = C.c_double(0.0)
+        self._check(self._lib.sat_search_exact(self._ctx, int(bool(lorder)), int(maxstart), int(max_nodes), C.byref(ms)))
+        scores, maps = self.results(lsoln=True)
+        return scores, maps, ms.value
+
+    def exact_results(self):
+        """(base_scores int32, unproven bool, nodes uint32) of the last exact search, shaped like results()' scores
+        (sat_exact_results).  Raises unless the last search was an exact one."""
+        nq = getattr(self, "n_queries", 1)
+        base = np.empty((nq, self.n_entries), np.int32)
+        flag = np.empty((nq, self.n_entries), np.uint8)
+        nodes = np.empty((nq, self.n_entries), np.uint32)
+        self._check(self._lib.sat_exact_results(self._ctx, base.ctypes.data, flag.ctypes.data, nodes.ctypes.data))
+        if not getattr(self, "_batch", False):
+            return base[0], flag[0].astype(bool), nodes[0]
+        return base, flag.astype(bool), nodes
+
+    def exact_stats(self):
+        """Per query of the last exact search, reduced on the device (sat_exact_stats): a structured array [nq] with
+        rows, proven, improved, gain (the summed score - base) and nodes."""
+        stats = np.zeros(getattr(self, "n_queries", 1), _EXACT_STAT_DTYPE)
+        self._check(self._lib.sat_exact_stats(self._ctx, stats.ctypes.data))
+        return stats
 
     def set_polish_all(self, tops):
         """Whole-database polish (sat_polish_all_set): with tops in 1..8 every plain whole-database search of this
@@ -1024,6 +1056,31 @@ class MultiSearcher:
         ms = C.c_double(0.0)
         self._check(self._lib.sat_multi_search_only(self._m, int(bool(lorder)), int(bool(lsoln)), int(maxstart), C.byref(ms)))
         return ms.value
+
+    def search_exact(self, lorder=True, maxstart=DEFAULT_MAXSTART, max_nodes=_native.EXACT_DEFAULT_NODES):
+        """Searcher.search_exact on every shard; the rows stay on the shards (sat_multi_search_exact).  Returns wall_ms;
+        exact_results() brings the rows back."""
+        ms = C.c_double(0.0)
+        self._check(self._lib.sat_multi_search_exact(self._m, int(bool(lorder)), int(maxstart), int(max_nodes), C.byref(ms)))
+        return ms.value
+
+    def exact_results(self, maps=True):
+        """The whole database's rows of the last exact search in file order (sat_multi_exact_results): (scores int32[nq, N],
+        ssemaps int32[nq, N, 111] or None, base_scores int32[nq, N], unproven bool[nq, N], nodes uint32[nq, N]) - what one
+        Searcher holding the whole database returns."""
+        shape = (self.n_queries, self.n_entries)
+        scores, base = np.empty(shape, np.int32), np.empty(shape, np.int32)
+        flag, nodes = np.empty(shape, np.uint8), np.empty(shape, np.uint32)
+        ssemaps = np.full(shape + (MAXDIM,), -1, np.int32) if maps else None
+        self._check(self._lib.sat_multi_exact_results(self._m, scores.ctypes.data, ssemaps.ctypes.data if maps else None,
+                                                      base.ctypes.data, flag.ctypes.data, nodes.ctypes.data))
+        return scores, ssemaps, base, flag.astype(bool), nodes
+
+    def exact_stats(self):
+        """Searcher.exact_stats summed over the shards (sat_multi_exact_stats)."""
+        stats = np.zeros(self.n_queries, _EXACT_STAT_DTYPE)
+        self._check(self._lib.sat_multi_exact_stats(self._m, stats.ctypes.data))
+        return stats
 
     def cluster_begin(self):
         """Searcher.cluster_begin on every shard, over the whole database's nodes (sat_multi_cluster_begin)."""

@@ -905,6 +905,63 @@ int sat_multi_reorder_hits(sat_multi *m, double max_pvalue, double min_base_pval
 int sat_multi_search_reordered(sat_multi *m, int maxstart, double censor, double *wall_ms);
 
 /*
+ * Exact search for small queries: every row's score proven optimal, or improved, by a depth-first branch
+ * and bound on the GPU behind the ordinary search.  No command-line option: the C ABI and the Python classes only.
+ *
+ * A feasible map of a query into an entry is a partial injective map between SSEs of equal type, under lorder with
+ * images ascending in the query index; its score is the objective the search maximises (the reference's tmscord, K.cu:
+ * 396-440): the sum of the pair terms of its matched pairs.  Every map the search or the polish reports is feasible; the
+ * empty map scores 0.
+ *
+ * sat_search_exact   (1) the search the context's settings make, with lsoln (polished where sat_polish_all_set is on):
+ *                    its rows are the incumbents, their scores the BASE scores.  (2) The proof pass: for every row a walk
+ *                    over the feasible maps - query SSEs in index order, for each the allowed db SSEs ascending, then
+ *                    "unmatched" -, a node (one such extension evaluated) pruned when its partial score plus an
+ *                    admissible bound does not exceed max(incumbent, best found so far in its unit).  A row changes only
+ *                    when a map STRICTLY better than the incumbent is found: otherwise its score and map are the
+ *                    incumbent's byte for byte.  A row's parallel units are its top-level subtrees (the image of query SSE
+ *                    0: n2 + 1 of them); among better maps of equal score each unit keeps its first, the lowest unit wins.
+ *                    max_nodes, 1 .. 2^32 (SAT_EXACT_DEFAULT_NODES), bounds the nodes of one row: split evenly over its
+ *                    units, a unit that spends its share stops and the row is flagged UNPROVEN - its score is then the
+ *                    best feasible score known, a lower bound >= base.  A unit prunes with the incumbent and its own best
+ *                    only, so score, map, flag and node count of a row depend on (query, entry, lorder, maxstart, seed,
+ *                    polish setting, max_nodes) alone: not on the run, the launch cuts, SAT_EXP_* or the sharding.
+ *                    Afterwards the context is in the state sat_search with lsoln leaves: scores and maps stand in the
+ *                    ordinary buffers, fits are dropped, and sat_results, sat_topk_hits, sat_hits_cutoff,
+ *                    sat_score_histogram / sat_stats_fit, the cluster, cover, eval and profile calls and
+ *                    sat_baseline_keep work on the exact rows.  *kernel_ms (may be NULL): both parts' time on the stream.
+ *                    Refusals, all SAT_EINVAL with a message, before anything is queued and with the searched state
+ *                    unchanged: no database, no query, maxstart < 1, max_nodes outside 1 .. 2^32, a query of more than
+ *                    SAT_EXACT_MAX_QUERY SSEs anywhere in the batch (either lorder).  Entries may have any order.
+ * sat_exact_results  per row, laid out [n_queries][n_entries]; any pointer may be NULL: the base score, the unproven
+ *                    flag (0 / 1), the nodes expanded (saturating at 2^32 - 1).  SAT_EINVAL unless the last search was
+ *                    an exact one.
+ * sat_exact_stats    per query, reduced on the device, 40 bytes a query back: rows, proven rows, improved rows
+ *                    (score > base), the summed gain score - base, the summed nodes.
+ * sat_multi_*        the same over every shard, rows left on the shards (as sat_multi_search_only); every refusal is made
+ *                    for every shard before the first one works.  sat_multi_exact_results returns the whole database's
+ *                    rows in file order - scores, ssemaps ([n_queries][n_entries][SAT_MAXDIM]) and the three arrays of
+ *                    sat_exact_results, any pointer NULL - bit-equal to one context holding the whole database;
+ *                    sat_multi_exact_stats sums the shards' statistics.
+ */
+#define SAT_EXACT_MAX_QUERY      16
+#define SAT_EXACT_DEFAULT_NODES  (1ull << 18)
+typedef struct sat_exact_stat {
+    int64_t  rows;          /* rows of the query: the resident entries                 */
+    int64_t  proven;        /* rows whose walk finished within max_nodes              */
+    int64_t  improved;      /* rows with score > base                                  */
+    int64_t  gain;          /* sum of score - base                                     */
+    uint64_t nodes;         /* sum of the rows' node counts                            */
+} sat_exact_stat;           /* 40 bytes */
+int sat_search_exact(sat_ctx *ctx, int lorder, int maxstart, unsigned long long max_nodes, double *kernel_ms);
+int sat_exact_results(sat_ctx *ctx, int32_t *base_scores, uint8_t *unproven, uint32_t *nodes);
+int sat_exact_stats(sat_ctx *ctx, sat_exact_stat *per_query);
+int sat_multi_search_exact(sat_multi *m, int lorder, int maxstart, unsigned long long max_nodes, double *wall_ms);
+int sat_multi_exact_results(sat_multi *m, int32_t *scores, int32_t *ssemaps, int32_t *base_scores, uint8_t *unproven,
+                            uint32_t *nodes);
+int sat_multi_exact_stats(sat_multi *m, sat_exact_stat *per_query);
+
+/*
  * Time `repeats` back-to-back searches with HIP events on the launch stream
  * (inputs resident, no copies inside the window).  Returns total milliseconds
  * in *total_ms and the dominant SA kernel's summed device time in *kernel_ms.
