@@ -7,8 +7,8 @@
 # The sources, flags and dependencies of all three are cuda_satabsearch_amd/build.py's alone (DEVICE_SOURCES: one object
 # per translation unit of the device library, re-made only when it or a header it includes changed: sat_launch.hip,
 # sat_capi.hip, sat_pairs.hip, sat_db.hip, sat_topk.hip, sat_multi.hip, sat_polish.hip, sat_qfromdb.hip,
-# sat_cluster.hip, sat_eval.hip, sat_cover.hip, sat_profile.hip, sat_reorder.hip, sat_exact.hip; the host library's
-# plain-C files, csrc/host/sat_exact.c among them, are build_host's list there).
+# sat_cluster.hip, sat_eval.hip, sat_cover.hip, sat_profile.hip, sat_reorder.hip, sat_exact.hip, sat_reach.hip; the host
+# library's plain-C files, csrc/host/sat_exact.c and csrc/host/sat_reach.c among them, are build_host's list there).
 PKG      = cuda_satabsearch_amd
 
 all:

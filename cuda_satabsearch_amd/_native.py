@@ -47,6 +47,9 @@ ABI_SYMBOLS = (
     "sat_multi_search_reordered",
     "sat_search_exact", "sat_exact_results", "sat_exact_stats",
     "sat_multi_search_exact", "sat_multi_exact_results", "sat_multi_exact_stats",
+    "sat_reach_begin", "sat_reach_add", "sat_reach_frontier", "sat_reach_rows", "sat_reach_end", "sat_search_reach",
+    "sat_multi_reach_begin", "sat_multi_reach_add", "sat_multi_reach_frontier", "sat_multi_reach_rows",
+    "sat_multi_reach_end", "sat_multi_search_reach",
 )
 
 MAX_CLUSTER_LEVELS = 8
@@ -60,6 +63,11 @@ STAT_BINS = 4096
 EXACT_MAX_QUERY = 16
 EXACT_DEFAULT_NODES = 1 << 18
 STAT_BINS_PER_UNIT = 256
+# the key of the transitive search (csrc/host/sat_reach.h) and the stop reasons of sat_search_reach
+REACH_UNREACHED = 0xFFFFFFFFFFFFFFFF
+REACH_NO_PARENT = 0x7FFFFFF
+REACH_MAX_DEPTH = 62
+REACH_EXHAUSTED, REACH_DEPTH, REACH_BUDGET = 0, 1, 2
 
 
 class SatError(RuntimeError):
@@ -94,6 +102,18 @@ class ExactStat(C.Structure):
     """struct sat_exact_stat of include/satabsearch.h, 40 bytes"""
     _fields_ = [("rows", C.c_int64), ("proven", C.c_int64), ("improved", C.c_int64), ("gain", C.c_int64),
                 ("nodes", C.c_uint64)]
+
+
+class ReachRow(C.Structure):
+    """struct sat_reach_row of include/satabsearch.h (sat_reach_rec of csrc/host/sat_reach.h), 20 bytes"""
+    _fields_ = [("node", C.c_int32), ("depth", C.c_int32), ("parent", C.c_int32), ("support", C.c_int32),
+                ("pvalue", C.c_float)]
+
+
+class ReachInfo(C.Structure):
+    """struct sat_reach_info of include/satabsearch.h, 32 bytes"""
+    _fields_ = [("levels", C.c_int32), ("queries", C.c_int32), ("reached", C.c_int32), ("stop", C.c_int32),
+                ("search_ms", C.c_double), ("pass_ms", C.c_double)]
 
 
 class StructSetC(C.Structure):
@@ -263,6 +283,21 @@ def device_lib():
             lib.sat_multi_search_exact.argtypes = lib.sat_search_exact.argtypes
             lib.sat_multi_exact_results.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             lib.sat_multi_exact_stats.argtypes = [C.c_void_p, C.c_void_p]
+        # (as above: a build of the parent commit predates the transitive search)
+        if hasattr(lib, "sat_reach_begin"):
+            lib.sat_reach_begin.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+            lib.sat_reach_add.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_void_p]
+            lib.sat_reach_frontier.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int32)]
+            lib.sat_reach_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int32)]
+            lib.sat_reach_end.argtypes = [C.c_void_p]
+            lib.sat_search_reach.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
+                                             C.c_double, C.c_uint32, C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(ReachInfo)]
+            lib.sat_multi_reach_begin.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+            lib.sat_multi_reach_add.argtypes = lib.sat_reach_add.argtypes
+            lib.sat_multi_reach_frontier.argtypes = lib.sat_reach_frontier.argtypes
+            lib.sat_multi_reach_rows.argtypes = lib.sat_reach_rows.argtypes
+            lib.sat_multi_reach_end.argtypes = [C.c_void_p]
+            lib.sat_multi_search_reach.argtypes = lib.sat_search_reach.argtypes
         lib.sat_hits_cutoff.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         lib.sat_multi_search_cutoff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                                 C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
@@ -341,6 +376,12 @@ def host_lib():
         lib.sat_map_kind.restype = C.c_int32
         lib.sat_exact_host.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_int32, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.sat_reach_pack_key.argtypes = [C.c_int32, C.c_double, C.c_int32]
+        lib.sat_reach_pack_key.restype = C.c_uint64
+        lib.sat_reach_unpack_key.argtypes = [C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float)]
+        lib.sat_reach_unpack_key.restype = None
+        lib.sat_reach_join.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.sat_reach_decode.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _host = lib
     return _host
 

@@ -3,7 +3,7 @@
     python -m cuda_satabsearch_amd.build [--oracle] [--ref]
 
 * libsatabsearch.so   HIP kernels + C ABI (include/satabsearch.h), hipcc --offload-arch=gfx950
-* libsathost.so       host-only C: ASCII reader, Gumbel statistics, shard cuts, cluster tables, AUC / ROC-n, greedy cover, profile core, map order, exact-search twin (csrc/host/)
+* libsathost.so       host-only C: ASCII reader, Gumbel statistics, shard cuts, cluster tables, AUC / ROC-n, greedy cover, profile core, map order, exact-search twin, reach keys (csrc/host/)
 * bin/satabsearch     the command line (csrc/host/sat_main.c), links both
 
 `--oracle` additionally runs oracle/Makefile (test infrastructure, never linked into
@@ -42,7 +42,7 @@ def _stale(target, sources):
 # of them: the library, its diagnostic twin, the Makefile and scripts/exp/variant_lib.sh all build from it.
 DEVICE_SOURCES = ("sat_launch.hip", "sat_capi.hip", "sat_pairs.hip", "sat_db.hip", "sat_topk.hip", "sat_multi.hip",
                   "sat_polish.hip", "sat_qfromdb.hip", "sat_cluster.hip", "sat_eval.hip", "sat_cover.hip", "sat_profile.hip",
-                  "sat_reorder.hip", "sat_exact.hip")
+                  "sat_reorder.hip", "sat_exact.hip", "sat_reach.hip")
 # sat_launch.hip and what it includes from csrc/ (diag/ apart, which only -DSAT_DIAG builds read)
 KERNEL_SOURCES = ("sat_sa_kernel.hpp", "sat_sa_body.inc", "sat_launch.hpp", "sat_launch.hip")
 HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "-I", INC, "-I", CSRC]
@@ -88,9 +88,9 @@ def include_closure(src):
 def build_host(force=False):
     out = os.path.join(PKG, "libsathost.so")
     srcs = [os.path.join(HOST, f) for f in ("sat_parse.c", "sat_gumbel.c", "sat_shard.c", "sat_cluster.c", "sat_eval.c", "sat_cover.c",
-                                            "sat_profile.c", "sat_reorder.c", "sat_exact.c")]
+                                            "sat_profile.c", "sat_reorder.c", "sat_exact.c", "sat_reach.c")]
     deps = srcs + [os.path.join(HOST, f) for f in ("sat_parse.h", "sat_gumbel.h", "sat_stats.h", "sat_shard.h", "sat_cluster.h", "sat_eval.h",
-                                                "sat_cover.h", "sat_profile.h", "sat_reorder.h", "sat_exact.h")]
+                                                "sat_cover.h", "sat_profile.h", "sat_reorder.h", "sat_exact.h", "sat_reach.h")]
     if force or _stale(out, deps):
         _run([CC, "-O2", "-fPIC", "-shared", "-Wall", "-Wextra", "-I", HOST, "-o", out] + srcs + ["-lm", "-lpthread"])
     return out
@@ -100,14 +100,14 @@ def _host_objects(force=False):
     """plain-C host pieces linked into the device library (and its diagnostic twin): the Gumbel statistics (the
     context tabulates them with the host libm for the device-side best-k rows), the shard cost model and the join of the
     shards' cluster labels, the reduction of the shards' summed evaluation tables, the cover's table and its plain-C
-    restatement"""
+    restatement, the join and the rows of the shards' reach arrays"""
     host_c = [os.path.join(HOST, "sat_gumbel.c"), os.path.join(HOST, "sat_shard.c"), os.path.join(HOST, "sat_cluster.c"),
-              os.path.join(HOST, "sat_eval.c"), os.path.join(HOST, "sat_cover.c")]
+              os.path.join(HOST, "sat_eval.c"), os.path.join(HOST, "sat_cover.c"), os.path.join(HOST, "sat_reach.c")]
     host_o = [os.path.join(PKG, "sat_gumbel.o"), os.path.join(PKG, "sat_shard.o"), os.path.join(PKG, "sat_cluster.o"),
-              os.path.join(PKG, "sat_eval.o"), os.path.join(PKG, "sat_cover.o")]
+              os.path.join(PKG, "sat_eval.o"), os.path.join(PKG, "sat_cover.o"), os.path.join(PKG, "sat_reach.o")]
     for c, o in zip(host_c, host_o):
         if force or _stale(o, [c] + [os.path.join(HOST, h) for h in ("sat_gumbel.h", "sat_stats.h", "sat_shard.h", "sat_cluster.h", "sat_eval.h",
-                                                                      "sat_cover.h")]):
+                                                                      "sat_cover.h", "sat_reach.h")]):
             _run([CC, "-O2", "-fPIC", "-ffp-contract=off", "-Wall", "-Wextra", "-I", HOST, "-c", "-o", o, c])
     return host_o
 
@@ -117,8 +117,8 @@ def build_device_libs(libs, force=False):
     own, re-made only when it or a file it includes is newer, all of them side by side; then the link.  A library newer
     than everything it is made from is left alone, objects or not."""
     host_c = [os.path.join(HOST, f) for f in ("sat_gumbel.c", "sat_shard.c", "sat_cluster.c", "sat_eval.c", "sat_cover.c",
-                                              "sat_gumbel.h", "sat_stats.h", "sat_shard.h", "sat_cluster.h", "sat_eval.h",
-                                              "sat_cover.h")]
+                                              "sat_reach.c", "sat_gumbel.h", "sat_stats.h", "sat_shard.h", "sat_cluster.h",
+                                              "sat_eval.h", "sat_cover.h", "sat_reach.h")]
     srcs = [os.path.join(CSRC, f) for f in DEVICE_SOURCES]
     deps = [include_closure(src) for src in srcs]
     todo = [lib for lib in libs if force or _stale(lib[0], host_c + sum(deps, []))]

@@ -361,7 +361,7 @@ sat_ctx *sat_ctx_create(int device, uint64_t seed)
             (rc_load = sat_pairs_load_code(ctx)) != SAT_OK || (rc_load = sat_cluster_load_code(ctx)) != SAT_OK ||
             (rc_load = sat_eval_load_code(ctx)) != SAT_OK || (rc_load = sat_cover_load_code(ctx)) != SAT_OK ||
             (rc_load = sat_profile_load_code(ctx)) != SAT_OK || (rc_load = sat_reorder_load_code(ctx)) != SAT_OK ||
-            (rc_load = sat_exact_load_code(ctx)) != SAT_OK)
+            (rc_load = sat_exact_load_code(ctx)) != SAT_OK || (rc_load = sat_reach_load_code(ctx)) != SAT_OK)
             return rc_load;
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         return build_gumbel_tables(ctx);

@@ -108,6 +108,7 @@ struct sat_ctx {
     DevBuf<float> d_dist;
     DevBuf<uint32_t> d_ordinal;
     uint32_t max_ordinal = 0;               // the largest of them (sat_cluster_begin sizes its nodes by it)
+    std::vector<uint32_t> h_ordinal;        // the host's copy (sat_search_reach turns a frontier's nodes into entries)
     DevBuf<int32_t> d_lists;                // entry indices grouped by bucket
     int bucket_begin[kNumBuckets + 1] = { 0 };
     int bucket_n2max[kNumBuckets] = { 0 };
@@ -225,6 +226,16 @@ struct sat_ctx {
     DevBuf<int32_t> d_cl_parent, d_cl_out, d_cl_qnode;
     DevBuf<unsigned long long> d_cl_edges;
 
+    // transitive search (sat_reach_*, sat_reach.hip): the accumulator over reach_nodes nodes (0 = none) -
+    // a 64-bit key (host/sat_reach.h) and a support count per node; the batch's node of each query.  Scratch of the
+    // ordered compaction, which only grows: the count of every block of 1024 nodes, then their running sums, then the
+    // total; the compacted nodes, or rows, before they leave.  It shares no word with the other accumulators.  An upload
+    // drops it (free_db).
+    int reach_nodes = 0;
+    DevBuf<unsigned long long> d_rc_key;
+    DevBuf<int32_t> d_rc_support, d_rc_qnode, d_rc_scan, d_rc_out;
+    DevBuf<sat_reach_row> d_rc_rows;
+
     // clustering around representatives (sat_cover_*, sat_cover.hip): the accumulator over cover_nodes nodes
     // (0 = none) - the adjacency bit matrix, [nodes] rows of sat_cover_stride(nodes) words (host/sat_cover.h); the
     // `unassigned` mask and then the representatives' mask, a row's words each; rep [nodes] then degree [nodes] in one
@@ -286,6 +297,19 @@ int sat_db_load_code(sat_ctx *ctx);
 // ---- sat_cluster.hip.  Load that file's code object (an empty launch of a small kernel); drop the accumulator.
 int sat_cluster_load_code(sat_ctx *ctx);
 void sat_cluster_drop(sat_ctx *ctx);
+
+// ---- sat_reach.hip.  Load that file's code object (an empty launch of a small kernel); drop the accumulator; and for
+// the sharded calls of sat_multi.hip: the argument checks of sat_reach_begin behind the context's and the database's, of
+// sat_reach_add behind the accumulator's and the searched state's, of the frontier and rows calls; the context's keys
+// and supports to the host (counted in its d2h bytes); the nodes at `depth` (-1: the reached nodes) of joined keys.
+int sat_reach_load_code(sat_ctx *ctx);
+void sat_reach_drop(sat_ctx *ctx);
+int sat_reach_check_begin(int n_nodes, int n_seeds, const int32_t *seed_node);
+int sat_reach_check_add(int depth, double max_pvalue, int nq, const int32_t *query_node, int nodes);
+int sat_reach_check_fetch(int depth, int cap, const void *out, const int32_t *count);
+int sat_reach_check_search(int n_seeds, const int32_t *seed_entry, int n_entries, int maxstart, double max_pvalue, int max_depth,
+                           int max_queries, int batch, double censor, int cap, const void *rows, const int32_t *count, const void *info);
+int sat_reach_arrays_fetch(sat_ctx *ctx, unsigned long long *keys, int32_t *support);
 
 // ---- sat_cover.hip.  Load that file's code object (an empty launch of a small kernel); drop the accumulator; and for
 // sat_multi_cover_solve: rows row0 .. row0 + rows - 1 of the context's adjacency matrix to the host (counted in its

@@ -34,8 +34,10 @@ void free_db(sat_ctx *ctx)
     ctx->d_dist.reset();
     ctx->d_ordinal.reset();
     ctx->max_ordinal = 0;
+    ctx->h_ordinal.clear();
     sat_cluster_drop(ctx);                    // its nodes were this database's
     sat_cover_drop(ctx);                      // and the cover accumulator's
+    sat_reach_drop(ctx);                      // and the transitive search's
     sat_eval_drop(ctx);                       // and so were the classes'
     ctx->d_lists.reset();
     ctx->d_scores.reset();
@@ -284,6 +286,7 @@ static int upload_impl(sat_ctx *ctx, int n_entries, const int32_t *orders,
         lap("header copies");
         ctx->n_entries = n_entries;
         ctx->max_ordinal = max_ordinal;
+        ctx->h_ordinal = ord;
 
         // The two big arrays go up in slices from a few host threads (each slice a synchronous copy out
         // of the caller's pageable memory: the runtime stages it through its pinned buffers, and several

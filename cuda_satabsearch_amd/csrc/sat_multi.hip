@@ -44,6 +44,7 @@
 #include "host/sat_cluster.h"
 #include "host/sat_cover.h"
 #include "host/sat_eval.h"
+#include "host/sat_reach.h"
 
 namespace {
 
@@ -1050,6 +1051,130 @@ int sat_multi_cluster_labels_levels(sat_multi *m, int32_t *label, int32_t *degre
             return sat_fail(SAT_EDEVICE, "a shard returned a label outside 0..%d", m->n_entries - 1);
     const int broken = sat_cluster_nested((int)n, (int)levels, label);
     if (broken != 0) return sat_fail(SAT_EDEVICE, "the joined labels of level %d do not lie inside level %d's", broken - 1, broken);
+    return SAT_OK;
+}
+
+// ---- Transitive search (sat_reach_*).  Every shard keeps keys and supports over the whole database's
+// nodes; a step a -> b is added by the shard that holds b's entry, so the element-wise min of the shards' keys and the
+// sum of their supports (sat_reach_join) are what one context holding the whole database has.
+
+// the shards' arrays joined on the host: keys [n], support [n]
+static int reach_joined(sat_multi *m, std::vector<uint64_t> &keys, std::vector<int32_t> &support)
+{
+    const size_t n = (size_t)m->n_entries, ndev = (size_t)m->ndev;
+    std::vector<uint64_t> k(ndev * n);
+    std::vector<int32_t> s(ndev * n);
+    for (size_t g = 0; g < ndev; g++)
+        SAT_TRY(sat_reach_arrays_fetch(m->ctx[g], reinterpret_cast<unsigned long long *>(k.data() + g * n), s.data() + g * n));
+    keys.resize(n);
+    support.resize(n);
+    if (sat_reach_join((int)n, (int)ndev, k.data(), s.data(), keys.data(), support.data()) != 0)
+        return sat_fail(SAT_EDEVICE, "the shards' reach arrays could not be joined");
+    return SAT_OK;
+}
+
+int sat_multi_reach_begin(sat_multi *m, int n_seeds, const int32_t *seed_node)
+{
+    SAT_TRY(check_multi(m));
+    SAT_TRY(sat_reach_check_begin(m->n_entries, n_seeds, seed_node));
+    // every shard's nodes are the whole database's, and every shard knows the seeds
+    for (sat_ctx *c : m->ctx) SAT_TRY(sat_reach_begin(c, m->n_entries, n_seeds, seed_node));
+    return SAT_OK;
+}
+
+int sat_multi_reach_add(sat_multi *m, int depth, double max_pvalue, const int32_t *query_node)
+{
+    SAT_TRY(check_multi(m));
+    // the checks of sat_reach_add, made for all shards before the first one adds anything
+    for (sat_ctx *c : m->ctx) {
+        if (c->reach_nodes <= 0)
+            return sat_fail(SAT_ESTATE, "no reach accumulator (sat_reach_begin has not been called since the last database upload)");
+        SAT_TRY(sat_check_searched(c));
+    }
+    SAT_TRY(sat_reach_check_add(depth, max_pvalue, (int)m->ctx[0]->queries.size(), query_node, m->n_entries));
+    return each_shard(m, [&](int g) { return sat_reach_add(m->ctx[(size_t)g], depth, max_pvalue, query_node); });
+}
+
+int sat_multi_reach_frontier(sat_multi *m, int depth, int cap, int32_t *nodes, int32_t *count)
+{
+    SAT_TRY(check_multi(m));
+    if (m->ndev == 1) return sat_reach_frontier(m->ctx[0], depth, cap, nodes, count);
+    SAT_TRY(sat_reach_check_fetch(depth, cap, nodes, count));
+    std::vector<uint64_t> keys;
+    std::vector<int32_t> support;
+    SAT_TRY(reach_joined(m, keys, support));
+    int32_t c = 0;
+    for (size_t v = 0; v < keys.size(); v++)
+        if ((int)(keys[v] >> 58) == depth) {
+            if (c < cap) nodes[c] = (int32_t)v;
+            c++;
+        }
+    *count = c;
+    return SAT_OK;
+}
+
+int sat_multi_reach_rows(sat_multi *m, int cap, sat_reach_row *rows, int32_t *count)
+{
+    SAT_TRY(check_multi(m));
+    if (m->ndev == 1) return sat_reach_rows(m->ctx[0], cap, rows, count);
+    SAT_TRY(sat_reach_check_fetch(0, cap, rows, count));
+    std::vector<uint64_t> keys;
+    std::vector<int32_t> support;
+    SAT_TRY(reach_joined(m, keys, support));
+    const int c = sat_reach_decode(m->n_entries, keys.data(), support.data(), cap, reinterpret_cast<sat_reach_rec *>(rows));
+    if (c < 0) return sat_fail(SAT_EDEVICE, "a shard returned a key whose parent lies outside 0..%d", m->n_entries - 1);
+    *count = c;
+    return SAT_OK;
+}
+
+int sat_multi_reach_end(sat_multi *m)
+{
+    SAT_TRY(sat_check_context(m));
+    for (sat_ctx *c : m->ctx) SAT_TRY(sat_reach_end(c));
+    return SAT_OK;
+}
+
+int sat_multi_search_reach(sat_multi *m, int n_seeds, const int32_t *seed_entry, int lorder, int maxstart, double max_pvalue,
+                           int max_depth, int max_queries, int batch, double censor, uint32_t first_query_ordinal, int cap,
+                           sat_reach_row *rows, int32_t *count, sat_reach_info *info)
+{
+    SAT_TRY(check_multi(m));
+    SAT_TRY(sat_reach_check_search(n_seeds, seed_entry, m->n_entries, maxstart, max_pvalue, max_depth, max_queries, batch, censor,
+                                   cap, rows, count, info));
+    // the whole database's entries are its nodes
+    SAT_TRY(sat_multi_reach_begin(m, n_seeds, seed_entry));
+    *info = sat_reach_info{ 0, 0, 0, SAT_REACH_EXHAUSTED, 0.0, 0.0 };
+    std::vector<int32_t> frontier;
+    for (int d = 1;; d++) {
+        frontier.resize((size_t)std::min(max_queries - info->queries, m->n_entries));
+        int32_t c = 0;
+        SAT_TRY(sat_multi_reach_frontier(m, d - 1, (int)frontier.size(), frontier.data(), &c));
+        if (c == 0) { info->stop = SAT_REACH_EXHAUSTED; break; }
+        if (d - 1 == max_depth) { info->stop = SAT_REACH_DEPTH; break; }
+        if (c > max_queries - info->queries) { info->stop = SAT_REACH_BUDGET; break; }
+        for (int at = 0; at < c; at += batch) {
+            const int nb = std::min(batch, c - at);
+            SAT_TRY(sat_multi_queries_from_db(m, nb, frontier.data() + at, first_query_ordinal + (uint32_t)(info->queries + at)));
+            double ms = 0.0;
+            SAT_TRY(sat_multi_search_only(m, lorder, 0, maxstart, &ms));
+            info->search_ms += ms;
+            if (censor >= 0.0) {
+                const int rc = sat_fit_queries((size_t)nb, censor, nullptr,
+                                               [&](uint32_t *counts, int32_t *below) { return sat_multi_score_histogram(m, counts, below); },
+                                               [&](const sat_fit *fit) { return sat_multi_stats_set(m, fit); });
+                if (rc != SAT_OK) return bail(m, rc);
+            }
+            const Stopwatch clock;
+            SAT_TRY(sat_multi_reach_add(m, d, max_pvalue, frontier.data() + at));
+            SAT_TRY(each_shard(m, [&](int g) { return sat_sync(m->ctx[(size_t)g]); }));
+            clock.stop(&ms);
+            info->pass_ms += ms;
+        }
+        info->queries += c;
+        info->levels++;
+    }
+    SAT_TRY(sat_multi_reach_rows(m, cap, rows, count));
+    info->reached = *count;
     return SAT_OK;
 }
 

@@ -285,3 +285,31 @@ def exact_table(stats, names=None):
                                               int(s["gain"]) / improved if improved else 0.0,
                                               int(s["nodes"]) / rows if rows else 0.0))
     return lines
+
+
+def reach_table(rows, names):
+    """The reached nodes of a transitive search (Searcher.reach_rows / search_reach) as text lines `name depth parent_name
+    pvalue support`, in the rows' order; a seed or a node reached from an external query has the parent `-`.  names: the
+    names of the whole database's structures, by node."""
+    lines = ["# name depth parent pvalue support"]
+    for r in rows:
+        parent = int(r["parent"])
+        lines.append("%s %d %s %s %d" % (names[int(r["node"])], int(r["depth"]), names[parent] if parent >= 0 else "-",
+                                         _g(float(r["pvalue"])), int(r["support"])))
+    return lines
+
+
+def reach_path(rows, node):
+    """The chain of parents from `node` back to a seed (or to a node reached from an external query): the nodes, `node`
+    first.  Every link goes one level up, so the chain has depth + 1 nodes.  Raises KeyError for a node the rows do not
+    hold, ValueError for rows whose depths do not descend along the chain."""
+    by_node = {int(r["node"]): r for r in rows}
+    path, at = [int(node)], by_node[int(node)]
+    while int(at["parent"]) >= 0:
+        up = by_node[int(at["parent"])]
+        if int(up["depth"]) != int(at["depth"]) - 1:
+            raise ValueError("node %d at depth %d has its parent %d at depth %d" % (int(at["node"]), int(at["depth"]),
+                                                                                   int(up["node"]), int(up["depth"])))
+        path.append(int(up["node"]))
+        at = up
+    return path

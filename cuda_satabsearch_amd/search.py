@@ -128,6 +128,10 @@ KIND_SEQUENTIAL, KIND_CIRCULAR, KIND_PERMUTED, KIND_ALL = 1, 2, 4, 7
 
 _EXACT_STAT_DTYPE = np.dtype([("rows", np.int64), ("proven", np.int64), ("improved", np.int64), ("gain", np.int64),
                               ("nodes", np.uint64)])
+_REACH_DTYPE = np.dtype([("node", np.int32), ("depth", np.int32), ("parent", np.int32), ("support", np.int32),
+                         ("pvalue", np.float32)])
+assert _REACH_DTYPE.itemsize == C.sizeof(_native.ReachRow) == 20
+REACH_STOP = {_native.REACH_EXHAUSTED: "exhausted", _native.REACH_DEPTH: "depth", _native.REACH_BUDGET: "budget"}
 _FIT_DTYPE = np.dtype([("a", np.float64), ("b", np.float64), ("rows", np.int32), ("censored", np.int32),
                        ("below", np.int32), ("fitted", np.int32)], align=True)
 assert _FIT_DTYPE.itemsize == C.sizeof(_native.Fit)
@@ -237,6 +241,72 @@ def _cluster_labels(obj, fn, handle, n_nodes):
     edges = C.c_ulonglong(0)
     obj._check(fn(handle, labels.ctypes.data, degrees.ctypes.data, C.byref(edges)))
     return labels, degrees, int(edges.value)
+
+
+def _reach_begin(obj, call, seeds):
+    """shared by Searcher / MultiSearcher.reach_begin: call(n_seeds, pointer)"""
+    seeds = np.ascontiguousarray(() if seeds is None else seeds, dtype=np.int32).ravel()
+    obj._check(call(len(seeds), seeds.ctypes.data if len(seeds) else None))
+
+
+def _reach_add(obj, fn, handle, depth, max_pvalue, query_nodes):
+    """shared by Searcher / MultiSearcher.reach_add"""
+    nodes = np.ascontiguousarray(query_nodes, dtype=np.int32).ravel()
+    if len(nodes) != getattr(obj, "n_queries", 1):
+        raise ValueError("one node per query of the batch is needed")
+    obj._check(fn(handle, int(depth), float(max_pvalue), nodes.ctypes.data))
+
+
+def _reach_frontier(obj, fn, handle, depth, cap):
+    """shared by Searcher / MultiSearcher.reach_frontier: (nodes int32[min(cap, count)], count).  cap None: all of them,
+    by a call that asks for the count alone first"""
+    count = C.c_int32(0)
+    if cap is None:
+        obj._check(fn(handle, int(depth), 0, None, C.byref(count)))
+        cap = count.value
+    nodes = np.empty(int(cap), np.int32)
+    obj._check(fn(handle, int(depth), int(cap), nodes.ctypes.data if cap else None, C.byref(count)))
+    return nodes[:min(int(cap), count.value)].copy(), int(count.value)
+
+
+def _reach_rows(obj, fn, handle, cap):
+    """shared by Searcher / MultiSearcher.reach_rows: (rows [min(cap, count)], count); cap None as _reach_frontier"""
+    count = C.c_int32(0)
+    if cap is None:
+        obj._check(fn(handle, 0, None, C.byref(count)))
+        cap = count.value
+    rows = np.zeros(int(cap), _REACH_DTYPE)
+    obj._check(fn(handle, int(cap), rows.ctypes.data if cap else None, C.byref(count)))
+    return rows[:min(int(cap), count.value)].copy(), int(count.value)
+
+
+def _search_reach(obj, fn, handle, n_nodes, seeds, max_pvalue, max_depth, max_queries, batch, censor, first_query_ordinal, cap,
+                  lorder, maxstart):
+    """shared by Searcher / MultiSearcher.search_reach: (rows, info dict)"""
+    seeds = np.ascontiguousarray(seeds, dtype=np.int32).ravel()
+    cap = int(n_nodes if cap is None else cap)
+    rows = np.zeros(cap, _REACH_DTYPE)
+    count = C.c_int32(0)
+    info = _native.ReachInfo()
+    obj._check(fn(handle, len(seeds), seeds.ctypes.data if len(seeds) else None, int(bool(lorder)), int(maxstart), float(max_pvalue),
+                  int(max_depth), int(n_nodes if max_queries is None else max_queries), int(batch),
+                  -1.0 if censor is None else float(censor), int(first_query_ordinal), cap, rows.ctypes.data if cap else None,
+                  C.byref(count), C.byref(info)))
+    return rows[:min(cap, count.value)].copy(), {
+        "levels": int(info.levels), "queries": int(info.queries), "reached": int(info.reached), "stop": REACH_STOP[int(info.stop)],
+        "search_ms": float(info.search_ms), "pass_ms": float(info.pass_ms)}
+
+
+def _reach_last_batch(obj, frontier_fn, handle, out, batch, order_of):
+    """the Python side of the batch a search_reach left in the library: the tail of the last level searched, read from
+    the accumulator the run left (4 bytes a node) - the rows may be capped and need not show that level"""
+    info = out[1]
+    if not info["queries"]:
+        return
+    level, _ = _reach_frontier(obj, frontier_fn, handle, info["levels"] - 1, None)
+    last = level[len(level) - ((len(level) - 1) % int(batch) + 1):]
+    n1s = np.array([order_of(int(v)) for v in last], np.int32)
+    obj.n1, obj.n1max, obj._n1s, obj.n_queries, obj._batch = int(n1s[0]), int(n1s.max()), n1s, len(last), True
 
 
 def _cluster_levels(pvalues):
@@ -361,6 +431,7 @@ class Searcher:
             db.dist.ctypes.data, ordinal.ctypes.data if ordinal is not None else None))
         self.n_entries = n
         self._orders = db.orders.copy()
+        self._ordinal = ordinal
 
     def upload_search(self, db: StructSet, lorder=True, lsoln=False, maxstart=DEFAULT_MAXSTART, db_ordinal=None):
         """upload() and the first search of the query (batch) set before, overlapped: each piece of the
@@ -378,6 +449,7 @@ class Searcher:
             int(bool(lorder)), int(bool(lsoln)), int(maxstart)))
         self.n_entries = n
         self._orders = db.orders.copy()
+        self._ordinal = ordinal
 
     def upload_dense(self, orders, tabs, dmats, pitch, db_ordinal=None):
         orders = np.ascontiguousarray(orders, dtype=np.int32)
@@ -389,6 +461,7 @@ class Searcher:
             ordinal.ctypes.data if ordinal is not None else None))
         self.n_entries = int(orders.shape[0])
         self._orders = orders.copy()
+        self._ordinal = ordinal
 
     # ---- query --------------------------------------------------------------
     def set_query(self, qtab, qdmat, qssetypes=None, query_ordinal=0):
@@ -721,6 +794,50 @@ class Searcher:
         self._check(self._lib.sat_cluster_end(self._ctx))
         self._cluster_nodes = 0
         self._cluster_levels = 0
+
+    # ---- transitive search (sat_reach_*, sat_search_reach) ---------------------
+    def reach_begin(self, seeds=None, n_nodes=None):
+        """Start (or restart, emptied) the transitive search's accumulator over n_nodes nodes (default as cluster_begin)
+        with the nodes `seeds` at depth 0 (sat_reach_begin); no seeds: an external start."""
+        n = self.n_entries if n_nodes is None else int(n_nodes)
+        _reach_begin(self, lambda c, p: self._lib.sat_reach_begin(self._ctx, n, c, p), seeds)
+
+    def reach_add(self, depth, max_pvalue, query_nodes):
+        """Add the rows of the last search that qualify as cluster_add has it as directed steps query_nodes[q] -> the
+        entry's node at `depth` (1..62): a node keeps the shallowest depth, then the smallest p, then the smallest parent;
+        its support counts every step to it (sat_reach_add).  query_nodes[q] == -1: an external query.  Nothing is copied
+        back."""
+        _reach_add(self, self._lib.sat_reach_add, self._ctx, depth, max_pvalue, query_nodes)
+
+    def reach_frontier(self, depth, cap=None):
+        """(the first `cap` nodes at exactly `depth`, ascending, int32; their uncapped count), compacted on the device
+        (sat_reach_frontier).  cap None: all of them."""
+        return _reach_frontier(self, self._lib.sat_reach_frontier, self._ctx, depth, cap)
+
+    def reach_rows(self, cap=None):
+        """(the first `cap` reached nodes, ascending, as records node, depth, parent, support, pvalue; their uncapped
+        count) (sat_reach_rows).  parent -1: a seed or an external query.  report.reach_table prints them."""
+        return _reach_rows(self, self._lib.sat_reach_rows, self._ctx, cap)
+
+    def reach_end(self):
+        """Free the accumulator (sat_reach_end)."""
+        self._check(self._lib.sat_reach_end(self._ctx))
+
+    def search_reach(self, seeds, max_pvalue, max_depth=_native.REACH_MAX_DEPTH, max_queries=None, batch=256, censor=None,
+                     first_query_ordinal=0, cap=None, lorder=True, maxstart=DEFAULT_MAXSTART):
+        """Transitive search from the entries `seeds` (sat_search_reach): level d searches the nodes first reached at
+        depth d - 1, in ascending node order and batches of `batch`, and adds their hits at max_pvalue, until nothing new
+        turns up, max_depth is reached or a level would take the queries past max_queries (default: every node once).
+        censor not None: each batch fitted to its own scores.  Returns (rows as reach_rows, info: levels, queries,
+        reached, stop = "exhausted" / "depth" / "budget", search_ms, pass_ms).  Afterwards the searcher holds the last
+        batch, as after set_queries_from_db and search."""
+        out = _search_reach(self, self._lib.sat_search_reach, self._ctx, self.n_entries, seeds, max_pvalue, max_depth,
+                            max_queries, batch, censor, first_query_ordinal, cap, lorder, maxstart)
+        ordinal = getattr(self, "_ordinal", None)
+        entry_of = None if ordinal is None else {int(o): e for e, o in reversed(list(enumerate(ordinal)))}
+        _reach_last_batch(self, self._lib.sat_reach_frontier, self._ctx, out, batch,
+                          lambda v: self._orders[v if entry_of is None else entry_of[v]])
+        return out
 
     # ---- the same at several cutoffs in one pass (sat_cluster_*_levels) -------
     def cluster_begin_levels(self, pvalues, n_nodes=None):
@@ -1095,6 +1212,35 @@ class MultiSearcher:
         """Searcher.cluster_labels of the whole database: the shards' labels joined, degrees and edges summed
         (sat_multi_cluster_labels) - exactly what one searcher holding the whole database returns."""
         return _cluster_labels(self, self._lib.sat_multi_cluster_labels, self._m, self.n_entries)
+
+    def reach_begin(self, seeds=None):
+        """Searcher.reach_begin on every shard, over the whole database's nodes (sat_multi_reach_begin)."""
+        _reach_begin(self, lambda c, p: self._lib.sat_multi_reach_begin(self._m, c, p), seeds)
+
+    def reach_add(self, depth, max_pvalue, query_nodes):
+        """Searcher.reach_add on every shard: each adds the steps that end at its own entries."""
+        _reach_add(self, self._lib.sat_multi_reach_add, self._m, depth, max_pvalue, query_nodes)
+
+    def reach_frontier(self, depth, cap=None):
+        """Searcher.reach_frontier of the whole database: the shards' keys joined on the host (sat_multi_reach_frontier)."""
+        return _reach_frontier(self, self._lib.sat_multi_reach_frontier, self._m, depth, cap)
+
+    def reach_rows(self, cap=None):
+        """Searcher.reach_rows of the whole database: the shards' keys joined by minimum, their supports summed
+        (sat_multi_reach_rows) - exactly what one searcher holding the whole database returns."""
+        return _reach_rows(self, self._lib.sat_multi_reach_rows, self._m, cap)
+
+    def reach_end(self):
+        """Free every shard's accumulator (sat_multi_reach_end)."""
+        self._check(self._lib.sat_multi_reach_end(self._m))
+
+    def search_reach(self, seeds, max_pvalue, max_depth=_native.REACH_MAX_DEPTH, max_queries=None, batch=256, censor=None,
+                     first_query_ordinal=0, cap=None, lorder=True, maxstart=DEFAULT_MAXSTART):
+        """Searcher.search_reach over every shard (sat_multi_search_reach); search_ms and pass_ms are wall clock."""
+        out = _search_reach(self, self._lib.sat_multi_search_reach, self._m, self.n_entries, seeds, max_pvalue, max_depth,
+                            max_queries, batch, censor, first_query_ordinal, cap, lorder, maxstart)
+        _reach_last_batch(self, self._lib.sat_multi_reach_frontier, self._m, out, batch, lambda v: self._orders[v])
+        return out
 
     def cover_begin(self):
         """Searcher.cover_begin on every shard, over the whole database's nodes (sat_multi_cover_begin)."""

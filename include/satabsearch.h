@@ -962,6 +962,87 @@ int sat_multi_exact_results(sat_multi *m, int32_t *scores, int32_t *ssemaps, int
 int sat_multi_exact_stats(sat_multi *m, sat_exact_stat *per_query);
 
 /*
+ * ---- Transitive search: follow hits of hits from a seed, kept on the device (the key's layout and the
+ * host-side functions are in csrc/host/sat_reach.h).  No command-line option: the C ABI and the Python classes only.
+ * Nodes, qualifying rows and the double tested are those of sat_cluster_add.  A qualifying row (q, e) is the DIRECTED
+ * step a -> b from a = query_node[q] to b = the ordinal of entry e; a row with a == b is none.  query_node[q] == -1 is an
+ * EXTERNAL query, one not taken from the database: it has no self row and is recorded as parent -1.  Each node has one
+ * 64-bit key - depth (63: unreached) above the bits of (float)p above the parent - and a support count; adding the rows
+ * of a search at depth d does, for every step a -> b, atomicMin(key[b], pack(d, p, a)) and atomicAdd(support[b], 1).  So
+ * a node keeps the shallowest depth it was ever reached at, within it the smallest float-rounded p, and of equal ones
+ * the smallest parent node, external queries last.  Everything is integers and a function of the multiset of (depth,
+ * row) pairs added: nothing depends on the launch shape, the cut of a level into batches, the order of the add calls or
+ * the sharding.
+ *
+ * sat_reach_begin     start (or restart, emptied) the accumulator over n_nodes nodes with the n_seeds nodes of seed_node
+ *                     at depth 0.  Checks as sat_cluster_begin; n_nodes above 2^27 - 1, n_seeds < 0, a null list with
+ *                     n_seeds > 0, a seed outside 0 .. n_nodes - 1 or listed twice (the message names its position):
+ *                     SAT_EINVAL, an earlier accumulator stays as it was.  n_seeds == 0 is allowed: an external start.
+ * sat_reach_add       add the qualifying rows of the last search at `depth`; SAT_ESTATE as sat_cluster_add.  query_node
+ *                     NULL, depth outside 1 .. 62, a max_pvalue that is not finite or negative, a node below -1 or above
+ *                     n_nodes - 1 (the message names its position): SAT_EINVAL, nothing added.  Copies 4 * n_queries
+ *                     bytes (and the queries' table pointers) to the device and NOTHING back.  One pass on the context's
+ *                     stream behind the search; the call does not wait for it.
+ * sat_reach_frontier  wait; *count = the nodes whose key has exactly `depth` (0 .. 62), and the first min(cap, *count) of
+ *                     them, ascending, to `nodes` - compacted on the device.  Copies exactly 4 + 4 * min(cap, *count)
+ *                     bytes.  count NULL, cap < 0, nodes NULL with cap > 0: SAT_EINVAL.
+ * sat_reach_rows      the same for the REACHED nodes as rows: 4 + 20 * min(cap, *count) bytes; parent -1 for seeds and
+ *                     external parents, pvalue 0 for seeds.  An unreached node never crosses to the host.
+ * sat_reach_end       free the accumulator.  A database upload drops it too; query changes and searches keep it.
+ *
+ * sat_search_reach    the loop.  The seeds are entries of the resident database (outside it or listed twice: SAT_EINVAL);
+ *                     the accumulator is restarted over max ordinal + 1 nodes (a resident ordinal of 2^27 - 1 or above:
+ *                     SAT_EINVAL, before anything is allocated or changed).  Level d = 1, 2, ... takes the nodes at
+ *                     depth d - 1 as queries, in ascending node order, in batches of `batch` (1 .. 256) built by
+ *                     sat_queries_from_db, searches each batch with the context's ordinary search (lsoln off, polished
+ *                     where sat_polish_all_set is on), installs sat_stats_fit(censor) if censor >= 0, and calls
+ *                     sat_reach_add(d).  Query ordinals number the queries in the order searched, from
+ *                     first_query_ordinal: a query's random stream does not depend on `batch`.  Before level d the loop
+ *                     stops, in this order, when no node is at depth d - 1 (SAT_REACH_EXHAUSTED), when d - 1 ==
+ *                     max_depth (1 .. 62; SAT_REACH_DEPTH), or when the level would take the queries searched past
+ *                     max_queries (>= 1; SAT_REACH_BUDGET): a level is searched whole or not at all.  Then rows and
+ *                     *count as sat_reach_rows(cap); the accumulator stays.  Between levels only the frontier list
+ *                     crosses: 4 bytes a node up, and down again.  The result buffers afterwards hold the last batch.
+ * sat_multi_*         every shard keeps keys and supports over the whole database's nodes and adds the rows of its own
+ *                     entries; checks are made for every shard before the first one works; frontier and rows fetch the
+ *                     shards' arrays and join them on the host (sat_reach_join: element-wise min and sum).  Bit-equal to
+ *                     one context holding the whole database.  Seeds of sat_multi_search_reach are entries of the whole
+ *                     database, which are its nodes.  sat_multi_reach_end frees every shard's
+ *                     accumulator.
+ */
+#define SAT_REACH_EXHAUSTED 0
+#define SAT_REACH_DEPTH     1
+#define SAT_REACH_BUDGET    2
+typedef struct sat_reach_row {
+    int32_t node, depth, parent, support;
+    float   pvalue;
+} sat_reach_row;            /* 20 bytes */
+typedef struct sat_reach_info {
+    int32_t levels;         /* levels searched                                         */
+    int32_t queries;        /* queries searched                                        */
+    int32_t reached;        /* nodes reached, the seeds among them                     */
+    int32_t stop;           /* SAT_REACH_EXHAUSTED / _DEPTH / _BUDGET                  */
+    double  search_ms;      /* the searches' summed time (multi: wall clock)           */
+    double  pass_ms;        /* the add passes' summed time                             */
+} sat_reach_info;           /* 32 bytes */
+int sat_reach_begin(sat_ctx *ctx, int n_nodes, int n_seeds, const int32_t *seed_node);
+int sat_reach_add(sat_ctx *ctx, int depth, double max_pvalue, const int32_t *query_node);
+int sat_reach_frontier(sat_ctx *ctx, int depth, int cap, int32_t *nodes, int32_t *count);
+int sat_reach_rows(sat_ctx *ctx, int cap, sat_reach_row *rows, int32_t *count);
+int sat_reach_end(sat_ctx *ctx);
+int sat_search_reach(sat_ctx *ctx, int n_seeds, const int32_t *seed_entry, int lorder, int maxstart, double max_pvalue,
+                     int max_depth, int max_queries, int batch, double censor, uint32_t first_query_ordinal, int cap,
+                     sat_reach_row *rows, int32_t *count, sat_reach_info *info);
+int sat_multi_reach_begin(sat_multi *m, int n_seeds, const int32_t *seed_node);
+int sat_multi_reach_add(sat_multi *m, int depth, double max_pvalue, const int32_t *query_node);
+int sat_multi_reach_frontier(sat_multi *m, int depth, int cap, int32_t *nodes, int32_t *count);
+int sat_multi_reach_rows(sat_multi *m, int cap, sat_reach_row *rows, int32_t *count);
+int sat_multi_reach_end(sat_multi *m);
+int sat_multi_search_reach(sat_multi *m, int n_seeds, const int32_t *seed_entry, int lorder, int maxstart, double max_pvalue,
+                           int max_depth, int max_queries, int batch, double censor, uint32_t first_query_ordinal, int cap,
+                           sat_reach_row *rows, int32_t *count, sat_reach_info *info);
+
+/*
  * Time `repeats` back-to-back searches with HIP events on the launch stream
  * (inputs resident, no copies inside the window).  Returns total milliseconds
  * in *total_ms and the dominant SA kernel's summed device time in *kernel_ms.
