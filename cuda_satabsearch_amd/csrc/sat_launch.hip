@@ -317,13 +317,19 @@ void sat_debug_lds_layout(int m2w, int n1, int n1p, int n2, int chains, int thre
                           uint32_t out[11])
 {
     // m2w: low byte = words of a db-side set; bits 8-9 = 1 + cell layout (SAT_CELLS_*), 0 = the layout launches of
-    // such entries get (satk::cell_layout)
-    const int cells = (m2w >> 8) ? ((m2w >> 8) & 3) - 1 : satk::cell_layout(n2);
+    // such entries get (satk::cell_layout); bit 16 = three more words: qmask, qbase, pos
+    const int cells = ((m2w >> 8) & 3) ? ((m2w >> 8) & 3) - 1 : satk::cell_layout(n2);
+    const bool more = (m2w >> 16) & 1;
     m2w &= 0xFF;
     const satk::LdsLayout L = satk::lds_layout(m2w, cells, n2, satk::map_words((n1 + 3) >> 2), n1p, chains, threads,
                                                q_in_lds != 0, compact != 0);
     const uint32_t v[11] = { L.code, L.qdist, L.qcode, L.smap, L.tmask, L.qtypes, L.leader, L.red, L.red_stride, L.items, L.total };
     for (int i = 0; i < 11; i++) out[i] = v[i];
+    if (more) {
+        out[11] = L.qmask;
+        out[12] = L.qbase;
+        out[13] = L.pos;
+    }
 }
 
 // satabsearch_debug.h: every instantiation pick_sa_kernel can choose, named as sat_last_launch_info names it, one per

@@ -83,6 +83,11 @@
     // M2W == 1: the candidate mask of query SSE i by ONE LDS read (tmask[qtypes[i]] is two, one after the other,
     // on the path of every SA step)
     uint32_t *qmask = reinterpret_cast<uint32_t *>(lds_slot + lay.qmask);
+    // ... and the rank table of the LORDER step's pick: the entry's SSEs sorted by (type, index), and per query SSE
+    // where its type's run starts (read next to qmask, so the table read is the only dependent one)
+    uint8_t *qbase = lds_slot + lay.qbase;
+    uint8_t *pos = lds_slot + lay.pos;
+    constexpr bool PICK_TABLE = SAT_PICK_TABLE && M2W == 1;
     unsigned char *red_b = lds_slot + lay.red;
     auto red_key = [&](int w) -> unsigned long long * { return reinterpret_cast<unsigned long long *>(red_b + (uint32_t)w * lay.red_stride); };
     constexpr int TMS = M2W;                                  // words per type of the type masks
@@ -222,7 +227,26 @@
     }
     __syncthreads();
     if constexpr (M2W == 1) {
-        for (int i = lane_id; i < N1P; i += nthreads) qmask[i] = tmask[qtypes[i] & 3];
+        // db SSEs of the types below each type: where a type's run starts in `pos`
+        const uint32_t tm0 = tmask[0], tm1 = tmask[1], tm2 = tmask[2], tm3 = tmask[3];
+        const int b1 = __popc(tm0), b2 = b1 + __popc(tm1), b3 = b2 + __popc(tm2);
+        for (int i = lane_id; i < N1P; i += nthreads) {
+            const int t = qtypes[i] & 3;
+            qmask[i] = t == 0 ? tm0 : (t == 1 ? tm1 : (t == 2 ? tm2 : tm3));
+            qbase[i] = (uint8_t)(t == 0 ? 0 : (t == 1 ? b1 : (t == 2 ? b2 : b3)));
+        }
+        // db SSE j goes to its rank among the SSEs of its type, behind the types below; the bytes past the last
+        // SSE are read (and dropped) by steps without a candidate.  (A slot has at least 64 lanes.)
+        if (lane_id < (int)SAT_POS_BYTES) {
+            const int j = lane_id;
+            const uint32_t bit = j < n2 ? 1u << j : 0u, below = bit - 1u;
+            int rank = j;
+            if (tm0 & bit) rank = __popc(tm0 & below);
+            if (tm1 & bit) rank = b1 + __popc(tm1 & below);
+            if (tm2 & bit) rank = b2 + __popc(tm2 & below);
+            if (tm3 & bit) rank = b3 + __popc(tm3 & below);
+            pos[rank] = (uint8_t)j;
+        }
         __syncthreads();
     }
 
@@ -600,6 +624,7 @@
             // candidate db SSEs: free, same type, inside the order window (K.cu:1053-1086)
             int oldj;
             Bits<M2W> cand;
+            int rank_base = 0;            // PICK_TABLE: where the window's first candidate stands in `pos`
             if (M2W == 1 && opt_lorder) {
                 // LORDER maps are order preserving (thinit builds them so and every move stays
                 // inside its window), so the images of the mapped query SSEs are the set bits of
@@ -622,7 +647,12 @@
                 // no mapped SSE at or below ssei: startj = n2, empty (K.cu:1060-1063); no mapped
                 // successor: endj = -1, empty, unless ssei is the last query SSE (K.cu:1064-1077)
                 const bool empty = none || (y == 0u && ssei != n1 - 1);
-                cand.w[0] = empty ? 0u : (qmask[ssei] & gap);
+                const uint32_t qm = qmask[ssei];
+                cand.w[0] = empty ? 0u : (qm & gap);
+                // Everything in the window is free, so its candidates are simply the SSEs of the type above A, in
+                // order: the first of them stands in the type's run of `pos` behind the SSEs of the type up to A.
+                // (No candidate - `empty`, or A = 31 - leaves an index of at most the run's end: read, not used.)
+                if constexpr (PICK_TABLE) rank_base = qbase[ssei] + __popc(qm & ~above);
             } else if (M2W == 2 && FAST && opt_lorder) {
                 // The same for entries of 33..64 SSEs with the two words of the db-side sets taken as ONE 64-bit
                 // word: p, A and the old image as above, the window is the run of free bits between A and the next
@@ -696,7 +726,11 @@
             const int cnt = bits_count<M2W>(cand);
             const int pick = scaled_index16(word_a & 0xFFFFu, cnt, max(cnt - 1, 0));   // 0 for cnt <= 1: no draw used
             int sel;
-            if (M2W == 1 && opt_lorder) {
+            if (PICK_TABLE && opt_lorder) {
+                // the pick-th candidate by its rank: one table read whatever the largest pick of the wave (stripping
+                // `pick` bits cost every lane of the wave what its deepest pick cost, ~4 trips for a mean pick of 0.15)
+                sel = pos[rank_base + pick];
+            } else if (M2W == 1 && opt_lorder) {
                 // inside an order window the picked rank is small (few free same-type SSEs): strip
                 // the lowest set bit `pick` times, looping while any lane of the wave still has to
                 uint32_t c = cand.w[0];

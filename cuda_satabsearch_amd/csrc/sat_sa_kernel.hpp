@@ -34,6 +34,10 @@
 //        walks the matched pairs (i, k) of each chain and fetches one such cell per pair.
 //   qmask (LDS, launches with one-word db sets) per query SSE the db SSEs of its type,
 //        tmask[qtypes[i]]: one read on the path of every SA step instead of two dependent ones.
+//   pos, qbase (LDS, the same launches) the entry's SSEs sorted by (type, index), one byte each, and per query
+//        SSE the start of its type's run in it.  Under LORDER a step's candidates are all the free SSEs of the
+//        type between the predecessor's image A and the next occupied SSE, so the pick-th of them is the
+//        (SSEs of the type at or below A) + pick -th of the run: one table read instead of stripping `pick` bits.
 //   smap (LDS) per-chain SSE map, one byte per query SSE (the image's index, or with 8-byte cells its cell's
 //        byte offset in a row, l << 3, and 0x04 for "unmatched": map_bytes_scaled), stored word-interleaved
 //        smap[w*(T+1) + chain]: word w of every chain is contiguous, so a loop over a
@@ -150,6 +154,10 @@
 // the initial full score of two chains walked by a pair of lanes together (one-word sets, one lane per chain)
 #ifndef SAT_FS_TEAMS
 #define SAT_FS_TEAMS 1
+#endif
+// the LORDER step's candidate of one-word db sets read from the rank table `pos` (0: the strip loop, for A/B builds)
+#ifndef SAT_PICK_TABLE
+#define SAT_PICK_TABLE 1
 #endif
 #define SAT_K_MAXITER 100
 #define SAT_K_MAXDIM 111              // SAT_MAXDIM of satabsearch.h: the pitch of a pair's map
@@ -445,6 +453,9 @@ template <int CELLS> __device__ __forceinline__ uint2 db_cell(const DbRow<CELLS>
 // kernel sees the encoding: its outputs, the items of the compaction tables and every other layout keep plain indices
 // with the null SSE n2 for "unmatched".
 #define SAT_MAP_UNMATCHED 0x04u
+// Bytes of the rank table `pos` of a launch with one-word db sets: up to 32 SSEs, and one byte more for the lanes of
+// a step that have no candidate - they read at up to (SSEs of the type) past its run's start and drop the byte.
+#define SAT_POS_BYTES 36u
 __host__ __device__ constexpr bool map_bytes_scaled(int m2w, int cells) { return cells == SAT_CELLS_FULL8 && m2w == 1; }
 template <bool SCALED> __device__ __forceinline__ uint32_t map_encode(int j, int nullj)
 {
@@ -611,6 +622,8 @@ struct LdsLayout {
     uint32_t tmask;       // [4 types][4 words] db SSEs of a type
     uint32_t qtypes;      // query SSE types
     uint32_t qmask;       // one-word db sets only: per query SSE the mask of the db SSEs of its type (tmask[qtypes[i]])
+    uint32_t qbase;       // one-word db sets only: per query SSE the first byte of its type's run in `pos`
+    uint32_t pos;         // one-word db sets only: the entry's SSEs sorted by (type, index), SAT_POS_BYTES bytes
     uint32_t leader;      // the LSOLN leader key (64-bit)
     uint32_t red;         // the waves' arg-max keys (64-bit), red_stride bytes apart
     uint32_t red_stride;
@@ -651,6 +664,10 @@ __host__ __device__ inline LdsLayout lds_layout(int m2w, int cells, int n2, int 
     off += ((uint32_t)n1p + 15u) & ~15u;
     L.qmask = off;
     if (m2w == 1) off += (uint32_t)n1p * 4u;
+    L.qbase = off;
+    if (m2w == 1) off += (uint32_t)n1p;                       // (n1p is a multiple of 4)
+    L.pos = off;
+    if (m2w == 1) off += SAT_POS_BYTES;
     off = (off + 7u) & ~7u;
     L.leader = off;
     off += 8u;
