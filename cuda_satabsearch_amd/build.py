@@ -181,6 +181,10 @@ def build_test_native(force=False, twin=True):
     src2, out2 = os.path.join(tdir, "lds_residency.hip"), os.path.join(tdir, "liblds_residency.so")
     if os.path.exists(src2) and (force or _stale(out2, [src2])):
         _run([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", out2, src2])
+    # the caller's side of a stream (tests/stream_lib.py)
+    src3, out3 = os.path.join(tdir, "stream_probe.hip"), os.path.join(tdir, "libstream_probe.so")
+    if os.path.exists(src3) and (force or _stale(out3, [src3])):
+        _run([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", out3, src3])
     return out
 
 

@@ -1222,3 +1222,26 @@ def rises_and_falls(walk, multi=False):
                 out[name][0 if v > last[name] else 1] += 1
             last[name] = v
     return {k: tuple(v) for k, v in out.items()}
+
+
+# ---------------------------------------------------------------- the walks of tests/test_gpu_caller_stream.py
+def caller_stream_walks(first=4, second=4):
+    """the walks that run once more on every kind of caller's stream, as (name, operations): `first` greedy walks of the
+    first schedule and `second` of the second one, chosen - most kinds not yet seen first, the lower index among equals -
+    so that with the two hand-made walks of the second schedule every kind of ALL_KINDS occurs
+    (tests/test_history_cpu.py asserts it)"""
+    def make():
+        old, new = schedule(SEED)[:-1], schedule(SEED, False, True)[:-2]              # (the greedy ones)
+        hand = schedule(SEED, False, True)[-2:]
+        seen = {o.kind for w in hand for o in w}
+        out = []
+        for name, walks, count in (("walk", old, first), ("new_walk", new, second)):
+            taken = []
+            for _ in range(count):
+                gain = [-1 if i in taken else len({o.kind for o in w} - seen) for i, w in enumerate(walks)]
+                i = int(np.argmax(gain))
+                taken.append(i)
+                seen |= {o.kind for o in walks[i]}
+            out += [("%s%d" % (name, i), walks[i]) for i in sorted(taken)]
+        return out + [("named", hand[0]), ("sizes", hand[1])]
+    return _memo(("caller_stream_walks", first, second), make)

@@ -24,11 +24,14 @@ def text(o):
     return "%s(%s)" % (o.kind, ", ".join("%s=%s" % kv for kv in o.args))
 
 
-def follow(s, ops, multi=False, after_step=None):
-    """run `ops` on `s`, comparing every data-returning step with its reference; returns the number compared"""
+def follow(s, ops, multi=False, after_step=None, before_step=None):
+    """run `ops` on `s`, comparing every data-returning step with its reference; returns the number compared.
+    before_step(s, m) runs in front of every step (tests/test_gpu_caller_stream.py queues the caller's work there)"""
     m, compared = hl.Model(multi), 0
     for step, o in enumerate(ops):
         assert m.legal(o.kind), "step %d: the model does not allow %s" % (step, text(o))
+        if before_step:
+            before_step(s, m)
         got = hl.run(s, o, m)
         if o.kind in hl.DATA_KINDS:
             diff = hl.same(got, hl.expect(o, m))

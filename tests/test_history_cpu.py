@@ -515,3 +515,22 @@ def test_the_reference_cache_keeps_the_new_cpu_side_short():
     print("%d references of %d walks in %.1f s" % (steps, hl.NEW_WALKS, time.time() - started))
     assert steps == sum(1 for w in hl.schedule(hl.SEED, False, True) for o in w if o.kind in hl.DATA_KINDS) and steps > 800
     assert {o.kind for w in hl.schedule(hl.SEED, False, True) for o in w} == set(hl.ALL_KINDS)
+
+
+def test_caller_stream_walks_cover_every_kind():
+    """the ten walks tests/test_gpu_caller_stream.py runs on every kind of caller's stream: four of the first schedule,
+    four of the second, its two hand-made ones - every kind of call occurs among them, and each walk is legal from a
+    fresh context"""
+    walks = hl.caller_stream_walks()
+    names = [name for name, _ in walks]
+    assert len(walks) == 10 and len(set(names)) == 10 and names[-2:] == ["named", "sizes"]
+    assert sum(n.startswith("walk") for n in names) == 4 and sum(n.startswith("new_walk") for n in names) == 4
+    first, second = hl.schedule(hl.SEED), hl.schedule(hl.SEED, False, True)
+    for name, ops in walks:
+        assert any(ops == w for w in (first[:-1] if name.startswith("walk") else second)), name
+        m = hl.Model()
+        for o in ops:
+            assert m.legal(o.kind), (name, o)
+            m.apply(o)
+    seen = {o.kind for _, ops in walks for o in ops}
+    assert seen == set(hl.ALL_KINDS), sorted(set(hl.ALL_KINDS) - seen)
