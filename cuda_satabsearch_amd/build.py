@@ -53,6 +53,10 @@ HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "
 DEVICE_LIB = (os.path.join(PKG, "libsatabsearch.so"), os.path.join(PKG, "obj", "lib"), [])
 SELFCHECK_LIB = (os.path.join(ROOT, "tests", "native", "libsat_selfcheck.so"), os.path.join(PKG, "obj", "selfcheck"),
                  ["-DSAT_DIAG", "-DSAT_DIAG_SELFCHECK"])
+# ... and once more with the initial full score's flat pair walk compiled out (-DSAT_FS_FLAT=0: the team walk it replaced):
+# tests/test_gpu_flat_walk.py asks both builds for the same bytes, and A/B runs load it through SAT_DEVICE_LIB
+TEAMWALK_LIB = (os.path.join(ROOT, "tests", "native", "libsat_teamwalk.so"), os.path.join(PKG, "obj", "teamwalk"),
+                ["-DSAT_FS_FLAT=0"])
 JOBS = 16       # compile commands running at once, all libraries together
 
 
@@ -198,8 +202,8 @@ def build_oracle(ref=False):
 def build_all(force=False, oracle=False, ref=False):
     build_host(force)
     if oracle:
-        # the device library and its diagnostic twin: their translation units compile side by side
-        build_device_libs([DEVICE_LIB, SELFCHECK_LIB], force)
+        # the device library and its twins: their translation units compile side by side
+        build_device_libs([DEVICE_LIB, SELFCHECK_LIB, TEAMWALK_LIB], force)
         build_test_native(force, twin=False)
         build_cli(force)
         build_oracle(ref)

@@ -456,7 +456,91 @@
             constexpr bool FS_TEAMS = SAT_FS_TEAMS && M1W == 1 && M2W == 1 && FAST && (OPT == 0 || OPT == 1);
             bool teamed = false;
             if constexpr (FS_TEAMS) teamed = __builtin_amdgcn_ballot_w64(true) == ~0ull;
-            if (FS_TEAMS && teamed) {
+            // The wave's matched pairs in ONE order, dealt evenly (sat_sa_kernel.hpp: fs_seek, fs_advance; DESIGN §4 (32)).  The team walk
+            // still pays every row trip for its busiest team and every inner trip for the wave's longest row: counted
+            // on the bench inputs (scripts/exp/fs_walk_model.py) 12 row trips and 47 inner trips of two pairs per
+            // wave where the pairs, dealt evenly, are 18 trips.  Here the chains that own a pair are compacted to the
+            // first lanes (one ds_permute per set), a wave scan of their pair counts gives every chain its first
+            // pair's number, lane t takes the pairs [t q, (t + 1) q) with q = ceil(P / 64): it finds the chain that
+            // holds pair t q by a search over the scan (6 ds_bpermute), the row and partner inside it by stripping
+            // bits (fs_seek), and then walks ONE flat loop of q pairs for the whole wave - next partner, next row,
+            // next chain (its sets from the lane that holds them) all by selects (fs_advance).  A pair's term goes
+            // to its chain's sum with an LDS atomic: the wave's item table, idle until the first SA step, one dword
+            // per compacted chain; the chain's own lane reads it back.  Only launches with the work compaction HAVE that
+            // table (satk::lds_layout): LORDER = F (OPT 0) keeps the team walk.
+            constexpr bool FS_FLAT = SAT_FS_FLAT && FS_TEAMS && OPT == 1;
+            if (FS_FLAT && teamed) {
+                const uint32_t mp = mapped.w[0], oc = occ.w[0];
+                const bool owns = (mp & (mp - 1u)) != 0u;                              // two matched SSEs or more
+                const unsigned long long nzb = __builtin_amdgcn_ballot_w64(owns);
+                const int NZ = __popcll(nzb);                                           // wave-uniform
+                const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(nzb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)nzb, 0));
+                // a permutation of the lanes: owners to 0 .. NZ - 1 in lane order, the rest behind them
+                const int dest = (owns ? rank : NZ + wlane - rank) << 2;
+                uint32_t cm = (uint32_t)__builtin_amdgcn_ds_permute(dest, (int)mp), co = (uint32_t)__builtin_amdgcn_ds_permute(dest, (int)oc);
+                cm = wlane < NZ ? cm : SAT_FS_DUMMY_SET;
+                co = wlane < NZ ? co : SAT_FS_DUMMY_SET;
+                const int p = wlane < NZ ? fs_pairs(cm) : 0;
+                // inclusive wave scan: inside the rows of 16 lanes by row_shr 1, 2, 4, 8 (a lane without a source adds
+                // the 0 given as the old value), then lane 15 of rows 0 and 2 to rows 1 and 3 (row_bcast:15, row mask
+                // 0xA), then lane 31 to rows 2 and 3 (row_bcast:31, row mask 0xC)
+                int incl = p;
+                incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xF, 0xF, false);
+                incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xF, 0xF, false);
+                incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xF, 0xF, false);
+                incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xF, 0xF, false);
+                incl += __builtin_amdgcn_update_dpp(0, incl, 0x142, 0xA, 0xF, false);
+                incl += __builtin_amdgcn_update_dpp(0, incl, 0x143, 0xC, 0xF, false);
+                const int P = __builtin_amdgcn_readlane(incl, 63);
+                const int q = fs_chunk(P);
+                const int first = __mul24(wlane, q), mine = fs_chunk_pairs(P, q, wlane);
+                // the last compacted chain whose first pair is at or below this lane's (only owners come before P)
+                int r = 0;
+#pragma unroll
+                for (int d = 32; d > 0; d >>= 1) {
+                    const int s = __builtin_amdgcn_ds_bpermute((r + d) << 2, incl - p);
+                    r = s <= first ? r + d : r;
+                }
+                const int s0 = __builtin_amdgcn_ds_bpermute(r << 2, incl - p);
+                FsCursor cur = fs_seek((uint32_t)__builtin_amdgcn_ds_bpermute(r << 2, (int)cm),
+                                       (uint32_t)__builtin_amdgcn_ds_bpermute(r << 2, (int)co), mine > 0 ? first - s0 : 0);
+                items[wlane] = 0u;
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                for (int it = 0; it < q; it += SAT_FS_UNROLL) {
+                    int ll[SAT_FS_UNROLL], rr[SAT_FS_UNROLL];
+                    bool vv[SAT_FS_UNROLL];
+                    DbRow<CELLS> drow[SAT_FS_UNROLL];
+                    u32x2_t qcell[SAT_FS_UNROLL];
+#pragma unroll
+                    for (int u = 0; u < SAT_FS_UNROLL; u++) {
+                        vv[u] = it + u < mine;
+                        const int i = __builtin_ctz(cur.rm), k = __builtin_ctz(cur.rk);
+                        drow[u] = db_row(__builtin_ctz(cur.ro));
+                        ll[u] = __builtin_ctz(cur.rl);
+                        rr[u] = r;
+                        qcell[u] = *(gptr_u2)(qpairG + ((uint32_t)__mul24(i, N1P * 8) + ((uint32_t)k << 3)));
+                        // (a lane that leaves the last chain fetches from lane 0 and stands there, its chunk done)
+                        const uint32_t nm = (uint32_t)__builtin_amdgcn_ds_bpermute((r + 1) << 2, (int)cm);
+                        const uint32_t no = (uint32_t)__builtin_amdgcn_ds_bpermute((r + 1) << 2, (int)co);
+                        r += fs_advance(cur, vv[u] ? 1u : 0u, nm, no) ? 1 : 0;
+                    }
+#pragma unroll
+                    for (int u = 0; u < SAT_FS_UNROLL; u++) {
+                        const uint2 c = db_cell<CELLS>(drow[u], ll[u]);
+                        int term = pair_term(qcell[u].x, qcell[u].y, c.x, c.y);
+                        // (opaque: left to itself the compiler sinks a pair's cell reads and its term under the lane
+                        // mask of its atomic, one pair's loads waiting behind the other's)
+                        asm volatile("" : "+v"(term));
+                        if (vv[u]) __hip_atomic_fetch_add((lds_i32_t *)(items + rr[u]), term, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                    }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                score = owns ? (int)items[rank] : 0;
+            } else if (FS_TEAMS && teamed) {
                 const int pl = wlane & 1;
                 const uint32_t om = (uint32_t)__shfl_xor((int)mapped.w[0], 1, 64), oo = (uint32_t)__shfl_xor((int)occ.w[0], 1, 64);
                 const uint32_t m0 = pl ? om : mapped.w[0], o0 = pl ? oo : occ.w[0];       // chain 0: the even lane's

@@ -101,9 +101,99 @@
 // host's expf, bit for bit.
 #pragma once
 
+#ifndef SAT_FS_CHUNKS_ONLY
 #include <hip/hip_runtime.h>
 #include <type_traits>
+#endif
 #include <stdint.h>
+
+// ---------------------------------------------------------------- chunk arithmetic of the flat pair walk
+// (initial full score, sat_sa_body.inc: FS_FLAT).  Plain C++ without a device intrinsic, so that a host program runs
+// the very functions the kernel runs: tests/native/fs_chunks_check.cpp defines SAT_FS_CHUNKS_ONLY and gets this
+// section alone.
+//
+// A wave holds 64 chains; chain c has the matched query SSEs `mapped` and their images `occ` (thinit's maps are order
+// preserving: the a-th set bit of one belongs to the a-th of the other) and owns the pairs (a, b), a < b, of its
+// matched SSEs: p = m (m - 1) / 2 of them, ordered by a, then b.  The chains that own a pair are numbered 0 .. NZ - 1
+// in lane order ("compacted": lane r holds the sets of the r-th of them), the wave's P pairs are ordered by chain,
+// then inside the chain, and lane t takes the pairs [t q, min((t + 1) q, P)) with q = ceil(P / 64).
+#if defined(__HIPCC__)
+#define SAT_FS_HD __host__ __device__ __forceinline__
+#else
+#define SAT_FS_HD inline
+#endif
+
+namespace satk {
+
+// the sets a compacted lane at or past NZ holds: a chain of one pair, never counted, so that a lane that has
+// finished its chunk (or has none) always stands on a pair it can address
+#define SAT_FS_DUMMY_SET 3u
+
+SAT_FS_HD int fs_pairs(uint32_t mapped)
+{
+    const int m = __builtin_popcount(mapped);
+    return (m * (m - 1)) >> 1;
+}
+SAT_FS_HD int fs_chunk(int P) { return (P + 63) >> 6; }
+// pairs of lane t's chunk
+SAT_FS_HD int fs_chunk_pairs(int P, int q, int t)
+{
+    const int left = P - t * q;
+    return left < 0 ? 0 : (left < q ? left : q);
+}
+
+// Where a lane stands: rm / ro = the chain's two sets from the current row on (lowest bits: the row's SSE i and its
+// image), rk / rl = the row's partners not yet visited (lowest bits: the pair's SSE k and its image).  rk is never
+// empty between two calls.
+struct FsCursor { uint32_t rm, ro, rk, rl; };
+
+// the cursor on pair `off` (0 <= off < fs_pairs(mapped)) of a chain: rows are stripped while the pair lies behind
+// them, then partners
+SAT_FS_HD FsCursor fs_seek(uint32_t mapped, uint32_t occ, int off)
+{
+    FsCursor c;
+    c.rm = mapped;
+    c.ro = occ;
+    int len = __builtin_popcount(mapped) - 1;          // partners of row 0
+    while (off >= len && len > 1) {
+        off -= len;
+        len--;
+        c.rm &= c.rm - 1u;
+        c.ro &= c.ro - 1u;
+    }
+    c.rk = c.rm & (c.rm - 1u);
+    c.rl = c.ro & (c.ro - 1u);
+    while (off > 0 && (c.rk & (c.rk - 1u)) != 0u) {
+        off--;
+        c.rk &= c.rk - 1u;
+        c.rl &= c.rl - 1u;
+    }
+    return c;
+}
+
+// Leaves the pair the cursor is on (go = 1; go = 0 leaves the cursor alone): the next partner, behind the row's last
+// one the next row, behind the chain's last row the first pair of the chain with the sets (nm, no).  All by selects.
+// Returns whether the chain was left.
+SAT_FS_HD bool fs_advance(FsCursor &c, uint32_t go, uint32_t nm, uint32_t no)
+{
+    c.rk &= c.rk - go;
+    c.rl &= c.rl - go;
+    const bool row_end = c.rk == 0u;
+    const uint32_t e = row_end ? 1u : 0u;
+    uint32_t rm = c.rm & (c.rm - e), ro = c.ro & (c.ro - e);
+    const bool chain_end = row_end && (rm & (rm - 1u)) == 0u;
+    rm = chain_end ? nm : rm;
+    ro = chain_end ? no : ro;
+    c.rm = rm;
+    c.ro = ro;
+    c.rk = row_end ? rm & (rm - 1u) : c.rk;
+    c.rl = row_end ? ro & (ro - 1u) : c.rl;
+    return chain_end;
+}
+
+}   // namespace satk
+
+#ifndef SAT_FS_CHUNKS_ONLY
 
 // Hook points of the diagnostic builds (phase timers, perturbations, duplicated LDS accesses, the per-move
 // self-check): their code lives in diag/sat_diag.hpp, which the shipped library does not include - every hook is
@@ -154,6 +244,11 @@
 // the initial full score of two chains walked by a pair of lanes together (one-word sets, one lane per chain)
 #ifndef SAT_FS_TEAMS
 #define SAT_FS_TEAMS 1
+#endif
+// ... or, where that applies, the wave's matched pairs in ONE order dealt to the 64 lanes in equal chunks (0: the team
+// walk, for A/B builds)
+#ifndef SAT_FS_FLAT
+#define SAT_FS_FLAT 1
 #endif
 // the LORDER step's candidate of one-word db sets read from the rank table `pos` (0: the strip loop, for A/B builds)
 #ifndef SAT_PICK_TABLE
@@ -750,3 +845,5 @@ sat_sa_pair_match_kernel(const SatKernelArgs a, const SatPairArgs px, const SatM
     constexpr int OPT = -1, WPL = 0;
 #include "sat_sa_body.inc"
 }
+
+#endif   // SAT_FS_CHUNKS_ONLY

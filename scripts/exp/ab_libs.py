@@ -2,9 +2,11 @@
     python scripts/exp/ab_libs.py WORKLOAD ROUNDS lib1.so lib2.so ...
 WORKLOAD: bench (32-SSE query x 125 000 32-SSE entries), lorderf (same, LORDER = F, 40 000 entries), q101 (101-SSE
 query x 30 000 entries of 8..96 SSEs), n96 (32-SSE query x 20 000 96-SSE entries), n64, mixed (8..32 sorted), c4 (BASELINE
-configs[4]: 101-SSE query x C5 orders, LSOLN).  The parent builds the inputs once (npz in /tmp); every (round, library)
+configs[4]: 101-SSE query x C5 orders, LSOLN), allhit (20 000 copies of the query's source structure: dense initial maps),
+q200 (the query list: 200 members of a 15 000-entry database of 4..40 SSEs as one batch), realNN, qnNN.  The parent builds the inputs once (npz in /tmp); every (round, library)
 is a fresh process (the library is chosen at import, SAT_DEVICE_LIB) that times 5 searches with HIP events; the rounds
-interleave the libraries so that clock drift hits all alike.  Prints one line per run and the per-library medians."""
+interleave the libraries so that clock drift hits all alike.  Prints one line per run and per library the median, min, max and max - min.  A child
+that fails or runs past its time limit ends the whole run: nothing more is started on a GPU that may have faulted."""
 import os, subprocess, sys, json, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -18,7 +20,12 @@ z = np.load(sys.argv[1], allow_pickle=False)
 db = sat.StructSet(z["orders"], ["e%%d" %% i for i in range(len(z["orders"]))], z["cell_off"], z["tab"], z["dist"])
 lorder, lsoln, r = bool(int(sys.argv[2])), bool(int(sys.argv[3])), int(sys.argv[4])
 with sat.Searcher(0) as s:
-    s.upload(db); s.set_query(z["qt"], z["qd"], z["qtypes"], 0)
+    s.upload(db)
+    if int(sys.argv[5]):          # the query list: that many database members, one batch
+        pick = np.random.default_rng(5).choice(len(db), int(sys.argv[5]), replace=False)
+        s.set_queries([(*db.dense(int(k)), db.ssetypes(int(k))) for k in pick], 0)
+    else:
+        s.set_query(z["qt"], z["qd"], z["qtypes"], 0)
     s.search_timed(lorder, lsoln, r, 1)
     tot, _ = s.search_timed(lorder, lsoln, r, 5)
     sc, _, _ = s.search(lorder, lsoln, r)
@@ -31,7 +38,14 @@ def workload(name):
     import cuda_satabsearch_amd as sat
     from cuda_satabsearch_amd import workloads
     lorder, lsoln, r = True, False, 128
-    if name == "bench":
+    if name == "allhit":          # scripts/exp/dense_hits.py's all-hit leg
+        base = sat.synth.make_db(1, 32, 32, seed=5)
+        t, d = base.dense(0)
+        db = sat.StructSet.from_dense([32] * 20_000, [t] * 20_000, [d] * 20_000)
+        q = sat.synth.planted_query(base, 0, keep=1.0, jitter=0.5)
+    elif name == "q200":          # scripts/run_config.py q200; the child draws the 200 members
+        db, q = sat.synth.make_db(15_000, 4, 40, sort=True), sat.synth.make_query(32)
+    elif name == "bench":
         db, q = sat.synth.make_db(125_000, 32, 32), sat.synth.make_query(32)
     elif name == "lorderf":
         db, q, lorder = sat.synth.make_db(40_000, 32, 32), sat.synth.make_query(32), False
@@ -88,10 +102,13 @@ def main():
             libpath, _, extra = l.partition("#")
             env = dict(os.environ, SAT_DEVICE_LIB=os.path.join(ROOT, libpath))
             env.update(dict(kv.split("=", 1) for kv in extra.split(",") if kv))
-            p = subprocess.run([sys.executable, child, path, str(int(lorder)), str(int(lsoln)), str(r)], capture_output=True, text=True, env=env)
+            try:
+                p = subprocess.run([sys.executable, child, path, str(int(lorder)), str(int(lsoln)), str(r), "200" if name == "q200" else "0"],
+                                   capture_output=True, text=True, env=env, timeout=240)
+            except subprocess.TimeoutExpired:
+                raise SystemExit(f"{name} round {k} {l}: no result after 240 s - stopping")
             if p.returncode != 0:
-                print(l, "FAILED", p.stderr[-500:], flush=True)
-                continue
+                raise SystemExit(f"{name} round {k} {l}: FAILED ({p.returncode}) - stopping\n{p.stderr[-1500:]}")
             o = json.loads(p.stdout.strip().splitlines()[-1])
             res[l].append(o["ms"])
             sums.setdefault(o["checksum"], []).append(l)
@@ -100,7 +117,7 @@ def main():
     for l in libs:
         if res[l]:
             m = float(np.median(res[l]))
-            print(f"MEDIAN {name} {l}: {m:.3f} ms = {len(db) / m * 1e3 / 1e6:.3f} M scorings/s")
+            print(f"SUMMARY {name} {l}: median {m:.4f} ms min {min(res[l]):.4f} max {max(res[l]):.4f} spread {max(res[l]) - min(res[l]):.4f}")
 
 
 if __name__ == "__main__":

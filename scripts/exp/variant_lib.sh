@@ -12,5 +12,5 @@ srcs=$(cd $repo && python -c "from cuda_satabsearch_amd import build; print(' '.
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -fPIC -shared "$@" \
   -I $repo/include -I $repo/cuda_satabsearch_amd/csrc -o $repo/cuda_satabsearch_amd/libsat_$name.so $srcs \
   -Wl,$repo/cuda_satabsearch_amd/sat_gumbel.o -Wl,$repo/cuda_satabsearch_amd/sat_shard.o -Wl,$repo/cuda_satabsearch_amd/sat_cluster.o \
-  -Wl,$repo/cuda_satabsearch_amd/sat_eval.o -Wl,$repo/cuda_satabsearch_amd/sat_cover.o -lm -ldl
+  -Wl,$repo/cuda_satabsearch_amd/sat_eval.o -Wl,$repo/cuda_satabsearch_amd/sat_cover.o -Wl,$repo/cuda_satabsearch_amd/sat_reach.o -lm -ldl
 echo "built cuda_satabsearch_amd/libsat_$name.so"
